@@ -2,7 +2,7 @@
 """bench.py -- the hot path (batched DFA walk) on N GPUs of one node.
 
     python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c5] [--n INPUTS_PER_GPU] [--subs auto|none]
-                    [--scaling weak|strong] [--full-parity]
+                    [--scaling weak|strong] [--full-parity] [--dump-outputs DIR]
 
 A "step" is one pass of the walk kernel over one batch of synthetic inputs that is already resident in
 HBM (generated on the device, so nothing crosses PCIe), followed -- for N > 1 -- by the RCCL all-gather of
@@ -74,7 +74,15 @@ def parse():
     ap.add_argument("--no-full-parity", action="store_true",
                     help="skip the full-N check: after timing, ALL inputs of the main workload are streamed back and every end state is "
                          "compared with the threaded CPU table walker (about 25 s at 1e8 x 1 KiB)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the main workload's last step returned (end states and accept bits of a fixed "
+                         "seeded sample of the inputs) as DIR/<name>.npy, for comparing two builds output for output")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (it is the number of timed steps)")
+    if a.dump_outputs and "_" in a.workload:
+        ap.error("--dump-outputs covers the whole-row workloads; the packed-lines workloads (%s) are not dumped" % a.workload)
+    return a
 
 
 def c3_affixes(which="c3"):
@@ -235,6 +243,26 @@ def sample_indices(n, sample):
         idx.append(np.arange((1 << 22) - 32, (1 << 22) + 32))
     idx = np.unique(np.concatenate(idx))
     return idx[idx < n]
+
+
+DUMP_ROWS = 1 << 20    # --dump-outputs: up to this many inputs in full, a sample_indices() sample of larger runs (about 20 MB written)
+
+
+def dump_outputs(d, end, bm, n):
+    """--dump-outputs DIR: what the caller of exec_batch_device received from the last timed step -- the u32 end state of
+    every input and the accept bitmap -- for all n inputs when n <= DUMP_ROWS, else for sample_indices(n, DUMP_ROWS), which
+    is the same set of rows on every run with the same arguments (as are the inputs: seeded generators):
+      DIR/index.npy      float64  the input indices written
+      DIR/end_state.npy  float64  their end states (NO_MATCH = 4294967295; float64 holds every u32 exactly)
+      DIR/accept.npy     float32  their accept bits read back from the bitmap, 1.0 / 0.0"""
+    import torch
+    idx = np.arange(n, dtype=np.int64) if n <= DUMP_ROWS else sample_indices(n, DUMP_ROWS)
+    t = torch.from_numpy(idx).to(end.device)
+    es = end[t].cpu().numpy().view(np.uint32)
+    acc = ((bm[t >> 6] >> (t & 63)) & 1).cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    for name, v in (("index", idx.astype(np.float64)), ("end_state", es.astype(np.float64)), ("accept", acc.astype(np.float32))):
+        np.save(os.path.join(d, name + ".npy"), v)
 
 
 def kernels_sha16():
@@ -716,8 +744,9 @@ def main():
     buf_all = torch.empty((n, L), dtype=torch.uint8, device="cuda")
     end_all = torch.empty(n, dtype=torch.int32, device="cuda")
 
-    def run(wl, variant=None, n_wl=None, first_wl=0, with_cpu=True):
-        """Generate the workload's inputs in the resident buffer, time a.steps walks, return the result dict."""
+    def run(wl, variant=None, n_wl=None, first_wl=0, with_cpu=True, dump_dir=None):
+        """Generate the workload's inputs in the resident buffer, time a.steps walks, return the result dict (dump_dir: write the
+        last step's outputs there, see dump_outputs)."""
         n_ = n if n_wl is None else min(n_wl, n)
         buf, end = buf_all[:n_], end_all[:n_]
         words = None
@@ -796,6 +825,8 @@ def main():
         if dist_on:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
         elapsed = float(el.item())
+        if dump_dir and rank == 0:     # before anything else reuses the buffers; at N > 1, rank 0's shard
+            dump_outputs(dump_dir, end, bms[(tick[0] - 1) % len(bms)], n_)
 
         acc_t = (end != -1).sum().to(torch.int64).reshape(1)
         rank_kms = None
@@ -1291,7 +1322,7 @@ def main():
         emit(r)
         return
     progress("main workload %s" % a.workload)
-    main_res = run(a.workload)
+    main_res = run(a.workload, dump_dir=a.dump_outputs)
     subs = []
     if not dist_on and a.subs == "auto" and a.n == 0 and not shrunk:
         plan = []

@@ -6,15 +6,15 @@
 # src/rx/main.c and src/re/main.c.  The printer itself is print_hip_ir.c (ours): an ir_print_f that expands libfsm's
 # codegen IR (print/ir.h) to rows the way the VM compiler's dfa_table does (vm/ir.c:649-750) and writes the FSMHIP form.
 # irflat_check (test infrastructure) compares that expansion with the shim's fsm_walk_edges flattening, file by file.  As in
-# integration/retest: the four files are copied from $FSM_REF into the git-ignored integration/_build/, patched,
+# integration/retest: the four files are copied from $FSM_REF into the git-ignored oracle/_ref/integration/, patched,
 # compiled against the reference archive (minus its own print.o) and libfsm_hip.so, and the copies are deleted;
 # nothing of the reference is stored here.
-#   integration/_build/print/rx    integration/_build/print/re    integration/_build/print/irflat_check
+#   oracle/_ref/integration/print/rx    oracle/_ref/integration/print/re    oracle/_ref/integration/print/irflat_check
 set -e
 R=${FSM_REF:-/root/reference}
 HERE=$(cd "$(dirname "$0")" && pwd)
 ROOT=$(cd "$HERE/../.." && pwd)
-OUT=$ROOT/integration/_build
+OUT=$ROOT/oracle/_ref/integration
 if [ ! -d "$R/src/rx" ]; then
 	echo "integration/print/build.sh: reference tree not found at $R; keeping prebuilt $OUT/print/" >&2
 	exit 0
@@ -36,7 +36,7 @@ gcc -std=c99 -O2 -DNDEBUG -D_POSIX_C_SOURCE=200809L $INC -c "$W/src/libfsm/print
 gcc -std=c99 -O2 -Wall -Wextra -D_POSIX_C_SOURCE=200809L $INC -c "$HERE/print_hip_ir.c" -o "$W/print_hip_ir.o"
 cp "$ROOT/oracle/_ref/libfsmre.a" "$W/libfsmre.a"
 ar d "$W/libfsmre.a" libfsm_print.o
-LINK="$W/print_hip.o $W/print_hip_ir.o -Wl,--whole-archive $W/libfsmre.a -Wl,--no-whole-archive -rdynamic -L$ROOT/libfsm_amd -lfsm_hip -Wl,-rpath,\$ORIGIN/../../../libfsm_amd -Wl,-rpath-link,/opt/rocm/lib -ldl"
+LINK="$W/print_hip.o $W/print_hip_ir.o -Wl,--whole-archive $W/libfsmre.a -Wl,--no-whole-archive -rdynamic -L$ROOT/libfsm_amd -lfsm_hip -Wl,-rpath,\$ORIGIN/../../../../libfsm_amd -Wl,-rpath-link,/opt/rocm/lib -ldl"
 gcc -std=c99 -O2 -DNDEBUG -D_XOPEN_SOURCE=700 $INC "$W/src/rx/main.c" $LINK -o "$OUT/print/rx"
 gcc -std=c99 -O2 -DNDEBUG -D_XOPEN_SOURCE=700 $INC "$W/src/re/main.c" $LINK -o "$OUT/print/re"
 gcc -std=c99 -O2 -Wall -Wextra -D_POSIX_C_SOURCE=200809L $INC "$HERE/irflat_check.c" $LINK -o "$OUT/print/irflat_check"

@@ -3,14 +3,14 @@
 # hip_exec.patch is the whole change to src/re/main.c: -H compiles the DFA's table for the GPU (fsm_hip_compile) and
 # matches ALL string arguments in one launch (fsm_hip_exec_batch_offsets; end states are the ids fsm_exec returns, so
 # -z keeps working), files (-x) through fsm_hip_match_file.  As in integration/retest: main.c is copied from $FSM_REF
-# into the git-ignored integration/_build/, patched, compiled against the reference archive and libfsm_hip.so, and the
+# into the git-ignored oracle/_ref/integration/, patched, compiled against the reference archive and libfsm_hip.so, and the
 # copy is deleted; nothing of the reference is stored here.
-#   integration/_build/re               `re -H -r pcre '^ab+c$' abc abbc xyz`
+#   oracle/_ref/integration/re               `re -H -r pcre '^ab+c$' abc abbc xyz`
 set -e
 R=${FSM_REF:-/root/reference}
 HERE=$(cd "$(dirname "$0")" && pwd)
 ROOT=$(cd "$HERE/../.." && pwd)
-OUT=$ROOT/integration/_build
+OUT=$ROOT/oracle/_ref/integration
 if [ ! -d "$R/src/re" ]; then
 	echo "integration/re/build.sh: reference tree not found at $R; keeping prebuilt $OUT/re" >&2
 	exit 0
@@ -26,7 +26,7 @@ gcc -std=c99 -O2 -DNDEBUG -D_XOPEN_SOURCE=700 \
 	-I"$R/include" -I"$R/src" -I"$R/src/libfsm" -I"$R/src/libre" -I"$ROOT/include" \
 	"$OUT/src/re/main.c" \
 	-Wl,--whole-archive "$ROOT/oracle/_ref/libfsmre.a" -Wl,--no-whole-archive \
-	-rdynamic -L"$ROOT/libfsm_amd" -lfsm_hip -Wl,-rpath,'$ORIGIN/../../libfsm_amd' -Wl,-rpath-link,/opt/rocm/lib -ldl \
+	-rdynamic -L"$ROOT/libfsm_amd" -lfsm_hip -Wl,-rpath,'$ORIGIN/../../../libfsm_amd' -Wl,-rpath-link,/opt/rocm/lib -ldl \
 	-o "$OUT/re"
 rm -rf "$OUT/src"
 echo "built $OUT/re"

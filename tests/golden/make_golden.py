@@ -511,6 +511,24 @@ def gen_fsm_corpus():
     print(f"fsm corpus: {k} automata, {ncase} inputs, {skipped} skipped")
 
 
+def gen_fsm_text():
+    """The reference's regex-dialect golden automata (tests/{pcre,pcre-anchor,pcre-flags,pcre-repeat,native,glob,like,
+    literal,sql}/out*.fsm) as the .fsm text itself, for tests/test_print_patch.py's IR-flattening check.  One file:
+    names (newline-separated) and the texts back to back, split at off."""
+    import glob as _glob
+    names, texts = [], []
+    for d in ("pcre", "pcre-anchor", "pcre-flags", "pcre-repeat", "native", "glob", "like", "literal", "sql"):
+        for path in sorted(_glob.glob(os.path.join(REF, "tests", d, "out*.fsm"))):
+            names.append(os.path.relpath(path, REF))
+            texts.append(open(path, "rb").read())
+    off = np.zeros(len(texts) + 1, np.int64)
+    off[1:] = np.cumsum([len(t) for t in texts])
+    os.makedirs(os.path.join(OUT, "fsm_text"), exist_ok=True)
+    np.savez_compressed(os.path.join(OUT, "fsm_text", "dialects.npz"), names=np.frombuffer("\n".join(names).encode(), np.uint8),
+                        text=np.frombuffer(b"".join(texts), np.uint8), off=off)
+    print(f"fsm text: {len(names)} files, {int(off[-1])} bytes")
+
+
 def gen_recorded():
     """Compile the reference's own C test programs (tests/endids, tests/re_strings, tests/capture)
     where they lie, with fsm_exec routed through record_exec.c, run them, and freeze every
@@ -666,6 +684,7 @@ if __name__ == "__main__":
     gen_c3u()
     gen_eager()
     gen_fsm_corpus()
+    gen_fsm_text()
     gen_recorded()
     gen_aho_corasick()
     gen_reperf()

@@ -887,6 +887,40 @@ def test_bench_two_ranks_share_one_gpu(hip):
     assert abs(r["config"]["accepted_inputs"] - 262144 // 8) < 64
 
 
+def test_bench_dump_outputs(hip, tmp_path):
+    """bench.py --dump-outputs DIR: the main workload's end states and accept bits as .npy files, equal to the oracle's walk
+    of the same seeded inputs, and the same files from a second run with another --steps."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    from oracle.pyoracle import Oracle
+    n, L = 65536 + 37, 256
+    got = []
+    for steps in (3, 1):
+        d = tmp_path / ("out%d" % steps)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--workload", "c3",
+               "--inputs", str(n), "--len", str(L), "--no-cpu-baseline", "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root,
+                             env=dict(os.environ, FSM_BENCH_DETAIL=str(tmp_path / "detail.json")))
+        assert out.returncode == 0, out.stderr[-2000:]
+        r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert r["steps"] == steps and r["config"]["inputs_per_gpu"] == n
+        arrs = {k: np.load(d / (k + ".npy")) for k in ("index", "end_state", "accept")}
+        assert arrs["index"].dtype == np.float64 and arrs["end_state"].dtype == np.float64 and arrs["accept"].dtype == np.float32
+        got.append(arrs)
+    a = got[0]
+    assert np.array_equal(a["index"], np.arange(n))
+    flat = hip.FlatDfa.load(os.path.join(root, "tests", "golden", "c3.npz"))
+    want = Oracle(flat).table_walk(bench.generate_host(hip, "c3", n, L, 0))
+    assert np.array_equal(a["end_state"], want.astype(np.float64))
+    assert np.array_equal(a["accept"], (want != NO).astype(np.float32)) and a["accept"].sum() > n // 4
+    for k in a:
+        assert np.array_equal(a[k], got[1][k]), k
+
+
 def test_retest_style_c_driver(hip, tmp_path):
     """examples/retest_hip.c: a plain-C retest(1) over .tst files -- libre compiles each regex, the HIP path
     runs each block's +/- lines in ONE batch.  The .tst files are regenerated here from the retest goldens

@@ -50,7 +50,7 @@ def _missing_integration(what):
 def _need_ref():
     from oracle import pyoracle
     if not pyoracle.have_ref():
-        pytest.skip("oracle/_ref not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref not built (needs the reference tree at build time)")
 
 
 EAGER_LAYOUTS = ("TINY", "COMBSELF", "COMB256", "LDSSELF", "LDS", "COMB", "SPARSE", "GLOBAL", "AUTO")
@@ -564,11 +564,11 @@ def test_retest_l_hip(hip, tmp_path):
     interpreter) prints the same [OK] lines; a flipped expectation is reported by all three.  The read-ahead's
     control flow is also covered without a GPU in tests/test_retest_patch.py."""
     from common import retest_tst_lines
-    exe = os.path.join(ROOT, "integration", "_build", "retest")
+    exe = os.path.join(ROOT, "oracle", "_ref", "integration", "retest")
     if not os.path.exists(exe):
         sh = subprocess.run(["sh", os.path.join(ROOT, "integration", "retest", "build.sh")], capture_output=True, text=True)
         if not os.path.exists(exe):
-            _missing_integration("integration/_build/retest not built (needs /root/reference at build time): " + sh.stderr[-300:])
+            _missing_integration("oracle/_ref/integration/retest not built (needs the reference tree at build time): " + sh.stderr[-300:])
     lines, flip = retest_tst_lines()
     tst = tmp_path / "all.tst"
     tst.write_bytes(("\n".join(lines) + "\n").encode("latin1"))
@@ -598,14 +598,14 @@ def test_retest_l_hip(hip, tmp_path):
 
 
 def test_reperf_l_hip(hip, tmp_path):
-    """The reference's reperf(1) with the same runner patch (integration/_build/reperf): reperf/boost.scr's five string
+    """The reference's reperf(1) with the same runner patch (oracle/_ref/integration/reperf): reperf/boost.scr's five string
     cases, re-emitted from the frozen goldens.  `-l hip` sends the N runs of a case as batches of N copies
     (fsm_runner_run_repeat -> fsm_hip_exec_batch: 10^6 runs = one launch), `-l hip-line` makes N calls as the loop at
     src/retest/reperf.c:772-784 does; both agree with `-l vm`, and an inverted expectation is reported by all."""
     from common import reperf_scr_lines
-    exe = os.path.join(ROOT, "integration", "_build", "reperf")
+    exe = os.path.join(ROOT, "oracle", "_ref", "integration", "reperf")
     if not os.path.exists(exe):
-        _missing_integration("integration/_build/reperf not built (needs /root/reference at build time)")
+        _missing_integration("oracle/_ref/integration/reperf not built (needs the reference tree at build time)")
     env = dict(os.environ, LD_LIBRARY_PATH="/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
 
     def go(impl, lines):
@@ -639,7 +639,7 @@ def test_reference_test_programs_on_the_hip_path(hip):
     from test_retest_patch import reference_test_programs
     progs = reference_test_programs()
     if len(progs) != 42:
-        _missing_integration("integration/_build/reftests not built (needs /root/reference at build time)")
+        _missing_integration("oracle/_ref/integration/reftests not built (needs the reference tree at build time)")
     env = dict(os.environ, LD_LIBRARY_PATH="/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
     total = eager = 0
     for exe in progs:
@@ -657,13 +657,13 @@ def test_reference_test_programs_on_the_hip_path(hip):
 
 
 def test_re_H(hip, tmp_path):
-    """The reference's re(1) with integration/re/hip_exec.patch (integration/_build/re): `re -H` matches all its text
+    """The reference's re(1) with integration/re/hip_exec.patch (oracle/_ref/integration/re): `re -H` matches all its text
     arguments in one launch and files (-x) through fsm_hip_match_file; exit status and -z output equal plain `re`'s
     for every case of tests/test_retest_patch.py::RE_CASES, plus a 3 MB file that needs the chunked walk."""
     from test_retest_patch import RE_CASES
-    exe = os.path.join(ROOT, "integration", "_build", "re")
+    exe = os.path.join(ROOT, "oracle", "_ref", "integration", "re")
     if not os.path.exists(exe):
-        _missing_integration("integration/_build/re not built (needs /root/reference at build time)")
+        _missing_integration("oracle/_ref/integration/re not built (needs the reference tree at build time)")
     env = dict(os.environ, LD_LIBRARY_PATH="/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
     for args, rc in RE_CASES:
         ref = subprocess.run([exe] + args, capture_output=True, text=True, env=env, timeout=120)
@@ -685,9 +685,9 @@ def test_fsm_H(hip, tmp_path):
     """The reference's fsm(1) with integration/fsm/hip_exec.patch: `fsm -H file.fsm text...` exits like plain `fsm`
     (tests/test_retest_patch.py::FSM_CASES), -x reads a file through fsm_hip_match_file, an NFA is refused (EINVAL)."""
     from test_retest_patch import FSM_CASES, FSM_DFA, FSM_NFA
-    exe = os.path.join(ROOT, "integration", "_build", "fsm")
+    exe = os.path.join(ROOT, "oracle", "_ref", "integration", "fsm")
     if not os.path.exists(exe):
-        _missing_integration("integration/_build/fsm not built (needs /root/reference at build time)")
+        _missing_integration("oracle/_ref/integration/fsm not built (needs the reference tree at build time)")
     env = dict(os.environ, LD_LIBRARY_PATH="/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
     dfa, nfa, txt = tmp_path / "d.fsm", tmp_path / "n.fsm", tmp_path / "t.txt"
     dfa.write_text(FSM_DFA)

@@ -462,11 +462,11 @@ def test_bench_one_rank_per_visible_gpu():
 def _integration_exe(*parts):
     """An integration binary: built where /root/reference exists, prebuilt files elsewhere.  Missing: skip -- or fail
     when FSM_REQUIRE_INTEGRATION is set (a GPU box that is expected to carry the prebuilt files)."""
-    exe = os.path.join(ROOT, "integration", "_build", *parts)
+    exe = os.path.join(ROOT, "oracle", "_ref", "integration", *parts)
     if not os.path.exists(exe):
         if os.environ.get("FSM_REQUIRE_INTEGRATION"):
             pytest.fail("%s missing and FSM_REQUIRE_INTEGRATION is set" % exe)
-        pytest.skip("%s not built (needs /root/reference at build time)" % exe)
+        pytest.skip("%s not built (needs the reference tree at build time)" % exe)
     return exe
 
 

@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RX = os.path.join(ROOT, "integration", "_build", "print", "rx")
-RE = os.path.join(ROOT, "integration", "_build", "print", "re")
+RX = os.path.join(ROOT, "oracle", "_ref", "integration", "print", "rx")
+RE = os.path.join(ROOT, "oracle", "_ref", "integration", "print", "re")
 
 
 @pytest.fixture(scope="module")
@@ -22,8 +22,8 @@ def printers(built):
         subprocess.run(["sh", os.path.join(ROOT, "integration", "print", "build.sh")], capture_output=True, text=True)
     if not (os.path.exists(RX) and os.path.exists(RE)):
         if os.environ.get("FSM_REQUIRE_INTEGRATION"):
-            pytest.fail("integration/_build/print/{rx,re} missing and FSM_REQUIRE_INTEGRATION is set")
-        pytest.skip("integration/_build/print not built (needs /root/reference at build time)")
+            pytest.fail("oracle/_ref/integration/print/{rx,re} missing and FSM_REQUIRE_INTEGRATION is set")
+        pytest.skip("oracle/_ref/integration/print not built (needs the reference tree at build time)")
     return RX, RE
 
 
@@ -80,15 +80,20 @@ def test_ir_flattening_equals_walk_edges_flattening(printers, tmp_path):
     ranges -- expanded the way the VM compiler's dfa_table does it, vm/ir.c:649-750) against the shim's flattening through
     fsm_walk_edges, on every DFA of the reference's regex-dialect corpus (tests/{pcre,...}/out*.fsm, determinised and
     minimised first where the fixture is an NFA) and on the 1 024-pattern union of configs[2]."""
-    import glob
+    from common import GOLDEN
     check = os.path.join(os.path.dirname(printers[0]), "irflat_check")
     if not os.path.exists(check):
-        pytest.skip("integration/_build/print/irflat_check not built")
-    ref = "/root/reference/tests"
-    files = sorted(f for d in ("pcre", "pcre-anchor", "pcre-flags", "pcre-repeat", "native", "glob", "like", "literal", "sql")
-                   for f in glob.glob(os.path.join(ref, d, "out*.fsm")))
-    if len(files) < 200:
-        pytest.skip("the reference's fixture corpus is not on this machine")
+        pytest.skip("oracle/_ref/integration/print/irflat_check not built")
+    # the corpus's .fsm texts, frozen in tests/golden/fsm_text/dialects.npz by tests/golden/make_golden.py
+    z = np.load(os.path.join(GOLDEN, "fsm_text", "dialects.npz"))
+    names, text, off = bytes(z["names"]).decode().split("\n"), bytes(z["text"]), z["off"]
+    files = []
+    for i, name in enumerate(names):
+        f = tmp_path / "corpus" / name
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_bytes(text[off[i]:off[i + 1]])
+        files.append(str(f))
+    assert len(files) >= 200
     out = subprocess.run([check, "-d"] + files, capture_output=True, text=True, timeout=600)
     tail = out.stdout.strip().splitlines()[-1]
     nok, nbad, nskip = (int(x) for x in __import__("re").findall(r"\d+", tail))

@@ -16,7 +16,7 @@ from common import reperf_scr_lines, retest_tst_lines
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-EXE = os.path.join(ROOT, "integration", "_build", "retest")
+EXE = os.path.join(ROOT, "oracle", "_ref", "integration", "retest")
 
 
 @pytest.fixture(scope="module")
@@ -28,7 +28,7 @@ def stub_dir(tmp_path_factory):
     subprocess.run(["sh", os.path.join(ROOT, "integration", "reftests", "build.sh")], capture_output=True, text=True)
     subprocess.run(["sh", os.path.join(ROOT, "integration", "fsm", "build.sh")], capture_output=True, text=True)
     if not os.path.exists(EXE):
-        pytest.skip("integration/_build/retest not built: " + sh.stderr[-300:])
+        pytest.skip("oracle/_ref/integration/retest not built: " + sh.stderr[-300:])
     d = tmp_path_factory.mktemp("stub")
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-shared", "-fPIC", os.path.join(ROOT, "tests", "c", "stub_fsm_hip.c"),
                            "-Wl,-soname,libfsm_hip.so", "-o", str(d / "libfsm_hip.so")])
@@ -131,9 +131,9 @@ def test_reperf_runs_go_out_as_batches_of_copies(stub_dir, tmp_path):
     """reperf(1) with the same patch: `-l hip` turns the N runs of a test (src/retest/reperf.c:772-784: N calls of
     fsm_runner_run on the same string) into fsm_runner_run_repeat() -- batches of copies through fsm_hip_exec_batch --
     `-l hip-line` keeps N calls; a wrong expectation (R 0 where the string matches) is reported."""
-    exe = os.path.join(ROOT, "integration", "_build", "reperf")
+    exe = os.path.join(ROOT, "oracle", "_ref", "integration", "reperf")
     if not os.path.exists(exe):
-        pytest.skip("integration/_build/reperf not built")
+        pytest.skip("oracle/_ref/integration/reperf not built")
     env = dict(os.environ, LD_LIBRARY_PATH=stub_dir)
 
     def go(impl, lines):
@@ -172,9 +172,9 @@ def test_re_H_matches_all_arguments_in_one_call(stub_dir, tmp_path):
     """re(1) with integration/re/hip_exec.patch: `re -H ... -- text...` answers like plain `re` (exit status, -z's
     pattern lines) from ONE fsm_hip_exec_batch_offsets call over all the arguments; -x files go through
     fsm_hip_match_file."""
-    exe = os.path.join(ROOT, "integration", "_build", "re")
+    exe = os.path.join(ROOT, "oracle", "_ref", "integration", "re")
     if not os.path.exists(exe):
-        pytest.skip("integration/_build/re not built")
+        pytest.skip("oracle/_ref/integration/re not built")
     env = dict(os.environ, LD_LIBRARY_PATH=stub_dir)
     for args, rc in RE_CASES:
         ref = subprocess.run([exe] + args, capture_output=True, text=True, env=env, timeout=60)
@@ -197,7 +197,7 @@ def test_re_H_matches_all_arguments_in_one_call(stub_dir, tmp_path):
 
 
 def reference_test_programs():
-    d = os.path.join(ROOT, "integration", "_build", "reftests")
+    d = os.path.join(ROOT, "oracle", "_ref", "integration", "reftests")
     return sorted(os.path.join(d, f) for f in os.listdir(d)) if os.path.isdir(d) else []
 
 
@@ -208,7 +208,7 @@ def test_reference_test_programs_route_fsm_exec(stub_dir):
     library's eager front: GPU suite.)"""
     progs = [p for p in reference_test_programs() if not os.path.basename(p).startswith("eager_")]   # the stand-in has no eager front
     if len(progs) != 20:
-        pytest.skip("integration/_build/reftests not built")
+        pytest.skip("oracle/_ref/integration/reftests not built")
     env = dict(os.environ, LD_LIBRARY_PATH=stub_dir)
     total = 0
     for exe in progs:
@@ -230,9 +230,9 @@ FSM_CASES = [(["abc", "abbcc"], 0), (["abc", "abd"], 1), (["", "a"], 1), ([], 0)
 def test_fsm_H_matches_all_arguments_in_one_call(stub_dir, tmp_path):
     """fsm(1) with integration/fsm/hip_exec.patch: `fsm -H file.fsm text...` answers like plain `fsm` from one
     fsm_hip_exec_batch_offsets call; an NFA is refused where fsm_exec refuses it."""
-    exe = os.path.join(ROOT, "integration", "_build", "fsm")
+    exe = os.path.join(ROOT, "oracle", "_ref", "integration", "fsm")
     if not os.path.exists(exe):
-        pytest.skip("integration/_build/fsm not built")
+        pytest.skip("oracle/_ref/integration/fsm not built")
     env = dict(os.environ, LD_LIBRARY_PATH=stub_dir)
     dfa, nfa = tmp_path / "d.fsm", tmp_path / "n.fsm"
     dfa.write_text(FSM_DFA)

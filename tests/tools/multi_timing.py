@@ -5,7 +5,7 @@
   A. library level (one process, warm HIP context), per pass over the 37 records, table build included:
        before: for each record  fsm_hip_dfa_create (upload)  + fsm_hip_exec_batch_offsets (one launch)  + free
        after : for each record  fsm_hip_dfa_create(FSM_HIP_DEFER_UPLOAD) ; ONE fsm_hip_exec_multi ; free
-  B. the patched retest binary (integration/_build/retest), wall time of the whole process (fork, HIP context, regex
+  B. the patched retest binary (oracle/_ref/integration/retest), wall time of the whole process (fork, HIP context, regex
      compile on the CPU included) for -l hip (file per submission), -l hip-record (record per launch), -l hip-line, -l vm.
 Prints one JSON object."""
 import json
@@ -78,7 +78,7 @@ def main():
     out["speedup_with_table_build"] = round(out["before_ms"]["median"] / out["after_ms"]["median"], 2)
     out["speedup_submit_only"] = round(statistics.median(tb) / statistics.median(ts), 2)
 
-    exe = os.path.join(ROOT, "integration", "_build", "retest")
+    exe = os.path.join(ROOT, "oracle", "_ref", "integration", "retest")
     if os.path.exists(exe):
         lines, _ = retest_tst_lines()
         tst = "/tmp/multi_timing_all.tst"

@@ -4,7 +4,7 @@
 # Pass 1: --kernel-trace --stats (per-kernel time).  Passes 2,3: PMC FETCH_SIZE / WRITE_SIZE, each on
 # its own (TCC slots: FETCH_SIZE 3 + WRITE_SIZE 2 do not fit one pass; never mixed with sys/hip traces).
 WL=$1; OUT=$2; shift 2
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 FSM_BENCH_DETAIL="$OUT/bench_detail_trace.json" rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace -- python "$ROOT/bench.py" --workload "$WL" --steps 5 --warmup 2 --no-cpu-baseline --subs none "$@" > "$OUT/bench_trace.json" 2> "$OUT/trace.err"
