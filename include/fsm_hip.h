@@ -290,8 +290,18 @@ int fsm_hip_match_buffer(const struct fsm_hip_dfa *dfa, const char *buf, size_t 
 int fsm_hip_match_file(const struct fsm_hip_dfa *dfa, FILE *f);
 /* the same engine over memory; *end_state (optional) receives the caller's end state id or FSM_HIP_NO_MATCH */
 int fsm_hip_match_buffer_big(const struct fsm_hip_dfa *dfa, const char *buf, size_t n, uint32_t *end_state);
-/* how the last such call of this process went: windows walked and passes over them (2 per window where every guess stood
- * after its first correction; 0 / 0: a small input, one plain call) */
+/* The same engine with eager outputs: ONE input walked by the whole device, returning what fsm_hip_match_buffer_big /
+ * fsm_hip_match_file return, and eager_out (W = fsm_hip_eager_words(dfa) words, required; the encoding of
+ * fsm_hip_exec_batch_eager) is overwritten with the set fsm_exec's callback would have received over the whole input
+ * (exec.c:126-151).  The pieces walk through fsm_hip_exec_batch_eager_resume_device, one set per piece kept on the device;
+ * guesses start from the start state by its caller's id (a guess must not fire the start state's outputs), and a window's
+ * sets are OR-ed into the result only at the fixed point, when every piece has walked from its true in-state (file.hip).
+ * A read error gives 0, as fsm_hip_match_file, and leaves eager_out zeroed.  NULL dfa / f / eager_out: -1, EINVAL. */
+int fsm_hip_match_buffer_big_eager(const struct fsm_hip_dfa *dfa, const char *buf, size_t n,
+	uint32_t *end_state, uint64_t *eager_out);
+int fsm_hip_match_file_eager(const struct fsm_hip_dfa *dfa, FILE *f, uint32_t *end_state, uint64_t *eager_out);
+/* how the last such call of this process went (the four above): windows walked and passes over them (2 per window where every
+ * guess stood after its first correction; 0 / 0: a small input, one plain call) */
 void fsm_hip_match_last_passes(unsigned *windows, unsigned *passes);
 
 /* Flatten a struct fsm * into a malloc'd description (free with
@@ -438,6 +448,27 @@ int fsm_hip_exec_batch_eager_offsets(const struct fsm_hip_dfa *dfa,
 int fsm_hip_exec_batch_eager_offsets_device(const struct fsm_hip_dfa *dfa,
 	const void *d_base, const uint64_t *d_off, size_t n,
 	uint32_t *d_end_out, uint64_t *d_eager_out, void *hip_stream);
+
+/* Eager outputs of inputs that arrive in pieces: the resumed walk (fsm_hip_exec_batch_resume) with eager-output sets, after
+ * fsm_exec (exec.c:126-151).  Per input i:
+ *   - from FSM_HIP_STATE_START, the start state's outputs fire before the first byte;
+ *   - from a caller's state id carried over from an earlier piece, that state's outputs do NOT fire again (they fired when
+ *     it was entered); from FSM_HIP_STATE_DEAD nothing fires;
+ *   - every byte that enters a state fires that state's outputs (a set: re-entering a state adds nothing);
+ *   - after a missing edge nothing fires, and the state becomes FSM_HIP_STATE_DEAD.
+ * eager_io holds n * W words (W = fsm_hip_eager_words(dfa), the encoding of fsm_hip_exec_batch_eager) and is OR-ed into,
+ * never cleared: the caller zeroes it before a stream's first piece.  So: zero eager_io, set state_io = START, feed an input's
+ * pieces through successive calls -- after the last one eager_io is the set fsm_exec's callback receives over the
+ * concatenated input, state_io its final state and end_out what fsm_exec returns (whatever the cut points, empty pieces
+ * included).  Inputs: packed (off != NULL: n + 1 offsets, stride and len ignored; decreasing host offsets: EINVAL) or fixed
+ * stride (+ len, may be NULL), as fsm_hip_exec_batch_eager_trace takes them.  end_out optional.  NULL dfa, state_io or
+ * eager_io: -1, EINVAL. */
+int fsm_hip_exec_batch_eager_resume(const struct fsm_hip_dfa *dfa,
+	const unsigned char *base, size_t stride, const uint32_t *len, const uint64_t *off, size_t n,
+	uint32_t *state_io, uint32_t *end_out, uint64_t *eager_io);
+int fsm_hip_exec_batch_eager_resume_device(const struct fsm_hip_dfa *dfa,
+	const void *d_base, size_t stride, const uint32_t *d_len, const uint64_t *d_off, size_t n,
+	uint32_t *d_state_io, uint32_t *d_end_out, uint64_t *d_eager_io, void *hip_stream);
 
 /* The callback STREAM of fsm_exec (exec.c:120-144, match_eager_outputs_for_state :62-78), order and repeats kept:
  * for input i, count_out[i] = how many times the reference would have called the eager-output callback, and the

@@ -185,8 +185,9 @@ class FlatDfa:
                    eo, arr(d.eager_ids, int(eo[n]), np.uint32) if eo is not None else None)
 
     @classmethod
-    def from_dense(cls, next_tab: np.ndarray, start: int, is_end: Sequence[int], endids=None) -> "FlatDfa":
-        """next_tab: [S][256] int64/uint32, negative or 0xFFFFFFFF = no edge."""
+    def from_dense(cls, next_tab: np.ndarray, start: int, is_end: Sequence[int], endids=None, eager_off=None, eager_ids=None) -> "FlatDfa":
+        """next_tab: [S][256] int64/uint32, negative or 0xFFFFFFFF = no edge.  eager_off (u32 [S + 1], CSR) / eager_ids: the
+        eager outputs of every state (the ids of state s are eager_ids[eager_off[s]:eager_off[s + 1]]), or None."""
         nt = np.asarray(next_tab, dtype=np.int64)
         S = nt.shape[0]
         rng, off = [], [0]
@@ -209,8 +210,10 @@ class FlatDfa:
             if endids is not None and s in endids:
                 ei.extend(sorted(set(endids[s])))
             eo.append(len(ei))
+        if eager_off is not None and len(eager_off) != S + 1:
+            raise ValueError("eager_off needs nstates + 1 entries")
         return cls(S, start, np.array(off, np.uint32), np.array(rng, dtype=RANGE_DTYPE) if rng else np.zeros(0, RANGE_DTYPE),
-                   np.asarray(is_end, np.uint8), np.array(eo, np.uint32), np.array(ei, np.uint32))
+                   np.asarray(is_end, np.uint8), np.array(eo, np.uint32), np.array(ei, np.uint32), eager_off, eager_ids)
 
     def dense(self) -> np.ndarray:
         """[S][256] uint32 next table, NO_MATCH = no edge."""
@@ -613,6 +616,48 @@ class HipDfa:
             raise _oserr("fsm_hip_exec_batch_ids_offsets")
         return out
 
+    def _eager_ids_of(self, words: np.ndarray) -> np.ndarray:
+        """a W-word set -> the sorted ids it holds"""
+        self._lib.fsm_hip_eager_id_count.restype = C.c_size_t
+        self._lib.fsm_hip_eager_id.restype = C.c_uint32
+        k = self._lib.fsm_hip_eager_id_count(C.c_void_p(self._h))
+        bits = np.unpackbits(np.ascontiguousarray(words, np.uint64).view(np.uint8), bitorder="little")[:k].astype(bool)
+        return np.array(sorted(self._lib.fsm_hip_eager_id(C.c_void_p(self._h), C.c_uint(b)) for b in np.nonzero(bits)[0]), np.uint32)
+
+    def exec_batch_eager_resume(self, data: np.ndarray, state_io: np.ndarray, eager_io: np.ndarray, lens: Optional[np.ndarray] = None,
+                                off: Optional[np.ndarray] = None):
+        """fsm_hip_exec_batch_eager_resume: one more piece of every input.  data: [n][stride] rows (+ lens), or with off (n + 1
+        u64 offsets) the packed bytes.  eager_io: n * eager_words() u64 (zeroed before a stream's first piece), OR-ed into.
+        Returns (state_out, end, eager_io) -- new arrays; the arguments are left as they are."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if off is not None:
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+            n, stride = len(off) - 1, 0
+        else:
+            n, stride = data.shape
+        st = np.ascontiguousarray(state_io, dtype=np.uint32).copy()
+        eo = np.ascontiguousarray(eager_io, dtype=np.uint64).copy()
+        if eo.size != n * self.eager_words():
+            raise ValueError("eager_io needs n * eager_words() words")
+        end = np.empty(n, dtype=np.uint32)
+        if lens is not None:
+            lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        C.set_errno(0)
+        vp = C.c_void_p
+        if self._lib.fsm_hip_exec_batch_eager_resume(vp(self._h), vp(data.ctypes.data if data.size else None), C.c_size_t(stride), _ptr(lens),
+                                                     _ptr(off), C.c_size_t(n), _ptr(st), _ptr(end), _ptr(eo)) != 0:
+            raise _oserr("fsm_hip_exec_batch_eager_resume")
+        return st, end, eo
+
+    def exec_batch_eager_resume_device(self, d_base: int, stride: int, n: int, d_state_io: int, d_eager_io: int, d_len: int = 0, d_off: int = 0,
+                                       d_end: int = 0, stream: int = 0):
+        C.set_errno(0)
+        vp = C.c_void_p
+        if self._lib.fsm_hip_exec_batch_eager_resume_device(vp(self._h), vp(d_base or None), C.c_size_t(stride), vp(d_len or None), vp(d_off or None),
+                                                            C.c_size_t(n), vp(d_state_io or None), vp(d_end or None), vp(d_eager_io or None),
+                                                            vp(stream or None)) != 0:
+            raise _oserr("fsm_hip_exec_batch_eager_resume_device")
+
     def exec_offsets_resume(self, base: np.ndarray, off: np.ndarray, state_io: np.ndarray):
         base = np.ascontiguousarray(base, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
@@ -741,6 +786,38 @@ class HipDfa:
         if r < 0:
             raise _oserr("fsm_hip_match_buffer_big")
         return r, e.value
+
+    def match_buffer_big_eager(self, data: bytes):
+        """fsm_hip_match_buffer_big_eager: (1 / 0, caller's end state or NO_MATCH, sorted u32 ids of the eager outputs emitted
+        over the whole input) of ONE input walked by the whole device."""
+        e = C.c_uint32(NO_MATCH)
+        eo = np.zeros(self.eager_words(), np.uint64)
+        buf = (C.c_char * max(len(data), 1)).from_buffer_copy(data if len(data) else b"\0")
+        C.set_errno(0)
+        r = self._lib.fsm_hip_match_buffer_big_eager(C.c_void_p(self._h), buf, C.c_size_t(len(data)), C.byref(e), _ptr(eo))
+        if r < 0:
+            raise _oserr("fsm_hip_match_buffer_big_eager")
+        return r, e.value, self._eager_ids_of(eo)
+
+    def match_file_eager(self, path: str):
+        """fsm_hip_match_file_eager on a file opened with the C library: (1 / 0, end state or NO_MATCH, sorted u32 ids)."""
+        libc = C.CDLL(None, use_errno=True)
+        libc.fopen.restype = C.c_void_p
+        libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
+        libc.fclose.argtypes = [C.c_void_p]
+        e = C.c_uint32(NO_MATCH)
+        eo = np.zeros(self.eager_words(), np.uint64)
+        f = libc.fopen(path.encode(), b"rb")
+        if not f:
+            raise OSError(C.get_errno(), "fopen")
+        try:
+            C.set_errno(0)
+            r = self._lib.fsm_hip_match_file_eager(C.c_void_p(self._h), C.c_void_p(f), C.byref(e), _ptr(eo))
+        finally:
+            libc.fclose(f)
+        if r < 0:
+            raise _oserr("fsm_hip_match_file_eager")
+        return r, e.value, self._eager_ids_of(eo)
 
     def match_last_passes(self):
         """(windows, passes) of the last match_file / match_buffer_big call of this process"""

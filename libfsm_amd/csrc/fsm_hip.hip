@@ -834,6 +834,9 @@ static int launch_walk(const fsm_hip_dfa *d, WalkArgs a, bool fast_ok, hipStream
 {
 	if (a.n == 0) return 0;
 	const int eager = a.eager_out == nullptr ? 0 : a.eager_words > 1 ? 2 : 1;
+	/* the kernel family: a resumed eager walk (state_io + eager_out) has instantiations of its own (launch.h: 3 / 4); the
+	 * choice of kernel is the eager walk's */
+	const int keager = eager != 0 && a.state_io != nullptr ? eager + 2 : eager;
 	const bool varlen = a.off != nullptr || a.off32 != nullptr || a.len != nullptr;
 	const uint64_t known_bytes = hint.bytes != 0 ? hint.bytes : !varlen ? (uint64_t)a.n * a.stride : 0;
 	const LaunchCfg c = pick_cfg(d, fast_ok, a.stride, eager, hint.short_mean, known_bytes >= ((uint64_t)1 << 36), a.state_io != nullptr, a.n >= ((uint64_t)1 << 32));
@@ -912,7 +915,7 @@ static int launch_walk(const fsm_hip_dfa *d, WalkArgs a, bool fast_ok, hipStream
 			if (!eager && d->knob_waves <= 0 && d->knob_blocks_per_cu <= 0 && d->table_lds != 0 && d->plan.layout != FSM_HIP_LAYOUT_TINY) {
 				g.probe = 1;
 				g.kfn = nullptr;
-				if (launch_layout(d, eager, g, ag, dim3(1), dim3(64), s) == hipSuccess && g.kfn != nullptr) {
+				if (launch_layout(d, keager, g, ag, dim3(1), dim3(64), s) == hipSuccess && g.kfn != nullptr) {
 					const int by_lds = (int)(d->lds_limit / d->table_lds);
 					g.waves = waves_by_occupancy(kernel_vgprs(g.kfn), by_lds < 1 ? 1 : by_lds, g0.waves);
 					int bpc = by_lds < 1 ? 1 : by_lds;
@@ -924,7 +927,7 @@ static int launch_walk(const fsm_hip_dfa *d, WalkArgs a, bool fast_ok, hipStream
 			const uint64_t gb0 = (ntiles + g.waves - 1) / g.waves, gcap = (uint64_t)d->ncu * g.blocks_per_cu;
 			const dim3 ggrid((unsigned)(gb0 < gcap ? gb0 : gcap)), gblock((unsigned)g.waves * 64u);
 			g.kfn = nullptr;
-			e = launch_layout(d, eager, g, ag, ggrid, gblock, s);
+			e = launch_layout(d, keager, g, ag, ggrid, gblock, s);
 			if (e == hipSuccess) {
 				md->last_kernel = kernel_name(g.kfn, s);
 				md->last_kernel_pick[ag.run_when] = md->last_kernel;
@@ -935,7 +938,7 @@ static int launch_walk(const fsm_hip_dfa *d, WalkArgs a, bool fast_ok, hipStream
 	if (e == hipSuccess && c.mode != IN_GENERIC) {
 		a.run_when = PICK_RAGGED;
 		c.kfn = nullptr;
-		e = launch_layout(d, eager, c, a, dim3((unsigned)nblocks), dim3((unsigned)c.waves * 64u), s);
+		e = launch_layout(d, keager, c, a, dim3((unsigned)nblocks), dim3((unsigned)c.waves * 64u), s);
 		if (e == hipSuccess) {
 			md->last_kernel = kernel_name(c.kfn, s);
 			md->last_kernel_pick[PICK_RAGGED] = md->last_kernel;
@@ -2093,14 +2096,14 @@ extern "C" int fsm_hip_state_is_absorbing(const struct fsm_hip_dfa *d, uint32_t 
 
 static int resume_device(fsm_hip_dfa *d, const void *d_base, size_t stride, const uint32_t *d_len, const uint64_t *d_off, size_t n,
 	uint32_t *d_state_io, uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream, const BatchHint &hint,
-	const uint32_t *d_off32 = nullptr, bool lens_only = false)
+	const uint32_t *d_off32 = nullptr, bool lens_only = false, uint64_t *d_eager_io = nullptr)
 {
 	if (d == nullptr || d_state_io == nullptr || (n != 0 && d_off == nullptr && d_off32 == nullptr && !lens_only && d_base == nullptr && stride != 0) ||
 	    (lens_only && n != 0 && d_len == nullptr)) { errno = EINVAL; return -1; }
 	if (n == 0) return 0;
 	{
 		const fsm_hip_dfa *t = route(d, false);     /* (a resumed walk never takes the fixed-stride kernels of the pair table) */
-		if (t != d) return resume_device(const_cast<fsm_hip_dfa *>(t), d_base, stride, d_len, d_off, n, d_state_io, d_end_out, d_accept_bitmap, hip_stream, hint, d_off32, lens_only);
+		if (t != d) return resume_device(const_cast<fsm_hip_dfa *>(t), d_base, stride, d_len, d_off, n, d_state_io, d_end_out, d_accept_bitmap, hip_stream, hint, d_off32, lens_only, d_eager_io);
 	}
 	if (ensure_resume(d) != 0) return -1;
 	DevGuard dg(d->device);
@@ -2121,6 +2124,8 @@ static int resume_device(fsm_hip_dfa *d, const void *d_base, size_t stride, cons
 	a.enc_of = d->d_enc_of;
 	a.orig_of = d->d_orig_of;
 	a.nstates = d->plan.nstates;
+	/* eager sets carried across pieces (OR-ed into, never cleared); where no state emits, the plain resumed walk leaves them as they are */
+	if (d_eager_io != nullptr && !d->plan.emask.empty()) a.eager_out = d_eager_io;
 	const bool lo = lens_only && d_off == nullptr && d_off32 == nullptr;
 	DfaLock lk(d->mu);   /* pre-pass, walk and the block's event in one critical section (see exec_packed_device) */
 	if (lo && tile_bases(d, d_len, n, s, &a.tbase) != 0) return -1;
@@ -2242,6 +2247,40 @@ extern "C" int fsm_hip_exec_batch_resume_offsets(const struct fsm_hip_dfa *d,
 {
 	if (n != 0 && off == nullptr) { errno = EINVAL; return -1; }
 	return resume_host(d, base, 0, nullptr, off, n, state_io, end_out);
+}
+
+/* resume + eager outputs: the carry of fsm_vm_match_file with fsm_exec's callback installed (exec.c:126-151) */
+extern "C" int fsm_hip_exec_batch_eager_resume_device(const struct fsm_hip_dfa *dc,
+	const void *d_base, size_t stride, const uint32_t *d_len, const uint64_t *d_off, size_t n,
+	uint32_t *d_state_io, uint32_t *d_end_out, uint64_t *d_eager_io, void *hip_stream)
+{
+	if (dc == nullptr || d_state_io == nullptr || d_eager_io == nullptr) { errno = EINVAL; return -1; }
+	return resume_device(const_cast<fsm_hip_dfa *>(dc), d_base, d_off != nullptr ? 0 : stride, d_off != nullptr ? nullptr : d_len, d_off, n,
+	                     d_state_io, d_end_out, nullptr, hip_stream, BatchHint(), nullptr, false, d_eager_io);
+}
+
+extern "C" int fsm_hip_exec_batch_eager_resume(const struct fsm_hip_dfa *d,
+	const unsigned char *base, size_t stride, const uint32_t *len, const uint64_t *off, size_t n,
+	uint32_t *state_io, uint32_t *end_out, uint64_t *eager_io)
+{
+	size_t in_bytes = 0;
+	if (off != nullptr) { stride = 0; len = nullptr; }
+	if (d == nullptr || state_io == nullptr || eager_io == nullptr || check_host_batch(base, stride, len, off, n, &in_bytes) != 0) { errno = EINVAL; return -1; }
+	if (n == 0) return 0;
+	DevGuard dg(d->device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
+	HostCall hc(d);
+	const int p_in = hc.add(HostCall::IN, base, nullptr, in_bytes, 32);
+	const int p_len = len ? hc.add(HostCall::IN, len, nullptr, n * sizeof(uint32_t)) : -1;
+	const int p_off = off ? hc.add(HostCall::IN, off, nullptr, (n + 1) * sizeof(uint64_t)) : -1;
+	const int p_st = hc.add(HostCall::INOUT, state_io, state_io, n * sizeof(uint32_t));
+	const int p_eo = hc.add(HostCall::INOUT, eager_io, eager_io, n * fsm_hip_eager_words(d) * sizeof(uint64_t));
+	const int p_end = hc.add(HostCall::OUT, nullptr, end_out, n * sizeof(uint32_t));
+	if (hc.begin() != 0) return -1;
+	if (resume_device(hc.d, hc.dev<unsigned char>(p_in), stride, hc.dev<uint32_t>(p_len), hc.dev<uint64_t>(p_off), n,
+	                  hc.dev<uint32_t>(p_st), hc.dev<uint32_t>(p_end), nullptr, hc.d->hs, host_hint(in_bytes, len, off, n, pick_mean_of(d, false)),
+	                  nullptr, false, hc.dev<uint64_t>(p_eo)) != 0) return -1;
+	return hc.end();
 }
 
 /* ------------------------------------------------------------------ */

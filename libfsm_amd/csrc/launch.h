@@ -36,7 +36,8 @@ enum {
 	POL_COMB = 0, POL_COMB256 = 1, POL_COMBSELF = 2,
 	POL_GLOB = 0, POL_SPARSE = 1
 };
-/* eager: 0 = plain walk, 1 = EagerPol (<= 64 ids, set in registers), 2 = EagerWidePol */
+/* eager: 0 = plain walk, 1 = EagerPol (<= 64 ids, set in registers), 2 = EagerWidePol; 3 / 4: the same resumed (state_io:
+ * the set is added to, the start state's outputs fire only from FSM_HIP_STATE_START) */
 hipError_t launch_tiny(int pol, int eager, const LaunchCfg &c, const WalkArgs &a, dim3 grid, dim3 block, hipStream_t s);
 hipError_t launch_lds(int pol, int eager, const LaunchCfg &c, const WalkArgs &a, dim3 grid, dim3 block, hipStream_t s);
 hipError_t launch_comb(int pol, int eager, const LaunchCfg &c, const WalkArgs &a, dim3 grid, dim3 block, hipStream_t s);
@@ -133,7 +134,9 @@ static hipError_t launch_family(int eager, const LaunchCfg &c, const WalkArgs &a
 {
 	if (eager == 0) return launch_pol<Pol>(c, a, grid, block, s);
 	if (eager == 1) return launch_eager_pol<EagerPol<Pol>, true, eager_dma_threads<Pol>::value>(c, a, grid, block, s);
-	return launch_eager_pol<EagerWidePol<Pol>, false, 1024>(c, a, grid, block, s);
+	if (eager == 2) return launch_eager_pol<EagerWidePol<Pol>, false, 1024>(c, a, grid, block, s);
+	if (eager == 3) return launch_eager_pol<EagerPol<Pol, true>, true, eager_dma_threads<Pol>::value>(c, a, grid, block, s);
+	return launch_eager_pol<EagerWidePol<Pol, true>, false, 1024>(c, a, grid, block, s);
 }
 
 } // namespace fsmhip

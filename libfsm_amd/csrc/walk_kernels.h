@@ -941,6 +941,9 @@ struct SparseFastPol : SparsePol {
  * ids attached to the start state and to every state entered are OR-ed into a 64-bit set carried
  * next to the state.  States with outputs are numbered so that one range test on the encoded state
  * finds them; only lanes entering such a state do the (exec-masked) mask lookup.
+ * RES (a resumed walk, state_io != NULL): the start state's outputs fire only for an input that starts
+ * from FSM_HIP_STATE_START (a state carried over from an earlier piece fired when it was entered), and
+ * the set is OR-ed into eager_out[i], which holds what the earlier pieces emitted.
  */
 template <class Pol>
 struct EagerState {
@@ -948,7 +951,7 @@ struct EagerState {
 	uint64_t acc;
 };
 
-template <class Pol>
+template <class Pol, bool RES = false>
 struct EagerPol : Pol {
 	typedef EagerState<Pol> S;
 	typedef typename Pol::P P;
@@ -976,6 +979,14 @@ struct EagerPol : Pol {
 		S st;
 		st.s = Pol::init(code);
 		st.acc = outputs_of(code); /* the start state emits before any input (exec.c:126-130) */
+		return st;
+	}
+	__device__ __forceinline__ S init_at(uint32_t code, const WalkArgs &a, uint64_t i, bool valid) const
+	{
+		if constexpr (!RES) return init(code);
+		S st;
+		st.s = Pol::init(code);
+		st.acc = valid && a.state_io[i] == FSMHIP_STATE_START ? outputs_of(code) : 0;
 		return st;
 	}
 	__device__ __forceinline__ static uint32_t code(const S &st) { return Pol::code(st.s); }
@@ -1034,7 +1045,11 @@ struct EagerPol : Pol {
 	}
 	__device__ __forceinline__ static void finish(const WalkArgs &a, uint64_t i, bool valid, const S &st)
 	{
-		if (valid && a.eager_out != nullptr) a.eager_out[i] = st.acc;
+		if constexpr (RES) {
+			if (valid && a.eager_out != nullptr) a.eager_out[i] |= st.acc;
+		} else {
+			if (valid && a.eager_out != nullptr) a.eager_out[i] = st.acc;
+		}
 	}
 };
 
@@ -1042,7 +1057,8 @@ struct EagerPol : Pol {
  * EagerWidePol<Pol>: the same side channel for more than 64 ids.  The id set of input i is
  * eager_words u64 in device memory, owned by the lane that walks i: entering a state with outputs
  * ORs that state's (word, mask) pairs into it (plain read-modify-write, no atomics; rare).  The
- * buffer is zeroed on the launch stream before the kernel.
+ * buffer is zeroed on the launch stream before the kernel -- except for a resumed walk (RES), which
+ * adds to what the earlier pieces emitted and fires the start state's outputs only from FSM_HIP_STATE_START.
  */
 template <class Pol>
 struct EagerWideState {
@@ -1051,7 +1067,7 @@ struct EagerWideState {
 	uint32_t pend;     /* encoded state whose outputs are not written yet, or NONE */
 };
 
-template <class Pol>
+template <class Pol, bool RES = false>
 struct EagerWidePol : Pol {
 	typedef EagerWideState<Pol> S;
 	typedef typename Pol::P P;
@@ -1084,6 +1100,9 @@ struct EagerWidePol : Pol {
 		st.s = Pol::init(code);
 		st.row = valid ? a.eager_out + i * a.eager_words : nullptr;
 		st.pend = emits(code) ? code : 0xFFFFFFFFu;   /* the start state emits before any input (exec.c:126-130) */
+		if constexpr (RES) {
+			if (!valid || a.state_io[i] != FSMHIP_STATE_START) st.pend = 0xFFFFFFFFu;
+		}
 		return st;
 	}
 	__device__ __forceinline__ static uint32_t code(const S &st) { return Pol::code(st.s); }
