@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- the hot path (batched DFA walk) on N GPUs of one node.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c5] [--n INPUTS_PER_GPU] [--subs auto|none]
-                    [--scaling weak|strong] [--full-parity] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c5] [--n INPUTS_PER_GPU] [--full [--subs auto|none]]
+                    [--scaling weak|strong] [--dump-outputs DIR]
 
 A "step" is one pass of the walk kernel over one batch of synthetic inputs that is already resident in
 HBM (generated on the device, so nothing crosses PCIe), followed -- for N > 1 -- by the RCCL all-gather of
 the accept bitmap (asynchronous: it overlaps the next step's kernel; all K gathers finish inside the timed
 region).  Inputs are sharded by contiguous global index range, one shard per rank.  Rank 0 prints ONE JSON
 line.
+
+A plain run does what the headline needs and no more: set-up, warm-up, the K timed steps, --dump-outputs, the line.
+--full adds everything else the benchmark measures and checks: the CPU baselines and the parity checks against them
+(sample and full-N), the sub_results below, the read-stream and gather probes, and the node front.
 
 Workloads (BASELINE.json configs):
   c3  configs[2], the north star's target config: 1 024 anchored PCRE unioned into one ~4 096-state DFA,
@@ -20,7 +24,7 @@ Workloads (BASELINE.json configs):
       requests, not by HBM.
   c3t the transition-dense twin of c3 (not a BASELINE config): 1 024 patterns ^<pfx>([0-9][a-f])+(x|yz)$, half the
       rows alternating digit / letter, so a live row changes state on every byte and no chunk can be skipped.
-At N = 1 the line carries the other configs as `sub_results` (each with its own roofline, cpu_baseline and
+At N = 1 a --full line carries the other configs as `sub_results` (each with its own roofline, cpu_baseline and
 parity): c3 with the chunk skip disabled (every byte pays its lookup test), c3t, c2, c5.  N > 1 defaults to configs[3]'s shard, 1.25e8 inputs per GPU.
 The c2/c3 DFA tables come from tests/golden/{c1,c3}.npz (flattened from the real reference by
 tests/golden/make_golden.py); /root/reference is not needed at run time.
@@ -49,7 +53,10 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="c3", choices=["c2", "c3", "c3t", "c3u", "lds2", "c5", "c2_short", "c3_short", "c2_ragged", "c3_ragged", "c5_short", "c5_ragged", "c3_eager40"],
-                    help="c*_short / c*_ragged: the packed-lines front alone (what the default run reports as sub_results), for profiling")
+                    help="c*_short / c*_ragged: the packed-lines front alone (what a --full run reports as sub_results), for profiling")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU baselines, parity checks, sub_results, probes, the node front "
+                         "(the options below that select among these act only with --full)")
     ap.add_argument("--subs", default="auto", choices=["auto", "none"],
                     help="auto: at N = 1 also measure the other configs and report them as sub_results")
     ap.add_argument("--n", "--inputs", dest="n", type=int, default=0,
@@ -68,7 +75,7 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--node-front", action="store_true",
                     help="measure the C multi-device front (fsm_hip_node_*: one replica + host thread per visible GPU, one process) "
-                         "on the main workload and print its JSON; bench.py runs this by itself, in a subprocess, when N = 1 sees several GPUs")
+                         "on the main workload and print its JSON; bench.py --full runs this by itself, in a subprocess, when N = 1 sees several GPUs")
     ap.add_argument("--full-parity", action="store_true",
                     help="(the default for the main workload at N = 1; kept for old command lines)")
     ap.add_argument("--no-full-parity", action="store_true",
@@ -662,7 +669,7 @@ T_START = time.perf_counter()
 
 
 def over_budget():
-    """The full-N checks of the SUB-results are the long part of a default run (host-side: every byte streamed back and walked by the
+    """The full-N checks of the SUB-results are the long part of a --full run (host-side: every byte streamed back and walked by the
     CPU checker).  On a slow or throttled host they stop once the run is FSM_BENCH_TIME_BUDGET seconds old (default 420): the sample
     parity of every sub-result still runs, the main workload's full check always does, and the record says what was skipped."""
     return time.perf_counter() - T_START > float(os.environ.get("FSM_BENCH_TIME_BUDGET", "420"))
@@ -907,7 +914,7 @@ def main():
                                        "input byte where the record-as-state walk made 0.33 -- and is bound by instruction issue now, not by gathers and not by HBM "
                                        "(profiles/r06b_c5_lazy_pmc_rows2.txt; DESIGN.md section 3): the fraction of HBM peak is reported for uniformity, "
                                        "roofline.gather_ceiling gives the memory-side denominator")
-        if not dist_on and with_cpu and not a.no_cpu_baseline and a.cpu_sample != 0:
+        if a.full and not dist_on and with_cpu and not a.no_cpu_baseline and a.cpu_sample != 0:
             sample = a.cpu_sample if a.cpu_sample > 0 else (400_000 if wl == "c2" else 100_000)
             idx = sample_indices(n_, sample)
             tidx = torch.from_numpy(idx).cuda()
@@ -922,17 +929,17 @@ def main():
             res["parity_sample"] = f"{len(idx)} inputs: seeded stratified sample of [0, {n_}) + first/last 64 rows" + (" + rows around byte offset 2^32" if n_ > (1 << 22) + 64 else "")
             if not (parity and twin):
                 res["value"] = None  # a fast wrong answer is not a result
-        # the full-N compare, for the main workload of a default run -- and for c5 wherever it runs (round 4: its
+        # the full-N compare, for the main workload of a --full run -- and for c5 wherever it runs (round 4: its
         # table is 1 GB as the oracle keeps it and the cpu_baseline leg has built it already; 1e7 rows take the walker's threads
         # about a minute)
-        if not dist_on and variant is None and not a.no_full_parity and with_cpu and not a.no_cpu_baseline and (a.full_parity or wl == a.workload or wl == "c5") \
+        if a.full and not dist_on and variant is None and not a.no_full_parity and with_cpu and not a.no_cpu_baseline and (a.full_parity or wl == a.workload or wl == "c5") \
                 and wl != a.workload and over_budget():
             res["full_parity_skipped"] = "time budget (FSM_BENCH_TIME_BUDGET) reached: sample parity only"
-        elif not dist_on and variant is None and not a.no_full_parity and with_cpu and not a.no_cpu_baseline and (a.full_parity or wl == a.workload or wl == "c5"):
+        elif a.full and not dist_on and variant is None and not a.no_full_parity and with_cpu and not a.no_cpu_baseline and (a.full_parity or wl == a.workload or wl == "c5"):
             res["full_parity"] = full_parity(torch, flat, buf, end, n_, L)
             if res["full_parity"]["mismatches"]:
                 res["value"] = None
-        if wl == "c5":
+        if wl == "c5" and a.full:
             # a denominator for this walk: what the memory system gives 16-byte gathers from a table of this size at full occupancy
             # (the walk's own-record gathers, 0.07 per input byte), and what the instruction stream allows
             try:
@@ -1027,7 +1034,7 @@ def main():
 
         wall, k_ms = timed("off64_end", lambda: dfa.exec_batch_offsets_device(packed.data_ptr(), off.data_ptr(), n_l, end.data_ptr(), 0, stream=stream), 8, 4)
         ok_forms = True
-        only64 = os.environ.get("FSM_BENCH_LINES_FORMS") == "off64"      # profiling runs: one kernel, one form
+        only64 = not a.full or os.environ.get("FSM_BENCH_LINES_FORMS") == "off64"      # the headline's form alone (profiling runs: one kernel)
         if off32 is not None and not only64:
             timed("off32_end", lambda: dfa.exec_batch_offsets32_device(packed.data_ptr(), off32.data_ptr(), n_l, end2.data_ptr(), 0, stream=stream), 4, 4)
             ok_forms = ok_forms and bool(torch.equal(end, end2))
@@ -1066,7 +1073,7 @@ def main():
                 pass
         # parity: a stratified sample of the lines -- their bytes gathered from the PACKED buffer the kernel walked -- against
         # the oracle's walk
-        if not a.no_cpu_baseline and a.cpu_sample != 0:
+        if a.full and not a.no_cpu_baseline and a.cpu_sample != 0:
             idx = sample_indices(n_l, 100_000)
             tidx = torch.from_numpy(idx).cuda()
             sl = lens[tidx].to(torch.int64)
@@ -1127,8 +1134,9 @@ def main():
         sets = torch.zeros((n_e, W), dtype=torch.int64, device="cuda")
         torch.cuda.synchronize()
         res = {"workload": "c3_eager40"}
-        for name, fn in (("plain", lambda: dfa.exec_batch_device(buf.data_ptr(), L, n_e, end.data_ptr(), 0, stream=stream)),
-                         ("eager", lambda: dfa.exec_batch_eager_device(buf.data_ptr(), L, n_e, end.data_ptr(), sets.data_ptr(), stream=stream))):
+        plain = ("plain", lambda: dfa.exec_batch_device(buf.data_ptr(), L, n_e, end.data_ptr(), 0, stream=stream))   # --full: the same dfa's plain walk beside it
+        eager = ("eager", lambda: dfa.exec_batch_eager_device(buf.data_ptr(), L, n_e, end.data_ptr(), sets.data_ptr(), stream=stream))
+        for name, fn in ((plain, eager) if a.full else (eager,)):
             for _ in range(3):
                 fn()
             torch.cuda.synchronize()
@@ -1151,7 +1159,7 @@ def main():
                    roofline={"bound": "hbm", "achieved": round(alg / k_ms / 1e6, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(alg / k_ms / 1e6 / HBM_PEAK_GBS, 4),
                              "kernel": res["eager"]["kernel"], "kernel_ms_avg": k_ms, "algorithmic_bytes_per_launch": alg,
                              "algorithmic_bytes": "L bytes + 4 B end state + 8 B id set per input", "traffic": None, "traffic_source": None,
-                             "plain_walk_same_dfa_GBps": res["plain"]["GBps"]})
+                             "plain_walk_same_dfa_GBps": res["plain"]["GBps"] if "plain" in res else None})
         pj = os.path.join(ROOT, "profiles", "pmc_c3_eager40.json")
         if os.path.exists(pj):
             try:
@@ -1161,7 +1169,7 @@ def main():
                     res["roofline"]["traffic_source"] = f"profiles/{t.get('source')}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over this sub-result (recorded, not measured in this run)"
             except Exception:
                 pass
-        if not a.no_cpu_baseline and a.cpu_sample != 0:
+        if a.full and not a.no_cpu_baseline and a.cpu_sample != 0:
             # the oracle's eager walk (exec.c:126-144 restated) on a stratified sample: end state AND id set per input
             o = get_oracle(flat)
             idx = sample_indices(n_e, 20_000)
@@ -1324,7 +1332,7 @@ def main():
     progress("main workload %s" % a.workload)
     main_res = run(a.workload, dump_dir=a.dump_outputs)
     subs = []
-    if not dist_on and a.subs == "auto" and a.n == 0 and not shrunk:
+    if a.full and not dist_on and a.subs == "auto" and a.n == 0 and not shrunk:
         plan = []
         if a.workload == "c3":
             plan.append(("c3", "noskip", None))
@@ -1379,10 +1387,11 @@ def main():
     buf, bm = main_res.pop("_buf")
     main_res.pop("_digest", None)
     stream_gbps = None
-    try:  # what a read-only kernel sustains over the same resident bytes (three access patterns, the fastest)
-        stream_gbps = hip.stream_read_probe_gbps(buf.data_ptr(), buf.numel(), bm.data_ptr(), 3, stream)
-    except Exception:
-        pass
+    if a.full:
+        try:  # what a read-only kernel sustains over the same resident bytes (three access patterns, the fastest)
+            stream_gbps = hip.stream_read_probe_gbps(buf.data_ptr(), buf.numel(), bm.data_ptr(), 3, stream)
+        except Exception:
+            pass
     res = {
         "metric": "input GB/s matched (whole node)", "value": main_res["value"], "unit": "GB/s",
         "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": main_res["ms_per_step"],
@@ -1397,7 +1406,7 @@ def main():
             res[k] = main_res[k]
     # N = 1 on a box that shows several GPUs: the C multi-device front on all of them, in a subprocess of its own
     # (its failure must not cost the line above); FSM_BENCH_NODE_FRONT=1 forces it on a one-GPU box
-    if not dist_on and a.subs == "auto" and a.n == 0 and (torch.cuda.device_count() > 1 or os.environ.get("FSM_BENCH_NODE_FRONT")):
+    if a.full and not dist_on and a.subs == "auto" and a.n == 0 and (torch.cuda.device_count() > 1 or os.environ.get("FSM_BENCH_NODE_FRONT")):
         import subprocess
         del buf, bm
         buf_all = end_all = None

@@ -921,6 +921,29 @@ def test_bench_dump_outputs(hip, tmp_path):
         assert np.array_equal(a[k], got[1][k]), k
 
 
+def test_bench_checks_run_with_full_only(hip, tmp_path):
+    """A plain bench.py run times its steps and prints the line, nothing more; --full adds the CPU baseline, the sample and
+    full-N parity checks and the read-stream probe to the same measurement."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "c2",
+           "--inputs", "65536", "--len", "256"]
+    lines = []
+    for extra in ([], ["--full"]):
+        out = subprocess.run(cmd + extra, capture_output=True, text=True, timeout=600, cwd=root,
+                             env=dict(os.environ, FSM_BENCH_DETAIL=str(tmp_path / "detail.json")))
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1]))
+    plain, full = lines
+    for k in ("cpu_baseline", "parity_vs_cpu_sample", "full_parity"):
+        assert k not in plain and k in full, k
+    assert full["parity_vs_cpu_sample"] == "bit-exact" and full["full_parity"]["mismatches"] == 0
+    assert "measured_read_stream_GBps" not in plain["roofline"] and full["roofline"]["measured_read_stream_GBps"] > 0
+    assert plain["value"] > 0 and full["value"] > 0 and plain["config"]["accepted_inputs"] == full["config"]["accepted_inputs"]
+
+
 def test_retest_style_c_driver(hip, tmp_path):
     """examples/retest_hip.c: a plain-C retest(1) over .tst files -- libre compiles each regex, the HIP path
     runs each block's +/- lines in ONE batch.  The .tst files are regenerated here from the retest goldens
