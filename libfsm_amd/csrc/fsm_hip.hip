@@ -1045,104 +1045,213 @@ static void tile_bases_done(fsm_hip_dfa *d, hipStream_t s)
 	if (hipEventRecord(d->tb_scratch_ev, s) == hipSuccess) d->tb_scratch_busy = true;
 }
 
-static int exec_stride_device(const struct fsm_hip_dfa *d,
-	const void *d_base, size_t stride, const uint32_t *d_len, size_t n,
-	uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream, const BatchHint &hint)
-{
-	if (d == nullptr || (n != 0 && d_base == nullptr && stride != 0)) { errno = EINVAL; return -1; }
+/* ------------------------------------------------------------------ */
+/* the two fronts of the walk: a batch is described once              */
+/* ------------------------------------------------------------------ */
+
+/* Where a batch's inputs are (device pointers for walk_device, host pointers for walk_host).  The two builders are the only
+ * writers, so at most one of len / off / off32 is set: offsets win over lengths, u64 offsets over u32 offsets. */
+struct Inputs {
+	const void *base;
+	size_t stride;           /* rows: bytes between inputs (0: packed, or empty inputs) */
+	const uint32_t *len;     /* rows: per-row lengths or NULL (= stride); lens_only: the packed inputs' lengths */
+	const uint64_t *off;     /* packed: n+1 offsets */
+	const uint32_t *off32;   /* packed, below 4 GiB: n+1 offsets */
+	bool lens_only;          /* packed back to back, located by their lengths alone */
+	size_t n;
+
+	/* rows of `stride` bytes (whole, or with per-row lengths), or packed inputs where u64 offsets are given */
+	static Inputs rows_or_offsets(const void *base, size_t stride, const uint32_t *len, const uint64_t *off, size_t n)
 	{
-		const fsm_hip_dfa *t = route(d, d_len == nullptr && stride != 0 && stride % 16u == 0 && (reinterpret_cast<uintptr_t>(d_base) % 16u) == 0);
-		if (t != d) return exec_stride_device(t, d_base, stride, d_len, n, d_end_out, d_accept_bitmap, hip_stream, hint);
+		if (off != nullptr) return Inputs{ base, 0, nullptr, off, nullptr, false, n };
+		return Inputs{ base, stride, len, nullptr, nullptr, false, n };
 	}
+	/* packed inputs whose metadata is u64 offsets, u32 offsets or lengths alone (FSM_HIP_META_*); false: no such form, or no metadata */
+	static bool packed_by(int meta_form, const void *base, const void *meta, size_t n, Inputs *in)
+	{
+		if (n != 0 && meta == nullptr) return false;
+		*in = Inputs{ base, 0, nullptr, nullptr, nullptr, false, n };
+		switch (meta_form) {
+		case FSM_HIP_META_OFF64:   in->off = static_cast<const uint64_t *>(meta); return true;
+		case FSM_HIP_META_OFF32:   in->off32 = static_cast<const uint32_t *>(meta); return true;
+		case FSM_HIP_META_LENGTHS: in->len = static_cast<const uint32_t *>(meta); in->lens_only = true; return true;
+		default:                   return false;
+		}
+	}
+	bool packed() const { return off != nullptr || off32 != nullptr || lens_only; }
+	/* whole rows, stride and base 16-byte aligned: what the fixed-stride kernels take (an automaton tuned to IN_GENERIC still
+	 * declines: that term is applied where launch_walk is called) */
+	bool fixed_fast() const
+	{
+		return !packed() && len == nullptr && stride != 0 && stride % 16u == 0 && (reinterpret_cast<uintptr_t>(base) % 16u) == 0;
+	}
+	void fill(WalkArgs &a) const
+	{
+		a.base = static_cast<const uint8_t *>(base);
+		a.stride = stride;
+		a.len = len;
+		a.off = off;
+		a.off32 = off32;
+		a.n = n;
+	}
+};
+
+/* What the caller wants back, whichever are asked for: the walk kernels write all of them in one pass */
+struct Outputs {
+	uint32_t *end_out = nullptr;
+	uint64_t *bitmap = nullptr;
+	int ids_mode = 0;               /* FSM_HIP_IDS_*, read where id_out is set */
+	uint32_t *id_out = nullptr;     /* device-side end-ids */
+	uint64_t *eager_out = nullptr;  /* eager sets, written */
+	uint32_t *state_io = nullptr;   /* resume: the state to start from, the state reached */
+	uint64_t *eager_io = nullptr;   /* resume: eager sets carried across pieces (OR-ed into, never cleared) */
+
+	static Outputs ends(uint32_t *end_out, uint64_t *bitmap)
+	{
+		Outputs o;
+		o.end_out = end_out;
+		o.bitmap = bitmap;
+		return o;
+	}
+};
+
+/* Where the entry points differ without their batch or their outputs saying so.  Each of these is how the fronts behaved
+ * while they were separate functions; none has been decided on its merits yet. */
+struct FrontTraits {
+	/* an empty batch (n == 0): GOES_ON to the device (guard, upload of a FSM_HIP_DEFER_UPLOAD automaton, end-id tables) and
+	 * leaves it to launch_walk; RETURNS 0 before anything is touched or routed; RETURNS_AFTER_IDS: routed, ids_mode checked and
+	 * the end-id tables built first */
+	enum Empty { GOES_ON, RETURNS, RETURNS_AFTER_IDS } empty;
+	/* fsm_hip_exec_batch_eager{,_offsets}{,_device}: an automaton with eager ids walks on its own image whatever the batch's
+	 * form (route() is not asked, where FRONT_ALL asks it for the same batch); one without eager ids zeroes the sets and is the
+	 * plain front from there on, an empty batch included.  (Not asking route() cannot be observed today: only the pair table
+	 * keeps a second image, and the planner gives no automaton with eager ids the pair table -- plan.cpp emit_lds2.) */
+	bool eager_front;
+	/* host pointers, packed inputs: the mean length is held against pick_mean_of(d, true) where walk_lines32 is the per-lane
+	 * kernel (128, not 96) */
+	bool lines32_mean;
+	/* an ids_mode that does not exist is refused after route(), not with the other arguments before it: the refused call
+	 * has then moved fsm_hip_last_kernel_name() to the image the batch would have gone to */
+	bool ids_mode_after_route;
+};
+static const FrontTraits
+	FRONT_ROWS   = { FrontTraits::GOES_ON, false, true, false },            /* fsm_hip_exec_batch{,_device} */
+	FRONT_PACKED = { FrontTraits::RETURNS, false, true, false },            /* ..._offsets, _offsets32, _lengths {,_device} */
+	FRONT_IDS    = { FrontTraits::GOES_ON, false, false, false },           /* ..._ids{,_offsets}{,_device} */
+	FRONT_RESUME = { FrontTraits::RETURNS, false, false, false },           /* ..._resume*, _eager_resume {,_device} */
+	FRONT_EAGER  = { FrontTraits::GOES_ON, true, false, false },            /* ..._eager{,_offsets}{,_device} */
+	FRONT_ALL    = { FrontTraits::RETURNS_AFTER_IDS, false, false, true };  /* ..._all_device, _packed_all{,_device} */
+
+/* The device-pointer front of every walk: one batch, every output asked for, one launch_walk */
+static int walk_device(const fsm_hip_dfa *dc, const Inputs &in, Outputs out, void *hip_stream, const BatchHint &hint, const FrontTraits &tr)
+{
+	fsm_hip_dfa *d = const_cast<fsm_hip_dfa *>(dc);
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	const bool no_such_mode = out.id_out != nullptr && out.ids_mode != FSM_HIP_IDS_EARLIEST && out.ids_mode != FSM_HIP_IDS_RET && out.ids_mode != FSM_HIP_IDS_ERROR;
+	if (d == nullptr || (in.n != 0 && !in.packed() && in.base == nullptr && in.stride != 0) || (no_such_mode && !tr.ids_mode_after_route)) {
+		errno = EINVAL;
+		return -1;
+	}
+	if (in.n == 0 && tr.empty == FrontTraits::RETURNS) return 0;
+	if (tr.eager_front && d->plan.emask.empty()) {
+		/* no state emits anything: the answer is all zeros, the walk is the plain one */
+		DevGuard dg(d->device);
+		if (!dg.ok()) { errno = ENODEV; return -1; }
+		const hipError_t e = zero_async(out.eager_out, in.n * sizeof(uint64_t), s);
+		if (e != hipSuccess) { errno = hip_errno(e); return -1; }
+		out.eager_out = nullptr;
+		return walk_device(d, in, out, hip_stream, hint, in.off != nullptr ? FRONT_PACKED : FRONT_ROWS);
+	}
+	if (!tr.eager_front) {
+		/* (a resumed walk never takes the fixed-stride kernels of the pair table) */
+		const fsm_hip_dfa *t = route(d, out.state_io == nullptr && in.fixed_fast());
+		if (t != d) return walk_device(t, in, out, hip_stream, hint, tr);
+	}
+	if (out.id_out != nullptr) {
+		if (no_such_mode) { errno = EINVAL; return -1; }
+		if (ensure_ids(d) != 0) return -1;
+		if (out.ids_mode == FSM_HIP_IDS_ERROR) {
+			/* AMBIG_ERROR: an end state with more than one id is refused (print/c.c:67-72 fails the
+			 * print with EINVAL); without such a state it is AMBIG_EARLIEST */
+			if (d->ids_conflict != FSM_HIP_NO_MATCH) { errno = EINVAL; return -1; }
+			out.ids_mode = FSM_HIP_IDS_EARLIEST;
+		}
+	}
+	if (in.n == 0 && tr.empty == FrontTraits::RETURNS_AFTER_IDS) return 0;
+	if (out.state_io != nullptr && ensure_resume(d) != 0) return -1;
 	DevGuard dg(d->device);
 	if (!dg.ok()) { errno = ENODEV; return -1; }
 	if (ensure_uploaded(d) != 0) return -1;
 	WalkArgs a = d->proto;
-	a.base = static_cast<const uint8_t *>(d_base);
-	a.stride = stride;
-	a.len = d_len;
-	a.off = nullptr;
-	a.n = n;
-	a.end_out = d_end_out;
-	a.bitmap = d_accept_bitmap;
-	const bool fast = d_len == nullptr && stride != 0 && stride % 16u == 0 &&
-		(reinterpret_cast<uintptr_t>(d_base) % 16u) == 0 && d->knob_input_mode != IN_GENERIC;
-	return launch_walk(d, a, fast, static_cast<hipStream_t>(hip_stream), hint);
+	in.fill(a);
+	a.end_out = out.end_out;
+	a.bitmap = out.bitmap;
+	if (out.id_out != nullptr) {
+		a.fin2 = out.ids_mode == FSM_HIP_IDS_EARLIEST ? d->d_fin_earliest : d->d_fin_ret;
+		a.out2 = out.id_out;
+	}
+	if (out.state_io != nullptr) {
+		a.state_io = out.state_io;
+		a.enc_of = d->d_enc_of;
+		a.orig_of = d->d_orig_of;
+		a.nstates = d->plan.nstates;
+		/* where no state emits, the plain resumed walk leaves the carried sets as they are */
+		if (!d->plan.emask.empty()) a.eager_out = out.eager_io;
+	} else if (out.eager_out != nullptr) {
+		if (d->plan.emask.empty() || d->plan.eager_words > 1) {
+			/* no state emits anything: all zeros; wide sets are OR-ed in place by the kernel: start from zero */
+			const size_t w = d->plan.emask.empty() ? 1 : d->plan.eager_words;
+			const hipError_t e = zero_async(out.eager_out, in.n * w * sizeof(uint64_t), s);
+			if (e != hipSuccess) { errno = hip_errno(e); return -1; }
+		}
+		if (!d->plan.emask.empty()) a.eager_out = out.eager_out;
+	}
+	/* The lengths-only form: ONE critical section over the pre-pass, the walk and the "block busy until here" event: another
+	 * host thread's call on this dfa must not refill the tile-base block between them (the mutex is recursive: the three take
+	 * it again) */
+	std::unique_lock<std::recursive_mutex> lk(d->mu, std::defer_lock);
+	if (in.lens_only) {
+		lk.lock();
+		if (tile_bases(d, in.len, in.n, s, &a.tbase) != 0) return -1;
+	}
+	const int r = launch_walk(d, a, in.fixed_fast() && d->knob_input_mode != IN_GENERIC, s, hint);
+	if (in.lens_only) tile_bases_done(d, s);
+	return r;
 }
 
 extern "C" int fsm_hip_exec_batch_device(const struct fsm_hip_dfa *d,
 	const void *d_base, size_t stride, const uint32_t *d_len, size_t n,
 	uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream)
 {
-	return exec_stride_device(d, d_base, stride, d_len, n, d_end_out, d_accept_bitmap, hip_stream, BatchHint());
+	return walk_device(d, Inputs::rows_or_offsets(d_base, stride, d_len, nullptr, n), Outputs::ends(d_end_out, d_accept_bitmap), hip_stream, BatchHint(), FRONT_ROWS);
 }
 
-/* inputs packed back to back, located by u64 offsets, u32 offsets, or their lengths alone (exactly one of the three) */
-static int exec_packed_device(const struct fsm_hip_dfa *d,
-	const void *d_base, const uint64_t *d_off, const uint32_t *d_off32, const uint32_t *d_len, size_t n,
-	uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream, const BatchHint &hint)
-{
-	if (d == nullptr || (n != 0 && d_off == nullptr && d_off32 == nullptr && d_len == nullptr)) { errno = EINVAL; return -1; }
-	if (n == 0) return 0;
-	{
-		const fsm_hip_dfa *t = route(d, false);
-		if (t != d) return exec_packed_device(t, d_base, d_off, d_off32, d_len, n, d_end_out, d_accept_bitmap, hip_stream, hint);
-	}
-	DevGuard dg(d->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	if (ensure_uploaded(d) != 0) return -1;
-	WalkArgs a = d->proto;
-	a.base = static_cast<const uint8_t *>(d_base);
-	a.stride = 0;
-	a.len = nullptr;
-	a.off = d_off;
-	a.off32 = d_off == nullptr ? d_off32 : nullptr;
-	a.n = n;
-	a.end_out = d_end_out;
-	a.bitmap = d_accept_bitmap;
-	const bool lenonly = d_off == nullptr && d_off32 == nullptr;
-	/* ONE critical section over the pre-pass, the walk and the "block busy until here" event: another host thread's call on
-	 * this dfa must not refill the tile-base block between them (the mutex is recursive: the three take it again) */
-	DfaLock lk(const_cast<fsm_hip_dfa *>(d)->mu);
-	if (lenonly) {
-		a.len = d_len;
-		if (tile_bases(const_cast<fsm_hip_dfa *>(d), d_len, n, s, &a.tbase) != 0) return -1;
-	}
-	const int r = launch_walk(d, a, false, s, hint);
-	if (lenonly) tile_bases_done(const_cast<fsm_hip_dfa *>(d), s);
-	return r;
-}
-
-static int exec_offsets_device(const struct fsm_hip_dfa *d,
-	const void *d_base, const uint64_t *d_off, size_t n,
-	uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream, const BatchHint &hint)
-{
-	if (n != 0 && d_off == nullptr) { errno = EINVAL; return -1; }
-	return exec_packed_device(d, d_base, d_off, nullptr, nullptr, n, d_end_out, d_accept_bitmap, hip_stream, hint);
-}
-
+/* inputs packed back to back, located by u64 offsets, u32 offsets, or their lengths alone */
 extern "C" int fsm_hip_exec_batch_offsets_device(const struct fsm_hip_dfa *d,
 	const void *d_base, const uint64_t *d_off, size_t n,
 	uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream)
 {
-	return exec_offsets_device(d, d_base, d_off, n, d_end_out, d_accept_bitmap, hip_stream, BatchHint());
+	Inputs in;
+	if (!Inputs::packed_by(FSM_HIP_META_OFF64, d_base, d_off, n, &in)) { errno = EINVAL; return -1; }
+	return walk_device(d, in, Outputs::ends(d_end_out, d_accept_bitmap), hip_stream, BatchHint(), FRONT_PACKED);
 }
 
 extern "C" int fsm_hip_exec_batch_offsets32_device(const struct fsm_hip_dfa *d,
 	const void *d_base, const uint32_t *d_off32, size_t n,
 	uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream)
 {
-	if (n != 0 && d_off32 == nullptr) { errno = EINVAL; return -1; }
-	return exec_packed_device(d, d_base, nullptr, d_off32, nullptr, n, d_end_out, d_accept_bitmap, hip_stream, BatchHint());
+	Inputs in;
+	if (!Inputs::packed_by(FSM_HIP_META_OFF32, d_base, d_off32, n, &in)) { errno = EINVAL; return -1; }
+	return walk_device(d, in, Outputs::ends(d_end_out, d_accept_bitmap), hip_stream, BatchHint(), FRONT_PACKED);
 }
 
 extern "C" int fsm_hip_exec_batch_lengths_device(const struct fsm_hip_dfa *d,
 	const void *d_base, const uint32_t *d_len, size_t n,
 	uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream)
 {
-	if (n != 0 && d_len == nullptr) { errno = EINVAL; return -1; }
-	return exec_packed_device(d, d_base, nullptr, nullptr, d_len, n, d_end_out, d_accept_bitmap, hip_stream, BatchHint());
+	Inputs in;
+	if (!Inputs::packed_by(FSM_HIP_META_LENGTHS, d_base, d_len, n, &in)) { errno = EINVAL; return -1; }
+	return walk_device(d, in, Outputs::ends(d_end_out, d_accept_bitmap), hip_stream, BatchHint(), FRONT_PACKED);
 }
 
 extern "C" const char *fsm_hip_last_kernel_name(const struct fsm_hip_dfa *d)
@@ -1285,42 +1394,93 @@ struct HostCall {
 	}
 };
 
-static int exec_host(const struct fsm_hip_dfa *d,
-	const unsigned char *base, size_t in_bytes, size_t stride,
-	const uint32_t *len, const uint64_t *off, size_t n,
-	uint32_t *end_out, uint64_t *accept_bitmap, const uint32_t *off32 = nullptr, bool packed_len = false)
+/* A host batch's metadata is checked before anything is staged: offsets non-decreasing, len[i] <= stride, base == NULL only
+ * for a batch without bytes.  *in_bytes: what is staged; *payload: the bytes the inputs themselves hold (rows with lengths:
+ * their sum, not the rows they sit in) */
+static int check_host_inputs(const Inputs &in, size_t *in_bytes, uint64_t *payload)
 {
-	if (d == nullptr) { errno = EINVAL; return -1; }
+	const size_t n = in.n;
+	uint64_t sum = 0;
+	if (!in.packed()) {
+		if (n != 0 && in.base == nullptr && in.stride != 0) return -1;
+		if (in.len != nullptr)
+			for (size_t i = 0; i < n; i++) {
+				if (in.len[i] > in.stride) return -1;
+				sum += in.len[i];
+			}
+		*in_bytes = n * in.stride;
+		*payload = in.len != nullptr ? sum : (uint64_t)*in_bytes;
+		return 0;
+	}
+	if (in.off != nullptr) {
+		for (size_t i = 0; i < n; i++)
+			if (in.off[i + 1] < in.off[i]) return -1;
+		sum = n ? in.off[n] : 0;
+	} else if (in.off32 != nullptr) {
+		for (size_t i = 0; i < n; i++)
+			if (in.off32[i + 1] < in.off32[i]) return -1;
+		sum = n ? in.off32[n] : 0;
+	} else {
+		for (size_t i = 0; i < n; i++) sum += in.len[i];
+	}
+	if (sum != 0 && in.base == nullptr) return -1;
+	*in_bytes = (size_t)sum;
+	*payload = sum;
+	return 0;
+}
+
+/* what a host front knows about its batch (launch_walk picks the kernel from it): the size, and whether the inputs are short
+ * on average -- asked of variable-length batches only */
+static BatchHint host_hint(const fsm_hip_dfa *d, const Inputs &in, size_t in_bytes, uint64_t payload, const FrontTraits &tr)
+{
+	BatchHint hint;
+	hint.bytes = in_bytes;
+	if (in.packed() || in.len != nullptr) {
+		/* a plain walk of packed lines: walk_lines32 is the per-lane kernel (below 4 GiB and 2^29 lines, not the record walk) */
+		const bool l32 = tr.lines32_mean && in.packed() && in_bytes < ((uint64_t)1 << 32) && in.n < 0x1FFFFFF0ull && d->plan.layout != FSM_HIP_LAYOUT_SPARSE;
+		hint.short_mean = payload / in.n < (uint64_t)pick_mean_of(d, l32);
+	}
+	return hint;
+}
+
+/* The host-pointer front of every walk: stage the batch, walk_device on the private stream, bring the outputs back */
+static int walk_host(const fsm_hip_dfa *dc, const Inputs &in, const Outputs &out, const FrontTraits &tr)
+{
+	fsm_hip_dfa *d = const_cast<fsm_hip_dfa *>(dc);
+	const size_t n = in.n;
+	size_t in_bytes = 0;
+	uint64_t payload = 0;
+	if (d == nullptr || check_host_inputs(in, &in_bytes, &payload) != 0) { errno = EINVAL; return -1; }
 	if (n == 0) return 0;
 	DevGuard dg(d->device);
 	if (!dg.ok()) { errno = ENODEV; return -1; }
 	HostCall hc(d);
+	const size_t sets = n * fsm_hip_eager_words(d) * sizeof(uint64_t);
 	/* +32: the generic kernel reads whole aligned 16-byte chunks */
-	const int p_in = hc.add(HostCall::IN, base, nullptr, in_bytes, 32);
-	const int p_len = len ? hc.add(HostCall::IN, len, nullptr, n * sizeof(uint32_t)) : -1;
-	const int p_off = off ? hc.add(HostCall::IN, off, nullptr, (n + 1) * sizeof(uint64_t)) : -1;
-	const int p_off32 = off32 ? hc.add(HostCall::IN, off32, nullptr, (n + 1) * sizeof(uint32_t)) : -1;
-	const int p_end = hc.add(HostCall::OUT, nullptr, end_out, n * sizeof(uint32_t));
-	const int p_bm = hc.add(HostCall::OUT, nullptr, accept_bitmap, ((n + 63) / 64) * sizeof(uint64_t));
+	const int p_in = hc.add(HostCall::IN, in.base, nullptr, in_bytes, 32);
+	const int p_len = in.len ? hc.add(HostCall::IN, in.len, nullptr, n * sizeof(uint32_t)) : -1;
+	const int p_off = in.off ? hc.add(HostCall::IN, in.off, nullptr, (n + 1) * sizeof(uint64_t)) : -1;
+	const int p_off32 = in.off32 ? hc.add(HostCall::IN, in.off32, nullptr, (n + 1) * sizeof(uint32_t)) : -1;
+	const int p_st = hc.add(HostCall::INOUT, out.state_io, out.state_io, n * sizeof(uint32_t));
+	const int p_eio = hc.add(HostCall::INOUT, out.eager_io, out.eager_io, sets);
+	const int p_end = hc.add(HostCall::OUT, nullptr, out.end_out, n * sizeof(uint32_t));
+	const int p_bm = hc.add(HostCall::OUT, nullptr, out.bitmap, ((n + 63) / 64) * sizeof(uint64_t));
+	const int p_id = hc.add(HostCall::OUT, nullptr, out.id_out, n * sizeof(uint32_t));
+	const int p_eo = hc.add(HostCall::OUT, nullptr, out.eager_out, sets);
 	if (hc.begin() != 0) return -1;
-	BatchHint hint;
-	hint.bytes = in_bytes;
-	if (off != nullptr || off32 != nullptr || packed_len) {
-		/* a plain walk of packed lines: walk_lines32 is the per-lane kernel (below 4 GiB and 2^29 lines, not the record walk) */
-		const bool l32 = in_bytes < ((uint64_t)1 << 32) && n < 0x1FFFFFF0ull && d->plan.layout != FSM_HIP_LAYOUT_SPARSE;
-		hint.short_mean = in_bytes / n < (size_t)pick_mean_of(d, l32);
-	} else if (len != nullptr) {   /* the average of the lengths, not of the rows they sit in */
-		uint64_t sum = 0;
-		for (size_t i = 0; i < n; i++) sum += len[i];
-		hint.short_mean = sum / n < (uint64_t)pick_mean_of(d, false);
-	}
-	if (off || off32 || packed_len) {
-		if (exec_packed_device(d, hc.dev<unsigned char>(p_in), hc.dev<uint64_t>(p_off), hc.dev<uint32_t>(p_off32), packed_len ? hc.dev<uint32_t>(p_len) : nullptr, n,
-		                       hc.dev<uint32_t>(p_end), hc.dev<uint64_t>(p_bm), hc.d->hs, hint) != 0) return -1;
-	} else {
-		if (exec_stride_device(d, hc.dev<unsigned char>(p_in), stride, hc.dev<uint32_t>(p_len), n,
-		                       hc.dev<uint32_t>(p_end), hc.dev<uint64_t>(p_bm), hc.d->hs, hint) != 0) return -1;
-	}
+	Inputs din = in;
+	din.base = hc.dev<unsigned char>(p_in);
+	din.len = hc.dev<uint32_t>(p_len);
+	din.off = hc.dev<uint64_t>(p_off);
+	din.off32 = hc.dev<uint32_t>(p_off32);
+	Outputs dout = out;
+	dout.state_io = hc.dev<uint32_t>(p_st);
+	dout.eager_io = hc.dev<uint64_t>(p_eio);
+	dout.end_out = hc.dev<uint32_t>(p_end);
+	dout.bitmap = hc.dev<uint64_t>(p_bm);
+	dout.id_out = hc.dev<uint32_t>(p_id);
+	dout.eager_out = hc.dev<uint64_t>(p_eo);
+	if (walk_device(d, din, dout, d->hs, host_hint(d, in, in_bytes, payload, tr), tr) != 0) return -1;
 	return hc.end();
 }
 
@@ -1328,46 +1488,34 @@ extern "C" int fsm_hip_exec_batch(const struct fsm_hip_dfa *d,
 	const unsigned char *base, size_t stride, const uint32_t *len, size_t n,
 	uint32_t *end_out, uint64_t *accept_bitmap)
 {
-	if (n != 0 && base == nullptr && stride != 0) { errno = EINVAL; return -1; }
-	if (len != nullptr)
-		for (size_t i = 0; i < n; i++)
-			if (len[i] > stride) { errno = EINVAL; return -1; }
-	return exec_host(d, base, n * stride, stride, len, nullptr, n, end_out, accept_bitmap);
+	return walk_host(d, Inputs::rows_or_offsets(base, stride, len, nullptr, n), Outputs::ends(end_out, accept_bitmap), FRONT_ROWS);
 }
 
 extern "C" int fsm_hip_exec_batch_offsets(const struct fsm_hip_dfa *d,
 	const unsigned char *base, const uint64_t *off, size_t n,
 	uint32_t *end_out, uint64_t *accept_bitmap)
 {
-	if (n != 0 && off == nullptr) { errno = EINVAL; return -1; }
-	for (size_t i = 0; i < n; i++)
-		if (off[i + 1] < off[i]) { errno = EINVAL; return -1; }
-	const size_t total = n ? (size_t)off[n] : 0;
-	if (total != 0 && base == nullptr) { errno = EINVAL; return -1; }
-	return exec_host(d, base, total, 0, nullptr, off, n, end_out, accept_bitmap);
+	Inputs in;
+	if (!Inputs::packed_by(FSM_HIP_META_OFF64, base, off, n, &in)) { errno = EINVAL; return -1; }
+	return walk_host(d, in, Outputs::ends(end_out, accept_bitmap), FRONT_PACKED);
 }
 
 extern "C" int fsm_hip_exec_batch_offsets32(const struct fsm_hip_dfa *d,
 	const unsigned char *base, const uint32_t *off32, size_t n,
 	uint32_t *end_out, uint64_t *accept_bitmap)
 {
-	if (n != 0 && off32 == nullptr) { errno = EINVAL; return -1; }
-	for (size_t i = 0; i < n; i++)
-		if (off32[i + 1] < off32[i]) { errno = EINVAL; return -1; }
-	const size_t total = n ? (size_t)off32[n] : 0;
-	if (total != 0 && base == nullptr) { errno = EINVAL; return -1; }
-	return exec_host(d, base, total, 0, nullptr, nullptr, n, end_out, accept_bitmap, off32);
+	Inputs in;
+	if (!Inputs::packed_by(FSM_HIP_META_OFF32, base, off32, n, &in)) { errno = EINVAL; return -1; }
+	return walk_host(d, in, Outputs::ends(end_out, accept_bitmap), FRONT_PACKED);
 }
 
 extern "C" int fsm_hip_exec_batch_lengths(const struct fsm_hip_dfa *d,
 	const unsigned char *base, const uint32_t *len, size_t n,
 	uint32_t *end_out, uint64_t *accept_bitmap)
 {
-	if (n != 0 && len == nullptr) { errno = EINVAL; return -1; }
-	size_t total = 0;
-	for (size_t i = 0; i < n; i++) total += len[i];
-	if (total != 0 && base == nullptr) { errno = EINVAL; return -1; }
-	return exec_host(d, base, total, 0, len, nullptr, n, end_out, accept_bitmap, nullptr, true);
+	Inputs in;
+	if (!Inputs::packed_by(FSM_HIP_META_LENGTHS, base, len, n, &in)) { errno = EINVAL; return -1; }
+	return walk_host(d, in, Outputs::ends(end_out, accept_bitmap), FRONT_PACKED);
 }
 
 extern "C" double fsm_hip_lds_chain_probe_gbps(size_t table_bytes, int waves, int blocks_per_cu, size_t steps, void *d_scratch4, void *hip_stream)
@@ -1916,118 +2064,44 @@ fail:
 	return -1;
 }
 
-static int ids_device(fsm_hip_dfa *d, const void *d_base, size_t stride, const uint32_t *d_len, const uint64_t *d_off, size_t n,
-	int mode, uint32_t *d_id_out, void *hip_stream, const BatchHint &hint)
+static Outputs ids_outputs(int mode, uint32_t *id_out)
 {
-	if (d == nullptr || d_id_out == nullptr || (mode != FSM_HIP_IDS_EARLIEST && mode != FSM_HIP_IDS_RET && mode != FSM_HIP_IDS_ERROR) ||
-	    (n != 0 && d_off == nullptr && d_base == nullptr && stride != 0)) { errno = EINVAL; return -1; }
-	{
-		const fsm_hip_dfa *t = route(d, d_off == nullptr && d_len == nullptr && stride != 0 && stride % 16u == 0 && (reinterpret_cast<uintptr_t>(d_base) % 16u) == 0);
-		if (t != d) return ids_device(const_cast<fsm_hip_dfa *>(t), d_base, stride, d_len, d_off, n, mode, d_id_out, hip_stream, hint);
-	}
-	if (ensure_ids(d) != 0) return -1;
-	if (mode == FSM_HIP_IDS_ERROR) {
-		/* AMBIG_ERROR: an end state with more than one id is refused (print/c.c:67-72 fails the
-		 * print with EINVAL); without such a state it is AMBIG_EARLIEST */
-		if (d->ids_conflict != FSM_HIP_NO_MATCH) { errno = EINVAL; return -1; }
-		mode = FSM_HIP_IDS_EARLIEST;
-	}
-	DevGuard dg(d->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	if (ensure_uploaded(d) != 0) return -1;
-	WalkArgs a = d->proto;
-	a.base = static_cast<const uint8_t *>(d_base);
-	a.stride = d_off ? 0 : stride;
-	a.len = d_off ? nullptr : d_len;
-	a.off = d_off;
-	a.n = n;
-	a.fin2 = mode == FSM_HIP_IDS_EARLIEST ? d->d_fin_earliest : d->d_fin_ret;
-	a.out2 = d_id_out;
-	const bool fast = d_off == nullptr && d_len == nullptr && stride != 0 && stride % 16u == 0 &&
-		(reinterpret_cast<uintptr_t>(d_base) % 16u) == 0 && d->knob_input_mode != IN_GENERIC;
-	return launch_walk(d, a, fast, static_cast<hipStream_t>(hip_stream), hint);
+	Outputs o;
+	o.ids_mode = mode;
+	o.id_out = id_out;
+	return o;
 }
 
-extern "C" int fsm_hip_exec_batch_ids_device(const struct fsm_hip_dfa *dc,
+extern "C" int fsm_hip_exec_batch_ids_device(const struct fsm_hip_dfa *d,
 	const void *d_base, size_t stride, const uint32_t *d_len, size_t n,
 	int mode, uint32_t *d_id_out, void *hip_stream)
 {
-	return ids_device(const_cast<fsm_hip_dfa *>(dc), d_base, stride, d_len, nullptr, n, mode, d_id_out, hip_stream, BatchHint());
+	if (d_id_out == nullptr) { errno = EINVAL; return -1; }
+	return walk_device(d, Inputs::rows_or_offsets(d_base, stride, d_len, nullptr, n), ids_outputs(mode, d_id_out), hip_stream, BatchHint(), FRONT_IDS);
 }
 
-extern "C" int fsm_hip_exec_batch_ids_offsets_device(const struct fsm_hip_dfa *dc,
+extern "C" int fsm_hip_exec_batch_ids_offsets_device(const struct fsm_hip_dfa *d,
 	const void *d_base, const uint64_t *d_off, size_t n,
 	int mode, uint32_t *d_id_out, void *hip_stream)
 {
-	if (n != 0 && d_off == nullptr) { errno = EINVAL; return -1; }
-	return ids_device(const_cast<fsm_hip_dfa *>(dc), d_base, 0, nullptr, d_off, n, mode, d_id_out, hip_stream, BatchHint());
-}
-
-/* what the host fronts know about their batch (launch_walk picks the kernel from it) */
-static BatchHint host_hint(size_t in_bytes, const uint32_t *len, const uint64_t *off, size_t n, int pick_mean)
-{
-	BatchHint hint;
-	hint.bytes = in_bytes;
-	if (n == 0) return hint;
-	if (len != nullptr) {   /* the average of the lengths, not of the rows they sit in */
-		uint64_t sum = 0;
-		for (size_t i = 0; i < n; i++) sum += len[i];
-		hint.short_mean = sum / n < (uint64_t)pick_mean;
-	} else if (off != nullptr) {
-		hint.short_mean = in_bytes / n < (size_t)pick_mean;
-	}
-	return hint;
-}
-
-static int check_host_batch(const unsigned char *base, size_t stride, const uint32_t *len, const uint64_t *off, size_t n, size_t *in_bytes)
-{
-	if (off != nullptr) {
-		for (size_t i = 0; i < n; i++)
-			if (off[i + 1] < off[i]) return -1;
-		*in_bytes = n ? (size_t)off[n] : 0;
-		if (*in_bytes != 0 && base == nullptr) return -1;
-		return 0;
-	}
-	if (n != 0 && base == nullptr && stride != 0) return -1;
-	if (len != nullptr)
-		for (size_t i = 0; i < n; i++)
-			if (len[i] > stride) return -1;
-	*in_bytes = n * stride;
-	return 0;
-}
-
-static int ids_host(const struct fsm_hip_dfa *d, const unsigned char *base, size_t stride, const uint32_t *len, const uint64_t *off, size_t n,
-	int mode, uint32_t *id_out)
-{
-	size_t in_bytes = 0;
-	if (d == nullptr || id_out == nullptr || check_host_batch(base, stride, len, off, n, &in_bytes) != 0) { errno = EINVAL; return -1; }
-	if (n == 0) return 0;
-	DevGuard dg(d->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	HostCall hc(d);
-	const int p_in = hc.add(HostCall::IN, base, nullptr, in_bytes, 32);
-	const int p_len = len ? hc.add(HostCall::IN, len, nullptr, n * sizeof(uint32_t)) : -1;
-	const int p_off = off ? hc.add(HostCall::IN, off, nullptr, (n + 1) * sizeof(uint64_t)) : -1;
-	const int p_out = hc.add(HostCall::OUT, nullptr, id_out, n * sizeof(uint32_t));
-	if (hc.begin() != 0) return -1;
-	if (ids_device(hc.d, hc.dev<unsigned char>(p_in), stride, hc.dev<uint32_t>(p_len), hc.dev<uint64_t>(p_off), n, mode,
-	               hc.dev<uint32_t>(p_out), hc.d->hs, host_hint(in_bytes, len, off, n, pick_mean_of(d, false))) != 0) return -1;
-	return hc.end();
+	if (d_id_out == nullptr || (n != 0 && d_off == nullptr)) { errno = EINVAL; return -1; }
+	return walk_device(d, Inputs::rows_or_offsets(d_base, 0, nullptr, d_off, n), ids_outputs(mode, d_id_out), hip_stream, BatchHint(), FRONT_IDS);
 }
 
 extern "C" int fsm_hip_exec_batch_ids(const struct fsm_hip_dfa *d,
 	const unsigned char *base, size_t stride, const uint32_t *len, size_t n,
 	int mode, uint32_t *id_out)
 {
-	return ids_host(d, base, stride, len, nullptr, n, mode, id_out);
+	if (id_out == nullptr) { errno = EINVAL; return -1; }
+	return walk_host(d, Inputs::rows_or_offsets(base, stride, len, nullptr, n), ids_outputs(mode, id_out), FRONT_IDS);
 }
 
 extern "C" int fsm_hip_exec_batch_ids_offsets(const struct fsm_hip_dfa *d,
 	const unsigned char *base, const uint64_t *off, size_t n,
 	int mode, uint32_t *id_out)
 {
-	if (n != 0 && off == nullptr) { errno = EINVAL; return -1; }
-	return ids_host(d, base, 0, nullptr, off, n, mode, id_out);
+	if (id_out == nullptr || (n != 0 && off == nullptr)) { errno = EINVAL; return -1; }
+	return walk_host(d, Inputs::rows_or_offsets(base, 0, nullptr, off, n), ids_outputs(mode, id_out), FRONT_IDS);
 }
 
 extern "C" int fsm_hip_ids_conflict(const struct fsm_hip_dfa *dc, fsm_state_t *state)
@@ -2094,193 +2168,81 @@ extern "C" int fsm_hip_state_is_absorbing(const struct fsm_hip_dfa *d, uint32_t 
 	return d->plan.old2new[state] >= d->plan.abs_min ? 1 : 0;
 }
 
-static int resume_device(fsm_hip_dfa *d, const void *d_base, size_t stride, const uint32_t *d_len, const uint64_t *d_off, size_t n,
-	uint32_t *d_state_io, uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream, const BatchHint &hint,
-	const uint32_t *d_off32 = nullptr, bool lens_only = false, uint64_t *d_eager_io = nullptr)
+static Outputs resume_outputs(uint32_t *state_io, uint32_t *end_out, uint64_t *bitmap, uint64_t *eager_io)
 {
-	if (d == nullptr || d_state_io == nullptr || (n != 0 && d_off == nullptr && d_off32 == nullptr && !lens_only && d_base == nullptr && stride != 0) ||
-	    (lens_only && n != 0 && d_len == nullptr)) { errno = EINVAL; return -1; }
-	if (n == 0) return 0;
-	{
-		const fsm_hip_dfa *t = route(d, false);     /* (a resumed walk never takes the fixed-stride kernels of the pair table) */
-		if (t != d) return resume_device(const_cast<fsm_hip_dfa *>(t), d_base, stride, d_len, d_off, n, d_state_io, d_end_out, d_accept_bitmap, hip_stream, hint, d_off32, lens_only, d_eager_io);
-	}
-	if (ensure_resume(d) != 0) return -1;
-	DevGuard dg(d->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	if (ensure_uploaded(d) != 0) return -1;
-	WalkArgs a = d->proto;
-	const bool packed = d_off != nullptr || d_off32 != nullptr || lens_only;
-	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	a.base = static_cast<const uint8_t *>(d_base);
-	a.stride = packed ? 0 : stride;
-	a.len = d_off != nullptr || d_off32 != nullptr ? nullptr : d_len;
-	a.off = d_off;
-	a.off32 = d_off == nullptr ? d_off32 : nullptr;
-	a.n = n;
-	a.end_out = d_end_out;
-	a.bitmap = d_accept_bitmap;
-	a.state_io = d_state_io;
-	a.enc_of = d->d_enc_of;
-	a.orig_of = d->d_orig_of;
-	a.nstates = d->plan.nstates;
-	/* eager sets carried across pieces (OR-ed into, never cleared); where no state emits, the plain resumed walk leaves them as they are */
-	if (d_eager_io != nullptr && !d->plan.emask.empty()) a.eager_out = d_eager_io;
-	const bool lo = lens_only && d_off == nullptr && d_off32 == nullptr;
-	DfaLock lk(d->mu);   /* pre-pass, walk and the block's event in one critical section (see exec_packed_device) */
-	if (lo && tile_bases(d, d_len, n, s, &a.tbase) != 0) return -1;
-	const bool fast = !packed && d_len == nullptr && stride != 0 && stride % 16u == 0 &&
-		(reinterpret_cast<uintptr_t>(d_base) % 16u) == 0 && d->knob_input_mode != IN_GENERIC;
-	const int r = launch_walk(d, a, fast, s, hint);
-	if (lo) tile_bases_done(d, s);
-	return r;
+	Outputs o = Outputs::ends(end_out, bitmap);
+	o.state_io = state_io;
+	o.eager_io = eager_io;
+	return o;
+}
+
+extern "C" int fsm_hip_exec_batch_resume_device(const struct fsm_hip_dfa *d,
+	const void *d_base, size_t stride, const uint32_t *d_len, size_t n,
+	uint32_t *d_state_io, uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream)
+{
+	if (d_state_io == nullptr) { errno = EINVAL; return -1; }
+	return walk_device(d, Inputs::rows_or_offsets(d_base, stride, d_len, nullptr, n), resume_outputs(d_state_io, d_end_out, d_accept_bitmap, nullptr), hip_stream, BatchHint(), FRONT_RESUME);
+}
+
+extern "C" int fsm_hip_exec_batch_resume_offsets_device(const struct fsm_hip_dfa *d,
+	const void *d_base, const uint64_t *d_off, size_t n,
+	uint32_t *d_state_io, uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream)
+{
+	if (d_state_io == nullptr || (n != 0 && d_off == nullptr)) { errno = EINVAL; return -1; }
+	return walk_device(d, Inputs::rows_or_offsets(d_base, 0, nullptr, d_off, n), resume_outputs(d_state_io, d_end_out, d_accept_bitmap, nullptr), hip_stream, BatchHint(), FRONT_RESUME);
 }
 
 /* resume over packed inputs whose metadata is u64 offsets, u32 offsets or lengths alone: the carry of fsm_vm_match_file
  * (src/libfsm/vm.c:188-216: the state survives from one buffer to the next) for batches in the compact forms */
-extern "C" int fsm_hip_exec_batch_resume_packed_device(const struct fsm_hip_dfa *dc,
+extern "C" int fsm_hip_exec_batch_resume_packed_device(const struct fsm_hip_dfa *d,
 	const void *d_base, int meta_form, const void *d_meta, size_t n,
 	uint32_t *d_state_io, uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream)
 {
-	fsm_hip_dfa *d = const_cast<fsm_hip_dfa *>(dc);
-	if (n != 0 && d_meta == nullptr) { errno = EINVAL; return -1; }
-	switch (meta_form) {
-	case FSM_HIP_META_OFF64:
-		return resume_device(d, d_base, 0, nullptr, static_cast<const uint64_t *>(d_meta), n, d_state_io, d_end_out, d_accept_bitmap, hip_stream, BatchHint());
-	case FSM_HIP_META_OFF32:
-		return resume_device(d, d_base, 0, nullptr, nullptr, n, d_state_io, d_end_out, d_accept_bitmap, hip_stream, BatchHint(), static_cast<const uint32_t *>(d_meta), false);
-	case FSM_HIP_META_LENGTHS:
-		return resume_device(d, d_base, 0, static_cast<const uint32_t *>(d_meta), nullptr, n, d_state_io, d_end_out, d_accept_bitmap, hip_stream, BatchHint(), nullptr, true);
-	default:
-		errno = EINVAL;
-		return -1;
-	}
-}
-
-extern "C" int fsm_hip_exec_batch_resume_packed(const struct fsm_hip_dfa *d,
-	const unsigned char *base, int meta_form, const void *meta, size_t n,
-	uint32_t *state_io, uint32_t *end_out)
-{
-	if (d == nullptr || state_io == nullptr || (n != 0 && meta == nullptr) ||
-	    (meta_form != FSM_HIP_META_OFF64 && meta_form != FSM_HIP_META_OFF32 && meta_form != FSM_HIP_META_LENGTHS)) { errno = EINVAL; return -1; }
-	if (n == 0) return 0;
-	size_t in_bytes = 0, meta_bytes = 0;
-	if (meta_form == FSM_HIP_META_OFF64) {
-		const uint64_t *o = static_cast<const uint64_t *>(meta);
-		for (size_t i = 0; i < n; i++) if (o[i + 1] < o[i]) { errno = EINVAL; return -1; }
-		in_bytes = (size_t)o[n]; meta_bytes = (n + 1) * sizeof(uint64_t);
-	} else if (meta_form == FSM_HIP_META_OFF32) {
-		const uint32_t *o = static_cast<const uint32_t *>(meta);
-		for (size_t i = 0; i < n; i++) if (o[i + 1] < o[i]) { errno = EINVAL; return -1; }
-		in_bytes = o[n]; meta_bytes = (n + 1) * sizeof(uint32_t);
-	} else {
-		const uint32_t *l = static_cast<const uint32_t *>(meta);
-		uint64_t sum = 0;
-		for (size_t i = 0; i < n; i++) sum += l[i];
-		in_bytes = (size_t)sum; meta_bytes = n * sizeof(uint32_t);
-	}
-	if (in_bytes != 0 && base == nullptr) { errno = EINVAL; return -1; }
-	DevGuard dg(d->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	HostCall hc(d);
-	const int p_in = hc.add(HostCall::IN, base, nullptr, in_bytes, 32);
-	const int p_meta = hc.add(HostCall::IN, meta, nullptr, meta_bytes);
-	const int p_st = hc.add(HostCall::INOUT, state_io, state_io, n * sizeof(uint32_t));
-	const int p_end = hc.add(HostCall::OUT, nullptr, end_out, n * sizeof(uint32_t));
-	if (hc.begin() != 0) return -1;
-	BatchHint hint;
-	hint.bytes = in_bytes;
-	hint.short_mean = in_bytes / n < (size_t)pick_mean_of(d, false);
-	const void *dm = hc.dev<unsigned char>(p_meta);
-	if (resume_device(hc.d, hc.dev<unsigned char>(p_in), 0, meta_form == FSM_HIP_META_LENGTHS ? static_cast<const uint32_t *>(dm) : nullptr,
-	                  meta_form == FSM_HIP_META_OFF64 ? static_cast<const uint64_t *>(dm) : nullptr, n,
-	                  hc.dev<uint32_t>(p_st), hc.dev<uint32_t>(p_end), nullptr, hc.d->hs, hint,
-	                  meta_form == FSM_HIP_META_OFF32 ? static_cast<const uint32_t *>(dm) : nullptr, meta_form == FSM_HIP_META_LENGTHS) != 0) return -1;
-	return hc.end();
-}
-
-extern "C" int fsm_hip_exec_batch_resume_device(const struct fsm_hip_dfa *dc,
-	const void *d_base, size_t stride, const uint32_t *d_len, size_t n,
-	uint32_t *d_state_io, uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream)
-{
-	return resume_device(const_cast<fsm_hip_dfa *>(dc), d_base, stride, d_len, nullptr, n, d_state_io, d_end_out, d_accept_bitmap, hip_stream, BatchHint());
-}
-
-extern "C" int fsm_hip_exec_batch_resume_offsets_device(const struct fsm_hip_dfa *dc,
-	const void *d_base, const uint64_t *d_off, size_t n,
-	uint32_t *d_state_io, uint32_t *d_end_out, uint64_t *d_accept_bitmap, void *hip_stream)
-{
-	if (n != 0 && d_off == nullptr) { errno = EINVAL; return -1; }
-	return resume_device(const_cast<fsm_hip_dfa *>(dc), d_base, 0, nullptr, d_off, n, d_state_io, d_end_out, d_accept_bitmap, hip_stream, BatchHint());
-}
-
-static int resume_host(const struct fsm_hip_dfa *d, const unsigned char *base, size_t stride, const uint32_t *len, const uint64_t *off, size_t n,
-	uint32_t *state_io, uint32_t *end_out)
-{
-	size_t in_bytes = 0;
-	if (d == nullptr || state_io == nullptr || check_host_batch(base, stride, len, off, n, &in_bytes) != 0) { errno = EINVAL; return -1; }
-	if (n == 0) return 0;
-	DevGuard dg(d->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	HostCall hc(d);
-	const int p_in = hc.add(HostCall::IN, base, nullptr, in_bytes, 32);
-	const int p_len = len ? hc.add(HostCall::IN, len, nullptr, n * sizeof(uint32_t)) : -1;
-	const int p_off = off ? hc.add(HostCall::IN, off, nullptr, (n + 1) * sizeof(uint64_t)) : -1;
-	const int p_st = hc.add(HostCall::INOUT, state_io, state_io, n * sizeof(uint32_t));
-	const int p_end = hc.add(HostCall::OUT, nullptr, end_out, n * sizeof(uint32_t));
-	if (hc.begin() != 0) return -1;
-	if (resume_device(hc.d, hc.dev<unsigned char>(p_in), stride, hc.dev<uint32_t>(p_len), hc.dev<uint64_t>(p_off), n,
-	                  hc.dev<uint32_t>(p_st), hc.dev<uint32_t>(p_end), nullptr, hc.d->hs, host_hint(in_bytes, len, off, n, pick_mean_of(d, false))) != 0) return -1;
-	return hc.end();
+	Inputs in;
+	if (d_state_io == nullptr || !Inputs::packed_by(meta_form, d_base, d_meta, n, &in)) { errno = EINVAL; return -1; }
+	return walk_device(d, in, resume_outputs(d_state_io, d_end_out, d_accept_bitmap, nullptr), hip_stream, BatchHint(), FRONT_RESUME);
 }
 
 extern "C" int fsm_hip_exec_batch_resume(const struct fsm_hip_dfa *d,
 	const unsigned char *base, size_t stride, const uint32_t *len, size_t n,
 	uint32_t *state_io, uint32_t *end_out)
 {
-	return resume_host(d, base, stride, len, nullptr, n, state_io, end_out);
+	if (state_io == nullptr) { errno = EINVAL; return -1; }
+	return walk_host(d, Inputs::rows_or_offsets(base, stride, len, nullptr, n), resume_outputs(state_io, end_out, nullptr, nullptr), FRONT_RESUME);
 }
 
 extern "C" int fsm_hip_exec_batch_resume_offsets(const struct fsm_hip_dfa *d,
 	const unsigned char *base, const uint64_t *off, size_t n,
 	uint32_t *state_io, uint32_t *end_out)
 {
-	if (n != 0 && off == nullptr) { errno = EINVAL; return -1; }
-	return resume_host(d, base, 0, nullptr, off, n, state_io, end_out);
+	if (state_io == nullptr || (n != 0 && off == nullptr)) { errno = EINVAL; return -1; }
+	return walk_host(d, Inputs::rows_or_offsets(base, 0, nullptr, off, n), resume_outputs(state_io, end_out, nullptr, nullptr), FRONT_RESUME);
+}
+
+extern "C" int fsm_hip_exec_batch_resume_packed(const struct fsm_hip_dfa *d,
+	const unsigned char *base, int meta_form, const void *meta, size_t n,
+	uint32_t *state_io, uint32_t *end_out)
+{
+	Inputs in;
+	if (state_io == nullptr || !Inputs::packed_by(meta_form, base, meta, n, &in)) { errno = EINVAL; return -1; }
+	return walk_host(d, in, resume_outputs(state_io, end_out, nullptr, nullptr), FRONT_RESUME);
 }
 
 /* resume + eager outputs: the carry of fsm_vm_match_file with fsm_exec's callback installed (exec.c:126-151) */
-extern "C" int fsm_hip_exec_batch_eager_resume_device(const struct fsm_hip_dfa *dc,
+extern "C" int fsm_hip_exec_batch_eager_resume_device(const struct fsm_hip_dfa *d,
 	const void *d_base, size_t stride, const uint32_t *d_len, const uint64_t *d_off, size_t n,
 	uint32_t *d_state_io, uint32_t *d_end_out, uint64_t *d_eager_io, void *hip_stream)
 {
-	if (dc == nullptr || d_state_io == nullptr || d_eager_io == nullptr) { errno = EINVAL; return -1; }
-	return resume_device(const_cast<fsm_hip_dfa *>(dc), d_base, d_off != nullptr ? 0 : stride, d_off != nullptr ? nullptr : d_len, d_off, n,
-	                     d_state_io, d_end_out, nullptr, hip_stream, BatchHint(), nullptr, false, d_eager_io);
+	if (d_state_io == nullptr || d_eager_io == nullptr) { errno = EINVAL; return -1; }
+	return walk_device(d, Inputs::rows_or_offsets(d_base, stride, d_len, d_off, n), resume_outputs(d_state_io, d_end_out, nullptr, d_eager_io), hip_stream, BatchHint(), FRONT_RESUME);
 }
 
 extern "C" int fsm_hip_exec_batch_eager_resume(const struct fsm_hip_dfa *d,
 	const unsigned char *base, size_t stride, const uint32_t *len, const uint64_t *off, size_t n,
 	uint32_t *state_io, uint32_t *end_out, uint64_t *eager_io)
 {
-	size_t in_bytes = 0;
-	if (off != nullptr) { stride = 0; len = nullptr; }
-	if (d == nullptr || state_io == nullptr || eager_io == nullptr || check_host_batch(base, stride, len, off, n, &in_bytes) != 0) { errno = EINVAL; return -1; }
-	if (n == 0) return 0;
-	DevGuard dg(d->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	HostCall hc(d);
-	const int p_in = hc.add(HostCall::IN, base, nullptr, in_bytes, 32);
-	const int p_len = len ? hc.add(HostCall::IN, len, nullptr, n * sizeof(uint32_t)) : -1;
-	const int p_off = off ? hc.add(HostCall::IN, off, nullptr, (n + 1) * sizeof(uint64_t)) : -1;
-	const int p_st = hc.add(HostCall::INOUT, state_io, state_io, n * sizeof(uint32_t));
-	const int p_eo = hc.add(HostCall::INOUT, eager_io, eager_io, n * fsm_hip_eager_words(d) * sizeof(uint64_t));
-	const int p_end = hc.add(HostCall::OUT, nullptr, end_out, n * sizeof(uint32_t));
-	if (hc.begin() != 0) return -1;
-	if (resume_device(hc.d, hc.dev<unsigned char>(p_in), stride, hc.dev<uint32_t>(p_len), hc.dev<uint64_t>(p_off), n,
-	                  hc.dev<uint32_t>(p_st), hc.dev<uint32_t>(p_end), nullptr, hc.d->hs, host_hint(in_bytes, len, off, n, pick_mean_of(d, false)),
-	                  nullptr, false, hc.dev<uint64_t>(p_eo)) != 0) return -1;
-	return hc.end();
+	if (state_io == nullptr || eager_io == nullptr) { errno = EINVAL; return -1; }
+	return walk_host(d, Inputs::rows_or_offsets(base, stride, len, off, n), resume_outputs(state_io, end_out, nullptr, eager_io), FRONT_RESUME);
 }
 
 /* ------------------------------------------------------------------ */
@@ -2303,118 +2265,62 @@ extern "C" uint32_t fsm_hip_eager_id(const struct fsm_hip_dfa *d, unsigned bit)
 	return d->plan.eager_ids[bit];
 }
 
-static int eager_device(const struct fsm_hip_dfa *d, const void *d_base, size_t stride, const uint32_t *d_len, const uint64_t *d_off, size_t n,
-	uint32_t *d_end_out, uint64_t *d_eager_out, void *hip_stream, const BatchHint &hint)
+static Outputs eager_outputs(uint32_t *end_out, uint64_t *eager_out)
 {
-	if (d == nullptr || d_eager_out == nullptr || (n != 0 && d_off == nullptr && d_base == nullptr && stride != 0)) { errno = EINVAL; return -1; }
-	DevGuard dg(d->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	if (d->plan.emask.empty()) {
-		/* no state emits anything: the answer is all zeros, the walk is the plain one */
-		hipError_t e = zero_async(d_eager_out, n * sizeof(uint64_t), static_cast<hipStream_t>(hip_stream));
-		if (e != hipSuccess) { errno = hip_errno(e); return -1; }
-		if (d_off != nullptr) return exec_offsets_device(d, d_base, d_off, n, d_end_out, nullptr, hip_stream, hint);
-		return exec_stride_device(d, d_base, stride, d_len, n, d_end_out, nullptr, hip_stream, hint);
-	}
-	if (d->plan.eager_words > 1) {
-		/* wide sets are OR-ed in place by the kernel: start from zero */
-		hipError_t e = zero_async(d_eager_out, n * d->plan.eager_words * sizeof(uint64_t), static_cast<hipStream_t>(hip_stream));
-		if (e != hipSuccess) { errno = hip_errno(e); return -1; }
-	}
-	if (ensure_uploaded(d) != 0) return -1;
-	WalkArgs a = d->proto;
-	a.base = static_cast<const uint8_t *>(d_base);
-	a.stride = d_off ? 0 : stride;
-	a.len = d_off ? nullptr : d_len;
-	a.off = d_off;
-	a.n = n;
-	a.end_out = d_end_out;
-	a.eager_out = d_eager_out;
-	const bool fast = d_off == nullptr && d_len == nullptr && stride != 0 && stride % 16u == 0 &&
-		(reinterpret_cast<uintptr_t>(d_base) % 16u) == 0 && d->knob_input_mode != IN_GENERIC;
-	return launch_walk(d, a, fast, static_cast<hipStream_t>(hip_stream), hint);
+	Outputs o = Outputs::ends(end_out, nullptr);
+	o.eager_out = eager_out;
+	return o;
 }
 
 extern "C" int fsm_hip_exec_batch_eager_device(const struct fsm_hip_dfa *d,
 	const void *d_base, size_t stride, const uint32_t *d_len, size_t n,
 	uint32_t *d_end_out, uint64_t *d_eager_out, void *hip_stream)
 {
-	return eager_device(d, d_base, stride, d_len, nullptr, n, d_end_out, d_eager_out, hip_stream, BatchHint());
+	if (d_eager_out == nullptr) { errno = EINVAL; return -1; }
+	return walk_device(d, Inputs::rows_or_offsets(d_base, stride, d_len, nullptr, n), eager_outputs(d_end_out, d_eager_out), hip_stream, BatchHint(), FRONT_EAGER);
 }
 
 extern "C" int fsm_hip_exec_batch_eager_offsets_device(const struct fsm_hip_dfa *d,
 	const void *d_base, const uint64_t *d_off, size_t n,
 	uint32_t *d_end_out, uint64_t *d_eager_out, void *hip_stream)
 {
-	if (n != 0 && d_off == nullptr) { errno = EINVAL; return -1; }
-	return eager_device(d, d_base, 0, nullptr, d_off, n, d_end_out, d_eager_out, hip_stream, BatchHint());
+	if (d_eager_out == nullptr || (n != 0 && d_off == nullptr)) { errno = EINVAL; return -1; }
+	return walk_device(d, Inputs::rows_or_offsets(d_base, 0, nullptr, d_off, n), eager_outputs(d_end_out, d_eager_out), hip_stream, BatchHint(), FRONT_EAGER);
+}
+
+extern "C" int fsm_hip_exec_batch_eager(const struct fsm_hip_dfa *d,
+	const unsigned char *base, size_t stride, const uint32_t *len, size_t n,
+	uint32_t *end_out, uint64_t *eager_out)
+{
+	if (eager_out == nullptr) { errno = EINVAL; return -1; }
+	return walk_host(d, Inputs::rows_or_offsets(base, stride, len, nullptr, n), eager_outputs(end_out, eager_out), FRONT_EAGER);
+}
+
+extern "C" int fsm_hip_exec_batch_eager_offsets(const struct fsm_hip_dfa *d,
+	const unsigned char *base, const uint64_t *off, size_t n,
+	uint32_t *end_out, uint64_t *eager_out)
+{
+	if (eager_out == nullptr || (n != 0 && off == nullptr)) { errno = EINVAL; return -1; }
+	return walk_host(d, Inputs::rows_or_offsets(base, 0, nullptr, off, n), eager_outputs(end_out, eager_out), FRONT_EAGER);
+}
+
+static Outputs all_outputs(uint32_t *end_out, uint64_t *bitmap, int ids_mode, uint32_t *id_out, uint64_t *eager_out)
+{
+	Outputs o = Outputs::ends(end_out, bitmap);
+	o.ids_mode = ids_mode;
+	o.id_out = id_out;
+	o.eager_out = eager_out;
+	return o;
 }
 
 /* Every output of one batch from ONE walk: end states and / or the accept bitmap, device-side end-ids (ids_mode, d_id_out) and
- * eager sets (d_eager_out), whichever are asked for -- the walk kernels write all of them in one pass (the multi-device front used
- * to launch one walk per output) */
-static int all_device(const struct fsm_hip_dfa *dc,
-	const void *d_base, size_t stride, const uint32_t *d_len, const uint64_t *d_off, const uint32_t *d_off32, bool lens_only, size_t n,
-	uint32_t *d_end_out, uint64_t *d_accept_bitmap, int ids_mode, uint32_t *d_id_out, uint64_t *d_eager_out, void *hip_stream, const BatchHint &hint)
-{
-	fsm_hip_dfa *d = const_cast<fsm_hip_dfa *>(dc);
-	const bool packed = d_off != nullptr || d_off32 != nullptr || lens_only;
-	if (d == nullptr || (n != 0 && !packed && d_base == nullptr && stride != 0) || (d_off != nullptr && d_len != nullptr) ||
-	    (lens_only && n != 0 && d_len == nullptr)) { errno = EINVAL; return -1; }
-	{
-		const fsm_hip_dfa *t = route(d, !packed && d_len == nullptr && stride != 0 && stride % 16u == 0 && (reinterpret_cast<uintptr_t>(d_base) % 16u) == 0);
-		if (t != d) return all_device(t, d_base, stride, d_len, d_off, d_off32, lens_only, n, d_end_out, d_accept_bitmap, ids_mode, d_id_out, d_eager_out, hip_stream, hint);
-	}
-	if (d_id_out != nullptr) {
-		if (ids_mode != FSM_HIP_IDS_EARLIEST && ids_mode != FSM_HIP_IDS_RET && ids_mode != FSM_HIP_IDS_ERROR) { errno = EINVAL; return -1; }
-		if (ensure_ids(d) != 0) return -1;
-		if (ids_mode == FSM_HIP_IDS_ERROR) {
-			if (d->ids_conflict != FSM_HIP_NO_MATCH) { errno = EINVAL; return -1; }
-			ids_mode = FSM_HIP_IDS_EARLIEST;
-		}
-	}
-	if (n == 0) return 0;
-	DevGuard dg(d->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	if (ensure_uploaded(d) != 0) return -1;
-	WalkArgs a = d->proto;
-	a.base = static_cast<const uint8_t *>(d_base);
-	a.stride = packed ? 0 : stride;
-	a.len = d_off != nullptr || d_off32 != nullptr ? nullptr : d_len;
-	a.off = d_off;
-	a.off32 = d_off == nullptr ? d_off32 : nullptr;
-	a.n = n;
-	a.end_out = d_end_out;
-	a.bitmap = d_accept_bitmap;
-	if (d_id_out != nullptr) {
-		a.fin2 = ids_mode == FSM_HIP_IDS_EARLIEST ? d->d_fin_earliest : d->d_fin_ret;
-		a.out2 = d_id_out;
-	}
-	if (d_eager_out != nullptr) {
-		if (d->plan.emask.empty() || d->plan.eager_words > 1) {
-			/* no state emits anything: all zeros; wide sets are OR-ed in place: start from zero */
-			const size_t w = d->plan.emask.empty() ? 1 : d->plan.eager_words;
-			hipError_t e = zero_async(d_eager_out, n * w * sizeof(uint64_t), s);
-			if (e != hipSuccess) { errno = hip_errno(e); return -1; }
-		}
-		if (!d->plan.emask.empty()) a.eager_out = d_eager_out;
-	}
-	const bool lo = lens_only && d_off == nullptr && d_off32 == nullptr;
-	DfaLock lk(d->mu);   /* pre-pass, walk and the block's event in one critical section (see exec_packed_device) */
-	if (lo && tile_bases(d, d_len, n, s, &a.tbase) != 0) return -1;
-	const bool fast = !packed && d_len == nullptr && stride != 0 && stride % 16u == 0 &&
-		(reinterpret_cast<uintptr_t>(d_base) % 16u) == 0 && d->knob_input_mode != IN_GENERIC;
-	const int r = launch_walk(d, a, fast, s, hint);
-	if (lo) tile_bases_done(d, s);
-	return r;
-}
-
+ * eager sets (d_eager_out), whichever are asked for (the multi-device front used to launch one walk per output) */
 extern "C" int fsm_hip_exec_batch_all_device(const struct fsm_hip_dfa *d,
 	const void *d_base, size_t stride, const uint32_t *d_len, const uint64_t *d_off, size_t n,
 	uint32_t *d_end_out, uint64_t *d_accept_bitmap, int ids_mode, uint32_t *d_id_out, uint64_t *d_eager_out, void *hip_stream)
 {
-	return all_device(d, d_base, stride, d_len, d_off, nullptr, false, n, d_end_out, d_accept_bitmap, ids_mode, d_id_out, d_eager_out, hip_stream, BatchHint());
+	if (d_off != nullptr && d_len != nullptr) { errno = EINVAL; return -1; }
+	return walk_device(d, Inputs::rows_or_offsets(d_base, stride, d_len, d_off, n), all_outputs(d_end_out, d_accept_bitmap, ids_mode, d_id_out, d_eager_out), hip_stream, BatchHint(), FRONT_ALL);
 }
 
 /* the same over packed inputs whose metadata is u64 offsets, u32 offsets or lengths alone */
@@ -2422,18 +2328,9 @@ extern "C" int fsm_hip_exec_batch_packed_all_device(const struct fsm_hip_dfa *d,
 	const void *d_base, int meta_form, const void *d_meta, size_t n,
 	uint32_t *d_end_out, uint64_t *d_accept_bitmap, int ids_mode, uint32_t *d_id_out, uint64_t *d_eager_out, void *hip_stream)
 {
-	if (n != 0 && d_meta == nullptr) { errno = EINVAL; return -1; }
-	switch (meta_form) {
-	case FSM_HIP_META_OFF64:
-		return all_device(d, d_base, 0, nullptr, static_cast<const uint64_t *>(d_meta), nullptr, false, n, d_end_out, d_accept_bitmap, ids_mode, d_id_out, d_eager_out, hip_stream, BatchHint());
-	case FSM_HIP_META_OFF32:
-		return all_device(d, d_base, 0, nullptr, nullptr, static_cast<const uint32_t *>(d_meta), false, n, d_end_out, d_accept_bitmap, ids_mode, d_id_out, d_eager_out, hip_stream, BatchHint());
-	case FSM_HIP_META_LENGTHS:
-		return all_device(d, d_base, 0, static_cast<const uint32_t *>(d_meta), nullptr, nullptr, true, n, d_end_out, d_accept_bitmap, ids_mode, d_id_out, d_eager_out, hip_stream, BatchHint());
-	default:
-		errno = EINVAL;
-		return -1;
-	}
+	Inputs in;
+	if (!Inputs::packed_by(meta_form, d_base, d_meta, n, &in)) { errno = EINVAL; return -1; }
+	return walk_device(d, in, all_outputs(d_end_out, d_accept_bitmap, ids_mode, d_id_out, d_eager_out), hip_stream, BatchHint(), FRONT_ALL);
 }
 
 /* host pointers: the metadata is checked (non-decreasing offsets, the lengths' sum is the batch) */
@@ -2441,78 +2338,9 @@ extern "C" int fsm_hip_exec_batch_packed_all(const struct fsm_hip_dfa *d,
 	const unsigned char *base, int meta_form, const void *meta, size_t n,
 	uint32_t *end_out, uint64_t *accept_bitmap, int ids_mode, uint32_t *id_out, uint64_t *eager_out)
 {
-	if (d == nullptr || (n != 0 && meta == nullptr) || (meta_form != FSM_HIP_META_OFF64 && meta_form != FSM_HIP_META_OFF32 && meta_form != FSM_HIP_META_LENGTHS)) { errno = EINVAL; return -1; }
-	if (n == 0) return 0;
-	size_t in_bytes = 0, meta_bytes = 0;
-	uint64_t sum = 0;
-	if (meta_form == FSM_HIP_META_OFF64) {
-		const uint64_t *o = static_cast<const uint64_t *>(meta);
-		for (size_t i = 0; i < n; i++) if (o[i + 1] < o[i]) { errno = EINVAL; return -1; }
-		in_bytes = (size_t)o[n]; meta_bytes = (n + 1) * sizeof(uint64_t);
-	} else if (meta_form == FSM_HIP_META_OFF32) {
-		const uint32_t *o = static_cast<const uint32_t *>(meta);
-		for (size_t i = 0; i < n; i++) if (o[i + 1] < o[i]) { errno = EINVAL; return -1; }
-		in_bytes = o[n]; meta_bytes = (n + 1) * sizeof(uint32_t);
-	} else {
-		const uint32_t *l = static_cast<const uint32_t *>(meta);
-		for (size_t i = 0; i < n; i++) sum += l[i];
-		in_bytes = (size_t)sum; meta_bytes = n * sizeof(uint32_t);
-	}
-	if (in_bytes != 0 && base == nullptr) { errno = EINVAL; return -1; }
-	DevGuard dg(d->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	HostCall hc(d);
-	const int p_in = hc.add(HostCall::IN, base, nullptr, in_bytes, 32);
-	const int p_meta = hc.add(HostCall::IN, meta, nullptr, meta_bytes);
-	const int p_end = hc.add(HostCall::OUT, nullptr, end_out, n * sizeof(uint32_t));
-	const int p_bm = hc.add(HostCall::OUT, nullptr, accept_bitmap, ((n + 63) / 64) * sizeof(uint64_t));
-	const int p_id = hc.add(HostCall::OUT, nullptr, id_out, n * sizeof(uint32_t));
-	const int p_eo = hc.add(HostCall::OUT, nullptr, eager_out, n * fsm_hip_eager_words(d) * sizeof(uint64_t));
-	if (hc.begin() != 0) return -1;
-	BatchHint hint;
-	hint.bytes = in_bytes;
-	hint.short_mean = in_bytes / n < (size_t)pick_mean_of(d, false);
-	const void *dm = hc.dev<unsigned char>(p_meta);
-	if (all_device(d, hc.dev<unsigned char>(p_in), 0, meta_form == FSM_HIP_META_LENGTHS ? static_cast<const uint32_t *>(dm) : nullptr,
-	               meta_form == FSM_HIP_META_OFF64 ? static_cast<const uint64_t *>(dm) : nullptr,
-	               meta_form == FSM_HIP_META_OFF32 ? static_cast<const uint32_t *>(dm) : nullptr, meta_form == FSM_HIP_META_LENGTHS, n,
-	               hc.dev<uint32_t>(p_end), hc.dev<uint64_t>(p_bm), ids_mode, hc.dev<uint32_t>(p_id), hc.dev<uint64_t>(p_eo), hc.d->hs, hint) != 0) return -1;
-	return hc.end();
-}
-
-static int eager_host(const struct fsm_hip_dfa *d, const unsigned char *base, size_t stride, const uint32_t *len, const uint64_t *off, size_t n,
-	uint32_t *end_out, uint64_t *eager_out)
-{
-	size_t in_bytes = 0;
-	if (d == nullptr || eager_out == nullptr || check_host_batch(base, stride, len, off, n, &in_bytes) != 0) { errno = EINVAL; return -1; }
-	if (n == 0) return 0;
-	DevGuard dg(d->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	HostCall hc(d);
-	const int p_in = hc.add(HostCall::IN, base, nullptr, in_bytes, 32);
-	const int p_len = len ? hc.add(HostCall::IN, len, nullptr, n * sizeof(uint32_t)) : -1;
-	const int p_off = off ? hc.add(HostCall::IN, off, nullptr, (n + 1) * sizeof(uint64_t)) : -1;
-	const int p_end = hc.add(HostCall::OUT, nullptr, end_out, n * sizeof(uint32_t));
-	const int p_eo = hc.add(HostCall::OUT, nullptr, eager_out, n * fsm_hip_eager_words(d) * sizeof(uint64_t));
-	if (hc.begin() != 0) return -1;
-	if (eager_device(d, hc.dev<unsigned char>(p_in), stride, hc.dev<uint32_t>(p_len), hc.dev<uint64_t>(p_off), n,
-	                 hc.dev<uint32_t>(p_end), hc.dev<uint64_t>(p_eo), hc.d->hs, host_hint(in_bytes, len, off, n, pick_mean_of(d, false))) != 0) return -1;
-	return hc.end();
-}
-
-extern "C" int fsm_hip_exec_batch_eager(const struct fsm_hip_dfa *d,
-	const unsigned char *base, size_t stride, const uint32_t *len, size_t n,
-	uint32_t *end_out, uint64_t *eager_out)
-{
-	return eager_host(d, base, stride, len, nullptr, n, end_out, eager_out);
-}
-
-extern "C" int fsm_hip_exec_batch_eager_offsets(const struct fsm_hip_dfa *d,
-	const unsigned char *base, const uint64_t *off, size_t n,
-	uint32_t *end_out, uint64_t *eager_out)
-{
-	if (n != 0 && off == nullptr) { errno = EINVAL; return -1; }
-	return eager_host(d, base, 0, nullptr, off, n, end_out, eager_out);
+	Inputs in;
+	if (!Inputs::packed_by(meta_form, base, meta, n, &in)) { errno = EINVAL; return -1; }
+	return walk_host(d, in, all_outputs(end_out, accept_bitmap, ids_mode, id_out, eager_out), FRONT_ALL);
 }
 
 /* ---- the emission stream (order and repeats kept): trace_kernel.h ---- */
@@ -2588,8 +2416,9 @@ extern "C" int fsm_hip_exec_batch_eager_trace(const struct fsm_hip_dfa *d,
 	uint32_t *end_out, uint32_t *count_out, uint32_t *ids_out, uint32_t *pos_out)
 {
 	size_t in_bytes = 0;
+	uint64_t payload = 0;
 	if (d == nullptr || count_out == nullptr || (cap != 0 && ids_out == nullptr) || cap > 0xFFFFFFFFu ||
-	    check_host_batch(base, stride, len, off, n, &in_bytes) != 0) { errno = EINVAL; return -1; }
+	    check_host_inputs(Inputs::rows_or_offsets(base, stride, len, off, n), &in_bytes, &payload) != 0) { errno = EINVAL; return -1; }
 	if (n == 0) return 0;
 	if (n > ((size_t)1 << 40) / (cap ? cap : 1)) { errno = EINVAL; return -1; }
 	DevGuard dg(d->device);
