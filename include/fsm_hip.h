@@ -99,7 +99,11 @@ enum {
 	FSM_HIP_LAYOUT_LDSSELF = 8,  /* dense table in LDS + self-loop mask per state (<= 32 classes) */
 	FSM_HIP_LAYOUT_LDS2   = 9,   /* dense table over PAIRS of byte classes in LDS: one lookup per two input bytes (plain walks) */
 	FSM_HIP_LAYOUT_MASK   = 0xf,
-	FSM_HIP_NO_EARLY_RETIRE = 0x10, /* never stop a wavefront early on absorbing states */
+	FSM_HIP_NO_EARLY_RETIRE = 0x10, /* stream every byte of every input: never stop a wavefront early on absorbing states, never leave
+	                                 * out the rest of an input whose state is absorbing.  Without it a plain walk (end states, bitmap,
+	                                 * end-ids) does both, as fsm_exec stops pulling bytes at a missing edge; the eager-output and the
+	                                 * resumed walks only retire whole wavefronts (no test yet shows their id sets / carried states equal
+	                                 * with the per-input skip on).  The results are the same either way. */
 	FSM_HIP_DEFER_UPLOAD  = 0x20    /* plan now, upload the layout's device image at the first call that needs it: a dfa used only
 	                                 * through fsm_hip_exec_multi (a new DFA per retest record, src/retest/main.c:1056) never does */
 };

@@ -27,8 +27,12 @@ enum {
 	FSM_HIP_KNOB_ROWS          = 3,  /* the lazy walk (walk_lazy.h): inputs / slots per lane -- 0 auto (3), 2 = round 5's shape (A/B aid; ignored elsewhere) */
 	FSM_HIP_KNOB_WAVES         = 4,  /* wavefronts per workgroup (1..16)                              */
 	FSM_HIP_KNOB_BLOCKS_PER_CU = 5,  /* persistent grid = CUs * this                                  */
-	FSM_HIP_KNOB_EARLY_RETIRE  = 6,  /* -1: from the dfa's flags; else a bit set -- 1: retire a wavefront whose lanes are all absorbing
-	                                  * (0 = FSM_HIP_NO_EARLY_RETIRE), 2: absorbing lanes stop loading, 4: no chunk skips, 8: no
+	FSM_HIP_KNOB_EARLY_RETIRE  = 6,  /* -1: the dfa's own default -- 0 with FSM_HIP_NO_EARLY_RETIRE; else 3 for a plain walk (end states, bitmap,
+	                                  * end-ids) of an automaton that can reach an absorbing state, 1 for every other automaton and for the
+	                                  * eager and the resumed walks; else a bit set that overrides it (1 = the default before the per-lane
+	                                  * load skip became one, for A/B runs on one build) -- 1: retire a wavefront whose lanes are all absorbing
+	                                  * (0 = FSM_HIP_NO_EARLY_RETIRE), 2: absorbing lanes stop loading (walk_ldsdma, walk_direct_np: fewer
+	                                  * bytes are fetched than matched), 4: no chunk skips, 8: no
 	                                  * absorbing-lane masking, 16: walk_generic always asks for four chunks; measurement / test aids
 	                                  * of the lines kernels: 32: never walk_lines32 (walk_generic's own body, what batches of 4 GiB
 	                                  * and more run), 64: walk_lines32 keeps the first chunk's skip tests, 128: round 4's resource

@@ -481,7 +481,10 @@ static int dfa_upload(fsm_hip_dfa *d)
 		a.tab = d->d_tab;
 		a.fin = d->d_fin;
 		a.btab = d->d_btab;
-		a.early = (flags & FSM_HIP_NO_EARLY_RETIRE) ? 0u : 1u;
+		/* bit 0: a wavefront retires once all its lanes are absorbing; bit 1: an absorbing lane stops fetching its row (what
+		 * fsm_exec does at a missing edge, exec.c:133-138).  Bit 1 costs a ballot per tile: set only where an absorbing
+		 * state can be reached at all (launch_walk clears it again for the eager and the resumed walks) */
+		a.early = (flags & FSM_HIP_NO_EARLY_RETIRE) ? 0u : p.abs_reachable ? 3u : 1u;
 	}
 	HIP_TRY(hipMalloc((void **)&d->d_pick, PICK_FLAGS * sizeof(uint32_t)));
 	HIP_TRY(hipEventCreateWithFlags(&d->tb_scratch_ev, hipEventDisableTiming));
@@ -846,7 +849,10 @@ static int launch_walk(const fsm_hip_dfa *d, WalkArgs a, bool fast_ok, hipStream
 		: c.mode == IN_LAZY_LINES ? ((a.n + FSMHIP_LAZY_PIECE - 1u) / FSMHIP_LAZY_PIECE + c.waves - 1) / c.waves : (ntiles + c.waves - 1) / c.waves;
 	const uint64_t cap = (uint64_t)d->ncu * c.blocks_per_cu;
 	if (nblocks > cap) nblocks = cap;
-	if (d->knob_early >= 0) a.early = (uint32_t)d->knob_early; /* bit 0 wave retire, bit 1 per-lane load skip */
+	/* bit 0 wave retire, bit 1 per-lane load skip: the knob decides, else the dfa's own default -- without bit 1 for the eager and
+	 * the resumed walks, which report more than an end state and have no test of their id sets / carried states with it on */
+	if (d->knob_early >= 0) a.early = (uint32_t)d->knob_early;
+	else if (eager != 0 || a.state_io != nullptr) a.early &= ~2u;
 	if (d->knob_noskip > 0) a.early |= 4u;
 
 	/* Variable-length inputs (the retest / rx front).  Short ones (mean < 96 bytes) walk fastest one per lane with per-lane

@@ -224,6 +224,9 @@ try {
 		for (uint32_t s : q) if (absorbing[s] && s != DEAD && emask_old[s] != 0) p.new2old.push_back(s);
 		p.new2old.push_back(DEAD);
 		p.nabsorbing = S1 - p.abs_min;
+		/* DEAD is always among them; what a walk can use is an absorbing state some input reaches */
+		p.abs_reachable = false;
+		for (uint32_t s = 0; s < S1; s++) if (vis[s] && absorbing[s]) p.abs_reachable = true;
 	}
 	for (uint32_t n = 0; n < S1; n++) p.old2new[p.new2old[n]] = n;
 	p.start = p.old2new[d->start];

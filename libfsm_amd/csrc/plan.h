@@ -27,6 +27,7 @@ struct Plan {
 	uint8_t  cls[256];        /* byte -> class                                 */
 	uint32_t abs_min = 0;     /* renumbered states >= abs_min are absorbing    */
 	uint32_t nabsorbing = 0;
+	bool abs_reachable = false;   /* some absorbing state (DEAD included) can be reached from the start state */
 	std::vector<uint32_t> old2new, new2old;   /* new2old[S1-1] = NO_MATCH (dead) */
 	std::vector<uint32_t> fin;    /* [S1] caller's state id if end state else FSM_HIP_NO_MATCH */
 	std::vector<uint32_t> dense;  /* [S1][C] next (renumbered) state per class */

@@ -1478,6 +1478,10 @@ walk_ldsdma(const WalkArgs a)
 	constexpr uint32_t NDMA = PIECES;           /* DMA instructions per tile: 4 | 8 */
 	constexpr uint32_t ROTSH = SEG == 64 ? 2u : 1u;
 	constexpr uint32_t TILE = 64u * SEG;
+#ifndef FSMHIP_AHEAD0
+#define FSMHIP_AHEAD0 1
+#endif
+	constexpr uint32_t AHEAD0 = FSMHIP_AHEAD0 < PIECES ? FSMHIP_AHEAD0 : PIECES;   /* pieces of a row's first segment walked before its second is requested */
 
 	extern __shared__ __align__(16) unsigned char lds[];
 	Pol pol;
@@ -1522,6 +1526,15 @@ walk_ldsdma(const WalkArgs a)
 				w[p][0] = *reinterpret_cast<const u32x4 *>(rd + ((p + rot) & (PIECES - 1u)) * 16u);
 			__builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0): tile is in registers, slot reusable */
 			__asm__ volatile("" ::: "memory");
+			/* The first segment under the per-lane load skip: its first AHEAD0 pieces are walked BEFORE the second segment is asked
+			 * for, so that a row which dies in its first 16 * AHEAD0 bytes (random text against anchored patterns: every such row)
+			 * costs one segment, not two, and a tile whose 64 rows all die there 8 KiB, not 16.  The tile is in registers by now;
+			 * what the request waits for is one piece's walk.  From the second segment on the request goes out first, as before. */
+			const bool ahead = AHEAD0 != 0u && s == 0 && (a.early & 2u);
+			if (ahead) {
+#pragma unroll
+				for (uint32_t p = 0; p < AHEAD0; p++) step16<Pol, 1>(pol, st, w[p]);
+			}
 			if (s + 1 < nseg) {
 				if (a.early & 2u) {
 					/* A lane in an absorbing state stops reading its row, as fsm_exec stops pulling bytes at a
@@ -1541,8 +1554,13 @@ walk_ldsdma(const WalkArgs a)
 						                                 (lds_void_t *)(stg + j * 1024u), 16, 0, AUX);
 				}
 			}
+			if (ahead) {
 #pragma unroll
-			for (uint32_t p = 0; p < PIECES; p++) step16<Pol, 1>(pol, st, w[p]);
+				for (uint32_t p = AHEAD0; p < PIECES; p++) step16<Pol, 1>(pol, st, w[p]);
+			} else {
+#pragma unroll
+				for (uint32_t p = 0; p < PIECES; p++) step16<Pol, 1>(pol, st, w[p]);
+			}
 			if ((a.early & 1u) && __all(Pol::code(st[0]) >= a.abs_min)) {
 				__builtin_amdgcn_s_waitcnt(0x0F70); /* drain the prefetch before the tile is reused */
 				break;
