@@ -556,6 +556,33 @@ int fsm_hip_multi_prepare(const struct fsm_hip_dfa *const *dfa, const struct fsm
 	struct fsm_hip_multi_prepared **out);
 int fsm_hip_multi_launch(const struct fsm_hip_multi_prepared *p, void *hip_stream);
 void fsm_hip_multi_prepared_free(struct fsm_hip_multi_prepared *p);
+/* ... with eager-output sets per job: what K automata built by fsm_union_repeated_pattern_group (include/fsm/bool.h:55-75; the
+ * callback of src/libfsm/exec.c:126-144) otherwise need K fsm_hip_exec_batch_eager_offsets calls for -- the reference's
+ * tests/eager_output programs are such a corpus.  eager_out (optional) holds n * fsm_hip_eager_words(dfa[q]) words and receives,
+ * word for word, what fsm_hip_exec_batch_eager_offsets(dfa[q], base, off, n, ...) writes (the encoding of fsm_hip_eager_words /
+ * fsm_hip_eager_id): the start state's outputs fire on every input, the empty one included; nothing fires after a missing edge;
+ * the result is a set, and it is OVERWRITTEN, never OR-ed into (a replayed prepared launch shows nothing of the replay before);
+ * a dfa without eager outputs gets all-zero words (W = 1).  end_out / accept_bitmap / id_out are exactly what
+ * fsm_hip_exec_multi_ids gives, from the same walk; errors as there.  A submission in which some job has eager_out is still ONE
+ * fused launch (the kernel's eager form; jobs without eager_out ride in it and take its plain path), one in which none has is
+ * the launch of fsm_hip_exec_multi_ids.  The eager masks ride in the submission's one copy, as the id tables do: a dfa created
+ * with FSM_HIP_DEFER_UPLOAD still uploads nothing of its own.  Sets of up to 64 ids are collected in registers; wider ones, up to
+ * 16 words (1 024 ids), in the line's own words of eager_out, which the kernel zeroes itself; a job whose automaton has more
+ * than 1 024 eager ids goes through its dfa's own walk (fsm_hip_exec_batch_packed_all*), as the jobs too big to fuse do, with
+ * eager_out passed through.  The prepared form is launched and freed by fsm_hip_multi_launch / fsm_hip_multi_prepared_free. */
+struct fsm_hip_multi_batch_eager {
+	const unsigned char *base;
+	const uint64_t *off;          /* n + 1 */
+	size_t n;
+	uint32_t *end_out;            /* optional */
+	uint64_t *accept_bitmap;      /* optional */
+	uint32_t *id_out;             /* optional, as fsm_hip_multi_batch_ids */
+	uint64_t *eager_out;          /* optional: n * fsm_hip_eager_words(dfa[q]) words */
+};
+int fsm_hip_exec_multi_eager(const struct fsm_hip_dfa *const *dfa, const struct fsm_hip_multi_batch_eager *b, size_t k, int ids_mode);
+int fsm_hip_exec_multi_eager_device(const struct fsm_hip_dfa *const *dfa, const struct fsm_hip_multi_batch_eager *b, size_t k, int ids_mode, void *hip_stream);
+int fsm_hip_multi_prepare_eager(const struct fsm_hip_dfa *const *dfa, const struct fsm_hip_multi_batch_eager *b, size_t k, int ids_mode,
+	struct fsm_hip_multi_prepared **out);
 /* kernels the last fsm_hip_exec_multi* / fsm_hip_multi_launch call of this process launched (1 when every job was small), and how many jobs rode
  * in the fused one */
 unsigned fsm_hip_multi_last_launches(void);

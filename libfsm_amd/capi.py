@@ -624,6 +624,17 @@ class HipDfa:
         bits = np.unpackbits(np.ascontiguousarray(words, np.uint64).view(np.uint8), bitorder="little")[:k].astype(bool)
         return np.array(sorted(self._lib.fsm_hip_eager_id(C.c_void_p(self._h), C.c_uint(b)) for b in np.nonzero(bits)[0]), np.uint32)
 
+    def decode_eager(self, words: np.ndarray) -> list:
+        """n * eager_words() u64 as the eager fronts write them -> per input the ids emitted, ascending (what exec_batch_eager returns)"""
+        W = self.eager_words()
+        eo = np.ascontiguousarray(words, np.uint64).reshape(-1, W)
+        self._lib.fsm_hip_eager_id_count.restype = C.c_size_t
+        self._lib.fsm_hip_eager_id.restype = C.c_uint32
+        k = self._lib.fsm_hip_eager_id_count(C.c_void_p(self._h))
+        ids = np.array([self._lib.fsm_hip_eager_id(C.c_void_p(self._h), C.c_uint(b)) for b in range(k)], np.uint32)
+        bits = np.unpackbits(eo.view(np.uint8).reshape(len(eo), W * 8), axis=1, bitorder="little")[:, :k].astype(bool)
+        return [ids[row] for row in bits]
+
     def exec_batch_eager_resume(self, data: np.ndarray, state_io: np.ndarray, eager_io: np.ndarray, lens: Optional[np.ndarray] = None,
                                 off: Optional[np.ndarray] = None):
         """fsm_hip_exec_batch_eager_resume: one more piece of every input.  data: [n][stride] rows (+ lens), or with off (n + 1
@@ -1093,22 +1104,79 @@ def exec_multi_ids_device(dfas: Sequence["HipDfa"], jobs: Sequence[tuple], ids_m
         raise _oserr("fsm_hip_exec_multi_ids_device")
 
 
+class MultiBatchEager(C.Structure):
+    """struct fsm_hip_multi_batch_eager (include/fsm_hip.h)"""
+    _fields_ = [("base", C.c_void_p), ("off", C.c_void_p), ("n", C.c_size_t), ("end_out", C.c_void_p), ("accept_bitmap", C.c_void_p), ("id_out", C.c_void_p),
+                ("eager_out", C.c_void_p)]
+
+
+def exec_multi_eager(dfas: Sequence["HipDfa"], jobs: Sequence[Sequence[bytes]], ids_mode: int = 1, want_eager: Optional[Sequence[bool]] = None):
+    """fsm_hip_exec_multi_eager: job q = the strings jobs[q] through dfas[q], ONE submission, end-ids and eager-output sets by
+    the device.  Returns [(end, bitmap, ids, sets), ...], sets decoded like exec_batch_eager (one array of emitted ids per
+    string); want_eager[q] = False leaves job q's eager_out NULL (its sets: None)."""
+    lib = load_library()
+    k = len(jobs)
+    keep, arr, outs, raw = [], (MultiBatchEager * max(k, 1))(), [], []
+    for q, strs in enumerate(jobs):
+        n = len(strs)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(x) for x in strs])
+        base = np.frombuffer(b"".join(strs) or b"\0", dtype=np.uint8)
+        end = np.full(n, 0xDEADBEEF, dtype=np.uint32)
+        ids = np.full(n, 0xDEADBEEF, dtype=np.uint32)
+        bm = np.zeros((n + 63) // 64, dtype=np.uint64)
+        eo = np.full((n, dfas[q].eager_words()), 0xDEADBEEFDEADBEEF, dtype=np.uint64) if (want_eager is None or want_eager[q]) else None
+        keep += [off, base, end, bm, ids, eo]
+        arr[q].base, arr[q].off, arr[q].n = base.ctypes.data, off.ctypes.data, n
+        arr[q].end_out, arr[q].accept_bitmap, arr[q].id_out = (end.ctypes.data, bm.ctypes.data, ids.ctypes.data) if n else (None, None, None)
+        arr[q].eager_out = eo.ctypes.data if (eo is not None and n) else None
+        outs.append((end, bm, ids))
+        raw.append(eo)
+    hs = (C.c_void_p * max(k, 1))(*[d._h for d in dfas])
+    C.set_errno(0)
+    if lib.fsm_hip_exec_multi_eager(hs, arr, C.c_size_t(k), C.c_int(ids_mode)) != 0:
+        raise _oserr("fsm_hip_exec_multi_eager")
+    return [(e, m, i, None if eo is None else dfas[q].decode_eager(eo)) for q, ((e, m, i), eo) in enumerate(zip(outs, raw))]
+
+
+def exec_multi_eager_device(dfas: Sequence["HipDfa"], jobs: Sequence[tuple], ids_mode: int = 1, stream: int = 0):
+    """fsm_hip_exec_multi_eager_device: jobs[q] = (d_base, d_off, n, d_end, d_bitmap, d_ids, d_eager) device pointers (0 = NULL);
+    d_eager: n * dfas[q].eager_words() u64."""
+    lib = load_library()
+    k = len(jobs)
+    arr = (MultiBatchEager * max(k, 1))()
+    for q, (b, o, n, e, m, i, g) in enumerate(jobs):
+        arr[q].base, arr[q].off, arr[q].n, arr[q].end_out, arr[q].accept_bitmap, arr[q].id_out, arr[q].eager_out = b or None, o or None, n, e or None, m or None, i or None, g or None
+    hs = (C.c_void_p * max(k, 1))(*[d._h for d in dfas])
+    C.set_errno(0)
+    if lib.fsm_hip_exec_multi_eager_device(hs, arr, C.c_size_t(k), C.c_int(ids_mode), C.c_void_p(stream or None)) != 0:
+        raise _oserr("fsm_hip_exec_multi_eager_device")
+
+
 class MultiPrepared:
     """fsm_hip_multi_prepare / _launch / _prepared_free: a device-pointer submission put on the device once; launch() is
-    one kernel launch on the stream (capturable into a HIP graph).  jobs[q] = (d_base, d_off, n, d_end, d_bitmap, d_ids)."""
+    one kernel launch on the stream (capturable into a HIP graph).  jobs[q] = (d_base, d_off, n, d_end, d_bitmap, d_ids), or
+    -- every job of the submission -- (d_base, d_off, n, d_end, d_bitmap, d_ids, d_eager): fsm_hip_multi_prepare_eager."""
 
     def __init__(self, dfas: Sequence["HipDfa"], jobs: Sequence[tuple], ids_mode: int = 0):
         lib = load_library()
         k = len(jobs)
-        arr = (MultiBatchIds * max(k, 1))()
-        for q, (b, o, n, e, m, i) in enumerate(jobs):
+        eager = k != 0 and len(jobs[0]) == 7
+        if any(len(j) != (7 if eager else 6) for j in jobs):
+            raise ValueError("every job is a 6-tuple, or every job is a 7-tuple")
+        arr = ((MultiBatchEager if eager else MultiBatchIds) * max(k, 1))()
+        for q, j in enumerate(jobs):
+            b, o, n, e, m, i = j[:6]
             arr[q].base, arr[q].off, arr[q].n, arr[q].end_out, arr[q].accept_bitmap, arr[q].id_out = b or None, o or None, n, e or None, m or None, i or None
+            if eager:
+                arr[q].eager_out = j[6] or None
         hs = (C.c_void_p * max(k, 1))(*[d._h for d in dfas])
         self._keep = list(dfas)
         self._p = C.c_void_p()
         C.set_errno(0)
-        if lib.fsm_hip_multi_prepare(hs, arr, C.c_size_t(k), C.c_int(ids_mode), C.byref(self._p)) != 0:
-            raise _oserr("fsm_hip_multi_prepare")
+        fn = "fsm_hip_multi_prepare_eager" if eager else "fsm_hip_multi_prepare"
+        if getattr(lib, fn)(hs, arr, C.c_size_t(k), C.c_int(ids_mode), C.byref(self._p)) != 0:
+            raise _oserr(fn)
 
     def launch(self, stream: int = 0) -> None:
         C.set_errno(0)
