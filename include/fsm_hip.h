@@ -693,6 +693,76 @@ int fsm_hip_node_exec_batch_eager(struct fsm_hip_node *node,
 int fsm_hip_node_exec_multi(struct fsm_hip_node *const *nodes, const struct fsm_hip_multi_batch *b, size_t k);
 
 /* ------------------------------------------------------------------ */
+/* text front: one buffer with a delimiter between records             */
+/* ------------------------------------------------------------------ */
+
+/* Every front above takes inputs the caller has cut already.  A grep-like caller (re(1) over a file, rx, retest's +/- lines,
+ * examples/hipgrep.c) starts from ONE buffer with a delimiter between records.  Lines never contain the delimiter, and every
+ * line but possibly the last is followed by exactly one: in an automaton whose delimiter column is the identity, walking
+ * [off[i], off[i + 1]) of the UNTOUCHED text -- trailing delimiter included -- ends where walking the line alone ends in the
+ * original.  So nothing is squeezed or copied: a delimiter scan on the device leaves the offsets, and the text is a plain
+ * packed batch of the twin automaton. */
+
+/* A copy of desc in which `byte` is a self-loop of every state (free with fsm_hip_desc_free).  States, start, end states,
+ * end-ids and eager ids are unchanged; a range that contains `byte` is split around it, the ranges of a state come out sorted,
+ * neighbours to one target merged.  Applying it twice gives what applying it once gives.  Host arithmetic only: works without
+ * a device.  NULL + EINVAL for byte outside 0..255 or a bad desc (no states, bad ids, overlapping ranges). */
+struct fsm_hip_dfa_desc *fsm_hip_desc_identity_byte(const struct fsm_hip_dfa_desc *desc, int byte);
+
+/* A line matcher: the fsm_hip_dfa built from fsm_hip_desc_identity_byte(desc, delim), and the delimiter it was built for.
+ * flags and errors as fsm_hip_dfa_create (fsm_hip_lines_compile: as fsm_hip_compile).  The inner dfa (borrowed, valid until
+ * fsm_hip_lines_dfa_free) is the handle for fsm_hip_endid_get, fsm_hip_ret_get, fsm_hip_eager_id, fsm_hip_dfa_info,
+ * fsm_hip_last_kernel_ms and tuning: its state ids, end-ids and eager ids are the original's.  The ordered emission stream
+ * (fsm_hip_exec_batch_eager_trace) of the inner dfa sees the delimiter's extra step and is not the original's. */
+struct fsm_hip_lines_dfa;
+struct fsm_hip_lines_dfa *fsm_hip_lines_dfa_create(const struct fsm_hip_dfa_desc *desc, int delim, unsigned flags);
+struct fsm_hip_lines_dfa *fsm_hip_lines_compile(const struct fsm *fsm, int delim, unsigned flags);
+const struct fsm_hip_dfa *fsm_hip_lines_dfa_inner(const struct fsm_hip_lines_dfa *ld);
+int fsm_hip_lines_dfa_delim(const struct fsm_hip_lines_dfa *ld);
+void fsm_hip_lines_dfa_free(struct fsm_hip_lines_dfa *ld);
+
+/* A text: bytes on the device plus the offsets of their lines.  Every delimiter ends a line; bytes after the last delimiter
+ * form a last line iff there are any; an empty text has 0 lines; two delimiters in a row enclose an empty line; any byte value
+ * may be the delimiter (0: grep -z); a '\r' stays part of its line (the rule of examples/hipgrep.c).
+ *   off[0] = 0, off[k] = position of the k-th delimiter + 1, off[n] = nbytes       (n + 1 entries, device memory)
+ * fsm_hip_text_open copies host bytes to the current device once and returns when the offsets are there.
+ * fsm_hip_text_open_device borrows device bytes (any alignment; they must outlive the text and stay as they are); no byte
+ * outside [d_text, d_text + nbytes) is read.  The scan is enqueued on hip_stream, which is synchronised ONCE inside the call
+ * (the line count has to reach the host: it sizes the offsets and, later, the caller's outputs); the kernel that fills the
+ * offsets is still in flight at return -- work enqueued on hip_stream afterwards sees them, another stream has to wait for
+ * hip_stream first.  Not capturable into a HIP graph.  NULL + errno: EINVAL (delim outside 0..255), ENODEV, ENOMEM (a text
+ * that does not fit the device: windows are a later step). */
+struct fsm_hip_text;
+struct fsm_hip_text *fsm_hip_text_open(const void *text, size_t nbytes, int delim);
+struct fsm_hip_text *fsm_hip_text_open_device(const void *d_text, size_t nbytes, int delim, void *hip_stream);
+size_t fsm_hip_text_lines(const struct fsm_hip_text *t);                      /* n */
+const uint64_t *fsm_hip_text_offsets_device(const struct fsm_hip_text *t);   /* n + 1 entries, device memory */
+int fsm_hip_text_offsets(const struct fsm_hip_text *t, uint64_t *off);      /* copy the n + 1 entries out (waits for the scan) */
+void fsm_hip_text_free(struct fsm_hip_text *t);
+/* for tests and probes: bytes one workgroup scans per step; the most workgroups a scan launches on the current device (a
+ * longer text gives every workgroup several consecutive blocks); milliseconds of the three scan kernels of this text, from
+ * HIP events around them (the host's wait between the second and the third is left out; blocks until the scan has finished) */
+size_t fsm_hip_text_block_bytes(void);
+size_t fsm_hip_text_max_workgroups(void);
+double fsm_hip_text_scan_ms(const struct fsm_hip_text *t);
+
+/* Walk every line of the text: the outputs of fsm_hip_exec_batch_packed_all{,_device} for the n = fsm_hip_text_lines(t) lines
+ * WITHOUT their delimiters under the original automaton -- end_out (n), accept_bitmap (ceil(n / 64) words), id_out under
+ * ids_mode (FSM_HIP_IDS_*), eager_out (n * fsm_hip_eager_words(inner) words), whichever are not NULL.  The device form is
+ * one fsm_hip_exec_batch_packed_all_device(inner, d_text, FSM_HIP_META_OFF64, d_off, n, ...) on hip_stream and nothing else
+ * (its contract, HIP graphs included); the host form allocates the outputs on the device, calls it on the text's own stream
+ * and copies back.  One text may be walked by any number of line matchers, also from several host threads: the host form's
+ * calls on ONE text share that text's stream, so they run one after the other and each returns only when the stream is idle
+ * (the answers are each call's own); threads that want to overlap use the device form on streams of their own.  A text
+ * without a delimiter is one line of
+ * nbytes, walked as a long packed input is.  0, or -1 + errno: EINVAL when ld's delimiter differs from t's or they live on
+ * different devices (no output is touched); n == 0 returns 0 and touches no output. */
+int fsm_hip_text_exec(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t,
+	uint32_t *end_out, uint64_t *accept_bitmap, int ids_mode, uint32_t *id_out, uint64_t *eager_out);
+int fsm_hip_text_exec_device(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t,
+	uint32_t *d_end_out, uint64_t *d_accept_bitmap, int ids_mode, uint32_t *d_id_out, uint64_t *d_eager_out, void *hip_stream);
+
+/* ------------------------------------------------------------------ */
 /* synthetic input generator (benchmarks and parity tests)            */
 /* ------------------------------------------------------------------ */
 

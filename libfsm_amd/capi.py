@@ -1326,3 +1326,139 @@ def stream_read_probe_gbps(d_base: int, nbytes: int, d_scratch4: int, reps: int 
     if ms <= 0:
         raise _oserr("fsm_hip_stream_read_probe_ms")
     return nbytes / (ms * 1e-3) / 1e9
+
+
+# ---- the text front: one buffer with a delimiter between records (include/fsm_hip.h) ----
+
+def identity_byte(flat: FlatDfa, byte: int) -> FlatDfa:
+    """fsm_hip_desc_identity_byte: a copy of the description in which `byte` is a self-loop of every state (host arithmetic)."""
+    lib = load_library()
+    lib.fsm_hip_desc_identity_byte.restype = C.POINTER(_Desc)
+    lib.fsm_hip_desc_identity_byte.argtypes = [C.POINTER(_Desc), C.c_int]
+    d = flat.desc()
+    C.set_errno(0)
+    t = lib.fsm_hip_desc_identity_byte(C.byref(d), int(byte))
+    if not t:
+        raise _oserr("fsm_hip_desc_identity_byte")
+    try:
+        return FlatDfa.from_desc(t.contents)
+    finally:
+        lib.fsm_hip_desc_free(t)
+
+
+class LinesDfa:
+    """struct fsm_hip_lines_dfa *: the twin automaton in which the delimiter is a self-loop of every state, and that delimiter.
+    .inner is the HipDfa to ask for end-ids, ret sets, eager ids, info, the last kernel and tuning (borrowed)."""
+
+    def __init__(self, flat: FlatDfa, delim: int = 0x0A, flags: int = 0):
+        self._lib = load_library()
+        self._lib.fsm_hip_lines_dfa_create.restype = C.c_void_p
+        self._lib.fsm_hip_lines_dfa_inner.restype = C.c_void_p
+        d = flat.desc()
+        C.set_errno(0)
+        self._h = self._lib.fsm_hip_lines_dfa_create(C.byref(d), C.c_int(delim), C.c_uint(flags))
+        if not self._h:
+            raise _oserr("fsm_hip_lines_dfa_create")
+        self.inner = HipDfa(handle=self._lib.fsm_hip_lines_dfa_inner(C.c_void_p(self._h)), borrowed=True)
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def delim(self) -> int:
+        return int(self._lib.fsm_hip_lines_dfa_delim(C.c_void_p(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.inner._h = None
+            self._lib.fsm_hip_lines_dfa_free(C.c_void_p(self._h))
+            self._h = None
+
+    __del__ = close
+
+
+class HipText:
+    """struct fsm_hip_text *: bytes on the device plus the offsets of their lines.  data: host bytes (copied once), or
+    d_text = a device address with nbytes (borrowed: it must outlive the text; the scan is enqueued on `stream`)."""
+
+    def __init__(self, data=None, delim: int = 0x0A, *, d_text: int = 0, nbytes: int = 0, stream: int = 0):
+        self._lib = lib = load_library()
+        lib.fsm_hip_text_open.restype = C.c_void_p
+        lib.fsm_hip_text_open_device.restype = C.c_void_p
+        lib.fsm_hip_text_lines.restype = C.c_size_t
+        lib.fsm_hip_text_offsets_device.restype = C.c_void_p
+        lib.fsm_hip_text_scan_ms.restype = C.c_double
+        C.set_errno(0)
+        if data is not None:
+            buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data, dtype=np.uint8)
+            self._h = lib.fsm_hip_text_open(_ptr(buf) if buf.size else None, C.c_size_t(buf.size), C.c_int(delim))
+            what = "fsm_hip_text_open"
+        else:
+            self._h = lib.fsm_hip_text_open_device(C.c_void_p(d_text or None), C.c_size_t(nbytes), C.c_int(delim), C.c_void_p(stream or None))
+            what = "fsm_hip_text_open_device"
+        if not self._h:
+            raise _oserr(what)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.fsm_hip_text_free(C.c_void_p(self._h))
+            self._h = None
+
+    __del__ = close
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def lines(self) -> int:
+        return int(self._lib.fsm_hip_text_lines(C.c_void_p(self._h)))
+
+    @property
+    def d_off(self) -> int:
+        return int(self._lib.fsm_hip_text_offsets_device(C.c_void_p(self._h)) or 0)
+
+    def offsets(self) -> np.ndarray:
+        off = np.empty(self.lines + 1, np.uint64)
+        C.set_errno(0)
+        if self._lib.fsm_hip_text_offsets(C.c_void_p(self._h), _ptr(off)) != 0:
+            raise _oserr("fsm_hip_text_offsets")
+        return off
+
+    def scan_ms(self) -> float:
+        return float(self._lib.fsm_hip_text_scan_ms(C.c_void_p(self._h)))
+
+    def exec(self, ld: LinesDfa, ids_mode: int = 0, want_end=True, want_bitmap=False, want_eager=False, out: Optional[dict] = None):
+        """fsm_hip_text_exec: dict(end=, bitmap=, ids=, eager=) with the outputs asked for (out: arrays to write into instead)."""
+        n = self.lines
+        if out is None:
+            out = {"end": np.empty(n, np.uint32) if want_end else None, "bitmap": np.zeros((n + 63) // 64, np.uint64) if want_bitmap else None,
+                   "ids": np.empty(n, np.uint32) if ids_mode else None,
+                   "eager": np.zeros((n, ld.inner.eager_words()), np.uint64) if want_eager else None}
+        C.set_errno(0)
+        if self._lib.fsm_hip_text_exec(C.c_void_p(ld.handle), C.c_void_p(self._h), _ptr(out.get("end")), _ptr(out.get("bitmap")), C.c_int(ids_mode),
+                                       _ptr(out.get("ids")), _ptr(out.get("eager"))) != 0:
+            raise _oserr("fsm_hip_text_exec")
+        return out
+
+    def exec_device(self, ld: LinesDfa, d_end: int = 0, d_bitmap: int = 0, ids_mode: int = 0, d_ids: int = 0, d_eager: int = 0, stream: int = 0):
+        C.set_errno(0)
+        vp = C.c_void_p
+        if self._lib.fsm_hip_text_exec_device(vp(ld.handle), vp(self._h), vp(d_end or None), vp(d_bitmap or None), C.c_int(ids_mode), vp(d_ids or None),
+                                              vp(d_eager or None), vp(stream or None)) != 0:
+            raise _oserr("fsm_hip_text_exec_device")
+
+
+def text_block_bytes() -> int:
+    """fsm_hip_text_block_bytes: bytes one workgroup of the delimiter scan covers per step."""
+    lib = load_library()
+    lib.fsm_hip_text_block_bytes.restype = C.c_size_t
+    return int(lib.fsm_hip_text_block_bytes())
+
+
+def text_max_workgroups() -> int:
+    """fsm_hip_text_max_workgroups: the most workgroups a scan launches on the current device."""
+    lib = load_library()
+    lib.fsm_hip_text_max_workgroups.restype = C.c_size_t
+    return int(lib.fsm_hip_text_max_workgroups())

@@ -309,6 +309,25 @@ fsm_hip_compile(const struct fsm *fsm, unsigned flags)
 	return dfa;
 }
 
+/* the line matcher of the text front (lines.cpp): flatten, then the twin in which `delim` is a self-loop of every state */
+struct fsm_hip_lines_dfa *
+fsm_hip_lines_compile(const struct fsm *fsm, int delim, unsigned flags)
+{
+	struct fsm_hip_dfa_desc *desc;
+	struct fsm_hip_lines_dfa *ld;
+	int e;
+
+	desc = fsm_hip_flatten(fsm);
+	if (desc == NULL) {
+		return NULL;
+	}
+	ld = fsm_hip_lines_dfa_create(desc, delim, flags);
+	e = errno;
+	fsm_hip_desc_free(desc);
+	errno = e;
+	return ld;
+}
+
 struct fsm_hip_node *
 fsm_hip_node_compile(const struct fsm *fsm, unsigned flags, const int *devices, int ndev)
 {

@@ -1,0 +1,484 @@
+/*
+ * text.hip -- the text front: ONE buffer of bytes with a delimiter between records, cut into lines on the device and walked
+ * in one call.
+ *
+ * Every other front takes inputs the caller has already cut (rows of a stride, or packed bytes with offsets / lengths); a
+ * grep-like caller starts from a file.  examples/hipgrep.c cuts it on one host core, byte by byte, and memmoves every line
+ * to squeeze the newlines out, because off[i] .. off[i + 1] of the untouched buffer would include the '\n'.  Here nothing is
+ * squeezed or copied: the line matcher (lines.cpp) walks an automaton in which the delimiter is a self-loop of every
+ * state, so [off[i], off[i + 1]) of the untouched text -- trailing delimiter included -- is an ordinary packed input of
+ * fsm_hip_exec_batch_packed_all_device, and what remains is the offsets array:
+ *     off[0] = 0, off[k] = position of the k-th delimiter + 1, off[n] = nbytes.
+ * Three passes over a grid of workgroups that each own consecutive BLOCKs of the text:
+ *     text_count    cnt[block] = delimiters in the block          (reads the text)
+ *     text_scan     exclusive u64 scan of cnt[] by one workgroup; the total and "is the last byte a delimiter" for the host
+ *     text_offsets  re-reads the block; rank of a hit = cnt[block] + hits before it in the block; off[1 + rank] = position + 1
+ * The text is read twice.  A single-pass scan with decoupled look-back would read it once, at the price of workgroups that
+ * spin on their predecessors' flags; the second read is cheap next to a hang.
+ * Every global access names its address space (no FLAT instruction, as in the walk kernels: tests/test_abi.py), a lane's 16
+ * bytes are loaded from the text's own first byte whatever its alignment (gfx950 takes any: tools/probes/unaligned_dma.hip), and
+ * no byte outside [text, text + nbytes) is read: the last, partial block assembles its chunks from byte loads.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cerrno>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "../../include/fsm_hip.h"
+
+namespace {
+
+constexpr uint32_t TEXT_WAVES = 4;                          /* wavefronts per workgroup */
+constexpr uint32_t TEXT_THREADS = TEXT_WAVES * 64u;
+constexpr uint32_t TEXT_TILES = 4;                          /* 16-byte loads a lane keeps in flight */
+constexpr uint32_t TEXT_TILE = TEXT_THREADS * 16u;          /* bytes one load instruction of the workgroup covers */
+constexpr uint32_t TEXT_BLOCK = TEXT_TILES * TEXT_TILE;     /* bytes a workgroup scans per step: 16 KiB */
+constexpr uint32_t TEXT_WG_PER_CU = 8;                      /* 8 x 4 wavefronts: a full CU */
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 __attribute__((aligned(1))) u32x4_any;       /* the text starts at any byte */
+typedef const u32x4_any __attribute__((address_space(1))) *glb_chunk_p;
+typedef const unsigned char __attribute__((address_space(1))) *glb_u8p;
+typedef const uint64_t __attribute__((address_space(1))) *glb_u64p;
+typedef uint64_t __attribute__((address_space(1))) *glb_u64w;
+
+/* bit 7 of every byte of x that EQUALS the splat's byte, and of no other.  (x & 0x7f..) + 0x7f.. carries into bit 7 iff the low
+ * seven bits are not all zero and never out of the byte; | x adds the byte's own bit 7.  The shorter (x - 0x01..) & ~x & 0x80..
+ * borrows across bytes and flags a byte 0x01 above a true hit: it must not be used for counting. */
+__device__ __forceinline__ uint32_t eq_bytes(uint32_t x, uint32_t splat)
+{
+	x ^= splat;
+	return ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;
+}
+
+/* bits 7, 15, 23, 31 -> bits 0 .. 3 (the partial products land on distinct bits: nothing carries) */
+__device__ __forceinline__ uint32_t nibble_of(uint32_t m) { return (((m >> 7) * 0x00204081u) >> 21) & 0xfu; }
+
+/* bit k <=> byte k of the lane's 16 bytes is the delimiter */
+__device__ __forceinline__ uint32_t hit_mask16(const u32x4 &v, uint32_t splat)
+{
+	return nibble_of(eq_bytes(v.x, splat)) | nibble_of(eq_bytes(v.y, splat)) << 4 | nibble_of(eq_bytes(v.z, splat)) << 8 |
+	       nibble_of(eq_bytes(v.w, splat)) << 12;
+}
+
+__device__ __forceinline__ uint32_t hit_count16(const u32x4 &v, uint32_t splat)
+{
+	return (uint32_t)(__builtin_popcount(eq_bytes(v.x, splat)) + __builtin_popcount(eq_bytes(v.y, splat)) +
+	                  __builtin_popcount(eq_bytes(v.z, splat)) + __builtin_popcount(eq_bytes(v.w, splat)));
+}
+
+/* 16 bytes of which only [addr, limit) exist (the text's last block): the others read as a byte that is not the delimiter,
+ * so they never count -- also when the delimiter is 0 */
+__device__ __noinline__ u32x4 load16_edge(uint64_t addr, uint64_t limit, uint32_t splat)
+{
+	if (addr + 16u <= limit) return *(glb_chunk_p)addr;
+	uint32_t d[4] = {~splat, ~splat, ~splat, ~splat};
+#pragma unroll
+	for (uint32_t k = 0; k < 16u; k++) {
+		if (addr + k < limit) {
+			const uint32_t sh = (k & 3u) * 8u;
+			d[k >> 2] = (d[k >> 2] & ~(0xffu << sh)) | (uint32_t)((glb_u8p)addr)[k] << sh;
+		}
+	}
+	return u32x4{d[0], d[1], d[2], d[3]};
+}
+
+/* the lane's TEXT_TILES chunks of block b: chunk u = the 16 bytes at 16 * (u * TEXT_THREADS + tid) of the block, all loads
+ * issued before the first use (a pure read stream: one load at a time leaves most of the memory system idle) */
+__device__ __forceinline__ void load_block(u32x4 (&v)[TEXT_TILES], uint64_t text, uint64_t nbytes, uint64_t b, uint32_t splat)
+{
+	const uint64_t at = text + b * TEXT_BLOCK + 16u * threadIdx.x;
+	if ((b + 1u) * TEXT_BLOCK <= nbytes) {   /* the same for the whole workgroup */
+#pragma unroll
+		for (uint32_t u = 0; u < TEXT_TILES; u++) v[u] = *(glb_chunk_p)(at + (uint64_t)u * TEXT_TILE);
+	} else {
+#pragma unroll
+		for (uint32_t u = 0; u < TEXT_TILES; u++) v[u] = load16_edge(at + (uint64_t)u * TEXT_TILE, text + nbytes, splat);
+	}
+}
+
+/* pass 1: workgroup g owns blocks [g * per, (g + 1) * per); cnt[b] = delimiters in block b.  The wave totals alternate
+ * between two LDS rows, so one barrier per block is enough: a row is rewritten only after the barrier that follows its use. */
+__global__ void __launch_bounds__(TEXT_THREADS)
+text_count(const unsigned char *text, uint64_t nbytes, uint32_t splat, uint64_t nblocks, uint64_t per, uint64_t *cnt)
+{
+	__shared__ uint32_t wtot[2][TEXT_WAVES];
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	uint64_t b = (uint64_t)blockIdx.x * per;
+	const uint64_t bend = b + per < nblocks ? b + per : nblocks;
+	for (uint32_t it = 0; b < bend; b++, it ^= 1u) {
+		u32x4 v[TEXT_TILES];
+		load_block(v, (uint64_t)(uintptr_t)text, nbytes, b, splat);
+		uint32_t c = 0;
+#pragma unroll
+		for (uint32_t u = 0; u < TEXT_TILES; u++) c += hit_count16(v[u], splat);
+#pragma unroll
+		for (int d = 32; d >= 1; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d, 64);
+		if (lane == 0) wtot[it][wave] = c;
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			uint32_t s = 0;
+#pragma unroll
+			for (uint32_t w = 0; w < TEXT_WAVES; w++) s += wtot[it][w];
+			*(glb_u64w)(uintptr_t)(cnt + b) = s;
+		}
+	}
+}
+
+/* pass 2: exclusive scan of cnt[] in place by one workgroup (the shape of tile_bases_pass2, walk_aux.h); meta[0] = the
+ * number of delimiters, meta[1] = 1 iff the text's last byte is one: the 16 bytes the host waits for */
+__global__ void __launch_bounds__(1024)
+text_scan(uint64_t *cnt, uint64_t nblocks, const unsigned char *text, uint64_t nbytes, uint32_t delim, uint64_t *meta)
+{
+	__shared__ uint64_t wtot[16];
+	__shared__ uint64_t carry;
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	if (threadIdx.x == 0) carry = 0;
+	__syncthreads();
+	for (uint64_t b0 = 0; b0 < nblocks; b0 += 1024u) {
+		const uint64_t b = b0 + threadIdx.x;
+		const uint64_t mine = b < nblocks ? *(glb_u64p)(uintptr_t)(cnt + b) : 0u;
+		uint64_t x = mine;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const uint64_t y = __shfl_up(x, d, 64);
+			if (lane >= (uint32_t)d) x += y;
+		}
+		if (lane == 63u) wtot[wave] = x;
+		__syncthreads();
+		uint64_t before = carry;
+		for (uint32_t w = 0; w < wave; w++) before += wtot[w];
+		if (b < nblocks) *(glb_u64w)(uintptr_t)(cnt + b) = before + x - mine;
+		__syncthreads();
+		if (threadIdx.x == 1023u) carry = before + x;
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) {
+		glb_u64w m = (glb_u64w)(uintptr_t)meta;
+		m[0] = carry;
+		m[1] = nbytes != 0 && ((glb_u8p)(uintptr_t)text)[nbytes - 1u] == delim ? 1u : 0u;
+	}
+}
+
+/* pass 3: off[1 + rank] = position + 1 of every delimiter.  Positions run tile by tile, lane by lane inside a tile, so the
+ * rank of a lane's first hit in tile u is: base[b] (the scanned cnt) + the hits of the tiles before u + the hits of tile u in
+ * the waves before this one + those of the lanes before this one.  The four tiles' counts (<= 16 a lane, <= 1024 a wave)
+ * ride in 16-bit fields of two words: two wave scans, one LDS exchange and one barrier per block serve all of them.
+ * A store is made only for rank < ndelim: if the caller's buffer changed between the passes the array is wrong, not overrun. */
+__global__ void __launch_bounds__(TEXT_THREADS)
+text_offsets(const unsigned char *text, uint64_t nbytes, uint32_t splat, uint64_t nblocks, uint64_t per, const uint64_t *base,
+             uint64_t ndelim, uint64_t nlines, uint64_t *off)
+{
+	static_assert(TEXT_TILES == 4, "two words of two 16-bit fields");
+	__shared__ uint32_t wtot[2][TEXT_WAVES][2];
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	const glb_u64w out = (glb_u64w)(uintptr_t)off;
+	if (blockIdx.x == 0 && threadIdx.x == 0) {
+		out[0] = 0;
+		if (nlines > ndelim) out[nlines] = nbytes;   /* bytes after the last delimiter: a last line without one */
+	}
+	uint64_t b = (uint64_t)blockIdx.x * per;
+	const uint64_t bend = b + per < nblocks ? b + per : nblocks;
+	for (uint32_t it = 0; b < bend; b++, it ^= 1u) {
+		u32x4 v[TEXT_TILES];
+		load_block(v, (uint64_t)(uintptr_t)text, nbytes, b, splat);
+		const uint64_t rank0 = *(glb_u64p)(uintptr_t)(base + b);
+		uint32_t m[TEXT_TILES], c[TEXT_TILES];
+#pragma unroll
+		for (uint32_t u = 0; u < TEXT_TILES; u++) {
+			m[u] = hit_mask16(v[u], splat);
+			c[u] = (uint32_t)__builtin_popcount(m[u]);
+		}
+		uint32_t x0 = c[0] | c[1] << 16, x1 = c[2] | c[3] << 16;   /* inclusive scans over the wave */
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const uint32_t y0 = (uint32_t)__shfl_up((int)x0, d, 64), y1 = (uint32_t)__shfl_up((int)x1, d, 64);
+			if (lane >= (uint32_t)d) { x0 += y0; x1 += y1; }
+		}
+		if (lane == 63u) { wtot[it][wave][0] = x0; wtot[it][wave][1] = x1; }
+		__syncthreads();
+		uint32_t tot[TEXT_TILES] = {0u, 0u, 0u, 0u}, before[TEXT_TILES] = {0u, 0u, 0u, 0u};
+#pragma unroll
+		for (uint32_t w = 0; w < TEXT_WAVES; w++) {
+			const uint32_t t0 = wtot[it][w][0], t1 = wtot[it][w][1];
+			const uint32_t f[TEXT_TILES] = {t0 & 0xffffu, t0 >> 16, t1 & 0xffffu, t1 >> 16};
+#pragma unroll
+			for (uint32_t u = 0; u < TEXT_TILES; u++) {
+				tot[u] += f[u];
+				before[u] += w < wave ? f[u] : 0u;
+			}
+		}
+		const uint32_t incl[TEXT_TILES] = {x0 & 0xffffu, x0 >> 16, x1 & 0xffffu, x1 >> 16};
+		uint64_t tile_rank = rank0;
+		const uint64_t pos1 = b * TEXT_BLOCK + 16u * threadIdx.x + 1u;
+#pragma unroll
+		for (uint32_t u = 0; u < TEXT_TILES; u++) {
+			uint64_t r = tile_rank + before[u] + (incl[u] - c[u]);
+			for (uint32_t mm = m[u]; mm != 0; mm &= mm - 1u, r++)
+				if (r < ndelim) out[1u + r] = pos1 + (uint64_t)u * TEXT_TILE + (uint32_t)__builtin_ctz(mm);
+			tile_rank += tot[u];
+		}
+	}
+}
+
+int herr(hipError_t e)
+{
+	switch (e) {
+	case hipSuccess: return 0;
+	case hipErrorOutOfMemory: return ENOMEM;
+	case hipErrorNoDevice:
+	case hipErrorInvalidDevice:
+	case hipErrorInsufficientDriver: return ENODEV;
+	case hipErrorInvalidValue: return EINVAL;
+	default: return EIO;
+	}
+}
+#define TTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
+	if (getenv("FSM_HIP_DEBUG")) fprintf(stderr, "fsm_hip: %s -> %s\n", #expr, hipGetErrorString(e_)); \
+	errno = herr(e_); goto fail; } } while (0)
+
+/* make a device current for the duration of a call and give the caller's back */
+struct DevGuard {
+	int prev = -1;
+	bool good = true;
+	explicit DevGuard(int dev)
+	{
+		if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+		if (prev != dev && hipSetDevice(dev) != hipSuccess) good = false;
+		if (prev == dev) prev = -1;
+	}
+	~DevGuard() { if (prev >= 0 && good) { int e = errno; (void)hipSetDevice(prev); errno = e; } }
+	bool ok() const { return good; }
+};
+
+bool have_device()
+{
+	int ndev = 0;
+	return hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
+}
+
+unsigned max_workgroups(int dev)
+{
+	int ncu = 0;
+	if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+	return (unsigned)ncu * TEXT_WG_PER_CU;
+}
+
+}   // namespace
+
+struct fsm_hip_text {
+	int device = 0, delim = 0;
+	size_t nbytes = 0, n = 0;
+	const unsigned char *d_text = nullptr;   /* the caller's bytes (open_device) or `owned` */
+	unsigned char *owned = nullptr;
+	uint64_t *d_off = nullptr;               /* n + 1 */
+	uint64_t *d_cnt = nullptr;               /* per block: its delimiters, then their exclusive scan; + the 2 words of meta */
+	hipStream_t own = nullptr;               /* the host-pointer forms run here, never on the NULL stream */
+	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   /* around count + scan, around offsets; ev[3]: the offsets are there */
+};
+
+extern "C" void fsm_hip_text_free(struct fsm_hip_text *t)
+{
+	if (t == nullptr) return;
+	const int e = errno;
+	{
+		DevGuard dg(t->device);
+		if (t->ev[3] != nullptr) (void)hipEventSynchronize(t->ev[3]);   /* the scan may still be reading the caller's bytes */
+		for (hipEvent_t ev : t->ev) if (ev != nullptr) (void)hipEventDestroy(ev);
+		if (t->own != nullptr) (void)hipStreamDestroy(t->own);
+		if (t->d_off != nullptr) (void)hipFree(t->d_off);
+		if (t->d_cnt != nullptr) (void)hipFree(t->d_cnt);
+		if (t->owned != nullptr) (void)hipFree(t->owned);
+	}
+	delete t;
+	errno = e;
+}
+
+/* the three passes over t->d_text on stream s: one wait in the middle (the line count sizes the offsets array) */
+static int text_scan_lines(struct fsm_hip_text *t, hipStream_t s)
+{
+	const uint64_t nbytes = t->nbytes;
+	const uint32_t splat = (uint32_t)t->delim * 0x01010101u;
+	const uint64_t nblocks = (nbytes + TEXT_BLOCK - 1u) / TEXT_BLOCK;
+	uint64_t meta[2] = {0, 0};
+	for (hipEvent_t &ev : t->ev) TTRY(hipEventCreate(&ev));
+	if (nbytes == 0) {   /* no byte, no line: off[0] = 0 alone */
+		TTRY(hipMalloc((void **)&t->d_off, sizeof(uint64_t)));
+		TTRY(hipMemsetAsync(t->d_off, 0, sizeof(uint64_t), s));
+		for (hipEvent_t ev : t->ev) TTRY(hipEventRecord(ev, s));
+		return 0;
+	}
+	{
+		uint64_t grid = max_workgroups(t->device);
+		if (grid > nblocks) grid = nblocks;
+		const uint64_t per = (nblocks + grid - 1u) / grid;
+		grid = (nblocks + per - 1u) / per;
+		TTRY(hipMalloc((void **)&t->d_cnt, (nblocks + 2u) * sizeof(uint64_t)));
+		uint64_t *d_meta = t->d_cnt + nblocks;
+		TTRY(hipEventRecord(t->ev[0], s));
+		hipLaunchKernelGGL(text_count, dim3((unsigned)grid), dim3(TEXT_THREADS), 0, s, t->d_text, nbytes, splat, nblocks, per, t->d_cnt);
+		TTRY(hipGetLastError());
+		hipLaunchKernelGGL(text_scan, dim3(1), dim3(1024), 0, s, t->d_cnt, nblocks, t->d_text, nbytes, (uint32_t)t->delim, d_meta);
+		TTRY(hipGetLastError());
+		TTRY(hipEventRecord(t->ev[1], s));
+		TTRY(hipMemcpyAsync(meta, d_meta, sizeof meta, hipMemcpyDeviceToHost, s));
+		TTRY(hipStreamSynchronize(s));
+		t->n = (size_t)(meta[0] + (meta[1] != 0 ? 0u : 1u));   /* bytes after the last delimiter form a last line */
+		TTRY(hipMalloc((void **)&t->d_off, ((uint64_t)t->n + 1u) * sizeof(uint64_t)));
+		TTRY(hipEventRecord(t->ev[2], s));
+		hipLaunchKernelGGL(text_offsets, dim3((unsigned)grid), dim3(TEXT_THREADS), 0, s, t->d_text, nbytes, splat, nblocks, per,
+		                   (const uint64_t *)t->d_cnt, meta[0], (uint64_t)t->n, t->d_off);
+		TTRY(hipGetLastError());
+		TTRY(hipEventRecord(t->ev[3], s));
+	}
+	return 0;
+fail:
+	return -1;
+}
+
+static struct fsm_hip_text *text_new(size_t nbytes, int delim)
+{
+	if (delim < 0 || delim > 255) { errno = EINVAL; return nullptr; }
+	if (!have_device()) { errno = ENODEV; return nullptr; }   /* no CPU path, as everywhere in this library */
+	struct fsm_hip_text *t = new (std::nothrow) fsm_hip_text;
+	if (t == nullptr) { errno = ENOMEM; return nullptr; }
+	t->nbytes = nbytes;
+	t->delim = delim;
+	if (hipGetDevice(&t->device) != hipSuccess) { delete t; errno = ENODEV; return nullptr; }
+	hipError_t e = hipStreamCreateWithFlags(&t->own, hipStreamNonBlocking);
+	if (e != hipSuccess) { delete t; errno = herr(e); return nullptr; }
+	return t;
+}
+
+extern "C" struct fsm_hip_text *fsm_hip_text_open_device(const void *d_text, size_t nbytes, int delim, void *hip_stream)
+{
+	if (d_text == nullptr && nbytes != 0) { errno = EINVAL; return nullptr; }
+	struct fsm_hip_text *t = text_new(nbytes, delim);
+	if (t == nullptr) return nullptr;
+	t->d_text = static_cast<const unsigned char *>(d_text);
+	if (text_scan_lines(t, static_cast<hipStream_t>(hip_stream)) != 0) {
+		fsm_hip_text_free(t);
+		return nullptr;
+	}
+	return t;
+}
+
+extern "C" struct fsm_hip_text *fsm_hip_text_open(const void *text, size_t nbytes, int delim)
+{
+	if (text == nullptr && nbytes != 0) { errno = EINVAL; return nullptr; }
+	struct fsm_hip_text *t = text_new(nbytes, delim);
+	if (t == nullptr) return nullptr;
+	if (nbytes != 0) {
+		TTRY(hipMalloc((void **)&t->owned, nbytes));
+		TTRY(hipMemcpyAsync(t->owned, text, nbytes, hipMemcpyHostToDevice, t->own));
+	}
+	t->d_text = t->owned;
+	if (text_scan_lines(t, t->own) != 0) goto fail;
+	TTRY(hipStreamSynchronize(t->own));
+	return t;
+fail:
+	fsm_hip_text_free(t);
+	return nullptr;
+}
+
+extern "C" size_t fsm_hip_text_lines(const struct fsm_hip_text *t) { return t == nullptr ? 0 : t->n; }
+
+extern "C" const uint64_t *fsm_hip_text_offsets_device(const struct fsm_hip_text *t) { return t == nullptr ? nullptr : t->d_off; }
+
+extern "C" int fsm_hip_text_offsets(const struct fsm_hip_text *t, uint64_t *off)
+{
+	if (t == nullptr || off == nullptr) { errno = EINVAL; return -1; }
+	DevGuard dg(t->device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
+	TTRY(hipEventSynchronize(t->ev[3]));
+	TTRY(hipMemcpy(off, t->d_off, (t->n + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	return 0;
+fail:
+	return -1;
+}
+
+extern "C" size_t fsm_hip_text_block_bytes(void) { return TEXT_BLOCK; }
+
+extern "C" size_t fsm_hip_text_max_workgroups(void)
+{
+	int dev = 0;
+	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return 0; }
+	return max_workgroups(dev);
+}
+
+extern "C" double fsm_hip_text_scan_ms(const struct fsm_hip_text *t)
+{
+	float a = 0.f, b = 0.f;
+	if (t == nullptr) { errno = EINVAL; return -1.0; }
+	DevGuard dg(t->device);
+	if (!dg.ok()) { errno = ENODEV; return -1.0; }
+	TTRY(hipEventSynchronize(t->ev[3]));
+	TTRY(hipEventElapsedTime(&a, t->ev[0], t->ev[1]));
+	TTRY(hipEventElapsedTime(&b, t->ev[2], t->ev[3]));
+	return (double)a + (double)b;
+fail:
+	return -1.0;
+}
+
+/* ---- the walk: the untouched text + its offsets are a packed batch of the twin automaton ---- */
+
+static int text_exec_check(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t)
+{
+	struct fsm_hip_dfa_info info;
+	if (ld == nullptr || t == nullptr || fsm_hip_lines_dfa_delim(ld) != t->delim) { errno = EINVAL; return -1; }
+	if (fsm_hip_dfa_info(fsm_hip_lines_dfa_inner(ld), &info) != 0) return -1;
+	if ((int)info.device != t->device) { errno = EINVAL; return -1; }   /* the text lives where it was opened */
+	return 0;
+}
+
+extern "C" int fsm_hip_text_exec_device(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t,
+	uint32_t *d_end_out, uint64_t *d_accept_bitmap, int ids_mode, uint32_t *d_id_out, uint64_t *d_eager_out, void *hip_stream)
+{
+	if (text_exec_check(ld, t) != 0) return -1;
+	if (t->n == 0) return 0;
+	return fsm_hip_exec_batch_packed_all_device(fsm_hip_lines_dfa_inner(ld), t->d_text, FSM_HIP_META_OFF64, t->d_off, t->n,
+	                                            d_end_out, d_accept_bitmap, ids_mode, d_id_out, d_eager_out, hip_stream);
+}
+
+extern "C" int fsm_hip_text_exec(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t,
+	uint32_t *end_out, uint64_t *accept_bitmap, int ids_mode, uint32_t *id_out, uint64_t *eager_out)
+{
+	if (text_exec_check(ld, t) != 0) return -1;
+	const size_t n = t->n;
+	if (n == 0) return 0;
+	if (end_out == nullptr && accept_bitmap == nullptr && id_out == nullptr && eager_out == nullptr) return 0;
+	DevGuard dg(t->device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
+	auto up16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
+	const size_t W = fsm_hip_eager_words(fsm_hip_lines_dfa_inner(ld));
+	const size_t b_end = end_out ? up16(n * 4u) : 0, b_bm = accept_bitmap ? up16((n + 63u) / 64u * 8u) : 0,
+	             b_id = id_out ? up16(n * 4u) : 0, b_eo = eager_out ? up16(n * W * 8u) : 0;
+	unsigned char *d = nullptr;
+	int rc = -1;
+	{
+		TTRY(hipMalloc((void **)&d, b_end + b_bm + b_id + b_eo));
+		uint32_t *d_end = end_out ? (uint32_t *)d : nullptr;
+		uint64_t *d_bm = accept_bitmap ? (uint64_t *)(d + b_end) : nullptr;
+		uint32_t *d_id = id_out ? (uint32_t *)(d + b_end + b_bm) : nullptr;
+		uint64_t *d_eo = eager_out ? (uint64_t *)(d + b_end + b_bm + b_id) : nullptr;
+		TTRY(hipStreamWaitEvent(t->own, t->ev[3], 0));   /* a text opened on the caller's stream: its offsets first */
+		if (fsm_hip_text_exec_device(ld, t, d_end, d_bm, ids_mode, d_id, d_eo, t->own) != 0) goto fail;
+		if (end_out) TTRY(hipMemcpyAsync(end_out, d_end, n * 4u, hipMemcpyDeviceToHost, t->own));
+		if (accept_bitmap) TTRY(hipMemcpyAsync(accept_bitmap, d_bm, (n + 63u) / 64u * 8u, hipMemcpyDeviceToHost, t->own));
+		if (id_out) TTRY(hipMemcpyAsync(id_out, d_id, n * 4u, hipMemcpyDeviceToHost, t->own));
+		if (eager_out) TTRY(hipMemcpyAsync(eager_out, d_eo, n * W * 8u, hipMemcpyDeviceToHost, t->own));
+		TTRY(hipStreamSynchronize(t->own));
+		rc = 0;
+	}
+fail:
+	if (d != nullptr) {
+		const int e = errno;
+		(void)hipStreamSynchronize(t->own);
+		(void)hipFree(d);
+		errno = e;
+	}
+	return rc;
+}
