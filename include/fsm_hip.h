@@ -762,6 +762,50 @@ int fsm_hip_text_exec(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_t
 int fsm_hip_text_exec_device(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t,
 	uint32_t *d_end_out, uint64_t *d_accept_bitmap, int ids_mode, uint32_t *d_id_out, uint64_t *d_eager_out, void *hip_stream);
 
+/* The hits: the lines a bitmap selects -- their numbers, their byte ranges and their bytes, packed, on the device.  What a
+ * grep-like caller wants from a text is not n answers but the lines that matched; this is the stream compaction and the
+ * ragged gather that deliver them without a host loop over the answers or the offsets.
+ *   Selected: line i is selected iff i < n and (bit i of the bitmap) ^ (FSM_HIP_HITS_INVERT given) is set.  The bitmap has
+ *     ceil(n / 64) words, bit i = line i (the layout fsm_hip_text_exec_device writes); the bits at and above n of its last word
+ *     are ignored whatever they hold: INVERT does not turn them into lines.
+ *   lines    m line indices, 0-based, ascending.
+ *   bytes    text[off[i], off[i + 1]) of every selected line in that order, verbatim: the trailing delimiter where the line has
+ *            one, none added to a last line without.  Every selected line therefore contributes at least one byte.
+ *   out_off  m + 1 entries: out_off[k] = bytes before the k-th selected line, out_off[0] = 0, out_off[m] = nbytes.
+ *   Under FSM_HIP_HITS_NO_BYTES (grep -c, grep -n without the text) only m and lines are made: nbytes is 0, the offsets and the
+ *   bytes are NULL.  n == 0 or m == 0 gives a valid handle with count 0, out_off = {0} and no bytes.
+ * fsm_hip_text_hits walks t with ld (accept bitmap only, kept on the device) on the text's own stream, as fsm_hip_text_exec
+ * does, and returns when everything is there.  fsm_hip_text_hits_device takes any caller-made bitmap: the work is enqueued on
+ * hip_stream after a wait for the text's "offsets are there" event, and hip_stream is synchronised ONCE inside the call (m and
+ * the byte total size the arrays: fsm_hip_text_open_device's rule); the kernels that fill the arrays are still in flight at
+ * return -- later work on hip_stream sees the arrays, fsm_hip_text_hits_copy and _ms wait for the hits' own event.  Not
+ * capturable into a HIP graph.  The bitmap and the text must stay as they are until that event (if they do not, the arrays are
+ * wrong, never overrun, and no byte outside the text is read).  The hits must be freed before their text.
+ * NULL + errno: EINVAL (t NULL, d_bitmap NULL with n > 0, an unknown flag bit; in the host form ld NULL or its delimiter or
+ * device not the text's), ENOMEM, ENODEV (checked first: there is no CPU path). */
+#define FSM_HIP_HITS_INVERT   1u   /* select the lines whose bit is 0 (grep -v) */
+#define FSM_HIP_HITS_NO_BYTES 2u   /* numbers and count only: no gather, no output offsets */
+struct fsm_hip_text_hits;
+struct fsm_hip_text_hits *fsm_hip_text_hits(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t, unsigned flags);
+struct fsm_hip_text_hits *fsm_hip_text_hits_device(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags, void *hip_stream);
+size_t fsm_hip_text_hits_count(const struct fsm_hip_text_hits *h);                    /* m */
+size_t fsm_hip_text_hits_nbytes(const struct fsm_hip_text_hits *h);                   /* bytes of the m lines; 0 under NO_BYTES */
+const uint64_t *fsm_hip_text_hits_lines_device(const struct fsm_hip_text_hits *h);    /* m entries; NULL when m == 0 */
+const uint64_t *fsm_hip_text_hits_offsets_device(const struct fsm_hip_text_hits *h);  /* m + 1 entries; NULL under NO_BYTES */
+const unsigned char *fsm_hip_text_hits_bytes_device(const struct fsm_hip_text_hits *h);   /* nbytes; NULL when there are none */
+/* copy out whichever are not NULL (lines: m, out_off: m + 1, bytes: nbytes); waits for the hits.  -1 + EINVAL: h NULL, or out_off
+ * asked of hits made under NO_BYTES */
+int fsm_hip_text_hits_copy(const struct fsm_hip_text_hits *h, uint64_t *lines, uint64_t *out_off, void *bytes);
+/* milliseconds of the hits' kernels from HIP events around them, the host's wait in the middle left out (as fsm_hip_text_scan_ms;
+ * blocks until the hits are there); _gather_ms: the gather kernel's share of it, 0 when there was none */
+double fsm_hip_text_hits_ms(const struct fsm_hip_text_hits *h);
+double fsm_hip_text_hits_gather_ms(const struct fsm_hip_text_hits *h);
+void fsm_hip_text_hits_free(struct fsm_hip_text_hits *h);
+/* for tests: lines one workgroup selects per step; output bytes one workgroup gathers per step (the most workgroups of either:
+ * fsm_hip_text_max_workgroups) */
+size_t fsm_hip_text_hits_block_lines(void);
+size_t fsm_hip_text_hits_block_bytes(void);
+
 /* ------------------------------------------------------------------ */
 /* synthetic input generator (benchmarks and parity tests)            */
 /* ------------------------------------------------------------------ */

@@ -1449,6 +1449,109 @@ class HipText:
                                               vp(d_eager or None), vp(stream or None)) != 0:
             raise _oserr("fsm_hip_text_exec_device")
 
+    def hits(self, ld: LinesDfa, invert: bool = False, want_bytes: bool = True) -> "HipHits":
+        """fsm_hip_text_hits: walk the text with ld and select the accepted lines (invert: the others)."""
+        lib = self._lib
+        lib.fsm_hip_text_hits.restype = C.c_void_p
+        C.set_errno(0)
+        h = lib.fsm_hip_text_hits(C.c_void_p(ld.handle), C.c_void_p(self._h), C.c_uint(hits_flags(invert, want_bytes)))
+        if not h:
+            raise _oserr("fsm_hip_text_hits")
+        return HipHits(h, self)
+
+    def hits_device(self, d_bitmap: int, invert: bool = False, want_bytes: bool = True, stream: int = 0, flags: Optional[int] = None) -> "HipHits":
+        """fsm_hip_text_hits_device: select by a caller-made bitmap on the device (ceil(n / 64) words, bit i = line i), enqueued on
+        `stream`.  flags: the raw flag word instead of invert / want_bytes."""
+        lib = self._lib
+        lib.fsm_hip_text_hits_device.restype = C.c_void_p
+        C.set_errno(0)
+        h = lib.fsm_hip_text_hits_device(C.c_void_p(self._h), C.c_void_p(d_bitmap or None),
+                                         C.c_uint(hits_flags(invert, want_bytes) if flags is None else flags), C.c_void_p(stream or None))
+        if not h:
+            raise _oserr("fsm_hip_text_hits_device")
+        return HipHits(h, self)
+
+
+HITS_INVERT, HITS_NO_BYTES = 1, 2
+
+
+def hits_flags(invert: bool, want_bytes: bool) -> int:
+    return (HITS_INVERT if invert else 0) | (0 if want_bytes else HITS_NO_BYTES)
+
+
+class HipHits:
+    """struct fsm_hip_text_hits *: the selected lines' numbers, output offsets and bytes, packed on the device.  Keeps its text
+    alive: the hits must be freed first."""
+
+    def __init__(self, handle, text: HipText):
+        self._lib = lib = load_library()
+        self._h, self._text = handle, text
+        for f in ("count", "nbytes"):
+            getattr(lib, "fsm_hip_text_hits_" + f).restype = C.c_size_t
+        for f in ("lines_device", "offsets_device", "bytes_device"):
+            getattr(lib, "fsm_hip_text_hits_" + f).restype = C.c_void_p
+        lib.fsm_hip_text_hits_ms.restype = C.c_double
+        lib.fsm_hip_text_hits_gather_ms.restype = C.c_double
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.fsm_hip_text_hits_free(C.c_void_p(self._h))
+            self._h = None
+            self._text = None
+
+    __del__ = close
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def count(self) -> int:
+        return int(self._lib.fsm_hip_text_hits_count(C.c_void_p(self._h)))
+
+    @property
+    def nbytes(self) -> int:
+        return int(self._lib.fsm_hip_text_hits_nbytes(C.c_void_p(self._h)))
+
+    @property
+    def lines_device(self) -> int:
+        return int(self._lib.fsm_hip_text_hits_lines_device(C.c_void_p(self._h)) or 0)
+
+    @property
+    def offsets_device(self) -> int:
+        return int(self._lib.fsm_hip_text_hits_offsets_device(C.c_void_p(self._h)) or 0)
+
+    @property
+    def bytes_device(self) -> int:
+        return int(self._lib.fsm_hip_text_hits_bytes_device(C.c_void_p(self._h)) or 0)
+
+    def _copy(self, lines=None, off=None, data=None):
+        C.set_errno(0)
+        if self._lib.fsm_hip_text_hits_copy(C.c_void_p(self._h), _ptr(lines), _ptr(off), _ptr(data)) != 0:
+            raise _oserr("fsm_hip_text_hits_copy")
+
+    def lines(self) -> np.ndarray:
+        out = np.empty(self.count, np.uint64)
+        self._copy(lines=out)
+        return out
+
+    def offsets(self) -> np.ndarray:
+        out = np.empty(self.count + 1, np.uint64)
+        self._copy(off=out)
+        return out
+
+    def bytes(self) -> np.ndarray:
+        out = np.empty(self.nbytes, np.uint8)
+        self._copy(data=out)
+        return out
+
+    def ms(self) -> float:
+        return float(self._lib.fsm_hip_text_hits_ms(C.c_void_p(self._h)))
+
+    def gather_ms(self) -> float:
+        return float(self._lib.fsm_hip_text_hits_gather_ms(C.c_void_p(self._h)))
+
+
 
 def text_block_bytes() -> int:
     """fsm_hip_text_block_bytes: bytes one workgroup of the delimiter scan covers per step."""
@@ -1462,3 +1565,17 @@ def text_max_workgroups() -> int:
     lib = load_library()
     lib.fsm_hip_text_max_workgroups.restype = C.c_size_t
     return int(lib.fsm_hip_text_max_workgroups())
+
+
+def text_hits_block_lines() -> int:
+    """fsm_hip_text_hits_block_lines: lines one workgroup of the select covers per step."""
+    lib = load_library()
+    lib.fsm_hip_text_hits_block_lines.restype = C.c_size_t
+    return int(lib.fsm_hip_text_hits_block_lines())
+
+
+def text_hits_block_bytes() -> int:
+    """fsm_hip_text_hits_block_bytes: output bytes one workgroup of the gather covers per step."""
+    lib = load_library()
+    lib.fsm_hip_text_hits_block_bytes.restype = C.c_size_t
+    return int(lib.fsm_hip_text_hits_block_bytes())

@@ -482,3 +482,450 @@ fail:
 	}
 	return rc;
 }
+
+/* ---- the hits: the selected lines' numbers, ranges and bytes ----------------------------------------------------
+ * A caller like grep does not want n answers, it wants the lines that matched.  A bitmap (bit i = line i, the layout the walk
+ * writes) and the offsets become: m line numbers, m + 1 output offsets and the lines' bytes, packed.  A select in three
+ * passes, shaped as the delimiter scan is, and a gather that partitions the OUTPUT:
+ *     hits_count   pair[block] = (lines selected, their bytes) of a block of HITS_LINES lines    (reads bitmap and offsets)
+ *     hits_scan    exclusive scan of the pairs by one workgroup, HITS_SCAN_PER pairs a thread and round; m and the bytes for the host
+ *     hits_emit    re-reads the block; lines[rank] = i, out_off[rank], src[rank] = off[i]; the line whose output range covers
+ *                  byte g * HITS_BLOCK leaves first[g] = rank (ranges are non-empty and tile the output: exactly one does)
+ *     hits_gather  a workgroup owns blocks of HITS_BLOCK output bytes, a lane 16-byte chunks: the line of the chunk's first byte
+ *                  by an upper-bound search of out_off between first[g] and first[g + 1]; a chunk inside one line is one
+ *                  unaligned 16-byte load, a chunk across boundaries is assembled from byte loads line by line
+ * No line belongs to a lane or a wavefront: a 64 MiB line is 4 096 output blocks like any other 64 MiB.  No workgroup waits on
+ * another.  Stores are made only below the counted totals and loads only inside [text, text + nbytes): a bitmap that changes
+ * between the passes gives wrong arrays, not an overrun. */
+namespace {
+
+constexpr uint32_t HITS_WAVES = 4;
+constexpr uint32_t HITS_THREADS = HITS_WAVES * 64u;
+constexpr uint32_t HITS_PER = 4;                            /* consecutive lines a lane tests: never across a bitmap word */
+constexpr uint32_t HITS_LINES = HITS_THREADS * HITS_PER;    /* lines a workgroup selects per step: 1 024 */
+constexpr uint32_t HITS_TILES = 4;
+constexpr uint32_t HITS_TILE = HITS_THREADS * 16u;          /* output bytes one store instruction of the workgroup covers */
+constexpr uint32_t HITS_BLOCK = HITS_TILES * HITS_TILE;     /* output bytes a workgroup gathers per step: 16 KiB */
+constexpr uint32_t HITS_SCAN_PER = 4;                       /* pairs a thread of the scan takes per round: 4 096 a round */
+
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+typedef const u64x2 __attribute__((address_space(1))) *glb_u64x2p;
+typedef u64x2 __attribute__((address_space(1))) *glb_u64x2w;
+typedef u32x4 __attribute__((address_space(1))) *glb_chunk_w;
+
+/* the lane's HITS_PER lines from i0 (a multiple of HITS_PER): bit j <=> line i0 + j < n is selected; o[j], o[j + 1] its range */
+__device__ __forceinline__ uint32_t lane_lines(uint64_t bitmap, uint64_t off, uint64_t n, uint64_t i0, uint32_t invert, uint64_t (&o)[HITS_PER + 1])
+{
+	static_assert(HITS_PER == 4, "two 16-byte loads and one word");
+#pragma unroll
+	for (uint32_t j = 0; j <= HITS_PER; j++) o[j] = 0;
+	if (i0 >= n) return 0u;
+	const uint64_t w = ((glb_u64p)bitmap)[i0 >> 6];
+	uint32_t sel = (uint32_t)((invert != 0u ? ~w : w) >> (i0 & 63u)) & 0xfu;
+	if (i0 + HITS_PER <= n) {
+		const glb_u64x2p p = (glb_u64x2p)(off + 8u * i0);   /* 32-byte aligned: the offsets are the text's own allocation */
+		const u64x2 a = p[0], b = p[1];
+		o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
+		o[4] = ((glb_u64p)off)[i0 + 4u];
+	} else {
+		sel &= (1u << (uint32_t)(n - i0)) - 1u;              /* bits at and above n are no lines, whatever they hold */
+#pragma unroll
+		for (uint32_t j = 0; j <= HITS_PER; j++)
+			if (i0 + j <= n) o[j] = ((glb_u64p)off)[i0 + j];
+	}
+	return sel;
+}
+
+/* pass 1: workgroup g owns blocks [g * per, (g + 1) * per) of HITS_LINES lines; pairs[2b], pairs[2b + 1] = lines and bytes
+ * selected in block b.  Two LDS rows in turn, one barrier a block, as text_count. */
+__global__ void __launch_bounds__(HITS_THREADS)
+hits_count(const uint64_t *bitmap, const uint64_t *off, uint64_t n, uint32_t invert, uint64_t nblocks, uint64_t per, uint64_t *pairs)
+{
+	__shared__ uint64_t wtot[2][HITS_WAVES][2];
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	uint64_t b = (uint64_t)blockIdx.x * per;
+	const uint64_t bend = b + per < nblocks ? b + per : nblocks;
+	for (uint32_t it = 0; b < bend; b++, it ^= 1u) {
+		uint64_t o[HITS_PER + 1];
+		const uint32_t sel = lane_lines((uint64_t)(uintptr_t)bitmap, (uint64_t)(uintptr_t)off, n, b * HITS_LINES + HITS_PER * threadIdx.x, invert, o);
+		uint32_t c = (uint32_t)__builtin_popcount(sel);
+		uint64_t by = 0;
+#pragma unroll
+		for (uint32_t j = 0; j < HITS_PER; j++) by += (sel >> j & 1u) != 0u ? o[j + 1u] - o[j] : 0u;
+#pragma unroll
+		for (int d = 32; d >= 1; d >>= 1) {
+			c += (uint32_t)__shfl_xor((int)c, d, 64);
+			by += __shfl_xor(by, d, 64);
+		}
+		if (lane == 0) { wtot[it][wave][0] = c; wtot[it][wave][1] = by; }
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			uint64_t sc = 0, sb = 0;
+#pragma unroll
+			for (uint32_t w = 0; w < HITS_WAVES; w++) { sc += wtot[it][w][0]; sb += wtot[it][w][1]; }
+			*(glb_u64x2w)(uintptr_t)(pairs + 2u * b) = u64x2{sc, sb};
+		}
+	}
+}
+
+/* pass 2: exclusive scan of the pairs in place by one workgroup; meta[0] = m, meta[1] = the bytes of the m lines.  text_scan's
+ * shape with the lever NOTES.md names for it pulled: HITS_SCAN_PER consecutive pairs a thread, so one memory round trip serves
+ * 4 096 blocks (4 Mi lines) instead of 1 024. */
+__global__ void __launch_bounds__(1024)
+hits_scan(uint64_t *pairs, uint64_t nblocks, uint64_t *meta)
+{
+	__shared__ uint64_t wtot[16][2];
+	__shared__ uint64_t carry[2];
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	if (threadIdx.x == 0) { carry[0] = 0; carry[1] = 0; }
+	__syncthreads();
+	for (uint64_t b0 = 0; b0 < nblocks; b0 += 1024u * HITS_SCAN_PER) {
+		const uint64_t b = b0 + (uint64_t)HITS_SCAN_PER * threadIdx.x;
+		u64x2 e[HITS_SCAN_PER];
+#pragma unroll
+		for (uint32_t k = 0; k < HITS_SCAN_PER; k++)
+			e[k] = b + k < nblocks ? *(glb_u64x2p)(uintptr_t)(pairs + 2u * (b + k)) : u64x2{0u, 0u};
+		u64x2 mine = e[0];
+#pragma unroll
+		for (uint32_t k = 1; k < HITS_SCAN_PER; k++) mine += e[k];
+		uint64_t xc = mine.x, xb = mine.y;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const uint64_t yc = __shfl_up(xc, d, 64), yb = __shfl_up(xb, d, 64);
+			if (lane >= (uint32_t)d) { xc += yc; xb += yb; }
+		}
+		if (lane == 63u) { wtot[wave][0] = xc; wtot[wave][1] = xb; }
+		__syncthreads();
+		uint64_t bc = carry[0], bb = carry[1];
+		for (uint32_t w = 0; w < wave; w++) { bc += wtot[w][0]; bb += wtot[w][1]; }
+		u64x2 run = u64x2{bc + xc - mine.x, bb + xb - mine.y};
+#pragma unroll
+		for (uint32_t k = 0; k < HITS_SCAN_PER; k++) {
+			if (b + k < nblocks) *(glb_u64x2w)(uintptr_t)(pairs + 2u * (b + k)) = run;
+			run += e[k];
+		}
+		__syncthreads();
+		if (threadIdx.x == 1023u) { carry[0] = bc + xc; carry[1] = bb + xb; }
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) {
+		glb_u64w m = (glb_u64w)(uintptr_t)meta;
+		m[0] = carry[0];
+		m[1] = carry[1];
+	}
+}
+
+/* pass 3: the rank of a selected line = base[block] + the selected lines of the waves and lanes before it (a wave scan and an
+ * LDS exchange); the bytes before it likewise.  out_off == NULL (NO_BYTES): the numbers alone.  ngb = output blocks. */
+__global__ void __launch_bounds__(HITS_THREADS)
+hits_emit(const uint64_t *bitmap, const uint64_t *off, uint64_t n, uint32_t invert, uint64_t nblocks, uint64_t per, const uint64_t *base,
+          uint64_t m, uint64_t total, uint64_t *lines, uint64_t *out_off, uint64_t *src, uint64_t *first, uint64_t ngb)
+{
+	__shared__ uint64_t wtot[2][HITS_WAVES][2];
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	const glb_u64w ln = (glb_u64w)(uintptr_t)lines, oo = (glb_u64w)(uintptr_t)out_off, sr = (glb_u64w)(uintptr_t)src,
+	               fi = (glb_u64w)(uintptr_t)first;
+	const bool bytes = out_off != nullptr;
+	if (blockIdx.x == 0 && threadIdx.x == 0 && bytes) {
+		oo[m] = total;
+		if (first != nullptr) fi[ngb] = m;   /* the search's upper end in the last block */
+	}
+	uint64_t b = (uint64_t)blockIdx.x * per;
+	const uint64_t bend = b + per < nblocks ? b + per : nblocks;
+	for (uint32_t it = 0; b < bend; b++, it ^= 1u) {
+		uint64_t o[HITS_PER + 1];
+		const uint64_t i0 = b * HITS_LINES + HITS_PER * threadIdx.x;
+		const uint32_t sel = lane_lines((uint64_t)(uintptr_t)bitmap, (uint64_t)(uintptr_t)off, n, i0, invert, o);
+		const u64x2 bs = *(glb_u64x2p)(uintptr_t)(base + 2u * b);
+		const uint32_t c = (uint32_t)__builtin_popcount(sel);
+		uint64_t by = 0;
+#pragma unroll
+		for (uint32_t j = 0; j < HITS_PER; j++) by += (sel >> j & 1u) != 0u ? o[j + 1u] - o[j] : 0u;
+		uint32_t xc = c;
+		uint64_t xb = by;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const uint32_t yc = (uint32_t)__shfl_up((int)xc, d, 64);
+			const uint64_t yb = __shfl_up(xb, d, 64);
+			if (lane >= (uint32_t)d) { xc += yc; xb += yb; }
+		}
+		if (lane == 63u) { wtot[it][wave][0] = xc; wtot[it][wave][1] = xb; }
+		__syncthreads();
+		uint64_t r = bs.x + (xc - c), p = bs.y + (xb - by);
+#pragma unroll
+		for (uint32_t w = 0; w < HITS_WAVES; w++) {
+			r += w < wave ? wtot[it][w][0] : 0u;
+			p += w < wave ? wtot[it][w][1] : 0u;
+		}
+#pragma unroll
+		for (uint32_t j = 0; j < HITS_PER; j++) {
+			if ((sel >> j & 1u) == 0u) continue;
+			const uint64_t len = o[j + 1u] - o[j];
+			if (r < m) {
+				ln[r] = i0 + j;
+				if (bytes) {
+					oo[r] = p;
+					sr[r] = o[j];
+					/* the block boundaries inside [p, p + len): one for most lines that have any, many for a long line */
+					for (uint64_t g = (p + HITS_BLOCK - 1u) / HITS_BLOCK; g < ngb && g * HITS_BLOCK < p + len; g++) fi[g] = r;
+				}
+			}
+			r++;
+			p += len;
+		}
+	}
+}
+
+/* the gather: workgroup w owns output blocks [w * per, (w + 1) * per).  The lane's chunk starts at output byte p; its line is
+ * the last k in [first[g], first[g + 1]] with out_off[k] <= p.  Everything read through a rank is clamped below m and every
+ * text byte is tested against nbytes, so arrays gone wrong (a bitmap that changed) cannot send a load outside. */
+__global__ void __launch_bounds__(HITS_THREADS)
+hits_gather(const unsigned char *text, uint64_t nbytes, const uint64_t *out_off, const uint64_t *src, const uint64_t *first,
+            uint64_t m, uint64_t total, uint64_t ngb, uint64_t per, unsigned char *out)
+{
+	const glb_u64p oo = (glb_u64p)(uintptr_t)out_off, sr = (glb_u64p)(uintptr_t)src, fi = (glb_u64p)(uintptr_t)first;
+	const uint64_t tx = (uint64_t)(uintptr_t)text, ox = (uint64_t)(uintptr_t)out;
+	uint64_t g = (uint64_t)blockIdx.x * per;
+	const uint64_t gend = g + per < ngb ? g + per : ngb;
+	for (; g < gend; g++) {
+		uint64_t k = fi[g], hi = fi[g + 1u];
+		if (k > m - 1u) k = m - 1u;
+		if (hi > m - 1u) hi = m - 1u;
+#pragma unroll 1
+		for (uint32_t u = 0; u < HITS_TILES; u++) {
+			const uint64_t p = g * HITS_BLOCK + (uint64_t)u * HITS_TILE + 16u * threadIdx.x;
+			if (p >= total) break;
+			uint64_t z = hi;
+			while (k < z) {                                   /* upper bound; the tiles of a lane ascend, so k only grows */
+				const uint64_t mid = k + (z - k + 1u) / 2u;
+				if (oo[mid] <= p) k = mid; else z = mid - 1u;
+			}
+			uint64_t end = oo[k + 1u];
+			uint64_t delta = sr[k] - oo[k];                   /* text position = output position + delta, inside line k */
+			u32x4 v;
+			if (end >= p + 16u && nbytes >= 16u && p + delta <= nbytes - 16u) {
+				v = *(glb_chunk_p)(tx + p + delta);           /* the whole chunk inside one line: any alignment */
+			} else {
+				uint32_t d[4] = {0u, 0u, 0u, 0u};
+				uint64_t kk = k;
+#pragma unroll
+				for (uint32_t j = 0; j < 16u; j++) {
+					const uint64_t pos = p + j;
+					if (pos < total) {
+						if (pos >= end && kk + 1u < m) {          /* lines are non-empty: one step reaches the byte's line */
+							kk++;
+							end = oo[kk + 1u];
+							delta = sr[kk] - oo[kk];
+						}
+						const uint64_t s = pos + delta;
+						if (s < nbytes) d[j >> 2] |= (uint32_t)((glb_u8p)tx)[s] << ((j & 3u) * 8u);
+					}
+				}
+				v = u32x4{d[0], d[1], d[2], d[3]};
+			}
+			*(glb_chunk_w)(ox + p) = v;                       /* the buffer is whole blocks: the last chunk is stored whole */
+		}
+	}
+}
+
+}   // namespace
+
+struct fsm_hip_text_hits {
+	int device = 0;
+	size_t m = 0, nbytes = 0;
+	uint64_t *d_pairs = nullptr;             /* per block of lines: (lines, bytes) selected, then their exclusive scan; + m and the bytes */
+	uint64_t *d_lines = nullptr;             /* m */
+	uint64_t *d_off = nullptr;               /* m + 1 */
+	uint64_t *d_src = nullptr;               /* m: where each selected line starts in the text */
+	uint64_t *d_first = nullptr;             /* per output block + 1: the rank of the line that covers its first byte */
+	unsigned char *d_bytes = nullptr;        /* nbytes, rounded up to whole blocks */
+	hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   /* around count + scan, emit, gather; ev[5]: all is there */
+};
+
+extern "C" void fsm_hip_text_hits_free(struct fsm_hip_text_hits *h)
+{
+	if (h == nullptr) return;
+	const int e = errno;
+	{
+		DevGuard dg(h->device);
+		if (h->ev[5] != nullptr) (void)hipEventSynchronize(h->ev[5]);
+		for (hipEvent_t ev : h->ev) if (ev != nullptr) (void)hipEventDestroy(ev);
+		if (h->d_pairs != nullptr) (void)hipFree(h->d_pairs);
+		if (h->d_lines != nullptr) (void)hipFree(h->d_lines);
+		if (h->d_off != nullptr) (void)hipFree(h->d_off);
+		if (h->d_src != nullptr) (void)hipFree(h->d_src);
+		if (h->d_first != nullptr) (void)hipFree(h->d_first);
+		if (h->d_bytes != nullptr) (void)hipFree(h->d_bytes);
+	}
+	delete h;
+	errno = e;
+}
+
+/* the passes over d_bitmap on stream s: one wait in the middle (m and the bytes size the arrays); emit and gather in flight at return */
+static struct fsm_hip_text_hits *text_hits_run(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags, hipStream_t s)
+{
+	const uint64_t n = t->n;
+	const uint32_t invert = (flags & FSM_HIP_HITS_INVERT) != 0u ? 1u : 0u;
+	const bool bytes = (flags & FSM_HIP_HITS_NO_BYTES) == 0u;
+	uint64_t nblocks = (n + HITS_LINES - 1u) / HITS_LINES, grid = 1, per = 1, ngb = 0;
+	uint64_t meta[2] = {0, 0};
+	struct fsm_hip_text_hits *h = new (std::nothrow) struct fsm_hip_text_hits;
+	if (h == nullptr) { errno = ENOMEM; return nullptr; }
+	h->device = t->device;
+	{
+		DevGuard dg(t->device);
+		if (!dg.ok()) { errno = ENODEV; goto fail; }
+		for (hipEvent_t &ev : h->ev) TTRY(hipEventCreate(&ev));
+		TTRY(hipStreamWaitEvent(s, t->ev[3], 0));   /* the text's offsets first */
+		TTRY(hipEventRecord(h->ev[0], s));
+		if (n != 0) {
+			grid = max_workgroups(t->device);
+			if (grid > nblocks) grid = nblocks;
+			per = (nblocks + grid - 1u) / grid;
+			grid = (nblocks + per - 1u) / per;
+			TTRY(hipMalloc((void **)&h->d_pairs, (2u * nblocks + 2u) * sizeof(uint64_t)));
+			uint64_t *d_meta = h->d_pairs + 2u * nblocks;
+			hipLaunchKernelGGL(hits_count, dim3((unsigned)grid), dim3(HITS_THREADS), 0, s, d_bitmap, (const uint64_t *)t->d_off, n, invert,
+			                   nblocks, per, h->d_pairs);
+			TTRY(hipGetLastError());
+			hipLaunchKernelGGL(hits_scan, dim3(1), dim3(1024), 0, s, h->d_pairs, nblocks, d_meta);
+			TTRY(hipGetLastError());
+			TTRY(hipEventRecord(h->ev[1], s));
+			TTRY(hipMemcpyAsync(meta, d_meta, sizeof meta, hipMemcpyDeviceToHost, s));
+			TTRY(hipStreamSynchronize(s));
+		} else {
+			TTRY(hipEventRecord(h->ev[1], s));
+		}
+		h->m = (size_t)meta[0];
+		h->nbytes = bytes ? (size_t)meta[1] : 0;
+		if (h->m == 0) { nblocks = 0; grid = 1; per = 1; }   /* nothing to re-read: the emit kernel leaves out_off = {0} alone */
+		ngb = ((uint64_t)h->nbytes + HITS_BLOCK - 1u) / HITS_BLOCK;
+		if (h->m != 0) TTRY(hipMalloc((void **)&h->d_lines, (uint64_t)h->m * sizeof(uint64_t)));
+		if (bytes) {
+			TTRY(hipMalloc((void **)&h->d_off, ((uint64_t)h->m + 1u) * sizeof(uint64_t)));
+			if (h->m != 0) {
+				TTRY(hipMalloc((void **)&h->d_src, (uint64_t)h->m * sizeof(uint64_t)));
+				TTRY(hipMalloc((void **)&h->d_first, (ngb + 1u) * sizeof(uint64_t)));
+				TTRY(hipMalloc((void **)&h->d_bytes, ngb * HITS_BLOCK));
+			}
+		}
+		TTRY(hipEventRecord(h->ev[2], s));
+		if (h->m != 0 || bytes) {
+			hipLaunchKernelGGL(hits_emit, dim3((unsigned)grid), dim3(HITS_THREADS), 0, s, d_bitmap, (const uint64_t *)t->d_off, n, invert, nblocks,
+			                   per, (const uint64_t *)h->d_pairs, (uint64_t)h->m, (uint64_t)h->nbytes, h->d_lines, h->d_off, h->d_src,
+			                   h->d_first, ngb);
+			TTRY(hipGetLastError());
+		}
+		TTRY(hipEventRecord(h->ev[3], s));
+		TTRY(hipEventRecord(h->ev[4], s));
+		if (ngb != 0) {
+			uint64_t gg = max_workgroups(t->device);
+			if (gg > ngb) gg = ngb;
+			const uint64_t gper = (ngb + gg - 1u) / gg;
+			gg = (ngb + gper - 1u) / gper;
+			hipLaunchKernelGGL(hits_gather, dim3((unsigned)gg), dim3(HITS_THREADS), 0, s, t->d_text, (uint64_t)t->nbytes,
+			                   (const uint64_t *)h->d_off, (const uint64_t *)h->d_src, (const uint64_t *)h->d_first, (uint64_t)h->m,
+			                   (uint64_t)h->nbytes, ngb, gper, h->d_bytes);
+			TTRY(hipGetLastError());
+		}
+		TTRY(hipEventRecord(h->ev[5], s));
+	}
+	return h;
+fail:
+	{
+		const int e = errno;
+		(void)hipStreamSynchronize(s);
+		fsm_hip_text_hits_free(h);
+		errno = e;
+	}
+	return nullptr;
+}
+
+static int text_hits_check(const struct fsm_hip_text *t, unsigned flags)
+{
+	if (t == nullptr || (flags & ~(FSM_HIP_HITS_INVERT | FSM_HIP_HITS_NO_BYTES)) != 0u) { errno = EINVAL; return -1; }
+	return 0;
+}
+
+extern "C" struct fsm_hip_text_hits *fsm_hip_text_hits_device(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags,
+	void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (text_hits_check(t, flags) != 0) return nullptr;
+	if (d_bitmap == nullptr && t->n != 0) { errno = EINVAL; return nullptr; }
+	return text_hits_run(t, d_bitmap, flags, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" struct fsm_hip_text_hits *fsm_hip_text_hits(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t, unsigned flags)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (text_hits_check(t, flags) != 0 || text_exec_check(ld, t) != 0) return nullptr;
+	DevGuard dg(t->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	uint64_t *d_bm = nullptr;
+	struct fsm_hip_text_hits *h = nullptr;
+	{
+		if (t->n != 0) {
+			TTRY(hipMalloc((void **)&d_bm, (t->n + 63u) / 64u * sizeof(uint64_t)));
+			TTRY(hipStreamWaitEvent(t->own, t->ev[3], 0));
+			if (fsm_hip_text_exec_device(ld, t, nullptr, d_bm, 0, nullptr, nullptr, t->own) != 0) goto fail;
+		}
+		h = text_hits_run(t, d_bm, flags, t->own);
+		if (h == nullptr) goto fail;
+		TTRY(hipStreamSynchronize(t->own));
+	}
+	if (d_bm != nullptr) (void)hipFree(d_bm);
+	return h;
+fail:
+	{
+		const int e = errno;
+		(void)hipStreamSynchronize(t->own);
+		if (h != nullptr) fsm_hip_text_hits_free(h);
+		if (d_bm != nullptr) (void)hipFree(d_bm);
+		errno = e;
+	}
+	return nullptr;
+}
+
+extern "C" size_t fsm_hip_text_hits_count(const struct fsm_hip_text_hits *h) { return h == nullptr ? 0 : h->m; }
+extern "C" size_t fsm_hip_text_hits_nbytes(const struct fsm_hip_text_hits *h) { return h == nullptr ? 0 : h->nbytes; }
+extern "C" const uint64_t *fsm_hip_text_hits_lines_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_lines; }
+extern "C" const uint64_t *fsm_hip_text_hits_offsets_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_off; }
+extern "C" const unsigned char *fsm_hip_text_hits_bytes_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_bytes; }
+extern "C" size_t fsm_hip_text_hits_block_lines(void) { return HITS_LINES; }
+extern "C" size_t fsm_hip_text_hits_block_bytes(void) { return HITS_BLOCK; }
+
+extern "C" int fsm_hip_text_hits_copy(const struct fsm_hip_text_hits *h, uint64_t *lines, uint64_t *out_off, void *bytes)
+{
+	if (h == nullptr || (out_off != nullptr && h->d_off == nullptr)) { errno = EINVAL; return -1; }
+	DevGuard dg(h->device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
+	TTRY(hipEventSynchronize(h->ev[5]));
+	if (lines != nullptr && h->m != 0) TTRY(hipMemcpy(lines, h->d_lines, h->m * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	if (out_off != nullptr) TTRY(hipMemcpy(out_off, h->d_off, (h->m + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	if (bytes != nullptr && h->nbytes != 0) TTRY(hipMemcpy(bytes, h->d_bytes, h->nbytes, hipMemcpyDeviceToHost));
+	return 0;
+fail:
+	return -1;
+}
+
+static double hits_ms_of(const struct fsm_hip_text_hits *h, bool select, bool gather)
+{
+	float a = 0.f, b = 0.f, c = 0.f;
+	if (h == nullptr) { errno = EINVAL; return -1.0; }
+	DevGuard dg(h->device);
+	if (!dg.ok()) { errno = ENODEV; return -1.0; }
+	TTRY(hipEventSynchronize(h->ev[5]));
+	if (select) {
+		TTRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+		TTRY(hipEventElapsedTime(&b, h->ev[2], h->ev[3]));
+	}
+	if (gather) TTRY(hipEventElapsedTime(&c, h->ev[4], h->ev[5]));
+	return (double)a + (double)b + (double)c;
+fail:
+	return -1.0;
+}
+
+extern "C" double fsm_hip_text_hits_ms(const struct fsm_hip_text_hits *h) { return hits_ms_of(h, true, true); }
+extern "C" double fsm_hip_text_hits_gather_ms(const struct fsm_hip_text_hits *h) { return hits_ms_of(h, false, true); }
