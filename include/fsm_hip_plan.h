@@ -38,7 +38,7 @@ enum {
 	                                  * and more run), 64: walk_lines32 keeps the first chunk's skip tests, 128: round 4's resource
 	                                  * bound (total - 8: loses bytes; for the test that pins the range rule: EINVAL unless FSM_HIP_TEST_KNOBS is set in the environment) */
 	FSM_HIP_KNOB_MASK          = 7,  /* retired (accepted, ignored)                                   */
-	FSM_HIP_KNOB_HOT_BYTES     = 8,  /* global layout: bytes of the table head mirrored in LDS        */
+	FSM_HIP_KNOB_HOT_BYTES     = 8,  /* global layout: bytes of the table head mirrored in LDS: whole rows, one at least, what LDS holds at most */
 	FSM_HIP_KNOB_SEG           = 9,  /* LDS-DMA mode: bytes of each row per tile, 64 or 128 (0 auto)  */
 	FSM_HIP_KNOB_PREFETCH      = 10, /* direct mode: 0 = no register double-buffer (<= 64 VGPRs)      */
 	FSM_HIP_KNOB_NT            = 11, /* LDS-DMA mode, 128-byte segments: nontemporal input loads       */
@@ -93,7 +93,8 @@ enum {
 	FSM_HIP_PLAN_COMB_RNG    = 23, /* u16[] by comb row offset: self-loop byte range lo | hi << 8 (0x0080: none) */
 	FSM_HIP_PLAN_LAZY        = 24, /* u32[] image of the sparse layout's lazy form (plan.cpp build_lazy); empty: the automaton has none */
 	FSM_HIP_PLAN_GLOB_TAB16  = 25, /* u16[S1*C], global layout of an automaton of <= 65 535 states: the next state's ROW (empty otherwise) */
-	FSM_HIP_PLAN_GLOB16_RANK = 26  /* u32[S1]: the row of every renumbered state in that table (rows in visit-frequency order); empty: row = state */
+	FSM_HIP_PLAN_GLOB16_RANK = 26, /* u32[S1]: the row of every renumbered state in that table (rows in visit-frequency order); empty: row = state */
+	FSM_HIP_PLAN_GLOB16_FIN  = 27  /* u32[S1]: FSM_HIP_PLAN_FIN in that table's ROW order (empty where the table is) */
 };
 
 /* lds_limit 0 = 160 KiB (gfx950).  NULL + errno on failure. */

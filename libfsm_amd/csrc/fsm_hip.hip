@@ -130,6 +130,10 @@ static void set_hot_bytes(fsm_hip_dfa *d, uint32_t want)
 	const uint32_t keep = d->glob16 ? 64u : 8u * 4096u;
 	if (hot + lds_bytes_btab() + keep > d->lds_limit) hot = d->lds_limit - lds_bytes_btab() - keep;
 	hot -= hot % d->glob_row_bytes;
+	/* never less than one row: a lane whose row is beyond the head still issues its LDS read, at offset 0 of the head
+	 * (GlobPol::next, Glob16Pol::next / next2), and with no head at all that address is the first byte PAST what the
+	 * per-lane kernels allocate (lds_bytes(0), no tiles behind it) */
+	if (hot < d->glob_row_bytes) hot = d->glob_row_bytes < d->glob_tab_bytes ? d->glob_row_bytes : d->glob_tab_bytes;
 	d->proto.tab_bytes = (uint32_t)hot;
 	d->table_lds = GlobPol::lds_bytes((uint32_t)hot);
 }
@@ -1685,6 +1689,7 @@ extern "C" int fsm_hip_plan_get(const struct fsm_hip_plan *pl, int what, const v
 	case FSM_HIP_PLAN_GLOB_TAB: *data = p.glob_tab.data(); *count = p.glob_tab.size(); return 0;
 	case FSM_HIP_PLAN_GLOB_TAB16: *data = p.glob_tab16.data(); *count = p.glob_tab16.size(); return 0;
 	case FSM_HIP_PLAN_GLOB16_RANK: *data = p.glob16_rank.data(); *count = p.glob16_rank.size(); return 0;
+	case FSM_HIP_PLAN_GLOB16_FIN: *data = p.glob16_fin.data(); *count = p.glob16_fin.size(); return 0;
 	case FSM_HIP_PLAN_SPARSE: *data = p.sparse_img.data(); *count = p.sparse_img.size(); return 0;
 	case FSM_HIP_PLAN_LAZY: *data = p.lazy_img.data(); *count = p.lazy_img.size(); return 0;
 	case FSM_HIP_PLAN_COMB256: *data = p.comb256.data(); *count = p.comb256.size(); return 0;

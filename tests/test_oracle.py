@@ -194,3 +194,39 @@ def test_packed_table_walker_equals_the_goldens(built):
         o = Oracle(g.flat)
         for nt in (1, 3):
             assert np.array_equal(o.table_walk_packed_mt(base, off, nt), want), g.name
+
+
+@pytest.mark.parametrize("name", ["last16", "first32", "odd_rows", "bytewise_reordered", "dying", "eager40", "eager100"])
+def test_affine_family_reference_agrees_with_the_oracle(name, built):
+    """tests/global_ref.py judges the GPU walks of tests/test_gpu_global_table.py by the automaton's formula; here the two
+    references meet: the formula's walk and the oracle's (fsm_exec restated, on the flat description) on a few hundred rows --
+    whole rows, prefixes, resumed from a carried state, and with eager outputs."""
+    import global_ref as G
+    from oracle.pyoracle import Oracle
+    flat, dense, cls = G.family(name)
+    kw = G.FAMILY[name][2]
+    o = Oracle(flat)
+    rng = np.random.RandomState(11)
+    n, L = 300, 256
+    rows = rng.randint(0, 256, (n, L)).astype(np.uint8)
+    lens = G.varlens(n, L, rng)
+    st = G.walk(dense, cls, 0, rows)
+    assert np.array_equal(o.table_walk(rows), G.ends(flat, st))
+    st_len = G.walk(dense, cls, 0, rows, lens)
+    assert np.array_equal(o.table_walk(rows, lens), G.ends(flat, st_len))
+    start = np.full(n, 0xFFFFFFFD, np.uint32)
+    assert np.array_equal(o.state_walk(rows, start, lens), G.carried(st_len))
+    assert np.array_equal(o.state_walk(rows, G.carried(st_len), None), G.carried(G.walk(dense, cls, 0, rows, state_in=st_len)))
+    if kw.get("holes"):
+        assert (st < 0).sum() > 50 and (st >= flat.nstates - kw["sinks"]).sum() > 0
+    if kw.get("endids"):
+        slots = G.endid_slots(flat.nstates, flat.is_end.astype(bool))
+        for s in set(G.ends(flat, st).tolist()) - {0xFFFFFFFF}:
+            assert np.array_equal(o.endids(s), slots[s][slots[s] >= 0]) and np.array_equal(flat.endids_of(s), G.endids_of(flat, s))
+    if kw.get("eager"):
+        E = kw["eager"]
+        for ln in (None, lens):
+            ret, end, sets = o.exec_eager(rows, ln, cap=E + 8)
+            ws, em = G.walk_eager(dense, cls, 0, rows, E, ln)
+            assert np.array_equal(end, G.ends(flat, ws))
+            assert all(np.array_equal(a, b) for a, b in zip(sets, G.eager_sets(em)))

@@ -20,6 +20,26 @@ def reference_table(flat):
     return np.vstack([d, np.full((1, 256), S, np.int64)])
 
 
+def reference_rows(flat, states):
+    """reference_table(flat)[states] without the whole table: the ranges of the states asked for, spread over their
+    bytes in one pass (a description's ranges do not overlap: the planner refuses one whose ranges do)."""
+    S = flat.nstates
+    states = np.asarray(states, np.int64)
+    eo = np.append(flat.edge_off.astype(np.int64), flat.edge_off[-1])       # state S (dead): no ranges
+    cnt = eo[states + 1] - eo[states]
+    first = np.cumsum(cnt) - cnt
+    k = np.repeat(eo[states] - first, cnt) + np.arange(int(cnt.sum()))
+    row = np.repeat(np.arange(len(states)), cnt)
+    r = flat.ranges[k]
+    to1 = r["to"].astype(np.int64) + 1
+    d = np.zeros((len(states), 257), np.int64)
+    np.add.at(d, (row, r["lo"].astype(np.int64)), to1)
+    np.add.at(d, (row, r["hi"].astype(np.int64) + 1), -to1)
+    t = np.cumsum(d, axis=1)[:, :256] - 1
+    t[t < 0] = S
+    return t
+
+
 def decode_sparse(p, S1, lds_limit=160 * 1024):
     """SparsePol::next for every (state, byte), vectorised over the 256 bytes; the LDS mirror (records and
     dense rows of the first states) is read exactly where the kernel reads it."""
@@ -138,8 +158,9 @@ def check_plan(flat, layout):
         p = Plan(flat, layout)
     except OSError:
         return False  # this layout cannot hold this DFA (ENOTSUP)
-    ref = reference_table(flat)
     S, S1, Cn = flat.nstates, p.S1, p.C
+    if len(flat.ranges) <= 100000:      # (flat.dense() is a loop over the ranges)
+        assert np.array_equal(reference_rows(flat, np.arange(S + 1)), reference_table(flat))
     cls = p.get("cls").astype(np.int64)
     new2old = p.get("new2old").astype(np.int64)
     new2old[S1 - 1] = S
@@ -166,13 +187,45 @@ def check_plan(flat, layout):
         assert em[S1 - 1] == 0
     else:
         assert len(em) == 0
-    # expected next state in NEW numbering for all (new state, byte)
-    want = old2new[ref[new2old]]            # [S1][256]
-    # absorbing threshold
-    absorbing = (want == np.arange(S1)[:, None]).all(axis=1)
-    assert absorbing[p.abs_min:].all() and not absorbing[:p.abs_min].any()
     assert p.nabsorbing == S1 - p.abs_min
     bytes_ = np.arange(256)
+
+    def want_of(lo, hi):
+        """expected next state in NEW numbering for all bytes of the new states lo .. hi - 1, and which of them are absorbing"""
+        w = old2new[reference_rows(flat, new2old[lo:hi])]
+        ab = (w == np.arange(lo, hi)[:, None]).all(axis=1)
+        assert ab[max(p.abs_min - lo, 0):].all() and not ab[:max(p.abs_min - lo, 0)].any()      # the absorbing threshold
+        return w, ab
+
+    if p.layout == LAYOUT_GLOBAL:
+        # the layout that must hold ANY automaton: decoded in slices of states, [S1][256] arrays of 64-bit numbers being
+        # hundreds of megabytes each at 65 535 states
+        tab = p.get("glob_tab").astype(np.int64)
+        # ... and its 2-byte form (Glob16Pol: the next state's ROW at row * C * 2 + class * 2) where the automaton has <= 65 535 states
+        t16 = p.get("glob_tab16").astype(np.int64)
+        fin16 = p.get("glob16_fin")
+        assert (len(t16) != 0) == (S1 <= 65535) and len(tab) == S1 * Cn and len(t16) in (0, S1 * Cn)
+        rank = p.get("glob16_rank").astype(np.int64)          # rows in visit-frequency order (empty: renumbered order)
+        if len(t16):
+            if len(rank) == 0:
+                rank = np.arange(S1)
+            assert np.array_equal(np.sort(rank), np.arange(S1)) and np.array_equal(rank[p.abs_min:], np.arange(p.abs_min, S1))
+            assert len(fin16) == S1 and np.array_equal(fin16[rank], fin)      # fin follows the rows
+        else:
+            assert len(rank) == 0 and len(fin16) == 0
+        step = max(1, (1 << 20) // 256)
+        for lo in range(0, S1, step):
+            hi = min(lo + step, S1)
+            want, _ = want_of(lo, hi)
+            st = np.arange(lo, hi)[:, None] * Cn * 4
+            e = tab[(st + cls[bytes_][None, :] * 4) // 4]
+            assert (e % (Cn * 4) == 0).all()
+            got = e // (Cn * 4)
+            if len(t16):
+                assert np.array_equal(t16[rank[lo:hi, None] * Cn + cls[bytes_][None, :]], rank[got])
+            assert np.array_equal(got, want)
+        return True
+    want, absorbing = want_of(0, S1)        # [S1][256]
     if p.layout == LAYOUT_TINY:
         col = p.get("tiny_col")
         got = np.stack([(col >> np.uint64(4 * s)) & np.uint64(15) for s in range(S1)]).astype(np.int64)
@@ -273,19 +326,7 @@ def check_plan(flat, layout):
         got = decode_sparse(p, S1)
         check_sparse_fast(p, got)
     else:
-        tab = p.get("glob_tab").astype(np.int64)
-        st = np.arange(S1)[:, None] * Cn * 4
-        e = tab[(st + cls[bytes_][None, :] * 4) // 4]
-        got = e // (Cn * 4)
-        # ... and its 2-byte form (Glob16Pol: the next state's index at row * C * 2 + class * 2) where the automaton has <= 65 535 states
-        t16 = p.get("glob_tab16").astype(np.int64)
-        assert (len(t16) != 0) == (S1 <= 65535)
-        if len(t16):
-            rank = p.get("glob16_rank").astype(np.int64)          # rows in visit-frequency order (empty: renumbered order)
-            if len(rank) == 0:
-                rank = np.arange(S1)
-            assert np.array_equal(np.sort(rank), np.arange(S1)) and np.array_equal(rank[p.abs_min:], np.arange(p.abs_min, S1))
-            assert np.array_equal(t16[rank[:, None] * Cn + cls[bytes_][None, :]], rank[got])
+        raise AssertionError("a layout this test cannot decode: %d" % p.layout)
     assert np.array_equal(got, want)
     return True
 
@@ -296,6 +337,35 @@ def test_layouts_encode_delta(path, built):
     ok = {L: check_plan(flat, L) for L in ALL_LAYOUTS}
     assert ok[LAYOUT_GLOBAL], "the global layout must hold any DFA"
     assert check_plan(flat, 0)
+
+
+AFFINE = {"below16": (65533, 4, {}), "above32": (65536, 4, {})}      # beside global_ref.FAMILY: one state to either side of the pair
+
+
+@pytest.mark.parametrize("name", ["last16", "first32", "below16", "above32", "odd_rows", "bytewise_plain", "dying", "eager40"])
+def test_global_layout_of_affine_automata(name, built):
+    """The automata of tests/global_ref.py (the GPU walks of tests/test_gpu_global_table.py run on them): up to 65 536 states
+    to either side of the switch between 2-byte and 4-byte entries, a table beyond the size at which the planner stops
+    re-ordering rows, reachable DEAD and absorbing accepts, eager outputs.  Every entry of both forms decodes to the
+    caller's transition, the rows' order leaves the absorbing states where they are and fin follows it (check_plan)."""
+    import global_ref
+    S, K, kw = global_ref.FAMILY.get(name) or AFFINE[name]
+    flat, dense, cmap = global_ref.affine(S, K, **kw)
+    # the description says what the formula says (the GPU tests judge by the formula)
+    some = np.unique(np.concatenate([np.arange(min(S, 300)), np.arange(S - 300, S), np.arange(0, S, 977)]))
+    d = dense[some][:, cmap]
+    assert np.array_equal(reference_rows(flat, some), np.where(d < 0, S, d))
+    assert check_plan(flat, LAYOUT_GLOBAL)
+    assert check_plan(flat, 0)
+    p = Plan(flat, LAYOUT_GLOBAL)
+    assert p.layout == LAYOUT_GLOBAL and p.S1 == S + 1 and p.C == K
+    # the boundary itself: the 2-byte table exists at S1 = 65 535 and not at 65 536
+    assert (len(p.get("glob_tab16")) == p.S1 * K) == (S + 1 <= 65535) and len(p.get("glob_tab16")) in (0, p.S1 * K)
+    assert len(p.get("glob_tab")) == p.S1 * K
+    # rows are re-ordered where there is a 2-byte table, no eager output and at most 4 Mi entries
+    assert (len(p.get("glob16_rank")) != 0) == (S + 1 <= 65535 and not kw.get("eager") and (S + 1) * K <= (4 << 20))
+    if name == "dying":
+        assert p.abs_min == p.S1 - 1 - kw["sinks"]         # the sinks and DEAD
 
 
 def test_auto_layout_choices(built):
