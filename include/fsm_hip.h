@@ -806,6 +806,45 @@ void fsm_hip_text_hits_free(struct fsm_hip_text_hits *h);
 size_t fsm_hip_text_hits_block_lines(void);
 size_t fsm_hip_text_hits_block_bytes(void);
 
+/* Files of a text: many files back to back in ONE text, lines cut at every file end as well, hits per file.  A grep-like
+ * caller has many files; one text per file costs an allocation, a wait and four launches each, and the plain text over the
+ * concatenation glues a file's last line without a delimiter to the next file's first and maps no hit back to its file.
+ *   file_off  nfiles + 1 byte positions: file_off[0] = 0, non-decreasing, file_off[nfiles] = nbytes.  File j is
+ *     text[file_off[j], file_off[j + 1]); equal neighbours are an empty file.
+ *   off       the sorted union, without duplicates, of the plain offsets (fsm_hip_text_open's rule) and the file_off values:
+ *     strictly increasing, n + 1 entries, off[0] = 0, off[n] = nbytes.  Equivalently: the lines of every file cut on its own,
+ *     in file order.  An empty file has no line; a file's last line has no delimiter iff the file does not end in one; a file
+ *     that begins with the delimiter begins with an empty line.  Every line still has at least one byte.
+ *   file_lines  nfiles + 1 entries with off[file_lines[j]] == file_off[j]: file_lines[0] = 0, file_lines[nfiles] = n, the lines
+ *     of file j are [file_lines[j], file_lines[j + 1]); all members of a run of equal file_off values get the same index.
+ * The result is an ordinary text: fsm_hip_text_exec{,_device}, fsm_hip_text_hits{,_device}, fsm_hip_text_offsets* and
+ * fsm_hip_text_lines take it unchanged (a line without a trailing delimiter in mid-buffer is a packed input like any other).
+ * fsm_hip_text_open_files follows fsm_hip_text_open's contract and copies file_off too; the array is checked on the host before
+ * any device work.  fsm_hip_text_open_files_device follows fsm_hip_text_open_device's: d_file_off is device memory that must
+ * outlive the text and stay as it is, it is checked in a kernel and the verdict rides the call's ONE wait on hip_stream with the
+ * line count (an added line end is counted from one text byte: a file end p with 0 < p < nbytes, once per run of equal values,
+ * adds one iff text[p - 1] != delim); the kernels that fill off and file_lines may be in flight at return, later work on
+ * hip_stream sees the arrays, the accessors that copy out wait for the text's event.  Whatever d_file_off holds, no byte outside
+ * [d_text, d_text + nbytes) is read and no store lands outside the arrays sized from the counted totals.
+ * NULL + errno: ENODEV (checked first), EINVAL (nfiles == 0, file_off NULL, an array that breaks the three conditions, delim
+ * outside 0..255; nothing is leaked and the next call works), ENOMEM.
+ *   The hits of a text of files carry file_first, nfiles + 1 entries: file_first[j] = the selected lines with index below
+ * file_lines[j], file_first[nfiles] = m.  The hits of file j are hits [file_first[j], file_first[j + 1]) of lines, out_off and
+ * bytes: their count is grep -c per file, non-zero / zero is -l / -L, lines[k] - file_lines[j] + 1 the number -n prints.  Both
+ * hits forms make it on their own stream and under their own event, also under FSM_HIP_HITS_NO_BYTES and when m == 0. */
+struct fsm_hip_text *fsm_hip_text_open_files(const void *text, size_t nbytes, int delim,
+	const uint64_t *file_off, size_t nfiles);
+struct fsm_hip_text *fsm_hip_text_open_files_device(const void *d_text, size_t nbytes, int delim,
+	const uint64_t *d_file_off, size_t nfiles, void *hip_stream);
+size_t fsm_hip_text_files(const struct fsm_hip_text *t);                       /* 0: a plain text (or NULL) */
+const uint64_t *fsm_hip_text_file_lines_device(const struct fsm_hip_text *t);  /* nfiles + 1; NULL: plain */
+int fsm_hip_text_file_lines(const struct fsm_hip_text *t, uint64_t *out);      /* copy out, waits; -1 + EINVAL: plain / NULL */
+double fsm_hip_text_files_ms(const struct fsm_hip_text *t);                    /* the added kernels alone, by HIP events; -1 + EINVAL: plain / NULL */
+size_t fsm_hip_text_files_block(void);                                         /* for tests: file ends one scan round takes */
+const uint64_t *fsm_hip_text_hits_file_first_device(const struct fsm_hip_text_hits *h);  /* nfiles + 1; NULL: plain text */
+int fsm_hip_text_hits_file_first(const struct fsm_hip_text_hits *h, uint64_t *out);      /* copy out, waits; -1 + EINVAL: plain / NULL */
+double fsm_hip_text_hits_file_first_ms(const struct fsm_hip_text_hits *h);               /* its one kernel; -1 + EINVAL: plain / NULL */
+
 /* ------------------------------------------------------------------ */
 /* synthetic input generator (benchmarks and parity tests)            */
 /* ------------------------------------------------------------------ */

@@ -1380,20 +1380,42 @@ class LinesDfa:
 
 class HipText:
     """struct fsm_hip_text *: bytes on the device plus the offsets of their lines.  data: host bytes (copied once), or
-    d_text = a device address with nbytes (borrowed: it must outlive the text; the scan is enqueued on `stream`)."""
+    d_text = a device address with nbytes (borrowed: it must outlive the text; the scan is enqueued on `stream`).
+    file_off: the text is files back to back (fsm_hip_text_open_files*): nfiles + 1 byte positions, a host array with `data`, with
+    d_text either a device address (borrowed, with nfiles=) or an array-like that is copied to the device and kept."""
 
-    def __init__(self, data=None, delim: int = 0x0A, *, d_text: int = 0, nbytes: int = 0, stream: int = 0):
+    def __init__(self, data=None, delim: int = 0x0A, *, d_text: int = 0, nbytes: int = 0, stream: int = 0, file_off=None, nfiles: int = 0):
         self._lib = lib = load_library()
         lib.fsm_hip_text_open.restype = C.c_void_p
         lib.fsm_hip_text_open_device.restype = C.c_void_p
         lib.fsm_hip_text_lines.restype = C.c_size_t
         lib.fsm_hip_text_offsets_device.restype = C.c_void_p
         lib.fsm_hip_text_scan_ms.restype = C.c_double
+        lib.fsm_hip_text_open_files.restype = C.c_void_p
+        lib.fsm_hip_text_open_files_device.restype = C.c_void_p
+        lib.fsm_hip_text_files.restype = C.c_size_t
+        lib.fsm_hip_text_file_lines_device.restype = C.c_void_p
+        lib.fsm_hip_text_files_ms.restype = C.c_double
         C.set_errno(0)
         if data is not None:
             buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data, dtype=np.uint8)
+        if data is not None and file_off is not None:
+            fo = np.ascontiguousarray(file_off, dtype=np.uint64)
+            self._h = lib.fsm_hip_text_open_files(_ptr(buf) if buf.size else None, C.c_size_t(buf.size), C.c_int(delim),
+                                                  _ptr(fo) if fo.size else None, C.c_size_t(max(fo.size, 1) - 1))
+            what = "fsm_hip_text_open_files"
+        elif data is not None:
             self._h = lib.fsm_hip_text_open(_ptr(buf) if buf.size else None, C.c_size_t(buf.size), C.c_int(delim))
             what = "fsm_hip_text_open"
+        elif file_off is not None:
+            if not isinstance(file_off, (int, np.integer)):   # a host array: its device copy lives as long as the text
+                import torch
+                fo = np.ascontiguousarray(file_off, dtype=np.uint64)
+                self._file_off = torch.from_numpy(fo.view(np.int64).copy()).cuda() if fo.size else None
+                file_off, nfiles = (self._file_off.data_ptr() if fo.size else 0), max(fo.size, 1) - 1
+            self._h = lib.fsm_hip_text_open_files_device(C.c_void_p(d_text or None), C.c_size_t(nbytes), C.c_int(delim), C.c_void_p(int(file_off) or None),
+                                                         C.c_size_t(nfiles), C.c_void_p(stream or None))
+            what = "fsm_hip_text_open_files_device"
         else:
             self._h = lib.fsm_hip_text_open_device(C.c_void_p(d_text or None), C.c_size_t(nbytes), C.c_int(delim), C.c_void_p(stream or None))
             what = "fsm_hip_text_open_device"
@@ -1428,6 +1450,26 @@ class HipText:
 
     def scan_ms(self) -> float:
         return float(self._lib.fsm_hip_text_scan_ms(C.c_void_p(self._h)))
+
+    @property
+    def files(self) -> int:
+        """fsm_hip_text_files: 0 for a plain text"""
+        return int(self._lib.fsm_hip_text_files(C.c_void_p(self._h)))
+
+    @property
+    def file_lines_ptr(self) -> int:
+        return int(self._lib.fsm_hip_text_file_lines_device(C.c_void_p(self._h)) or 0)
+
+    def file_lines(self) -> np.ndarray:
+        """fsm_hip_text_file_lines: the files + 1 line indices at which the files begin (raises EINVAL on a plain text)"""
+        out = np.empty(self.files + 1, np.uint64)
+        C.set_errno(0)
+        if self._lib.fsm_hip_text_file_lines(C.c_void_p(self._h), _ptr(out)) != 0:
+            raise _oserr("fsm_hip_text_file_lines")
+        return out
+
+    def files_ms(self) -> float:
+        return float(self._lib.fsm_hip_text_files_ms(C.c_void_p(self._h)))
 
     def exec(self, ld: LinesDfa, ids_mode: int = 0, want_end=True, want_bitmap=False, want_eager=False, out: Optional[dict] = None):
         """fsm_hip_text_exec: dict(end=, bitmap=, ids=, eager=) with the outputs asked for (out: arrays to write into instead)."""
@@ -1492,6 +1534,8 @@ class HipHits:
             getattr(lib, "fsm_hip_text_hits_" + f).restype = C.c_void_p
         lib.fsm_hip_text_hits_ms.restype = C.c_double
         lib.fsm_hip_text_hits_gather_ms.restype = C.c_double
+        lib.fsm_hip_text_hits_file_first_device.restype = C.c_void_p
+        lib.fsm_hip_text_hits_file_first_ms.restype = C.c_double
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1551,6 +1595,21 @@ class HipHits:
     def gather_ms(self) -> float:
         return float(self._lib.fsm_hip_text_hits_gather_ms(C.c_void_p(self._h)))
 
+    @property
+    def file_first_ptr(self) -> int:
+        return int(self._lib.fsm_hip_text_hits_file_first_device(C.c_void_p(self._h)) or 0)
+
+    def file_first(self) -> np.ndarray:
+        """fsm_hip_text_hits_file_first: files + 1 entries, the hits of file j are [file_first[j], file_first[j + 1])"""
+        out = np.empty(self._text.files + 1, np.uint64)
+        C.set_errno(0)
+        if self._lib.fsm_hip_text_hits_file_first(C.c_void_p(self._h), _ptr(out)) != 0:
+            raise _oserr("fsm_hip_text_hits_file_first")
+        return out
+
+    def file_first_ms(self) -> float:
+        return float(self._lib.fsm_hip_text_hits_file_first_ms(C.c_void_p(self._h)))
+
 
 
 def text_block_bytes() -> int:
@@ -1579,3 +1638,10 @@ def text_hits_block_bytes() -> int:
     lib = load_library()
     lib.fsm_hip_text_hits_block_bytes.restype = C.c_size_t
     return int(lib.fsm_hip_text_hits_block_bytes())
+
+
+def text_files_block() -> int:
+    """fsm_hip_text_files_block: file ends one round of the files scan takes."""
+    lib = load_library()
+    lib.fsm_hip_text_files_block.restype = C.c_size_t
+    return int(lib.fsm_hip_text_files_block())

@@ -278,6 +278,15 @@ struct fsm_hip_text {
 	uint64_t *d_cnt = nullptr;               /* per block: its delimiters, then their exclusive scan; + the 2 words of meta */
 	hipStream_t own = nullptr;               /* the host-pointer forms run here, never on the NULL stream */
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   /* around count + scan, around offsets; ev[3]: the offsets are there */
+	/* a text of files (fsm_hip_text_open_files*): all NULL / 0 in a plain text */
+	size_t nfiles = 0;
+	const uint64_t *d_file_off = nullptr;    /* nfiles + 1: the caller's (open_files_device) or `owned_file_off` */
+	uint64_t *owned_file_off = nullptr;
+	uint64_t *d_file_lines = nullptr;        /* nfiles + 1 */
+	uint64_t *d_plain = nullptr;             /* the plain offsets the merge reads; the host form frees them once its stream is idle */
+	uint64_t *d_frank = nullptr;             /* per file end: (added ends before it in its block) << 1 | it adds one */
+	uint64_t *d_fpairs = nullptr;            /* per block of file ends: (added ends, invalid entries), then their exclusive scan */
+	hipEvent_t fev[3] = {nullptr, nullptr, nullptr};   /* around mark + scan; fev[2]: the plain offsets are there, the merge runs to ev[3] */
 };
 
 extern "C" void fsm_hip_text_free(struct fsm_hip_text *t)
@@ -288,7 +297,13 @@ extern "C" void fsm_hip_text_free(struct fsm_hip_text *t)
 		DevGuard dg(t->device);
 		if (t->ev[3] != nullptr) (void)hipEventSynchronize(t->ev[3]);   /* the scan may still be reading the caller's bytes */
 		for (hipEvent_t ev : t->ev) if (ev != nullptr) (void)hipEventDestroy(ev);
+		for (hipEvent_t ev : t->fev) if (ev != nullptr) (void)hipEventDestroy(ev);
 		if (t->own != nullptr) (void)hipStreamDestroy(t->own);
+		if (t->owned_file_off != nullptr) (void)hipFree(t->owned_file_off);
+		if (t->d_file_lines != nullptr) (void)hipFree(t->d_file_lines);
+		if (t->d_plain != nullptr) (void)hipFree(t->d_plain);
+		if (t->d_frank != nullptr) (void)hipFree(t->d_frank);
+		if (t->d_fpairs != nullptr) (void)hipFree(t->d_fpairs);
 		if (t->d_off != nullptr) (void)hipFree(t->d_off);
 		if (t->d_cnt != nullptr) (void)hipFree(t->d_cnt);
 		if (t->owned != nullptr) (void)hipFree(t->owned);
@@ -417,7 +432,7 @@ extern "C" double fsm_hip_text_scan_ms(const struct fsm_hip_text *t)
 	if (!dg.ok()) { errno = ENODEV; return -1.0; }
 	TTRY(hipEventSynchronize(t->ev[3]));
 	TTRY(hipEventElapsedTime(&a, t->ev[0], t->ev[1]));
-	TTRY(hipEventElapsedTime(&b, t->ev[2], t->ev[3]));
+	TTRY(hipEventElapsedTime(&b, t->ev[2], t->nfiles != 0 ? t->fev[2] : t->ev[3]));   /* files: the merge after them is not the scan's */
 	return (double)a + (double)b;
 fail:
 	return -1.0;
@@ -729,6 +744,23 @@ hits_gather(const unsigned char *text, uint64_t nbytes, const uint64_t *out_off,
 	}
 }
 
+/* the hits of a text of files: one lane per file end, file_first[j] = the selected lines with index below file_lines[j], a
+ * lower-bound search in the ascending lines[0, m).  m == 0: every entry is 0 and lines (NULL then) is never read. */
+__global__ void __launch_bounds__(HITS_THREADS)
+hits_file_first(const uint64_t *lines, uint64_t m, const uint64_t *file_lines, uint64_t nends, uint64_t *file_first)
+{
+	const uint64_t j = (uint64_t)blockIdx.x * HITS_THREADS + threadIdx.x;
+	if (j >= nends) return;
+	const glb_u64p ln = (glb_u64p)(uintptr_t)lines;
+	const uint64_t v = ((glb_u64p)(uintptr_t)file_lines)[j];
+	uint64_t lo = 0, hi = m;
+	while (lo < hi) {
+		const uint64_t mid = lo + (hi - lo) / 2u;
+		if (ln[mid] < v) lo = mid + 1u; else hi = mid;
+	}
+	((glb_u64w)(uintptr_t)file_first)[j] = lo;
+}
+
 }   // namespace
 
 struct fsm_hip_text_hits {
@@ -741,6 +773,9 @@ struct fsm_hip_text_hits {
 	uint64_t *d_first = nullptr;             /* per output block + 1: the rank of the line that covers its first byte */
 	unsigned char *d_bytes = nullptr;        /* nbytes, rounded up to whole blocks */
 	hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   /* around count + scan, emit, gather; ev[5]: all is there */
+	size_t nfiles = 0;                       /* a text of files: its hits per file; 0 / NULL for a plain text */
+	uint64_t *d_file_first = nullptr;        /* nfiles + 1 */
+	hipEvent_t fev[2] = {nullptr, nullptr};  /* around hits_file_first, between emit and gather */
 };
 
 extern "C" void fsm_hip_text_hits_free(struct fsm_hip_text_hits *h)
@@ -751,6 +786,8 @@ extern "C" void fsm_hip_text_hits_free(struct fsm_hip_text_hits *h)
 		DevGuard dg(h->device);
 		if (h->ev[5] != nullptr) (void)hipEventSynchronize(h->ev[5]);
 		for (hipEvent_t ev : h->ev) if (ev != nullptr) (void)hipEventDestroy(ev);
+		for (hipEvent_t ev : h->fev) if (ev != nullptr) (void)hipEventDestroy(ev);
+		if (h->d_file_first != nullptr) (void)hipFree(h->d_file_first);
 		if (h->d_pairs != nullptr) (void)hipFree(h->d_pairs);
 		if (h->d_lines != nullptr) (void)hipFree(h->d_lines);
 		if (h->d_off != nullptr) (void)hipFree(h->d_off);
@@ -818,6 +855,17 @@ static struct fsm_hip_text_hits *text_hits_run(const struct fsm_hip_text *t, con
 			TTRY(hipGetLastError());
 		}
 		TTRY(hipEventRecord(h->ev[3], s));
+		if (t->nfiles != 0) {   /* also under NO_BYTES and when m == 0 */
+			const uint64_t nends = (uint64_t)t->nfiles + 1u;
+			h->nfiles = t->nfiles;
+			for (hipEvent_t &ev : h->fev) TTRY(hipEventCreate(&ev));
+			TTRY(hipMalloc((void **)&h->d_file_first, nends * sizeof(uint64_t)));
+			TTRY(hipEventRecord(h->fev[0], s));
+			hipLaunchKernelGGL(hits_file_first, dim3((unsigned)((nends + HITS_THREADS - 1u) / HITS_THREADS)), dim3(HITS_THREADS), 0, s,
+			                   (const uint64_t *)h->d_lines, (uint64_t)h->m, (const uint64_t *)t->d_file_lines, nends, h->d_file_first);
+			TTRY(hipGetLastError());
+			TTRY(hipEventRecord(h->fev[1], s));
+		}
 		TTRY(hipEventRecord(h->ev[4], s));
 		if (ngb != 0) {
 			uint64_t gg = max_workgroups(t->device);
@@ -910,6 +958,36 @@ fail:
 	return -1;
 }
 
+extern "C" const uint64_t *fsm_hip_text_hits_file_first_device(const struct fsm_hip_text_hits *h)
+{
+	return h == nullptr ? nullptr : h->d_file_first;
+}
+
+extern "C" int fsm_hip_text_hits_file_first(const struct fsm_hip_text_hits *h, uint64_t *out)
+{
+	if (h == nullptr || out == nullptr || h->d_file_first == nullptr) { errno = EINVAL; return -1; }
+	DevGuard dg(h->device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
+	TTRY(hipEventSynchronize(h->ev[5]));
+	TTRY(hipMemcpy(out, h->d_file_first, (h->nfiles + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	return 0;
+fail:
+	return -1;
+}
+
+extern "C" double fsm_hip_text_hits_file_first_ms(const struct fsm_hip_text_hits *h)
+{
+	float a = 0.f;
+	if (h == nullptr || h->d_file_first == nullptr) { errno = EINVAL; return -1.0; }
+	DevGuard dg(h->device);
+	if (!dg.ok()) { errno = ENODEV; return -1.0; }
+	TTRY(hipEventSynchronize(h->ev[5]));
+	TTRY(hipEventElapsedTime(&a, h->fev[0], h->fev[1]));
+	return (double)a;
+fail:
+	return -1.0;
+}
+
 static double hits_ms_of(const struct fsm_hip_text_hits *h, bool select, bool gather)
 {
 	float a = 0.f, b = 0.f, c = 0.f;
@@ -929,3 +1007,275 @@ fail:
 
 extern "C" double fsm_hip_text_hits_ms(const struct fsm_hip_text_hits *h) { return hits_ms_of(h, true, true); }
 extern "C" double fsm_hip_text_hits_gather_ms(const struct fsm_hip_text_hits *h) { return hits_ms_of(h, false, true); }
+
+/* ---- files of a text: lines cut at every file end as well ----------------------------------------------------------
+ * file_off[0 .. nfiles] are byte positions (0 first, non-decreasing, nbytes last); the offsets of the text become the sorted
+ * union of the plain offsets P (the scan above, untouched) and the file ends.  A file end p adds an entry iff it is not in P
+ * already: 0 < p < nbytes and text[p - 1] != delim -- one text byte tells, so the added ends S are COUNTED before any offset
+ * exists and their total rides the one wait with the delimiter count.  Of a run of equal ends the LAST member carries the
+ * flag: then the flags before any member j of the run belong to smaller values only, and
+ *     R(j) = #{S < file_off[j]} = scanned pair of j's block + flags before j in its block
+ * holds for every member alike.  The passes:
+ *     files_mark    one lane per file end: validates it against its neighbours, flags "adds an entry", leaves the flags before
+ *                   it in its block and the block's (flags, invalid entries)                       (reads file_off, one text byte)
+ *     files_scan    exclusive scan of the pairs by one workgroup in rounds; the totals for the host  (text_scan's shape)
+ *     files_merge   one lane per entry of P and per file end, a binary search each:
+ *                     P[i]         -> off[i + #{S < P[i]}]            #{S < v} = R(lower_bound(file_off, v))
+ *                     added end j  -> off[lower_bound(P, file_off[j]) + R(j)]
+ *                     file_lines[j] =   lower_bound(P, file_off[j]) + R(j)    for every j
+ * Every slot of off is written exactly once when the array is what files_mark validated.  Loads from the text are made only
+ * for 0 < p < nbytes and stores only below the counted totals: a file_off that changes between the passes gives wrong arrays,
+ * never an overrun. */
+namespace {
+
+constexpr uint32_t FILES_WAVES = 4;
+constexpr uint32_t FILES_THREADS = FILES_WAVES * 64u;       /* file ends a workgroup of files_mark takes */
+constexpr uint32_t FILES_SCAN_THREADS = 256;                /* pairs a round of files_scan takes */
+
+__global__ void __launch_bounds__(FILES_THREADS)
+files_mark(const unsigned char *text, uint64_t nbytes, uint32_t delim, const uint64_t *file_off, uint64_t nends, uint64_t *rank,
+           uint64_t *pairs)
+{
+	__shared__ uint32_t wtot[FILES_WAVES][2];
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	const glb_u64p fo = (glb_u64p)(uintptr_t)file_off;
+	const uint64_t j = (uint64_t)blockIdx.x * FILES_THREADS + threadIdx.x;
+	bool flag = false, bad = false;
+	if (j < nends) {
+		const uint64_t p = fo[j];
+		bad = j == 0 ? p != 0 : fo[j - 1u] > p;
+		if (j + 1u == nends) bad = bad || p != nbytes;
+		const bool last_of_run = j + 1u == nends || fo[j + 1u] != p;
+		if (last_of_run && p > 0 && p < nbytes) flag = ((glb_u8p)(uintptr_t)text)[p - 1u] != delim;   /* p - 1 is inside the text */
+	}
+	const uint64_t mf = __ballot(flag), mb = __ballot(bad);
+	if (lane == 0) { wtot[wave][0] = (uint32_t)__builtin_popcountll(mf); wtot[wave][1] = mb != 0 ? 1u : 0u; }
+	__syncthreads();
+	uint32_t before = (uint32_t)__builtin_popcountll(mf & ((1ull << lane) - 1ull)), tot = 0, anybad = 0;
+#pragma unroll
+	for (uint32_t w = 0; w < FILES_WAVES; w++) {
+		before += w < wave ? wtot[w][0] : 0u;
+		tot += wtot[w][0];
+		anybad |= wtot[w][1];
+	}
+	if (j < nends) ((glb_u64w)(uintptr_t)rank)[j] = (uint64_t)before << 1 | (flag ? 1u : 0u);
+	if (threadIdx.x == 0) *(glb_u64x2w)(uintptr_t)(pairs + 2u * blockIdx.x) = u64x2{tot, anybad};
+}
+
+/* exclusive scan of the pairs in place by one workgroup, FILES_SCAN_THREADS a round; meta[0] = the added ends, meta[1] != 0 iff
+ * the array is invalid: the second half of the 32 bytes the host waits for */
+__global__ void __launch_bounds__(FILES_SCAN_THREADS)
+files_scan(uint64_t *pairs, uint64_t nblocks, uint64_t *meta)
+{
+	__shared__ uint64_t wtot[FILES_SCAN_THREADS / 64u][2];
+	__shared__ uint64_t carry[2];
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	if (threadIdx.x == 0) { carry[0] = 0; carry[1] = 0; }
+	__syncthreads();
+	for (uint64_t b0 = 0; b0 < nblocks; b0 += FILES_SCAN_THREADS) {
+		const uint64_t b = b0 + threadIdx.x;
+		const u64x2 mine = b < nblocks ? *(glb_u64x2p)(uintptr_t)(pairs + 2u * b) : u64x2{0u, 0u};
+		uint64_t xc = mine.x, xb = mine.y;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const uint64_t yc = __shfl_up(xc, d, 64), yb = __shfl_up(xb, d, 64);
+			if (lane >= (uint32_t)d) { xc += yc; xb += yb; }
+		}
+		if (lane == 63u) { wtot[wave][0] = xc; wtot[wave][1] = xb; }
+		__syncthreads();
+		uint64_t bc = carry[0], bb = carry[1];
+		for (uint32_t w = 0; w < wave; w++) { bc += wtot[w][0]; bb += wtot[w][1]; }
+		if (b < nblocks) *(glb_u64x2w)(uintptr_t)(pairs + 2u * b) = u64x2{bc + xc - mine.x, bb + xb - mine.y};
+		__syncthreads();
+		if (threadIdx.x == FILES_SCAN_THREADS - 1u) { carry[0] = bc + xc; carry[1] = bb + xb; }
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) {
+		glb_u64w m = (glb_u64w)(uintptr_t)meta;
+		m[0] = carry[0];
+		m[1] = carry[1];
+	}
+}
+
+/* the first index in a[0, n) whose entry is >= v (n if none) */
+__device__ __forceinline__ uint64_t lower_bound_glb(glb_u64p a, uint64_t n, uint64_t v)
+{
+	uint64_t lo = 0, hi = n;
+	while (lo < hi) {
+		const uint64_t mid = lo + (hi - lo) / 2u;
+		if (a[mid] < v) lo = mid + 1u; else hi = mid;
+	}
+	return lo;
+}
+
+/* lanes [0, np1) take the plain offsets, lanes [np1, np1 + nends) the file ends; n + 1 = np1 + added entries of off */
+__global__ void __launch_bounds__(FILES_THREADS)
+files_merge(const uint64_t *plain, uint64_t np1, const uint64_t *file_off, uint64_t nends, const uint64_t *rank, const uint64_t *base,
+            uint64_t added, uint64_t n, uint64_t *off, uint64_t *file_lines)
+{
+	const glb_u64p pl = (glb_u64p)(uintptr_t)plain, fo = (glb_u64p)(uintptr_t)file_off, rk = (glb_u64p)(uintptr_t)rank,
+	               bs = (glb_u64p)(uintptr_t)base;
+	const glb_u64w out = (glb_u64w)(uintptr_t)off;
+	const uint64_t g = (uint64_t)blockIdx.x * FILES_THREADS + threadIdx.x;
+	if (g < np1) {
+		const uint64_t v = pl[g];
+		const uint64_t lb = lower_bound_glb(fo, nends, v);
+		const uint64_t dst = g + (lb < nends ? bs[2u * (lb / FILES_THREADS)] + (rk[lb] >> 1) : added);
+		if (dst <= n) out[dst] = v;
+	} else if (g - np1 < nends) {
+		const uint64_t j = g - np1, v = fo[j], r = rk[j];
+		const uint64_t dst = lower_bound_glb(pl, np1, v) + bs[2u * (j / FILES_THREADS)] + (r >> 1);
+		((glb_u64w)(uintptr_t)file_lines)[j] = dst;
+		if ((r & 1u) != 0u && dst <= n) out[dst] = v;
+	}
+}
+
+}   // namespace
+
+/* count + scan of the delimiters and mark + scan of the file ends, ONE wait, then the plain offsets and the merge: on stream s */
+static int text_scan_files(struct fsm_hip_text *t, hipStream_t s)
+{
+	const uint64_t nbytes = t->nbytes, nends = (uint64_t)t->nfiles + 1u;
+	const uint32_t splat = (uint32_t)t->delim * 0x01010101u;
+	const uint64_t nblocks = (nbytes + TEXT_BLOCK - 1u) / TEXT_BLOCK, nfb = (nends + FILES_THREADS - 1u) / FILES_THREADS;
+	uint64_t meta[4] = {0, 0, 0, 0}, grid = 1, per = 1, np1 = 1, nmerge = 0;
+	if (nfb > 0x7fffffffu) { errno = ENOMEM; return -1; }
+	for (hipEvent_t &ev : t->ev) TTRY(hipEventCreate(&ev));
+	for (hipEvent_t &ev : t->fev) TTRY(hipEventCreate(&ev));
+	TTRY(hipMalloc((void **)&t->d_cnt, (nblocks + 4u) * sizeof(uint64_t)));   /* + the 4 words of meta */
+	TTRY(hipMalloc((void **)&t->d_frank, nends * sizeof(uint64_t)));
+	TTRY(hipMalloc((void **)&t->d_fpairs, 2u * nfb * sizeof(uint64_t)));
+	TTRY(hipMalloc((void **)&t->d_file_lines, nends * sizeof(uint64_t)));
+	{
+		uint64_t *d_meta = t->d_cnt + nblocks;
+		TTRY(hipEventRecord(t->ev[0], s));
+		if (nbytes != 0) {
+			grid = max_workgroups(t->device);
+			if (grid > nblocks) grid = nblocks;
+			per = (nblocks + grid - 1u) / grid;
+			grid = (nblocks + per - 1u) / per;
+			hipLaunchKernelGGL(text_count, dim3((unsigned)grid), dim3(TEXT_THREADS), 0, s, t->d_text, nbytes, splat, nblocks, per, t->d_cnt);
+			TTRY(hipGetLastError());
+			hipLaunchKernelGGL(text_scan, dim3(1), dim3(1024), 0, s, t->d_cnt, nblocks, t->d_text, nbytes, (uint32_t)t->delim, d_meta);
+			TTRY(hipGetLastError());
+		} else {
+			TTRY(hipMemsetAsync(d_meta, 0, 2u * sizeof(uint64_t), s));
+		}
+		TTRY(hipEventRecord(t->ev[1], s));
+		TTRY(hipEventRecord(t->fev[0], s));
+		hipLaunchKernelGGL(files_mark, dim3((unsigned)nfb), dim3(FILES_THREADS), 0, s, t->d_text, nbytes, (uint32_t)t->delim, t->d_file_off,
+		                   nends, t->d_frank, t->d_fpairs);
+		TTRY(hipGetLastError());
+		hipLaunchKernelGGL(files_scan, dim3(1), dim3(FILES_SCAN_THREADS), 0, s, t->d_fpairs, nfb, d_meta + 2);
+		TTRY(hipGetLastError());
+		TTRY(hipEventRecord(t->fev[1], s));
+		TTRY(hipMemcpyAsync(meta, d_meta, sizeof meta, hipMemcpyDeviceToHost, s));
+		TTRY(hipStreamSynchronize(s));
+		if (meta[3] != 0) { errno = EINVAL; goto fail; }
+		np1 = nbytes == 0 ? 1u : meta[0] + (meta[1] != 0 ? 0u : 1u) + 1u;   /* the plain offsets: fsm_hip_text_open's n + 1 */
+		t->n = (size_t)(np1 - 1u + meta[2]);
+		nmerge = (np1 + nends + FILES_THREADS - 1u) / FILES_THREADS;
+		if (nmerge > 0x7fffffffu) { errno = ENOMEM; goto fail; }
+		TTRY(hipMalloc((void **)&t->d_plain, np1 * sizeof(uint64_t)));
+		TTRY(hipMalloc((void **)&t->d_off, ((uint64_t)t->n + 1u) * sizeof(uint64_t)));
+		TTRY(hipEventRecord(t->ev[2], s));
+		if (nbytes != 0) {
+			hipLaunchKernelGGL(text_offsets, dim3((unsigned)grid), dim3(TEXT_THREADS), 0, s, t->d_text, nbytes, splat, nblocks, per,
+			                   (const uint64_t *)t->d_cnt, meta[0], np1 - 1u, t->d_plain);
+			TTRY(hipGetLastError());
+		} else {
+			TTRY(hipMemsetAsync(t->d_plain, 0, sizeof(uint64_t), s));
+		}
+		TTRY(hipEventRecord(t->fev[2], s));
+		hipLaunchKernelGGL(files_merge, dim3((unsigned)nmerge), dim3(FILES_THREADS), 0, s, (const uint64_t *)t->d_plain, np1, t->d_file_off,
+		                   nends, (const uint64_t *)t->d_frank, (const uint64_t *)t->d_fpairs, meta[2], (uint64_t)t->n, t->d_off,
+		                   t->d_file_lines);
+		TTRY(hipGetLastError());
+		TTRY(hipEventRecord(t->ev[3], s));
+	}
+	return 0;
+fail:
+	{
+		const int e = errno;
+		(void)hipStreamSynchronize(s);   /* nothing of this text is in flight when it is freed */
+		errno = e;
+	}
+	return -1;
+}
+
+extern "C" struct fsm_hip_text *fsm_hip_text_open_files_device(const void *d_text, size_t nbytes, int delim, const uint64_t *d_file_off,
+	size_t nfiles, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if ((d_text == nullptr && nbytes != 0) || d_file_off == nullptr || nfiles == 0) { errno = EINVAL; return nullptr; }
+	struct fsm_hip_text *t = text_new(nbytes, delim);
+	if (t == nullptr) return nullptr;
+	t->d_text = static_cast<const unsigned char *>(d_text);
+	t->nfiles = nfiles;
+	t->d_file_off = d_file_off;
+	if (text_scan_files(t, static_cast<hipStream_t>(hip_stream)) != 0) {
+		fsm_hip_text_free(t);
+		return nullptr;
+	}
+	return t;
+}
+
+extern "C" struct fsm_hip_text *fsm_hip_text_open_files(const void *text, size_t nbytes, int delim, const uint64_t *file_off, size_t nfiles)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if ((text == nullptr && nbytes != 0) || file_off == nullptr || nfiles == 0) { errno = EINVAL; return nullptr; }
+	if (file_off[0] != 0 || file_off[nfiles] != nbytes) { errno = EINVAL; return nullptr; }
+	for (size_t j = 0; j < nfiles; j++)
+		if (file_off[j] > file_off[j + 1u]) { errno = EINVAL; return nullptr; }
+	struct fsm_hip_text *t = text_new(nbytes, delim);
+	if (t == nullptr) return nullptr;
+	t->nfiles = nfiles;
+	if (nbytes != 0) {
+		TTRY(hipMalloc((void **)&t->owned, nbytes));
+		TTRY(hipMemcpyAsync(t->owned, text, nbytes, hipMemcpyHostToDevice, t->own));
+	}
+	t->d_text = t->owned;
+	TTRY(hipMalloc((void **)&t->owned_file_off, ((uint64_t)nfiles + 1u) * sizeof(uint64_t)));
+	TTRY(hipMemcpyAsync(t->owned_file_off, file_off, ((uint64_t)nfiles + 1u) * sizeof(uint64_t), hipMemcpyHostToDevice, t->own));
+	t->d_file_off = t->owned_file_off;
+	if (text_scan_files(t, t->own) != 0) goto fail;
+	TTRY(hipStreamSynchronize(t->own));
+	(void)hipFree(t->d_plain);   /* the merge has read them */
+	t->d_plain = nullptr;
+	return t;
+fail:
+	fsm_hip_text_free(t);
+	return nullptr;
+}
+
+extern "C" size_t fsm_hip_text_files(const struct fsm_hip_text *t) { return t == nullptr ? 0 : t->nfiles; }
+
+extern "C" const uint64_t *fsm_hip_text_file_lines_device(const struct fsm_hip_text *t) { return t == nullptr ? nullptr : t->d_file_lines; }
+
+extern "C" int fsm_hip_text_file_lines(const struct fsm_hip_text *t, uint64_t *out)
+{
+	if (t == nullptr || out == nullptr || t->nfiles == 0) { errno = EINVAL; return -1; }
+	DevGuard dg(t->device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
+	TTRY(hipEventSynchronize(t->ev[3]));
+	TTRY(hipMemcpy(out, t->d_file_lines, (t->nfiles + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	return 0;
+fail:
+	return -1;
+}
+
+extern "C" double fsm_hip_text_files_ms(const struct fsm_hip_text *t)
+{
+	float a = 0.f, b = 0.f;
+	if (t == nullptr || t->nfiles == 0) { errno = EINVAL; return -1.0; }
+	DevGuard dg(t->device);
+	if (!dg.ok()) { errno = ENODEV; return -1.0; }
+	TTRY(hipEventSynchronize(t->ev[3]));
+	TTRY(hipEventElapsedTime(&a, t->fev[0], t->fev[1]));
+	TTRY(hipEventElapsedTime(&b, t->fev[2], t->ev[3]));
+	return (double)a + (double)b;
+fail:
+	return -1.0;
+}
+
+extern "C" size_t fsm_hip_text_files_block(void) { return (size_t)FILES_THREADS * FILES_SCAN_THREADS; }
