@@ -845,6 +845,41 @@ const uint64_t *fsm_hip_text_hits_file_first_device(const struct fsm_hip_text_hi
 int fsm_hip_text_hits_file_first(const struct fsm_hip_text_hits *h, uint64_t *out);      /* copy out, waits; -1 + EINVAL: plain / NULL */
 double fsm_hip_text_hits_file_first_ms(const struct fsm_hip_text_hits *h);               /* its one kernel; -1 + EINVAL: plain / NULL */
 
+/* Context: the hits of the lines within reach of a selected line of the same file (grep -A NUM, -B NUM, -C NUM), with the two
+ * marks a printer needs, and no host pass over the n lines.  The rule, for a text of n lines:
+ *   S[i]     = i < n and (bit i of the bitmap ^ FSM_HIP_HITS_INVERT given); the spare bits of the last word are ignored.  INVERT
+ *              applies BEFORE the widening (grep -v -A).
+ *   file(i)  = 0 for a plain text; for a text of files the j with file_lines[j] <= i < file_lines[j + 1].
+ *   W[i]     holds iff there is a p with S[p], file(p) == file(i) and p - before <= i <= p + after, over the integers: before
+ *              and after are any uint64_t, before = after = 2^64 - 1 means "the whole file" and does not wrap.
+ *   The hits are those of W: m, lines, out_off, bytes and file_first are exactly what fsm_hip_text_hits_device would make of a
+ *   bitmap holding W (FSM_HIP_HITS_NO_BYTES still makes lines, core, group and file_first).
+ *   core     ceil(m / 64) words, bit k set iff S[lines[k]]: the hit is a selected line (grep's ':'), not context ('-').  The
+ *            spare bits are 0.
+ *   group    ceil(m / 64) words, bit k set iff k == 0, or lines[k] != lines[k - 1] + 1, or file(lines[k]) != file(lines[k - 1]):
+ *            grep prints "--" before every group but the first.  The spare bits are 0.
+ *   core_count = the number of i with S[i] (what -c prints: context does not change it); groups = the set group bits.
+ *   before = after = 0 gives the lines of the plain hits, core all ones and group marking the runs; no selected line gives
+ *   m == 0 whatever the context.
+ * The two forms follow the contracts of fsm_hip_text_hits and fsm_hip_text_hits_device word for word: the same two flags (an
+ * unknown bit: EINVAL), ENODEV checked first, the device form waits for the text's offsets event and synchronises hip_stream
+ * ONCE (m, the byte total and core_count ride that wait); emit, marks and gather may be in flight at return; stores land only
+ * below the counted totals and no byte outside the text is read, whatever the bitmap holds or becomes.  The cost does not grow
+ * with before or after.  The widened bitmap belongs to the hits and is freed with them.
+ * On hits made by fsm_hip_text_hits{,_device}: the two _device accessors return NULL, _marks returns -1 + EINVAL, _core_count and
+ * _groups return 0, _context_ms returns -1 + EINVAL. */
+struct fsm_hip_text_hits *fsm_hip_text_hits_context(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t,
+	unsigned flags, uint64_t before, uint64_t after);
+struct fsm_hip_text_hits *fsm_hip_text_hits_context_device(const struct fsm_hip_text *t, const uint64_t *d_bitmap,
+	unsigned flags, uint64_t before, uint64_t after, void *hip_stream);
+const uint64_t *fsm_hip_text_hits_core_device(const struct fsm_hip_text_hits *h);    /* ceil(m / 64) words; NULL: m == 0 or hits without context */
+const uint64_t *fsm_hip_text_hits_group_device(const struct fsm_hip_text_hits *h);   /* likewise */
+int fsm_hip_text_hits_marks(const struct fsm_hip_text_hits *h, uint64_t *core, uint64_t *group);  /* copy out whichever are not NULL; waits */
+size_t fsm_hip_text_hits_core_count(const struct fsm_hip_text_hits *h);
+size_t fsm_hip_text_hits_groups(const struct fsm_hip_text_hits *h);                  /* may wait for the hits' event */
+double fsm_hip_text_hits_context_ms(const struct fsm_hip_text_hits *h);              /* the added kernels alone, by HIP events */
+size_t fsm_hip_text_context_scan_block(void);                                        /* for tests: blocks of lines one round of the context scan takes */
+
 /* ------------------------------------------------------------------ */
 /* synthetic input generator (benchmarks and parity tests)            */
 /* ------------------------------------------------------------------ */

@@ -10,5 +10,5 @@ from .capi import (  # noqa: F401
     IN_DIRECT, IN_LDSDMA, IN_GENERIC, IN_RAGGED, KNOB_PICK_MEAN, KNOB_SPARSE_FAST, KNOB_LAZY_DYN, KNOB_LAZY_LINES, LIB_PATH, pack_affixes, gen_pack_rows_device, gather_probe_ms, gen_affix_inputs_host, gen_affix_inputs_device, stream_read_probe_gbps,
     DEFER_UPLOAD, MultiBatch, MultiBatchIds, exec_multi, exec_multi_device, exec_multi_ids, exec_multi_ids_device, MultiBatchEager, exec_multi_eager, exec_multi_eager_device, MultiPrepared, multi_last_launches, multi_last_fused_jobs, multi_assign, lds_chain_probe_gbps, waves_by_occupancy,
     identity_byte, LinesDfa, HipText, text_block_bytes, text_max_workgroups,
-    HipHits, HITS_INVERT, HITS_NO_BYTES, text_hits_block_lines, text_hits_block_bytes, text_files_block,
+    HipHits, HITS_INVERT, HITS_NO_BYTES, text_hits_block_lines, text_hits_block_bytes, text_files_block, text_context_scan_block,
 )

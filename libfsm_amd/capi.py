@@ -1513,6 +1513,31 @@ class HipText:
             raise _oserr("fsm_hip_text_hits_device")
         return HipHits(h, self)
 
+    def hits_context(self, ld: LinesDfa, before: int, after: int, invert: bool = False, want_bytes: bool = True) -> "HipHits":
+        """fsm_hip_text_hits_context: the hits of the lines within `before` / `after` lines of an accepted line of the same file
+        (grep -B / -A; any value below 2 ** 64), with the core and group marks."""
+        lib = self._lib
+        lib.fsm_hip_text_hits_context.restype = C.c_void_p
+        C.set_errno(0)
+        h = lib.fsm_hip_text_hits_context(C.c_void_p(ld.handle), C.c_void_p(self._h), C.c_uint(hits_flags(invert, want_bytes)),
+                                          C.c_uint64(before), C.c_uint64(after))
+        if not h:
+            raise _oserr("fsm_hip_text_hits_context")
+        return HipHits(h, self)
+
+    def hits_context_device(self, d_bitmap: int, before: int, after: int, invert: bool = False, want_bytes: bool = True, stream: int = 0,
+                            flags: Optional[int] = None) -> "HipHits":
+        """fsm_hip_text_hits_context_device: as hits_device, widened by the context."""
+        lib = self._lib
+        lib.fsm_hip_text_hits_context_device.restype = C.c_void_p
+        C.set_errno(0)
+        h = lib.fsm_hip_text_hits_context_device(C.c_void_p(self._h), C.c_void_p(d_bitmap or None),
+                                                 C.c_uint(hits_flags(invert, want_bytes) if flags is None else flags),
+                                                 C.c_uint64(before), C.c_uint64(after), C.c_void_p(stream or None))
+        if not h:
+            raise _oserr("fsm_hip_text_hits_context_device")
+        return HipHits(h, self)
+
 
 HITS_INVERT, HITS_NO_BYTES = 1, 2
 
@@ -1528,14 +1553,15 @@ class HipHits:
     def __init__(self, handle, text: HipText):
         self._lib = lib = load_library()
         self._h, self._text = handle, text
-        for f in ("count", "nbytes"):
+        for f in ("count", "nbytes", "core_count", "groups"):
             getattr(lib, "fsm_hip_text_hits_" + f).restype = C.c_size_t
-        for f in ("lines_device", "offsets_device", "bytes_device"):
+        for f in ("lines_device", "offsets_device", "bytes_device", "core_device", "group_device"):
             getattr(lib, "fsm_hip_text_hits_" + f).restype = C.c_void_p
         lib.fsm_hip_text_hits_ms.restype = C.c_double
         lib.fsm_hip_text_hits_gather_ms.restype = C.c_double
         lib.fsm_hip_text_hits_file_first_device.restype = C.c_void_p
         lib.fsm_hip_text_hits_file_first_ms.restype = C.c_double
+        lib.fsm_hip_text_hits_context_ms.restype = C.c_double
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1610,6 +1636,51 @@ class HipHits:
     def file_first_ms(self) -> float:
         return float(self._lib.fsm_hip_text_hits_file_first_ms(C.c_void_p(self._h)))
 
+    # hits with context (HipText.hits_context*); on plain hits: 0 from the pointers and the counts, EINVAL from the copies
+    @property
+    def core_ptr(self) -> int:
+        return int(self._lib.fsm_hip_text_hits_core_device(C.c_void_p(self._h)) or 0)
+
+    @property
+    def group_ptr(self) -> int:
+        return int(self._lib.fsm_hip_text_hits_group_device(C.c_void_p(self._h)) or 0)
+
+    @property
+    def core_count(self) -> int:
+        """fsm_hip_text_hits_core_count: the selected lines, context left out (grep -c)"""
+        return int(self._lib.fsm_hip_text_hits_core_count(C.c_void_p(self._h)))
+
+    @property
+    def groups(self) -> int:
+        return int(self._lib.fsm_hip_text_hits_groups(C.c_void_p(self._h)))
+
+    def _marks(self, which: int) -> np.ndarray:
+        m = self.count
+        words = np.zeros((m + 63) // 64, np.uint64)
+        C.set_errno(0)
+        if self._lib.fsm_hip_text_hits_marks(C.c_void_p(self._h), _ptr(words) if which == 0 else None, _ptr(words) if which == 1 else None) != 0:
+            raise _oserr("fsm_hip_text_hits_marks")
+        return np.unpackbits(words.view(np.uint8), bitorder="little")[:m].astype(bool)
+
+    def core(self) -> np.ndarray:
+        """one bool per hit: the hit is a selected line, not context"""
+        return self._marks(0)
+
+    def group(self) -> np.ndarray:
+        """one bool per hit: the hit begins a group (grep prints -- before every group but the first)"""
+        return self._marks(1)
+
+    def marks_words(self):
+        """fsm_hip_text_hits_marks as it is: (core, group), ceil(m / 64) words each"""
+        core, group = np.zeros((self.count + 63) // 64, np.uint64), np.zeros((self.count + 63) // 64, np.uint64)
+        C.set_errno(0)
+        if self._lib.fsm_hip_text_hits_marks(C.c_void_p(self._h), _ptr(core), _ptr(group)) != 0:
+            raise _oserr("fsm_hip_text_hits_marks")
+        return core, group
+
+    def context_ms(self) -> float:
+        return float(self._lib.fsm_hip_text_hits_context_ms(C.c_void_p(self._h)))
+
 
 
 def text_block_bytes() -> int:
@@ -1645,3 +1716,10 @@ def text_files_block() -> int:
     lib = load_library()
     lib.fsm_hip_text_files_block.restype = C.c_size_t
     return int(lib.fsm_hip_text_files_block())
+
+
+def text_context_scan_block() -> int:
+    """fsm_hip_text_context_scan_block: blocks of lines one round of the context scan takes."""
+    lib = load_library()
+    lib.fsm_hip_text_context_scan_block.restype = C.c_size_t
+    return int(lib.fsm_hip_text_context_scan_block())

@@ -763,6 +763,246 @@ hits_file_first(const uint64_t *lines, uint64_t m, const uint64_t *file_lines, u
 
 }   // namespace
 
+/* ---- context: the lines within reach of a selected line of the same file (grep -A / -B / -C) -------------------------
+ * S = the selected lines (bitmap ^ invert, below n), F = the lines that begin a file after the first (none in a plain text).
+ * W[i] <=> some selected p of i's file has p - before <= i <= p + after; the hits of W are made by the five kernels above,
+ * unchanged.  The nearest selected line on either side is the best witness, so with
+ *     prevS(i) / nextS(i) = the last / first selected line <= i / >= i,   prevF(i) = the last file start <= i (0 if none),
+ *     nextF(i) = the first file start > i (n if none)
+ * W[i] <=> (prevS exists, i - prevS <= after, prevF(i) <= prevS) or (nextS exists, nextS - i <= before, nextS < nextF(i)):
+ * arithmetic on two bitmaps whose cost does not know before or after.  A lane owns a WORD of 64 lines, CTX_TEAM lanes a block
+ * of HITS_LINES lines.  The passes:
+ *     ctx_file_starts  one lane per entry of file_lines: a bit of F for every distinct value in (0, n)       (vector atomic or)
+ *     ctx_summary      per block: (last selected + 1, last file start; first selected, first file start); the selected lines
+ *                      are counted on the way (core_count)
+ *     ctx_scan         one workgroup: exclusive max-scan forward of the first pair, exclusive min-scan backward of the second,
+ *                      CTX_SCAN_THREADS blocks a round from either end, a carry from round to round
+ *     ctx_apply        re-reads the words; the team's exclusive scans continue the block's carries to every word; a word is
+ *                      the union of what reaches it from the nearest selected line on its left, on its right, and from its
+ *                      own selected lines, each cut at the file starts: masks, no loop over before or after
+ *     ctx_marks        after hits_emit, one lane per hit: core = S[lines[k]], group = "a -- goes before it"; whole words by ballot
+ * Distances are compared, never positions added: before = after = 2^64 - 1 cannot wrap.  No workgroup waits for another; every
+ * workgroup of summary / apply takes ONE step of CTX_WG_BLOCKS blocks and carries nothing.  Loads stay below ceil(n / 64) words
+ * and stores below the counted totals, whatever the bitmap or lines hold. */
+namespace {
+
+constexpr uint32_t CTX_TEAM = HITS_LINES / 64u;             /* lanes (words) of a block: 16, a team never straddles a wavefront */
+constexpr uint32_t CTX_THREADS = 256;
+constexpr uint32_t CTX_WG_BLOCKS = CTX_THREADS / CTX_TEAM;  /* blocks a workgroup of summary / apply takes */
+constexpr uint32_t CTX_SCAN_THREADS = 1024;                 /* blocks a round of ctx_scan takes from either end */
+constexpr uint64_t CTX_NONE = ~(uint64_t)0;
+static_assert(CTX_TEAM == 16 && 64u % CTX_TEAM == 0, "a team is a quarter of a wavefront");
+
+__device__ __forceinline__ uint64_t umax64(uint64_t a, uint64_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+/* bits lo .. hi of a word, 0 <= lo <= hi <= 63 */
+__device__ __forceinline__ uint64_t bits_between(uint32_t lo, uint32_t hi) { return (~(uint64_t)0 >> (63u - hi)) & (~(uint64_t)0 << lo); }
+
+/* word wi of S and of F (0 beyond the last word; the bits at and above n are no lines) */
+__device__ __forceinline__ void ctx_words(uint64_t bitmap, uint64_t fmap, uint64_t n, uint64_t nwords, uint32_t invert, uint64_t wi,
+                                          uint64_t &w, uint64_t &f)
+{
+	w = 0;
+	f = 0;
+	if (wi >= nwords) return;
+	const uint64_t live = n - 64u * wi >= 64u ? ~(uint64_t)0 : ((uint64_t)1 << (uint32_t)(n - 64u * wi)) - 1u;
+	const uint64_t x = ((glb_u64p)bitmap)[wi];
+	w = (invert != 0u ? ~x : x) & live;
+	if (fmap != 0) f = ((glb_u64p)fmap)[wi] & live;
+}
+
+/* the word's own summary: s[0] = last selected + 1 (0: none), s[1] = last file start (0: none), s[2] = first selected (NONE),
+ * s[3] = first file start (n: none) */
+__device__ __forceinline__ void ctx_own(uint64_t w, uint64_t f, uint64_t base, uint64_t n, uint64_t (&s)[4])
+{
+	s[0] = w != 0 ? base + (63u - (uint32_t)__builtin_clzll(w)) + 1u : 0u;
+	s[1] = f != 0 ? base + (63u - (uint32_t)__builtin_clzll(f)) : 0u;
+	s[2] = w != 0 ? base + (uint32_t)__builtin_ctzll(w) : CTX_NONE;
+	s[3] = f != 0 ? base + (uint32_t)__builtin_ctzll(f) : n;
+}
+
+__global__ void __launch_bounds__(CTX_THREADS)
+ctx_file_starts(const uint64_t *file_lines, uint64_t nends, uint64_t n, uint64_t *fmap)
+{
+	const uint64_t j = (uint64_t)blockIdx.x * CTX_THREADS + threadIdx.x;
+	if (j >= nends) return;
+	const glb_u64p fl = (glb_u64p)(uintptr_t)file_lines;
+	const uint64_t v = fl[j];
+	if (v == 0 || v >= n || (j != 0 && fl[j - 1u] == v)) return;   /* the first of a run sets the bit; line 0 and n begin no later file */
+	(void)__hip_atomic_fetch_or((glb_u64w)(uintptr_t)(fmap + (v >> 6)), (uint64_t)1 << (uint32_t)(v & 63u), __ATOMIC_RELAXED,
+	                            __HIP_MEMORY_SCOPE_AGENT);
+}
+
+/* sum[4b .. 4b + 3] = the summary of block b; meta[0] += the selected lines */
+__global__ void __launch_bounds__(CTX_THREADS)
+ctx_summary(const uint64_t *bitmap, const uint64_t *fmap, uint64_t n, uint64_t nwords, uint32_t invert, uint64_t nblocks, uint64_t *sum,
+            uint64_t *meta)
+{
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint64_t wi = (uint64_t)blockIdx.x * CTX_THREADS + threadIdx.x;
+	uint64_t w, f, s[4];
+	ctx_words((uint64_t)(uintptr_t)bitmap, (uint64_t)(uintptr_t)fmap, n, nwords, invert, wi, w, f);
+	ctx_own(w, f, 64u * wi, n, s);
+#pragma unroll
+	for (int d = 1; d < (int)CTX_TEAM; d <<= 1) {
+		s[0] = umax64(s[0], __shfl_xor(s[0], d, (int)CTX_TEAM));
+		s[1] = umax64(s[1], __shfl_xor(s[1], d, (int)CTX_TEAM));
+		s[2] = umin64(s[2], __shfl_xor(s[2], d, (int)CTX_TEAM));
+		s[3] = umin64(s[3], __shfl_xor(s[3], d, (int)CTX_TEAM));
+	}
+	const uint64_t b = wi / CTX_TEAM;
+	if ((lane & (CTX_TEAM - 1u)) == 0u && b < nblocks) {
+		const glb_u64x2w out = (glb_u64x2w)(uintptr_t)(sum + 4u * b);
+		out[0] = u64x2{s[0], s[1]};
+		out[1] = u64x2{s[2], s[3]};
+	}
+	uint32_t c = (uint32_t)__builtin_popcountll(w);
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d, 64);
+	if (lane == 0 && c != 0u)
+		(void)__hip_atomic_fetch_add((glb_u64w)(uintptr_t)meta, (uint64_t)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+/* in place: sum[4b], sum[4b + 1] become the max over the blocks BEFORE b, sum[4b + 2], sum[4b + 3] the min over the blocks AFTER b.
+ * Thread k of a round takes block b0 + k for the forward pair and block nblocks - 1 - (b0 + k) for the backward pair: one loop,
+ * one carry of four words, the two directions never touch the same word. */
+__global__ void __launch_bounds__(CTX_SCAN_THREADS)
+ctx_scan(uint64_t *sum, uint64_t nblocks, uint64_t n)
+{
+	__shared__ uint64_t wtot[CTX_SCAN_THREADS / 64u][4];
+	__shared__ uint64_t carry[4];
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	if (threadIdx.x == 0) { carry[0] = 0; carry[1] = 0; carry[2] = CTX_NONE; carry[3] = n; }
+	__syncthreads();
+	for (uint64_t b0 = 0; b0 < nblocks; b0 += CTX_SCAN_THREADS) {
+		const uint64_t k = b0 + threadIdx.x;
+		const bool act = k < nblocks;
+		const glb_u64x2w fw = (glb_u64x2w)(uintptr_t)(sum + 4u * (act ? k : 0u));
+		const glb_u64x2w bw = (glb_u64x2w)(uintptr_t)(sum + 4u * (act ? nblocks - 1u - k : 0u) + 2u);
+		const u64x2 mf = act ? *fw : u64x2{0u, 0u}, mb = act ? *bw : u64x2{CTX_NONE, n};
+		uint64_t x0 = mf.x, x1 = mf.y, x2 = mb.x, x3 = mb.y;   /* inclusive over the wave */
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const uint64_t y0 = __shfl_up(x0, d, 64), y1 = __shfl_up(x1, d, 64), y2 = __shfl_up(x2, d, 64), y3 = __shfl_up(x3, d, 64);
+			if (lane >= (uint32_t)d) { x0 = umax64(x0, y0); x1 = umax64(x1, y1); x2 = umin64(x2, y2); x3 = umin64(x3, y3); }
+		}
+		if (lane == 63u) { wtot[wave][0] = x0; wtot[wave][1] = x1; wtot[wave][2] = x2; wtot[wave][3] = x3; }
+		__syncthreads();
+		uint64_t c0 = carry[0], c1 = carry[1], c2 = carry[2], c3 = carry[3];
+		for (uint32_t w = 0; w < wave; w++) {
+			c0 = umax64(c0, wtot[w][0]); c1 = umax64(c1, wtot[w][1]); c2 = umin64(c2, wtot[w][2]); c3 = umin64(c3, wtot[w][3]);
+		}
+		/* exclusive: the lanes before this one */
+		const uint64_t p0 = __shfl_up(x0, 1, 64), p1 = __shfl_up(x1, 1, 64), p2 = __shfl_up(x2, 1, 64), p3 = __shfl_up(x3, 1, 64);
+		if (act) {
+			*fw = lane == 0 ? u64x2{c0, c1} : u64x2{umax64(c0, p0), umax64(c1, p1)};
+			*bw = lane == 0 ? u64x2{c2, c3} : u64x2{umin64(c2, p2), umin64(c3, p3)};
+		}
+		__syncthreads();
+		if (threadIdx.x == CTX_SCAN_THREADS - 1u) {
+			carry[0] = umax64(c0, x0); carry[1] = umax64(c1, x1); carry[2] = umin64(c2, x2); carry[3] = umin64(c3, x3);
+		}
+		__syncthreads();
+	}
+}
+
+/* out[wi] = word wi of W.  ps1 / pf: the last selected line + 1 / the last file start before the word (0: none); ns / nf: the
+ * first selected line / file start after it (NONE / n): the block's carries continued through the team. */
+__global__ void __launch_bounds__(CTX_THREADS)
+ctx_apply(const uint64_t *bitmap, const uint64_t *fmap, uint64_t n, uint64_t nwords, uint32_t invert, uint64_t nblocks, const uint64_t *sum,
+          uint64_t before, uint64_t after, uint64_t *out)
+{
+	const uint32_t sub = threadIdx.x & (CTX_TEAM - 1u);
+	const uint64_t wi = (uint64_t)blockIdx.x * CTX_THREADS + threadIdx.x, base = 64u * wi;
+	uint64_t w, f, s[4];
+	ctx_words((uint64_t)(uintptr_t)bitmap, (uint64_t)(uintptr_t)fmap, n, nwords, invert, wi, w, f);
+	ctx_own(w, f, base, n, s);
+#pragma unroll
+	for (int d = 1; d < (int)CTX_TEAM; d <<= 1) {   /* inclusive over the team: up for the forward pair, down for the backward */
+		const uint64_t y0 = __shfl_up(s[0], d, (int)CTX_TEAM), y1 = __shfl_up(s[1], d, (int)CTX_TEAM);
+		const uint64_t y2 = __shfl_down(s[2], d, (int)CTX_TEAM), y3 = __shfl_down(s[3], d, (int)CTX_TEAM);
+		if (sub >= (uint32_t)d) { s[0] = umax64(s[0], y0); s[1] = umax64(s[1], y1); }
+		if (sub + (uint32_t)d < CTX_TEAM) { s[2] = umin64(s[2], y2); s[3] = umin64(s[3], y3); }
+	}
+	const uint64_t e0 = __shfl_up(s[0], 1, (int)CTX_TEAM), e1 = __shfl_up(s[1], 1, (int)CTX_TEAM);
+	const uint64_t e2 = __shfl_down(s[2], 1, (int)CTX_TEAM), e3 = __shfl_down(s[3], 1, (int)CTX_TEAM);
+	if (wi >= nwords) return;   /* after the last shuffle: the lanes of a team are all there for them */
+	const uint64_t b = wi / CTX_TEAM;   /* < nblocks, as wi < nwords */
+	const u64x2 cf = *(glb_u64x2p)(uintptr_t)(sum + 4u * b), cb = *(glb_u64x2p)(uintptr_t)(sum + 4u * b + 2u);
+	(void)nblocks;
+	const uint64_t ps1 = sub == 0u ? cf.x : umax64(cf.x, e0), pf = sub == 0u ? cf.y : umax64(cf.y, e1);
+	const uint64_t ns = sub == CTX_TEAM - 1u ? cb.x : umin64(cb.x, e2), nf = sub == CTX_TEAM - 1u ? cb.y : umin64(cb.y, e3);
+	uint64_t W = 0;
+	/* from the left: lines up to `after` past p, as long as no file starts in (p, i] */
+	if (ps1 != 0u && pf <= ps1 - 1u && (f & 1u) == 0u) {
+		const uint64_t d = base - (ps1 - 1u);           /* >= 1: from p to the word's first line */
+		if (after >= d) {
+			uint32_t hi = after - d >= 63u ? 63u : (uint32_t)(after - d);
+			if (f != 0) { const uint32_t c = (uint32_t)__builtin_ctzll(f) - 1u; hi = hi < c ? hi : c; }
+			W |= bits_between(0u, hi);
+		}
+	}
+	/* from the right: lines down to `before` ahead of q, as long as no file starts in (i, q] */
+	if (ns != CTX_NONE && ns < nf) {
+		const uint64_t d = ns - (base + 63u);           /* >= 1: from the word's last line to q */
+		if (before >= d) {
+			uint32_t lo = before - d >= 63u ? 0u : 63u - (uint32_t)(before - d);
+			if (f != 0) { const uint32_t c = 63u - (uint32_t)__builtin_clzll(f); lo = lo > c ? lo : c; }
+			W |= bits_between(lo, 63u);
+		}
+	}
+	/* the word's own selected lines: [max(j - before, last file start <= j), min(j + after, first file start > j - 1)] */
+	for (uint64_t ww = w; ww != 0; ww &= ww - 1u) {
+		const uint32_t j = (uint32_t)__builtin_ctzll(ww);
+		const uint64_t upto = ((uint64_t)2 << j) - 1u;  /* bits 0 .. j (j == 63: all) */
+		const uint64_t fa = f & ~upto, fb = f & upto;
+		uint32_t hi = fa != 0 ? (uint32_t)__builtin_ctzll(fa) - 1u : 63u;
+		uint32_t lo = fb != 0 ? 63u - (uint32_t)__builtin_clzll(fb) : 0u;
+		if (after < hi - j) hi = j + (uint32_t)after;
+		if (before < j - lo) lo = j - (uint32_t)before;
+		W |= bits_between(lo, hi);
+	}
+	if (n - base < 64u) W &= ((uint64_t)1 << (uint32_t)(n - base)) - 1u;
+	((glb_u64w)(uintptr_t)out)[wi] = W;
+}
+
+/* one lane per hit; word k / 64 of core and of group by ballot, stored by the wavefront's first lane; meta[1] += the groups.
+ * A line number that is none (arrays gone wrong) reads nothing. */
+__global__ void __launch_bounds__(CTX_THREADS)
+ctx_marks(const uint64_t *lines, uint64_t m, const uint64_t *bitmap, const uint64_t *fmap, uint64_t n, uint32_t invert, uint64_t *core,
+          uint64_t *group, uint64_t *meta)
+{
+	const uint64_t k = (uint64_t)blockIdx.x * CTX_THREADS + threadIdx.x;
+	const glb_u64p ln = (glb_u64p)(uintptr_t)lines;
+	bool c = false, g = false;
+	if (k < m) {
+		const uint64_t i = ln[k];
+		if (i < n) {
+			const uint64_t x = ((glb_u64p)(uintptr_t)bitmap)[i >> 6];
+			c = (((invert != 0u ? ~x : x) >> (uint32_t)(i & 63u)) & 1u) != 0u;
+			g = k == 0 || ln[k - 1u] + 1u != i || (fmap != nullptr && ((((glb_u64p)(uintptr_t)fmap)[i >> 6] >> (uint32_t)(i & 63u)) & 1u) != 0u);
+		}
+	}
+	const uint64_t mc = __ballot(c), mg = __ballot(g);
+	if ((threadIdx.x & 63u) == 0u && k < m) {
+		((glb_u64w)(uintptr_t)core)[k >> 6] = mc;
+		((glb_u64w)(uintptr_t)group)[k >> 6] = mg;
+		if (mg != 0)
+			(void)__hip_atomic_fetch_add((glb_u64w)(uintptr_t)(meta + 1), (uint64_t)__builtin_popcountll(mg), __ATOMIC_RELAXED,
+			                             __HIP_MEMORY_SCOPE_AGENT);
+	}
+}
+
+/* what the context adds to a run of the hits' passes */
+struct ctx_run {
+	const uint64_t *d_bitmap;   /* the caller's: S = bitmap ^ invert */
+	uint32_t invert;
+	uint64_t core_count;        /* rides the hits' one wait */
+};
+
+}   // namespace
+
 struct fsm_hip_text_hits {
 	int device = 0;
 	size_t m = 0, nbytes = 0;
@@ -776,6 +1016,16 @@ struct fsm_hip_text_hits {
 	size_t nfiles = 0;                       /* a text of files: its hits per file; 0 / NULL for a plain text */
 	uint64_t *d_file_first = nullptr;        /* nfiles + 1 */
 	hipEvent_t fev[2] = {nullptr, nullptr};  /* around hits_file_first, between emit and gather */
+	/* hits with context (fsm_hip_text_hits_context*): all NULL / 0 in plain hits */
+	bool context = false;
+	size_t core_count = 0;
+	uint64_t *d_wide = nullptr;              /* ceil(n / 64): W, the bitmap the passes above select by */
+	uint64_t *d_fmap = nullptr;              /* ceil(n / 64): F, the file starts; NULL for a plain text */
+	uint64_t *d_sum = nullptr;               /* per block of lines: its summary, then the carries; + the 2 words of d_cmeta */
+	uint64_t *d_cmeta = nullptr;             /* inside d_sum: (core_count, groups), counted by atomics from 0 */
+	uint64_t *d_core = nullptr;              /* ceil(m / 64) */
+	uint64_t *d_group = nullptr;             /* ceil(m / 64) */
+	hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};   /* around the widening, around the marks */
 };
 
 extern "C" void fsm_hip_text_hits_free(struct fsm_hip_text_hits *h)
@@ -787,6 +1037,12 @@ extern "C" void fsm_hip_text_hits_free(struct fsm_hip_text_hits *h)
 		if (h->ev[5] != nullptr) (void)hipEventSynchronize(h->ev[5]);
 		for (hipEvent_t ev : h->ev) if (ev != nullptr) (void)hipEventDestroy(ev);
 		for (hipEvent_t ev : h->fev) if (ev != nullptr) (void)hipEventDestroy(ev);
+		for (hipEvent_t ev : h->cev) if (ev != nullptr) (void)hipEventDestroy(ev);
+		if (h->d_wide != nullptr) (void)hipFree(h->d_wide);
+		if (h->d_fmap != nullptr) (void)hipFree(h->d_fmap);
+		if (h->d_sum != nullptr) (void)hipFree(h->d_sum);
+		if (h->d_core != nullptr) (void)hipFree(h->d_core);
+		if (h->d_group != nullptr) (void)hipFree(h->d_group);
 		if (h->d_file_first != nullptr) (void)hipFree(h->d_file_first);
 		if (h->d_pairs != nullptr) (void)hipFree(h->d_pairs);
 		if (h->d_lines != nullptr) (void)hipFree(h->d_lines);
@@ -799,15 +1055,17 @@ extern "C" void fsm_hip_text_hits_free(struct fsm_hip_text_hits *h)
 	errno = e;
 }
 
-/* the passes over d_bitmap on stream s: one wait in the middle (m and the bytes size the arrays); emit and gather in flight at return */
-static struct fsm_hip_text_hits *text_hits_run(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags, hipStream_t s)
+/* the passes over d_bitmap on stream s: one wait in the middle (m and the bytes size the arrays); emit and gather in flight at return.
+ * cx != NULL (text_hits_context_run): h is the caller's, d_bitmap is its W; core_count joins the wait, the marks follow the emit. */
+static struct fsm_hip_text_hits *text_hits_run(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags, hipStream_t s,
+	struct fsm_hip_text_hits *h = nullptr, struct ctx_run *cx = nullptr)
 {
 	const uint64_t n = t->n;
 	const uint32_t invert = (flags & FSM_HIP_HITS_INVERT) != 0u ? 1u : 0u;
 	const bool bytes = (flags & FSM_HIP_HITS_NO_BYTES) == 0u;
 	uint64_t nblocks = (n + HITS_LINES - 1u) / HITS_LINES, grid = 1, per = 1, ngb = 0;
 	uint64_t meta[2] = {0, 0};
-	struct fsm_hip_text_hits *h = new (std::nothrow) struct fsm_hip_text_hits;
+	if (h == nullptr) h = new (std::nothrow) struct fsm_hip_text_hits;
 	if (h == nullptr) { errno = ENOMEM; return nullptr; }
 	h->device = t->device;
 	{
@@ -830,10 +1088,12 @@ static struct fsm_hip_text_hits *text_hits_run(const struct fsm_hip_text *t, con
 			TTRY(hipGetLastError());
 			TTRY(hipEventRecord(h->ev[1], s));
 			TTRY(hipMemcpyAsync(meta, d_meta, sizeof meta, hipMemcpyDeviceToHost, s));
+			if (cx != nullptr) TTRY(hipMemcpyAsync(&cx->core_count, h->d_cmeta, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
 			TTRY(hipStreamSynchronize(s));
 		} else {
 			TTRY(hipEventRecord(h->ev[1], s));
 		}
+		if (cx != nullptr) h->core_count = (size_t)cx->core_count;
 		h->m = (size_t)meta[0];
 		h->nbytes = bytes ? (size_t)meta[1] : 0;
 		if (h->m == 0) { nblocks = 0; grid = 1; per = 1; }   /* nothing to re-read: the emit kernel leaves out_off = {0} alone */
@@ -855,6 +1115,20 @@ static struct fsm_hip_text_hits *text_hits_run(const struct fsm_hip_text *t, con
 			TTRY(hipGetLastError());
 		}
 		TTRY(hipEventRecord(h->ev[3], s));
+		if (cx != nullptr) {    /* the marks of the m hits: core and group, ceil(m / 64) words each */
+			TTRY(hipEventRecord(h->cev[2], s));
+			if (h->m != 0) {
+				const uint64_t mwords = ((uint64_t)h->m + 63u) / 64u, mgrid = ((uint64_t)h->m + CTX_THREADS - 1u) / CTX_THREADS;
+				if (mgrid > 0x7fffffffu) { errno = ENOMEM; goto fail; }
+				TTRY(hipMalloc((void **)&h->d_core, mwords * sizeof(uint64_t)));
+				TTRY(hipMalloc((void **)&h->d_group, mwords * sizeof(uint64_t)));
+				hipLaunchKernelGGL(ctx_marks, dim3((unsigned)mgrid), dim3(CTX_THREADS), 0, s, (const uint64_t *)h->d_lines, (uint64_t)h->m,
+				                   cx->d_bitmap, (const uint64_t *)h->d_fmap, n, cx->invert, h->d_core, h->d_group,
+				                   h->d_cmeta);
+				TTRY(hipGetLastError());
+			}
+			TTRY(hipEventRecord(h->cev[3], s));
+		}
 		if (t->nfiles != 0) {   /* also under NO_BYTES and when m == 0 */
 			const uint64_t nends = (uint64_t)t->nfiles + 1u;
 			h->nfiles = t->nfiles;
@@ -934,6 +1208,147 @@ fail:
 		errno = e;
 	}
 	return nullptr;
+}
+
+/* the widening on stream s, then the hits' own passes over W with invert 0: the one wait is theirs */
+static struct fsm_hip_text_hits *text_hits_context_run(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags, uint64_t before,
+	uint64_t after, hipStream_t s)
+{
+	const uint64_t n = t->n, nwords = (n + 63u) / 64u, nblocks = (n + HITS_LINES - 1u) / HITS_LINES;
+	const uint64_t grid = (nblocks + CTX_WG_BLOCKS - 1u) / CTX_WG_BLOCKS;
+	struct ctx_run cx = {d_bitmap, (flags & FSM_HIP_HITS_INVERT) != 0u ? 1u : 0u, 0u};
+	struct fsm_hip_text_hits *h = new (std::nothrow) struct fsm_hip_text_hits;
+	if (h == nullptr) { errno = ENOMEM; return nullptr; }
+	h->device = t->device;
+	h->context = true;
+	{
+		DevGuard dg(t->device);
+		if (!dg.ok()) { errno = ENODEV; goto fail; }
+		if (grid > 0x7fffffffu) { errno = ENOMEM; goto fail; }
+		for (hipEvent_t &ev : h->cev) TTRY(hipEventCreate(&ev));
+		TTRY(hipStreamWaitEvent(s, t->ev[3], 0));   /* the text's offsets and file_lines first */
+		if (n != 0) {
+			TTRY(hipMalloc((void **)&h->d_wide, nwords * sizeof(uint64_t)));
+			TTRY(hipMalloc((void **)&h->d_sum, (4u * nblocks + 2u) * sizeof(uint64_t)));
+			if (t->nfiles != 0) TTRY(hipMalloc((void **)&h->d_fmap, nwords * sizeof(uint64_t)));
+		}
+		TTRY(hipEventRecord(h->cev[0], s));
+		if (n != 0) {
+			uint64_t *d_meta = h->d_cmeta = h->d_sum + 4u * nblocks;
+			TTRY(hipMemsetAsync(d_meta, 0, 2u * sizeof(uint64_t), s));
+			if (t->nfiles != 0) {
+				const uint64_t nends = (uint64_t)t->nfiles + 1u;
+				TTRY(hipMemsetAsync(h->d_fmap, 0, nwords * sizeof(uint64_t), s));
+				hipLaunchKernelGGL(ctx_file_starts, dim3((unsigned)((nends + CTX_THREADS - 1u) / CTX_THREADS)), dim3(CTX_THREADS), 0, s,
+				                   (const uint64_t *)t->d_file_lines, nends, n, h->d_fmap);
+				TTRY(hipGetLastError());
+			}
+			hipLaunchKernelGGL(ctx_summary, dim3((unsigned)grid), dim3(CTX_THREADS), 0, s, d_bitmap, (const uint64_t *)h->d_fmap, n, nwords,
+			                   cx.invert, nblocks, h->d_sum, d_meta);
+			TTRY(hipGetLastError());
+			hipLaunchKernelGGL(ctx_scan, dim3(1), dim3(CTX_SCAN_THREADS), 0, s, h->d_sum, nblocks, n);
+			TTRY(hipGetLastError());
+			hipLaunchKernelGGL(ctx_apply, dim3((unsigned)grid), dim3(CTX_THREADS), 0, s, d_bitmap, (const uint64_t *)h->d_fmap, n, nwords,
+			                   cx.invert, nblocks, (const uint64_t *)h->d_sum, before, after, h->d_wide);
+			TTRY(hipGetLastError());
+		}
+		TTRY(hipEventRecord(h->cev[1], s));
+	}
+	return text_hits_run(t, h->d_wide, flags & FSM_HIP_HITS_NO_BYTES, s, h, &cx);   /* frees h when it fails */
+fail:
+	{
+		const int e = errno;
+		(void)hipStreamSynchronize(s);
+		fsm_hip_text_hits_free(h);
+		errno = e;
+	}
+	return nullptr;
+}
+
+extern "C" struct fsm_hip_text_hits *fsm_hip_text_hits_context_device(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags,
+	uint64_t before, uint64_t after, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (text_hits_check(t, flags) != 0) return nullptr;
+	if (d_bitmap == nullptr && t->n != 0) { errno = EINVAL; return nullptr; }
+	return text_hits_context_run(t, d_bitmap, flags, before, after, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" struct fsm_hip_text_hits *fsm_hip_text_hits_context(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t, unsigned flags,
+	uint64_t before, uint64_t after)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (text_hits_check(t, flags) != 0 || text_exec_check(ld, t) != 0) return nullptr;
+	DevGuard dg(t->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	uint64_t *d_bm = nullptr;
+	struct fsm_hip_text_hits *h = nullptr;
+	{
+		if (t->n != 0) {
+			TTRY(hipMalloc((void **)&d_bm, (t->n + 63u) / 64u * sizeof(uint64_t)));
+			TTRY(hipStreamWaitEvent(t->own, t->ev[3], 0));
+			if (fsm_hip_text_exec_device(ld, t, nullptr, d_bm, 0, nullptr, nullptr, t->own) != 0) goto fail;
+		}
+		h = text_hits_context_run(t, d_bm, flags, before, after, t->own);
+		if (h == nullptr) goto fail;
+		TTRY(hipStreamSynchronize(t->own));   /* the marks have read the walk's bitmap */
+	}
+	if (d_bm != nullptr) (void)hipFree(d_bm);
+	return h;
+fail:
+	{
+		const int e = errno;
+		(void)hipStreamSynchronize(t->own);
+		if (h != nullptr) fsm_hip_text_hits_free(h);
+		if (d_bm != nullptr) (void)hipFree(d_bm);
+		errno = e;
+	}
+	return nullptr;
+}
+
+extern "C" const uint64_t *fsm_hip_text_hits_core_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_core; }
+extern "C" const uint64_t *fsm_hip_text_hits_group_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_group; }
+extern "C" size_t fsm_hip_text_hits_core_count(const struct fsm_hip_text_hits *h) { return h == nullptr ? 0 : h->core_count; }
+extern "C" size_t fsm_hip_text_context_scan_block(void) { return CTX_SCAN_THREADS; }
+
+extern "C" int fsm_hip_text_hits_marks(const struct fsm_hip_text_hits *h, uint64_t *core, uint64_t *group)
+{
+	if (h == nullptr || !h->context) { errno = EINVAL; return -1; }
+	DevGuard dg(h->device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
+	TTRY(hipEventSynchronize(h->ev[5]));
+	if (core != nullptr && h->m != 0) TTRY(hipMemcpy(core, h->d_core, (h->m + 63u) / 64u * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	if (group != nullptr && h->m != 0) TTRY(hipMemcpy(group, h->d_group, (h->m + 63u) / 64u * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	return 0;
+fail:
+	return -1;
+}
+
+extern "C" size_t fsm_hip_text_hits_groups(const struct fsm_hip_text_hits *h)
+{
+	uint64_t g = 0;
+	if (h == nullptr || !h->context || h->m == 0) return 0;
+	DevGuard dg(h->device);
+	if (!dg.ok()) { errno = ENODEV; return 0; }
+	TTRY(hipEventSynchronize(h->ev[5]));
+	TTRY(hipMemcpy(&g, h->d_cmeta + 1, sizeof g, hipMemcpyDeviceToHost));
+	return (size_t)g;
+fail:
+	return 0;
+}
+
+extern "C" double fsm_hip_text_hits_context_ms(const struct fsm_hip_text_hits *h)
+{
+	float a = 0.f, b = 0.f;
+	if (h == nullptr || !h->context) { errno = EINVAL; return -1.0; }
+	DevGuard dg(h->device);
+	if (!dg.ok()) { errno = ENODEV; return -1.0; }
+	TTRY(hipEventSynchronize(h->ev[5]));
+	TTRY(hipEventElapsedTime(&a, h->cev[0], h->cev[1]));
+	TTRY(hipEventElapsedTime(&b, h->cev[2], h->cev[3]));
+	return (double)a + (double)b;
+fail:
+	return -1.0;
 }
 
 extern "C" size_t fsm_hip_text_hits_count(const struct fsm_hip_text_hits *h) { return h == nullptr ? 0 : h->m; }
