@@ -25,6 +25,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
+#include <new>
 
 #include "../../include/fsm_hip.h"
 
@@ -127,39 +129,86 @@ text_count(const unsigned char *text, uint64_t nbytes, uint32_t splat, uint64_t 
 	}
 }
 
-/* pass 2: exclusive scan of cnt[] in place by one workgroup (the shape of tile_bases_pass2, walk_aux.h); meta[0] = the
- * number of delimiters, meta[1] = 1 iff the text's last byte is one: the 16 bytes the host waits for */
+/* inclusive scan of x over the wavefront: lane l leaves op over the x of lanes 0 .. l */
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_scan(T x, uint32_t lane, Op op)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const T y = __shfl_up(x, d, 64);
+		if (lane >= (uint32_t)d) x = op(x, y);
+	}
+	return x;
+}
+
+struct op_add {
+	template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+};
+
+/* exclusive sum scan of rec[0, nrec), records of WORDS 64-bit words each, in place by ONE workgroup of THREADS (the shape of
+ * tile_bases_pass2, walk_aux.h); meta[0 .. WORDS) = the totals.  A thread takes PER consecutive records a round, so one memory
+ * round trip serves THREADS * PER records; the wave scans and an LDS exchange of the wave totals order the threads of a round, a
+ * carry in LDS the rounds. */
+template <uint32_t THREADS, uint32_t WORDS, uint32_t PER>
+__device__ __forceinline__ void sum_scan(uint64_t *rec, uint64_t nrec, uint64_t *meta)
+{
+	typedef uint64_t rec_t __attribute__((ext_vector_type(WORDS)));
+	typedef rec_t __attribute__((address_space(1))) *glb_rec_w;
+	__shared__ uint64_t wtot[THREADS / 64u][WORDS];
+	__shared__ uint64_t carry[WORDS];
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	if (threadIdx.x == 0)
+		for (uint32_t i = 0; i < WORDS; i++) carry[i] = 0;
+	__syncthreads();
+	for (uint64_t b0 = 0; b0 < nrec; b0 += (uint64_t)THREADS * PER) {
+		const uint64_t b = b0 + (uint64_t)PER * threadIdx.x;
+		rec_t e[PER], mine, run, x;
+		uint64_t before[WORDS];
+#pragma unroll
+		for (uint32_t k = 0; k < PER; k++)
+			e[k] = b + k < nrec ? *(glb_rec_w)(uintptr_t)(rec + WORDS * (b + k)) : (rec_t)(0u);
+		mine = e[0];
+#pragma unroll
+		for (uint32_t k = 1; k < PER; k++) mine += e[k];
+		x = mine;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {   /* the words' inclusive scans over the wave, side by side */
+			rec_t y;
+#pragma unroll
+			for (uint32_t i = 0; i < WORDS; i++) y[i] = __shfl_up(x[i], d, 64);
+			if (lane >= (uint32_t)d) x += y;
+		}
+		if (lane == 63u)
+			for (uint32_t i = 0; i < WORDS; i++) wtot[wave][i] = x[i];
+		__syncthreads();
+#pragma unroll
+		for (uint32_t i = 0; i < WORDS; i++) before[i] = carry[i];
+		for (uint32_t w = 0; w < wave; w++)
+			for (uint32_t i = 0; i < WORDS; i++) before[i] += wtot[w][i];
+#pragma unroll
+		for (uint32_t i = 0; i < WORDS; i++) run[i] = before[i] + x[i] - mine[i];
+#pragma unroll
+		for (uint32_t k = 0; k < PER; k++) {
+			if (b + k < nrec) *(glb_rec_w)(uintptr_t)(rec + WORDS * (b + k)) = run;
+			run += e[k];
+		}
+		__syncthreads();
+		if (threadIdx.x == THREADS - 1u)
+			for (uint32_t i = 0; i < WORDS; i++) carry[i] = before[i] + x[i];
+		__syncthreads();
+	}
+	if (threadIdx.x == 0)
+		for (uint32_t i = 0; i < WORDS; i++) ((glb_u64w)(uintptr_t)meta)[i] = carry[i];
+}
+
+/* pass 2: the exclusive scan of cnt[]; meta[0] = the number of delimiters, meta[1] = 1 iff the text's last byte is one: the 16
+ * bytes the host waits for */
 __global__ void __launch_bounds__(1024)
 text_scan(uint64_t *cnt, uint64_t nblocks, const unsigned char *text, uint64_t nbytes, uint32_t delim, uint64_t *meta)
 {
-	__shared__ uint64_t wtot[16];
-	__shared__ uint64_t carry;
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	if (threadIdx.x == 0) carry = 0;
-	__syncthreads();
-	for (uint64_t b0 = 0; b0 < nblocks; b0 += 1024u) {
-		const uint64_t b = b0 + threadIdx.x;
-		const uint64_t mine = b < nblocks ? *(glb_u64p)(uintptr_t)(cnt + b) : 0u;
-		uint64_t x = mine;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint64_t y = __shfl_up(x, d, 64);
-			if (lane >= (uint32_t)d) x += y;
-		}
-		if (lane == 63u) wtot[wave] = x;
-		__syncthreads();
-		uint64_t before = carry;
-		for (uint32_t w = 0; w < wave; w++) before += wtot[w];
-		if (b < nblocks) *(glb_u64w)(uintptr_t)(cnt + b) = before + x - mine;
-		__syncthreads();
-		if (threadIdx.x == 1023u) carry = before + x;
-		__syncthreads();
-	}
-	if (threadIdx.x == 0) {
-		glb_u64w m = (glb_u64w)(uintptr_t)meta;
-		m[0] = carry;
-		m[1] = nbytes != 0 && ((glb_u8p)(uintptr_t)text)[nbytes - 1u] == delim ? 1u : 0u;
-	}
+	sum_scan<1024, 1, 1>(cnt, nblocks, meta);
+	if (threadIdx.x == 0)
+		((glb_u64w)(uintptr_t)meta)[1] = nbytes != 0 && ((glb_u8p)(uintptr_t)text)[nbytes - 1u] == delim ? 1u : 0u;
 }
 
 /* pass 3: off[1 + rank] = position + 1 of every delimiter.  Positions run tile by tile, lane by lane inside a tile, so the
@@ -192,7 +241,7 @@ text_offsets(const unsigned char *text, uint64_t nbytes, uint32_t splat, uint64_
 			m[u] = hit_mask16(v[u], splat);
 			c[u] = (uint32_t)__builtin_popcount(m[u]);
 		}
-		uint32_t x0 = c[0] | c[1] << 16, x1 = c[2] | c[3] << 16;   /* inclusive scans over the wave */
+		uint32_t x0 = c[0] | c[1] << 16, x1 = c[2] | c[3] << 16;   /* inclusive scans over the wave, the two interleaved */
 #pragma unroll
 		for (int d = 1; d < 64; d <<= 1) {
 			const uint32_t y0 = (uint32_t)__shfl_up((int)x0, d, 64), y1 = (uint32_t)__shfl_up((int)x1, d, 64);
@@ -236,9 +285,16 @@ int herr(hipError_t e)
 	default: return EIO;
 	}
 }
-#define TTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
-	if (getenv("FSM_HIP_DEBUG")) fprintf(stderr, "fsm_hip: %s -> %s\n", #expr, hipGetErrorString(e_)); \
-	errno = herr(e_); goto fail; } } while (0)
+
+/* false, with errno set, when a HIP call failed: `if (!TOK(call)) return ...;` */
+bool hip_ok(hipError_t e, const char *what)
+{
+	if (e == hipSuccess) return true;
+	if (getenv("FSM_HIP_DEBUG")) fprintf(stderr, "fsm_hip: %s -> %s\n", what, hipGetErrorString(e));
+	errno = herr(e);
+	return false;
+}
+#define TOK(expr) hip_ok((expr), #expr)
 
 /* make a device current for the duration of a call and give the caller's back */
 struct DevGuard {
@@ -254,6 +310,53 @@ struct DevGuard {
 	bool ok() const { return good; }
 };
 
+/* device memory that goes with its owner.  The owner sees to it that the memory's device is current (DevGuard) and that no
+ * kernel still touches it (a wait for its last event or its stream) before it lets go.  errno survives the release. */
+template <typename T>
+struct DevBuf {
+	T *p = nullptr;
+	DevBuf() = default;
+	DevBuf(const DevBuf &) = delete;
+	DevBuf &operator=(const DevBuf &) = delete;
+	DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+	DevBuf &operator=(DevBuf &&o) noexcept
+	{
+		if (this != &o) { reset(); p = o.p; o.p = nullptr; }
+		return *this;
+	}
+	~DevBuf() { reset(); }
+	void reset()
+	{
+		if (p == nullptr) return;
+		const int e = errno;
+		(void)hipFree(p);
+		p = nullptr;
+		errno = e;
+	}
+	hipError_t alloc(uint64_t count)
+	{
+		reset();
+		return hipMalloc((void **)&p, count * sizeof(T));
+	}
+	operator T *() const { return p; }
+};
+
+struct DevEvent {
+	hipEvent_t e = nullptr;
+	DevEvent() = default;
+	DevEvent(const DevEvent &) = delete;
+	DevEvent &operator=(const DevEvent &) = delete;
+	~DevEvent()
+	{
+		if (e == nullptr) return;
+		const int en = errno;
+		(void)hipEventDestroy(e);
+		errno = en;
+	}
+	hipError_t create() { return hipEventCreate(&e); }
+	operator hipEvent_t() const { return e; }
+};
+
 bool have_device()
 {
 	int ndev = 0;
@@ -267,26 +370,78 @@ unsigned max_workgroups(int dev)
 	return (unsigned)ncu * TEXT_WG_PER_CU;
 }
 
+/* the grid for nblocks blocks: at most max_workgroups workgroups of `per` consecutive blocks each, none without a block (one
+ * workgroup for no block: the kernels that run then do their first thread's work alone) */
+struct Grid {
+	uint64_t wgs = 1, per = 1;
+};
+Grid grid_of(uint64_t nblocks, int dev)
+{
+	Grid g;
+	if (nblocks == 0) return g;
+	g.wgs = max_workgroups(dev);
+	if (g.wgs > nblocks) g.wgs = nblocks;
+	g.per = (nblocks + g.wgs - 1u) / g.wgs;
+	g.wgs = (nblocks + g.per - 1u) / g.per;
+	return g;
+}
+
+/* wait for `done`, then copy every {dst, src, nbytes} with a dst and bytes out of the device */
+struct OutCopy {
+	void *dst;
+	const void *src;
+	size_t nbytes;
+};
+int copy_out(int device, hipEvent_t done, std::initializer_list<OutCopy> copies)
+{
+	DevGuard dg(device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
+	if (!TOK(hipEventSynchronize(done))) return -1;
+	for (const OutCopy &c : copies)
+		if (c.dst != nullptr && c.nbytes != 0 && !TOK(hipMemcpy(c.dst, c.src, c.nbytes, hipMemcpyDeviceToHost))) return -1;
+	return 0;
+}
+
+/* wait for `done`, then the milliseconds between the events of every pair, summed; -1 when it fails */
+struct EventPair {
+	hipEvent_t from, to;
+};
+double elapsed_ms(int device, hipEvent_t done, std::initializer_list<EventPair> pairs)
+{
+	double ms = 0.0;
+	DevGuard dg(device);
+	if (!dg.ok()) { errno = ENODEV; return -1.0; }
+	if (!TOK(hipEventSynchronize(done))) return -1.0;
+	for (const EventPair &p : pairs) {
+		float one = 0.f;
+		if (!TOK(hipEventElapsedTime(&one, p.from, p.to))) return -1.0;
+		ms += (double)one;
+	}
+	return ms;
+}
+
 }   // namespace
 
-struct fsm_hip_text {
+/* the types are the library's own: their destructors are no exported symbols */
+struct __attribute__((visibility("hidden"))) fsm_hip_text {
 	int device = 0, delim = 0;
 	size_t nbytes = 0, n = 0;
 	const unsigned char *d_text = nullptr;   /* the caller's bytes (open_device) or `owned` */
-	unsigned char *owned = nullptr;
-	uint64_t *d_off = nullptr;               /* n + 1 */
-	uint64_t *d_cnt = nullptr;               /* per block: its delimiters, then their exclusive scan; + the 2 words of meta */
+	DevBuf<unsigned char> owned;
+	DevBuf<uint64_t> d_off;                  /* n + 1 */
+	DevBuf<uint64_t> d_cnt;                  /* per block: its delimiters, then their exclusive scan; + the 2 (files: 4) words of meta */
 	hipStream_t own = nullptr;               /* the host-pointer forms run here, never on the NULL stream */
-	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   /* around count + scan, around offsets; ev[3]: the offsets are there */
+	DevEvent ev[4];                          /* around count + scan, around offsets; ev[3]: the offsets are there */
 	/* a text of files (fsm_hip_text_open_files*): all NULL / 0 in a plain text */
 	size_t nfiles = 0;
 	const uint64_t *d_file_off = nullptr;    /* nfiles + 1: the caller's (open_files_device) or `owned_file_off` */
-	uint64_t *owned_file_off = nullptr;
-	uint64_t *d_file_lines = nullptr;        /* nfiles + 1 */
-	uint64_t *d_plain = nullptr;             /* the plain offsets the merge reads; the host form frees them once its stream is idle */
-	uint64_t *d_frank = nullptr;             /* per file end: (added ends before it in its block) << 1 | it adds one */
-	uint64_t *d_fpairs = nullptr;            /* per block of file ends: (added ends, invalid entries), then their exclusive scan */
-	hipEvent_t fev[3] = {nullptr, nullptr, nullptr};   /* around mark + scan; fev[2]: the plain offsets are there, the merge runs to ev[3] */
+	DevBuf<uint64_t> owned_file_off;
+	DevBuf<uint64_t> d_file_lines;           /* nfiles + 1 */
+	DevBuf<uint64_t> d_plain;                /* the plain offsets the merge reads; the host form frees them once its stream is idle */
+	DevBuf<uint64_t> d_frank;                /* per file end: (added ends before it in its block) << 1 | it adds one */
+	DevBuf<uint64_t> d_fpairs;               /* per block of file ends: (added ends, invalid entries), then their exclusive scan */
+	DevEvent fev[3];                         /* around mark + scan; fev[2]: the plain offsets are there, the merge runs to ev[3] */
+	~fsm_hip_text() { if (own != nullptr) (void)hipStreamDestroy(own); }
 };
 
 extern "C" void fsm_hip_text_free(struct fsm_hip_text *t)
@@ -296,123 +451,19 @@ extern "C" void fsm_hip_text_free(struct fsm_hip_text *t)
 	{
 		DevGuard dg(t->device);
 		if (t->ev[3] != nullptr) (void)hipEventSynchronize(t->ev[3]);   /* the scan may still be reading the caller's bytes */
-		for (hipEvent_t ev : t->ev) if (ev != nullptr) (void)hipEventDestroy(ev);
-		for (hipEvent_t ev : t->fev) if (ev != nullptr) (void)hipEventDestroy(ev);
-		if (t->own != nullptr) (void)hipStreamDestroy(t->own);
-		if (t->owned_file_off != nullptr) (void)hipFree(t->owned_file_off);
-		if (t->d_file_lines != nullptr) (void)hipFree(t->d_file_lines);
-		if (t->d_plain != nullptr) (void)hipFree(t->d_plain);
-		if (t->d_frank != nullptr) (void)hipFree(t->d_frank);
-		if (t->d_fpairs != nullptr) (void)hipFree(t->d_fpairs);
-		if (t->d_off != nullptr) (void)hipFree(t->d_off);
-		if (t->d_cnt != nullptr) (void)hipFree(t->d_cnt);
-		if (t->owned != nullptr) (void)hipFree(t->owned);
+		delete t;
 	}
-	delete t;
 	errno = e;
-}
-
-/* the three passes over t->d_text on stream s: one wait in the middle (the line count sizes the offsets array) */
-static int text_scan_lines(struct fsm_hip_text *t, hipStream_t s)
-{
-	const uint64_t nbytes = t->nbytes;
-	const uint32_t splat = (uint32_t)t->delim * 0x01010101u;
-	const uint64_t nblocks = (nbytes + TEXT_BLOCK - 1u) / TEXT_BLOCK;
-	uint64_t meta[2] = {0, 0};
-	for (hipEvent_t &ev : t->ev) TTRY(hipEventCreate(&ev));
-	if (nbytes == 0) {   /* no byte, no line: off[0] = 0 alone */
-		TTRY(hipMalloc((void **)&t->d_off, sizeof(uint64_t)));
-		TTRY(hipMemsetAsync(t->d_off, 0, sizeof(uint64_t), s));
-		for (hipEvent_t ev : t->ev) TTRY(hipEventRecord(ev, s));
-		return 0;
-	}
-	{
-		uint64_t grid = max_workgroups(t->device);
-		if (grid > nblocks) grid = nblocks;
-		const uint64_t per = (nblocks + grid - 1u) / grid;
-		grid = (nblocks + per - 1u) / per;
-		TTRY(hipMalloc((void **)&t->d_cnt, (nblocks + 2u) * sizeof(uint64_t)));
-		uint64_t *d_meta = t->d_cnt + nblocks;
-		TTRY(hipEventRecord(t->ev[0], s));
-		hipLaunchKernelGGL(text_count, dim3((unsigned)grid), dim3(TEXT_THREADS), 0, s, t->d_text, nbytes, splat, nblocks, per, t->d_cnt);
-		TTRY(hipGetLastError());
-		hipLaunchKernelGGL(text_scan, dim3(1), dim3(1024), 0, s, t->d_cnt, nblocks, t->d_text, nbytes, (uint32_t)t->delim, d_meta);
-		TTRY(hipGetLastError());
-		TTRY(hipEventRecord(t->ev[1], s));
-		TTRY(hipMemcpyAsync(meta, d_meta, sizeof meta, hipMemcpyDeviceToHost, s));
-		TTRY(hipStreamSynchronize(s));
-		t->n = (size_t)(meta[0] + (meta[1] != 0 ? 0u : 1u));   /* bytes after the last delimiter form a last line */
-		TTRY(hipMalloc((void **)&t->d_off, ((uint64_t)t->n + 1u) * sizeof(uint64_t)));
-		TTRY(hipEventRecord(t->ev[2], s));
-		hipLaunchKernelGGL(text_offsets, dim3((unsigned)grid), dim3(TEXT_THREADS), 0, s, t->d_text, nbytes, splat, nblocks, per,
-		                   (const uint64_t *)t->d_cnt, meta[0], (uint64_t)t->n, t->d_off);
-		TTRY(hipGetLastError());
-		TTRY(hipEventRecord(t->ev[3], s));
-	}
-	return 0;
-fail:
-	return -1;
-}
-
-static struct fsm_hip_text *text_new(size_t nbytes, int delim)
-{
-	if (delim < 0 || delim > 255) { errno = EINVAL; return nullptr; }
-	if (!have_device()) { errno = ENODEV; return nullptr; }   /* no CPU path, as everywhere in this library */
-	struct fsm_hip_text *t = new (std::nothrow) fsm_hip_text;
-	if (t == nullptr) { errno = ENOMEM; return nullptr; }
-	t->nbytes = nbytes;
-	t->delim = delim;
-	if (hipGetDevice(&t->device) != hipSuccess) { delete t; errno = ENODEV; return nullptr; }
-	hipError_t e = hipStreamCreateWithFlags(&t->own, hipStreamNonBlocking);
-	if (e != hipSuccess) { delete t; errno = herr(e); return nullptr; }
-	return t;
-}
-
-extern "C" struct fsm_hip_text *fsm_hip_text_open_device(const void *d_text, size_t nbytes, int delim, void *hip_stream)
-{
-	if (d_text == nullptr && nbytes != 0) { errno = EINVAL; return nullptr; }
-	struct fsm_hip_text *t = text_new(nbytes, delim);
-	if (t == nullptr) return nullptr;
-	t->d_text = static_cast<const unsigned char *>(d_text);
-	if (text_scan_lines(t, static_cast<hipStream_t>(hip_stream)) != 0) {
-		fsm_hip_text_free(t);
-		return nullptr;
-	}
-	return t;
-}
-
-extern "C" struct fsm_hip_text *fsm_hip_text_open(const void *text, size_t nbytes, int delim)
-{
-	if (text == nullptr && nbytes != 0) { errno = EINVAL; return nullptr; }
-	struct fsm_hip_text *t = text_new(nbytes, delim);
-	if (t == nullptr) return nullptr;
-	if (nbytes != 0) {
-		TTRY(hipMalloc((void **)&t->owned, nbytes));
-		TTRY(hipMemcpyAsync(t->owned, text, nbytes, hipMemcpyHostToDevice, t->own));
-	}
-	t->d_text = t->owned;
-	if (text_scan_lines(t, t->own) != 0) goto fail;
-	TTRY(hipStreamSynchronize(t->own));
-	return t;
-fail:
-	fsm_hip_text_free(t);
-	return nullptr;
 }
 
 extern "C" size_t fsm_hip_text_lines(const struct fsm_hip_text *t) { return t == nullptr ? 0 : t->n; }
 
-extern "C" const uint64_t *fsm_hip_text_offsets_device(const struct fsm_hip_text *t) { return t == nullptr ? nullptr : t->d_off; }
+extern "C" const uint64_t *fsm_hip_text_offsets_device(const struct fsm_hip_text *t) { return t == nullptr ? nullptr : t->d_off.p; }
 
 extern "C" int fsm_hip_text_offsets(const struct fsm_hip_text *t, uint64_t *off)
 {
 	if (t == nullptr || off == nullptr) { errno = EINVAL; return -1; }
-	DevGuard dg(t->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	TTRY(hipEventSynchronize(t->ev[3]));
-	TTRY(hipMemcpy(off, t->d_off, (t->n + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-	return 0;
-fail:
-	return -1;
+	return copy_out(t->device, t->ev[3], {{off, t->d_off, (t->n + 1u) * sizeof(uint64_t)}});
 }
 
 extern "C" size_t fsm_hip_text_block_bytes(void) { return TEXT_BLOCK; }
@@ -426,16 +477,9 @@ extern "C" size_t fsm_hip_text_max_workgroups(void)
 
 extern "C" double fsm_hip_text_scan_ms(const struct fsm_hip_text *t)
 {
-	float a = 0.f, b = 0.f;
 	if (t == nullptr) { errno = EINVAL; return -1.0; }
-	DevGuard dg(t->device);
-	if (!dg.ok()) { errno = ENODEV; return -1.0; }
-	TTRY(hipEventSynchronize(t->ev[3]));
-	TTRY(hipEventElapsedTime(&a, t->ev[0], t->ev[1]));
-	TTRY(hipEventElapsedTime(&b, t->ev[2], t->nfiles != 0 ? t->fev[2] : t->ev[3]));   /* files: the merge after them is not the scan's */
-	return (double)a + (double)b;
-fail:
-	return -1.0;
+	/* files: the merge after the plain offsets is not the scan's */
+	return elapsed_ms(t->device, t->ev[3], {{t->ev[0], t->ev[1]}, {t->ev[2], t->nfiles != 0 ? t->fev[2] : t->ev[3]}});
 }
 
 /* ---- the walk: the untouched text + its offsets are a packed batch of the twin automaton ---- */
@@ -467,35 +511,29 @@ extern "C" int fsm_hip_text_exec(const struct fsm_hip_lines_dfa *ld, const struc
 	if (end_out == nullptr && accept_bitmap == nullptr && id_out == nullptr && eager_out == nullptr) return 0;
 	DevGuard dg(t->device);
 	if (!dg.ok()) { errno = ENODEV; return -1; }
-	auto up16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
 	const size_t W = fsm_hip_eager_words(fsm_hip_lines_dfa_inner(ld));
-	const size_t b_end = end_out ? up16(n * 4u) : 0, b_bm = accept_bitmap ? up16((n + 63u) / 64u * 8u) : 0,
-	             b_id = id_out ? up16(n * 4u) : 0, b_eo = eager_out ? up16(n * W * 8u) : 0;
-	unsigned char *d = nullptr;
-	int rc = -1;
-	{
-		TTRY(hipMalloc((void **)&d, b_end + b_bm + b_id + b_eo));
-		uint32_t *d_end = end_out ? (uint32_t *)d : nullptr;
-		uint64_t *d_bm = accept_bitmap ? (uint64_t *)(d + b_end) : nullptr;
-		uint32_t *d_id = id_out ? (uint32_t *)(d + b_end + b_bm) : nullptr;
-		uint64_t *d_eo = eager_out ? (uint64_t *)(d + b_end + b_bm + b_id) : nullptr;
-		TTRY(hipStreamWaitEvent(t->own, t->ev[3], 0));   /* a text opened on the caller's stream: its offsets first */
-		if (fsm_hip_text_exec_device(ld, t, d_end, d_bm, ids_mode, d_id, d_eo, t->own) != 0) goto fail;
-		if (end_out) TTRY(hipMemcpyAsync(end_out, d_end, n * 4u, hipMemcpyDeviceToHost, t->own));
-		if (accept_bitmap) TTRY(hipMemcpyAsync(accept_bitmap, d_bm, (n + 63u) / 64u * 8u, hipMemcpyDeviceToHost, t->own));
-		if (id_out) TTRY(hipMemcpyAsync(id_out, d_id, n * 4u, hipMemcpyDeviceToHost, t->own));
-		if (eager_out) TTRY(hipMemcpyAsync(eager_out, d_eo, n * W * 8u, hipMemcpyDeviceToHost, t->own));
-		TTRY(hipStreamSynchronize(t->own));
-		rc = 0;
-	}
-fail:
-	if (d != nullptr) {
+	/* the outputs that are asked for, staged one after the other in one allocation, each at a multiple of 16 bytes */
+	auto up16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
+	const size_t n_end = n * 4u, n_bm = (n + 63u) / 64u * 8u, n_id = n * 4u, n_eo = n * W * 8u;
+	const size_t at_bm = end_out ? up16(n_end) : 0, at_id = at_bm + (accept_bitmap ? up16(n_bm) : 0), at_eo = at_id + (id_out ? up16(n_id) : 0);
+	DevBuf<unsigned char> d;
+	if (!TOK(d.alloc(at_eo + (eager_out ? up16(n_eo) : 0)))) return -1;
+	uint32_t *d_end = end_out ? (uint32_t *)d.p : nullptr, *d_id = id_out ? (uint32_t *)(d + at_id) : nullptr;
+	uint64_t *d_bm = accept_bitmap ? (uint64_t *)(d + at_bm) : nullptr, *d_eo = eager_out ? (uint64_t *)(d + at_eo) : nullptr;
+	auto fail = [&] {   /* the stream idle before the staging memory goes */
 		const int e = errno;
 		(void)hipStreamSynchronize(t->own);
-		(void)hipFree(d);
 		errno = e;
-	}
-	return rc;
+		return -1;
+	};
+	if (!TOK(hipStreamWaitEvent(t->own, t->ev[3], 0))) return fail();   /* a text opened on the caller's stream: its offsets first */
+	if (fsm_hip_text_exec_device(ld, t, d_end, d_bm, ids_mode, d_id, d_eo, t->own) != 0) return fail();
+	if (end_out && !TOK(hipMemcpyAsync(end_out, d_end, n_end, hipMemcpyDeviceToHost, t->own))) return fail();
+	if (accept_bitmap && !TOK(hipMemcpyAsync(accept_bitmap, d_bm, n_bm, hipMemcpyDeviceToHost, t->own))) return fail();
+	if (id_out && !TOK(hipMemcpyAsync(id_out, d_id, n_id, hipMemcpyDeviceToHost, t->own))) return fail();
+	if (eager_out && !TOK(hipMemcpyAsync(eager_out, d_eo, n_eo, hipMemcpyDeviceToHost, t->own))) return fail();
+	if (!TOK(hipStreamSynchronize(t->own))) return fail();
+	return 0;
 }
 
 /* ---- the hits: the selected lines' numbers, ranges and bytes ----------------------------------------------------
@@ -551,6 +589,26 @@ __device__ __forceinline__ uint32_t lane_lines(uint64_t bitmap, uint64_t off, ui
 	return sel;
 }
 
+/* the bytes of the lane's selected lines */
+__device__ __forceinline__ uint64_t lane_bytes(uint32_t sel, const uint64_t (&o)[HITS_PER + 1])
+{
+	uint64_t by = 0;
+#pragma unroll
+	for (uint32_t j = 0; j < HITS_PER; j++) by += (sel >> j & 1u) != 0u ? o[j + 1u] - o[j] : 0u;
+	return by;
+}
+
+/* the first index in a[0, n) whose entry is >= v (n if none) */
+__device__ __forceinline__ uint64_t lower_bound_glb(glb_u64p a, uint64_t n, uint64_t v)
+{
+	uint64_t lo = 0, hi = n;
+	while (lo < hi) {
+		const uint64_t mid = lo + (hi - lo) / 2u;
+		if (a[mid] < v) lo = mid + 1u; else hi = mid;
+	}
+	return lo;
+}
+
 /* pass 1: workgroup g owns blocks [g * per, (g + 1) * per) of HITS_LINES lines; pairs[2b], pairs[2b + 1] = lines and bytes
  * selected in block b.  Two LDS rows in turn, one barrier a block, as text_count. */
 __global__ void __launch_bounds__(HITS_THREADS)
@@ -564,9 +622,7 @@ hits_count(const uint64_t *bitmap, const uint64_t *off, uint64_t n, uint32_t inv
 		uint64_t o[HITS_PER + 1];
 		const uint32_t sel = lane_lines((uint64_t)(uintptr_t)bitmap, (uint64_t)(uintptr_t)off, n, b * HITS_LINES + HITS_PER * threadIdx.x, invert, o);
 		uint32_t c = (uint32_t)__builtin_popcount(sel);
-		uint64_t by = 0;
-#pragma unroll
-		for (uint32_t j = 0; j < HITS_PER; j++) by += (sel >> j & 1u) != 0u ? o[j + 1u] - o[j] : 0u;
+		uint64_t by = lane_bytes(sel, o);
 #pragma unroll
 		for (int d = 32; d >= 1; d >>= 1) {
 			c += (uint32_t)__shfl_xor((int)c, d, 64);
@@ -583,51 +639,12 @@ hits_count(const uint64_t *bitmap, const uint64_t *off, uint64_t n, uint32_t inv
 	}
 }
 
-/* pass 2: exclusive scan of the pairs in place by one workgroup; meta[0] = m, meta[1] = the bytes of the m lines.  text_scan's
- * shape with the lever NOTES.md names for it pulled: HITS_SCAN_PER consecutive pairs a thread, so one memory round trip serves
- * 4 096 blocks (4 Mi lines) instead of 1 024. */
+/* pass 2: the exclusive scan of the pairs; meta[0] = m, meta[1] = the bytes of the m lines.  HITS_SCAN_PER consecutive pairs a
+ * thread: one memory round trip serves 4 096 blocks (4 Mi lines). */
 __global__ void __launch_bounds__(1024)
 hits_scan(uint64_t *pairs, uint64_t nblocks, uint64_t *meta)
 {
-	__shared__ uint64_t wtot[16][2];
-	__shared__ uint64_t carry[2];
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	if (threadIdx.x == 0) { carry[0] = 0; carry[1] = 0; }
-	__syncthreads();
-	for (uint64_t b0 = 0; b0 < nblocks; b0 += 1024u * HITS_SCAN_PER) {
-		const uint64_t b = b0 + (uint64_t)HITS_SCAN_PER * threadIdx.x;
-		u64x2 e[HITS_SCAN_PER];
-#pragma unroll
-		for (uint32_t k = 0; k < HITS_SCAN_PER; k++)
-			e[k] = b + k < nblocks ? *(glb_u64x2p)(uintptr_t)(pairs + 2u * (b + k)) : u64x2{0u, 0u};
-		u64x2 mine = e[0];
-#pragma unroll
-		for (uint32_t k = 1; k < HITS_SCAN_PER; k++) mine += e[k];
-		uint64_t xc = mine.x, xb = mine.y;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint64_t yc = __shfl_up(xc, d, 64), yb = __shfl_up(xb, d, 64);
-			if (lane >= (uint32_t)d) { xc += yc; xb += yb; }
-		}
-		if (lane == 63u) { wtot[wave][0] = xc; wtot[wave][1] = xb; }
-		__syncthreads();
-		uint64_t bc = carry[0], bb = carry[1];
-		for (uint32_t w = 0; w < wave; w++) { bc += wtot[w][0]; bb += wtot[w][1]; }
-		u64x2 run = u64x2{bc + xc - mine.x, bb + xb - mine.y};
-#pragma unroll
-		for (uint32_t k = 0; k < HITS_SCAN_PER; k++) {
-			if (b + k < nblocks) *(glb_u64x2w)(uintptr_t)(pairs + 2u * (b + k)) = run;
-			run += e[k];
-		}
-		__syncthreads();
-		if (threadIdx.x == 1023u) { carry[0] = bc + xc; carry[1] = bb + xb; }
-		__syncthreads();
-	}
-	if (threadIdx.x == 0) {
-		glb_u64w m = (glb_u64w)(uintptr_t)meta;
-		m[0] = carry[0];
-		m[1] = carry[1];
-	}
+	sum_scan<1024, 2, HITS_SCAN_PER>(pairs, nblocks, meta);
 }
 
 /* pass 3: the rank of a selected line = base[block] + the selected lines of the waves and lanes before it (a wave scan and an
@@ -654,17 +671,9 @@ hits_emit(const uint64_t *bitmap, const uint64_t *off, uint64_t n, uint32_t inve
 		const uint32_t sel = lane_lines((uint64_t)(uintptr_t)bitmap, (uint64_t)(uintptr_t)off, n, i0, invert, o);
 		const u64x2 bs = *(glb_u64x2p)(uintptr_t)(base + 2u * b);
 		const uint32_t c = (uint32_t)__builtin_popcount(sel);
-		uint64_t by = 0;
-#pragma unroll
-		for (uint32_t j = 0; j < HITS_PER; j++) by += (sel >> j & 1u) != 0u ? o[j + 1u] - o[j] : 0u;
-		uint32_t xc = c;
-		uint64_t xb = by;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t yc = (uint32_t)__shfl_up((int)xc, d, 64);
-			const uint64_t yb = __shfl_up(xb, d, 64);
-			if (lane >= (uint32_t)d) { xc += yc; xb += yb; }
-		}
+		const uint64_t by = lane_bytes(sel, o);
+		const uint32_t xc = wave_scan(c, lane, op_add());
+		const uint64_t xb = wave_scan(by, lane, op_add());
 		if (lane == 63u) { wtot[it][wave][0] = xc; wtot[it][wave][1] = xb; }
 		__syncthreads();
 		uint64_t r = bs.x + (xc - c), p = bs.y + (xb - by);
@@ -751,14 +760,8 @@ hits_file_first(const uint64_t *lines, uint64_t m, const uint64_t *file_lines, u
 {
 	const uint64_t j = (uint64_t)blockIdx.x * HITS_THREADS + threadIdx.x;
 	if (j >= nends) return;
-	const glb_u64p ln = (glb_u64p)(uintptr_t)lines;
 	const uint64_t v = ((glb_u64p)(uintptr_t)file_lines)[j];
-	uint64_t lo = 0, hi = m;
-	while (lo < hi) {
-		const uint64_t mid = lo + (hi - lo) / 2u;
-		if (ln[mid] < v) lo = mid + 1u; else hi = mid;
-	}
-	((glb_u64w)(uintptr_t)file_first)[j] = lo;
+	((glb_u64w)(uintptr_t)file_first)[j] = lower_bound_glb((glb_u64p)(uintptr_t)lines, m, v);
 }
 
 }   // namespace
@@ -881,7 +884,7 @@ ctx_scan(uint64_t *sum, uint64_t nblocks, uint64_t n)
 		const glb_u64x2w fw = (glb_u64x2w)(uintptr_t)(sum + 4u * (act ? k : 0u));
 		const glb_u64x2w bw = (glb_u64x2w)(uintptr_t)(sum + 4u * (act ? nblocks - 1u - k : 0u) + 2u);
 		const u64x2 mf = act ? *fw : u64x2{0u, 0u}, mb = act ? *bw : u64x2{CTX_NONE, n};
-		uint64_t x0 = mf.x, x1 = mf.y, x2 = mb.x, x3 = mb.y;   /* inclusive over the wave */
+		uint64_t x0 = mf.x, x1 = mf.y, x2 = mb.x, x3 = mb.y;   /* inclusive over the wave, the four side by side */
 #pragma unroll
 		for (int d = 1; d < 64; d <<= 1) {
 			const uint64_t y0 = __shfl_up(x0, d, 64), y1 = __shfl_up(x1, d, 64), y2 = __shfl_up(x2, d, 64), y3 = __shfl_up(x3, d, 64);
@@ -910,8 +913,8 @@ ctx_scan(uint64_t *sum, uint64_t nblocks, uint64_t n)
 /* out[wi] = word wi of W.  ps1 / pf: the last selected line + 1 / the last file start before the word (0: none); ns / nf: the
  * first selected line / file start after it (NONE / n): the block's carries continued through the team. */
 __global__ void __launch_bounds__(CTX_THREADS)
-ctx_apply(const uint64_t *bitmap, const uint64_t *fmap, uint64_t n, uint64_t nwords, uint32_t invert, uint64_t nblocks, const uint64_t *sum,
-          uint64_t before, uint64_t after, uint64_t *out)
+ctx_apply(const uint64_t *bitmap, const uint64_t *fmap, uint64_t n, uint64_t nwords, uint32_t invert, const uint64_t *sum, uint64_t before,
+          uint64_t after, uint64_t *out)
 {
 	const uint32_t sub = threadIdx.x & (CTX_TEAM - 1u);
 	const uint64_t wi = (uint64_t)blockIdx.x * CTX_THREADS + threadIdx.x, base = 64u * wi;
@@ -928,9 +931,8 @@ ctx_apply(const uint64_t *bitmap, const uint64_t *fmap, uint64_t n, uint64_t nwo
 	const uint64_t e0 = __shfl_up(s[0], 1, (int)CTX_TEAM), e1 = __shfl_up(s[1], 1, (int)CTX_TEAM);
 	const uint64_t e2 = __shfl_down(s[2], 1, (int)CTX_TEAM), e3 = __shfl_down(s[3], 1, (int)CTX_TEAM);
 	if (wi >= nwords) return;   /* after the last shuffle: the lanes of a team are all there for them */
-	const uint64_t b = wi / CTX_TEAM;   /* < nblocks, as wi < nwords */
+	const uint64_t b = wi / CTX_TEAM;   /* a block of the summary, as wi < nwords */
 	const u64x2 cf = *(glb_u64x2p)(uintptr_t)(sum + 4u * b), cb = *(glb_u64x2p)(uintptr_t)(sum + 4u * b + 2u);
-	(void)nblocks;
 	const uint64_t ps1 = sub == 0u ? cf.x : umax64(cf.x, e0), pf = sub == 0u ? cf.y : umax64(cf.y, e1);
 	const uint64_t ns = sub == CTX_TEAM - 1u ? cb.x : umin64(cb.x, e2), nf = sub == CTX_TEAM - 1u ? cb.y : umin64(cb.y, e3);
 	uint64_t W = 0;
@@ -994,38 +996,31 @@ ctx_marks(const uint64_t *lines, uint64_t m, const uint64_t *bitmap, const uint6
 	}
 }
 
-/* what the context adds to a run of the hits' passes */
-struct ctx_run {
-	const uint64_t *d_bitmap;   /* the caller's: S = bitmap ^ invert */
-	uint32_t invert;
-	uint64_t core_count;        /* rides the hits' one wait */
-};
-
 }   // namespace
 
-struct fsm_hip_text_hits {
+struct __attribute__((visibility("hidden"))) fsm_hip_text_hits {
 	int device = 0;
 	size_t m = 0, nbytes = 0;
-	uint64_t *d_pairs = nullptr;             /* per block of lines: (lines, bytes) selected, then their exclusive scan; + m and the bytes */
-	uint64_t *d_lines = nullptr;             /* m */
-	uint64_t *d_off = nullptr;               /* m + 1 */
-	uint64_t *d_src = nullptr;               /* m: where each selected line starts in the text */
-	uint64_t *d_first = nullptr;             /* per output block + 1: the rank of the line that covers its first byte */
-	unsigned char *d_bytes = nullptr;        /* nbytes, rounded up to whole blocks */
-	hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   /* around count + scan, emit, gather; ev[5]: all is there */
+	DevBuf<uint64_t> d_pairs;                /* per block of lines: (lines, bytes) selected, then their exclusive scan; + m and the bytes */
+	DevBuf<uint64_t> d_lines;                /* m */
+	DevBuf<uint64_t> d_off;                  /* m + 1 */
+	DevBuf<uint64_t> d_src;                  /* m: where each selected line starts in the text */
+	DevBuf<uint64_t> d_first;                /* per output block + 1: the rank of the line that covers its first byte */
+	DevBuf<unsigned char> d_bytes;           /* nbytes, rounded up to whole blocks */
+	DevEvent ev[6];                          /* around count + scan, emit, gather; ev[5]: all is there */
 	size_t nfiles = 0;                       /* a text of files: its hits per file; 0 / NULL for a plain text */
-	uint64_t *d_file_first = nullptr;        /* nfiles + 1 */
-	hipEvent_t fev[2] = {nullptr, nullptr};  /* around hits_file_first, between emit and gather */
+	DevBuf<uint64_t> d_file_first;           /* nfiles + 1 */
+	DevEvent fev[2];                         /* around hits_file_first, between emit and gather */
 	/* hits with context (fsm_hip_text_hits_context*): all NULL / 0 in plain hits */
 	bool context = false;
 	size_t core_count = 0;
-	uint64_t *d_wide = nullptr;              /* ceil(n / 64): W, the bitmap the passes above select by */
-	uint64_t *d_fmap = nullptr;              /* ceil(n / 64): F, the file starts; NULL for a plain text */
-	uint64_t *d_sum = nullptr;               /* per block of lines: its summary, then the carries; + the 2 words of d_cmeta */
+	DevBuf<uint64_t> d_wide;                 /* ceil(n / 64): W, the bitmap the select reads */
+	DevBuf<uint64_t> d_fmap;                 /* ceil(n / 64): F, the file starts; NULL for a plain text */
+	DevBuf<uint64_t> d_sum;                  /* per block of lines: its summary, then the carries; + the 2 words of d_cmeta */
 	uint64_t *d_cmeta = nullptr;             /* inside d_sum: (core_count, groups), counted by atomics from 0 */
-	uint64_t *d_core = nullptr;              /* ceil(m / 64) */
-	uint64_t *d_group = nullptr;             /* ceil(m / 64) */
-	hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};   /* around the widening, around the marks */
+	DevBuf<uint64_t> d_core;                 /* ceil(m / 64) */
+	DevBuf<uint64_t> d_group;                /* ceil(m / 64) */
+	DevEvent cev[4];                         /* around the widening, around the marks */
 };
 
 extern "C" void fsm_hip_text_hits_free(struct fsm_hip_text_hits *h)
@@ -1035,132 +1030,142 @@ extern "C" void fsm_hip_text_hits_free(struct fsm_hip_text_hits *h)
 	{
 		DevGuard dg(h->device);
 		if (h->ev[5] != nullptr) (void)hipEventSynchronize(h->ev[5]);
-		for (hipEvent_t ev : h->ev) if (ev != nullptr) (void)hipEventDestroy(ev);
-		for (hipEvent_t ev : h->fev) if (ev != nullptr) (void)hipEventDestroy(ev);
-		for (hipEvent_t ev : h->cev) if (ev != nullptr) (void)hipEventDestroy(ev);
-		if (h->d_wide != nullptr) (void)hipFree(h->d_wide);
-		if (h->d_fmap != nullptr) (void)hipFree(h->d_fmap);
-		if (h->d_sum != nullptr) (void)hipFree(h->d_sum);
-		if (h->d_core != nullptr) (void)hipFree(h->d_core);
-		if (h->d_group != nullptr) (void)hipFree(h->d_group);
-		if (h->d_file_first != nullptr) (void)hipFree(h->d_file_first);
-		if (h->d_pairs != nullptr) (void)hipFree(h->d_pairs);
-		if (h->d_lines != nullptr) (void)hipFree(h->d_lines);
-		if (h->d_off != nullptr) (void)hipFree(h->d_off);
-		if (h->d_src != nullptr) (void)hipFree(h->d_src);
-		if (h->d_first != nullptr) (void)hipFree(h->d_first);
-		if (h->d_bytes != nullptr) (void)hipFree(h->d_bytes);
+		delete h;
 	}
-	delete h;
 	errno = e;
 }
 
-/* the passes over d_bitmap on stream s: one wait in the middle (m and the bytes size the arrays); emit and gather in flight at return.
- * cx != NULL (text_hits_context_run): h is the caller's, d_bitmap is its W; core_count joins the wait, the marks follow the emit. */
-static struct fsm_hip_text_hits *text_hits_run(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags, hipStream_t s,
-	struct fsm_hip_text_hits *h = nullptr, struct ctx_run *cx = nullptr)
+/* the passes over d_bitmap on stream s into *h, t's device current: with a context (ctx = {before, after}) the widening first,
+ * and the select then reads W with no invert.  One wait in the middle (m and the bytes size the arrays, the core count rides
+ * along); emit, marks and gather in flight at return. */
+static int text_hits_run(struct fsm_hip_text_hits *h, const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags,
+	const uint64_t *ctx, hipStream_t s)
 {
-	const uint64_t n = t->n;
+	const uint64_t n = t->n, nwords = (n + 63u) / 64u;
 	const uint32_t invert = (flags & FSM_HIP_HITS_INVERT) != 0u ? 1u : 0u;
 	const bool bytes = (flags & FSM_HIP_HITS_NO_BYTES) == 0u;
-	uint64_t nblocks = (n + HITS_LINES - 1u) / HITS_LINES, grid = 1, per = 1, ngb = 0;
-	uint64_t meta[2] = {0, 0};
-	if (h == nullptr) h = new (std::nothrow) struct fsm_hip_text_hits;
+	uint64_t nblocks = (n + HITS_LINES - 1u) / HITS_LINES;
+	const uint64_t *d_sel = d_bitmap;   /* what the select reads */
+	uint32_t sel_invert = invert;
+	uint64_t meta[2] = {0, 0}, core = 0;
+	for (DevEvent &ev : h->ev)
+		if (!TOK(ev.create())) return -1;
+	if (!TOK(hipStreamWaitEvent(s, t->ev[3], 0))) return -1;   /* the text's offsets and file_lines first */
+	if (ctx != nullptr) {
+		const uint64_t wgrid = (nblocks + CTX_WG_BLOCKS - 1u) / CTX_WG_BLOCKS;
+		if (wgrid > 0x7fffffffu) { errno = ENOMEM; return -1; }
+		h->context = true;
+		for (DevEvent &ev : h->cev)
+			if (!TOK(ev.create())) return -1;
+		if (n != 0) {
+			if (!TOK(h->d_wide.alloc(nwords)) || !TOK(h->d_sum.alloc(4u * nblocks + 2u))) return -1;
+			if (t->nfiles != 0 && !TOK(h->d_fmap.alloc(nwords))) return -1;
+		}
+		if (!TOK(hipEventRecord(h->cev[0], s))) return -1;
+		if (n != 0) {
+			h->d_cmeta = h->d_sum + 4u * nblocks;
+			if (!TOK(hipMemsetAsync(h->d_cmeta, 0, 2u * sizeof(uint64_t), s))) return -1;
+			if (t->nfiles != 0) {
+				const uint64_t nends = (uint64_t)t->nfiles + 1u;
+				if (!TOK(hipMemsetAsync(h->d_fmap, 0, nwords * sizeof(uint64_t), s))) return -1;
+				hipLaunchKernelGGL(ctx_file_starts, dim3((unsigned)((nends + CTX_THREADS - 1u) / CTX_THREADS)), dim3(CTX_THREADS), 0, s,
+				                   t->d_file_lines, nends, n, h->d_fmap);
+				if (!TOK(hipGetLastError())) return -1;
+			}
+			hipLaunchKernelGGL(ctx_summary, dim3((unsigned)wgrid), dim3(CTX_THREADS), 0, s, d_bitmap, h->d_fmap, n, nwords, invert, nblocks,
+			                   h->d_sum, h->d_cmeta);
+			if (!TOK(hipGetLastError())) return -1;
+			hipLaunchKernelGGL(ctx_scan, dim3(1), dim3(CTX_SCAN_THREADS), 0, s, h->d_sum, nblocks, n);
+			if (!TOK(hipGetLastError())) return -1;
+			hipLaunchKernelGGL(ctx_apply, dim3((unsigned)wgrid), dim3(CTX_THREADS), 0, s, d_bitmap, h->d_fmap, n, nwords, invert, h->d_sum,
+			                   ctx[0], ctx[1], h->d_wide);
+			if (!TOK(hipGetLastError())) return -1;
+		}
+		if (!TOK(hipEventRecord(h->cev[1], s))) return -1;
+		d_sel = h->d_wide;
+		sel_invert = 0u;
+	}
+	Grid g = grid_of(nblocks, t->device);
+	if (!TOK(hipEventRecord(h->ev[0], s))) return -1;
+	if (n != 0) {
+		if (!TOK(h->d_pairs.alloc(2u * nblocks + 2u))) return -1;
+		uint64_t *d_meta = h->d_pairs + 2u * nblocks;
+		hipLaunchKernelGGL(hits_count, dim3((unsigned)g.wgs), dim3(HITS_THREADS), 0, s, d_sel, t->d_off, n, sel_invert, nblocks, g.per, h->d_pairs);
+		if (!TOK(hipGetLastError())) return -1;
+		hipLaunchKernelGGL(hits_scan, dim3(1), dim3(1024), 0, s, h->d_pairs, nblocks, d_meta);
+		if (!TOK(hipGetLastError())) return -1;
+		if (!TOK(hipEventRecord(h->ev[1], s))) return -1;
+		if (!TOK(hipMemcpyAsync(meta, d_meta, sizeof meta, hipMemcpyDeviceToHost, s))) return -1;
+		if (ctx != nullptr && !TOK(hipMemcpyAsync(&core, h->d_cmeta, sizeof core, hipMemcpyDeviceToHost, s))) return -1;
+		if (!TOK(hipStreamSynchronize(s))) return -1;
+	} else if (!TOK(hipEventRecord(h->ev[1], s))) {
+		return -1;
+	}
+	h->core_count = (size_t)core;
+	h->m = (size_t)meta[0];
+	h->nbytes = bytes ? (size_t)meta[1] : 0;
+	if (h->m == 0) { nblocks = 0; g = Grid(); }   /* nothing to re-read: the emit kernel leaves out_off = {0} alone */
+	const uint64_t m = h->m, ngb = ((uint64_t)h->nbytes + HITS_BLOCK - 1u) / HITS_BLOCK;
+	if (m != 0 && !TOK(h->d_lines.alloc(m))) return -1;
+	if (bytes) {
+		if (!TOK(h->d_off.alloc(m + 1u))) return -1;
+		if (m != 0 && (!TOK(h->d_src.alloc(m)) || !TOK(h->d_first.alloc(ngb + 1u)) || !TOK(h->d_bytes.alloc(ngb * HITS_BLOCK)))) return -1;
+	}
+	if (!TOK(hipEventRecord(h->ev[2], s))) return -1;
+	if (m != 0 || bytes) {
+		hipLaunchKernelGGL(hits_emit, dim3((unsigned)g.wgs), dim3(HITS_THREADS), 0, s, d_sel, t->d_off, n, sel_invert, nblocks, g.per, h->d_pairs,
+		                   m, (uint64_t)h->nbytes, h->d_lines, h->d_off, h->d_src, h->d_first, ngb);
+		if (!TOK(hipGetLastError())) return -1;
+	}
+	if (!TOK(hipEventRecord(h->ev[3], s))) return -1;
+	if (ctx != nullptr) {   /* the marks of the m hits: core and group, ceil(m / 64) words each; they read the caller's bitmap */
+		if (!TOK(hipEventRecord(h->cev[2], s))) return -1;
+		if (m != 0) {
+			const uint64_t mwords = (m + 63u) / 64u, mgrid = (m + CTX_THREADS - 1u) / CTX_THREADS;
+			if (mgrid > 0x7fffffffu) { errno = ENOMEM; return -1; }
+			if (!TOK(h->d_core.alloc(mwords)) || !TOK(h->d_group.alloc(mwords))) return -1;
+			hipLaunchKernelGGL(ctx_marks, dim3((unsigned)mgrid), dim3(CTX_THREADS), 0, s, h->d_lines, m, d_bitmap, h->d_fmap, n, invert, h->d_core,
+			                   h->d_group, h->d_cmeta);
+			if (!TOK(hipGetLastError())) return -1;
+		}
+		if (!TOK(hipEventRecord(h->cev[3], s))) return -1;
+	}
+	if (t->nfiles != 0) {   /* also under NO_BYTES and when m == 0 */
+		const uint64_t nends = (uint64_t)t->nfiles + 1u;
+		h->nfiles = t->nfiles;
+		for (DevEvent &ev : h->fev)
+			if (!TOK(ev.create())) return -1;
+		if (!TOK(h->d_file_first.alloc(nends))) return -1;
+		if (!TOK(hipEventRecord(h->fev[0], s))) return -1;
+		hipLaunchKernelGGL(hits_file_first, dim3((unsigned)((nends + HITS_THREADS - 1u) / HITS_THREADS)), dim3(HITS_THREADS), 0, s, h->d_lines, m,
+		                   t->d_file_lines, nends, h->d_file_first);
+		if (!TOK(hipGetLastError())) return -1;
+		if (!TOK(hipEventRecord(h->fev[1], s))) return -1;
+	}
+	if (!TOK(hipEventRecord(h->ev[4], s))) return -1;
+	if (ngb != 0) {
+		const Grid gg = grid_of(ngb, t->device);
+		hipLaunchKernelGGL(hits_gather, dim3((unsigned)gg.wgs), dim3(HITS_THREADS), 0, s, t->d_text, (uint64_t)t->nbytes, h->d_off, h->d_src,
+		                   h->d_first, m, (uint64_t)h->nbytes, ngb, gg.per, h->d_bytes);
+		if (!TOK(hipGetLastError())) return -1;
+	}
+	return TOK(hipEventRecord(h->ev[5], s)) ? 0 : -1;
+}
+
+/* the hits object of a run on stream s; when the run fails, the stream is made idle before what it has launched on is released */
+static struct fsm_hip_text_hits *text_hits_new(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags, const uint64_t *ctx,
+	hipStream_t s)
+{
+	DevGuard dg(t->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	struct fsm_hip_text_hits *h = new (std::nothrow) struct fsm_hip_text_hits;
 	if (h == nullptr) { errno = ENOMEM; return nullptr; }
 	h->device = t->device;
-	{
-		DevGuard dg(t->device);
-		if (!dg.ok()) { errno = ENODEV; goto fail; }
-		for (hipEvent_t &ev : h->ev) TTRY(hipEventCreate(&ev));
-		TTRY(hipStreamWaitEvent(s, t->ev[3], 0));   /* the text's offsets first */
-		TTRY(hipEventRecord(h->ev[0], s));
-		if (n != 0) {
-			grid = max_workgroups(t->device);
-			if (grid > nblocks) grid = nblocks;
-			per = (nblocks + grid - 1u) / grid;
-			grid = (nblocks + per - 1u) / per;
-			TTRY(hipMalloc((void **)&h->d_pairs, (2u * nblocks + 2u) * sizeof(uint64_t)));
-			uint64_t *d_meta = h->d_pairs + 2u * nblocks;
-			hipLaunchKernelGGL(hits_count, dim3((unsigned)grid), dim3(HITS_THREADS), 0, s, d_bitmap, (const uint64_t *)t->d_off, n, invert,
-			                   nblocks, per, h->d_pairs);
-			TTRY(hipGetLastError());
-			hipLaunchKernelGGL(hits_scan, dim3(1), dim3(1024), 0, s, h->d_pairs, nblocks, d_meta);
-			TTRY(hipGetLastError());
-			TTRY(hipEventRecord(h->ev[1], s));
-			TTRY(hipMemcpyAsync(meta, d_meta, sizeof meta, hipMemcpyDeviceToHost, s));
-			if (cx != nullptr) TTRY(hipMemcpyAsync(&cx->core_count, h->d_cmeta, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-			TTRY(hipStreamSynchronize(s));
-		} else {
-			TTRY(hipEventRecord(h->ev[1], s));
-		}
-		if (cx != nullptr) h->core_count = (size_t)cx->core_count;
-		h->m = (size_t)meta[0];
-		h->nbytes = bytes ? (size_t)meta[1] : 0;
-		if (h->m == 0) { nblocks = 0; grid = 1; per = 1; }   /* nothing to re-read: the emit kernel leaves out_off = {0} alone */
-		ngb = ((uint64_t)h->nbytes + HITS_BLOCK - 1u) / HITS_BLOCK;
-		if (h->m != 0) TTRY(hipMalloc((void **)&h->d_lines, (uint64_t)h->m * sizeof(uint64_t)));
-		if (bytes) {
-			TTRY(hipMalloc((void **)&h->d_off, ((uint64_t)h->m + 1u) * sizeof(uint64_t)));
-			if (h->m != 0) {
-				TTRY(hipMalloc((void **)&h->d_src, (uint64_t)h->m * sizeof(uint64_t)));
-				TTRY(hipMalloc((void **)&h->d_first, (ngb + 1u) * sizeof(uint64_t)));
-				TTRY(hipMalloc((void **)&h->d_bytes, ngb * HITS_BLOCK));
-			}
-		}
-		TTRY(hipEventRecord(h->ev[2], s));
-		if (h->m != 0 || bytes) {
-			hipLaunchKernelGGL(hits_emit, dim3((unsigned)grid), dim3(HITS_THREADS), 0, s, d_bitmap, (const uint64_t *)t->d_off, n, invert, nblocks,
-			                   per, (const uint64_t *)h->d_pairs, (uint64_t)h->m, (uint64_t)h->nbytes, h->d_lines, h->d_off, h->d_src,
-			                   h->d_first, ngb);
-			TTRY(hipGetLastError());
-		}
-		TTRY(hipEventRecord(h->ev[3], s));
-		if (cx != nullptr) {    /* the marks of the m hits: core and group, ceil(m / 64) words each */
-			TTRY(hipEventRecord(h->cev[2], s));
-			if (h->m != 0) {
-				const uint64_t mwords = ((uint64_t)h->m + 63u) / 64u, mgrid = ((uint64_t)h->m + CTX_THREADS - 1u) / CTX_THREADS;
-				if (mgrid > 0x7fffffffu) { errno = ENOMEM; goto fail; }
-				TTRY(hipMalloc((void **)&h->d_core, mwords * sizeof(uint64_t)));
-				TTRY(hipMalloc((void **)&h->d_group, mwords * sizeof(uint64_t)));
-				hipLaunchKernelGGL(ctx_marks, dim3((unsigned)mgrid), dim3(CTX_THREADS), 0, s, (const uint64_t *)h->d_lines, (uint64_t)h->m,
-				                   cx->d_bitmap, (const uint64_t *)h->d_fmap, n, cx->invert, h->d_core, h->d_group,
-				                   h->d_cmeta);
-				TTRY(hipGetLastError());
-			}
-			TTRY(hipEventRecord(h->cev[3], s));
-		}
-		if (t->nfiles != 0) {   /* also under NO_BYTES and when m == 0 */
-			const uint64_t nends = (uint64_t)t->nfiles + 1u;
-			h->nfiles = t->nfiles;
-			for (hipEvent_t &ev : h->fev) TTRY(hipEventCreate(&ev));
-			TTRY(hipMalloc((void **)&h->d_file_first, nends * sizeof(uint64_t)));
-			TTRY(hipEventRecord(h->fev[0], s));
-			hipLaunchKernelGGL(hits_file_first, dim3((unsigned)((nends + HITS_THREADS - 1u) / HITS_THREADS)), dim3(HITS_THREADS), 0, s,
-			                   (const uint64_t *)h->d_lines, (uint64_t)h->m, (const uint64_t *)t->d_file_lines, nends, h->d_file_first);
-			TTRY(hipGetLastError());
-			TTRY(hipEventRecord(h->fev[1], s));
-		}
-		TTRY(hipEventRecord(h->ev[4], s));
-		if (ngb != 0) {
-			uint64_t gg = max_workgroups(t->device);
-			if (gg > ngb) gg = ngb;
-			const uint64_t gper = (ngb + gg - 1u) / gg;
-			gg = (ngb + gper - 1u) / gper;
-			hipLaunchKernelGGL(hits_gather, dim3((unsigned)gg), dim3(HITS_THREADS), 0, s, t->d_text, (uint64_t)t->nbytes,
-			                   (const uint64_t *)h->d_off, (const uint64_t *)h->d_src, (const uint64_t *)h->d_first, (uint64_t)h->m,
-			                   (uint64_t)h->nbytes, ngb, gper, h->d_bytes);
-			TTRY(hipGetLastError());
-		}
-		TTRY(hipEventRecord(h->ev[5], s));
-	}
-	return h;
-fail:
-	{
-		const int e = errno;
-		(void)hipStreamSynchronize(s);
-		fsm_hip_text_hits_free(h);
-		errno = e;
-	}
+	if (text_hits_run(h, t, d_bitmap, flags, ctx, s) == 0) return h;
+	const int e = errno;
+	(void)hipStreamSynchronize(s);
+	fsm_hip_text_hits_free(h);
+	errno = e;
 	return nullptr;
 }
 
@@ -1170,258 +1175,135 @@ static int text_hits_check(const struct fsm_hip_text *t, unsigned flags)
 	return 0;
 }
 
-extern "C" struct fsm_hip_text_hits *fsm_hip_text_hits_device(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags,
+/* the device forms: the caller's bitmap, the caller's stream, nothing waited for beyond the run's own wait */
+static struct fsm_hip_text_hits *text_hits_device(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags, const uint64_t *ctx,
 	void *hip_stream)
 {
 	if (!have_device()) { errno = ENODEV; return nullptr; }
 	if (text_hits_check(t, flags) != 0) return nullptr;
 	if (d_bitmap == nullptr && t->n != 0) { errno = EINVAL; return nullptr; }
-	return text_hits_run(t, d_bitmap, flags, static_cast<hipStream_t>(hip_stream));
+	return text_hits_new(t, d_bitmap, flags, ctx, static_cast<hipStream_t>(hip_stream));
 }
 
-extern "C" struct fsm_hip_text_hits *fsm_hip_text_hits(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t, unsigned flags)
+/* the host forms: the walk's bitmap on the text's own stream, which is idle at return: the bitmap is released then, and the
+ * gather and the marks have read it */
+static struct fsm_hip_text_hits *text_hits_host(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t, unsigned flags,
+	const uint64_t *ctx)
 {
 	if (!have_device()) { errno = ENODEV; return nullptr; }
 	if (text_hits_check(t, flags) != 0 || text_exec_check(ld, t) != 0) return nullptr;
 	DevGuard dg(t->device);
 	if (!dg.ok()) { errno = ENODEV; return nullptr; }
-	uint64_t *d_bm = nullptr;
+	DevBuf<uint64_t> d_bm;
 	struct fsm_hip_text_hits *h = nullptr;
-	{
-		if (t->n != 0) {
-			TTRY(hipMalloc((void **)&d_bm, (t->n + 63u) / 64u * sizeof(uint64_t)));
-			TTRY(hipStreamWaitEvent(t->own, t->ev[3], 0));
-			if (fsm_hip_text_exec_device(ld, t, nullptr, d_bm, 0, nullptr, nullptr, t->own) != 0) goto fail;
-		}
-		h = text_hits_run(t, d_bm, flags, t->own);
-		if (h == nullptr) goto fail;
-		TTRY(hipStreamSynchronize(t->own));
-	}
-	if (d_bm != nullptr) (void)hipFree(d_bm);
-	return h;
-fail:
-	{
-		const int e = errno;
-		(void)hipStreamSynchronize(t->own);
-		if (h != nullptr) fsm_hip_text_hits_free(h);
-		if (d_bm != nullptr) (void)hipFree(d_bm);
-		errno = e;
-	}
+	bool ok = true;
+	if (t->n != 0)
+		ok = TOK(d_bm.alloc((t->n + 63u) / 64u)) && TOK(hipStreamWaitEvent(t->own, t->ev[3], 0)) &&
+		     fsm_hip_text_exec_device(ld, t, nullptr, d_bm, 0, nullptr, nullptr, t->own) == 0;
+	ok = ok && (h = text_hits_new(t, d_bm, flags, ctx, t->own)) != nullptr;
+	ok = ok && TOK(hipStreamSynchronize(t->own));
+	if (ok) return h;
+	const int e = errno;
+	(void)hipStreamSynchronize(t->own);
+	if (h != nullptr) fsm_hip_text_hits_free(h);
+	errno = e;
 	return nullptr;
 }
 
-/* the widening on stream s, then the hits' own passes over W with invert 0: the one wait is theirs */
-static struct fsm_hip_text_hits *text_hits_context_run(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags, uint64_t before,
-	uint64_t after, hipStream_t s)
+extern "C" struct fsm_hip_text_hits *fsm_hip_text_hits_device(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags,
+	void *hip_stream)
 {
-	const uint64_t n = t->n, nwords = (n + 63u) / 64u, nblocks = (n + HITS_LINES - 1u) / HITS_LINES;
-	const uint64_t grid = (nblocks + CTX_WG_BLOCKS - 1u) / CTX_WG_BLOCKS;
-	struct ctx_run cx = {d_bitmap, (flags & FSM_HIP_HITS_INVERT) != 0u ? 1u : 0u, 0u};
-	struct fsm_hip_text_hits *h = new (std::nothrow) struct fsm_hip_text_hits;
-	if (h == nullptr) { errno = ENOMEM; return nullptr; }
-	h->device = t->device;
-	h->context = true;
-	{
-		DevGuard dg(t->device);
-		if (!dg.ok()) { errno = ENODEV; goto fail; }
-		if (grid > 0x7fffffffu) { errno = ENOMEM; goto fail; }
-		for (hipEvent_t &ev : h->cev) TTRY(hipEventCreate(&ev));
-		TTRY(hipStreamWaitEvent(s, t->ev[3], 0));   /* the text's offsets and file_lines first */
-		if (n != 0) {
-			TTRY(hipMalloc((void **)&h->d_wide, nwords * sizeof(uint64_t)));
-			TTRY(hipMalloc((void **)&h->d_sum, (4u * nblocks + 2u) * sizeof(uint64_t)));
-			if (t->nfiles != 0) TTRY(hipMalloc((void **)&h->d_fmap, nwords * sizeof(uint64_t)));
-		}
-		TTRY(hipEventRecord(h->cev[0], s));
-		if (n != 0) {
-			uint64_t *d_meta = h->d_cmeta = h->d_sum + 4u * nblocks;
-			TTRY(hipMemsetAsync(d_meta, 0, 2u * sizeof(uint64_t), s));
-			if (t->nfiles != 0) {
-				const uint64_t nends = (uint64_t)t->nfiles + 1u;
-				TTRY(hipMemsetAsync(h->d_fmap, 0, nwords * sizeof(uint64_t), s));
-				hipLaunchKernelGGL(ctx_file_starts, dim3((unsigned)((nends + CTX_THREADS - 1u) / CTX_THREADS)), dim3(CTX_THREADS), 0, s,
-				                   (const uint64_t *)t->d_file_lines, nends, n, h->d_fmap);
-				TTRY(hipGetLastError());
-			}
-			hipLaunchKernelGGL(ctx_summary, dim3((unsigned)grid), dim3(CTX_THREADS), 0, s, d_bitmap, (const uint64_t *)h->d_fmap, n, nwords,
-			                   cx.invert, nblocks, h->d_sum, d_meta);
-			TTRY(hipGetLastError());
-			hipLaunchKernelGGL(ctx_scan, dim3(1), dim3(CTX_SCAN_THREADS), 0, s, h->d_sum, nblocks, n);
-			TTRY(hipGetLastError());
-			hipLaunchKernelGGL(ctx_apply, dim3((unsigned)grid), dim3(CTX_THREADS), 0, s, d_bitmap, (const uint64_t *)h->d_fmap, n, nwords,
-			                   cx.invert, nblocks, (const uint64_t *)h->d_sum, before, after, h->d_wide);
-			TTRY(hipGetLastError());
-		}
-		TTRY(hipEventRecord(h->cev[1], s));
-	}
-	return text_hits_run(t, h->d_wide, flags & FSM_HIP_HITS_NO_BYTES, s, h, &cx);   /* frees h when it fails */
-fail:
-	{
-		const int e = errno;
-		(void)hipStreamSynchronize(s);
-		fsm_hip_text_hits_free(h);
-		errno = e;
-	}
-	return nullptr;
+	return text_hits_device(t, d_bitmap, flags, nullptr, hip_stream);
+}
+
+extern "C" struct fsm_hip_text_hits *fsm_hip_text_hits(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t, unsigned flags)
+{
+	return text_hits_host(ld, t, flags, nullptr);
 }
 
 extern "C" struct fsm_hip_text_hits *fsm_hip_text_hits_context_device(const struct fsm_hip_text *t, const uint64_t *d_bitmap, unsigned flags,
 	uint64_t before, uint64_t after, void *hip_stream)
 {
-	if (!have_device()) { errno = ENODEV; return nullptr; }
-	if (text_hits_check(t, flags) != 0) return nullptr;
-	if (d_bitmap == nullptr && t->n != 0) { errno = EINVAL; return nullptr; }
-	return text_hits_context_run(t, d_bitmap, flags, before, after, static_cast<hipStream_t>(hip_stream));
+	const uint64_t ctx[2] = {before, after};
+	return text_hits_device(t, d_bitmap, flags, ctx, hip_stream);
 }
 
 extern "C" struct fsm_hip_text_hits *fsm_hip_text_hits_context(const struct fsm_hip_lines_dfa *ld, const struct fsm_hip_text *t, unsigned flags,
 	uint64_t before, uint64_t after)
 {
-	if (!have_device()) { errno = ENODEV; return nullptr; }
-	if (text_hits_check(t, flags) != 0 || text_exec_check(ld, t) != 0) return nullptr;
-	DevGuard dg(t->device);
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
-	uint64_t *d_bm = nullptr;
-	struct fsm_hip_text_hits *h = nullptr;
-	{
-		if (t->n != 0) {
-			TTRY(hipMalloc((void **)&d_bm, (t->n + 63u) / 64u * sizeof(uint64_t)));
-			TTRY(hipStreamWaitEvent(t->own, t->ev[3], 0));
-			if (fsm_hip_text_exec_device(ld, t, nullptr, d_bm, 0, nullptr, nullptr, t->own) != 0) goto fail;
-		}
-		h = text_hits_context_run(t, d_bm, flags, before, after, t->own);
-		if (h == nullptr) goto fail;
-		TTRY(hipStreamSynchronize(t->own));   /* the marks have read the walk's bitmap */
-	}
-	if (d_bm != nullptr) (void)hipFree(d_bm);
-	return h;
-fail:
-	{
-		const int e = errno;
-		(void)hipStreamSynchronize(t->own);
-		if (h != nullptr) fsm_hip_text_hits_free(h);
-		if (d_bm != nullptr) (void)hipFree(d_bm);
-		errno = e;
-	}
-	return nullptr;
+	const uint64_t ctx[2] = {before, after};
+	return text_hits_host(ld, t, flags, ctx);
 }
 
-extern "C" const uint64_t *fsm_hip_text_hits_core_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_core; }
-extern "C" const uint64_t *fsm_hip_text_hits_group_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_group; }
+extern "C" const uint64_t *fsm_hip_text_hits_core_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_core.p; }
+extern "C" const uint64_t *fsm_hip_text_hits_group_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_group.p; }
 extern "C" size_t fsm_hip_text_hits_core_count(const struct fsm_hip_text_hits *h) { return h == nullptr ? 0 : h->core_count; }
 extern "C" size_t fsm_hip_text_context_scan_block(void) { return CTX_SCAN_THREADS; }
 
 extern "C" int fsm_hip_text_hits_marks(const struct fsm_hip_text_hits *h, uint64_t *core, uint64_t *group)
 {
 	if (h == nullptr || !h->context) { errno = EINVAL; return -1; }
-	DevGuard dg(h->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	TTRY(hipEventSynchronize(h->ev[5]));
-	if (core != nullptr && h->m != 0) TTRY(hipMemcpy(core, h->d_core, (h->m + 63u) / 64u * sizeof(uint64_t), hipMemcpyDeviceToHost));
-	if (group != nullptr && h->m != 0) TTRY(hipMemcpy(group, h->d_group, (h->m + 63u) / 64u * sizeof(uint64_t), hipMemcpyDeviceToHost));
-	return 0;
-fail:
-	return -1;
+	const size_t nb = (h->m + 63u) / 64u * sizeof(uint64_t);
+	return copy_out(h->device, h->ev[5], {{core, h->d_core, nb}, {group, h->d_group, nb}});
 }
 
 extern "C" size_t fsm_hip_text_hits_groups(const struct fsm_hip_text_hits *h)
 {
 	uint64_t g = 0;
 	if (h == nullptr || !h->context || h->m == 0) return 0;
-	DevGuard dg(h->device);
-	if (!dg.ok()) { errno = ENODEV; return 0; }
-	TTRY(hipEventSynchronize(h->ev[5]));
-	TTRY(hipMemcpy(&g, h->d_cmeta + 1, sizeof g, hipMemcpyDeviceToHost));
+	(void)copy_out(h->device, h->ev[5], {{&g, h->d_cmeta + 1, sizeof g}});   /* g stays 0 when it fails */
 	return (size_t)g;
-fail:
-	return 0;
 }
 
 extern "C" double fsm_hip_text_hits_context_ms(const struct fsm_hip_text_hits *h)
 {
-	float a = 0.f, b = 0.f;
 	if (h == nullptr || !h->context) { errno = EINVAL; return -1.0; }
-	DevGuard dg(h->device);
-	if (!dg.ok()) { errno = ENODEV; return -1.0; }
-	TTRY(hipEventSynchronize(h->ev[5]));
-	TTRY(hipEventElapsedTime(&a, h->cev[0], h->cev[1]));
-	TTRY(hipEventElapsedTime(&b, h->cev[2], h->cev[3]));
-	return (double)a + (double)b;
-fail:
-	return -1.0;
+	return elapsed_ms(h->device, h->ev[5], {{h->cev[0], h->cev[1]}, {h->cev[2], h->cev[3]}});
 }
 
 extern "C" size_t fsm_hip_text_hits_count(const struct fsm_hip_text_hits *h) { return h == nullptr ? 0 : h->m; }
 extern "C" size_t fsm_hip_text_hits_nbytes(const struct fsm_hip_text_hits *h) { return h == nullptr ? 0 : h->nbytes; }
-extern "C" const uint64_t *fsm_hip_text_hits_lines_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_lines; }
-extern "C" const uint64_t *fsm_hip_text_hits_offsets_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_off; }
-extern "C" const unsigned char *fsm_hip_text_hits_bytes_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_bytes; }
+extern "C" const uint64_t *fsm_hip_text_hits_lines_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_lines.p; }
+extern "C" const uint64_t *fsm_hip_text_hits_offsets_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_off.p; }
+extern "C" const unsigned char *fsm_hip_text_hits_bytes_device(const struct fsm_hip_text_hits *h) { return h == nullptr ? nullptr : h->d_bytes.p; }
 extern "C" size_t fsm_hip_text_hits_block_lines(void) { return HITS_LINES; }
 extern "C" size_t fsm_hip_text_hits_block_bytes(void) { return HITS_BLOCK; }
 
 extern "C" int fsm_hip_text_hits_copy(const struct fsm_hip_text_hits *h, uint64_t *lines, uint64_t *out_off, void *bytes)
 {
 	if (h == nullptr || (out_off != nullptr && h->d_off == nullptr)) { errno = EINVAL; return -1; }
-	DevGuard dg(h->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	TTRY(hipEventSynchronize(h->ev[5]));
-	if (lines != nullptr && h->m != 0) TTRY(hipMemcpy(lines, h->d_lines, h->m * sizeof(uint64_t), hipMemcpyDeviceToHost));
-	if (out_off != nullptr) TTRY(hipMemcpy(out_off, h->d_off, (h->m + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-	if (bytes != nullptr && h->nbytes != 0) TTRY(hipMemcpy(bytes, h->d_bytes, h->nbytes, hipMemcpyDeviceToHost));
-	return 0;
-fail:
-	return -1;
+	return copy_out(h->device, h->ev[5], {{lines, h->d_lines, h->m * sizeof(uint64_t)}, {out_off, h->d_off, (h->m + 1u) * sizeof(uint64_t)},
+	                                      {bytes, h->d_bytes, h->nbytes}});
 }
 
 extern "C" const uint64_t *fsm_hip_text_hits_file_first_device(const struct fsm_hip_text_hits *h)
 {
-	return h == nullptr ? nullptr : h->d_file_first;
+	return h == nullptr ? nullptr : h->d_file_first.p;
 }
 
 extern "C" int fsm_hip_text_hits_file_first(const struct fsm_hip_text_hits *h, uint64_t *out)
 {
 	if (h == nullptr || out == nullptr || h->d_file_first == nullptr) { errno = EINVAL; return -1; }
-	DevGuard dg(h->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	TTRY(hipEventSynchronize(h->ev[5]));
-	TTRY(hipMemcpy(out, h->d_file_first, (h->nfiles + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-	return 0;
-fail:
-	return -1;
+	return copy_out(h->device, h->ev[5], {{out, h->d_file_first, (h->nfiles + 1u) * sizeof(uint64_t)}});
 }
 
 extern "C" double fsm_hip_text_hits_file_first_ms(const struct fsm_hip_text_hits *h)
 {
-	float a = 0.f;
 	if (h == nullptr || h->d_file_first == nullptr) { errno = EINVAL; return -1.0; }
-	DevGuard dg(h->device);
-	if (!dg.ok()) { errno = ENODEV; return -1.0; }
-	TTRY(hipEventSynchronize(h->ev[5]));
-	TTRY(hipEventElapsedTime(&a, h->fev[0], h->fev[1]));
-	return (double)a;
-fail:
-	return -1.0;
+	return elapsed_ms(h->device, h->ev[5], {{h->fev[0], h->fev[1]}});
 }
 
-static double hits_ms_of(const struct fsm_hip_text_hits *h, bool select, bool gather)
+extern "C" double fsm_hip_text_hits_ms(const struct fsm_hip_text_hits *h)
 {
-	float a = 0.f, b = 0.f, c = 0.f;
 	if (h == nullptr) { errno = EINVAL; return -1.0; }
-	DevGuard dg(h->device);
-	if (!dg.ok()) { errno = ENODEV; return -1.0; }
-	TTRY(hipEventSynchronize(h->ev[5]));
-	if (select) {
-		TTRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-		TTRY(hipEventElapsedTime(&b, h->ev[2], h->ev[3]));
-	}
-	if (gather) TTRY(hipEventElapsedTime(&c, h->ev[4], h->ev[5]));
-	return (double)a + (double)b + (double)c;
-fail:
-	return -1.0;
+	return elapsed_ms(h->device, h->ev[5], {{h->ev[0], h->ev[1]}, {h->ev[2], h->ev[3]}, {h->ev[4], h->ev[5]}});
 }
 
-extern "C" double fsm_hip_text_hits_ms(const struct fsm_hip_text_hits *h) { return hits_ms_of(h, true, true); }
-extern "C" double fsm_hip_text_hits_gather_ms(const struct fsm_hip_text_hits *h) { return hits_ms_of(h, false, true); }
+extern "C" double fsm_hip_text_hits_gather_ms(const struct fsm_hip_text_hits *h)
+{
+	if (h == nullptr) { errno = EINVAL; return -1.0; }
+	return elapsed_ms(h->device, h->ev[5], {{h->ev[4], h->ev[5]}});
+}
 
 /* ---- files of a text: lines cut at every file end as well ----------------------------------------------------------
  * file_off[0 .. nfiles] are byte positions (0 first, non-decreasing, nbytes last); the offsets of the text become the sorted
@@ -1477,50 +1359,12 @@ files_mark(const unsigned char *text, uint64_t nbytes, uint32_t delim, const uin
 	if (threadIdx.x == 0) *(glb_u64x2w)(uintptr_t)(pairs + 2u * blockIdx.x) = u64x2{tot, anybad};
 }
 
-/* exclusive scan of the pairs in place by one workgroup, FILES_SCAN_THREADS a round; meta[0] = the added ends, meta[1] != 0 iff
- * the array is invalid: the second half of the 32 bytes the host waits for */
+/* the exclusive scan of the pairs, FILES_SCAN_THREADS a round; meta[0] = the added ends, meta[1] != 0 iff the array is invalid:
+ * the second half of the 32 bytes the host waits for */
 __global__ void __launch_bounds__(FILES_SCAN_THREADS)
 files_scan(uint64_t *pairs, uint64_t nblocks, uint64_t *meta)
 {
-	__shared__ uint64_t wtot[FILES_SCAN_THREADS / 64u][2];
-	__shared__ uint64_t carry[2];
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	if (threadIdx.x == 0) { carry[0] = 0; carry[1] = 0; }
-	__syncthreads();
-	for (uint64_t b0 = 0; b0 < nblocks; b0 += FILES_SCAN_THREADS) {
-		const uint64_t b = b0 + threadIdx.x;
-		const u64x2 mine = b < nblocks ? *(glb_u64x2p)(uintptr_t)(pairs + 2u * b) : u64x2{0u, 0u};
-		uint64_t xc = mine.x, xb = mine.y;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint64_t yc = __shfl_up(xc, d, 64), yb = __shfl_up(xb, d, 64);
-			if (lane >= (uint32_t)d) { xc += yc; xb += yb; }
-		}
-		if (lane == 63u) { wtot[wave][0] = xc; wtot[wave][1] = xb; }
-		__syncthreads();
-		uint64_t bc = carry[0], bb = carry[1];
-		for (uint32_t w = 0; w < wave; w++) { bc += wtot[w][0]; bb += wtot[w][1]; }
-		if (b < nblocks) *(glb_u64x2w)(uintptr_t)(pairs + 2u * b) = u64x2{bc + xc - mine.x, bb + xb - mine.y};
-		__syncthreads();
-		if (threadIdx.x == FILES_SCAN_THREADS - 1u) { carry[0] = bc + xc; carry[1] = bb + xb; }
-		__syncthreads();
-	}
-	if (threadIdx.x == 0) {
-		glb_u64w m = (glb_u64w)(uintptr_t)meta;
-		m[0] = carry[0];
-		m[1] = carry[1];
-	}
-}
-
-/* the first index in a[0, n) whose entry is >= v (n if none) */
-__device__ __forceinline__ uint64_t lower_bound_glb(glb_u64p a, uint64_t n, uint64_t v)
-{
-	uint64_t lo = 0, hi = n;
-	while (lo < hi) {
-		const uint64_t mid = lo + (hi - lo) / 2u;
-		if (a[mid] < v) lo = mid + 1u; else hi = mid;
-	}
-	return lo;
+	sum_scan<FILES_SCAN_THREADS, 2, 1>(pairs, nblocks, meta);
 }
 
 /* lanes [0, np1) take the plain offsets, lanes [np1, np1 + nends) the file ends; n + 1 = np1 + added entries of off */
@@ -1547,75 +1391,133 @@ files_merge(const uint64_t *plain, uint64_t np1, const uint64_t *file_off, uint6
 
 }   // namespace
 
-/* count + scan of the delimiters and mark + scan of the file ends, ONE wait, then the plain offsets and the merge: on stream s */
-static int text_scan_files(struct fsm_hip_text *t, hipStream_t s)
+/* ---- opening a text: plain (nfiles == 0) or of files ---- */
+
+/* on stream s over t->d_text: count + scan of the delimiters and, for files, mark + scan of the file ends; ONE wait (the totals
+ * size the arrays, and tell a file_off that is none); then the plain offsets and, for files, the merge */
+static int text_cut(struct fsm_hip_text *t, hipStream_t s)
 {
-	const uint64_t nbytes = t->nbytes, nends = (uint64_t)t->nfiles + 1u;
+	const bool files = t->nfiles != 0;
+	const uint64_t nbytes = t->nbytes, nends = files ? (uint64_t)t->nfiles + 1u : 0u;
 	const uint32_t splat = (uint32_t)t->delim * 0x01010101u;
 	const uint64_t nblocks = (nbytes + TEXT_BLOCK - 1u) / TEXT_BLOCK, nfb = (nends + FILES_THREADS - 1u) / FILES_THREADS;
-	uint64_t meta[4] = {0, 0, 0, 0}, grid = 1, per = 1, np1 = 1, nmerge = 0;
+	const uint64_t nmeta = files ? 4u : 2u;
+	uint64_t meta[4] = {0, 0, 0, 0};
 	if (nfb > 0x7fffffffu) { errno = ENOMEM; return -1; }
-	for (hipEvent_t &ev : t->ev) TTRY(hipEventCreate(&ev));
-	for (hipEvent_t &ev : t->fev) TTRY(hipEventCreate(&ev));
-	TTRY(hipMalloc((void **)&t->d_cnt, (nblocks + 4u) * sizeof(uint64_t)));   /* + the 4 words of meta */
-	TTRY(hipMalloc((void **)&t->d_frank, nends * sizeof(uint64_t)));
-	TTRY(hipMalloc((void **)&t->d_fpairs, 2u * nfb * sizeof(uint64_t)));
-	TTRY(hipMalloc((void **)&t->d_file_lines, nends * sizeof(uint64_t)));
-	{
-		uint64_t *d_meta = t->d_cnt + nblocks;
-		TTRY(hipEventRecord(t->ev[0], s));
-		if (nbytes != 0) {
-			grid = max_workgroups(t->device);
-			if (grid > nblocks) grid = nblocks;
-			per = (nblocks + grid - 1u) / grid;
-			grid = (nblocks + per - 1u) / per;
-			hipLaunchKernelGGL(text_count, dim3((unsigned)grid), dim3(TEXT_THREADS), 0, s, t->d_text, nbytes, splat, nblocks, per, t->d_cnt);
-			TTRY(hipGetLastError());
-			hipLaunchKernelGGL(text_scan, dim3(1), dim3(1024), 0, s, t->d_cnt, nblocks, t->d_text, nbytes, (uint32_t)t->delim, d_meta);
-			TTRY(hipGetLastError());
-		} else {
-			TTRY(hipMemsetAsync(d_meta, 0, 2u * sizeof(uint64_t), s));
-		}
-		TTRY(hipEventRecord(t->ev[1], s));
-		TTRY(hipEventRecord(t->fev[0], s));
-		hipLaunchKernelGGL(files_mark, dim3((unsigned)nfb), dim3(FILES_THREADS), 0, s, t->d_text, nbytes, (uint32_t)t->delim, t->d_file_off,
-		                   nends, t->d_frank, t->d_fpairs);
-		TTRY(hipGetLastError());
+	for (DevEvent &ev : t->ev)
+		if (!TOK(ev.create())) return -1;
+	if (!files && nbytes == 0) {   /* no byte, no line: off[0] = 0 alone */
+		if (!TOK(t->d_off.alloc(1)) || !TOK(hipMemsetAsync(t->d_off, 0, sizeof(uint64_t), s))) return -1;
+		for (DevEvent &ev : t->ev)
+			if (!TOK(hipEventRecord(ev, s))) return -1;
+		return 0;
+	}
+	const Grid g = grid_of(nblocks, t->device);
+	if (!TOK(t->d_cnt.alloc(nblocks + nmeta))) return -1;
+	uint64_t *d_meta = t->d_cnt + nblocks;
+	if (files) {
+		for (DevEvent &ev : t->fev)
+			if (!TOK(ev.create())) return -1;
+		if (!TOK(t->d_frank.alloc(nends)) || !TOK(t->d_fpairs.alloc(2u * nfb)) || !TOK(t->d_file_lines.alloc(nends))) return -1;
+	}
+	if (!TOK(hipEventRecord(t->ev[0], s))) return -1;
+	if (nbytes != 0) {
+		hipLaunchKernelGGL(text_count, dim3((unsigned)g.wgs), dim3(TEXT_THREADS), 0, s, t->d_text, nbytes, splat, nblocks, g.per, t->d_cnt);
+		if (!TOK(hipGetLastError())) return -1;
+		hipLaunchKernelGGL(text_scan, dim3(1), dim3(1024), 0, s, t->d_cnt, nblocks, t->d_text, nbytes, (uint32_t)t->delim, d_meta);
+		if (!TOK(hipGetLastError())) return -1;
+	} else if (!TOK(hipMemsetAsync(d_meta, 0, 2u * sizeof(uint64_t), s))) {
+		return -1;
+	}
+	if (!TOK(hipEventRecord(t->ev[1], s))) return -1;
+	if (files) {
+		if (!TOK(hipEventRecord(t->fev[0], s))) return -1;
+		hipLaunchKernelGGL(files_mark, dim3((unsigned)nfb), dim3(FILES_THREADS), 0, s, t->d_text, nbytes, (uint32_t)t->delim, t->d_file_off, nends,
+		                   t->d_frank, t->d_fpairs);
+		if (!TOK(hipGetLastError())) return -1;
 		hipLaunchKernelGGL(files_scan, dim3(1), dim3(FILES_SCAN_THREADS), 0, s, t->d_fpairs, nfb, d_meta + 2);
-		TTRY(hipGetLastError());
-		TTRY(hipEventRecord(t->fev[1], s));
-		TTRY(hipMemcpyAsync(meta, d_meta, sizeof meta, hipMemcpyDeviceToHost, s));
-		TTRY(hipStreamSynchronize(s));
-		if (meta[3] != 0) { errno = EINVAL; goto fail; }
-		np1 = nbytes == 0 ? 1u : meta[0] + (meta[1] != 0 ? 0u : 1u) + 1u;   /* the plain offsets: fsm_hip_text_open's n + 1 */
-		t->n = (size_t)(np1 - 1u + meta[2]);
-		nmerge = (np1 + nends + FILES_THREADS - 1u) / FILES_THREADS;
-		if (nmerge > 0x7fffffffu) { errno = ENOMEM; goto fail; }
-		TTRY(hipMalloc((void **)&t->d_plain, np1 * sizeof(uint64_t)));
-		TTRY(hipMalloc((void **)&t->d_off, ((uint64_t)t->n + 1u) * sizeof(uint64_t)));
-		TTRY(hipEventRecord(t->ev[2], s));
-		if (nbytes != 0) {
-			hipLaunchKernelGGL(text_offsets, dim3((unsigned)grid), dim3(TEXT_THREADS), 0, s, t->d_text, nbytes, splat, nblocks, per,
-			                   (const uint64_t *)t->d_cnt, meta[0], np1 - 1u, t->d_plain);
-			TTRY(hipGetLastError());
-		} else {
-			TTRY(hipMemsetAsync(t->d_plain, 0, sizeof(uint64_t), s));
-		}
-		TTRY(hipEventRecord(t->fev[2], s));
-		hipLaunchKernelGGL(files_merge, dim3((unsigned)nmerge), dim3(FILES_THREADS), 0, s, (const uint64_t *)t->d_plain, np1, t->d_file_off,
-		                   nends, (const uint64_t *)t->d_frank, (const uint64_t *)t->d_fpairs, meta[2], (uint64_t)t->n, t->d_off,
-		                   t->d_file_lines);
-		TTRY(hipGetLastError());
-		TTRY(hipEventRecord(t->ev[3], s));
+		if (!TOK(hipGetLastError())) return -1;
+		if (!TOK(hipEventRecord(t->fev[1], s))) return -1;
 	}
-	return 0;
-fail:
-	{
-		const int e = errno;
-		(void)hipStreamSynchronize(s);   /* nothing of this text is in flight when it is freed */
-		errno = e;
+	if (!TOK(hipMemcpyAsync(meta, d_meta, nmeta * sizeof(uint64_t), hipMemcpyDeviceToHost, s))) return -1;
+	if (!TOK(hipStreamSynchronize(s))) return -1;
+	if (meta[3] != 0) { errno = EINVAL; return -1; }
+	/* the plain offsets: bytes after the last delimiter form a last line */
+	const uint64_t np1 = nbytes == 0 ? 1u : meta[0] + (meta[1] != 0 ? 0u : 1u) + 1u;
+	const uint64_t nmerge = (np1 + nends + FILES_THREADS - 1u) / FILES_THREADS;
+	t->n = (size_t)(np1 - 1u + meta[2]);
+	if (files) {
+		if (nmerge > 0x7fffffffu) { errno = ENOMEM; return -1; }
+		if (!TOK(t->d_plain.alloc(np1))) return -1;
 	}
-	return -1;
+	if (!TOK(t->d_off.alloc((uint64_t)t->n + 1u))) return -1;
+	uint64_t *d_plain = files ? t->d_plain : t->d_off;
+	if (!TOK(hipEventRecord(t->ev[2], s))) return -1;
+	if (nbytes != 0) {
+		hipLaunchKernelGGL(text_offsets, dim3((unsigned)g.wgs), dim3(TEXT_THREADS), 0, s, t->d_text, nbytes, splat, nblocks, g.per, t->d_cnt, meta[0],
+		                   np1 - 1u, d_plain);
+		if (!TOK(hipGetLastError())) return -1;
+	} else if (!TOK(hipMemsetAsync(d_plain, 0, sizeof(uint64_t), s))) {
+		return -1;
+	}
+	if (files) {
+		if (!TOK(hipEventRecord(t->fev[2], s))) return -1;
+		hipLaunchKernelGGL(files_merge, dim3((unsigned)nmerge), dim3(FILES_THREADS), 0, s, d_plain, np1, t->d_file_off, nends, t->d_frank,
+		                   t->d_fpairs, meta[2], (uint64_t)t->n, t->d_off, t->d_file_lines);
+		if (!TOK(hipGetLastError())) return -1;
+	}
+	return TOK(hipEventRecord(t->ev[3], s)) ? 0 : -1;
+}
+
+/* what the four open entry points share once their own arguments are checked */
+static struct fsm_hip_text *text_open(const void *text, size_t nbytes, int delim, const uint64_t *file_off, size_t nfiles, void *hip_stream,
+	bool host)
+{
+	if (delim < 0 || delim > 255) { errno = EINVAL; return nullptr; }
+	if (!have_device()) { errno = ENODEV; return nullptr; }   /* no CPU path, as everywhere in this library */
+	struct fsm_hip_text *t = new (std::nothrow) fsm_hip_text;
+	if (t == nullptr) { errno = ENOMEM; return nullptr; }
+	t->nbytes = nbytes;
+	t->delim = delim;
+	t->nfiles = nfiles;
+	if (hipGetDevice(&t->device) != hipSuccess) { delete t; errno = ENODEV; return nullptr; }
+	if (!TOK(hipStreamCreateWithFlags(&t->own, hipStreamNonBlocking))) { delete t; return nullptr; }
+	hipStream_t s = host ? t->own : static_cast<hipStream_t>(hip_stream);
+	bool ok = true;
+	if (!host) {   /* the caller's device memory, the caller's stream: the offsets are in flight at return */
+		t->d_text = static_cast<const unsigned char *>(text);
+		t->d_file_off = file_off;
+	} else {       /* copied to the device on the text's own stream, which is idle at return */
+		const uint64_t nends = (uint64_t)nfiles + 1u;
+		if (nbytes != 0) ok = TOK(t->owned.alloc(nbytes)) && TOK(hipMemcpyAsync(t->owned, text, nbytes, hipMemcpyHostToDevice, s));
+		if (ok && nfiles != 0)
+			ok = TOK(t->owned_file_off.alloc(nends)) &&
+			     TOK(hipMemcpyAsync(t->owned_file_off, file_off, nends * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+		t->d_text = t->owned;
+		t->d_file_off = t->owned_file_off;
+	}
+	ok = ok && text_cut(t, s) == 0 && (!host || TOK(hipStreamSynchronize(s)));
+	if (ok) {
+		if (host) t->d_plain.reset();   /* the merge has read them */
+		return t;
+	}
+	const int e = errno;
+	(void)hipStreamSynchronize(s);   /* nothing of this text is in flight when it is freed */
+	fsm_hip_text_free(t);
+	errno = e;
+	return nullptr;
+}
+
+extern "C" struct fsm_hip_text *fsm_hip_text_open_device(const void *d_text, size_t nbytes, int delim, void *hip_stream)
+{
+	if (d_text == nullptr && nbytes != 0) { errno = EINVAL; return nullptr; }
+	return text_open(d_text, nbytes, delim, nullptr, 0, hip_stream, false);
+}
+
+extern "C" struct fsm_hip_text *fsm_hip_text_open(const void *text, size_t nbytes, int delim)
+{
+	if (text == nullptr && nbytes != 0) { errno = EINVAL; return nullptr; }
+	return text_open(text, nbytes, delim, nullptr, 0, nullptr, true);
 }
 
 extern "C" struct fsm_hip_text *fsm_hip_text_open_files_device(const void *d_text, size_t nbytes, int delim, const uint64_t *d_file_off,
@@ -1623,16 +1525,7 @@ extern "C" struct fsm_hip_text *fsm_hip_text_open_files_device(const void *d_tex
 {
 	if (!have_device()) { errno = ENODEV; return nullptr; }
 	if ((d_text == nullptr && nbytes != 0) || d_file_off == nullptr || nfiles == 0) { errno = EINVAL; return nullptr; }
-	struct fsm_hip_text *t = text_new(nbytes, delim);
-	if (t == nullptr) return nullptr;
-	t->d_text = static_cast<const unsigned char *>(d_text);
-	t->nfiles = nfiles;
-	t->d_file_off = d_file_off;
-	if (text_scan_files(t, static_cast<hipStream_t>(hip_stream)) != 0) {
-		fsm_hip_text_free(t);
-		return nullptr;
-	}
-	return t;
+	return text_open(d_text, nbytes, delim, d_file_off, nfiles, hip_stream, false);
 }
 
 extern "C" struct fsm_hip_text *fsm_hip_text_open_files(const void *text, size_t nbytes, int delim, const uint64_t *file_off, size_t nfiles)
@@ -1642,55 +1535,23 @@ extern "C" struct fsm_hip_text *fsm_hip_text_open_files(const void *text, size_t
 	if (file_off[0] != 0 || file_off[nfiles] != nbytes) { errno = EINVAL; return nullptr; }
 	for (size_t j = 0; j < nfiles; j++)
 		if (file_off[j] > file_off[j + 1u]) { errno = EINVAL; return nullptr; }
-	struct fsm_hip_text *t = text_new(nbytes, delim);
-	if (t == nullptr) return nullptr;
-	t->nfiles = nfiles;
-	if (nbytes != 0) {
-		TTRY(hipMalloc((void **)&t->owned, nbytes));
-		TTRY(hipMemcpyAsync(t->owned, text, nbytes, hipMemcpyHostToDevice, t->own));
-	}
-	t->d_text = t->owned;
-	TTRY(hipMalloc((void **)&t->owned_file_off, ((uint64_t)nfiles + 1u) * sizeof(uint64_t)));
-	TTRY(hipMemcpyAsync(t->owned_file_off, file_off, ((uint64_t)nfiles + 1u) * sizeof(uint64_t), hipMemcpyHostToDevice, t->own));
-	t->d_file_off = t->owned_file_off;
-	if (text_scan_files(t, t->own) != 0) goto fail;
-	TTRY(hipStreamSynchronize(t->own));
-	(void)hipFree(t->d_plain);   /* the merge has read them */
-	t->d_plain = nullptr;
-	return t;
-fail:
-	fsm_hip_text_free(t);
-	return nullptr;
+	return text_open(text, nbytes, delim, file_off, nfiles, nullptr, true);
 }
 
 extern "C" size_t fsm_hip_text_files(const struct fsm_hip_text *t) { return t == nullptr ? 0 : t->nfiles; }
 
-extern "C" const uint64_t *fsm_hip_text_file_lines_device(const struct fsm_hip_text *t) { return t == nullptr ? nullptr : t->d_file_lines; }
+extern "C" const uint64_t *fsm_hip_text_file_lines_device(const struct fsm_hip_text *t) { return t == nullptr ? nullptr : t->d_file_lines.p; }
 
 extern "C" int fsm_hip_text_file_lines(const struct fsm_hip_text *t, uint64_t *out)
 {
 	if (t == nullptr || out == nullptr || t->nfiles == 0) { errno = EINVAL; return -1; }
-	DevGuard dg(t->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	TTRY(hipEventSynchronize(t->ev[3]));
-	TTRY(hipMemcpy(out, t->d_file_lines, (t->nfiles + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-	return 0;
-fail:
-	return -1;
+	return copy_out(t->device, t->ev[3], {{out, t->d_file_lines, (t->nfiles + 1u) * sizeof(uint64_t)}});
 }
 
 extern "C" double fsm_hip_text_files_ms(const struct fsm_hip_text *t)
 {
-	float a = 0.f, b = 0.f;
 	if (t == nullptr || t->nfiles == 0) { errno = EINVAL; return -1.0; }
-	DevGuard dg(t->device);
-	if (!dg.ok()) { errno = ENODEV; return -1.0; }
-	TTRY(hipEventSynchronize(t->ev[3]));
-	TTRY(hipEventElapsedTime(&a, t->fev[0], t->fev[1]));
-	TTRY(hipEventElapsedTime(&b, t->fev[2], t->ev[3]));
-	return (double)a + (double)b;
-fail:
-	return -1.0;
+	return elapsed_ms(t->device, t->ev[3], {{t->fev[0], t->fev[1]}, {t->fev[2], t->ev[3]}});
 }
 
 extern "C" size_t fsm_hip_text_files_block(void) { return (size_t)FILES_THREADS * FILES_SCAN_THREADS; }
