@@ -932,17 +932,23 @@ class HipNode:
             raise _oserr("fsm_hip_node_exec_batch_lengths")
         return end, bm
 
+    def exec_batch_offsets(self, base: np.ndarray, off: np.ndarray, want_bitmap: bool = True, want_end: bool = True):
+        """fsm_hip_node_exec_batch_offsets: u64 offsets, sharded over the devices."""
+        base = np.ascontiguousarray(base, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = len(off) - 1
+        end = np.empty(n, dtype=np.uint32) if want_end else None
+        bm = np.zeros((n + 63) // 64, dtype=np.uint64) if want_bitmap else None
+        C.set_errno(0)
+        if self._lib.fsm_hip_node_exec_batch_offsets(C.c_void_p(self._h), C.c_void_p(base.ctypes.data if len(base) else None), C.c_void_p(off.ctypes.data),
+                                                     C.c_size_t(n), C.c_void_p(end.ctypes.data if want_end else None), C.c_void_p(bm.ctypes.data if want_bitmap else None)) != 0:
+            raise _oserr("fsm_hip_node_exec_batch_offsets")
+        return end, bm
+
     def exec_strings(self, strings: Sequence[bytes]):
         off = np.zeros(len(strings) + 1, dtype=np.uint64)
         off[1:] = np.cumsum([len(s) for s in strings])
-        base = np.frombuffer(b"".join(strings) or b"\0", dtype=np.uint8)
-        n = len(strings)
-        end = np.empty(n, dtype=np.uint32)
-        bm = np.zeros((n + 63) // 64, dtype=np.uint64)
-        C.set_errno(0)
-        if self._lib.fsm_hip_node_exec_batch_offsets(C.c_void_p(self._h), _ptr(base), _ptr(off), C.c_size_t(n), _ptr(end), _ptr(bm)) != 0:
-            raise _oserr("fsm_hip_node_exec_batch_offsets")
-        return end, bm
+        return self.exec_batch_offsets(np.frombuffer(b"".join(strings) or b"\0", dtype=np.uint8), off)
 
     def exec_batch_device(self, d_base: Sequence[int], stride: int, n: int, d_end: Optional[Sequence[int]] = None,
                           d_bitmap_all: Optional[Sequence[int]] = None, want_count: bool = False):
@@ -1008,9 +1014,29 @@ def _node_exec_batch_ids(self, data: np.ndarray, mode: int, lens: Optional[np.nd
     return out
 
 
+def _node_exec_batch_eager(self, data: np.ndarray, lens: Optional[np.ndarray] = None, want_end: bool = True, eager_out: Optional[np.ndarray] = None):
+    """fsm_hip_node_exec_batch_eager: (end u32[n] or None, the raw sets u64[n, W]); decode with replica(0).decode_eager.
+    eager_out: the caller's own n * W words to write into (returned reshaped) instead of fresh zeros."""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    n, stride = data.shape
+    W = self.replica(0).eager_words()
+    end = np.empty(n, dtype=np.uint32) if want_end else None
+    if eager_out is None:
+        eager_out = np.zeros((n, W), dtype=np.uint64)
+    if eager_out.dtype != np.uint64 or eager_out.size != n * W or not eager_out.flags.c_contiguous:
+        raise ValueError("eager_out: n * W contiguous u64 words")
+    if lens is not None:
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    C.set_errno(0)
+    if self._lib.fsm_hip_node_exec_batch_eager(C.c_void_p(self._h), _ptr(data), C.c_size_t(stride), _ptr(lens), C.c_size_t(n), _ptr(end), _ptr(eager_out)) != 0:
+        raise _oserr("fsm_hip_node_exec_batch_eager")
+    return end, eager_out.reshape(n, W)
+
+
 HipNode.exec_device = _node_exec_device
 HipNode.wait = _node_wait
 HipNode.exec_batch_ids = _node_exec_batch_ids
+HipNode.exec_batch_eager = _node_exec_batch_eager
 
 
 class MultiBatch(C.Structure):

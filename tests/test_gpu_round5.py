@@ -123,6 +123,8 @@ def test_hipnode_every_public_method(hip):
     bits = lambda b: np.unpackbits(b.view(np.uint8), bitorder="little")[:n].astype(bool)
     end, bm = node.exec_strings(strs)
     assert np.array_equal(end, wantl) and np.array_equal(bits(bm), wantl != NO)
+    end, bm = node.exec_batch_offsets(base, off)
+    assert np.array_equal(end, wantl) and np.array_equal(bits(bm), wantl != NO)
     end, bm = node.exec_batch_offsets32(base, off.astype(np.uint32))
     assert np.array_equal(end, wantl) and np.array_equal(bits(bm), wantl != NO)
     end, bm = node.exec_batch_lengths(base, lens)
@@ -153,7 +155,9 @@ def test_hipnode_every_public_method(hip):
     node.exec_device(n, [b.data_ptr() for b in bufs], stride=L, d_end=[e.data_ptr() for e in ends], d_bitmap_all=[m.data_ptr() for m in bms], want_count=True, async_=True)
     assert node.wait(want_count=True) == cnt
     public = [m for m in dir(node) if not m.startswith("_") and callable(getattr(node, m))]
-    covered = {"close", "uses_rccl", "rccl_path", "replica", "shard", "bitmap_words", "exec_batch", "exec_batch_offsets32", "exec_batch_lengths", "exec_strings",
+    _, words = node.exec_batch_eager(rows)                  # c1 emits nothing: every set is empty
+    assert words.shape == (n, 1) and not words.any()
+    covered = {"close", "uses_rccl", "rccl_path", "replica", "shard", "bitmap_words", "exec_batch", "exec_batch_offsets", "exec_batch_offsets32", "exec_batch_lengths", "exec_strings",
                "exec_batch_device", "exec_device", "wait", "exec_batch_ids", "exec_batch_eager", "exec_multi"}
     assert set(public) <= covered, sorted(set(public) - covered)
     node.close()
