@@ -1179,6 +1179,29 @@ def exec_multi_eager_device(dfas: Sequence["HipDfa"], jobs: Sequence[tuple], ids
         raise _oserr("fsm_hip_exec_multi_eager_device")
 
 
+def exec_multi_ptrs(dfas: Sequence[Optional["HipDfa"]], jobs: Sequence[tuple], ids_mode: int = 0, device: bool = False, stream: int = 0) -> None:
+    """A many-DFA submission given as addresses, host memory (device=False) or device memory: jobs[q] = (base, off, n, end,
+    bitmap) -> fsm_hip_exec_multi[_device], with a sixth (ids) -> fsm_hip_exec_multi_ids[_device], with a seventh (eager) ->
+    fsm_hip_exec_multi_eager[_device]; every job of a submission has the same length.  0 = NULL: an output left out; dfas[q]
+    None: a NULL handle.  The caller keeps the memory alive and reads the outputs where it put them."""
+    lib = load_library()
+    k = len(jobs)
+    width = len(jobs[0]) if k else 5
+    if width not in (5, 6, 7) or any(len(j) != width for j in jobs):
+        raise ValueError("every job is a 5-tuple, a 6-tuple or a 7-tuple")
+    arr = ({5: MultiBatch, 6: MultiBatchIds, 7: MultiBatchEager}[width] * max(k, 1))()
+    names = ("base", "off", "n", "end_out", "accept_bitmap", "id_out", "eager_out")
+    for q, j in enumerate(jobs):
+        for name, v in zip(names, j):
+            setattr(arr[q], name, v if name == "n" else (v or None))
+    hs = (C.c_void_p * max(k, 1))(*[d._h if d is not None else None for d in dfas])
+    fn = "fsm_hip_exec_multi" + {5: "", 6: "_ids", 7: "_eager"}[width] + ("_device" if device else "")
+    args = [hs, arr, C.c_size_t(k)] + ([C.c_int(ids_mode)] if width != 5 else []) + ([C.c_void_p(stream or None)] if device else [])
+    C.set_errno(0)
+    if getattr(lib, fn)(*args) != 0:
+        raise _oserr(fn)
+
+
 class MultiPrepared:
     """fsm_hip_multi_prepare / _launch / _prepared_free: a device-pointer submission put on the device once; launch() is
     one kernel launch on the stream (capturable into a HIP graph).  jobs[q] = (d_base, d_off, n, d_end, d_bitmap, d_ids), or
