@@ -551,6 +551,39 @@ class HipDfa:
         sets = [ids[row] for row in bits]
         return end, sets
 
+    def exec_eager_words(self, data: np.ndarray, lens: Optional[np.ndarray] = None, off: Optional[np.ndarray] = None, want_end: bool = True,
+                         eager_out: Optional[np.ndarray] = None, null_sets: bool = False):
+        """fsm_hip_exec_batch_eager (data: [n][stride] rows, + lens) or, with off (n + 1 u64 offsets), fsm_hip_exec_batch_eager_offsets
+        (data: the packed bytes), with the sets as the library writes them: returns (end or None, u64 [n][eager_words()]).
+        eager_out: the caller's own array, written in place; null_sets: NULL is passed for the sets (the fronts refuse it)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if off is not None:
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+            n = len(off) - 1
+        else:
+            n, stride = data.shape
+        end = np.empty(n, dtype=np.uint32) if want_end else None
+        eo = None if null_sets else eager_out if eager_out is not None else np.zeros((n, self.eager_words()), dtype=np.uint64)
+        if lens is not None:
+            lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        C.set_errno(0)
+        vp = C.c_void_p
+        if off is not None:
+            r = self._lib.fsm_hip_exec_batch_eager_offsets(vp(self._h), vp(data.ctypes.data if data.size else None), _ptr(off), C.c_size_t(n), _ptr(end), _ptr(eo))
+        else:
+            r = self._lib.fsm_hip_exec_batch_eager(vp(self._h), vp(data.ctypes.data if data.size else None), C.c_size_t(stride), _ptr(lens), C.c_size_t(n), _ptr(end), _ptr(eo))
+        if r != 0:
+            raise _oserr("fsm_hip_exec_batch_eager" + ("_offsets" if off is not None else ""))
+        return end, eo
+
+    def exec_batch_eager_offsets_device(self, d_base: int, d_off: int, n: int, d_end: int, d_sets: int, stream: int = 0):
+        """fsm_hip_exec_batch_eager_offsets_device; d_sets: n * eager_words() u64 on the device"""
+        C.set_errno(0)
+        vp = C.c_void_p
+        if self._lib.fsm_hip_exec_batch_eager_offsets_device(vp(self._h), vp(d_base or None), vp(d_off or None), C.c_size_t(n), vp(d_end or None), vp(d_sets or None),
+                                                             vp(stream or None)) != 0:
+            raise _oserr("fsm_hip_exec_batch_eager_offsets_device")
+
     def exec_batch_eager_trace(self, data: np.ndarray, lens: Optional[np.ndarray] = None, off: Optional[np.ndarray] = None, cap: int = 64):
         """fsm_exec's eager-output callback stream per input, order and repeats kept: (end u32[n], count u32[n],
         [(ids, positions) of the first min(count, cap) emissions]).  data: (n, stride) rows (+ lens), or a flat byte
@@ -635,8 +668,8 @@ class HipDfa:
         bits = np.unpackbits(eo.view(np.uint8).reshape(len(eo), W * 8), axis=1, bitorder="little")[:, :k].astype(bool)
         return [ids[row] for row in bits]
 
-    def exec_batch_eager_resume(self, data: np.ndarray, state_io: np.ndarray, eager_io: np.ndarray, lens: Optional[np.ndarray] = None,
-                                off: Optional[np.ndarray] = None):
+    def exec_batch_eager_resume(self, data: np.ndarray, state_io: np.ndarray, eager_io: Optional[np.ndarray], lens: Optional[np.ndarray] = None,
+                                off: Optional[np.ndarray] = None, want_end: bool = True):
         """fsm_hip_exec_batch_eager_resume: one more piece of every input.  data: [n][stride] rows (+ lens), or with off (n + 1
         u64 offsets) the packed bytes.  eager_io: n * eager_words() u64 (zeroed before a stream's first piece), OR-ed into.
         Returns (state_out, end, eager_io) -- new arrays; the arguments are left as they are."""
@@ -646,11 +679,11 @@ class HipDfa:
             n, stride = len(off) - 1, 0
         else:
             n, stride = data.shape
-        st = np.ascontiguousarray(state_io, dtype=np.uint32).copy()
-        eo = np.ascontiguousarray(eager_io, dtype=np.uint64).copy()
-        if eo.size != n * self.eager_words():
+        st = np.ascontiguousarray(state_io, dtype=np.uint32).copy() if state_io is not None else None
+        eo = np.ascontiguousarray(eager_io, dtype=np.uint64).copy() if eager_io is not None else None   # (None: NULL, which the front refuses)
+        if eo is not None and eo.size != n * self.eager_words():
             raise ValueError("eager_io needs n * eager_words() words")
-        end = np.empty(n, dtype=np.uint32)
+        end = np.empty(n, dtype=np.uint32) if want_end else None
         if lens is not None:
             lens = np.ascontiguousarray(lens, dtype=np.uint32)
         C.set_errno(0)

@@ -854,7 +854,8 @@ static int launch_walk(const fsm_hip_dfa *d, WalkArgs a, bool fast_ok, hipStream
 	const uint64_t cap = (uint64_t)d->ncu * c.blocks_per_cu;
 	if (nblocks > cap) nblocks = cap;
 	/* bit 0 wave retire, bit 1 per-lane load skip: the knob decides, else the dfa's own default -- without bit 1 for the eager and
-	 * the resumed walks, which report more than an end state and have no test of their id sets / carried states with it on */
+	 * the resumed walks, which report more than an end state: tests/test_gpu_eager_front.py judges their id sets / carried states on
+	 * every layout and input path (bit 1 off, as here); nothing has run it with bit 1 on yet */
 	if (d->knob_early >= 0) a.early = (uint32_t)d->knob_early;
 	else if (eager != 0 || a.state_io != nullptr) a.early &= ~2u;
 	if (d->knob_noskip > 0) a.early |= 4u;

@@ -31,12 +31,12 @@ def class_map(K):
     return cls, bounds
 
 
-def eager_ids_of_states(S, E):
-    """[S][2] index (0 .. E - 1) of the eager outputs of every state, -1 = none: every 11th state emits one or two.
-    The id of index k is 5 + 3 * k: ids are not bit numbers."""
+def eager_ids_of_states(S, E, every=11):
+    """[S][2] index (0 .. E - 1) of the eager outputs of every state, -1 = none: every `every`-th state (every 11th unless
+    asked otherwise) emits one or two.  The id of index k is 5 + 3 * k: ids are not bit numbers."""
     s = np.arange(S, dtype=np.int64)
-    q = s // 11
-    has = s % 11 == 0
+    q = s // every
+    has = s % every == 0
     k1 = np.where(has, q % E, -1)
     k2 = np.where(has & (q % 2 == 1), (q * 7 + 3) % E, -1)
     k2[k2 == k1] = -1
@@ -54,7 +54,7 @@ def endid_slots(S, is_end):
     return ids
 
 
-def affine(S, K, *, holes=0, sinks=0, endids=False, eager=0):
+def affine(S, K, *, holes=0, sinks=0, endids=False, eager=0, every=11):
     """-> (FlatDfa, dense[S][K] int64 with -1 = no edge, cls[256]).  Start state 0."""
     cls, bounds = class_map(K)
     mult = [a for a in range(3, 200, 2) if gcd(a, S) == 1][:8]
@@ -83,7 +83,7 @@ def affine(S, K, *, holes=0, sinks=0, endids=False, eager=0):
         ids = slots[slots >= 0].astype(np.uint32)
     eo = ei = None
     if eager:
-        ek = eager_ids_of_states(S, eager)
+        ek = eager_ids_of_states(S, eager, every)
         eo = np.zeros(S + 1, np.uint32)
         eo[1:] = np.cumsum((ek >= 0).sum(axis=1))
         lo, hi = np.minimum(ek[:, 0], ek[:, 1]), np.maximum(ek[:, 0], ek[:, 1])      # ascending within a state
@@ -149,12 +149,12 @@ def carried(states):
     return np.where(st < 0, LIB_DEAD, st).astype(np.uint32)
 
 
-def walk_eager(dense, cls, start, rows, E, lens=None, state_in=None):
+def walk_eager(dense, cls, start, rows, E, lens=None, state_in=None, every=11):
     """-> (end states as walk(), emitted[n][E] bool by id INDEX): the outputs of the start state (a walk from the start
     only: a resumed piece emits nothing for the state it is handed) and of every state entered; DEAD emits nothing."""
     tr = trace(dense, cls, start, rows, lens, state_in)
     n, L1 = tr.shape
-    ek = np.vstack([eager_ids_of_states(dense.shape[0], E), [[-1, -1]]])
+    ek = np.vstack([eager_ids_of_states(dense.shape[0], E, every), [[-1, -1]]])
     lens = np.full(n, L1 - 1, np.int64) if lens is None else np.asarray(lens, np.int64)
     emitted = np.zeros((n, E + 1), bool)                           # column E takes the "none" writes
     ar = np.arange(n)
