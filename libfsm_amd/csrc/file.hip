@@ -38,6 +38,7 @@
 
 #include "../../include/fsm_hip.h"
 #include "dfa_access.h"
+#include "hip_host.h"
 
 using namespace fsmhip;
 
@@ -71,71 +72,52 @@ __global__ void __launch_bounds__(256) walk_or_rows(const uint64_t *rows, uint32
 	}
 }
 
-int herr(hipError_t e)
-{
-	switch (e) {
-	case hipSuccess: return 0;
-	case hipErrorOutOfMemory: return ENOMEM;
-	case hipErrorNoDevice:
-	case hipErrorInvalidDevice: return ENODEV;
-	default: return EIO;
-	}
-}
-#define FTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { errno = herr(e_); return -1; } } while (0)
+/* a failing HIP call inside the file engine is EIO, never EINVAL: EINVAL here means the caller's arguments */
+bool file_ok(hipError_t e, const char *what) { const bool ok = hip_ok(e, what); if (!ok && errno == EINVAL) errno = EIO; return ok; }
+#define FILE_OK(expr) file_ok((expr), #expr)
 
 struct Engine {
-	const fsm_hip_dfa *d = nullptr;
-	int dev = 0, prev = -1;
-	hipStream_t s = nullptr;
-	unsigned char *pin[2] = {nullptr, nullptr}, *dbuf[2] = {nullptr, nullptr};
-	uint32_t *d_st = nullptr, *h_in = nullptr, *h_out = nullptr;   /* states: device array, pinned host copies */
+	const fsm_hip_dfa *d;
+	DevGuard dg;                                    /* first: the caller's device comes back after everything below has gone */
+	PinBuf<unsigned char> pin[2];
+	DevBuf<unsigned char> dbuf[2];
+	DevBuf<uint32_t> d_st;                          /* states: device array, pinned host copies */
+	PinBuf<uint32_t> h_in, h_out;
 	unsigned passes = 0, windows = 0;
 	size_t W = 0;                                   /* eager: words per set (0: the plain walk) */
-	uint64_t *d_sets = nullptr, *d_acc = nullptr;   /* eager: one set per piece of a window; the set of the windows walked so far */
+	DevBuf<uint64_t> d_sets, d_acc;                 /* eager: one set per piece of a window; the set of the windows walked so far */
 	uint32_t guess = FSM_HIP_STATE_START;           /* where pieces i >= 1 start on the first pass */
+	DevStream s;                                    /* last: it goes first, once ~Engine has waited for it */
 
-	int open(const fsm_hip_dfa *dfa, size_t eager_words)
+	explicit Engine(const fsm_hip_dfa *dfa) : d(dfa), dg(dfa_device(dfa)) {}
+	int open(size_t eager_words)
 	{
-		d = dfa;
-		dev = dfa_device(dfa);
-		(void)hipGetDevice(&prev);
-		if (prev != dev) FTRY(hipSetDevice(dev));
-		FTRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+		if (!dg.ok()) { errno = ENODEV; return -1; }
+		if (!FILE_OK(s.create(hipStreamNonBlocking))) return -1;
 		for (int k = 0; k < 2; k++) {
-			FTRY(hipHostMalloc((void **)&pin[k], WINDOW, hipHostMallocDefault));
-			FTRY(hipMalloc((void **)&dbuf[k], WINDOW));
+			if (!FILE_OK(pin[k].alloc(WINDOW))) return -1;
+			if (!FILE_OK(dbuf[k].alloc(WINDOW))) return -1;
 		}
 		const size_t n = WINDOW / CHUNK;
-		FTRY(hipMalloc((void **)&d_st, n * 4u));
-		FTRY(hipHostMalloc((void **)&h_in, n * 4u, hipHostMallocDefault));
-		FTRY(hipHostMalloc((void **)&h_out, n * 4u, hipHostMallocDefault));
+		if (!FILE_OK(d_st.alloc(n))) return -1;
+		if (!FILE_OK(h_in.alloc(n))) return -1;
+		if (!FILE_OK(h_out.alloc(n))) return -1;
 		W = eager_words;
 		if (W != 0) {
-			FTRY(hipMalloc((void **)&d_sets, n * W * sizeof(uint64_t)));
-			FTRY(hipMalloc((void **)&d_acc, W * sizeof(uint64_t)));
-			FTRY(hipMemsetAsync(d_acc, 0, W * sizeof(uint64_t), s));
-			const Plan *p = dfa_plan(dfa);
+			if (!FILE_OK(d_sets.alloc(n * W))) return -1;
+			if (!FILE_OK(d_acc.alloc(W))) return -1;
+			if (!FILE_OK(hipMemsetAsync(d_acc, 0, W * sizeof(uint64_t), s))) return -1;
+			const Plan *p = dfa_plan(d);
 			guess = p->new2old[p->start];   /* the start state by its caller's id: a guess must not fire its outputs */
 		}
 		return 0;
 	}
-	~Engine()
-	{
-		const int e = errno;
-		if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-		for (int k = 0; k < 2; k++) { if (pin[k]) (void)hipHostFree(pin[k]); if (dbuf[k]) (void)hipFree(dbuf[k]); }
-		if (d_st) (void)hipFree(d_st);
-		if (h_in) (void)hipHostFree(h_in);
-		if (h_out) (void)hipHostFree(h_out);
-		if (d_sets) (void)hipFree(d_sets);
-		if (d_acc) (void)hipFree(d_acc);
-		if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-		errno = e;
-	}
+	/* nothing goes while the stream still works */
+	~Engine() { if (s) { const int e = errno; (void)hipStreamSynchronize(s); errno = e; } }
 	/* the window's bytes on their way to the device (returns at once) */
 	int upload(int k, size_t bytes)
 	{
-		FTRY(hipMemcpyAsync(dbuf[k], pin[k], bytes, hipMemcpyHostToDevice, s));
+		if (!FILE_OK(hipMemcpyAsync(dbuf[k], pin[k], bytes, hipMemcpyHostToDevice, s))) return -1;
 		return 0;
 	}
 	/* n whole pieces of window k, from `carry`: the state after them */
@@ -146,14 +128,14 @@ struct Engine {
 		for (size_t i = 1; i < n; i++) h_in[i] = guess;
 		for (;;) {
 			passes++;
-			FTRY(hipMemcpyAsync(d_st, h_in, n * 4u, hipMemcpyHostToDevice, s));
+			if (!FILE_OK(hipMemcpyAsync(d_st, h_in, n * 4u, hipMemcpyHostToDevice, s))) return -1;
 			if (W != 0) {
 				/* every piece is walked again: its set from this pass's in-state only */
-				FTRY(hipMemsetAsync(d_sets, 0, n * W * sizeof(uint64_t), s));
+				if (!FILE_OK(hipMemsetAsync(d_sets, 0, n * W * sizeof(uint64_t), s))) return -1;
 				if (fsm_hip_exec_batch_eager_resume_device(d, dbuf[k], CHUNK, nullptr, nullptr, n, d_st, nullptr, d_sets, s) != 0) return -1;
 			} else if (fsm_hip_exec_batch_resume_device(d, dbuf[k], CHUNK, nullptr, n, d_st, nullptr, nullptr, s) != 0) return -1;
-			FTRY(hipMemcpyAsync(h_out, d_st, n * 4u, hipMemcpyDeviceToHost, s));
-			FTRY(hipStreamSynchronize(s));
+			if (!FILE_OK(hipMemcpyAsync(h_out, d_st, n * 4u, hipMemcpyDeviceToHost, s))) return -1;
+			if (!FILE_OK(hipStreamSynchronize(s))) return -1;
 			bool same = true;
 			for (size_t i = 1; i < n; i++) {
 				if (h_in[i] != h_out[i - 1]) { h_in[i] = h_out[i - 1]; same = false; }
@@ -163,16 +145,16 @@ struct Engine {
 		*out_state = h_out[n - 1];
 		if (W != 0) {
 			/* the fixed point: every piece's set is from its true in-state */
-			hipLaunchKernelGGL(walk_or_rows, dim3((unsigned)W), dim3(256), 0, s, (const uint64_t *)d_sets, (uint32_t)n, (uint32_t)W, d_acc);
-			FTRY(hipGetLastError());
+			hipLaunchKernelGGL(walk_or_rows, dim3((unsigned)W), dim3(256), 0, s, (const uint64_t *)d_sets.p, (uint32_t)n, (uint32_t)W, d_acc.p);
+			if (!FILE_OK(hipGetLastError())) return -1;
 		}
 		return 0;
 	}
 	/* eager: the accumulated set into host memory */
 	int sets_out(uint64_t *h)
 	{
-		FTRY(hipMemcpyAsync(h, d_acc, W * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-		FTRY(hipStreamSynchronize(s));
+		if (!FILE_OK(hipMemcpyAsync(h, d_acc, W * sizeof(uint64_t), hipMemcpyDeviceToHost, s))) return -1;
+		if (!FILE_OK(hipStreamSynchronize(s))) return -1;
 		return 0;
 	}
 };
@@ -214,8 +196,8 @@ int match_stream(const fsm_hip_dfa *dfa, Read read, uint32_t *end_out, unsigned 
 		*end_out = end;
 		return 0;
 	}
-	Engine en;
-	if (en.open(dfa, W) != 0) return -1;
+	Engine en(dfa);
+	if (en.open(W) != 0) return -1;
 	memcpy(en.pin[0], head.data(), SMALL);
 	size_t have = SMALL;       /* bytes in the window being filled */
 	int k = 0;

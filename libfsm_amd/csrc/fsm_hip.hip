@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <utility>
@@ -27,6 +28,7 @@
 #include "walk_aux.h"
 #include "walk_lazy.h"   /* FSMHIP_LAZY_PIECE (the kernels themselves are instantiated in kern_glob.hip) */
 #include "trace_kernel.h"
+#include "hip_host.h"
 
 using namespace fsmhip;
 
@@ -37,54 +39,54 @@ struct fsm_hip_dfa {
 	int device = 0;
 	int ncu = 256;
 	uint32_t lds_limit = 160u * 1024u;
-	void *d_tab = nullptr;
-	uint32_t *d_fin = nullptr;
-	uint32_t *d_btab = nullptr;
-	uint32_t *d_lazy = nullptr;                      /* sparse layout: the lazy image (plan.cpp build_lazy), if the automaton has one */
-	uint32_t *d_lazy_ctr = nullptr;                  /* ... and a ring of tile counters: a launch zeroes and uses the next one (launches on
+	DevBuf<unsigned char> d_tab;                     /* (its element type differs per layout: owned as bytes) */
+	DevBuf<uint32_t> d_fin;
+	DevBuf<uint32_t> d_btab;
+	DevBuf<uint32_t> d_lazy;                         /* sparse layout: the lazy image (plan.cpp build_lazy), if the automaton has one */
+	DevBuf<uint32_t> d_lazy_ctr;                     /* ... and a ring of tile counters: a launch zeroes and uses the next one (launches on
 	                                                  * several streams may be in flight; LAZY_CTRS of them never are) */
 	unsigned lazy_ctr_next = 0;
 	int knob_lazy_lines = 1;                         /* the lazy walk also serves the variable-length fronts and resumed walks (0: walk_ragged / walk_generic over the records, for A/B runs) */
 	int knob_lazy_dyn = 1;                           /* the lazy walk's wavefronts claim their tiles from a counter (0: static striding) */
 	/* device end-id delivery (built on first use) */
 	std::vector<uint32_t> fin_host;                 /* copy of the fin table uploaded to d_fin */
-	uint32_t *d_fin_earliest = nullptr, *d_fin_ret = nullptr;
+	DevBuf<uint32_t> d_fin_earliest, d_fin_ret;
 	std::vector<uint32_t> ret_off, ret_ids;          /* de-duplicated id sets, CSR */
 	bool ids_ready = false;
 	uint32_t ids_conflict = FSM_HIP_NO_MATCH;        /* lowest end state carrying more than one id */
 	/* resume tables (built on first use) */
-	uint32_t *d_enc_of = nullptr, *d_orig_of = nullptr;
+	DevBuf<uint32_t> d_enc_of, d_orig_of;
 	std::vector<uint32_t> enc_host;                  /* [S1] encoded state per renumbered state */
 	bool resume_ready = false;
-	uint64_t *d_emask = nullptr;                     /* eager-output masks, indexed like fin */
-	uint32_t *d_ew_off = nullptr, *d_ew_word = nullptr; /* wide eager sets (> 64 ids) */
-	uint64_t *d_ew_mask = nullptr;
+	DevBuf<uint64_t> d_emask;                        /* eager-output masks, indexed like fin */
+	DevBuf<uint32_t> d_ew_off, d_ew_word;            /* wide eager sets (> 64 ids) */
+	DevBuf<uint64_t> d_ew_mask;
 	/* the eager-output stream (trace_kernel.h; built on first use): plain renumbered table, byte classes, id lists (CSR), fin */
-	uint32_t *d_tr_dense = nullptr, *d_tr_cls4 = nullptr, *d_tr_eoff = nullptr, *d_tr_eids = nullptr, *d_tr_fin = nullptr;
+	DevBuf<uint32_t> d_tr_dense, d_tr_cls4, d_tr_eoff, d_tr_eids, d_tr_fin;
 	bool trace_ready = false;
 	/* device-side choice between walk_generic and walk_ragged: a ring of flags, one per launch (launches on several streams
 	 * may be in flight; PICK_FLAGS of them never are), allocated with the dfa */
-	uint32_t *d_pick = nullptr;
+	DevBuf<uint32_t> d_pick;
 	unsigned pick_next = 0;
 	/* the lengths-only front: tile bases (u64 per 64 inputs) + block totals: one grow-only block per dfa.  Calls are enqueued
 	 * under the dfa's lock; every call waits for the block's last user's event, so the block is never shared by two
 	 * launches in flight (waiting on one's own stream costs nothing) */
-	unsigned char *tb_scratch = nullptr;
+	DevBuf<unsigned char> tb_scratch;
 	size_t tb_scratch_bytes = 0;
-	hipEvent_t tb_scratch_ev = nullptr;
+	DevEvent tb_scratch_ev;
 	bool tb_scratch_busy = false;
-	std::vector<void *> tb_scratch_old;              /* outgrown blocks: freed with the dfa */
-	unsigned char *arena = nullptr;                  /* device scratch of the host-pointer front */
+	std::vector<DevBuf<unsigned char>> tb_scratch_old;   /* outgrown blocks: they go with the dfa */
+	DevBuf<unsigned char> arena;                     /* device scratch of the host-pointer front */
 	size_t arena_bytes = 0;
-	unsigned char *stage = nullptr;                  /* pinned host staging for small calls */
-	hipStream_t hs = nullptr;                        /* private stream of the host-pointer fronts */
+	PinBuf<unsigned char> stage;                     /* pinned host staging for small calls */
+	DevStream hs;                                    /* private stream of the host-pointer fronts */
 	/* guards everything an exec call mutates: arena / stage, the timing events, the lazily built
 	 * end-id and resume tables.  Host-pointer fronts hold it for the whole call (they share the
 	 * arena), device-pointer fronts only while they enqueue. */
 	std::recursive_mutex mu;
 	WalkArgs proto;
 	uint32_t table_lds = 0;      /* LDS bytes of the policy's tables */
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	DevEvent ev0, ev1;
 	bool timed = false;
 	std::string last_kernel;     /* demangled name of the walk kernel of the last launch */
 	std::string last_kernel_pick[3];   /* a device-side pick launched several (indexed by PICK_*): which one RAN is read from the flag on demand */
@@ -114,7 +116,8 @@ struct fsm_hip_dfa {
 	std::atomic<const fsm_hip_dfa *> last_used{nullptr};   /* which of the two the last launch went to (timing / kernel name); written by concurrent callers */
 	std::atomic<bool> uploaded{false};   /* the layout's tables are on the device (FSM_HIP_DEFER_UPLOAD: not before the first single-dfa call);
 	                                      * release-stored under mu once everything is in place, acquire-loaded without it */
-	int upload_errno = 0;        /* a failed upload is not retried over its partial allocations (fsm_hip_dfa_free releases them): every later call fails with this */
+	int upload_errno = 0;        /* a failed upload is not retried: every later call fails with this */
+	~fsm_hip_dfa() { fsm_hip_dfa_free(alt); }
 };
 
 /* GLOBAL layout: how much of the table head (rows nearest the start state) every workgroup
@@ -140,37 +143,6 @@ static void set_hot_bytes(fsm_hip_dfa *d, uint32_t want)
 
 static const unsigned LAZY_CTRS = 64, PICK_FLAGS = 64;
 
-static int hip_errno(hipError_t e)
-{
-	switch (e) {
-	case hipSuccess: return 0;
-	case hipErrorOutOfMemory: return ENOMEM;
-	case hipErrorNoDevice:
-	case hipErrorInvalidDevice:
-	case hipErrorInsufficientDriver: return ENODEV;
-	case hipErrorInvalidValue: return EINVAL;
-	default: return EIO;
-	}
-}
-
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
-	if (getenv("FSM_HIP_DEBUG")) fprintf(stderr, "fsm_hip: %s -> %s\n", #expr, hipGetErrorString(e_)); \
-	errno = hip_errno(e_); goto fail; } } while (0)
-
-/* make the dfa's device current for the duration of a call and give the caller's device back */
-struct DevGuard {
-	int prev = -1;
-	bool good = true;
-	explicit DevGuard(int dev)
-	{
-		if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-		if (prev != dev && hipSetDevice(dev) != hipSuccess) good = false;
-		if (prev == dev) prev = -1;
-	}
-	~DevGuard() { if (prev >= 0 && good) { int e = errno; (void)hipSetDevice(prev); errno = e; } }
-	bool ok() const { return good; }
-};
-
 typedef std::lock_guard<std::recursive_mutex> DfaLock;
 
 /* the automaton image a batch goes to: the second one (fsm_hip_dfa::alt) for everything the fixed-stride kernels do not take */
@@ -194,23 +166,18 @@ int dfa_ncu(const fsm_hip_dfa *d) { return d->ncu; }
 /* create / free / info                                               */
 /* ------------------------------------------------------------------ */
 
+/* the layout's table: its element type differs per layout */
 template <class T>
-static hipError_t upload(T **dst, const std::vector<T> &src)
+static hipError_t upload_tab(fsm_hip_dfa *d, const std::vector<T> &src)
 {
-	*dst = nullptr;
-	size_t bytes = src.size() * sizeof(T);
-	if (bytes == 0) bytes = sizeof(T);
-	hipError_t e = hipMalloc((void **)dst, (bytes + 15) & ~(size_t)15);
-	if (e != hipSuccess) return e;
-	if (!src.empty()) e = hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
-	return e;
+	return d->d_tab.upload_bytes(src.data(), src.size() * sizeof(T), sizeof(T));
 }
 
 /* the layout's device image + the per-dfa launch resources (events, private stream).  fsm_hip_dfa_create does this at once
  * unless FSM_HIP_DEFER_UPLOAD asks to wait for the first call that needs it: a dfa that is only ever used through
  * fsm_hip_exec_multi (retest: a new DFA per record, a few lines each) never needs it -- its plain table rides in that call's
  * one host-to-device copy */
-static int dfa_upload(fsm_hip_dfa *d)
+static int dfa_upload_all(fsm_hip_dfa *d)
 {
 	const unsigned flags = d->flags;
 	{
@@ -221,10 +188,8 @@ static int dfa_upload(fsm_hip_dfa *d)
 		switch (p.layout) {
 		case FSM_HIP_LAYOUT_TINY: {
 			if (!p.tiny5_col.empty()) {   /* <= 6 states: Tiny5Pol, state code = 5 * state */
-				uint32_t *t = nullptr;
-				HIP_TRY(upload(&t, p.tiny5_col));
-				d->d_tab = t;
-				HIP_TRY(upload(&d->d_fin, p.fin));
+				if (!HIP_OK(upload_tab(d, p.tiny5_col))) return -1;
+				if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
 				a.tab_bytes = 256 * 4;
 				a.start = p.start * 5u;
 				a.abs_min = p.abs_min * 5u;
@@ -232,10 +197,8 @@ static int dfa_upload(fsm_hip_dfa *d)
 				d->table_lds = Tiny5Pol::lds_bytes(0);
 				break;
 			}
-			uint64_t *t = nullptr;
-			HIP_TRY(upload(&t, p.tiny_col));
-			d->d_tab = t;
-			HIP_TRY(upload(&d->d_fin, p.fin));
+			if (!HIP_OK(upload_tab(d, p.tiny_col))) return -1;
+			if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
 			a.tab_bytes = 256 * 8;
 			a.start = p.start;
 			a.abs_min = p.abs_min;
@@ -249,7 +212,6 @@ static int dfa_upload(fsm_hip_dfa *d)
 			/* image: comb64[n] = {entry, smask(next)}, dsm[32] (mask of each class's default state), rng16[n]
 			 * (self-loop byte range by row offset) -- these three parts go to LDS (tab_bytes) -- then smask[n]
 			 * by row offset (global only: seeds a walk) */
-			uint32_t *t = nullptr;
 			const size_t n = p.comb.size(), rw = (n + 1) / 2;   /* rng16[n] in u32 words */
 			std::vector<uint32_t> img(2 * n + 64 + rw + n, 0);
 			for (size_t k = 0; k < n; k++) {
@@ -263,9 +225,8 @@ static int dfa_upload(fsm_hip_dfa *d)
 			}
 			for (size_t k = 0; k < n; k++) img[2 * n + 64 + k / 2] |= (uint32_t)p.comb_rng[k] << (16 * (k & 1));
 			for (size_t k = 0; k < n; k++) img[2 * n + 64 + rw + k] = p.comb_smask[k];
-			HIP_TRY(upload(&t, img));
-			d->d_tab = t;
-			HIP_TRY(upload(&d->d_fin, p.comb_fin));
+			if (!HIP_OK(upload_tab(d, img))) return -1;
+			if (!HIP_OK(d->d_fin.upload(p.comb_fin))) return -1;
 			for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
 			a.tab_bytes = (uint32_t)((2 * n + 64 + rw) * 4);
 			a.dflt = (uint32_t)n;   /* entries: tells the kernel where dsm[] and rng16[] start */
@@ -276,10 +237,8 @@ static int dfa_upload(fsm_hip_dfa *d)
 			break;
 		}
 		case FSM_HIP_LAYOUT_COMB256: {
-			uint32_t *t = nullptr;
-			HIP_TRY(upload(&t, p.comb256));
-			d->d_tab = t;
-			HIP_TRY(upload(&d->d_fin, p.comb256_fin));
+			if (!HIP_OK(upload_tab(d, p.comb256))) return -1;
+			if (!HIP_OK(d->d_fin.upload(p.comb256_fin))) return -1;
 			a.tab_bytes = (uint32_t)(p.comb256.size() * 4);
 			a.start = p.comb256_off[p.start];
 			a.abs_min = p.comb256_abs_min_off;
@@ -289,10 +248,8 @@ static int dfa_upload(fsm_hip_dfa *d)
 			break;
 		}
 		case FSM_HIP_LAYOUT_LDS: {
-			uint16_t *t = nullptr;
-			HIP_TRY(upload(&t, p.lds_tab));
-			d->d_tab = t;
-			HIP_TRY(upload(&d->d_fin, p.fin));
+			if (!HIP_OK(upload_tab(d, p.lds_tab))) return -1;
+			if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
 			for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
 			a.tab_bytes = (uint32_t)(p.lds_tab.size() * 2);
 			a.start = p.start * p.row_bytes;
@@ -302,10 +259,8 @@ static int dfa_upload(fsm_hip_dfa *d)
 			break;
 		}
 		case FSM_HIP_LAYOUT_LDS2: {
-			uint16_t *t = nullptr;
-			HIP_TRY(upload(&t, p.lds_tab));
-			d->d_tab = t;
-			HIP_TRY(upload(&d->d_fin, p.fin));
+			if (!HIP_OK(upload_tab(d, p.lds_tab))) return -1;
+			if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
 			for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
 			const uint32_t row = p.lds2_c1 * p.lds2_c1;      /* entries per state: the walk's state is state * row */
 			a.tab_bytes = (uint32_t)(p.lds_tab.size() * 2);
@@ -317,10 +272,8 @@ static int dfa_upload(fsm_hip_dfa *d)
 			break;
 		}
 		case FSM_HIP_LAYOUT_LDSSELF: {
-			uint16_t *t = nullptr;
-			HIP_TRY(upload(&t, p.lds_tab));
-			d->d_tab = t;
-			HIP_TRY(upload(&d->d_fin, p.fin));
+			if (!HIP_OK(upload_tab(d, p.lds_tab))) return -1;
+			if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
 			for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
 			a.tab_bytes = (uint32_t)(p.lds_tab.size() * 2);
 			a.start = p.start * p.row_bytes;
@@ -330,13 +283,11 @@ static int dfa_upload(fsm_hip_dfa *d)
 			break;
 		}
 		case FSM_HIP_LAYOUT_COMB: {
-			uint32_t *t = nullptr;
 			std::vector<uint32_t> img(p.comb);               /* image = comb[n], dflt[256] */
 			img.resize(p.comb.size() + 256, 0);
 			for (uint32_t c = 0; c < p.C; c++) img[p.comb.size() + c] = p.comb_dflt[c];
-			HIP_TRY(upload(&t, img));
-			d->d_tab = t;
-			HIP_TRY(upload(&d->d_fin, p.comb_fin));
+			if (!HIP_OK(upload_tab(d, img))) return -1;
+			if (!HIP_OK(d->d_fin.upload(p.comb_fin))) return -1;
 			for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
 			a.tab_bytes = (uint32_t)(img.size() * 4);
 			a.start = p.comb_off[p.start];
@@ -348,10 +299,8 @@ static int dfa_upload(fsm_hip_dfa *d)
 		case FSM_HIP_LAYOUT_GLOBAL: {
 			if (!p.glob_tab16.empty()) {
 				/* <= 65 535 states: 2-byte entries = the next state's index (Glob16Pol) */
-				uint16_t *t16 = nullptr;
-				HIP_TRY(upload(&t16, p.glob_tab16));
-				d->d_tab = t16;
-				HIP_TRY(upload(&d->d_fin, p.glob16_fin));      /* rows in visit-frequency order (plan.cpp): fin follows */
+				if (!HIP_OK(upload_tab(d, p.glob_tab16))) return -1;
+				if (!HIP_OK(d->d_fin.upload(p.glob16_fin))) return -1;      /* rows in visit-frequency order (plan.cpp): fin follows */
 				for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
 				a.start = p.glob16_rank.empty() ? p.start : p.glob16_rank[p.start];
 				a.abs_min = p.abs_min;
@@ -363,10 +312,8 @@ static int dfa_upload(fsm_hip_dfa *d)
 				set_hot_bytes(d, 160u * 1024u);
 				break;
 			}
-			uint32_t *t = nullptr;
-			HIP_TRY(upload(&t, p.glob_tab));
-			d->d_tab = t;
-			HIP_TRY(upload(&d->d_fin, p.fin));
+			if (!HIP_OK(upload_tab(d, p.glob_tab))) return -1;
+			if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
 			for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
 			a.start = p.start * p.C * 4u;
 			a.abs_min = p.abs_min * p.C * 4u;
@@ -377,10 +324,8 @@ static int dfa_upload(fsm_hip_dfa *d)
 			break;
 		}
 		case FSM_HIP_LAYOUT_SPARSE: {
-			uint32_t *t = nullptr;
-			HIP_TRY(upload(&t, p.sparse_img));
-			d->d_tab = t;
-			HIP_TRY(upload(&d->d_fin, p.fin));
+			if (!HIP_OK(upload_tab(d, p.sparse_img))) return -1;
+			if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
 			a.tab_bytes = p.sparse_lds_bytes;
 			a.start = p.start;
 			a.abs_min = p.abs_min;
@@ -389,12 +334,12 @@ static int dfa_upload(fsm_hip_dfa *d)
 			{
 				/* SparseFastPol::enter builds a record's address from a 32-bit low half: the record array must not cross
 				 * a 4 GiB boundary (hipMalloc hands out 2 MiB-aligned blocks, the array is a few MB: practically never) */
-				const uint64_t g = reinterpret_cast<uint64_t>(t) + p.sparse_img[5], bytes = (uint64_t)p.S1 * 16u;
+				const uint64_t g = reinterpret_cast<uint64_t>(d->d_tab.p) + p.sparse_img[5], bytes = (uint64_t)p.S1 * 16u;
 				if ((g >> 32) != ((g + bytes) >> 32)) d->sparse_fast_ok = false;
 			}
 			if (p.lazy_lds_bytes != 0 && ((p.lazy_lds_bytes + 15u) & ~15u) + FSMHIP_LAZY_QBYTES <= d->lds_limit) {
-				HIP_TRY(upload(&d->d_lazy, p.lazy_img));
-				HIP_TRY(hipMalloc((void **)&d->d_lazy_ctr, LAZY_CTRS * sizeof(uint32_t)));
+				if (!HIP_OK(d->d_lazy.upload(p.lazy_img))) return -1;
+				if (!HIP_OK(d->d_lazy_ctr.alloc(LAZY_CTRS))) return -1;
 				a.lazy = d->d_lazy;
 				/* the default where it pays: few states beyond the LDS set whose own record sends hits the exact way
 				 * (img[10]) or that carry nothing (img[9]) -- on the 1e5-literal automaton 4.5 % of them, deep in the trie */
@@ -405,9 +350,9 @@ static int dfa_upload(fsm_hip_dfa *d)
 		}
 		default:
 			errno = EINVAL;
-			goto fail;
+			return -1;
 		}
-		HIP_TRY(upload(&d->d_btab, btab));
+		if (!HIP_OK(d->d_btab.upload(btab))) return -1;
 		d->enc_host.resize(p.S1);
 		for (uint32_t n2 = 0; n2 < p.S1; n2++) {
 			switch (p.layout) {
@@ -433,7 +378,7 @@ static int dfa_upload(fsm_hip_dfa *d)
 				em[d->enc_host[n2] / a.fin_div] = p.emask[n2];
 				state_of[d->enc_host[n2] / a.fin_div] = n2;
 			}
-			HIP_TRY(upload(&d->d_emask, em));
+			if (!HIP_OK(d->d_emask.upload(em))) return -1;
 			a.emask = d->d_emask;
 			switch (p.layout) {
 			case FSM_HIP_LAYOUT_COMB:
@@ -465,9 +410,9 @@ static int dfa_upload(fsm_hip_dfa *d)
 				}
 				off[F] = (uint32_t)w.size();
 				if (w.empty()) { w.push_back(0); m.push_back(0); }
-				HIP_TRY(upload(&d->d_ew_off, off));
-				HIP_TRY(upload(&d->d_ew_word, w));
-				HIP_TRY(upload(&d->d_ew_mask, m));
+				if (!HIP_OK(d->d_ew_off.upload(off))) return -1;
+				if (!HIP_OK(d->d_ew_word.upload(w))) return -1;
+				if (!HIP_OK(d->d_ew_mask.upload(m))) return -1;
 				a.ew_off = d->d_ew_off;
 				a.ew_word = d->d_ew_word;
 				a.ew_mask = d->d_ew_mask;
@@ -490,14 +435,18 @@ static int dfa_upload(fsm_hip_dfa *d)
 		 * state can be reached at all (launch_walk clears it again for the eager and the resumed walks) */
 		a.early = (flags & FSM_HIP_NO_EARLY_RETIRE) ? 0u : p.abs_reachable ? 3u : 1u;
 	}
-	HIP_TRY(hipMalloc((void **)&d->d_pick, PICK_FLAGS * sizeof(uint32_t)));
-	HIP_TRY(hipEventCreateWithFlags(&d->tb_scratch_ev, hipEventDisableTiming));
-	HIP_TRY(hipEventCreate(&d->ev0));
-	HIP_TRY(hipEventCreate(&d->ev1));
-	HIP_TRY(hipStreamCreateWithFlags(&d->hs, hipStreamNonBlocking));
+	if (!HIP_OK(d->d_pick.alloc(PICK_FLAGS))) return -1;
+	if (!HIP_OK(d->tb_scratch_ev.create(hipEventDisableTiming))) return -1;
+	if (!HIP_OK(d->ev0.create())) return -1;
+	if (!HIP_OK(d->ev1.create())) return -1;
+	if (!HIP_OK(d->hs.create(hipStreamNonBlocking))) return -1;
 	d->uploaded.store(true, std::memory_order_release);
 	return 0;
-fail:
+}
+
+static int dfa_upload(fsm_hip_dfa *d)
+{
+	if (dfa_upload_all(d) == 0) return 0;
 	d->upload_errno = errno != 0 ? errno : EIO;
 	return -1;
 }
@@ -514,6 +463,9 @@ static int ensure_uploaded(const fsm_hip_dfa *cd)
 	return dfa_upload(d);
 }
 
+/* a handle that goes, when its creation fails, without touching that failure's errno */
+struct __attribute__((visibility("hidden"))) DfaDrop { void operator()(fsm_hip_dfa *d) const { const int e = errno; fsm_hip_dfa_free(d); errno = e; } };
+
 extern "C" struct fsm_hip_dfa *fsm_hip_dfa_create(const struct fsm_hip_dfa_desc *desc, unsigned flags)
 {
 	int ndev = 0;
@@ -521,66 +473,36 @@ extern "C" struct fsm_hip_dfa *fsm_hip_dfa_create(const struct fsm_hip_dfa_desc 
 		errno = ENODEV; /* no CPU fallback by design */
 		return nullptr;
 	}
-	fsm_hip_dfa *d = new (std::nothrow) fsm_hip_dfa();
+	std::unique_ptr<fsm_hip_dfa, DfaDrop> d(new (std::nothrow) fsm_hip_dfa());
 	if (d == nullptr) { errno = ENOMEM; return nullptr; }
 	d->flags = flags;
 	{
 		int v = 0;
-		HIP_TRY(hipGetDevice(&d->device));
+		if (!HIP_OK(hipGetDevice(&d->device))) return nullptr;
 		if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d->device) == hipSuccess && v > 0) d->ncu = v;
 		if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, d->device) == hipSuccess && v > 0) d->lds_limit = (uint32_t)v;
 		if (d->lds_limit > 160u * 1024u) d->lds_limit = 160u * 1024u;
 	}
 	{
 		int r = build_plan(desc, flags, d->lds_limit, d->plan);
-		if (r != 0) { errno = r; goto fail; }
+		if (r != 0) { errno = r; return nullptr; }
 	}
-	if (!(flags & FSM_HIP_DEFER_UPLOAD) && dfa_upload(d) != 0) goto fail;
+	if (!(flags & FSM_HIP_DEFER_UPLOAD) && dfa_upload(d.get()) != 0) return nullptr;
 	if (d->plan.layout == FSM_HIP_LAYOUT_LDS2 && (flags & FSM_HIP_LAYOUT_MASK) == FSM_HIP_LAYOUT_AUTO && !(flags & FSM_HIP_PLAN_NO_LDS2)) {
 		/* fewer than eight ragged wavefronts fit beside the pair table: the variable-length fronts get a table of their own */
 		const uint32_t pair_lds = Lds2Pol::lds_bytes((uint32_t)(d->plan.lds_tab.size() * 2));
 		if (pair_lds + 8u * FSMHIP_RAGGED_WAVE_LDS > d->lds_limit) {
 			d->alt = fsm_hip_dfa_create(desc, flags | FSM_HIP_PLAN_NO_LDS2);
-			if (d->alt == nullptr) goto fail;
+			if (d->alt == nullptr) return nullptr;
 		}
 	}
-	return d;
-fail:
-	{
-		int e = errno;
-		fsm_hip_dfa_free(d);
-		errno = e;
-	}
-	return nullptr;
+	return d.release();
 }
 
+/* everything the handle holds goes with it (the second image first: ~fsm_hip_dfa) */
 extern "C" void fsm_hip_dfa_free(struct fsm_hip_dfa *d)
 {
 	if (d == nullptr) return;
-	if (d->alt) fsm_hip_dfa_free(d->alt);
-	if (d->d_tab) (void)hipFree(d->d_tab);
-	if (d->d_fin) (void)hipFree(d->d_fin);
-	if (d->d_btab) (void)hipFree(d->d_btab);
-	if (d->d_lazy) (void)hipFree(d->d_lazy);
-	if (d->d_lazy_ctr) (void)hipFree(d->d_lazy_ctr);
-	if (d->d_fin_earliest) (void)hipFree(d->d_fin_earliest);
-	if (d->d_fin_ret) (void)hipFree(d->d_fin_ret);
-	if (d->d_enc_of) (void)hipFree(d->d_enc_of);
-	if (d->d_orig_of) (void)hipFree(d->d_orig_of);
-	if (d->d_emask) (void)hipFree(d->d_emask);
-	if (d->d_ew_off) (void)hipFree(d->d_ew_off);
-	if (d->d_ew_word) (void)hipFree(d->d_ew_word);
-	if (d->d_ew_mask) (void)hipFree(d->d_ew_mask);
-	for (uint32_t *q : { d->d_tr_dense, d->d_tr_cls4, d->d_tr_eoff, d->d_tr_eids, d->d_tr_fin }) if (q) (void)hipFree(q);
-	if (d->d_pick) (void)hipFree(d->d_pick);
-	if (d->tb_scratch) (void)hipFree(d->tb_scratch);
-	for (void *q : d->tb_scratch_old) (void)hipFree(q);
-	if (d->tb_scratch_ev) (void)hipEventDestroy(d->tb_scratch_ev);
-	if (d->arena) (void)hipFree(d->arena);
-	if (d->stage) (void)hipHostFree(d->stage);
-	if (d->hs) (void)hipStreamDestroy(d->hs);
-	if (d->ev0) (void)hipEventDestroy(d->ev0);
-	if (d->ev1) (void)hipEventDestroy(d->ev1);
 	delete d;
 }
 
@@ -988,12 +910,11 @@ static size_t tb_bytes_for(size_t n)
 static hipError_t tb_grow(fsm_hip_dfa *d, size_t want)
 {
 	if (want <= d->tb_scratch_bytes) return hipSuccess;
-	if (d->tb_scratch) d->tb_scratch_old.push_back(d->tb_scratch);
-	d->tb_scratch = nullptr;
+	if (d->tb_scratch) d->tb_scratch_old.push_back(std::move(d->tb_scratch));
 	d->tb_scratch_bytes = 0;
 	size_t cap = (size_t)1 << 16;
 	while (cap < want) cap *= 2;
-	const hipError_t e = hipMalloc((void **)&d->tb_scratch, cap);
+	const hipError_t e = d->tb_scratch.alloc(cap);
 	if (e == hipSuccess) d->tb_scratch_bytes = cap;
 	return e;
 }
@@ -1036,7 +957,7 @@ static int tile_bases(fsm_hip_dfa *d, const uint32_t *d_len, size_t n, hipStream
 		e = tb_grow(d, want);
 	}
 	if (e == hipSuccess) {
-		uint64_t *tb = reinterpret_cast<uint64_t *>(d->tb_scratch), *bt = tb + T1;
+		uint64_t *tb = reinterpret_cast<uint64_t *>(d->tb_scratch.p), *bt = tb + T1;
 		hipLaunchKernelGGL(tile_bases_pass1, dim3((unsigned)nb), dim3(1024), 0, s, d_len, (uint64_t)n, T1, tb, bt);
 		hipLaunchKernelGGL(tile_bases_pass2, dim3(1), dim3(1024), 0, s, bt, nb);
 		uint64_t g3 = (T1 + 255u) / 256u;
@@ -1308,7 +1229,7 @@ extern "C" double fsm_hip_last_kernel_ms(const struct fsm_hip_dfa *d)
 
 /*
  * Host-pointer fronts.  One device arena per dfa (grow-only up to ARENA_KEEP, so repeated calls --
- * retest / re(1) issue one per input line -- do no hipMalloc/hipFree), laid out
+ * retest / re(1) issue one per input line -- allocate and release nothing), laid out
  *     [inputs ...] [in/out arrays ...] [outputs ...]
  * Small calls gather their host arrays in one pinned buffer: one H2D copy (inputs + in/out), the
  * kernel, one D2H copy (in/out + outputs), one stream synchronise.  Large calls copy each array
@@ -1326,11 +1247,11 @@ struct HostCall {
 	Part parts[8];
 	int np = 0;
 	unsigned char *arena = nullptr;
-	bool temp = false, small = false;
+	DevBuf<unsigned char> temp;     /* a call beyond ARENA_KEEP: its own arena, gone with the call */
+	bool small = false;
 	size_t h2d_end = 0, d2h_begin = 0, total = 0;
 
 	explicit HostCall(const fsm_hip_dfa *cd) : d(const_cast<fsm_hip_dfa *>(cd)), lk(d->mu) {}
-	~HostCall() { if (temp && arena) { int e = errno; (void)hipFree(arena); errno = e; } }
 	/* declare the arrays in the order IN..., INOUT..., OUT...; returns the part's index (or -1 for a NULL array) */
 	int add(int kind, const void *src, void *dst, size_t bytes, size_t pad = 0)
 	{
@@ -1360,48 +1281,45 @@ struct HostCall {
 		if (total <= d->arena_bytes) {
 			arena = d->arena;
 		} else if (total <= ARENA_KEEP) {
-			if (d->arena) { (void)hipFree(d->arena); d->arena = nullptr; d->arena_bytes = 0; }
+			d->arena.reset();
+			d->arena_bytes = 0;
 			size_t want = (size_t)2 << 20;
 			while (want < total) want *= 2;
-			HIP_TRY(hipMalloc((void **)&d->arena, want));
+			if (!HIP_OK(d->arena.alloc(want))) return -1;
 			d->arena_bytes = want;
 			arena = d->arena;
 		} else {
-			HIP_TRY(hipMalloc((void **)&arena, total));
-			temp = true;
+			if (!HIP_OK(temp.alloc(total))) return -1;
+			arena = temp;
 		}
 		small = total <= STAGE_BYTES;
-		if (small && d->stage == nullptr) HIP_TRY(hipHostMalloc((void **)&d->stage, STAGE_BYTES, hipHostMallocDefault));
+		if (small && d->stage == nullptr && !HIP_OK(d->stage.alloc(STAGE_BYTES))) return -1;
 		if (small) {
 			for (int i = 0; i < np; i++)
 				if (parts[i].kind != OUT && parts[i].bytes) memcpy(d->stage + parts[i].off, parts[i].src, parts[i].bytes);
-			if (h2d_end) HIP_TRY(hipMemcpyAsync(arena, d->stage, h2d_end, hipMemcpyHostToDevice, d->hs));
+			if (h2d_end && !HIP_OK(hipMemcpyAsync(arena, d->stage, h2d_end, hipMemcpyHostToDevice, d->hs))) return -1;
 		} else {
 			for (int i = 0; i < np; i++)
-				if (parts[i].kind != OUT && parts[i].bytes)
-					HIP_TRY(hipMemcpyAsync(arena + parts[i].off, parts[i].src, parts[i].bytes, hipMemcpyHostToDevice, d->hs));
+				if (parts[i].kind != OUT && parts[i].bytes &&
+				    !HIP_OK(hipMemcpyAsync(arena + parts[i].off, parts[i].src, parts[i].bytes, hipMemcpyHostToDevice, d->hs))) return -1;
 		}
 		return 0;
-	fail:
-		return -1;
 	}
 
 	int end()
 	{
 		if (small) {
-			if (total > d2h_begin) HIP_TRY(hipMemcpyAsync(d->stage + d2h_begin, arena + d2h_begin, total - d2h_begin, hipMemcpyDeviceToHost, d->hs));
-			HIP_TRY(hipStreamSynchronize(d->hs));
+			if (total > d2h_begin && !HIP_OK(hipMemcpyAsync(d->stage + d2h_begin, arena + d2h_begin, total - d2h_begin, hipMemcpyDeviceToHost, d->hs))) return -1;
+			if (!HIP_OK(hipStreamSynchronize(d->hs))) return -1;
 			for (int i = 0; i < np; i++)
 				if (parts[i].kind != IN && parts[i].bytes) memcpy(parts[i].dst, d->stage + parts[i].off, parts[i].bytes);
 		} else {
 			for (int i = 0; i < np; i++)
-				if (parts[i].kind != IN && parts[i].bytes)
-					HIP_TRY(hipMemcpyAsync(parts[i].dst, arena + parts[i].off, parts[i].bytes, hipMemcpyDeviceToHost, d->hs));
-			HIP_TRY(hipStreamSynchronize(d->hs));
+				if (parts[i].kind != IN && parts[i].bytes &&
+				    !HIP_OK(hipMemcpyAsync(parts[i].dst, arena + parts[i].off, parts[i].bytes, hipMemcpyDeviceToHost, d->hs))) return -1;
+			if (!HIP_OK(hipStreamSynchronize(d->hs))) return -1;
 		}
 		return 0;
-	fail:
-		return -1;
 	}
 };
 
@@ -1532,30 +1450,25 @@ extern "C" int fsm_hip_exec_batch_lengths(const struct fsm_hip_dfa *d,
 extern "C" double fsm_hip_lds_chain_probe_gbps(size_t table_bytes, int waves, int blocks_per_cu, size_t steps, void *d_scratch4, void *hip_stream)
 {
 	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	hipEvent_t e0 = nullptr, e1 = nullptr;
+	DevEvent e0, e1;
 	float ms = -1.f;
-	double gbps = -1.0;
 	if (d_scratch4 == nullptr || table_bytes < 2048 || table_bytes > 160u * 1024u || waves < 1 || waves > 16 || blocks_per_cu < 1 || steps < 16) { errno = EINVAL; return -1.0; }
 	int dev = 0, ncu = 256;
 	(void)hipGetDevice(&dev);
 	(void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
 	const uint32_t words = (uint32_t)(table_bytes / 4u);
 	const unsigned grid = (unsigned)(ncu * blocks_per_cu);
-	HIP_TRY(hipFuncSetAttribute((const void *)lds_chain_probe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)table_bytes));
+	if (!HIP_OK(hipFuncSetAttribute((const void *)lds_chain_probe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)table_bytes))) return -1.0;
 	for (int rep = 0; rep < 2; rep++) {   /* the second launch is the timed one */
-		if (e0 == nullptr) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); }
-		HIP_TRY(hipEventRecord(e0, s));
+		if (e0 == nullptr && (!HIP_OK(e0.create()) || !HIP_OK(e1.create()))) return -1.0;
+		if (!HIP_OK(hipEventRecord(e0, s))) return -1.0;
 		hipLaunchKernelGGL(lds_chain_probe_kernel, dim3(grid), dim3((unsigned)waves * 64u), table_bytes, s, words, (uint32_t)(steps / 16u * 16u), static_cast<uint32_t *>(d_scratch4));
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipEventRecord(e1, s));
-		HIP_TRY(hipEventSynchronize(e1));
-		HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+		if (!HIP_OK(hipGetLastError())) return -1.0;
+		if (!HIP_OK(hipEventRecord(e1, s))) return -1.0;
+		if (!HIP_OK(hipEventSynchronize(e1))) return -1.0;
+		if (!HIP_OK(hipEventElapsedTime(&ms, e0, e1))) return -1.0;
 	}
-	gbps = (double)grid * waves * 64.0 * (double)(steps / 16u * 16u) / ((double)ms * 1e-3) / 1e9;
-fail:
-	if (e0) (void)hipEventDestroy(e0);
-	if (e1) (void)hipEventDestroy(e1);
-	return gbps;
+	return (double)grid * waves * 64.0 * (double)(steps / 16u * 16u) / ((double)ms * 1e-3) / 1e9;
 }
 
 /* ------------------------------------------------------------------ */
@@ -1816,9 +1729,8 @@ extern "C" int fsm_hip_gen_affix2_inputs_device(void *d_base, size_t stride, siz
 {
 	GenArgs g;
 	AffixArgs x;
-	unsigned char *d_tab = nullptr;
+	DevBuf<unsigned char> d_tab;
 	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	int rc = -1;
 	if (stride == 0 || stride % 8u != 0 || (reinterpret_cast<uintptr_t>(d_base) % 8u) != 0 ||
 	    fill_gen(g, d_base, stride, n, first_index, seed, alphabet, nalpha, nullptr, 0, 0) != 0 ||
 	    fill_affix(x, body, nbody, body2, nbody2, npfx, nsfx, every) != 0 ||
@@ -1827,9 +1739,9 @@ extern "C" int fsm_hip_gen_affix2_inputs_device(void *d_base, size_t stride, siz
 		return -1;
 	}
 	if (n == 0) return 0;
-	HIP_TRY(hipMalloc((void **)&d_tab, 8u * ((size_t)npfx + nsfx)));
-	HIP_TRY(hipMemcpy(d_tab, prefixes, 8u * (size_t)npfx, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_tab + 8u * (size_t)npfx, suffixes, 8u * (size_t)nsfx, hipMemcpyHostToDevice));
+	if (!HIP_OK(d_tab.alloc(8u * ((size_t)npfx + nsfx)))) return -1;
+	if (!HIP_OK(hipMemcpy(d_tab, prefixes, 8u * (size_t)npfx, hipMemcpyHostToDevice))) return -1;
+	if (!HIP_OK(hipMemcpy(d_tab + 8u * (size_t)npfx, suffixes, 8u * (size_t)nsfx, hipMemcpyHostToDevice))) return -1;
 	x.pfx = d_tab;
 	x.sfx = d_tab + 8u * (size_t)npfx;
 	{
@@ -1837,17 +1749,10 @@ extern "C" int fsm_hip_gen_affix2_inputs_device(void *d_base, size_t stride, siz
 		uint64_t blocks = (total + 255) / 256;
 		if (blocks > 256u * 64u) blocks = 256u * 64u;
 		hipLaunchKernelGGL(gen_affix_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g, x);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(s)); /* the table is freed below */
+		if (!HIP_OK(hipGetLastError())) return -1;
+		if (!HIP_OK(hipStreamSynchronize(s))) return -1; /* the table goes with this call */
 	}
-	rc = 0;
-fail:
-	{
-		int e = errno;
-		if (d_tab) (void)hipFree(d_tab);
-		errno = e;
-	}
-	return rc;
+	return 0;
 }
 
 extern "C" int fsm_hip_gen_affix_inputs_device(void *d_base, size_t stride, size_t n,
@@ -1904,27 +1809,27 @@ extern "C" void fsm_hip_gen_affix_inputs_host(unsigned char *base, size_t stride
 extern "C" double fsm_hip_stream_read_probe_ms(const void *d_base, size_t bytes, void *d_scratch4, int reps, void *hip_stream)
 {
 	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	hipEvent_t e0 = nullptr, e1 = nullptr;
+	DevEvent e0, e1;
 	float ms = -1.f;
 	if (d_base == nullptr || d_scratch4 == nullptr || bytes < 16 || reps <= 0 ||
 	    (reinterpret_cast<uintptr_t>(d_base) % 16u) != 0) { errno = EINVAL; return -1.0; }
 	int dev = 0, ncu = 256;
 	(void)hipGetDevice(&dev);
 	(void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-	HIP_TRY(hipEventCreate(&e0));
-	HIP_TRY(hipEventCreate(&e1));
+	if (!HIP_OK(e0.create())) return (double)ms;
+	if (!HIP_OK(e1.create())) return (double)ms;
 	for (int nt = 0; nt < 2; nt++) {   /* plain and nontemporal loads: the faster of the two is reported */
 		void (*k)(const u32x4 *, uint64_t, uint32_t *) = nt ? stream_read_kernel<true> : stream_read_kernel<false>;
 		float t = -1.f;
 		hipLaunchKernelGGL(k, dim3((unsigned)ncu * 8u), dim3(256), 0, s,
 		                   static_cast<const u32x4 *>(d_base), (uint64_t)(bytes / 16u), static_cast<uint32_t *>(d_scratch4));
-		HIP_TRY(hipEventRecord(e0, s));
+		if (!HIP_OK(hipEventRecord(e0, s))) return (double)ms;
 		for (int r = 0; r < reps; r++)
 			hipLaunchKernelGGL(k, dim3((unsigned)ncu * 8u), dim3(256), 0, s,
 			                   static_cast<const u32x4 *>(d_base), (uint64_t)(bytes / 16u), static_cast<uint32_t *>(d_scratch4));
-		HIP_TRY(hipEventRecord(e1, s));
-		HIP_TRY(hipEventSynchronize(e1));
-		HIP_TRY(hipEventElapsedTime(&t, e0, e1));
+		if (!HIP_OK(hipEventRecord(e1, s))) return (double)ms;
+		if (!HIP_OK(hipEventSynchronize(e1))) return (double)ms;
+		if (!HIP_OK(hipEventElapsedTime(&t, e0, e1))) return (double)ms;
 		t /= (float)reps;
 		if (ms < 0.f || t < ms) ms = t;
 	}
@@ -1935,52 +1840,46 @@ extern "C" double fsm_hip_stream_read_probe_ms(const void *d_base, size_t bytes,
 		for (int waves = 3; waves <= 12; waves *= 2) {   /* 3, 6, 12 waves per workgroup, two workgroups per CU */
 			const size_t ldsb = (size_t)waves * 8192u;
 			float t = -1.f;
-			HIP_TRY(hipFuncSetAttribute((const void *)dma_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
+			if (!HIP_OK(hipFuncSetAttribute((const void *)dma_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb))) return (double)ms;
 			hipLaunchKernelGGL(dma_stream_kernel, dim3((unsigned)ncu * 2u), dim3((unsigned)waves * 64u), ldsb, s,
 			                   static_cast<const uint8_t *>(d_base), nrows, stride, static_cast<uint32_t *>(d_scratch4));
-			HIP_TRY(hipEventRecord(e0, s));
+			if (!HIP_OK(hipEventRecord(e0, s))) return (double)ms;
 			for (int r = 0; r < reps; r++)
 				hipLaunchKernelGGL(dma_stream_kernel, dim3((unsigned)ncu * 2u), dim3((unsigned)waves * 64u), ldsb, s,
 				                   static_cast<const uint8_t *>(d_base), nrows, stride, static_cast<uint32_t *>(d_scratch4));
-			HIP_TRY(hipEventRecord(e1, s));
-			HIP_TRY(hipEventSynchronize(e1));
-			HIP_TRY(hipEventElapsedTime(&t, e0, e1));
+			if (!HIP_OK(hipEventRecord(e1, s))) return (double)ms;
+			if (!HIP_OK(hipEventSynchronize(e1))) return (double)ms;
+			if (!HIP_OK(hipEventElapsedTime(&t, e0, e1))) return (double)ms;
 			t = t / (float)reps * (float)((double)bytes / (double)(nrows * stride));   /* normalise to `bytes` */
 			if (t > 0.f && t < ms) ms = t;
 		}
 	}
-fail:
-	if (e0) (void)hipEventDestroy(e0);
-	if (e1) (void)hipEventDestroy(e1);
 	return (double)ms;
 }
 
 extern "C" double fsm_hip_gather_probe_ms(const void *d_base, size_t bytes, size_t ngathers, int vec_bytes, void *d_scratch4, void *hip_stream)
 {
 	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	hipEvent_t e0 = nullptr, e1 = nullptr;
+	DevEvent e0, e1;
 	float ms = -1.f;
 	if (d_base == nullptr || d_scratch4 == nullptr || (vec_bytes != 4 && vec_bytes != 16) || bytes < 16 || ngathers == 0 ||
 	    (reinterpret_cast<uintptr_t>(d_base) % 16u) != 0) { errno = EINVAL; return -1.0; }
 	int dev = 0, ncu = 256;
 	(void)hipGetDevice(&dev);
 	(void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-	HIP_TRY(hipEventCreate(&e0));
-	HIP_TRY(hipEventCreate(&e1));
-	HIP_TRY(hipEventRecord(e0, s));
+	if (!HIP_OK(e0.create())) return (double)ms;
+	if (!HIP_OK(e1.create())) return (double)ms;
+	if (!HIP_OK(hipEventRecord(e0, s))) return (double)ms;
 	if (vec_bytes == 16)
 		hipLaunchKernelGGL(gather_probe_kernel<16>, dim3((unsigned)ncu * 8u), dim3(256), 0, s, static_cast<const unsigned char *>(d_base),
 		                   (uint64_t)(bytes / 16u), (uint64_t)ngathers, static_cast<uint32_t *>(d_scratch4));
 	else
 		hipLaunchKernelGGL(gather_probe_kernel<4>, dim3((unsigned)ncu * 8u), dim3(256), 0, s, static_cast<const unsigned char *>(d_base),
 		                   (uint64_t)(bytes / 4u), (uint64_t)ngathers, static_cast<uint32_t *>(d_scratch4));
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(e1, s));
-	HIP_TRY(hipEventSynchronize(e1));
-	HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-fail:
-	if (e0) (void)hipEventDestroy(e0);
-	if (e1) (void)hipEventDestroy(e1);
+	if (!HIP_OK(hipGetLastError())) return (double)ms;
+	if (!HIP_OK(hipEventRecord(e1, s))) return (double)ms;
+	if (!HIP_OK(hipEventSynchronize(e1))) return (double)ms;
+	if (!HIP_OK(hipEventElapsedTime(&ms, e0, e1))) return (double)ms;
 	return (double)ms;
 }
 
@@ -2068,12 +1967,10 @@ static int ensure_ids(fsm_hip_dfa *d)
 	}
 	DevGuard dg(d->device);
 	if (!dg.ok()) { errno = ENODEV; return -1; }
-	HIP_TRY(upload(&d->d_fin_earliest, fe));
-	HIP_TRY(upload(&d->d_fin_ret, fr));
+	if (!HIP_OK(d->d_fin_earliest.upload(fe))) return -1;
+	if (!HIP_OK(d->d_fin_ret.upload(fr))) return -1;
 	d->ids_ready = true;
 	return 0;
-fail:
-	return -1;
 }
 
 static Outputs ids_outputs(int mode, uint32_t *id_out)
@@ -2163,12 +2060,10 @@ static int ensure_resume(fsm_hip_dfa *d)
 	for (uint32_t n2 = 0; n2 + 1 < p.S1; n2++) orig[d->enc_host[n2] / d->proto.fin_div] = p.new2old[n2];
 	DevGuard dg(d->device);
 	if (!dg.ok()) { errno = ENODEV; return -1; }
-	HIP_TRY(upload(&d->d_enc_of, enc));
-	HIP_TRY(upload(&d->d_orig_of, orig));
+	if (!HIP_OK(d->d_enc_of.upload(enc))) return -1;
+	if (!HIP_OK(d->d_orig_of.upload(orig))) return -1;
 	d->resume_ready = true;
 	return 0;
-fail:
-	return -1;
 }
 
 extern "C" int fsm_hip_state_is_absorbing(const struct fsm_hip_dfa *d, uint32_t state)
@@ -2383,15 +2278,13 @@ static int ensure_trace(fsm_hip_dfa *d)
 	for (unsigned b = 0; b < 256; b++) cls4[b >> 2] |= (uint32_t)p.cls[b] << ((b & 3u) * 8u);
 	DevGuard dg(d->device);
 	if (!dg.ok()) { errno = ENODEV; return -1; }
-	HIP_TRY(upload(&d->d_tr_dense, p.dense));
-	HIP_TRY(upload(&d->d_tr_cls4, cls4));
-	HIP_TRY(upload(&d->d_tr_eoff, eoff));
-	HIP_TRY(upload(&d->d_tr_eids, eids));
-	HIP_TRY(upload(&d->d_tr_fin, p.fin));
+	if (!HIP_OK(d->d_tr_dense.upload(p.dense))) return -1;
+	if (!HIP_OK(d->d_tr_cls4.upload(cls4))) return -1;
+	if (!HIP_OK(d->d_tr_eoff.upload(eoff))) return -1;
+	if (!HIP_OK(d->d_tr_eids.upload(eids))) return -1;
+	if (!HIP_OK(d->d_tr_fin.upload(p.fin))) return -1;
 	d->trace_ready = true;
 	return 0;
-fail:
-	return -1;
 }
 
 extern "C" int fsm_hip_exec_batch_eager_trace_device(const struct fsm_hip_dfa *cd,

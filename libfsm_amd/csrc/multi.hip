@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <numeric>
@@ -33,6 +34,7 @@
 
 #include "../../include/fsm_hip.h"
 #include "dfa_access.h"
+#include "hip_host.h"
 
 using namespace fsmhip;
 
@@ -338,48 +340,35 @@ walk_multi_eager(const MultiJob *jobs, const uint32_t *tile_job, const MultiEage
 
 struct MultiCtx {
 	std::mutex mu;
-	hipStream_t s = nullptr;
-	unsigned char *pin = nullptr, *dev = nullptr;
+	DevStream s;
+	PinBuf<unsigned char> pin;
+	DevBuf<unsigned char> dev;
 	size_t pin_bytes = 0, dev_bytes = 0;
-	hipEvent_t ev = nullptr;
+	DevEvent ev;
 	bool busy = false;           /* a device-pointer call's launch may still read the blocks */
 };
 constexpr int MAXDEV = 64;
-MultiCtx g_ctx[MAXDEV];
+MultiCtx *const g_ctx = new MultiCtx[MAXDEV];   /* never deleted: nothing of HIP is called while the process unloads */
 std::atomic<unsigned> g_last_launches{0}, g_last_fused_jobs{0};
-
-int hip_errno_(hipError_t e)
-{
-	switch (e) {
-	case hipSuccess: return 0;
-	case hipErrorOutOfMemory: return ENOMEM;
-	case hipErrorNoDevice:
-	case hipErrorInvalidDevice: return ENODEV;
-	case hipErrorInvalidValue: return EINVAL;
-	default: return EIO;
-	}
-}
-
-#define MTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
-	if (getenv("FSM_HIP_DEBUG")) fprintf(stderr, "fsm_hip multi: %s -> %s\n", #expr, hipGetErrorString(e_)); \
-	errno = hip_errno_(e_); return -1; } } while (0)
 
 size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
 
 int ctx_reserve(MultiCtx &cx, size_t bytes)
 {
-	if (cx.s == nullptr) MTRY(hipStreamCreateWithFlags(&cx.s, hipStreamNonBlocking));
-	if (cx.ev == nullptr) MTRY(hipEventCreateWithFlags(&cx.ev, hipEventDisableTiming));
-	if (cx.busy) { MTRY(hipEventSynchronize(cx.ev)); cx.busy = false; }
+	if (cx.s == nullptr && !HIP_OK(cx.s.create(hipStreamNonBlocking))) return -1;
+	if (cx.ev == nullptr && !HIP_OK(cx.ev.create(hipEventDisableTiming))) return -1;
+	if (cx.busy) {
+		if (!HIP_OK(hipEventSynchronize(cx.ev))) return -1;
+		cx.busy = false;
+	}
 	if (bytes > cx.pin_bytes) {
 		size_t want = (size_t)1 << 16;
 		while (want < bytes) want *= 2;
-		if (cx.pin) (void)hipHostFree(cx.pin);
-		if (cx.dev) (void)hipFree(cx.dev);
-		cx.pin = cx.dev = nullptr;
+		cx.pin.reset();
+		cx.dev.reset();
 		cx.pin_bytes = cx.dev_bytes = 0;
-		MTRY(hipHostMalloc((void **)&cx.pin, want, hipHostMallocDefault));
-		MTRY(hipMalloc((void **)&cx.dev, want));
+		if (!HIP_OK(cx.pin.alloc(want))) return -1;
+		if (!HIP_OK(cx.dev.alloc(want))) return -1;
 		cx.pin_bytes = cx.dev_bytes = want;
 	}
 	return 0;
@@ -529,10 +518,8 @@ int run_device_group(int device, const struct fsm_hip_dfa *const *dfa, const Job
 	bool host, hipStream_t stream, unsigned *launches, unsigned *fused_jobs)
 {
 	if (device < 0 || device >= MAXDEV) { errno = ENODEV; return -1; }
-	int prev = -1;
-	(void)hipGetDevice(&prev);
-	if (prev != device) MTRY(hipSetDevice(device));
-	struct Restore { int prev, dev; ~Restore() { if (prev >= 0 && prev != dev) { int e = errno; (void)hipSetDevice(prev); errno = e; } } } restore{prev, device};
+	DevGuard dg(device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
 
 	MultiCtx &cx = g_ctx[device];
 	std::lock_guard<std::mutex> lk(cx.mu);
@@ -627,15 +614,15 @@ int run_device_group(int device, const struct fsm_hip_dfa *const *dfa, const Job
 			t0 += nt;
 		}
 		hipStream_t s = host ? cx.s : stream;
-		MTRY(hipMemcpyAsync(cx.dev, cx.pin, L.in_end, hipMemcpyHostToDevice, s));
+		if (!HIP_OK(hipMemcpyAsync(cx.dev, cx.pin, L.in_end, hipMemcpyHostToDevice, s))) return -1;
 		launch_fused(cx.dev, L.jobs, L.tiles, L.ejobs, L.ntiles, s);
-		MTRY(hipGetLastError());
+		if (!HIP_OK(hipGetLastError())) return -1;
 		(*launches)++;
 		*fused_jobs += (unsigned)kf;
 		if (host) {
-			if (L.total > L.in_end) MTRY(hipMemcpyAsync(cx.pin + L.in_end, cx.dev + L.in_end, L.total - L.in_end, hipMemcpyDeviceToHost, s));
+			if (L.total > L.in_end && !HIP_OK(hipMemcpyAsync(cx.pin + L.in_end, cx.dev + L.in_end, L.total - L.in_end, hipMemcpyDeviceToHost, s))) return -1;
 		} else {
-			MTRY(hipEventRecord(cx.ev, s));
+			if (!HIP_OK(hipEventRecord(cx.ev, s))) return -1;
 			cx.busy = true;
 		}
 	}
@@ -645,7 +632,7 @@ int run_device_group(int device, const struct fsm_hip_dfa *const *dfa, const Job
 		(*launches)++;
 	}
 	if (host && !fj.empty()) {
-		MTRY(hipStreamSynchronize(cx.s));
+		if (!HIP_OK(hipStreamSynchronize(cx.s))) return -1;
 		for (size_t f = 0; f < fj.size(); f++) {
 			const size_t q = fj[f], n = b[q].n;
 			if (L.end[f] != (size_t)-1) memcpy(b[q].end_out, cx.pin + L.end[f], n * 4u);
@@ -773,9 +760,9 @@ extern "C" int fsm_hip_exec_multi_eager_device(const struct fsm_hip_dfa *const *
  * on the caller's stream -- no copy, no allocation, no wait: it can be captured into a HIP graph and replayed on whatever the
  * jobs' buffers hold by then (reperf's loop over the same matcher, src/retest/reperf.c:772-784, for K matchers at once).
  */
-struct fsm_hip_multi_prepared {
+struct __attribute__((visibility("hidden"))) fsm_hip_multi_prepared {      /* (the type: its members' C++ symbols stay out of the ABI) */
 	int device = 0, ids_mode = FSM_HIP_IDS_EARLIEST;
-	unsigned char *dev = nullptr;
+	DevBuf<unsigned char> dev;
 	size_t jobs_off = 0, tiles_off = 0, ejobs_off = (size_t)-1;
 	uint32_t ntiles = 0;
 	unsigned fused = 0;
@@ -791,7 +778,7 @@ static int multi_prepare(const struct fsm_hip_dfa *const *dfa, const std::vector
 	if (k != 0 && check_jobs(dfa, have_b ? v.data() : nullptr, &ids_mode, k, false) != 0) return -1;
 	for (size_t q = 1; q < k; q++)
 		if (dfa_device(dfa[q]) != dfa_device(dfa[0])) { errno = EINVAL; return -1; }      /* one stream, one device (fsm_hip_node_exec_multi shards) */
-	fsm_hip_multi_prepared *pp = new (std::nothrow) fsm_hip_multi_prepared;
+	std::unique_ptr<fsm_hip_multi_prepared> pp(new (std::nothrow) fsm_hip_multi_prepared);
 	if (pp == nullptr) { errno = ENOMEM; return -1; }
 	pp->ids_mode = ids_mode;
 	pp->device = k != 0 ? dfa_device(dfa[0]) : 0;
@@ -806,20 +793,18 @@ static int multi_prepare(const struct fsm_hip_dfa *const *dfa, const std::vector
 		const size_t kf = fj.size();
 		uint64_t tiles = 0;
 		for (size_t q : fj) tiles += (v[q].n + MULTI_WAVES * 64u - 1u) / (MULTI_WAVES * 64u);
-		if (tiles > 0x7FFFFFFFu) { delete pp; errno = EINVAL; return -1; }
+		if (tiles > 0x7FFFFFFFu) { errno = EINVAL; return -1; }
 		std::vector<std::vector<uint32_t>> fids(kf);
 		for (size_t f = 0; f < kf; f++)
-			if (v[fj[f]].id_out != nullptr && dfa_ids_by_state(dfa[fj[f]], ids_mode, fids[f], nullptr) != 0) { delete pp; return -1; }
+			if (v[fj[f]].id_out != nullptr && dfa_ids_by_state(dfa[fj[f]], ids_mode, fids[f], nullptr) != 0) return -1;
 		Lay L;
 		size_t o = lay_head(L, kf, tiles, eager);
 		for (size_t f = 0; f < kf; f++) o = lay_tables(L, f, dfa_plan(dfa[fj[f]]), !fids[f].empty(), v[fj[f]].eager_out != nullptr, o);
-		int prev = -1;
-		(void)hipGetDevice(&prev);
-		struct Restore { int prev, dev; ~Restore() { if (prev >= 0 && prev != dev) { int e = errno; (void)hipSetDevice(prev); errno = e; } } } restore{prev, pp->device};
-		hipError_t e = prev != pp->device ? hipSetDevice(pp->device) : hipSuccess;
+		DevGuard dg(pp->device);
+		if (!dg.ok()) { errno = ENODEV; return -1; }
 		std::vector<unsigned char> host(o);
-		if (e == hipSuccess) e = hipMalloc((void **)&pp->dev, o);
-		if (e != hipSuccess) { delete pp; errno = hip_errno_(e); return -1; }
+		DevBuf<unsigned char> dev;      /* (goes, if the copy fails, while its device is still current) */
+		if (!HIP_OK(dev.alloc(o))) return -1;
 		MultiJob *jobs = reinterpret_cast<MultiJob *>(host.data() + L.jobs);
 		MultiEager *ejobs = eager ? reinterpret_cast<MultiEager *>(host.data() + L.ejobs) : nullptr;
 		uint32_t *tile_job = reinterpret_cast<uint32_t *>(host.data() + L.tiles);
@@ -827,7 +812,7 @@ static int multi_prepare(const struct fsm_hip_dfa *const *dfa, const std::vector
 		for (size_t f = 0; f < kf; f++) {
 			const size_t q = fj[f];
 			MultiJob &j = jobs[f];
-			fill_tables(host.data(), pp->dev, L, f, dfa_plan(dfa[q]), fids[f], j, eager ? ejobs + f : nullptr);
+			fill_tables(host.data(), dev, L, f, dfa_plan(dfa[q]), fids[f], j, eager ? ejobs + f : nullptr);
 			j.base = v[q].base; j.off = v[q].off;
 			j.end_out = v[q].end_out; j.id_out = v[q].id_out; j.bitmap = v[q].accept_bitmap;
 			if (eager) ejobs[f].eager_out = v[q].eager_out;
@@ -838,11 +823,11 @@ static int multi_prepare(const struct fsm_hip_dfa *const *dfa, const std::vector
 			for (uint32_t t = 0; t < nt; t++) tile_job[t0 + t] = (uint32_t)f;
 			t0 += nt;
 		}
-		e = hipMemcpy(pp->dev, host.data(), o, hipMemcpyHostToDevice);
-		if (e != hipSuccess) { (void)hipFree(pp->dev); delete pp; errno = hip_errno_(e); return -1; }
+		if (!HIP_OK(hipMemcpy(dev, host.data(), o, hipMemcpyHostToDevice))) return -1;
+		pp->dev = std::move(dev);
 		pp->jobs_off = L.jobs; pp->tiles_off = L.tiles; pp->ejobs_off = L.ejobs; pp->ntiles = (uint32_t)tiles; pp->fused = (unsigned)kf;
 	}
-	*out = pp;
+	*out = pp.release();
 	return 0;
 }
 
@@ -862,14 +847,12 @@ extern "C" int fsm_hip_multi_launch(const struct fsm_hip_multi_prepared *pp, voi
 {
 	if (pp == nullptr) { errno = EINVAL; return -1; }
 	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	int prev = -1;
-	(void)hipGetDevice(&prev);
-	if (prev != pp->device) MTRY(hipSetDevice(pp->device));
-	struct Restore { int prev, dev; ~Restore() { if (prev >= 0 && prev != dev) { int e = errno; (void)hipSetDevice(prev); errno = e; } } } restore{prev, pp->device};
+	DevGuard dg(pp->device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
 	unsigned launches = 0;
 	if (pp->ntiles != 0) {
 		launch_fused(pp->dev, pp->jobs_off, pp->tiles_off, pp->ejobs_off, pp->ntiles, s);
-		MTRY(hipGetLastError());
+		if (!HIP_OK(hipGetLastError())) return -1;
 		launches++;
 	}
 	for (const auto &sg : pp->singles) {
@@ -884,14 +867,8 @@ extern "C" int fsm_hip_multi_launch(const struct fsm_hip_multi_prepared *pp, voi
 extern "C" void fsm_hip_multi_prepared_free(struct fsm_hip_multi_prepared *pp)
 {
 	if (pp == nullptr) return;
-	if (pp->dev != nullptr) {
-		int prev = -1;
-		(void)hipGetDevice(&prev);
-		if (prev != pp->device) (void)hipSetDevice(pp->device);
-		(void)hipFree(pp->dev);           /* (waits for the device: a launch still reading the block ends first) */
-		if (prev >= 0 && prev != pp->device) (void)hipSetDevice(prev);
-	}
-	delete pp;
+	DevGuard dg(pp->device);
+	delete pp;           /* (releasing the block waits for the device: a launch still reading it ends first) */
 }
 
 extern "C" unsigned fsm_hip_multi_last_launches(void) { return g_last_launches.load(); }

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/fsm_hip.h"
+#include "hip_host.h"
 
 /* the few RCCL entry points used (rccl/rccl.h:236, :260, :611, :678, :923, :933); ncclUint64 = 5, ncclSum = 0 */
 typedef struct ncclComm *ncclComm_t;
@@ -74,14 +75,20 @@ struct node_worker {
 	bool done = true, quit = false;
 };
 
+/* what the node holds on one device.  It goes with that device current, last member first: the dfa after everything else */
+struct __attribute__((visibility("hidden"))) DfaFree { void operator()(fsm_hip_dfa *d) const { fsm_hip_dfa_free(d); } };
+struct __attribute__((visibility("hidden"))) NodeDev {
+	std::unique_ptr<fsm_hip_dfa, DfaFree> dfa;
+	DevBuf<unsigned long long> d_count;          /* one u64 per slot */
+	DevStream stream;                            /* the walk */
+	DevEvent gathered[2];                        /* per slot: that call's collective is done */
+	DevEvent walked;                             /* walk done -> collective may start */
+	DevStream cstream;                           /* the collective of an asynchronous call */
+};
+
 struct fsm_hip_node {
 	std::vector<int> dev;
-	std::vector<fsm_hip_dfa *> dfa;
-	std::vector<hipStream_t> stream;             /* per device: the walk */
-	std::vector<hipStream_t> cstream;            /* per device: the collective of an asynchronous call */
-	std::vector<hipEvent_t> walked;              /* per device: walk done -> collective may start */
-	std::vector<hipEvent_t> gathered;            /* per device and slot [2k + slot]: that call's collective is done */
-	std::vector<unsigned long long *> d_count;   /* one u64 per device */
+	std::vector<NodeDev> on;                     /* [k]: on device dev[k]; complete, or absent (a create that failed) */
 	std::vector<ncclComm_t> comm;                /* empty: exchange by peer copies */
 	std::vector<std::unique_ptr<node_worker>> workers;   /* [k] drives device k, k >= 1 */
 	int aslot = 0;                               /* which of the two count slots / gathered events the next call uses */
@@ -149,21 +156,16 @@ extern "C" void fsm_hip_node_free(struct fsm_hip_node *nd)
 		w->cv.notify_all();
 		if (w->th.joinable()) w->th.join();
 	}
-	for (size_t k = 0; k < nd->dev.size(); k++) {          /* an asynchronous call may still be in flight */
+	for (size_t k = 0; k < nd->on.size(); k++) {          /* an asynchronous call may still be in flight */
 		(void)hipSetDevice(nd->dev[k]);
-		if (k < nd->stream.size() && nd->stream[k]) (void)hipStreamSynchronize(nd->stream[k]);
-		if (k < nd->cstream.size() && nd->cstream[k]) (void)hipStreamSynchronize(nd->cstream[k]);
+		(void)hipStreamSynchronize(nd->on[k].stream);
+		(void)hipStreamSynchronize(nd->on[k].cstream);
 	}
 	for (size_t k = 0; k < nd->comm.size(); k++)
 		if (nd->comm[k] != nullptr) (void)R.CommDestroy(nd->comm[k]);
-	for (size_t k = 0; k < nd->dev.size(); k++) {
+	for (size_t k = 0; k < nd->on.size(); k++) {
 		(void)hipSetDevice(nd->dev[k]);
-		if (k < nd->cstream.size() && nd->cstream[k]) (void)hipStreamDestroy(nd->cstream[k]);
-		if (k < nd->walked.size() && nd->walked[k]) (void)hipEventDestroy(nd->walked[k]);
-		for (size_t q = 2 * k; q < 2 * k + 2 && q < nd->gathered.size(); q++) if (nd->gathered[q]) (void)hipEventDestroy(nd->gathered[q]);
-		if (k < nd->stream.size() && nd->stream[k]) (void)hipStreamDestroy(nd->stream[k]);
-		if (k < nd->d_count.size() && nd->d_count[k]) (void)hipFree(nd->d_count[k]);
-		if (k < nd->dfa.size()) fsm_hip_dfa_free(nd->dfa[k]);
+		NodeDev gone(std::move(nd->on[k]));
 	}
 	if (prev >= 0) (void)hipSetDevice(prev);
 	delete nd;
@@ -187,27 +189,15 @@ extern "C" struct fsm_hip_node *fsm_hip_node_create(const struct fsm_hip_dfa_des
 	(void)hipGetDevice(&prev);
 	int err = 0;
 	for (size_t k = 0; k < nd->dev.size() && err == 0; k++) {
-		hipStream_t s = nullptr;
-		unsigned long long *c = nullptr;
+		NodeDev nv;                                     /* (one that stays incomplete goes here, with its device current) */
 		if (hipSetDevice(nd->dev[k]) != hipSuccess) { err = ENODEV; break; }
-		fsm_hip_dfa *d = fsm_hip_dfa_create(desc, flags);   /* the table lands on the current device */
-		if (d == nullptr) { err = errno ? errno : EIO; break; }
-		nd->dfa.push_back(d);
-		if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { err = EIO; break; }
-		nd->stream.push_back(s);
-		hipStream_t cs = nullptr;
-		hipEvent_t e0 = nullptr, e1 = nullptr;
-		if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess) { err = EIO; break; }
-		nd->cstream.push_back(cs);
-		if (hipEventCreateWithFlags(&e0, hipEventDisableTiming) != hipSuccess) { err = EIO; break; }
-		nd->walked.push_back(e0);
-		if (hipEventCreateWithFlags(&e1, hipEventDisableTiming) != hipSuccess) { err = EIO; break; }
-		nd->gathered.push_back(e1);
-		e1 = nullptr;
-		if (hipEventCreateWithFlags(&e1, hipEventDisableTiming) != hipSuccess) { err = EIO; break; }
-		nd->gathered.push_back(e1);
-		if (hipMalloc((void **)&c, 16) != hipSuccess) { err = ENOMEM; break; }
-		nd->d_count.push_back(c);
+		nv.dfa.reset(fsm_hip_dfa_create(desc, flags));   /* the table lands on the current device */
+		if (nv.dfa == nullptr) { err = errno ? errno : EIO; break; }
+		if (nv.stream.create(hipStreamNonBlocking) != hipSuccess || nv.cstream.create(hipStreamNonBlocking) != hipSuccess ||
+		    nv.walked.create(hipEventDisableTiming) != hipSuccess || nv.gathered[0].create(hipEventDisableTiming) != hipSuccess ||
+		    nv.gathered[1].create(hipEventDisableTiming) != hipSuccess) { err = EIO; break; }
+		if (nv.d_count.alloc(2) != hipSuccess) { err = ENOMEM; break; }
+		nd->on.push_back(std::move(nv));
 	}
 	if (prev >= 0) (void)hipSetDevice(prev);
 	if (err != 0) { fsm_hip_node_free(nd); errno = err; return nullptr; }
@@ -240,8 +230,8 @@ extern "C" const char *fsm_hip_node_rccl_path(void) { return rccl_path; }
 
 extern "C" struct fsm_hip_dfa *fsm_hip_node_dfa(struct fsm_hip_node *nd, int k)
 {
-	if (nd == nullptr || k < 0 || (size_t)k >= nd->dfa.size()) { errno = EINVAL; return nullptr; }
-	return nd->dfa[(size_t)k];
+	if (nd == nullptr || k < 0 || (size_t)k >= nd->on.size()) { errno = EINVAL; return nullptr; }
+	return nd->on[(size_t)k].dfa.get();
 }
 
 /* words of 64 inputs per device: the batch's words split evenly, the last shards may be short or empty */
@@ -301,7 +291,7 @@ extern "C" int fsm_hip_node_exec_batch(struct fsm_hip_node *nd,
 		fsm_hip_node_shard(nd, n, k, &first, &count);
 		if (count == 0) return 0;
 		/* the replica's own host front: H2D of the slice, the walk, D2H into the caller's arrays in place */
-		return fsm_hip_exec_batch(nd->dfa[(size_t)k], base + first * stride, stride, len ? len + first : nullptr, count,
+		return fsm_hip_exec_batch(nd->on[(size_t)k].dfa.get(), base + first * stride, stride, len ? len + first : nullptr, count,
 		                          end_out ? end_out + first : nullptr, accept_bitmap ? accept_bitmap + first / 64 : nullptr);
 	});
 }
@@ -323,7 +313,7 @@ extern "C" int fsm_hip_node_exec_batch_offsets(struct fsm_hip_node *nd,
 			if (off[first + i] < off[first]) { errno = EINVAL; return -1; }
 			o[i] = off[first + i] - off[first];
 		}
-		return fsm_hip_exec_batch_offsets(nd->dfa[(size_t)k], base ? base + off[first] : nullptr, o.data(), count,
+		return fsm_hip_exec_batch_offsets(nd->on[(size_t)k].dfa.get(), base ? base + off[first] : nullptr, o.data(), count,
 		                                  end_out ? end_out + first : nullptr, accept_bitmap ? accept_bitmap + first / 64 : nullptr);
 	});
 }
@@ -345,7 +335,7 @@ extern "C" int fsm_hip_node_exec_batch_offsets32(struct fsm_hip_node *nd,
 			if (off32[first + i] < off32[first]) { errno = EINVAL; return -1; }
 			o[i] = off32[first + i] - off32[first];
 		}
-		return fsm_hip_exec_batch_offsets32(nd->dfa[(size_t)k], base ? base + off32[first] : nullptr, o.data(), count,
+		return fsm_hip_exec_batch_offsets32(nd->on[(size_t)k].dfa.get(), base ? base + off32[first] : nullptr, o.data(), count,
 		                                    end_out ? end_out + first : nullptr, accept_bitmap ? accept_bitmap + first / 64 : nullptr);
 	});
 }
@@ -374,7 +364,7 @@ extern "C" int fsm_hip_node_exec_batch_lengths(struct fsm_hip_node *nd,
 		size_t first, count;
 		fsm_hip_node_shard(nd, n, k, &first, &count);
 		if (count == 0) return 0;
-		return fsm_hip_exec_batch_lengths(nd->dfa[(size_t)k], base ? base + sbeg[(size_t)k] : nullptr, len + first, count,
+		return fsm_hip_exec_batch_lengths(nd->on[(size_t)k].dfa.get(), base ? base + sbeg[(size_t)k] : nullptr, len + first, count,
 		                                  end_out ? end_out + first : nullptr, accept_bitmap ? accept_bitmap + first / 64 : nullptr);
 	});
 }
@@ -387,7 +377,7 @@ static int read_count(fsm_hip_node *nd, int slot, unsigned long long *total)
 	for (size_t k = 0; k < (nd->comm.empty() ? g : 1); k++) {
 		unsigned long long c = 0;
 		(void)hipSetDevice(nd->dev[k]);
-		if (hipMemcpy(&c, nd->d_count[k] + slot, sizeof c, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+		if (hipMemcpy(&c, nd->on[k].d_count + slot, sizeof c, hipMemcpyDeviceToHost) != hipSuccess) return -1;
 		*total += c;
 	}
 	return 0;
@@ -398,8 +388,8 @@ static int sync_all(fsm_hip_node *nd)
 	bool ok = true;
 	for (size_t k = 0; k < nd->dev.size(); k++) {
 		(void)hipSetDevice(nd->dev[k]);
-		ok = hipStreamSynchronize(nd->stream[k]) == hipSuccess && ok;
-		ok = hipStreamSynchronize(nd->cstream[k]) == hipSuccess && ok;
+		ok = hipStreamSynchronize(nd->on[k].stream) == hipSuccess && ok;
+		ok = hipStreamSynchronize(nd->on[k].cstream) == hipSuccess && ok;
 	}
 	return ok ? 0 : -1;
 }
@@ -445,13 +435,13 @@ extern "C" int fsm_hip_node_exec_device(struct fsm_hip_node *nd, const struct fs
 		size_t first, cnt;
 		fsm_hip_node_shard(nd, n, k, &first, &cnt);
 		if (hipSetDevice(nd->dev[(size_t)k]) != hipSuccess) { errno = ENODEV; return -1; }
-		hipStream_t s = nd->stream[(size_t)k];
+		hipStream_t s = nd->on[(size_t)k].stream;
 		/* this slot's buffers were last used two asynchronous calls ago: their collective must be over */
-		if (hipStreamWaitEvent(s, nd->gathered[2 * (size_t)k + (size_t)slot], 0) != hipSuccess) { errno = EIO; return -1; }
+		if (hipStreamWaitEvent(s, nd->on[(size_t)k].gathered[slot], 0) != hipSuccess) { errno = EIO; return -1; }
 		uint64_t *slice = b->d_bitmap_all ? b->d_bitmap_all[k] + (size_t)k * wpd : nullptr;
 		if (slice != nullptr && cnt < wpd * 64 &&
 		    node_zero_async(slice, wpd * sizeof(uint64_t), s) != hipSuccess) { errno = EIO; return -1; }
-		fsm_hip_dfa *d = nd->dfa[(size_t)k];
+		fsm_hip_dfa *d = nd->on[(size_t)k].dfa.get();
 		uint32_t *e_out = b->d_end_out ? b->d_end_out[k] : nullptr;
 		if (cnt != 0) {
 			/* one walk writes every output asked for (round 3 launched one per output) */
@@ -461,11 +451,11 @@ extern "C" int fsm_hip_node_exec_device(struct fsm_hip_node *nd, const struct fs
 			if (r != 0) return -1;
 		}
 		if (count) {
-			if (node_zero_async(nd->d_count[(size_t)k] + slot, sizeof(unsigned long long), s) != hipSuccess) { errno = EIO; return -1; }
-			hipLaunchKernelGGL(count_bits_kernel, dim3(256), dim3(256), 0, s, slice, (uint64_t)wpd, nd->d_count[(size_t)k] + slot);
+			if (node_zero_async(nd->on[(size_t)k].d_count + slot, sizeof(unsigned long long), s) != hipSuccess) { errno = EIO; return -1; }
+			hipLaunchKernelGGL(count_bits_kernel, dim3(256), dim3(256), 0, s, slice, (uint64_t)wpd, nd->on[(size_t)k].d_count + slot);
 			if (hipGetLastError() != hipSuccess) { errno = EIO; return -1; }
 		}
-		if (hipEventRecord(nd->walked[(size_t)k], s) != hipSuccess) { errno = EIO; return -1; }
+		if (hipEventRecord(nd->on[(size_t)k].walked, s) != hipSuccess) { errno = EIO; return -1; }
 		return 0;
 	});
 	const int rc_errno = errno;
@@ -474,19 +464,19 @@ extern "C" int fsm_hip_node_exec_device(struct fsm_hip_node *nd, const struct fs
 	bool ok = rc == 0;
 	for (size_t k = 0; k < g && ok; k++) {
 		(void)hipSetDevice(nd->dev[k]);
-		ok = hipStreamWaitEvent(nd->cstream[k], nd->walked[k], 0) == hipSuccess;
+		ok = hipStreamWaitEvent(nd->on[k].cstream, nd->on[k].walked, 0) == hipSuccess;
 	}
 	if (ok && !nd->comm.empty()) {
 		if (b->d_bitmap_all != nullptr) {
 			ok = ok && R.GroupStart() == 0;
 			for (size_t k = 0; k < g && ok; k++)
-				ok = R.AllGather(b->d_bitmap_all[k] + k * wpd, b->d_bitmap_all[k], wpd, 5 /* ncclUint64 */, nd->comm[k], nd->cstream[k]) == 0;
+				ok = R.AllGather(b->d_bitmap_all[k] + k * wpd, b->d_bitmap_all[k], wpd, 5 /* ncclUint64 */, nd->comm[k], nd->on[k].cstream) == 0;
 			ok = R.GroupEnd() == 0 && ok;
 		}
 		if (ok && count) {
 			ok = ok && R.GroupStart() == 0;
 			for (size_t k = 0; k < g && ok; k++)
-				ok = R.AllReduce(nd->d_count[k] + slot, nd->d_count[k] + slot, 1, 5 /* ncclUint64 */, 0 /* ncclSum */, nd->comm[k], nd->cstream[k]) == 0;
+				ok = R.AllReduce(nd->on[k].d_count + slot, nd->on[k].d_count + slot, 1, 5 /* ncclUint64 */, 0 /* ncclSum */, nd->comm[k], nd->on[k].cstream) == 0;
 			ok = R.GroupEnd() == 0 && ok;
 		}
 	} else if (ok && b->d_bitmap_all != nullptr) {
@@ -495,13 +485,13 @@ extern "C" int fsm_hip_node_exec_device(struct fsm_hip_node *nd, const struct fs
 			(void)hipSetDevice(nd->dev[k]);
 			for (size_t j = 0; j < g && ok; j++) {
 				if (j == k || b->d_bitmap_all[j] == b->d_bitmap_all[k]) continue;
-				ok = hipMemcpyPeerAsync(b->d_bitmap_all[j] + k * wpd, nd->dev[j], b->d_bitmap_all[k] + k * wpd, nd->dev[k], wpd * sizeof(uint64_t), nd->cstream[k]) == hipSuccess;
+				ok = hipMemcpyPeerAsync(b->d_bitmap_all[j] + k * wpd, nd->dev[j], b->d_bitmap_all[k] + k * wpd, nd->dev[k], wpd * sizeof(uint64_t), nd->on[k].cstream) == hipSuccess;
 			}
 		}
 	}
 	for (size_t k = 0; k < g && ok; k++) {
 		(void)hipSetDevice(nd->dev[k]);
-		ok = hipEventRecord(nd->gathered[2 * k + (size_t)slot], nd->cstream[k]) == hipSuccess;
+		ok = hipEventRecord(nd->on[k].gathered[slot], nd->on[k].cstream) == hipSuccess;
 	}
 	nd->aslot ^= 1;
 	nd->async_pending = true;
@@ -544,7 +534,7 @@ extern "C" int fsm_hip_node_exec_batch_ids(struct fsm_hip_node *nd,
 		size_t first, count;
 		fsm_hip_node_shard(nd, n, k, &first, &count);
 		if (count == 0) return 0;
-		return fsm_hip_exec_batch_ids(nd->dfa[(size_t)k], base + first * stride, stride, len ? len + first : nullptr, count, mode, id_out + first);
+		return fsm_hip_exec_batch_ids(nd->on[(size_t)k].dfa.get(), base + first * stride, stride, len ? len + first : nullptr, count, mode, id_out + first);
 	});
 }
 
@@ -554,12 +544,12 @@ extern "C" int fsm_hip_node_exec_batch_eager(struct fsm_hip_node *nd,
 	if (nd == nullptr || eager_out == nullptr || (n != 0 && base == nullptr && stride != 0)) { errno = EINVAL; return -1; }
 	if (n == 0) return 0;
 	std::lock_guard<std::mutex> lk(nd->mu);
-	const size_t W = fsm_hip_eager_words(nd->dfa[0]);
+	const size_t W = fsm_hip_eager_words(nd->on[0].dfa.get());
 	return per_device(nd, [&](int k) -> int {
 		size_t first, count;
 		fsm_hip_node_shard(nd, n, k, &first, &count);
 		if (count == 0) return 0;
-		return fsm_hip_exec_batch_eager(nd->dfa[(size_t)k], base + first * stride, stride, len ? len + first : nullptr, count,
+		return fsm_hip_exec_batch_eager(nd->on[(size_t)k].dfa.get(), base + first * stride, stride, len ? len + first : nullptr, count,
 		                                end_out ? end_out + first : nullptr, eager_out + first * W);
 	});
 }
@@ -583,7 +573,7 @@ extern "C" int fsm_hip_node_exec_multi(struct fsm_hip_node *const *nodes, const 
 		std::vector<const fsm_hip_dfa *> dl;
 		std::vector<fsm_hip_multi_batch> bl;
 		for (size_t q = 0; q < k; q++)
-			if (dev_of[q] == dv) { dl.push_back(nodes[q]->dfa[(size_t)dv]); bl.push_back(b[q]); }
+			if (dev_of[q] == dv) { dl.push_back(nodes[q]->on[(size_t)dv].dfa.get()); bl.push_back(b[q]); }
 		if (dl.empty()) return 0;
 		return fsm_hip_exec_multi(dl.data(), bl.data(), dl.size());
 	});

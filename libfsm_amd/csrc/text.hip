@@ -29,6 +29,7 @@
 #include <new>
 
 #include "../../include/fsm_hip.h"
+#include "hip_host.h"
 
 namespace {
 
@@ -273,90 +274,6 @@ text_offsets(const unsigned char *text, uint64_t nbytes, uint32_t splat, uint64_
 	}
 }
 
-int herr(hipError_t e)
-{
-	switch (e) {
-	case hipSuccess: return 0;
-	case hipErrorOutOfMemory: return ENOMEM;
-	case hipErrorNoDevice:
-	case hipErrorInvalidDevice:
-	case hipErrorInsufficientDriver: return ENODEV;
-	case hipErrorInvalidValue: return EINVAL;
-	default: return EIO;
-	}
-}
-
-/* false, with errno set, when a HIP call failed: `if (!TOK(call)) return ...;` */
-bool hip_ok(hipError_t e, const char *what)
-{
-	if (e == hipSuccess) return true;
-	if (getenv("FSM_HIP_DEBUG")) fprintf(stderr, "fsm_hip: %s -> %s\n", what, hipGetErrorString(e));
-	errno = herr(e);
-	return false;
-}
-#define TOK(expr) hip_ok((expr), #expr)
-
-/* make a device current for the duration of a call and give the caller's back */
-struct DevGuard {
-	int prev = -1;
-	bool good = true;
-	explicit DevGuard(int dev)
-	{
-		if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-		if (prev != dev && hipSetDevice(dev) != hipSuccess) good = false;
-		if (prev == dev) prev = -1;
-	}
-	~DevGuard() { if (prev >= 0 && good) { int e = errno; (void)hipSetDevice(prev); errno = e; } }
-	bool ok() const { return good; }
-};
-
-/* device memory that goes with its owner.  The owner sees to it that the memory's device is current (DevGuard) and that no
- * kernel still touches it (a wait for its last event or its stream) before it lets go.  errno survives the release. */
-template <typename T>
-struct DevBuf {
-	T *p = nullptr;
-	DevBuf() = default;
-	DevBuf(const DevBuf &) = delete;
-	DevBuf &operator=(const DevBuf &) = delete;
-	DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
-	DevBuf &operator=(DevBuf &&o) noexcept
-	{
-		if (this != &o) { reset(); p = o.p; o.p = nullptr; }
-		return *this;
-	}
-	~DevBuf() { reset(); }
-	void reset()
-	{
-		if (p == nullptr) return;
-		const int e = errno;
-		(void)hipFree(p);
-		p = nullptr;
-		errno = e;
-	}
-	hipError_t alloc(uint64_t count)
-	{
-		reset();
-		return hipMalloc((void **)&p, count * sizeof(T));
-	}
-	operator T *() const { return p; }
-};
-
-struct DevEvent {
-	hipEvent_t e = nullptr;
-	DevEvent() = default;
-	DevEvent(const DevEvent &) = delete;
-	DevEvent &operator=(const DevEvent &) = delete;
-	~DevEvent()
-	{
-		if (e == nullptr) return;
-		const int en = errno;
-		(void)hipEventDestroy(e);
-		errno = en;
-	}
-	hipError_t create() { return hipEventCreate(&e); }
-	operator hipEvent_t() const { return e; }
-};
-
 bool have_device()
 {
 	int ndev = 0;
@@ -396,9 +313,9 @@ int copy_out(int device, hipEvent_t done, std::initializer_list<OutCopy> copies)
 {
 	DevGuard dg(device);
 	if (!dg.ok()) { errno = ENODEV; return -1; }
-	if (!TOK(hipEventSynchronize(done))) return -1;
+	if (!HIP_OK(hipEventSynchronize(done))) return -1;
 	for (const OutCopy &c : copies)
-		if (c.dst != nullptr && c.nbytes != 0 && !TOK(hipMemcpy(c.dst, c.src, c.nbytes, hipMemcpyDeviceToHost))) return -1;
+		if (c.dst != nullptr && c.nbytes != 0 && !HIP_OK(hipMemcpy(c.dst, c.src, c.nbytes, hipMemcpyDeviceToHost))) return -1;
 	return 0;
 }
 
@@ -411,10 +328,10 @@ double elapsed_ms(int device, hipEvent_t done, std::initializer_list<EventPair> 
 	double ms = 0.0;
 	DevGuard dg(device);
 	if (!dg.ok()) { errno = ENODEV; return -1.0; }
-	if (!TOK(hipEventSynchronize(done))) return -1.0;
+	if (!HIP_OK(hipEventSynchronize(done))) return -1.0;
 	for (const EventPair &p : pairs) {
 		float one = 0.f;
-		if (!TOK(hipEventElapsedTime(&one, p.from, p.to))) return -1.0;
+		if (!HIP_OK(hipEventElapsedTime(&one, p.from, p.to))) return -1.0;
 		ms += (double)one;
 	}
 	return ms;
@@ -430,7 +347,6 @@ struct __attribute__((visibility("hidden"))) fsm_hip_text {
 	DevBuf<unsigned char> owned;
 	DevBuf<uint64_t> d_off;                  /* n + 1 */
 	DevBuf<uint64_t> d_cnt;                  /* per block: its delimiters, then their exclusive scan; + the 2 (files: 4) words of meta */
-	hipStream_t own = nullptr;               /* the host-pointer forms run here, never on the NULL stream */
 	DevEvent ev[4];                          /* around count + scan, around offsets; ev[3]: the offsets are there */
 	/* a text of files (fsm_hip_text_open_files*): all NULL / 0 in a plain text */
 	size_t nfiles = 0;
@@ -441,7 +357,7 @@ struct __attribute__((visibility("hidden"))) fsm_hip_text {
 	DevBuf<uint64_t> d_frank;                /* per file end: (added ends before it in its block) << 1 | it adds one */
 	DevBuf<uint64_t> d_fpairs;               /* per block of file ends: (added ends, invalid entries), then their exclusive scan */
 	DevEvent fev[3];                         /* around mark + scan; fev[2]: the plain offsets are there, the merge runs to ev[3] */
-	~fsm_hip_text() { if (own != nullptr) (void)hipStreamDestroy(own); }
+	DevStream own;                           /* the host-pointer forms run here, never on the NULL stream (last: it goes first) */
 };
 
 extern "C" void fsm_hip_text_free(struct fsm_hip_text *t)
@@ -517,7 +433,7 @@ extern "C" int fsm_hip_text_exec(const struct fsm_hip_lines_dfa *ld, const struc
 	const size_t n_end = n * 4u, n_bm = (n + 63u) / 64u * 8u, n_id = n * 4u, n_eo = n * W * 8u;
 	const size_t at_bm = end_out ? up16(n_end) : 0, at_id = at_bm + (accept_bitmap ? up16(n_bm) : 0), at_eo = at_id + (id_out ? up16(n_id) : 0);
 	DevBuf<unsigned char> d;
-	if (!TOK(d.alloc(at_eo + (eager_out ? up16(n_eo) : 0)))) return -1;
+	if (!HIP_OK(d.alloc(at_eo + (eager_out ? up16(n_eo) : 0)))) return -1;
 	uint32_t *d_end = end_out ? (uint32_t *)d.p : nullptr, *d_id = id_out ? (uint32_t *)(d + at_id) : nullptr;
 	uint64_t *d_bm = accept_bitmap ? (uint64_t *)(d + at_bm) : nullptr, *d_eo = eager_out ? (uint64_t *)(d + at_eo) : nullptr;
 	auto fail = [&] {   /* the stream idle before the staging memory goes */
@@ -526,13 +442,13 @@ extern "C" int fsm_hip_text_exec(const struct fsm_hip_lines_dfa *ld, const struc
 		errno = e;
 		return -1;
 	};
-	if (!TOK(hipStreamWaitEvent(t->own, t->ev[3], 0))) return fail();   /* a text opened on the caller's stream: its offsets first */
+	if (!HIP_OK(hipStreamWaitEvent(t->own, t->ev[3], 0))) return fail();   /* a text opened on the caller's stream: its offsets first */
 	if (fsm_hip_text_exec_device(ld, t, d_end, d_bm, ids_mode, d_id, d_eo, t->own) != 0) return fail();
-	if (end_out && !TOK(hipMemcpyAsync(end_out, d_end, n_end, hipMemcpyDeviceToHost, t->own))) return fail();
-	if (accept_bitmap && !TOK(hipMemcpyAsync(accept_bitmap, d_bm, n_bm, hipMemcpyDeviceToHost, t->own))) return fail();
-	if (id_out && !TOK(hipMemcpyAsync(id_out, d_id, n_id, hipMemcpyDeviceToHost, t->own))) return fail();
-	if (eager_out && !TOK(hipMemcpyAsync(eager_out, d_eo, n_eo, hipMemcpyDeviceToHost, t->own))) return fail();
-	if (!TOK(hipStreamSynchronize(t->own))) return fail();
+	if (end_out && !HIP_OK(hipMemcpyAsync(end_out, d_end, n_end, hipMemcpyDeviceToHost, t->own))) return fail();
+	if (accept_bitmap && !HIP_OK(hipMemcpyAsync(accept_bitmap, d_bm, n_bm, hipMemcpyDeviceToHost, t->own))) return fail();
+	if (id_out && !HIP_OK(hipMemcpyAsync(id_out, d_id, n_id, hipMemcpyDeviceToHost, t->own))) return fail();
+	if (eager_out && !HIP_OK(hipMemcpyAsync(eager_out, d_eo, n_eo, hipMemcpyDeviceToHost, t->own))) return fail();
+	if (!HIP_OK(hipStreamSynchronize(t->own))) return fail();
 	return 0;
 }
 
@@ -1049,56 +965,56 @@ static int text_hits_run(struct fsm_hip_text_hits *h, const struct fsm_hip_text 
 	uint32_t sel_invert = invert;
 	uint64_t meta[2] = {0, 0}, core = 0;
 	for (DevEvent &ev : h->ev)
-		if (!TOK(ev.create())) return -1;
-	if (!TOK(hipStreamWaitEvent(s, t->ev[3], 0))) return -1;   /* the text's offsets and file_lines first */
+		if (!HIP_OK(ev.create())) return -1;
+	if (!HIP_OK(hipStreamWaitEvent(s, t->ev[3], 0))) return -1;   /* the text's offsets and file_lines first */
 	if (ctx != nullptr) {
 		const uint64_t wgrid = (nblocks + CTX_WG_BLOCKS - 1u) / CTX_WG_BLOCKS;
 		if (wgrid > 0x7fffffffu) { errno = ENOMEM; return -1; }
 		h->context = true;
 		for (DevEvent &ev : h->cev)
-			if (!TOK(ev.create())) return -1;
+			if (!HIP_OK(ev.create())) return -1;
 		if (n != 0) {
-			if (!TOK(h->d_wide.alloc(nwords)) || !TOK(h->d_sum.alloc(4u * nblocks + 2u))) return -1;
-			if (t->nfiles != 0 && !TOK(h->d_fmap.alloc(nwords))) return -1;
+			if (!HIP_OK(h->d_wide.alloc(nwords)) || !HIP_OK(h->d_sum.alloc(4u * nblocks + 2u))) return -1;
+			if (t->nfiles != 0 && !HIP_OK(h->d_fmap.alloc(nwords))) return -1;
 		}
-		if (!TOK(hipEventRecord(h->cev[0], s))) return -1;
+		if (!HIP_OK(hipEventRecord(h->cev[0], s))) return -1;
 		if (n != 0) {
 			h->d_cmeta = h->d_sum + 4u * nblocks;
-			if (!TOK(hipMemsetAsync(h->d_cmeta, 0, 2u * sizeof(uint64_t), s))) return -1;
+			if (!HIP_OK(hipMemsetAsync(h->d_cmeta, 0, 2u * sizeof(uint64_t), s))) return -1;
 			if (t->nfiles != 0) {
 				const uint64_t nends = (uint64_t)t->nfiles + 1u;
-				if (!TOK(hipMemsetAsync(h->d_fmap, 0, nwords * sizeof(uint64_t), s))) return -1;
+				if (!HIP_OK(hipMemsetAsync(h->d_fmap, 0, nwords * sizeof(uint64_t), s))) return -1;
 				hipLaunchKernelGGL(ctx_file_starts, dim3((unsigned)((nends + CTX_THREADS - 1u) / CTX_THREADS)), dim3(CTX_THREADS), 0, s,
 				                   t->d_file_lines, nends, n, h->d_fmap);
-				if (!TOK(hipGetLastError())) return -1;
+				if (!HIP_OK(hipGetLastError())) return -1;
 			}
 			hipLaunchKernelGGL(ctx_summary, dim3((unsigned)wgrid), dim3(CTX_THREADS), 0, s, d_bitmap, h->d_fmap, n, nwords, invert, nblocks,
 			                   h->d_sum, h->d_cmeta);
-			if (!TOK(hipGetLastError())) return -1;
+			if (!HIP_OK(hipGetLastError())) return -1;
 			hipLaunchKernelGGL(ctx_scan, dim3(1), dim3(CTX_SCAN_THREADS), 0, s, h->d_sum, nblocks, n);
-			if (!TOK(hipGetLastError())) return -1;
+			if (!HIP_OK(hipGetLastError())) return -1;
 			hipLaunchKernelGGL(ctx_apply, dim3((unsigned)wgrid), dim3(CTX_THREADS), 0, s, d_bitmap, h->d_fmap, n, nwords, invert, h->d_sum,
 			                   ctx[0], ctx[1], h->d_wide);
-			if (!TOK(hipGetLastError())) return -1;
+			if (!HIP_OK(hipGetLastError())) return -1;
 		}
-		if (!TOK(hipEventRecord(h->cev[1], s))) return -1;
+		if (!HIP_OK(hipEventRecord(h->cev[1], s))) return -1;
 		d_sel = h->d_wide;
 		sel_invert = 0u;
 	}
 	Grid g = grid_of(nblocks, t->device);
-	if (!TOK(hipEventRecord(h->ev[0], s))) return -1;
+	if (!HIP_OK(hipEventRecord(h->ev[0], s))) return -1;
 	if (n != 0) {
-		if (!TOK(h->d_pairs.alloc(2u * nblocks + 2u))) return -1;
+		if (!HIP_OK(h->d_pairs.alloc(2u * nblocks + 2u))) return -1;
 		uint64_t *d_meta = h->d_pairs + 2u * nblocks;
 		hipLaunchKernelGGL(hits_count, dim3((unsigned)g.wgs), dim3(HITS_THREADS), 0, s, d_sel, t->d_off, n, sel_invert, nblocks, g.per, h->d_pairs);
-		if (!TOK(hipGetLastError())) return -1;
+		if (!HIP_OK(hipGetLastError())) return -1;
 		hipLaunchKernelGGL(hits_scan, dim3(1), dim3(1024), 0, s, h->d_pairs, nblocks, d_meta);
-		if (!TOK(hipGetLastError())) return -1;
-		if (!TOK(hipEventRecord(h->ev[1], s))) return -1;
-		if (!TOK(hipMemcpyAsync(meta, d_meta, sizeof meta, hipMemcpyDeviceToHost, s))) return -1;
-		if (ctx != nullptr && !TOK(hipMemcpyAsync(&core, h->d_cmeta, sizeof core, hipMemcpyDeviceToHost, s))) return -1;
-		if (!TOK(hipStreamSynchronize(s))) return -1;
-	} else if (!TOK(hipEventRecord(h->ev[1], s))) {
+		if (!HIP_OK(hipGetLastError())) return -1;
+		if (!HIP_OK(hipEventRecord(h->ev[1], s))) return -1;
+		if (!HIP_OK(hipMemcpyAsync(meta, d_meta, sizeof meta, hipMemcpyDeviceToHost, s))) return -1;
+		if (ctx != nullptr && !HIP_OK(hipMemcpyAsync(&core, h->d_cmeta, sizeof core, hipMemcpyDeviceToHost, s))) return -1;
+		if (!HIP_OK(hipStreamSynchronize(s))) return -1;
+	} else if (!HIP_OK(hipEventRecord(h->ev[1], s))) {
 		return -1;
 	}
 	h->core_count = (size_t)core;
@@ -1106,50 +1022,50 @@ static int text_hits_run(struct fsm_hip_text_hits *h, const struct fsm_hip_text 
 	h->nbytes = bytes ? (size_t)meta[1] : 0;
 	if (h->m == 0) { nblocks = 0; g = Grid(); }   /* nothing to re-read: the emit kernel leaves out_off = {0} alone */
 	const uint64_t m = h->m, ngb = ((uint64_t)h->nbytes + HITS_BLOCK - 1u) / HITS_BLOCK;
-	if (m != 0 && !TOK(h->d_lines.alloc(m))) return -1;
+	if (m != 0 && !HIP_OK(h->d_lines.alloc(m))) return -1;
 	if (bytes) {
-		if (!TOK(h->d_off.alloc(m + 1u))) return -1;
-		if (m != 0 && (!TOK(h->d_src.alloc(m)) || !TOK(h->d_first.alloc(ngb + 1u)) || !TOK(h->d_bytes.alloc(ngb * HITS_BLOCK)))) return -1;
+		if (!HIP_OK(h->d_off.alloc(m + 1u))) return -1;
+		if (m != 0 && (!HIP_OK(h->d_src.alloc(m)) || !HIP_OK(h->d_first.alloc(ngb + 1u)) || !HIP_OK(h->d_bytes.alloc(ngb * HITS_BLOCK)))) return -1;
 	}
-	if (!TOK(hipEventRecord(h->ev[2], s))) return -1;
+	if (!HIP_OK(hipEventRecord(h->ev[2], s))) return -1;
 	if (m != 0 || bytes) {
 		hipLaunchKernelGGL(hits_emit, dim3((unsigned)g.wgs), dim3(HITS_THREADS), 0, s, d_sel, t->d_off, n, sel_invert, nblocks, g.per, h->d_pairs,
 		                   m, (uint64_t)h->nbytes, h->d_lines, h->d_off, h->d_src, h->d_first, ngb);
-		if (!TOK(hipGetLastError())) return -1;
+		if (!HIP_OK(hipGetLastError())) return -1;
 	}
-	if (!TOK(hipEventRecord(h->ev[3], s))) return -1;
+	if (!HIP_OK(hipEventRecord(h->ev[3], s))) return -1;
 	if (ctx != nullptr) {   /* the marks of the m hits: core and group, ceil(m / 64) words each; they read the caller's bitmap */
-		if (!TOK(hipEventRecord(h->cev[2], s))) return -1;
+		if (!HIP_OK(hipEventRecord(h->cev[2], s))) return -1;
 		if (m != 0) {
 			const uint64_t mwords = (m + 63u) / 64u, mgrid = (m + CTX_THREADS - 1u) / CTX_THREADS;
 			if (mgrid > 0x7fffffffu) { errno = ENOMEM; return -1; }
-			if (!TOK(h->d_core.alloc(mwords)) || !TOK(h->d_group.alloc(mwords))) return -1;
+			if (!HIP_OK(h->d_core.alloc(mwords)) || !HIP_OK(h->d_group.alloc(mwords))) return -1;
 			hipLaunchKernelGGL(ctx_marks, dim3((unsigned)mgrid), dim3(CTX_THREADS), 0, s, h->d_lines, m, d_bitmap, h->d_fmap, n, invert, h->d_core,
 			                   h->d_group, h->d_cmeta);
-			if (!TOK(hipGetLastError())) return -1;
+			if (!HIP_OK(hipGetLastError())) return -1;
 		}
-		if (!TOK(hipEventRecord(h->cev[3], s))) return -1;
+		if (!HIP_OK(hipEventRecord(h->cev[3], s))) return -1;
 	}
 	if (t->nfiles != 0) {   /* also under NO_BYTES and when m == 0 */
 		const uint64_t nends = (uint64_t)t->nfiles + 1u;
 		h->nfiles = t->nfiles;
 		for (DevEvent &ev : h->fev)
-			if (!TOK(ev.create())) return -1;
-		if (!TOK(h->d_file_first.alloc(nends))) return -1;
-		if (!TOK(hipEventRecord(h->fev[0], s))) return -1;
+			if (!HIP_OK(ev.create())) return -1;
+		if (!HIP_OK(h->d_file_first.alloc(nends))) return -1;
+		if (!HIP_OK(hipEventRecord(h->fev[0], s))) return -1;
 		hipLaunchKernelGGL(hits_file_first, dim3((unsigned)((nends + HITS_THREADS - 1u) / HITS_THREADS)), dim3(HITS_THREADS), 0, s, h->d_lines, m,
 		                   t->d_file_lines, nends, h->d_file_first);
-		if (!TOK(hipGetLastError())) return -1;
-		if (!TOK(hipEventRecord(h->fev[1], s))) return -1;
+		if (!HIP_OK(hipGetLastError())) return -1;
+		if (!HIP_OK(hipEventRecord(h->fev[1], s))) return -1;
 	}
-	if (!TOK(hipEventRecord(h->ev[4], s))) return -1;
+	if (!HIP_OK(hipEventRecord(h->ev[4], s))) return -1;
 	if (ngb != 0) {
 		const Grid gg = grid_of(ngb, t->device);
 		hipLaunchKernelGGL(hits_gather, dim3((unsigned)gg.wgs), dim3(HITS_THREADS), 0, s, t->d_text, (uint64_t)t->nbytes, h->d_off, h->d_src,
 		                   h->d_first, m, (uint64_t)h->nbytes, ngb, gg.per, h->d_bytes);
-		if (!TOK(hipGetLastError())) return -1;
+		if (!HIP_OK(hipGetLastError())) return -1;
 	}
-	return TOK(hipEventRecord(h->ev[5], s)) ? 0 : -1;
+	return HIP_OK(hipEventRecord(h->ev[5], s)) ? 0 : -1;
 }
 
 /* the hits object of a run on stream s; when the run fails, the stream is made idle before what it has launched on is released */
@@ -1198,10 +1114,10 @@ static struct fsm_hip_text_hits *text_hits_host(const struct fsm_hip_lines_dfa *
 	struct fsm_hip_text_hits *h = nullptr;
 	bool ok = true;
 	if (t->n != 0)
-		ok = TOK(d_bm.alloc((t->n + 63u) / 64u)) && TOK(hipStreamWaitEvent(t->own, t->ev[3], 0)) &&
+		ok = HIP_OK(d_bm.alloc((t->n + 63u) / 64u)) && HIP_OK(hipStreamWaitEvent(t->own, t->ev[3], 0)) &&
 		     fsm_hip_text_exec_device(ld, t, nullptr, d_bm, 0, nullptr, nullptr, t->own) == 0;
 	ok = ok && (h = text_hits_new(t, d_bm, flags, ctx, t->own)) != nullptr;
-	ok = ok && TOK(hipStreamSynchronize(t->own));
+	ok = ok && HIP_OK(hipStreamSynchronize(t->own));
 	if (ok) return h;
 	const int e = errno;
 	(void)hipStreamSynchronize(t->own);
@@ -1405,42 +1321,42 @@ static int text_cut(struct fsm_hip_text *t, hipStream_t s)
 	uint64_t meta[4] = {0, 0, 0, 0};
 	if (nfb > 0x7fffffffu) { errno = ENOMEM; return -1; }
 	for (DevEvent &ev : t->ev)
-		if (!TOK(ev.create())) return -1;
+		if (!HIP_OK(ev.create())) return -1;
 	if (!files && nbytes == 0) {   /* no byte, no line: off[0] = 0 alone */
-		if (!TOK(t->d_off.alloc(1)) || !TOK(hipMemsetAsync(t->d_off, 0, sizeof(uint64_t), s))) return -1;
+		if (!HIP_OK(t->d_off.alloc(1)) || !HIP_OK(hipMemsetAsync(t->d_off, 0, sizeof(uint64_t), s))) return -1;
 		for (DevEvent &ev : t->ev)
-			if (!TOK(hipEventRecord(ev, s))) return -1;
+			if (!HIP_OK(hipEventRecord(ev, s))) return -1;
 		return 0;
 	}
 	const Grid g = grid_of(nblocks, t->device);
-	if (!TOK(t->d_cnt.alloc(nblocks + nmeta))) return -1;
+	if (!HIP_OK(t->d_cnt.alloc(nblocks + nmeta))) return -1;
 	uint64_t *d_meta = t->d_cnt + nblocks;
 	if (files) {
 		for (DevEvent &ev : t->fev)
-			if (!TOK(ev.create())) return -1;
-		if (!TOK(t->d_frank.alloc(nends)) || !TOK(t->d_fpairs.alloc(2u * nfb)) || !TOK(t->d_file_lines.alloc(nends))) return -1;
+			if (!HIP_OK(ev.create())) return -1;
+		if (!HIP_OK(t->d_frank.alloc(nends)) || !HIP_OK(t->d_fpairs.alloc(2u * nfb)) || !HIP_OK(t->d_file_lines.alloc(nends))) return -1;
 	}
-	if (!TOK(hipEventRecord(t->ev[0], s))) return -1;
+	if (!HIP_OK(hipEventRecord(t->ev[0], s))) return -1;
 	if (nbytes != 0) {
 		hipLaunchKernelGGL(text_count, dim3((unsigned)g.wgs), dim3(TEXT_THREADS), 0, s, t->d_text, nbytes, splat, nblocks, g.per, t->d_cnt);
-		if (!TOK(hipGetLastError())) return -1;
+		if (!HIP_OK(hipGetLastError())) return -1;
 		hipLaunchKernelGGL(text_scan, dim3(1), dim3(1024), 0, s, t->d_cnt, nblocks, t->d_text, nbytes, (uint32_t)t->delim, d_meta);
-		if (!TOK(hipGetLastError())) return -1;
-	} else if (!TOK(hipMemsetAsync(d_meta, 0, 2u * sizeof(uint64_t), s))) {
+		if (!HIP_OK(hipGetLastError())) return -1;
+	} else if (!HIP_OK(hipMemsetAsync(d_meta, 0, 2u * sizeof(uint64_t), s))) {
 		return -1;
 	}
-	if (!TOK(hipEventRecord(t->ev[1], s))) return -1;
+	if (!HIP_OK(hipEventRecord(t->ev[1], s))) return -1;
 	if (files) {
-		if (!TOK(hipEventRecord(t->fev[0], s))) return -1;
+		if (!HIP_OK(hipEventRecord(t->fev[0], s))) return -1;
 		hipLaunchKernelGGL(files_mark, dim3((unsigned)nfb), dim3(FILES_THREADS), 0, s, t->d_text, nbytes, (uint32_t)t->delim, t->d_file_off, nends,
 		                   t->d_frank, t->d_fpairs);
-		if (!TOK(hipGetLastError())) return -1;
+		if (!HIP_OK(hipGetLastError())) return -1;
 		hipLaunchKernelGGL(files_scan, dim3(1), dim3(FILES_SCAN_THREADS), 0, s, t->d_fpairs, nfb, d_meta + 2);
-		if (!TOK(hipGetLastError())) return -1;
-		if (!TOK(hipEventRecord(t->fev[1], s))) return -1;
+		if (!HIP_OK(hipGetLastError())) return -1;
+		if (!HIP_OK(hipEventRecord(t->fev[1], s))) return -1;
 	}
-	if (!TOK(hipMemcpyAsync(meta, d_meta, nmeta * sizeof(uint64_t), hipMemcpyDeviceToHost, s))) return -1;
-	if (!TOK(hipStreamSynchronize(s))) return -1;
+	if (!HIP_OK(hipMemcpyAsync(meta, d_meta, nmeta * sizeof(uint64_t), hipMemcpyDeviceToHost, s))) return -1;
+	if (!HIP_OK(hipStreamSynchronize(s))) return -1;
 	if (meta[3] != 0) { errno = EINVAL; return -1; }
 	/* the plain offsets: bytes after the last delimiter form a last line */
 	const uint64_t np1 = nbytes == 0 ? 1u : meta[0] + (meta[1] != 0 ? 0u : 1u) + 1u;
@@ -1448,25 +1364,25 @@ static int text_cut(struct fsm_hip_text *t, hipStream_t s)
 	t->n = (size_t)(np1 - 1u + meta[2]);
 	if (files) {
 		if (nmerge > 0x7fffffffu) { errno = ENOMEM; return -1; }
-		if (!TOK(t->d_plain.alloc(np1))) return -1;
+		if (!HIP_OK(t->d_plain.alloc(np1))) return -1;
 	}
-	if (!TOK(t->d_off.alloc((uint64_t)t->n + 1u))) return -1;
+	if (!HIP_OK(t->d_off.alloc((uint64_t)t->n + 1u))) return -1;
 	uint64_t *d_plain = files ? t->d_plain : t->d_off;
-	if (!TOK(hipEventRecord(t->ev[2], s))) return -1;
+	if (!HIP_OK(hipEventRecord(t->ev[2], s))) return -1;
 	if (nbytes != 0) {
 		hipLaunchKernelGGL(text_offsets, dim3((unsigned)g.wgs), dim3(TEXT_THREADS), 0, s, t->d_text, nbytes, splat, nblocks, g.per, t->d_cnt, meta[0],
 		                   np1 - 1u, d_plain);
-		if (!TOK(hipGetLastError())) return -1;
-	} else if (!TOK(hipMemsetAsync(d_plain, 0, sizeof(uint64_t), s))) {
+		if (!HIP_OK(hipGetLastError())) return -1;
+	} else if (!HIP_OK(hipMemsetAsync(d_plain, 0, sizeof(uint64_t), s))) {
 		return -1;
 	}
 	if (files) {
-		if (!TOK(hipEventRecord(t->fev[2], s))) return -1;
+		if (!HIP_OK(hipEventRecord(t->fev[2], s))) return -1;
 		hipLaunchKernelGGL(files_merge, dim3((unsigned)nmerge), dim3(FILES_THREADS), 0, s, d_plain, np1, t->d_file_off, nends, t->d_frank,
 		                   t->d_fpairs, meta[2], (uint64_t)t->n, t->d_off, t->d_file_lines);
-		if (!TOK(hipGetLastError())) return -1;
+		if (!HIP_OK(hipGetLastError())) return -1;
 	}
-	return TOK(hipEventRecord(t->ev[3], s)) ? 0 : -1;
+	return HIP_OK(hipEventRecord(t->ev[3], s)) ? 0 : -1;
 }
 
 /* what the four open entry points share once their own arguments are checked */
@@ -1481,7 +1397,7 @@ static struct fsm_hip_text *text_open(const void *text, size_t nbytes, int delim
 	t->delim = delim;
 	t->nfiles = nfiles;
 	if (hipGetDevice(&t->device) != hipSuccess) { delete t; errno = ENODEV; return nullptr; }
-	if (!TOK(hipStreamCreateWithFlags(&t->own, hipStreamNonBlocking))) { delete t; return nullptr; }
+	if (!HIP_OK(t->own.create(hipStreamNonBlocking))) { delete t; return nullptr; }
 	hipStream_t s = host ? t->own : static_cast<hipStream_t>(hip_stream);
 	bool ok = true;
 	if (!host) {   /* the caller's device memory, the caller's stream: the offsets are in flight at return */
@@ -1489,14 +1405,14 @@ static struct fsm_hip_text *text_open(const void *text, size_t nbytes, int delim
 		t->d_file_off = file_off;
 	} else {       /* copied to the device on the text's own stream, which is idle at return */
 		const uint64_t nends = (uint64_t)nfiles + 1u;
-		if (nbytes != 0) ok = TOK(t->owned.alloc(nbytes)) && TOK(hipMemcpyAsync(t->owned, text, nbytes, hipMemcpyHostToDevice, s));
+		if (nbytes != 0) ok = HIP_OK(t->owned.alloc(nbytes)) && HIP_OK(hipMemcpyAsync(t->owned, text, nbytes, hipMemcpyHostToDevice, s));
 		if (ok && nfiles != 0)
-			ok = TOK(t->owned_file_off.alloc(nends)) &&
-			     TOK(hipMemcpyAsync(t->owned_file_off, file_off, nends * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+			ok = HIP_OK(t->owned_file_off.alloc(nends)) &&
+			     HIP_OK(hipMemcpyAsync(t->owned_file_off, file_off, nends * sizeof(uint64_t), hipMemcpyHostToDevice, s));
 		t->d_text = t->owned;
 		t->d_file_off = t->owned_file_off;
 	}
-	ok = ok && text_cut(t, s) == 0 && (!host || TOK(hipStreamSynchronize(s)));
+	ok = ok && text_cut(t, s) == 0 && (!host || HIP_OK(hipStreamSynchronize(s)));
 	if (ok) {
 		if (host) t->d_plain.reset();   /* the merge has read them */
 		return t;
