@@ -881,6 +881,85 @@ double fsm_hip_text_hits_context_ms(const struct fsm_hip_text_hits *h);         
 size_t fsm_hip_text_context_scan_block(void);                                        /* for tests: blocks of lines one round of the context scan takes */
 
 /* ------------------------------------------------------------------ */
+/* match positions: first / last accepting offset, spans of a hit      */
+/* ------------------------------------------------------------------ */
+
+/* Accept positions: WHERE in an input the walk's state is an end state.  Every front above answers with the state a walk ends
+ * in; this one with the first and the last position on the way at which the state is an end state -- what grep -o, -b -o,
+ * --color, a lexer's longest match and "offset of the first hit in this record" need.
+ *   The input has bytes b[0 .. len).  s_0 = start, s_{k+1} = delta(s_k, b[k]); DEAD after a missing edge is sticky.  A(k) means
+ *   "s_k is an end state", for k in 0 .. len inclusive: k = 0 is the start state, before any byte.  first = the smallest k with
+ *   A(k), last = the largest; both FSM_HIP_NO_POS when there is none.  As fsm_exec stops pulling bytes at a missing edge, a lane
+ *   stops at DEAD; in an absorbing end state every later position accepts, so last = len and the lane stops.
+ * Range, direction, trim:
+ *   Input j is line i = pick[j] of a packed text with n + 1 u64 offsets (pick == NULL: j = i and m = n).  len = off[i + 1] -
+ *   off[i]; with trim_byte >= 0 a non-empty line whose last byte equals trim_byte is one byte shorter (the delimiter the text
+ *   front leaves at the end of every line but possibly the last of a text or of a file: this path takes the ORIGINAL automaton,
+ *   not the identity-column twin of fsm_hip_lines_dfa_create).  to' = min(to[j], len), to == NULL: len.  from' = from[j], from ==
+ *   NULL: 0.  If from' > to' the input is not walked and both outputs are NO_POS; this includes from[j] == FSM_HIP_NO_POS.
+ *   Forward: bytes from' .. to' - 1 ascending; the position after c bytes is from' + c.  FSM_HIP_POS_BACKWARD: bytes to' - 1 down
+ *   to from'; the position after c bytes is to' - c.  Positions are byte boundaries relative to the line's first byte, in
+ *   [from', to'].  first and last are in WALKING order: backward, first is the largest position and last the smallest.
+ * struct fsm_hip_pos_dfa is the device image of a dfa for this walk, made from its host-side plan (a FSM_HIP_DEFER_UPLOAD dfa
+ * serves as well and is not uploaded by it); the dfa may be freed once the image exists.  The image lives on the dfa's device.
+ * fsm_hip_exec_accept_pos takes host pointers: it stages, launches and copies back; offsets that decrease and a pick[j] >= n are
+ * EINVAL before any launch; `limit` is ignored (off[n] bytes of base are read).  fsm_hip_exec_accept_pos_device takes device
+ * pointers and is asynchronous on hip_stream; a pick[j] >= n gives NO_POS and nothing is read for it; no byte outside
+ * [base, base + limit) is read whatever the offsets hold (limit == 0: off[n], read on the device).  Either output may be NULL.
+ * m == 0 (n == 0 without a pick) launches nothing and returns 0.  0, or -1 + errno: ENODEV (checked first: there is no CPU
+ * path), EINVAL (pd or the batch NULL, off NULL, base NULL with bytes to read, an unknown flag bit, trim_byte outside -1 .. 255;
+ * no buffer is touched and the next call answers), ENOMEM. */
+#define FSM_HIP_NO_POS UINT64_MAX
+#define FSM_HIP_POS_BACKWARD 1u
+struct fsm_hip_pos_dfa;
+struct fsm_hip_pos_batch {
+	const void *base;          /* the text's bytes */
+	const uint64_t *off;       /* n + 1 line offsets into base */
+	size_t n;                  /* lines */
+	const uint64_t *pick;      /* m line indices, or NULL: every line in order */
+	size_t m;                  /* inputs; ignored (n) when pick == NULL */
+	const uint64_t *from;      /* m, or NULL: 0 */
+	const uint64_t *to;        /* m, or NULL: the line's length */
+	int trim_byte;             /* -1: none */
+	unsigned flags;            /* FSM_HIP_POS_BACKWARD */
+	uint64_t *first_out;       /* m, or NULL */
+	uint64_t *last_out;        /* m, or NULL */
+	uint64_t limit;            /* device form: bytes of base that may be read; 0: off[n] */
+};
+struct fsm_hip_pos_dfa *fsm_hip_pos_dfa_create(const struct fsm_hip_dfa *dfa);
+void fsm_hip_pos_dfa_free(struct fsm_hip_pos_dfa *pd);
+int fsm_hip_pos_dfa_in_lds(const struct fsm_hip_pos_dfa *pd);   /* 1: the table is walked from LDS (S1 * C <= 16 384 entries); 0: from device memory, or NULL */
+int fsm_hip_exec_accept_pos(const struct fsm_hip_pos_dfa *pd, const struct fsm_hip_pos_batch *batch);
+int fsm_hip_exec_accept_pos_device(const struct fsm_hip_pos_dfa *pd, const struct fsm_hip_pos_batch *d_batch, void *hip_stream);
+
+/* Spans of a text's hits: the leftmost-longest match of every hit, advanced match by match on the device.  The caller gives two
+ * automata: `starts` is walked backward, `ends` forward, both as ORIGINAL automata with trim_byte = the text's delimiter.  For
+ * a hit whose (trimmed) line has length len, and a search position p:
+ *   start = last of `starts` walked backward over [p, len); if start != NO_POS, end = last of `ends` walked forward over
+ *   [start, len).  If either is NO_POS the hit has no span: both are NO_POS.
+ * Round 0 has p = 0 for every hit.  fsm_hip_text_spans_next sets p = end if end > start, else end + 1 (an empty match advances by
+ * one; it is reported as it is and the caller drops it as grep does), runs the two walks again and returns 0 or -1 + errno.  A hit
+ * without a span gets p = NO_POS and stays without one.  When `starts` accepts the reversal of pat preceded by anything and
+ * `ends` accepts exactly pat, the rounds deliver POSIX leftmost-longest, non-overlapping matches: what grep -o prints.  The
+ * library does not check that the two automata belong together: the result is defined for any pair.
+ * It works on every kind of hits: inverted hits and context lines simply have no span; FSM_HIP_HITS_NO_BYTES hits are fine (the
+ * text is read, not the gathered bytes).  The work is enqueued on hip_stream after the hits' last event; _next uses the same
+ * stream.  m == 0 gives a valid object with count 0 and nothing launched.  _count: the hits with a span in the current round,
+ * counted on the device; one wait.  _copy copies out whichever of start / end are not NULL (m entries each) and waits; _ms: the
+ * current round's kernels by HIP events.  The spans must be freed before their hits, their text and the two images.
+ * NULL + errno: ENODEV (checked first), EINVAL (an argument NULL, an image on another device than the text), ENOMEM. */
+struct fsm_hip_text_spans;
+struct fsm_hip_text_spans *fsm_hip_text_hits_spans(const struct fsm_hip_text_hits *h, const struct fsm_hip_text *t,
+	const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_pos_dfa *ends, void *hip_stream);
+int fsm_hip_text_spans_next(struct fsm_hip_text_spans *sp);
+size_t fsm_hip_text_spans_count(const struct fsm_hip_text_spans *sp);
+const uint64_t *fsm_hip_text_spans_start_device(const struct fsm_hip_text_spans *sp);   /* m entries; NULL when m == 0 */
+const uint64_t *fsm_hip_text_spans_end_device(const struct fsm_hip_text_spans *sp);
+int fsm_hip_text_spans_copy(const struct fsm_hip_text_spans *sp, uint64_t *start, uint64_t *end);
+double fsm_hip_text_spans_ms(const struct fsm_hip_text_spans *sp);
+void fsm_hip_text_spans_free(struct fsm_hip_text_spans *sp);
+
+/* ------------------------------------------------------------------ */
 /* synthetic input generator (benchmarks and parity tests)            */
 /* ------------------------------------------------------------------ */
 

@@ -11,4 +11,5 @@ from .capi import (  # noqa: F401
     DEFER_UPLOAD, MultiBatch, MultiBatchIds, exec_multi, exec_multi_device, exec_multi_ids, exec_multi_ids_device, MultiBatchEager, exec_multi_eager, exec_multi_eager_device, exec_multi_ptrs, MultiPrepared, multi_last_launches, multi_last_fused_jobs, multi_assign, lds_chain_probe_gbps, waves_by_occupancy,
     identity_byte, LinesDfa, HipText, text_block_bytes, text_max_workgroups,
     HipHits, HITS_INVERT, HITS_NO_BYTES, text_hits_block_lines, text_hits_block_bytes, text_files_block, text_context_scan_block,
+    NO_POS, POS_BACKWARD, PosBatch, PosDfa, HipSpans,
 )

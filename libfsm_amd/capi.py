@@ -1805,3 +1805,139 @@ def text_context_scan_block() -> int:
     lib = load_library()
     lib.fsm_hip_text_context_scan_block.restype = C.c_size_t
     return int(lib.fsm_hip_text_context_scan_block())
+
+
+# ---- match positions: first / last accepting offset, spans of a text's hits (include/fsm_hip.h, "match positions") ----
+
+NO_POS = 0xFFFFFFFFFFFFFFFF
+POS_BACKWARD = 1
+
+
+class PosBatch(C.Structure):
+    """struct fsm_hip_pos_batch"""
+    _fields_ = [("base", C.c_void_p), ("off", C.c_void_p), ("n", C.c_size_t), ("pick", C.c_void_p), ("m", C.c_size_t),
+                ("from_", C.c_void_p), ("to", C.c_void_p), ("trim_byte", C.c_int), ("flags", C.c_uint),
+                ("first_out", C.c_void_p), ("last_out", C.c_void_p), ("limit", C.c_uint64)]
+
+
+class PosDfa:
+    """struct fsm_hip_pos_dfa *: the device image of a HipDfa for the accept-position walk (the dfa may be closed afterwards)."""
+
+    def __init__(self, dfa: "HipDfa"):
+        self._lib = lib = load_library()
+        lib.fsm_hip_pos_dfa_create.restype = C.c_void_p
+        C.set_errno(0)
+        self._h = lib.fsm_hip_pos_dfa_create(C.c_void_p(dfa.handle if dfa is not None else None))
+        if not self._h:
+            raise _oserr("fsm_hip_pos_dfa_create")
+
+    @classmethod
+    def from_flat(cls, flat: FlatDfa) -> "PosDfa":
+        """the image of a description: planned with DEFER_UPLOAD, so no other table goes to the device"""
+        dfa = HipDfa(flat, DEFER_UPLOAD)
+        try:
+            return cls(dfa)
+        finally:
+            dfa.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def in_lds(self) -> bool:
+        return bool(self._lib.fsm_hip_pos_dfa_in_lds(C.c_void_p(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.fsm_hip_pos_dfa_free(C.c_void_p(self._h))
+            self._h = None
+
+    __del__ = close
+
+    def accept_pos(self, base: np.ndarray, off: np.ndarray, pick=None, frm=None, to=None, trim_byte: int = -1, backward: bool = False,
+                   want_first: bool = True, want_last: bool = True, out: Optional[tuple] = None):
+        """fsm_hip_exec_accept_pos on host arrays -> (first, last), u64 [m] each (None for the one not asked for).  out: the
+        (first, last) arrays to write into instead."""
+        base = np.ascontiguousarray(base, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        u64 = lambda a: None if a is None else np.ascontiguousarray(a, np.uint64)   # noqa: E731
+        pick, frm, to = u64(pick), u64(frm), u64(to)
+        n = len(off) - 1
+        m = n if pick is None else len(pick)
+        if pick is not None and m == 0:
+            pick = np.zeros(1, np.uint64)   # an empty pick is still a pick: a non-NULL address
+        first, last = out if out is not None else (np.empty(m, np.uint64) if want_first else None, np.empty(m, np.uint64) if want_last else None)
+        b = PosBatch(_ptr(base) if base.size else None, _ptr(off), n, _ptr(pick) if pick is not None else None, m, _ptr(frm), _ptr(to), trim_byte,
+                     POS_BACKWARD if backward else 0, _ptr(first), _ptr(last), 0)
+        C.set_errno(0)
+        if self._lib.fsm_hip_exec_accept_pos(C.c_void_p(self._h), C.byref(b)) != 0:
+            raise _oserr("fsm_hip_exec_accept_pos")
+        return first, last
+
+    def accept_pos_device(self, d_base: int, d_off: int, n: int, d_first: int = 0, d_last: int = 0, d_pick: int = 0, m: int = 0, d_from: int = 0,
+                          d_to: int = 0, trim_byte: int = -1, backward: bool = False, limit: int = 0, stream: int = 0):
+        """fsm_hip_exec_accept_pos_device: device addresses, asynchronous on `stream`"""
+        b = PosBatch(d_base or None, d_off or None, n, d_pick or None, m, d_from or None, d_to or None, trim_byte, POS_BACKWARD if backward else 0,
+                     d_first or None, d_last or None, limit)
+        C.set_errno(0)
+        if self._lib.fsm_hip_exec_accept_pos_device(C.c_void_p(self._h), C.byref(b), C.c_void_p(stream or None)) != 0:
+            raise _oserr("fsm_hip_exec_accept_pos_device")
+
+
+class HipSpans:
+    """struct fsm_hip_text_spans *: the leftmost-longest span of every hit, one match per round.  Keeps its hits, its text and
+    the two images alive: the spans must be freed first."""
+
+    def __init__(self, hits: "HipHits", starts: PosDfa, ends: PosDfa, stream: int = 0):
+        self._lib = lib = load_library()
+        lib.fsm_hip_text_hits_spans.restype = C.c_void_p
+        lib.fsm_hip_text_spans_count.restype = C.c_size_t
+        lib.fsm_hip_text_spans_start_device.restype = C.c_void_p
+        lib.fsm_hip_text_spans_end_device.restype = C.c_void_p
+        lib.fsm_hip_text_spans_ms.restype = C.c_double
+        self._keep = (hits, hits._text, starts, ends)
+        self._m = hits.count
+        C.set_errno(0)
+        self._h = lib.fsm_hip_text_hits_spans(C.c_void_p(hits.handle), C.c_void_p(hits._text.handle), C.c_void_p(starts.handle),
+                                              C.c_void_p(ends.handle), C.c_void_p(stream or None))
+        if not self._h:
+            raise _oserr("fsm_hip_text_hits_spans")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.fsm_hip_text_spans_free(C.c_void_p(self._h))
+            self._h = None
+            self._keep = None
+
+    __del__ = close
+
+    def next(self) -> None:
+        """fsm_hip_text_spans_next: every hit's search position moves behind its match; the two walks run again"""
+        C.set_errno(0)
+        if self._lib.fsm_hip_text_spans_next(C.c_void_p(self._h)) != 0:
+            raise _oserr("fsm_hip_text_spans_next")
+
+    @property
+    def count(self) -> int:
+        """the hits with a span in the current round (one wait)"""
+        return int(self._lib.fsm_hip_text_spans_count(C.c_void_p(self._h)))
+
+    @property
+    def start_ptr(self) -> int:
+        return int(self._lib.fsm_hip_text_spans_start_device(C.c_void_p(self._h)) or 0)
+
+    @property
+    def end_ptr(self) -> int:
+        return int(self._lib.fsm_hip_text_spans_end_device(C.c_void_p(self._h)) or 0)
+
+    def copy(self):
+        """-> (start, end), u64 [m] each, NO_POS where the hit has no span in this round"""
+        start, end = np.empty(self._m, np.uint64), np.empty(self._m, np.uint64)
+        C.set_errno(0)
+        if self._lib.fsm_hip_text_spans_copy(C.c_void_p(self._h), _ptr(start), _ptr(end)) != 0:
+            raise _oserr("fsm_hip_text_spans_copy")
+        return start, end
+
+    def ms(self) -> float:
+        return float(self._lib.fsm_hip_text_spans_ms(C.c_void_p(self._h)))

@@ -30,6 +30,7 @@
 
 #include "../../include/fsm_hip.h"
 #include "hip_host.h"
+#include "span.h"
 
 namespace {
 
@@ -1471,3 +1472,161 @@ extern "C" double fsm_hip_text_files_ms(const struct fsm_hip_text *t)
 }
 
 extern "C" size_t fsm_hip_text_files_block(void) { return (size_t)FILES_THREADS * FILES_SCAN_THREADS; }
+
+/* ---- spans of the hits: where in a selected line the match is -----------------------------------------------------------
+ * Two accept-position walks (span.hip) over the hits' lines of the untouched text, trim_byte = the text's delimiter: `starts`
+ * backward over [p, len) gives the leftmost start at or after p (its LAST accept in walking order), `ends` forward over
+ * [start, len) the longest match from there.  spans_close makes a half-found span none and counts the hits with one;
+ * spans_advance moves p behind the match (an empty match: one byte on).  One lane per hit, the rounds driven by the host. */
+namespace {
+
+constexpr uint32_t SPANS_THREADS = 256;
+
+__global__ void __launch_bounds__(SPANS_THREADS)
+spans_close(uint64_t *start, const uint64_t *end, uint64_t m, uint64_t *count)
+{
+	const uint64_t k = (uint64_t)blockIdx.x * SPANS_THREADS + threadIdx.x;
+	bool has = false;
+	if (k < m) {
+		has = ((glb_u64p)(uintptr_t)end)[k] != FSM_HIP_NO_POS;   /* (end is NO_POS where start is: that input was not walked) */
+		if (!has) ((glb_u64w)(uintptr_t)start)[k] = FSM_HIP_NO_POS;
+	}
+	const uint64_t b = __ballot(has);
+	if ((threadIdx.x & 63u) == 0u && b != 0)
+		(void)__hip_atomic_fetch_add((glb_u64w)(uintptr_t)count, (uint64_t)__builtin_popcountll(b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void __launch_bounds__(SPANS_THREADS)
+spans_advance(const uint64_t *start, const uint64_t *end, uint64_t m, uint64_t *p)
+{
+	const uint64_t k = (uint64_t)blockIdx.x * SPANS_THREADS + threadIdx.x;
+	if (k >= m) return;
+	const uint64_t s = ((glb_u64p)(uintptr_t)start)[k], e = ((glb_u64p)(uintptr_t)end)[k];
+	((glb_u64w)(uintptr_t)p)[k] = s == FSM_HIP_NO_POS ? FSM_HIP_NO_POS : e > s ? e : e + 1u;
+}
+
+}   // namespace
+
+struct __attribute__((visibility("hidden"))) fsm_hip_text_spans {
+	int device = 0;
+	size_t m = 0;
+	const struct fsm_hip_text *t = nullptr;
+	const struct fsm_hip_text_hits *h = nullptr;
+	const struct fsm_hip_pos_dfa *starts = nullptr, *ends = nullptr;
+	hipStream_t s = nullptr;                 /* the caller's */
+	DevBuf<uint64_t> d_p;                    /* m: the search position of every hit */
+	DevBuf<uint64_t> d_start, d_end;         /* m each */
+	DevBuf<uint64_t> d_count;                /* 1: the hits with a span, counted from 0 every round */
+	DevEvent ev[2];                          /* around the round's kernels; ev[1]: the round is there */
+};
+
+extern "C" void fsm_hip_text_spans_free(struct fsm_hip_text_spans *sp)
+{
+	if (sp == nullptr) return;
+	const int e = errno;
+	{
+		DevGuard dg(sp->device);
+		if (sp->ev[1] != nullptr) (void)hipEventSynchronize(sp->ev[1]);
+		delete sp;
+	}
+	errno = e;
+}
+
+/* one round on sp's stream, its device current: (advance), starts backward, ends forward, close */
+static int spans_round(struct fsm_hip_text_spans *sp, bool advance)
+{
+	const uint64_t m = sp->m;
+	hipStream_t s = sp->s;
+	if (!HIP_OK(hipEventRecord(sp->ev[0], s))) return -1;
+	if (m != 0) {
+		const dim3 grid((unsigned)((m + SPANS_THREADS - 1u) / SPANS_THREADS)), block(SPANS_THREADS);
+		if (advance) {
+			hipLaunchKernelGGL(spans_advance, grid, block, 0, s, sp->d_start, sp->d_end, m, sp->d_p);
+			if (!HIP_OK(hipGetLastError())) return -1;
+		}
+		if (!HIP_OK(hipMemsetAsync(sp->d_count, 0, sizeof(uint64_t), s))) return -1;
+		struct fsm_hip_pos_batch b;
+		memset(&b, 0, sizeof b);
+		b.base = sp->t->d_text;
+		b.off = sp->t->d_off;
+		b.n = sp->t->n;
+		b.pick = sp->h->d_lines;
+		b.m = (size_t)m;
+		b.trim_byte = sp->t->delim;
+		b.limit = sp->t->nbytes;
+		b.from = sp->d_p;
+		b.flags = FSM_HIP_POS_BACKWARD;
+		b.last_out = sp->d_start;
+		if (fsm_hip_exec_accept_pos_device(sp->starts, &b, s) != 0) return -1;
+		b.from = sp->d_start;
+		b.flags = 0;
+		b.last_out = sp->d_end;
+		if (fsm_hip_exec_accept_pos_device(sp->ends, &b, s) != 0) return -1;
+		hipLaunchKernelGGL(spans_close, grid, block, 0, s, sp->d_start, sp->d_end, m, sp->d_count);
+		if (!HIP_OK(hipGetLastError())) return -1;
+	}
+	return HIP_OK(hipEventRecord(sp->ev[1], s)) ? 0 : -1;
+}
+
+extern "C" struct fsm_hip_text_spans *fsm_hip_text_hits_spans(const struct fsm_hip_text_hits *h, const struct fsm_hip_text *t,
+	const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_pos_dfa *ends, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (h == nullptr || t == nullptr || starts == nullptr || ends == nullptr) { errno = EINVAL; return nullptr; }
+	if (h->device != t->device || fsmhip::pos_dfa_device(starts) != t->device || fsmhip::pos_dfa_device(ends) != t->device) { errno = EINVAL; return nullptr; }
+	if (((uint64_t)h->m + SPANS_THREADS - 1u) / SPANS_THREADS > 0x7fffffffu) { errno = ENOMEM; return nullptr; }
+	DevGuard dg(t->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	struct fsm_hip_text_spans *sp = new (std::nothrow) struct fsm_hip_text_spans;
+	if (sp == nullptr) { errno = ENOMEM; return nullptr; }
+	sp->device = t->device;
+	sp->m = h->m;
+	sp->t = t;
+	sp->h = h;
+	sp->starts = starts;
+	sp->ends = ends;
+	sp->s = static_cast<hipStream_t>(hip_stream);
+	bool ok = HIP_OK(sp->ev[0].create()) && HIP_OK(sp->ev[1].create());
+	if (ok && sp->m != 0)
+		ok = HIP_OK(sp->d_p.alloc(sp->m)) && HIP_OK(sp->d_start.alloc(sp->m)) && HIP_OK(sp->d_end.alloc(sp->m)) && HIP_OK(sp->d_count.alloc(1)) &&
+		     HIP_OK(hipStreamWaitEvent(sp->s, h->ev[5], 0)) &&                              /* the hits' lines (and, behind them, the text's offsets) first */
+		     HIP_OK(hipMemsetAsync(sp->d_p, 0, sp->m * sizeof(uint64_t), sp->s));           /* round 0: p = 0 for every hit */
+	ok = ok && spans_round(sp, false) == 0;
+	if (ok) return sp;
+	const int e = errno;
+	(void)hipStreamSynchronize(sp->s);
+	fsm_hip_text_spans_free(sp);
+	errno = e;
+	return nullptr;
+}
+
+extern "C" int fsm_hip_text_spans_next(struct fsm_hip_text_spans *sp)
+{
+	if (sp == nullptr) { errno = EINVAL; return -1; }
+	DevGuard dg(sp->device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
+	return spans_round(sp, true);
+}
+
+extern "C" size_t fsm_hip_text_spans_count(const struct fsm_hip_text_spans *sp)
+{
+	uint64_t c = 0;
+	if (sp == nullptr || sp->m == 0) return 0;
+	(void)copy_out(sp->device, sp->ev[1], {{&c, sp->d_count, sizeof c}});   /* c stays 0 when it fails */
+	return (size_t)c;
+}
+
+extern "C" const uint64_t *fsm_hip_text_spans_start_device(const struct fsm_hip_text_spans *sp) { return sp == nullptr ? nullptr : sp->d_start.p; }
+extern "C" const uint64_t *fsm_hip_text_spans_end_device(const struct fsm_hip_text_spans *sp) { return sp == nullptr ? nullptr : sp->d_end.p; }
+
+extern "C" int fsm_hip_text_spans_copy(const struct fsm_hip_text_spans *sp, uint64_t *start, uint64_t *end)
+{
+	if (sp == nullptr) { errno = EINVAL; return -1; }
+	return copy_out(sp->device, sp->ev[1], {{start, sp->d_start, sp->m * sizeof(uint64_t)}, {end, sp->d_end, sp->m * sizeof(uint64_t)}});
+}
+
+extern "C" double fsm_hip_text_spans_ms(const struct fsm_hip_text_spans *sp)
+{
+	if (sp == nullptr) { errno = EINVAL; return -1.0; }
+	return elapsed_ms(sp->device, sp->ev[1], {{sp->ev[0], sp->ev[1]}});
+}
