@@ -4,11 +4,15 @@ Python is only the harness language here (tests, bench.py); the product is the
 shared library.  Nothing in this module matches inputs on the CPU: every
 exec_* call goes through the HIP kernels and raises if the library or a GPU is
 missing.
+
+The ABI is stated once, in PROTOTYPES and the struct mirrors below; load_library() applies the table to the library it
+returns, and tests/test_capi_prototypes.py holds table, mirrors and constants to the headers as the compiler reads them.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -32,46 +36,202 @@ KNOB_RAGGED_ALIGN = 14
 KNOB_DMA_BUFS = 15
 KNOB_PICK_MEAN, KNOB_SPARSE_FAST, KNOB_LAZY_DYN, KNOB_LAZY_LINES = 18, 20, 21, 22
 IN_DIRECT, IN_LDSDMA, IN_GENERIC, IN_RAGGED = 0, 1, 2, 3
+HITS_INVERT, HITS_NO_BYTES = 1, 2
+NO_POS = 0xFFFFFFFFFFFFFFFF
+POS_BACKWARD = 1
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfsm_hip.so")
+
+# ---- the ABI: structs -------------------------------------------------------------------------------------------------------
+P, S, I, U, U32, U64, D, STR = C.c_void_p, C.c_size_t, C.c_int, C.c_uint, C.c_uint32, C.c_uint64, C.c_double, C.c_char_p
+PP = C.POINTER(C.c_void_p)
 
 RANGE_DTYPE = np.dtype([("lo", "u1"), ("hi", "u1"), ("reserved", "<u2"), ("to", "<u4")])
 
 
 class _Desc(C.Structure):
-    _fields_ = [
-        ("nstates", C.c_uint32),
-        ("start", C.c_uint32),
-        ("edge_off", C.c_void_p),
-        ("ranges", C.c_void_p),
-        ("is_end", C.c_void_p),
-        ("endid_off", C.c_void_p),
-        ("endids", C.c_void_p),
-        ("eager_off", C.c_void_p),
-        ("eager_ids", C.c_void_p),
-    ]
+    """struct fsm_hip_dfa_desc"""
+    _fields_ = [("nstates", U32), ("start", U32), ("edge_off", P), ("ranges", P), ("is_end", P), ("endid_off", P), ("endids", P),
+                ("eager_off", P), ("eager_ids", P)]
 
 
 class _Info(C.Structure):
-    _fields_ = [
-        ("nstates", C.c_uint32),
-        ("nclasses", C.c_uint32),
-        ("layout", C.c_uint32),
-        ("nabsorbing", C.c_uint32),
-        ("table_bytes", C.c_uint64),
-        ("lds_bytes", C.c_uint32),
-        ("waves_per_block", C.c_uint32),
-        ("device", C.c_uint32),
-        ("reserved", C.c_uint32),
-    ]
+    """struct fsm_hip_dfa_info"""
+    _fields_ = [("nstates", U32), ("nclasses", U32), ("layout", U32), ("nabsorbing", U32), ("table_bytes", U64), ("lds_bytes", U32),
+                ("waves_per_block", U32), ("device", U32), ("reserved", U32)]
 
+
+class MultiBatch(C.Structure):
+    """struct fsm_hip_multi_batch"""
+    _fields_ = [("base", P), ("off", P), ("n", S), ("end_out", P), ("accept_bitmap", P)]
+
+
+class MultiBatchIds(C.Structure):
+    """struct fsm_hip_multi_batch_ids"""
+    _fields_ = MultiBatch._fields_ + [("id_out", P)]
+
+
+class MultiBatchEager(C.Structure):
+    """struct fsm_hip_multi_batch_eager"""
+    _fields_ = MultiBatchIds._fields_ + [("eager_out", P)]
+
+
+class NodeBatch(C.Structure):
+    """struct fsm_hip_node_batch: per-device lists of device pointers"""
+    _fields_ = [("d_base", PP), ("stride", S), ("d_len", PP), ("d_off", PP), ("d_end_out", PP), ("d_id_out", PP), ("ids_mode", I),
+                ("d_eager_out", PP), ("d_bitmap_all", PP), ("want_count", I)]
+
+
+class PosBatch(C.Structure):
+    """struct fsm_hip_pos_batch"""
+    _fields_ = [("base", P), ("off", P), ("n", S), ("pick", P), ("m", S), ("from_", P), ("to", P), ("trim_byte", I), ("flags", U),
+                ("first_out", P), ("last_out", P), ("limit", U64)]
+
+
+# ---- the ABI: every function the two headers declare, fsm_hip_<name>: (restype, argtypes) ------------------------------------
+# P: any pointer (handles, FILE *, struct fsm *, host and device arrays, structs by address); STR: a const char * that is
+# decoded; DESC: a returned description, read through .contents; S size_t, U unsigned, U32 / U64 uintN_t, I int, D double.
+# One line per family of like-signed functions; the parameter names are in the headers.
+DESC = C.POINTER(_Desc)
+PROTOTYPES = {"fsm_hip_" + name: (restype, args) for restype, names, *args in (
+    # a DFA on the device and its batch walks: rows (data, stride, len, n), packed (base, u64 off | u32 off | len, n); _device: + stream
+    (P, "dfa_create", P, U),
+    (None, "dfa_free", P),
+    (I, "dfa_info", P, P),
+    (I, "reserve", P, S),
+    (I, "exec_batch exec_batch_resume exec_batch_eager", P, P, S, P, S, P, P),
+    (I, "exec_batch_device exec_batch_eager_device", P, P, S, P, S, P, P, P),
+    (I, "exec_batch_offsets exec_batch_offsets32 exec_batch_lengths exec_batch_resume_offsets exec_batch_eager_offsets", P, P, P, S, P, P),
+    (I, "exec_batch_offsets_device exec_batch_offsets32_device exec_batch_lengths_device exec_batch_eager_offsets_device", P, P, P, S, P, P, P),
+    (I, "exec_batch_all_device", P, P, S, P, P, S, P, P, I, P, P, P),
+    (I, "exec_batch_packed_all", P, P, I, P, S, P, P, I, P, P),
+    (I, "exec_batch_packed_all_device", P, P, I, P, S, P, P, I, P, P, P),
+    (I, "exec_batch_resume_device", P, P, S, P, S, P, P, P, P),
+    (I, "exec_batch_resume_offsets_device", P, P, P, S, P, P, P, P),
+    (I, "exec_batch_resume_packed", P, P, I, P, S, P, P),
+    (I, "exec_batch_resume_packed_device", P, P, I, P, S, P, P, P, P),
+    (I, "exec_batch_ids", P, P, S, P, S, I, P),
+    (I, "exec_batch_ids_device", P, P, S, P, S, I, P, P),
+    (I, "exec_batch_ids_offsets", P, P, P, S, I, P),
+    (I, "exec_batch_ids_offsets_device", P, P, P, S, I, P, P),
+    (I, "exec_batch_eager_resume", P, P, S, P, P, S, P, P, P),
+    (I, "exec_batch_eager_resume_device", P, P, S, P, P, S, P, P, P, P),
+    (I, "exec_batch_eager_trace", P, P, S, P, P, S, S, P, P, P, P),
+    (I, "exec_batch_eager_trace_device", P, P, S, P, P, S, S, P, P, P, P, P),
+    (D, "last_kernel_ms", P),
+    (STR, "last_kernel_name", P),
+    (S, "endid_count", P, U32),
+    (I, "endid_get", P, U32, S, P),
+    (S, "ret_count eager_id_count eager_words", P),
+    (I, "ret_get", P, U32, P, P),
+    (U32, "eager_id", P, U),
+    (I, "ids_conflict", P, P),
+    (I, "state_is_absorbing", P, U32),
+    # libfsm's side: struct fsm * in, fsm_exec's and fsm_print's shapes, one input by the whole device, descriptions on disk
+    (P, "compile", P, U),
+    (I, "exec", P, P, P, P, P),
+    (I, "match_buffer", P, P, S),
+    (I, "match_file", P, P),
+    (I, "match_buffer_big", P, P, S, P),
+    (I, "match_buffer_big_eager", P, P, S, P, P),
+    (I, "match_file_eager", P, P, P, P),
+    (None, "match_last_passes", P, P),
+    (DESC, "flatten desc_read", P),
+    (None, "desc_free", P),
+    (I, "desc_write print", P, P),
+    (DESC, "desc_identity_byte", P, I),
+    # many DFAs in one submission: (dfas, batches, k[, ids_mode][, stream | out])
+    (I, "exec_multi node_exec_multi", P, P, S),
+    (I, "exec_multi_device", P, P, S, P),
+    (I, "exec_multi_ids exec_multi_eager", P, P, S, I),
+    (I, "exec_multi_ids_device exec_multi_eager_device multi_prepare multi_prepare_eager", P, P, S, I, P),
+    (I, "multi_launch", P, P),
+    (None, "multi_prepared_free", P),
+    (U, "multi_last_launches multi_last_fused_jobs"),
+    (I, "multi_assign", P, S, I, P),
+    # one replica per device
+    (P, "node_create node_compile", P, U, P, I),
+    (None, "node_free", P),
+    (I, "node_ndev node_uses_rccl", P),
+    (P, "node_dfa", P, I),
+    (None, "node_shard", P, S, I, P, P),
+    (STR, "node_rccl_path"),
+    (I, "node_exec_batch node_exec_batch_eager", P, P, S, P, S, P, P),
+    (I, "node_exec_batch_offsets node_exec_batch_offsets32 node_exec_batch_lengths", P, P, P, S, P, P),
+    (S, "node_bitmap_words", P, S),
+    (I, "node_exec_batch_device", P, P, S, S, P, P, P),
+    (I, "node_exec_device", P, P, S, P, I),
+    (I, "node_wait", P, P),
+    (I, "node_exec_batch_ids", P, P, S, P, S, I, P),
+    # the text front: lines, hits, files, context
+    (P, "lines_dfa_create lines_compile", P, I, U),
+    (P, "lines_dfa_inner", P),
+    (I, "lines_dfa_delim", P),
+    (None, "lines_dfa_free text_free text_hits_free", P),
+    (P, "text_open", P, S, I),
+    (P, "text_open_device", P, S, I, P),
+    (P, "text_open_files", P, S, I, P, S),
+    (P, "text_open_files_device", P, S, I, P, S, P),
+    (S, "text_lines text_files text_hits_count text_hits_nbytes text_hits_core_count text_hits_groups", P),
+    (P, "text_offsets_device text_file_lines_device text_hits_lines_device text_hits_offsets_device text_hits_bytes_device "
+        "text_hits_file_first_device text_hits_core_device text_hits_group_device", P),
+    (I, "text_offsets text_file_lines text_hits_file_first", P, P),
+    (D, "text_scan_ms text_files_ms text_hits_ms text_hits_gather_ms text_hits_file_first_ms text_hits_context_ms", P),
+    (S, "text_block_bytes text_max_workgroups text_hits_block_lines text_hits_block_bytes text_files_block text_context_scan_block"),
+    (I, "text_exec", P, P, P, P, I, P, P),
+    (I, "text_exec_device", P, P, P, P, I, P, P, P),
+    (P, "text_hits", P, P, U),
+    (P, "text_hits_device", P, P, U, P),
+    (P, "text_hits_context", P, P, U, U64, U64),
+    (P, "text_hits_context_device", P, P, U, U64, U64, P),
+    (I, "text_hits_copy", P, P, P, P),
+    (I, "text_hits_marks", P, P, P),
+    # match positions and spans
+    (P, "pos_dfa_create", P),
+    (None, "pos_dfa_free text_spans_free", P),
+    (I, "pos_dfa_in_lds text_spans_next", P),
+    (I, "exec_accept_pos", P, P),
+    (I, "exec_accept_pos_device", P, P, P),
+    (P, "text_hits_spans", P, P, P, P, P),
+    (S, "text_spans_count", P),
+    (P, "text_spans_start_device text_spans_end_device", P),
+    (I, "text_spans_copy", P, P, P),
+    (D, "text_spans_ms", P),
+    # input generators: (out, stride, n, first_index, seed, {bytes, count}..., every[, stream])
+    (I, "gen_inputs_device", P, S, S, U64, U64, P, U, P, U, U, P),
+    (None, "gen_inputs_host", P, S, S, U64, U64, P, U, P, U, U),
+    (I, "gen_pack_rows_device", P, S, P, P, S, S, P, P),
+    (I, "gen_affix_inputs_device", P, S, S, U64, U64, P, U, P, U, P, U, P, U, U, P),
+    (None, "gen_affix_inputs_host", P, S, S, U64, U64, P, U, P, U, P, U, P, U, U),
+    (I, "gen_affix2_inputs_device", P, S, S, U64, U64, P, U, P, U, P, U, P, U, P, U, U, P),
+    (None, "gen_affix2_inputs_host", P, S, S, U64, U64, P, U, P, U, P, U, P, U, P, U, U),
+    # literal sets
+    (P, "strings_new"),
+    (None, "strings_free", P),
+    (I, "strings_add_raw", P, P, S, P),
+    (I, "strings_add_str", P, P, P),
+    (DESC, "strings_build", P, U),
+    (DESC, "strings", P, S, U),
+    # include/fsm_hip_plan.h: version, knobs, the host-side plan, probes
+    (I, "version"),
+    (I, "dfa_tune", P, I, I),
+    (P, "plan_create", P, U, U32),
+    (None, "plan_free", P),
+    (I, "plan_get", P, I, P, P),
+    (D, "stream_read_probe_ms", P, S, P, I, P),
+    (D, "gather_probe_ms", P, S, S, I, P, P),
+    (D, "lds_chain_probe_gbps", S, I, I, S, P, P),
+    (I, "waves_by_occupancy", I, I, I),
+) for name in names.split()}
 
 _lib = None
+_libc = C.CDLL(None, use_errno=True)
+_libc.fopen.restype, _libc.fopen.argtypes, _libc.fclose.argtypes = P, [STR, STR], [P]
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
-    """Load libfsm_hip.so (built in-tree by __graft_entry__.build())."""
+    """Load libfsm_hip.so (built in-tree by __graft_entry__.build()) with PROTOTYPES applied."""
     global _lib
     if _lib is not None and path is None:
         return _lib
@@ -79,54 +239,101 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if not os.path.exists(p):
         raise RuntimeError(f"libfsm_hip.so not built at {p}: run `python __graft_entry__.py` (no CPU fallback exists)")
     lib = C.CDLL(p, mode=C.RTLD_GLOBAL, use_errno=True)
-    vp, u32p, u64p, sz = C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t
-    lib.fsm_hip_version.restype = C.c_int
-    lib.fsm_hip_dfa_create.restype = vp
-    lib.fsm_hip_dfa_create.argtypes = [C.POINTER(_Desc), C.c_uint]
-    lib.fsm_hip_dfa_free.argtypes = [vp]
-    lib.fsm_hip_dfa_info.argtypes = [vp, C.POINTER(_Info)]
-    lib.fsm_hip_exec_batch.argtypes = [vp, vp, sz, u32p, sz, u32p, u64p]
-    lib.fsm_hip_exec_batch_offsets.argtypes = [vp, vp, u64p, sz, u32p, u64p]
-    lib.fsm_hip_exec_batch_device.argtypes = [vp, vp, sz, u32p, sz, u32p, u64p, vp]
-    lib.fsm_hip_exec_batch_offsets_device.argtypes = [vp, vp, u64p, sz, u32p, u64p, vp]
-    lib.fsm_hip_last_kernel_ms.restype = C.c_double
-    lib.fsm_hip_last_kernel_ms.argtypes = [vp]
-    lib.fsm_hip_endid_count.restype = sz
-    lib.fsm_hip_endid_count.argtypes = [vp, C.c_uint32]
-    lib.fsm_hip_endid_get.argtypes = [vp, C.c_uint32, sz, u32p]
-    lib.fsm_hip_compile.restype = vp
-    lib.fsm_hip_compile.argtypes = [vp, C.c_uint]
-    lib.fsm_hip_exec.argtypes = [vp, vp, vp, C.POINTER(C.c_uint), vp]
-    lib.fsm_hip_match_buffer.argtypes = [vp, C.c_char_p, sz]
-    lib.fsm_hip_flatten.restype = C.POINTER(_Desc)
-    lib.fsm_hip_flatten.argtypes = [vp]
-    lib.fsm_hip_desc_free.argtypes = [C.POINTER(_Desc)]
-    lib.fsm_hip_desc_read.restype = C.POINTER(_Desc)
-    lib.fsm_hip_strings_new.restype = vp
-    lib.fsm_hip_strings_free.argtypes = [vp]
-    lib.fsm_hip_strings_add_raw.argtypes = [vp, C.c_char_p, sz, u32p]
-    lib.fsm_hip_strings_build.restype = C.POINTER(_Desc)
-    lib.fsm_hip_strings_build.argtypes = [vp, C.c_uint]
-    lib.fsm_hip_gen_inputs_device.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, vp, C.c_uint, vp, C.c_uint, C.c_uint, vp]
-    lib.fsm_hip_gen_inputs_host.restype = None
-    lib.fsm_hip_gen_inputs_host.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, vp, C.c_uint, vp, C.c_uint, C.c_uint]
-    lib.fsm_hip_dfa_tune.argtypes = [vp, C.c_int, C.c_int]
-    lib.fsm_hip_plan_create.restype = vp
-    lib.fsm_hip_plan_create.argtypes = [C.POINTER(_Desc), C.c_uint, C.c_uint32]
-    lib.fsm_hip_plan_free.argtypes = [vp]
-    lib.fsm_hip_plan_get.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if path is None:
         _lib = lib
     return lib
 
 
-def _ptr(a: Optional[np.ndarray]):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def _oserr(what: str):
     e = C.get_errno()
     return OSError(e, f"{what}: {os.strerror(e)}")
+
+
+def _call(name: str, *args, negative_only: bool = False):
+    """Clear errno, call the library's `name`, raise its errno as OSError(name) on failure: a non-zero int (negative_only: a
+    negative one, for the functions that answer 0 / 1), or NULL from a function that returns a pointer.  Returns the result."""
+    C.set_errno(0)
+    r = getattr(load_library(), name)(*args)
+    if (not r) if PROTOTYPES[name][0] is not I else (r < 0 if negative_only else r != 0):
+        raise _oserr(name)
+    return r
+
+
+def _ptr(a: Optional[np.ndarray]):
+    """the array's address as a pointer object that keeps the array alive (_affix_args hands such pointers on without the arrays)"""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _ptr0(a: Optional[np.ndarray]):
+    """NULL for an empty array too"""
+    return _ptr(a) if a is not None and a.size else None
+
+
+@contextmanager
+def _fopen(path: str, mode: bytes):
+    """a FILE * of the C library, closed on the way out"""
+    f = _libc.fopen(path.encode(), mode)
+    if not f:
+        raise OSError(C.get_errno(), "fopen")
+    try:
+        yield f
+    finally:
+        _libc.fclose(f)
+
+
+def _pack_strings(strings: Sequence[bytes], pad: bytes = b""):
+    """strings -> (base u8, off u64 [n + 1]); pad: what an empty base holds instead, for the callers that pass its address"""
+    off = np.zeros(len(strings) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(s) for s in strings])
+    return np.frombuffer(b"".join(strings) or pad, dtype=np.uint8), off
+
+
+def _outputs(n: int, want_end: bool = True, want_bitmap: bool = True, fill: Optional[int] = None):
+    """(end u32 [n], accept bitmap u64 [ceil(n / 64)], zeroed), None for the one not asked for; fill: what end holds before the call"""
+    end = None if not want_end else np.empty(n, np.uint32) if fill is None else np.full(n, fill, np.uint32)
+    return end, np.zeros((n + 63) // 64, np.uint64) if want_bitmap else None
+
+
+def _inputs(data, lens=None, off=None):
+    """a batch as the fronts take it -> (data u8, lens u32 or None, off u64 or None, n, stride): [n][stride] rows (+ lens), or
+    with off (n + 1 offsets) the packed bytes, stride 0"""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    if lens is not None:
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    if off is None:
+        return (data, lens, None) + data.shape
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    return data, lens, off, len(off) - 1, 0
+
+
+# ---- the host fronts HipDfa and HipNode share: fn names the entry point, h is the handle ------------------------------------
+
+def _exec_rows(fn, h, data, lens, want_bitmap=True):
+    """(end u32 [n], bitmap u64 [ceil(n / 64)] or None) of [n][stride] rows"""
+    data, lens, _, n, stride = _inputs(data, lens)
+    end, bm = _outputs(n, True, want_bitmap)
+    _call(fn, h, _ptr(data), stride, _ptr(lens), n, _ptr(end), _ptr(bm))
+    return end, bm
+
+
+def _exec_packed(fn, h, base, meta, dtype, want_bitmap=True, want_end=True):
+    """(end or None, bitmap or None) of packed inputs; meta: n + 1 offsets, or (u32, a *_lengths front) n lengths"""
+    base = np.ascontiguousarray(base, dtype=np.uint8)
+    meta = np.ascontiguousarray(meta, dtype=dtype)
+    n = len(meta) - (0 if fn.endswith("_lengths") else 1)
+    end, bm = _outputs(n, want_end, want_bitmap)
+    _call(fn, h, _ptr0(base), _ptr0(meta), n, _ptr(end), _ptr(bm))
+    return end, bm
+
+
+def _exec_rows_ids(fn, h, data, mode, lens):
+    data, lens, _, n, stride = _inputs(data, lens)
+    out = np.empty(n, dtype=np.uint32)
+    _call(fn, h, _ptr(data), stride, _ptr(lens), n, mode, _ptr(out))
+    return out
 
 
 @dataclass
@@ -229,56 +436,34 @@ class FlatDfa:
 
     def write_c(self, path: str):
         """fsm_hip_desc_write(): the library's own on-disk form ("FSMHIP01")."""
-        lib = load_library()
-        libc = C.CDLL(None, use_errno=True)
-        libc.fopen.restype = C.c_void_p
-        f = libc.fopen(path.encode(), b"wb")
-        assert f
         d = self.desc()
-        r = lib.fsm_hip_desc_write(C.byref(d), C.c_void_p(f))
-        libc.fclose(C.c_void_p(f))
-        if r != 0:
-            raise _oserr("fsm_hip_desc_write")
+        with _fopen(path, b"wb") as f:
+            _call("fsm_hip_desc_write", C.byref(d), f)
 
     @classmethod
-    def read_c(cls, path: str) -> "FlatDfa":
-        lib = load_library()
-        libc = C.CDLL(None, use_errno=True)
-        libc.fopen.restype = C.c_void_p
-        f = libc.fopen(path.encode(), b"rb")
-        if not f:
-            raise OSError(C.get_errno(), "fopen")
-        C.set_errno(0)
-        d = lib.fsm_hip_desc_read(C.c_void_p(f))
-        libc.fclose(C.c_void_p(f))
-        if not d:
-            raise _oserr("fsm_hip_desc_read")
+    def _take(cls, d) -> "FlatDfa":
+        """a copy of a description the library returned, which is freed"""
         try:
             return cls.from_desc(d.contents)
         finally:
-            lib.fsm_hip_desc_free(d)
+            load_library().fsm_hip_desc_free(d)
+
+    @classmethod
+    def read_c(cls, path: str) -> "FlatDfa":
+        with _fopen(path, b"rb") as f:
+            return cls._take(_call("fsm_hip_desc_read", f))
 
     @classmethod
     def from_strings(cls, words: Sequence[bytes], flags: int = 0, endids: Optional[Sequence[int]] = None) -> "FlatDfa":
         """fsm_hip_strings_*(): literal set -> DFA, the automaton libre's re_strings builds
         (flags: 1 anchor left, 2 anchor right, 4 AC automaton; endids: one per word or None)."""
         lib = load_library()
-        g = lib.fsm_hip_strings_new()
-        if not g:
-            raise _oserr("fsm_hip_strings_new")
+        g = _call("fsm_hip_strings_new")
         try:
             for i, w in enumerate(words):
-                eid = C.byref(C.c_uint32(int(endids[i]))) if endids is not None else None
-                if not lib.fsm_hip_strings_add_raw(g, w, len(w), C.cast(eid, C.POINTER(C.c_uint32)) if eid is not None else None):
+                if not lib.fsm_hip_strings_add_raw(g, w, len(w), C.byref(C.c_uint32(int(endids[i]))) if endids is not None else None):
                     raise _oserr("fsm_hip_strings_add_raw")
-            C.set_errno(0)
-            d = lib.fsm_hip_strings_build(g, flags)
-            if not d:
-                raise _oserr("fsm_hip_strings_build")
-            try:
-                return cls.from_desc(d.contents)
-            finally:
-                lib.fsm_hip_desc_free(d)
+            return cls._take(_call("fsm_hip_strings_build", g, flags))
         finally:
             lib.fsm_hip_strings_free(g)
 
@@ -322,13 +507,9 @@ class Plan:
                  comb_rng=(23, np.uint16), lazy=(24, np.uint32), glob_tab16=(25, np.uint16), glob16_rank=(26, np.uint32), glob16_fin=(27, np.uint32))
 
     def __init__(self, flat: FlatDfa, flags: int = 0, lds_limit: int = 0):
-        lib = load_library()
-        C.set_errno(0)
+        self._lib = load_library()
         d = flat.desc()
-        self._h = lib.fsm_hip_plan_create(C.byref(d), flags, lds_limit)
-        if not self._h:
-            raise _oserr("fsm_hip_plan_create")
-        self._lib = lib
+        self._h = _call("fsm_hip_plan_create", C.byref(d), flags, lds_limit)
         s = self.get("scalars")
         (self.nstates, self.S1, self.start, self.C, self.abs_min, self.nabsorbing, self.layout, self.row_bytes,
          self.comb_abs_min_off, self.comb256_abs_min_off, self.comb256_dflt, self.eager_lo_end,
@@ -338,8 +519,7 @@ class Plan:
     def get(self, what: str) -> np.ndarray:
         w, dt = self._WHAT[what]
         p, n = C.c_void_p(), C.c_size_t()
-        if self._lib.fsm_hip_plan_get(self._h, w, C.byref(p), C.byref(n)) != 0:
-            raise _oserr("fsm_hip_plan_get")
+        _call("fsm_hip_plan_get", self._h, w, C.byref(p), C.byref(n))
         if n.value == 0:
             return np.zeros(0, dt)
         buf = (C.c_char * (n.value * np.dtype(dt).itemsize)).from_address(p.value)
@@ -360,21 +540,13 @@ class HipDfa:
         if handle is not None:
             self._h = handle
         else:
-            C.set_errno(0)
             d = flat.desc()
-            self._h = self._lib.fsm_hip_dfa_create(C.byref(d), flags)
-            if not self._h:
-                raise _oserr("fsm_hip_dfa_create")
+            self._h = _call("fsm_hip_dfa_create", C.byref(d), flags)
 
     @classmethod
     def compile_fsm(cls, fsm_ptr: int, flags: int = 0) -> "HipDfa":
         """fsm_hip_compile(const struct fsm *): libfsm must already be loaded RTLD_GLOBAL."""
-        lib = load_library()
-        C.set_errno(0)
-        h = lib.fsm_hip_compile(fsm_ptr, flags)
-        if not h:
-            raise _oserr("fsm_hip_compile")
-        return cls(handle=h)
+        return cls(handle=_call("fsm_hip_compile", fsm_ptr, flags))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -390,328 +562,177 @@ class HipDfa:
 
     def info(self) -> dict:
         i = _Info()
-        if self._lib.fsm_hip_dfa_info(self._h, C.byref(i)) != 0:
-            raise _oserr("fsm_hip_dfa_info")
+        _call("fsm_hip_dfa_info", self._h, C.byref(i))
         d = {k: getattr(i, k) for k, _ in _Info._fields_ if k != "reserved"}
         d["layout_name"] = LAYOUT_NAMES.get(i.layout, "?")
         return d
 
     def tune(self, knob: int, value: int):
-        if self._lib.fsm_hip_dfa_tune(self._h, knob, value) != 0:
-            raise _oserr("fsm_hip_dfa_tune")
+        _call("fsm_hip_dfa_tune", self._h, knob, value)
 
     # ---- host-buffer fronts -------------------------------------------------
     def exec_batch(self, data: np.ndarray, lens: Optional[np.ndarray] = None, want_bitmap: bool = True):
         """data: uint8 [n, stride]; returns (end u32[n], bitmap u64[ceil(n/64)])."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        n, stride = data.shape
-        end = np.empty(n, dtype=np.uint32)
-        bm = np.zeros((n + 63) // 64, dtype=np.uint64) if want_bitmap else None
-        if lens is not None:
-            lens = np.ascontiguousarray(lens, dtype=np.uint32)
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch(self._h, _ptr(data), stride, _ptr(lens), n, _ptr(end), _ptr(bm)) != 0:
-            raise _oserr("fsm_hip_exec_batch")
-        return end, bm
+        return _exec_rows("fsm_hip_exec_batch", self._h, data, lens, want_bitmap)
 
     def exec_batch_offsets(self, base: np.ndarray, off: np.ndarray, want_bitmap: bool = True):
-        base = np.ascontiguousarray(base, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.uint64)
-        n = len(off) - 1
-        end = np.empty(n, dtype=np.uint32)
-        bm = np.zeros((n + 63) // 64, dtype=np.uint64) if want_bitmap else None
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_offsets(self._h, _ptr(base) if len(base) else None, _ptr(off), n, _ptr(end), _ptr(bm)) != 0:
-            raise _oserr("fsm_hip_exec_batch_offsets")
-        return end, bm
+        return _exec_packed("fsm_hip_exec_batch_offsets", self._h, base, off, np.uint64, want_bitmap)
 
     def exec_batch_offsets32(self, base: np.ndarray, off32: np.ndarray, want_bitmap: bool = True, want_end: bool = True):
         """fsm_hip_exec_batch_offsets32: u32 offsets (batches below 4 GiB)."""
-        base = np.ascontiguousarray(base, dtype=np.uint8)
-        off32 = np.ascontiguousarray(off32, dtype=np.uint32)
-        n = len(off32) - 1
-        end = np.empty(n, dtype=np.uint32) if want_end else None
-        bm = np.zeros((n + 63) // 64, dtype=np.uint64) if want_bitmap else None
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_offsets32(C.c_void_p(self._h), C.c_void_p(base.ctypes.data if len(base) else None), C.c_void_p(off32.ctypes.data),
-                                                  C.c_size_t(n), C.c_void_p(end.ctypes.data if want_end else None), C.c_void_p(bm.ctypes.data if want_bitmap else None)) != 0:
-            raise _oserr("fsm_hip_exec_batch_offsets32")
-        return end, bm
+        return _exec_packed("fsm_hip_exec_batch_offsets32", self._h, base, off32, np.uint32, want_bitmap, want_end)
 
     def exec_batch_lengths(self, base: np.ndarray, lens: np.ndarray, want_bitmap: bool = True, want_end: bool = True):
         """fsm_hip_exec_batch_lengths: inputs packed back to back, their lengths and nothing else."""
-        base = np.ascontiguousarray(base, dtype=np.uint8)
-        lens = np.ascontiguousarray(lens, dtype=np.uint32)
-        n = len(lens)
-        end = np.empty(n, dtype=np.uint32) if want_end else None
-        bm = np.zeros((n + 63) // 64, dtype=np.uint64) if want_bitmap else None
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_lengths(C.c_void_p(self._h), C.c_void_p(base.ctypes.data if len(base) else None), C.c_void_p(lens.ctypes.data if n else None),
-                                                C.c_size_t(n), C.c_void_p(end.ctypes.data if want_end else None), C.c_void_p(bm.ctypes.data if want_bitmap else None)) != 0:
-            raise _oserr("fsm_hip_exec_batch_lengths")
-        return end, bm
+        return _exec_packed("fsm_hip_exec_batch_lengths", self._h, base, lens, np.uint32, want_bitmap, want_end)
 
     def exec_batch_offsets32_device(self, d_base: int, d_off32: int, n: int, d_end: int = 0, d_bitmap: int = 0, stream: int = 0):
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_offsets32_device(C.c_void_p(self._h), C.c_void_p(d_base), C.c_void_p(d_off32), C.c_size_t(n), C.c_void_p(d_end or None),
-                                                         C.c_void_p(d_bitmap or None), C.c_void_p(stream or None)) != 0:
-            raise _oserr("fsm_hip_exec_batch_offsets32_device")
+        _call("fsm_hip_exec_batch_offsets32_device", self._h, d_base, d_off32, n, d_end or None, d_bitmap or None, stream or None)
 
     def exec_batch_lengths_device(self, d_base: int, d_len: int, n: int, d_end: int = 0, d_bitmap: int = 0, stream: int = 0):
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_lengths_device(C.c_void_p(self._h), C.c_void_p(d_base), C.c_void_p(d_len), C.c_size_t(n), C.c_void_p(d_end or None),
-                                                       C.c_void_p(d_bitmap or None), C.c_void_p(stream or None)) != 0:
-            raise _oserr("fsm_hip_exec_batch_lengths_device")
+        _call("fsm_hip_exec_batch_lengths_device", self._h, d_base, d_len, n, d_end or None, d_bitmap or None, stream or None)
 
     def exec_strings(self, strings: Sequence[bytes]):
-        off = np.zeros(len(strings) + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(s) for s in strings])
-        base = np.frombuffer(b"".join(strings), dtype=np.uint8)
-        return self.exec_batch_offsets(base, off)
+        return self.exec_batch_offsets(*_pack_strings(strings))
 
     def match_buffer(self, s: bytes) -> int:
-        C.set_errno(0)
-        r = self._lib.fsm_hip_match_buffer(self._h, s, len(s))
-        if r < 0:
-            raise _oserr("fsm_hip_match_buffer")
-        return r
+        return _call("fsm_hip_match_buffer", self._h, s, len(s), negative_only=True)
 
     # ---- device-pointer front (raw addresses, e.g. torch tensors' data_ptr()) ----
     def exec_batch_device(self, d_base: int, stride: int, n: int, d_end: int = 0, d_bitmap: int = 0, d_len: int = 0, stream: int = 0):
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_device(self._h, d_base, stride, d_len or None, n, d_end or None, d_bitmap or None, stream or None) != 0:
-            raise _oserr("fsm_hip_exec_batch_device")
+        _call("fsm_hip_exec_batch_device", self._h, d_base, stride, d_len or None, n, d_end or None, d_bitmap or None, stream or None)
 
     def last_kernel_name(self) -> str:
-        self._lib.fsm_hip_last_kernel_name.restype = C.c_char_p
-        return (self._lib.fsm_hip_last_kernel_name(C.c_void_p(self._h)) or b"").decode()
+        return (self._lib.fsm_hip_last_kernel_name(self._h) or b"").decode()
 
     def exec_batch_eager_device(self, d_base: int, stride: int, n: int, d_end: int, d_sets: int, d_len: int = 0, stream: int = 0):
         """d_sets: n * eager_words() u64 on the device."""
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_eager_device(C.c_void_p(self._h), C.c_void_p(d_base), C.c_size_t(stride), C.c_void_p(d_len or None),
-                                                     C.c_size_t(n), C.c_void_p(d_end or None), C.c_void_p(d_sets), C.c_void_p(stream or None)) != 0:
-            raise _oserr("fsm_hip_exec_batch_eager_device")
+        _call("fsm_hip_exec_batch_eager_device", self._h, d_base, stride, d_len or None, n, d_end or None, d_sets, stream or None)
 
     def eager_words(self) -> int:
-        self._lib.fsm_hip_eager_words.restype = C.c_size_t
-        return int(self._lib.fsm_hip_eager_words(C.c_void_p(self._h)))
+        return int(self._lib.fsm_hip_eager_words(self._h))
 
     def exec_batch_offsets_device(self, d_base: int, d_off: int, n: int, d_end: int = 0, d_bitmap: int = 0, stream: int = 0):
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_offsets_device(self._h, d_base, d_off, n, d_end or None, d_bitmap or None, stream or None) != 0:
-            raise _oserr("fsm_hip_exec_batch_offsets_device")
+        _call("fsm_hip_exec_batch_offsets_device", self._h, d_base, d_off, n, d_end or None, d_bitmap or None, stream or None)
 
     def exec_batch_ids(self, data: np.ndarray, mode: int, lens: Optional[np.ndarray] = None) -> np.ndarray:
         """Device-side end-id delivery: mode 1 = lowest id (AMBIG_EARLIEST), 2 = index into ret sets, 3 = AMBIG_ERROR."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        n, stride = data.shape
-        out = np.empty(n, dtype=np.uint32)
-        if lens is not None:
-            lens = np.ascontiguousarray(lens, dtype=np.uint32)
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_ids(C.c_void_p(self._h), _ptr(data), C.c_size_t(stride), _ptr(lens), C.c_size_t(n),
-                                            C.c_int(mode), _ptr(out)) != 0:
-            raise _oserr("fsm_hip_exec_batch_ids")
-        return out
+        return _exec_rows_ids("fsm_hip_exec_batch_ids", self._h, data, mode, lens)
 
     def exec_batch_resume(self, data: np.ndarray, state_io: np.ndarray, lens: Optional[np.ndarray] = None):
         """Streaming: start row i from state_io[i] (START/DEAD/state id); returns (state_out, end)."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        n, stride = data.shape
+        data, lens, _, n, stride = _inputs(data, lens)
         st = np.ascontiguousarray(state_io, dtype=np.uint32).copy()
         end = np.empty(n, dtype=np.uint32)
-        if lens is not None:
-            lens = np.ascontiguousarray(lens, dtype=np.uint32)
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_resume(C.c_void_p(self._h), _ptr(data), C.c_size_t(stride), _ptr(lens), C.c_size_t(n),
-                                               _ptr(st), _ptr(end)) != 0:
-            raise _oserr("fsm_hip_exec_batch_resume")
+        _call("fsm_hip_exec_batch_resume", self._h, _ptr(data), stride, _ptr(lens), n, _ptr(st), _ptr(end))
         return st, end
 
     def exec_batch_eager(self, data: np.ndarray, lens: Optional[np.ndarray] = None):
         """Walk + eager outputs: returns (end u32[n], list of emitted-id arrays per input)."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        n, stride = data.shape
-        end = np.empty(n, dtype=np.uint32)
-        self._lib.fsm_hip_eager_words.restype = C.c_size_t
-        W = self._lib.fsm_hip_eager_words(C.c_void_p(self._h))
-        eo = np.zeros((n, W), dtype=np.uint64)
-        if lens is not None:
-            lens = np.ascontiguousarray(lens, dtype=np.uint32)
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_eager(C.c_void_p(self._h), _ptr(data), C.c_size_t(stride), _ptr(lens), C.c_size_t(n),
-                                              _ptr(end), _ptr(eo)) != 0:
-            raise _oserr("fsm_hip_exec_batch_eager")
-        self._lib.fsm_hip_eager_id_count.restype = C.c_size_t
-        self._lib.fsm_hip_eager_id.restype = C.c_uint32
-        k = self._lib.fsm_hip_eager_id_count(C.c_void_p(self._h))
-        ids = np.array([self._lib.fsm_hip_eager_id(C.c_void_p(self._h), C.c_uint(b)) for b in range(k)], np.uint32)
-        bits = np.unpackbits(eo.view(np.uint8).reshape(n, W * 8), axis=1, bitorder="little")[:, :k].astype(bool)
-        sets = [ids[row] for row in bits]
-        return end, sets
+        data, lens, _, n, stride = _inputs(data, lens)
+        end, eo = np.empty(n, dtype=np.uint32), np.zeros((n, self.eager_words()), dtype=np.uint64)
+        _call("fsm_hip_exec_batch_eager", self._h, _ptr(data), stride, _ptr(lens), n, _ptr(end), _ptr(eo))
+        return end, self._decode(eo)
 
     def exec_eager_words(self, data: np.ndarray, lens: Optional[np.ndarray] = None, off: Optional[np.ndarray] = None, want_end: bool = True,
                          eager_out: Optional[np.ndarray] = None, null_sets: bool = False):
         """fsm_hip_exec_batch_eager (data: [n][stride] rows, + lens) or, with off (n + 1 u64 offsets), fsm_hip_exec_batch_eager_offsets
         (data: the packed bytes), with the sets as the library writes them: returns (end or None, u64 [n][eager_words()]).
         eager_out: the caller's own array, written in place; null_sets: NULL is passed for the sets (the fronts refuse it)."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        if off is not None:
-            off = np.ascontiguousarray(off, dtype=np.uint64)
-            n = len(off) - 1
-        else:
-            n, stride = data.shape
+        data, lens, off, n, stride = _inputs(data, lens, off)
         end = np.empty(n, dtype=np.uint32) if want_end else None
         eo = None if null_sets else eager_out if eager_out is not None else np.zeros((n, self.eager_words()), dtype=np.uint64)
-        if lens is not None:
-            lens = np.ascontiguousarray(lens, dtype=np.uint32)
-        C.set_errno(0)
-        vp = C.c_void_p
         if off is not None:
-            r = self._lib.fsm_hip_exec_batch_eager_offsets(vp(self._h), vp(data.ctypes.data if data.size else None), _ptr(off), C.c_size_t(n), _ptr(end), _ptr(eo))
+            _call("fsm_hip_exec_batch_eager_offsets", self._h, _ptr0(data), _ptr(off), n, _ptr(end), _ptr(eo))
         else:
-            r = self._lib.fsm_hip_exec_batch_eager(vp(self._h), vp(data.ctypes.data if data.size else None), C.c_size_t(stride), _ptr(lens), C.c_size_t(n), _ptr(end), _ptr(eo))
-        if r != 0:
-            raise _oserr("fsm_hip_exec_batch_eager" + ("_offsets" if off is not None else ""))
+            _call("fsm_hip_exec_batch_eager", self._h, _ptr0(data), stride, _ptr(lens), n, _ptr(end), _ptr(eo))
         return end, eo
 
     def exec_batch_eager_offsets_device(self, d_base: int, d_off: int, n: int, d_end: int, d_sets: int, stream: int = 0):
         """fsm_hip_exec_batch_eager_offsets_device; d_sets: n * eager_words() u64 on the device"""
-        C.set_errno(0)
-        vp = C.c_void_p
-        if self._lib.fsm_hip_exec_batch_eager_offsets_device(vp(self._h), vp(d_base or None), vp(d_off or None), C.c_size_t(n), vp(d_end or None), vp(d_sets or None),
-                                                             vp(stream or None)) != 0:
-            raise _oserr("fsm_hip_exec_batch_eager_offsets_device")
+        _call("fsm_hip_exec_batch_eager_offsets_device", self._h, d_base or None, d_off or None, n, d_end or None, d_sets or None, stream or None)
 
     def exec_batch_eager_trace(self, data: np.ndarray, lens: Optional[np.ndarray] = None, off: Optional[np.ndarray] = None, cap: int = 64):
         """fsm_exec's eager-output callback stream per input, order and repeats kept: (end u32[n], count u32[n],
         [(ids, positions) of the first min(count, cap) emissions]).  data: (n, stride) rows (+ lens), or a flat byte
         array with off[n + 1]."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        if off is not None:
-            off = np.ascontiguousarray(off, dtype=np.uint64)
-            n, stride = len(off) - 1, 0
-        else:
-            n, stride = data.shape
-        if lens is not None:
-            lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        data, lens, off, n, stride = _inputs(data, lens, off)
         end, cnt = np.empty(n, np.uint32), np.zeros(n, np.uint32)
         ids, pos = np.zeros((n, max(cap, 1)), np.uint32), np.zeros((n, max(cap, 1)), np.uint32)
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_eager_trace(C.c_void_p(self._h), _ptr(data) if data.size else None, C.c_size_t(stride), _ptr(lens), _ptr(off),
-                                                    C.c_size_t(n), C.c_size_t(cap), _ptr(end), _ptr(cnt), _ptr(ids), _ptr(pos)) != 0:
-            raise _oserr("fsm_hip_exec_batch_eager_trace")
+        _call("fsm_hip_exec_batch_eager_trace", self._h, _ptr0(data), stride, _ptr(lens), _ptr(off), n, cap, _ptr(end), _ptr(cnt), _ptr(ids), _ptr(pos))
         k = np.minimum(cnt, cap)
         return end, cnt, [(ids[i, :k[i]].copy(), pos[i, :k[i]].copy()) for i in range(n)]
 
     def exec_batch_eager_trace_device(self, d_base: int, stride: int, n: int, cap: int, d_count: int, d_ids: int, d_pos: int = 0, d_end: int = 0,
                                       d_len: int = 0, d_off: int = 0, stream: int = 0):
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_eager_trace_device(C.c_void_p(self._h), C.c_void_p(d_base or None), C.c_size_t(stride), C.c_void_p(d_len or None),
-                                                           C.c_void_p(d_off or None), C.c_size_t(n), C.c_size_t(cap), C.c_void_p(d_end or None),
-                                                           C.c_void_p(d_count), C.c_void_p(d_ids or None), C.c_void_p(d_pos or None), C.c_void_p(stream or None)) != 0:
-            raise _oserr("fsm_hip_exec_batch_eager_trace_device")
+        _call("fsm_hip_exec_batch_eager_trace_device", self._h, d_base or None, stride, d_len or None, d_off or None, n, cap, d_end or None,
+              d_count, d_ids or None, d_pos or None, stream or None)
 
     def exec_packed_all_form(self, base: np.ndarray, meta_form: int, meta: np.ndarray, n: int, ids_mode: int = 0, want_end=True, want_bitmap=False,
                              want_eager=False):
         """fsm_hip_exec_batch_packed_all: returns dict(end=, bitmap=, ids=, eager=) with the outputs asked for."""
         base = np.ascontiguousarray(base, dtype=np.uint8)
         meta = np.ascontiguousarray(meta, dtype=np.uint64 if meta_form == 0 else np.uint32)
-        end = np.empty(n, np.uint32) if want_end else None
-        bm = np.zeros((n + 63) // 64, np.uint64) if want_bitmap else None
+        end, bm = _outputs(n, want_end, want_bitmap)
         ids = np.empty(n, np.uint32) if ids_mode else None
-        W = self.eager_words()
-        eo = np.zeros((n, W), np.uint64) if want_eager else None
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_packed_all(C.c_void_p(self._h), _ptr(base) if base.size else None, C.c_int(meta_form), _ptr(meta), C.c_size_t(n),
-                                                   _ptr(end), _ptr(bm), C.c_int(ids_mode), _ptr(ids), _ptr(eo)) != 0:
-            raise _oserr("fsm_hip_exec_batch_packed_all")
+        eo = np.zeros((n, self.eager_words()), np.uint64) if want_eager else None
+        _call("fsm_hip_exec_batch_packed_all", self._h, _ptr0(base), meta_form, _ptr(meta), n, _ptr(end), _ptr(bm), ids_mode, _ptr(ids), _ptr(eo))
         return {"end": end, "bitmap": bm, "ids": ids, "eager": eo}
 
     def exec_packed_all_device(self, d_base: int, meta_form: int, d_meta: int, n: int, d_end: int = 0, d_bitmap: int = 0, ids_mode: int = 0, d_ids: int = 0,
                                d_eager: int = 0, stream: int = 0):
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_packed_all_device(C.c_void_p(self._h), C.c_void_p(d_base or None), C.c_int(meta_form), C.c_void_p(d_meta or None), C.c_size_t(n),
-                                                          C.c_void_p(d_end or None), C.c_void_p(d_bitmap or None), C.c_int(ids_mode), C.c_void_p(d_ids or None),
-                                                          C.c_void_p(d_eager or None), C.c_void_p(stream or None)) != 0:
-            raise _oserr("fsm_hip_exec_batch_packed_all_device")
+        _call("fsm_hip_exec_batch_packed_all_device", self._h, d_base or None, meta_form, d_meta or None, n, d_end or None, d_bitmap or None, ids_mode,
+              d_ids or None, d_eager or None, stream or None)
 
     # ---- the same three fronts over packed inputs (base + off[n + 1]) -----------
     def exec_offsets_ids(self, base: np.ndarray, off: np.ndarray, mode: int) -> np.ndarray:
-        base = np.ascontiguousarray(base, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.uint64)
-        n = len(off) - 1
+        base, _, off, n, _ = _inputs(base, None, off)
         out = np.empty(n, dtype=np.uint32)
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_ids_offsets(C.c_void_p(self._h), _ptr(base) if len(base) else None, _ptr(off), C.c_size_t(n),
-                                                    C.c_int(mode), _ptr(out)) != 0:
-            raise _oserr("fsm_hip_exec_batch_ids_offsets")
+        _call("fsm_hip_exec_batch_ids_offsets", self._h, _ptr0(base), _ptr(off), n, mode, _ptr(out))
         return out
+
+    def _eager_ids(self) -> np.ndarray:
+        """the id of every bit of a set, in bit order"""
+        return np.array([self._lib.fsm_hip_eager_id(self._h, b) for b in range(self._lib.fsm_hip_eager_id_count(self._h))], np.uint32)
+
+    def _decode(self, eo: np.ndarray) -> list:
+        """u64 [n][W] sets -> per input the ids emitted, ascending"""
+        ids = self._eager_ids()
+        bits = np.unpackbits(eo.view(np.uint8), axis=1, bitorder="little")[:, :len(ids)].astype(bool)
+        return [ids[row] for row in bits]
 
     def _eager_ids_of(self, words: np.ndarray) -> np.ndarray:
         """a W-word set -> the sorted ids it holds"""
-        self._lib.fsm_hip_eager_id_count.restype = C.c_size_t
-        self._lib.fsm_hip_eager_id.restype = C.c_uint32
-        k = self._lib.fsm_hip_eager_id_count(C.c_void_p(self._h))
-        bits = np.unpackbits(np.ascontiguousarray(words, np.uint64).view(np.uint8), bitorder="little")[:k].astype(bool)
-        return np.array(sorted(self._lib.fsm_hip_eager_id(C.c_void_p(self._h), C.c_uint(b)) for b in np.nonzero(bits)[0]), np.uint32)
+        return np.sort(self._decode(np.ascontiguousarray(words, np.uint64).reshape(1, -1))[0])
 
     def decode_eager(self, words: np.ndarray) -> list:
         """n * eager_words() u64 as the eager fronts write them -> per input the ids emitted, ascending (what exec_batch_eager returns)"""
-        W = self.eager_words()
-        eo = np.ascontiguousarray(words, np.uint64).reshape(-1, W)
-        self._lib.fsm_hip_eager_id_count.restype = C.c_size_t
-        self._lib.fsm_hip_eager_id.restype = C.c_uint32
-        k = self._lib.fsm_hip_eager_id_count(C.c_void_p(self._h))
-        ids = np.array([self._lib.fsm_hip_eager_id(C.c_void_p(self._h), C.c_uint(b)) for b in range(k)], np.uint32)
-        bits = np.unpackbits(eo.view(np.uint8).reshape(len(eo), W * 8), axis=1, bitorder="little")[:, :k].astype(bool)
-        return [ids[row] for row in bits]
+        return self._decode(np.ascontiguousarray(words, np.uint64).reshape(-1, self.eager_words()))
 
     def exec_batch_eager_resume(self, data: np.ndarray, state_io: np.ndarray, eager_io: Optional[np.ndarray], lens: Optional[np.ndarray] = None,
                                 off: Optional[np.ndarray] = None, want_end: bool = True):
         """fsm_hip_exec_batch_eager_resume: one more piece of every input.  data: [n][stride] rows (+ lens), or with off (n + 1
         u64 offsets) the packed bytes.  eager_io: n * eager_words() u64 (zeroed before a stream's first piece), OR-ed into.
         Returns (state_out, end, eager_io) -- new arrays; the arguments are left as they are."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        if off is not None:
-            off = np.ascontiguousarray(off, dtype=np.uint64)
-            n, stride = len(off) - 1, 0
-        else:
-            n, stride = data.shape
+        data, lens, off, n, stride = _inputs(data, lens, off)
         st = np.ascontiguousarray(state_io, dtype=np.uint32).copy() if state_io is not None else None
         eo = np.ascontiguousarray(eager_io, dtype=np.uint64).copy() if eager_io is not None else None   # (None: NULL, which the front refuses)
         if eo is not None and eo.size != n * self.eager_words():
             raise ValueError("eager_io needs n * eager_words() words")
         end = np.empty(n, dtype=np.uint32) if want_end else None
-        if lens is not None:
-            lens = np.ascontiguousarray(lens, dtype=np.uint32)
-        C.set_errno(0)
-        vp = C.c_void_p
-        if self._lib.fsm_hip_exec_batch_eager_resume(vp(self._h), vp(data.ctypes.data if data.size else None), C.c_size_t(stride), _ptr(lens),
-                                                     _ptr(off), C.c_size_t(n), _ptr(st), _ptr(end), _ptr(eo)) != 0:
-            raise _oserr("fsm_hip_exec_batch_eager_resume")
+        _call("fsm_hip_exec_batch_eager_resume", self._h, _ptr0(data), stride, _ptr(lens), _ptr(off), n, _ptr(st), _ptr(end), _ptr(eo))
         return st, end, eo
 
     def exec_batch_eager_resume_device(self, d_base: int, stride: int, n: int, d_state_io: int, d_eager_io: int, d_len: int = 0, d_off: int = 0,
                                        d_end: int = 0, stream: int = 0):
-        C.set_errno(0)
-        vp = C.c_void_p
-        if self._lib.fsm_hip_exec_batch_eager_resume_device(vp(self._h), vp(d_base or None), C.c_size_t(stride), vp(d_len or None), vp(d_off or None),
-                                                            C.c_size_t(n), vp(d_state_io or None), vp(d_end or None), vp(d_eager_io or None),
-                                                            vp(stream or None)) != 0:
-            raise _oserr("fsm_hip_exec_batch_eager_resume_device")
+        _call("fsm_hip_exec_batch_eager_resume_device", self._h, d_base or None, stride, d_len or None, d_off or None, n, d_state_io or None,
+              d_end or None, d_eager_io or None, stream or None)
 
     def exec_offsets_resume(self, base: np.ndarray, off: np.ndarray, state_io: np.ndarray):
-        base = np.ascontiguousarray(base, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.uint64)
-        n = len(off) - 1
+        base, _, off, n, _ = _inputs(base, None, off)
         st = np.ascontiguousarray(state_io, dtype=np.uint32).copy()
         end = np.empty(n, dtype=np.uint32)
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_resume_offsets(C.c_void_p(self._h), _ptr(base) if len(base) else None, _ptr(off), C.c_size_t(n),
-                                                       _ptr(st), _ptr(end)) != 0:
-            raise _oserr("fsm_hip_exec_batch_resume_offsets")
+        _call("fsm_hip_exec_batch_resume_offsets", self._h, _ptr0(base), _ptr(off), n, _ptr(st), _ptr(end))
         return st, end
 
     def exec_packed_resume(self, base: np.ndarray, meta_form: int, meta: np.ndarray, n: int, state_io: np.ndarray):
@@ -720,115 +741,60 @@ class HipDfa:
         meta = np.ascontiguousarray(meta)
         st = np.ascontiguousarray(state_io, dtype=np.uint32).copy()
         end = np.empty(n, dtype=np.uint32)
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_resume_packed(C.c_void_p(self._h), C.c_void_p(base.ctypes.data if len(base) else None), C.c_int(meta_form),
-                                                      C.c_void_p(meta.ctypes.data if len(meta) else None), C.c_size_t(n), _ptr(st), _ptr(end)) != 0:
-            raise _oserr("fsm_hip_exec_batch_resume_packed")
+        _call("fsm_hip_exec_batch_resume_packed", self._h, _ptr0(base), meta_form, _ptr0(meta), n, _ptr(st), _ptr(end))
         return st, end
 
     def exec_packed_resume_device(self, d_base: int, meta_form: int, d_meta: int, n: int, d_state_io: int, d_end: int = 0, d_bitmap: int = 0, stream: int = 0):
-        C.set_errno(0)
-        vp = C.c_void_p
-        if self._lib.fsm_hip_exec_batch_resume_packed_device(vp(self._h), vp(d_base or None), C.c_int(meta_form), vp(d_meta or None), C.c_size_t(n), vp(d_state_io),
-                                                             vp(d_end or None), vp(d_bitmap or None), vp(stream or None)) != 0:
-            raise _oserr("fsm_hip_exec_batch_resume_packed_device")
+        _call("fsm_hip_exec_batch_resume_packed_device", self._h, d_base or None, meta_form, d_meta or None, n, d_state_io, d_end or None,
+              d_bitmap or None, stream or None)
 
     def reserve(self, n: int):
         """fsm_hip_reserve: allocate now what batches of up to n inputs would allocate later (graph capture from the first launch)."""
-        C.set_errno(0)
-        if self._lib.fsm_hip_reserve(C.c_void_p(self._h), C.c_size_t(n)) != 0:
-            raise _oserr("fsm_hip_reserve")
+        _call("fsm_hip_reserve", self._h, n)
 
     def exec_offsets_eager(self, base: np.ndarray, off: np.ndarray):
-        base = np.ascontiguousarray(base, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.uint64)
-        n = len(off) - 1
-        end = np.empty(n, dtype=np.uint32)
-        self._lib.fsm_hip_eager_words.restype = C.c_size_t
-        W = self._lib.fsm_hip_eager_words(C.c_void_p(self._h))
-        eo = np.zeros((n, W), dtype=np.uint64)
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_batch_eager_offsets(C.c_void_p(self._h), _ptr(base) if len(base) else None, _ptr(off), C.c_size_t(n),
-                                                      _ptr(end), _ptr(eo)) != 0:
-            raise _oserr("fsm_hip_exec_batch_eager_offsets")
-        self._lib.fsm_hip_eager_id_count.restype = C.c_size_t
-        self._lib.fsm_hip_eager_id.restype = C.c_uint32
-        k = self._lib.fsm_hip_eager_id_count(C.c_void_p(self._h))
-        ids = np.array([self._lib.fsm_hip_eager_id(C.c_void_p(self._h), C.c_uint(b)) for b in range(k)], np.uint32)
-        bits = np.unpackbits(eo.view(np.uint8).reshape(n, W * 8), axis=1, bitorder="little")[:, :k].astype(bool)
-        return end, [ids[row] for row in bits]
+        end, eo = self.exec_eager_words(base, off=off)
+        return end, self._decode(eo)
 
     def exec_offsets_device_front(self, what: str, d_base: int, d_off: int, n: int, d_out: int, d_aux: int = 0, mode: int = 1, stream: int = 0):
         """The *_offsets_device entry points: what = 'ids' (d_out = ids), 'resume' (d_out = state_io, d_aux = end), 'eager' (d_out = end, d_aux = sets)."""
-        C.set_errno(0)
-        vp = C.c_void_p
-        if what == "ids":
-            r = self._lib.fsm_hip_exec_batch_ids_offsets_device(vp(self._h), vp(d_base), vp(d_off), C.c_size_t(n), C.c_int(mode), vp(d_out), vp(stream or None))
-        elif what == "resume":
-            r = self._lib.fsm_hip_exec_batch_resume_offsets_device(vp(self._h), vp(d_base), vp(d_off), C.c_size_t(n), vp(d_out), vp(d_aux or None), None, vp(stream or None))
-        else:
-            r = self._lib.fsm_hip_exec_batch_eager_offsets_device(vp(self._h), vp(d_base), vp(d_off), C.c_size_t(n), vp(d_out or None), vp(d_aux), vp(stream or None))
-        if r != 0:
-            raise _oserr("fsm_hip_exec_batch_%s_offsets_device" % what)
+        args = {"ids": (mode, d_out), "resume": (d_out, d_aux or None, None), "eager": (d_out or None, d_aux)}[what]
+        _call("fsm_hip_exec_batch_%s_offsets_device" % what, self._h, d_base, d_off, n, *args, stream or None)
 
     def eager_id_count(self) -> int:
-        self._lib.fsm_hip_eager_id_count.restype = C.c_size_t
-        return int(self._lib.fsm_hip_eager_id_count(C.c_void_p(self._h)))
+        return int(self._lib.fsm_hip_eager_id_count(self._h))
 
     def eager_id(self, bit: int) -> int:
-        self._lib.fsm_hip_eager_id.restype = C.c_uint32
-        return int(self._lib.fsm_hip_eager_id(C.c_void_p(self._h), C.c_uint(bit)))
+        return int(self._lib.fsm_hip_eager_id(self._h, bit))
 
     def ret_sets(self):
         """The de-duplicated end-id sets, in retlist order."""
-        self._lib.fsm_hip_ret_count.restype = C.c_size_t
         out = []
-        for k in range(self._lib.fsm_hip_ret_count(C.c_void_p(self._h))):
+        for k in range(self._lib.fsm_hip_ret_count(self._h)):
             p, n = C.c_void_p(), C.c_size_t()
-            assert self._lib.fsm_hip_ret_get(C.c_void_p(self._h), C.c_uint32(k), C.byref(p), C.byref(n)) == 0
+            assert self._lib.fsm_hip_ret_get(self._h, k, C.byref(p), C.byref(n)) == 0
             out.append(np.frombuffer((C.c_char * (n.value * 4)).from_address(p.value), dtype=np.uint32).copy() if n.value else np.zeros(0, np.uint32))
         return out
 
     def ids_conflict(self):
         """AMBIG_ERROR's check: None, or the lowest end state that carries more than one end-id."""
         st = C.c_uint(0)
-        r = self._lib.fsm_hip_ids_conflict(C.c_void_p(self._h), C.byref(st))
-        if r < 0:
-            raise _oserr("fsm_hip_ids_conflict")
+        r = _call("fsm_hip_ids_conflict", self._h, C.byref(st), negative_only=True)
         return int(st.value) if r == 1 else None
 
     def state_is_absorbing(self, state: int) -> bool:
-        r = self._lib.fsm_hip_state_is_absorbing(C.c_void_p(self._h), C.c_uint32(state))
-        if r < 0:
-            raise _oserr("fsm_hip_state_is_absorbing")
-        return bool(r)
+        return bool(_call("fsm_hip_state_is_absorbing", self._h, state, negative_only=True))
 
     def match_file(self, path: str) -> int:
         """fsm_hip_match_file(dfa, FILE *) on a file opened with the C library."""
-        libc = C.CDLL(None, use_errno=True)
-        libc.fopen.restype = C.c_void_p
-        libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
-        libc.fclose.argtypes = [C.c_void_p]
-        f = libc.fopen(path.encode(), b"rb")
-        if not f:
-            raise OSError(C.get_errno(), "fopen")
-        try:
-            C.set_errno(0)
-            r = self._lib.fsm_hip_match_file(C.c_void_p(self._h), C.c_void_p(f))
-        finally:
-            libc.fclose(f)
-        if r < 0:
-            raise _oserr("fsm_hip_match_file")
-        return r
+        with _fopen(path, b"rb") as f:
+            return _call("fsm_hip_match_file", self._h, f, negative_only=True)
 
     def match_buffer_big(self, data: bytes):
         """fsm_hip_match_buffer_big: (1 / 0, caller's end state or NO_MATCH) of ONE input walked by the whole device."""
         e = C.c_uint32(NO_MATCH)
         buf = (C.c_char * max(len(data), 1)).from_buffer_copy(data if len(data) else b"\0")
-        C.set_errno(0)
-        r = self._lib.fsm_hip_match_buffer_big(C.c_void_p(self._h), buf, C.c_size_t(len(data)), C.byref(e))
-        if r < 0:
-            raise _oserr("fsm_hip_match_buffer_big")
+        r = _call("fsm_hip_match_buffer_big", self._h, buf, len(data), C.byref(e), negative_only=True)
         return r, e.value
 
     def match_buffer_big_eager(self, data: bytes):
@@ -837,30 +803,15 @@ class HipDfa:
         e = C.c_uint32(NO_MATCH)
         eo = np.zeros(self.eager_words(), np.uint64)
         buf = (C.c_char * max(len(data), 1)).from_buffer_copy(data if len(data) else b"\0")
-        C.set_errno(0)
-        r = self._lib.fsm_hip_match_buffer_big_eager(C.c_void_p(self._h), buf, C.c_size_t(len(data)), C.byref(e), _ptr(eo))
-        if r < 0:
-            raise _oserr("fsm_hip_match_buffer_big_eager")
+        r = _call("fsm_hip_match_buffer_big_eager", self._h, buf, len(data), C.byref(e), _ptr(eo), negative_only=True)
         return r, e.value, self._eager_ids_of(eo)
 
     def match_file_eager(self, path: str):
         """fsm_hip_match_file_eager on a file opened with the C library: (1 / 0, end state or NO_MATCH, sorted u32 ids)."""
-        libc = C.CDLL(None, use_errno=True)
-        libc.fopen.restype = C.c_void_p
-        libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
-        libc.fclose.argtypes = [C.c_void_p]
         e = C.c_uint32(NO_MATCH)
         eo = np.zeros(self.eager_words(), np.uint64)
-        f = libc.fopen(path.encode(), b"rb")
-        if not f:
-            raise OSError(C.get_errno(), "fopen")
-        try:
-            C.set_errno(0)
-            r = self._lib.fsm_hip_match_file_eager(C.c_void_p(self._h), C.c_void_p(f), C.byref(e), _ptr(eo))
-        finally:
-            libc.fclose(f)
-        if r < 0:
-            raise _oserr("fsm_hip_match_file_eager")
+        with _fopen(path, b"rb") as f:
+            r = _call("fsm_hip_match_file_eager", self._h, f, C.byref(e), _ptr(eo), negative_only=True)
         return r, e.value, self._eager_ids_of(eo)
 
     def match_last_passes(self):
@@ -886,330 +837,176 @@ class HipNode:
 
     def __init__(self, flat: FlatDfa, devices: Optional[Sequence[int]] = None, flags: int = 0):
         self._lib = load_library()
-        lib = self._lib
-        lib.fsm_hip_node_create.restype = C.c_void_p
-        lib.fsm_hip_node_dfa.restype = C.c_void_p
-        lib.fsm_hip_node_bitmap_words.restype = C.c_size_t
         d = flat.desc()
         devs = (C.c_int * len(devices))(*devices) if devices else None
-        C.set_errno(0)
-        self._h = lib.fsm_hip_node_create(C.byref(d), C.c_uint(flags), devs, C.c_int(len(devices) if devices else 0))
-        if not self._h:
-            raise _oserr("fsm_hip_node_create")
-        self.ndev = int(lib.fsm_hip_node_ndev(C.c_void_p(self._h)))
+        self._h = _call("fsm_hip_node_create", C.byref(d), flags, devs, len(devices) if devices else 0)
+        self.ndev = int(self._lib.fsm_hip_node_ndev(self._h))
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.fsm_hip_node_free(C.c_void_p(self._h))
+            self._lib.fsm_hip_node_free(self._h)
             self._h = None
 
     __del__ = close
 
     def uses_rccl(self) -> bool:
-        return bool(self._lib.fsm_hip_node_uses_rccl(C.c_void_p(self._h)))
+        return bool(self._lib.fsm_hip_node_uses_rccl(self._h))
 
     def rccl_path(self) -> str:
-        self._lib.fsm_hip_node_rccl_path.restype = C.c_char_p
         return (self._lib.fsm_hip_node_rccl_path() or b"").decode()
 
     def replica(self, k: int) -> "HipDfa":
         """Borrowed view of the k-th replica (do not close it)."""
-        h = self._lib.fsm_hip_node_dfa(C.c_void_p(self._h), C.c_int(k))
+        h = self._lib.fsm_hip_node_dfa(self._h, k)
         if not h:
             raise _oserr("fsm_hip_node_dfa")
         return HipDfa(handle=h, borrowed=True)
 
     def shard(self, n: int, k: int):
         f, c = C.c_size_t(), C.c_size_t()
-        self._lib.fsm_hip_node_shard(C.c_void_p(self._h), C.c_size_t(n), C.c_int(k), C.byref(f), C.byref(c))
+        self._lib.fsm_hip_node_shard(self._h, n, k, C.byref(f), C.byref(c))
         return int(f.value), int(c.value)
 
     def bitmap_words(self, n: int) -> int:
-        return int(self._lib.fsm_hip_node_bitmap_words(C.c_void_p(self._h), C.c_size_t(n)))
+        return int(self._lib.fsm_hip_node_bitmap_words(self._h, n))
 
+    # ---- host-buffer fronts: HipDfa's, sharded over the devices ----
     def exec_batch(self, data: np.ndarray, lens: Optional[np.ndarray] = None):
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        n, stride = data.shape
-        end = np.empty(n, dtype=np.uint32)
-        bm = np.zeros((n + 63) // 64, dtype=np.uint64)
-        if lens is not None:
-            lens = np.ascontiguousarray(lens, dtype=np.uint32)
-        C.set_errno(0)
-        if self._lib.fsm_hip_node_exec_batch(C.c_void_p(self._h), _ptr(data), C.c_size_t(stride), _ptr(lens), C.c_size_t(n), _ptr(end), _ptr(bm)) != 0:
-            raise _oserr("fsm_hip_node_exec_batch")
-        return end, bm
+        return _exec_rows("fsm_hip_node_exec_batch", self._h, data, lens)
 
     def exec_batch_offsets32(self, base: np.ndarray, off32: np.ndarray, want_bitmap: bool = True, want_end: bool = True):
-        """fsm_hip_node_exec_batch_offsets32: u32 offsets (batches below 4 GiB), sharded over the devices."""
-        base = np.ascontiguousarray(base, dtype=np.uint8)
-        off32 = np.ascontiguousarray(off32, dtype=np.uint32)
-        n = len(off32) - 1
-        end = np.empty(n, dtype=np.uint32) if want_end else None
-        bm = np.zeros((n + 63) // 64, dtype=np.uint64) if want_bitmap else None
-        C.set_errno(0)
-        if self._lib.fsm_hip_node_exec_batch_offsets32(C.c_void_p(self._h), C.c_void_p(base.ctypes.data if len(base) else None), C.c_void_p(off32.ctypes.data),
-                                                  C.c_size_t(n), C.c_void_p(end.ctypes.data if want_end else None), C.c_void_p(bm.ctypes.data if want_bitmap else None)) != 0:
-            raise _oserr("fsm_hip_node_exec_batch_offsets32")
-        return end, bm
+        """fsm_hip_node_exec_batch_offsets32: u32 offsets (batches below 4 GiB)."""
+        return _exec_packed("fsm_hip_node_exec_batch_offsets32", self._h, base, off32, np.uint32, want_bitmap, want_end)
 
     def exec_batch_lengths(self, base: np.ndarray, lens: np.ndarray, want_bitmap: bool = True, want_end: bool = True):
-        """fsm_hip_node_exec_batch_lengths: inputs packed back to back, their lengths and nothing else, sharded over the devices."""
-        base = np.ascontiguousarray(base, dtype=np.uint8)
-        lens = np.ascontiguousarray(lens, dtype=np.uint32)
-        n = len(lens)
-        end = np.empty(n, dtype=np.uint32) if want_end else None
-        bm = np.zeros((n + 63) // 64, dtype=np.uint64) if want_bitmap else None
-        C.set_errno(0)
-        if self._lib.fsm_hip_node_exec_batch_lengths(C.c_void_p(self._h), C.c_void_p(base.ctypes.data if len(base) else None), C.c_void_p(lens.ctypes.data if n else None),
-                                                C.c_size_t(n), C.c_void_p(end.ctypes.data if want_end else None), C.c_void_p(bm.ctypes.data if want_bitmap else None)) != 0:
-            raise _oserr("fsm_hip_node_exec_batch_lengths")
-        return end, bm
+        """fsm_hip_node_exec_batch_lengths: inputs packed back to back, their lengths and nothing else."""
+        return _exec_packed("fsm_hip_node_exec_batch_lengths", self._h, base, lens, np.uint32, want_bitmap, want_end)
 
     def exec_batch_offsets(self, base: np.ndarray, off: np.ndarray, want_bitmap: bool = True, want_end: bool = True):
-        """fsm_hip_node_exec_batch_offsets: u64 offsets, sharded over the devices."""
-        base = np.ascontiguousarray(base, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.uint64)
-        n = len(off) - 1
-        end = np.empty(n, dtype=np.uint32) if want_end else None
-        bm = np.zeros((n + 63) // 64, dtype=np.uint64) if want_bitmap else None
-        C.set_errno(0)
-        if self._lib.fsm_hip_node_exec_batch_offsets(C.c_void_p(self._h), C.c_void_p(base.ctypes.data if len(base) else None), C.c_void_p(off.ctypes.data),
-                                                     C.c_size_t(n), C.c_void_p(end.ctypes.data if want_end else None), C.c_void_p(bm.ctypes.data if want_bitmap else None)) != 0:
-            raise _oserr("fsm_hip_node_exec_batch_offsets")
-        return end, bm
+        """fsm_hip_node_exec_batch_offsets: u64 offsets."""
+        return _exec_packed("fsm_hip_node_exec_batch_offsets", self._h, base, off, np.uint64, want_bitmap, want_end)
 
     def exec_strings(self, strings: Sequence[bytes]):
-        off = np.zeros(len(strings) + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(s) for s in strings])
-        return self.exec_batch_offsets(np.frombuffer(b"".join(strings) or b"\0", dtype=np.uint8), off)
+        return self.exec_batch_offsets(*_pack_strings(strings, pad=b"\0"))
+
+    def exec_batch_ids(self, data: np.ndarray, mode: int, lens: Optional[np.ndarray] = None) -> np.ndarray:
+        return _exec_rows_ids("fsm_hip_node_exec_batch_ids", self._h, data, mode, lens)
+
+    def exec_batch_eager(self, data: np.ndarray, lens: Optional[np.ndarray] = None, want_end: bool = True, eager_out: Optional[np.ndarray] = None):
+        """fsm_hip_node_exec_batch_eager: (end u32[n] or None, the raw sets u64[n, W]); decode with replica(0).decode_eager.
+        eager_out: the caller's own n * W words to write into (returned reshaped) instead of fresh zeros."""
+        data, lens, _, n, stride = _inputs(data, lens)
+        W = self.replica(0).eager_words()
+        end = np.empty(n, dtype=np.uint32) if want_end else None
+        if eager_out is None:
+            eager_out = np.zeros((n, W), dtype=np.uint64)
+        if eager_out.dtype != np.uint64 or eager_out.size != n * W or not eager_out.flags.c_contiguous:
+            raise ValueError("eager_out: n * W contiguous u64 words")
+        _call("fsm_hip_node_exec_batch_eager", self._h, _ptr(data), stride, _ptr(lens), n, _ptr(end), _ptr(eager_out))
+        return end, eager_out.reshape(n, W)
+
+    # ---- device-pointer fronts: per-device lists of device pointers ----
+    def _ptrs(self, xs):
+        """a list of ndev addresses (0 / None: NULL) as a C array, None as NULL"""
+        return None if xs is None else (C.c_void_p * self.ndev)(*[x or None for x in xs])
 
     def exec_batch_device(self, d_base: Sequence[int], stride: int, n: int, d_end: Optional[Sequence[int]] = None,
                           d_bitmap_all: Optional[Sequence[int]] = None, want_count: bool = False):
-        g = self.ndev
-        vp = C.c_void_p * g
-        base = vp(*[C.c_void_p(x) for x in d_base])
-        ends = vp(*[C.c_void_p(x or None) for x in d_end]) if d_end is not None else None
-        bms = vp(*[C.c_void_p(x) for x in d_bitmap_all]) if d_bitmap_all is not None else None
         cnt = C.c_uint64(0)
-        C.set_errno(0)
-        if self._lib.fsm_hip_node_exec_batch_device(C.c_void_p(self._h), base, C.c_size_t(stride), C.c_size_t(n), ends, bms,
-                                                    C.byref(cnt) if want_count else None) != 0:
-            raise _oserr("fsm_hip_node_exec_batch_device")
+        _call("fsm_hip_node_exec_batch_device", self._h, self._ptrs(d_base), stride, n, self._ptrs(d_end), self._ptrs(d_bitmap_all),
+              C.byref(cnt) if want_count else None)
+        return int(cnt.value) if want_count else None
+
+    def exec_device(self, n: int, d_base, stride: int = 0, d_len=None, d_off=None, d_end=None, d_ids=None, ids_mode: int = 1,
+                    d_eager=None, d_bitmap_all=None, want_count: bool = False, async_: bool = False):
+        """fsm_hip_node_exec_device: per-device lists of device pointers (None entries allowed where the header allows them)."""
+        keep = [self._ptrs(xs) for xs in (d_base, d_len, d_off, d_end, d_ids, d_eager, d_bitmap_all)]
+        base, lens, off, end, ids, eager, bms = (a if a is None else C.cast(a, PP) for a in keep)
+        b = NodeBatch(base, stride, lens, off, end, ids, ids_mode, eager, bms, 1 if want_count else 0)
+        cnt = C.c_uint64(0)
+        count_now = want_count and not async_
+        _call("fsm_hip_node_exec_device", self._h, C.byref(b), n, C.byref(cnt) if count_now else None, 1 if async_ else 0)
+        return int(cnt.value) if count_now else None
+
+    def wait(self, want_count: bool = False):
+        cnt = C.c_uint64(0)
+        _call("fsm_hip_node_wait", self._h, C.byref(cnt) if want_count else None)
         return int(cnt.value) if want_count else None
 
 
-class NodeBatch(C.Structure):
-    """struct fsm_hip_node_batch (include/fsm_hip.h)."""
-    _fields_ = [("d_base", C.POINTER(C.c_void_p)), ("stride", C.c_size_t), ("d_len", C.POINTER(C.c_void_p)), ("d_off", C.POINTER(C.c_void_p)),
-                ("d_end_out", C.POINTER(C.c_void_p)), ("d_id_out", C.POINTER(C.c_void_p)), ("ids_mode", C.c_int),
-                ("d_eager_out", C.POINTER(C.c_void_p)), ("d_bitmap_all", C.POINTER(C.c_void_p)), ("want_count", C.c_int)]
+# ---- many DFAs in one submission: MultiBatch (end, bitmap), MultiBatchIds (+ ids), MultiBatchEager (+ eager sets) --------------
+
+_MULTI = {5: (MultiBatch, ""), 6: (MultiBatchIds, "_ids"), 7: (MultiBatchEager, "_eager")}    # by the number of fields
 
 
-def _node_exec_device(self, n: int, d_base, stride: int = 0, d_len=None, d_off=None, d_end=None, d_ids=None, ids_mode: int = 1,
-                      d_eager=None, d_bitmap_all=None, want_count: bool = False, async_: bool = False):
-    """fsm_hip_node_exec_device: per-device lists of device pointers (None entries allowed where the header allows them)."""
-    g = self.ndev
-
-    def arr(xs):
-        if xs is None:
-            return None
-        a = (C.c_void_p * g)(*[C.c_void_p(x or None) for x in xs])
-        keep.append(a)
-        return C.cast(a, C.POINTER(C.c_void_p))
-
-    keep = []
-    b = NodeBatch(arr(d_base), stride, arr(d_len), arr(d_off), arr(d_end), arr(d_ids), ids_mode, arr(d_eager), arr(d_bitmap_all), 1 if want_count else 0)
-    cnt = C.c_uint64(0)
-    C.set_errno(0)
-    if self._lib.fsm_hip_node_exec_device(C.c_void_p(self._h), C.byref(b), C.c_size_t(n), C.byref(cnt) if (want_count and not async_) else None,
-                                          C.c_int(1 if async_ else 0)) != 0:
-        raise _oserr("fsm_hip_node_exec_device")
-    return int(cnt.value) if (want_count and not async_) else None
+def _multi_args(struct, owners, jobs):
+    """(handles, batches, k) of a submission: jobs[q] = the addresses of struct's fields, in order (0 / None: NULL; n: a count)"""
+    k = len(jobs)
+    if any(len(j) != len(struct._fields_) for j in jobs):
+        raise ValueError("a job of %s is a %d-tuple" % (struct.__name__, len(struct._fields_)))
+    arr = (struct * max(k, 1))()
+    for q, j in enumerate(jobs):
+        for (name, _), v in zip(struct._fields_, j):
+            setattr(arr[q], name, v if name == "n" else (v or None))
+    return (C.c_void_p * max(k, 1))(*[o._h if o is not None else None for o in owners]), arr, k
 
 
-def _node_wait(self, want_count: bool = False):
-    cnt = C.c_uint64(0)
-    C.set_errno(0)
-    if self._lib.fsm_hip_node_wait(C.c_void_p(self._h), C.byref(cnt) if want_count else None) != 0:
-        raise _oserr("fsm_hip_node_wait")
-    return int(cnt.value) if want_count else None
-
-
-def _node_exec_batch_ids(self, data: np.ndarray, mode: int, lens: Optional[np.ndarray] = None) -> np.ndarray:
-    data = np.ascontiguousarray(data, dtype=np.uint8)
-    n, stride = data.shape
-    out = np.empty(n, dtype=np.uint32)
-    if lens is not None:
-        lens = np.ascontiguousarray(lens, dtype=np.uint32)
-    C.set_errno(0)
-    if self._lib.fsm_hip_node_exec_batch_ids(C.c_void_p(self._h), _ptr(data), C.c_size_t(stride), _ptr(lens), C.c_size_t(n), C.c_int(mode), _ptr(out)) != 0:
-        raise _oserr("fsm_hip_node_exec_batch_ids")
-    return out
-
-
-def _node_exec_batch_eager(self, data: np.ndarray, lens: Optional[np.ndarray] = None, want_end: bool = True, eager_out: Optional[np.ndarray] = None):
-    """fsm_hip_node_exec_batch_eager: (end u32[n] or None, the raw sets u64[n, W]); decode with replica(0).decode_eager.
-    eager_out: the caller's own n * W words to write into (returned reshaped) instead of fresh zeros."""
-    data = np.ascontiguousarray(data, dtype=np.uint8)
-    n, stride = data.shape
-    W = self.replica(0).eager_words()
-    end = np.empty(n, dtype=np.uint32) if want_end else None
-    if eager_out is None:
-        eager_out = np.zeros((n, W), dtype=np.uint64)
-    if eager_out.dtype != np.uint64 or eager_out.size != n * W or not eager_out.flags.c_contiguous:
-        raise ValueError("eager_out: n * W contiguous u64 words")
-    if lens is not None:
-        lens = np.ascontiguousarray(lens, dtype=np.uint32)
-    C.set_errno(0)
-    if self._lib.fsm_hip_node_exec_batch_eager(C.c_void_p(self._h), _ptr(data), C.c_size_t(stride), _ptr(lens), C.c_size_t(n), _ptr(end), _ptr(eager_out)) != 0:
-        raise _oserr("fsm_hip_node_exec_batch_eager")
-    return end, eager_out.reshape(n, W)
-
-
-HipNode.exec_device = _node_exec_device
-HipNode.wait = _node_wait
-HipNode.exec_batch_ids = _node_exec_batch_ids
-HipNode.exec_batch_eager = _node_exec_batch_eager
-
-
-class MultiBatch(C.Structure):
-    """struct fsm_hip_multi_batch (include/fsm_hip.h)"""
-    _fields_ = [("base", C.c_void_p), ("off", C.c_void_p), ("n", C.c_size_t), ("end_out", C.c_void_p), ("accept_bitmap", C.c_void_p)]
+def _multi_host(width, fn, owners, jobs, *tail, want_bitmap=True, eager_words=None):
+    """One submission of strings: job q = jobs[q] packed, with fresh outputs (end and ids poisoned, so that a job the library
+    passes over shows) -> per job [end, bitmap, ids, sets][:width - 3].  eager_words[q]: the words of a set of job q, None: no sets."""
+    struct, outs, rows, keep = _MULTI[width][0], [], [], []
+    for q, strs in enumerate(jobs):
+        n = len(strs)
+        base, off = _pack_strings(strs, pad=b"\0")
+        out = list(_outputs(n, True, want_bitmap, fill=0xDEADBEEF))
+        if width >= 6:
+            out.append(np.full(n, 0xDEADBEEF, dtype=np.uint32))
+        if width == 7:
+            out.append(np.full((n, eager_words[q]), 0xDEADBEEFDEADBEEF, dtype=np.uint64) if eager_words[q] is not None else None)
+        keep.append((base, off))
+        rows.append((base.ctypes.data, off.ctypes.data, n) + tuple(a.ctypes.data if (a is not None and n) else None for a in out))
+        outs.append(out)
+    _call(fn, *_multi_args(struct, owners, rows), *tail)
+    return outs
 
 
 def exec_multi(dfas: Sequence["HipDfa"], jobs: Sequence[Sequence[bytes]], want_bitmap: bool = True, nodes: Optional[Sequence["HipNode"]] = None):
     """fsm_hip_exec_multi: job q = the strings jobs[q] through dfas[q]; ONE submission.  Returns [(end, bitmap), ...].
     nodes: fsm_hip_node_exec_multi instead (the list sharded by DFA over the nodes' devices)."""
-    lib = load_library()
-    k = len(jobs)
-    keep, arr = [], (MultiBatch * max(k, 1))()
-    outs = []
-    for q, strs in enumerate(jobs):
-        n = len(strs)
-        off = np.zeros(n + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(x) for x in strs])
-        base = np.frombuffer(b"".join(strs) or b"\0", dtype=np.uint8)
-        end = np.full(n, 0xDEADBEEF, dtype=np.uint32)
-        bm = np.zeros((n + 63) // 64, dtype=np.uint64) if want_bitmap else None
-        keep += [off, base, end, bm]
-        arr[q].base, arr[q].off, arr[q].n = base.ctypes.data, off.ctypes.data, n
-        arr[q].end_out = end.ctypes.data if n else None
-        arr[q].accept_bitmap = bm.ctypes.data if (want_bitmap and n) else None
-        outs.append((end, bm))
-    C.set_errno(0)
     if nodes is not None:
-        hs = (C.c_void_p * max(k, 1))(*[nd._h for nd in nodes])
-        if lib.fsm_hip_node_exec_multi(hs, arr, C.c_size_t(k)) != 0:
-            raise _oserr("fsm_hip_node_exec_multi")
-    else:
-        hs = (C.c_void_p * max(k, 1))(*[d._h for d in dfas])
-        if lib.fsm_hip_exec_multi(hs, arr, C.c_size_t(k)) != 0:
-            raise _oserr("fsm_hip_exec_multi")
-    return outs
-
-
-def exec_multi_device(dfas: Sequence["HipDfa"], jobs: Sequence[tuple], stream: int = 0):
-    """fsm_hip_exec_multi_device: jobs[q] = (d_base, d_off, n, d_end, d_bitmap) device pointers (0 = NULL)."""
-    lib = load_library()
-    k = len(jobs)
-    arr = (MultiBatch * max(k, 1))()
-    for q, (b, o, n, e, m) in enumerate(jobs):
-        arr[q].base, arr[q].off, arr[q].n, arr[q].end_out, arr[q].accept_bitmap = b or None, o or None, n, e or None, m or None
-    hs = (C.c_void_p * max(k, 1))(*[d._h for d in dfas])
-    C.set_errno(0)
-    if lib.fsm_hip_exec_multi_device(hs, arr, C.c_size_t(k), C.c_void_p(stream or None)) != 0:
-        raise _oserr("fsm_hip_exec_multi_device")
-
-
-class MultiBatchIds(C.Structure):
-    _fields_ = [("base", C.c_void_p), ("off", C.c_void_p), ("n", C.c_size_t), ("end_out", C.c_void_p), ("accept_bitmap", C.c_void_p), ("id_out", C.c_void_p)]
+        return [tuple(o) for o in _multi_host(5, "fsm_hip_node_exec_multi", nodes, jobs, want_bitmap=want_bitmap)]
+    return [tuple(o) for o in _multi_host(5, "fsm_hip_exec_multi", dfas, jobs, want_bitmap=want_bitmap)]
 
 
 def exec_multi_ids(dfas: Sequence["HipDfa"], jobs: Sequence[Sequence[bytes]], ids_mode: int):
     """fsm_hip_exec_multi_ids: job q = the strings jobs[q] through dfas[q], ONE submission, end-ids by the device.
     Returns [(end, bitmap, ids), ...]."""
-    lib = load_library()
-    k = len(jobs)
-    keep, arr, outs = [], (MultiBatchIds * max(k, 1))(), []
-    for q, strs in enumerate(jobs):
-        n = len(strs)
-        off = np.zeros(n + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(x) for x in strs])
-        base = np.frombuffer(b"".join(strs) or b"\0", dtype=np.uint8)
-        end = np.full(n, 0xDEADBEEF, dtype=np.uint32)
-        ids = np.full(n, 0xDEADBEEF, dtype=np.uint32)
-        bm = np.zeros((n + 63) // 64, dtype=np.uint64)
-        keep += [off, base, end, bm, ids]
-        arr[q].base, arr[q].off, arr[q].n = base.ctypes.data, off.ctypes.data, n
-        arr[q].end_out, arr[q].accept_bitmap, arr[q].id_out = (end.ctypes.data, bm.ctypes.data, ids.ctypes.data) if n else (None, None, None)
-        outs.append((end, bm, ids))
-    hs = (C.c_void_p * max(k, 1))(*[d._h for d in dfas])
-    C.set_errno(0)
-    if lib.fsm_hip_exec_multi_ids(hs, arr, C.c_size_t(k), C.c_int(ids_mode)) != 0:
-        raise _oserr("fsm_hip_exec_multi_ids")
-    return outs
-
-
-def exec_multi_ids_device(dfas: Sequence["HipDfa"], jobs: Sequence[tuple], ids_mode: int, stream: int = 0):
-    """fsm_hip_exec_multi_ids_device: jobs[q] = (d_base, d_off, n, d_end, d_bitmap, d_ids) device pointers (0 = NULL)."""
-    lib = load_library()
-    k = len(jobs)
-    arr = (MultiBatchIds * max(k, 1))()
-    for q, (b, o, n, e, m, i) in enumerate(jobs):
-        arr[q].base, arr[q].off, arr[q].n, arr[q].end_out, arr[q].accept_bitmap, arr[q].id_out = b or None, o or None, n, e or None, m or None, i or None
-    hs = (C.c_void_p * max(k, 1))(*[d._h for d in dfas])
-    C.set_errno(0)
-    if lib.fsm_hip_exec_multi_ids_device(hs, arr, C.c_size_t(k), C.c_int(ids_mode), C.c_void_p(stream or None)) != 0:
-        raise _oserr("fsm_hip_exec_multi_ids_device")
-
-
-class MultiBatchEager(C.Structure):
-    """struct fsm_hip_multi_batch_eager (include/fsm_hip.h)"""
-    _fields_ = [("base", C.c_void_p), ("off", C.c_void_p), ("n", C.c_size_t), ("end_out", C.c_void_p), ("accept_bitmap", C.c_void_p), ("id_out", C.c_void_p),
-                ("eager_out", C.c_void_p)]
+    return [tuple(o) for o in _multi_host(6, "fsm_hip_exec_multi_ids", dfas, jobs, ids_mode)]
 
 
 def exec_multi_eager(dfas: Sequence["HipDfa"], jobs: Sequence[Sequence[bytes]], ids_mode: int = 1, want_eager: Optional[Sequence[bool]] = None):
     """fsm_hip_exec_multi_eager: job q = the strings jobs[q] through dfas[q], ONE submission, end-ids and eager-output sets by
     the device.  Returns [(end, bitmap, ids, sets), ...], sets decoded like exec_batch_eager (one array of emitted ids per
     string); want_eager[q] = False leaves job q's eager_out NULL (its sets: None)."""
-    lib = load_library()
-    k = len(jobs)
-    keep, arr, outs, raw = [], (MultiBatchEager * max(k, 1))(), [], []
-    for q, strs in enumerate(jobs):
-        n = len(strs)
-        off = np.zeros(n + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(x) for x in strs])
-        base = np.frombuffer(b"".join(strs) or b"\0", dtype=np.uint8)
-        end = np.full(n, 0xDEADBEEF, dtype=np.uint32)
-        ids = np.full(n, 0xDEADBEEF, dtype=np.uint32)
-        bm = np.zeros((n + 63) // 64, dtype=np.uint64)
-        eo = np.full((n, dfas[q].eager_words()), 0xDEADBEEFDEADBEEF, dtype=np.uint64) if (want_eager is None or want_eager[q]) else None
-        keep += [off, base, end, bm, ids, eo]
-        arr[q].base, arr[q].off, arr[q].n = base.ctypes.data, off.ctypes.data, n
-        arr[q].end_out, arr[q].accept_bitmap, arr[q].id_out = (end.ctypes.data, bm.ctypes.data, ids.ctypes.data) if n else (None, None, None)
-        arr[q].eager_out = eo.ctypes.data if (eo is not None and n) else None
-        outs.append((end, bm, ids))
-        raw.append(eo)
-    hs = (C.c_void_p * max(k, 1))(*[d._h for d in dfas])
-    C.set_errno(0)
-    if lib.fsm_hip_exec_multi_eager(hs, arr, C.c_size_t(k), C.c_int(ids_mode)) != 0:
-        raise _oserr("fsm_hip_exec_multi_eager")
-    return [(e, m, i, None if eo is None else dfas[q].decode_eager(eo)) for q, ((e, m, i), eo) in enumerate(zip(outs, raw))]
+    words = [dfas[q].eager_words() if (want_eager is None or want_eager[q]) else None for q in range(len(jobs))]
+    outs = _multi_host(7, "fsm_hip_exec_multi_eager", dfas, jobs, ids_mode, eager_words=words)
+    return [(e, m, i, None if eo is None else dfas[q].decode_eager(eo)) for q, (e, m, i, eo) in enumerate(outs)]
+
+
+def exec_multi_device(dfas: Sequence["HipDfa"], jobs: Sequence[tuple], stream: int = 0):
+    """fsm_hip_exec_multi_device: jobs[q] = (d_base, d_off, n, d_end, d_bitmap) device pointers (0 = NULL)."""
+    _call("fsm_hip_exec_multi_device", *_multi_args(MultiBatch, dfas, jobs), stream or None)
+
+
+def exec_multi_ids_device(dfas: Sequence["HipDfa"], jobs: Sequence[tuple], ids_mode: int, stream: int = 0):
+    """fsm_hip_exec_multi_ids_device: jobs[q] = (d_base, d_off, n, d_end, d_bitmap, d_ids) device pointers (0 = NULL)."""
+    _call("fsm_hip_exec_multi_ids_device", *_multi_args(MultiBatchIds, dfas, jobs), ids_mode, stream or None)
 
 
 def exec_multi_eager_device(dfas: Sequence["HipDfa"], jobs: Sequence[tuple], ids_mode: int = 1, stream: int = 0):
     """fsm_hip_exec_multi_eager_device: jobs[q] = (d_base, d_off, n, d_end, d_bitmap, d_ids, d_eager) device pointers (0 = NULL);
     d_eager: n * dfas[q].eager_words() u64."""
-    lib = load_library()
-    k = len(jobs)
-    arr = (MultiBatchEager * max(k, 1))()
-    for q, (b, o, n, e, m, i, g) in enumerate(jobs):
-        arr[q].base, arr[q].off, arr[q].n, arr[q].end_out, arr[q].accept_bitmap, arr[q].id_out, arr[q].eager_out = b or None, o or None, n, e or None, m or None, i or None, g or None
-    hs = (C.c_void_p * max(k, 1))(*[d._h for d in dfas])
-    C.set_errno(0)
-    if lib.fsm_hip_exec_multi_eager_device(hs, arr, C.c_size_t(k), C.c_int(ids_mode), C.c_void_p(stream or None)) != 0:
-        raise _oserr("fsm_hip_exec_multi_eager_device")
+    _call("fsm_hip_exec_multi_eager_device", *_multi_args(MultiBatchEager, dfas, jobs), ids_mode, stream or None)
 
 
 def exec_multi_ptrs(dfas: Sequence[Optional["HipDfa"]], jobs: Sequence[tuple], ids_mode: int = 0, device: bool = False, stream: int = 0) -> None:
@@ -1217,22 +1014,12 @@ def exec_multi_ptrs(dfas: Sequence[Optional["HipDfa"]], jobs: Sequence[tuple], i
     bitmap) -> fsm_hip_exec_multi[_device], with a sixth (ids) -> fsm_hip_exec_multi_ids[_device], with a seventh (eager) ->
     fsm_hip_exec_multi_eager[_device]; every job of a submission has the same length.  0 = NULL: an output left out; dfas[q]
     None: a NULL handle.  The caller keeps the memory alive and reads the outputs where it put them."""
-    lib = load_library()
-    k = len(jobs)
-    width = len(jobs[0]) if k else 5
-    if width not in (5, 6, 7) or any(len(j) != width for j in jobs):
+    width = len(jobs[0]) if len(jobs) else 5
+    if width not in _MULTI or any(len(j) != width for j in jobs):
         raise ValueError("every job is a 5-tuple, a 6-tuple or a 7-tuple")
-    arr = ({5: MultiBatch, 6: MultiBatchIds, 7: MultiBatchEager}[width] * max(k, 1))()
-    names = ("base", "off", "n", "end_out", "accept_bitmap", "id_out", "eager_out")
-    for q, j in enumerate(jobs):
-        for name, v in zip(names, j):
-            setattr(arr[q], name, v if name == "n" else (v or None))
-    hs = (C.c_void_p * max(k, 1))(*[d._h if d is not None else None for d in dfas])
-    fn = "fsm_hip_exec_multi" + {5: "", 6: "_ids", 7: "_eager"}[width] + ("_device" if device else "")
-    args = [hs, arr, C.c_size_t(k)] + ([C.c_int(ids_mode)] if width != 5 else []) + ([C.c_void_p(stream or None)] if device else [])
-    C.set_errno(0)
-    if getattr(lib, fn)(*args) != 0:
-        raise _oserr(fn)
+    struct, suffix = _MULTI[width]
+    _call("fsm_hip_exec_multi" + suffix + ("_device" if device else ""), *_multi_args(struct, dfas, jobs),
+          *([ids_mode] if width != 5 else []), *([stream or None] if device else []))
 
 
 class MultiPrepared:
@@ -1241,101 +1028,69 @@ class MultiPrepared:
     -- every job of the submission -- (d_base, d_off, n, d_end, d_bitmap, d_ids, d_eager): fsm_hip_multi_prepare_eager."""
 
     def __init__(self, dfas: Sequence["HipDfa"], jobs: Sequence[tuple], ids_mode: int = 0):
-        lib = load_library()
-        k = len(jobs)
-        eager = k != 0 and len(jobs[0]) == 7
+        eager = len(jobs) != 0 and len(jobs[0]) == 7
         if any(len(j) != (7 if eager else 6) for j in jobs):
             raise ValueError("every job is a 6-tuple, or every job is a 7-tuple")
-        arr = ((MultiBatchEager if eager else MultiBatchIds) * max(k, 1))()
-        for q, j in enumerate(jobs):
-            b, o, n, e, m, i = j[:6]
-            arr[q].base, arr[q].off, arr[q].n, arr[q].end_out, arr[q].accept_bitmap, arr[q].id_out = b or None, o or None, n, e or None, m or None, i or None
-            if eager:
-                arr[q].eager_out = j[6] or None
-        hs = (C.c_void_p * max(k, 1))(*[d._h for d in dfas])
         self._keep = list(dfas)
         self._p = C.c_void_p()
-        C.set_errno(0)
-        fn = "fsm_hip_multi_prepare_eager" if eager else "fsm_hip_multi_prepare"
-        if getattr(lib, fn)(hs, arr, C.c_size_t(k), C.c_int(ids_mode), C.byref(self._p)) != 0:
-            raise _oserr(fn)
+        _call("fsm_hip_multi_prepare_eager" if eager else "fsm_hip_multi_prepare", *_multi_args(MultiBatchEager if eager else MultiBatchIds, dfas, jobs),
+              ids_mode, C.byref(self._p))
 
     def launch(self, stream: int = 0) -> None:
-        C.set_errno(0)
-        if load_library().fsm_hip_multi_launch(self._p, C.c_void_p(stream or None)) != 0:
-            raise _oserr("fsm_hip_multi_launch")
+        _call("fsm_hip_multi_launch", self._p, stream or None)
 
     def close(self) -> None:
         if self._p:
-            lib = load_library()
-            lib.fsm_hip_multi_prepared_free.restype = None
-            lib.fsm_hip_multi_prepared_free(self._p)
+            load_library().fsm_hip_multi_prepared_free(self._p)
             self._p = C.c_void_p()
 
 
 def multi_last_launches() -> int:
-    lib = load_library()
-    lib.fsm_hip_multi_last_launches.restype = C.c_uint
-    return int(lib.fsm_hip_multi_last_launches())
+    return int(load_library().fsm_hip_multi_last_launches())
 
 
 def multi_last_fused_jobs() -> int:
-    lib = load_library()
-    lib.fsm_hip_multi_last_fused_jobs.restype = C.c_uint
-    return int(lib.fsm_hip_multi_last_fused_jobs())
+    return int(load_library().fsm_hip_multi_last_fused_jobs())
 
 
 def multi_assign(cost: Sequence[int], ndev: int) -> np.ndarray:
     """fsm_hip_multi_assign: which device takes which job of a many-DFA submission (largest first, least loaded device).  Host arithmetic only."""
-    lib = load_library()
     c = np.ascontiguousarray(cost, dtype=np.uint64)
     out = np.zeros(len(c), dtype=np.int32)
-    C.set_errno(0)
-    if lib.fsm_hip_multi_assign(C.c_void_p(c.ctypes.data if len(c) else None), C.c_size_t(len(c)), C.c_int(ndev), C.c_void_p(out.ctypes.data if len(c) else None)) != 0:
-        raise _oserr("fsm_hip_multi_assign")
+    _call("fsm_hip_multi_assign", _ptr0(c), len(c), ndev, _ptr(out) if len(c) else None)
     return out
 
 
-def _gen_args(alphabet, plant):
-    a = np.frombuffer(bytes(alphabet), dtype=np.uint8).copy() if alphabet else None
-    p = np.frombuffer(bytes(plant), dtype=np.uint8).copy() if plant else None
-    return a, p
+# ---- input generators and probes ----
+
+def _bytes_arg(b):
+    """bytes -> (its u8 copy or None, its length) as the generators take a byte set"""
+    a = np.frombuffer(bytes(b), dtype=np.uint8).copy() if b else None
+    return a, (len(a) if a is not None else 0)
 
 
 def gen_inputs_host(n: int, stride: int, first_index: int = 0, seed: int = 0x5EEDF5A1, alphabet: Optional[bytes] = None,
                     plant: Optional[bytes] = None, plant_every: int = 0) -> np.ndarray:
-    lib = load_library()
     out = np.empty((n, stride), dtype=np.uint8)
-    a, p = _gen_args(alphabet, plant)
-    lib.fsm_hip_gen_inputs_host(_ptr(out), stride, n, first_index, seed, _ptr(a), len(a) if a is not None else 0,
-                                _ptr(p), len(p) if p is not None else 0, plant_every)
+    (a, na), (p, np_) = _bytes_arg(alphabet), _bytes_arg(plant)
+    load_library().fsm_hip_gen_inputs_host(_ptr(out), stride, n, first_index, seed, _ptr(a), na, _ptr(p), np_, plant_every)
     return out
 
 
 def gen_inputs_device(d_base: int, n: int, stride: int, first_index: int = 0, seed: int = 0x5EEDF5A1,
                       alphabet: Optional[bytes] = None, plant: Optional[bytes] = None, plant_every: int = 0, stream: int = 0):
-    lib = load_library()
-    a, p = _gen_args(alphabet, plant)
-    C.set_errno(0)
-    if lib.fsm_hip_gen_inputs_device(d_base, stride, n, first_index, seed, _ptr(a), len(a) if a is not None else 0,
-                                     _ptr(p), len(p) if p is not None else 0, plant_every, stream or None) != 0:
-        raise _oserr("fsm_hip_gen_inputs_device")
+    (a, na), (p, np_) = _bytes_arg(alphabet), _bytes_arg(plant)
+    _call("fsm_hip_gen_inputs_device", d_base, stride, n, first_index, seed, _ptr(a), na, _ptr(p), np_, plant_every, stream or None)
 
 
 def gen_pack_rows_device(d_rows: int, stride: int, d_len: int, d_off: int, n: int, max_len: int, d_out: int, stream: int = 0):
     """fsm_hip_gen_pack_rows_device: input i = the first len[i] bytes of row i, packed at d_out + off[i]."""
-    lib = load_library()
-    C.set_errno(0)
-    if lib.fsm_hip_gen_pack_rows_device(C.c_void_p(d_rows), C.c_size_t(stride), C.c_void_p(d_len), C.c_void_p(d_off), C.c_size_t(n),
-                                        C.c_size_t(max_len), C.c_void_p(d_out), C.c_void_p(stream or None)) != 0:
-        raise _oserr("fsm_hip_gen_pack_rows_device")
+    _call("fsm_hip_gen_pack_rows_device", d_rows, stride, d_len, d_off, n, max_len, d_out, stream or None)
 
 
 def gather_probe_ms(d_base: int, nbytes: int, ngathers: int, vec_bytes: int, d_scratch4: int, stream: int = 0) -> float:
     """fsm_hip_gather_probe_ms: one launch of `ngathers` independent vec_bytes-byte loads at pseudo-random offsets of the buffer."""
-    lib = load_library()
-    lib.fsm_hip_gather_probe_ms.restype = C.c_double
-    ms = lib.fsm_hip_gather_probe_ms(C.c_void_p(d_base), C.c_size_t(nbytes), C.c_size_t(ngathers), C.c_int(vec_bytes), C.c_void_p(d_scratch4), C.c_void_p(stream or None))
+    ms = load_library().fsm_hip_gather_probe_ms(d_base, nbytes, ngathers, vec_bytes, d_scratch4, stream or None)
     if ms < 0:
         raise _oserr("fsm_hip_gather_probe_ms")
     return float(ms)
@@ -1343,10 +1098,8 @@ def gather_probe_ms(d_base: int, nbytes: int, ngathers: int, vec_bytes: int, d_s
 
 def lds_chain_probe_gbps(table_bytes: int, waves: int, blocks_per_cu: int, steps: int, d_scratch4: int, stream: int = 0) -> float:
     """fsm_hip_lds_chain_probe_gbps: what a dependent chain of random LDS reads sustains (the lookup layouts' ceiling)."""
-    lib = load_library()
-    lib.fsm_hip_lds_chain_probe_gbps.restype = C.c_double
     C.set_errno(0)
-    r = lib.fsm_hip_lds_chain_probe_gbps(C.c_size_t(table_bytes), C.c_int(waves), C.c_int(blocks_per_cu), C.c_size_t(steps), C.c_void_p(d_scratch4), C.c_void_p(stream or None))
+    r = load_library().fsm_hip_lds_chain_probe_gbps(table_bytes, waves, blocks_per_cu, steps, d_scratch4, stream or None)
     if r < 0:
         raise _oserr("fsm_hip_lds_chain_probe_gbps")
     return float(r)
@@ -1354,9 +1107,7 @@ def lds_chain_probe_gbps(table_bytes: int, waves: int, blocks_per_cu: int, steps
 
 def waves_by_occupancy(vgprs: int, workgroups_by_lds: int, max_waves: int = 16) -> int:
     """fsm_hip_waves_by_occupancy: the workgroup size (wavefronts) a latency-bound per-lane kernel gets (pure arithmetic)."""
-    lib = load_library()
-    lib.fsm_hip_waves_by_occupancy.restype = C.c_int
-    return int(lib.fsm_hip_waves_by_occupancy(C.c_int(vgprs), C.c_int(workgroups_by_lds), C.c_int(max_waves)))
+    return int(load_library().fsm_hip_waves_by_occupancy(vgprs, workgroups_by_lds, max_waves))
 
 
 def pack_affixes(items: Sequence[bytes]) -> np.ndarray:
@@ -1369,42 +1120,30 @@ def pack_affixes(items: Sequence[bytes]) -> np.ndarray:
     return t
 
 
+def _affix_args(alphabet, body, body2, prefixes, suffixes, every):
+    """the generators' arguments between the seed and the stream: {bytes, count} of alphabet, body, body2, prefixes, suffixes; every"""
+    (a, na), (b, nb), (b2, nb2) = _bytes_arg(alphabet), _bytes_arg(body), _bytes_arg(body2)
+    p, s = pack_affixes(prefixes), pack_affixes(suffixes)
+    return _ptr(a), na, _ptr(b), nb, _ptr(b2), nb2, _ptr(p), len(p), _ptr(s), len(s), every
+
+
 def gen_affix_inputs_host(n: int, stride: int, first_index: int, seed: int, alphabet: bytes, body: bytes,
                           prefixes: Sequence[bytes], suffixes: Sequence[bytes], every: int = 2, body2: Optional[bytes] = None) -> np.ndarray:
     """body2: alternate body / body2 byte by byte after the prefix (fsm_hip_gen_affix2_inputs_host)."""
-    lib = load_library()
-    lib.fsm_hip_gen_affix2_inputs_host.restype = None
     out = np.empty((n, stride), dtype=np.uint8)
-    a, b = _gen_args(alphabet, body)
-    b2 = np.frombuffer(bytes(body2), dtype=np.uint8).copy() if body2 else None
-    p, s = pack_affixes(prefixes), pack_affixes(suffixes)
-    lib.fsm_hip_gen_affix2_inputs_host(_ptr(out), C.c_size_t(stride), C.c_size_t(n), C.c_uint64(first_index), C.c_uint64(seed),
-                                       _ptr(a), C.c_uint(len(a)), _ptr(b), C.c_uint(len(b)), _ptr(b2), C.c_uint(len(b2) if b2 is not None else 0),
-                                       _ptr(p), C.c_uint(len(p)), _ptr(s), C.c_uint(len(s)), C.c_uint(every))
+    load_library().fsm_hip_gen_affix2_inputs_host(_ptr(out), stride, n, first_index, seed, *_affix_args(alphabet, body, body2, prefixes, suffixes, every))
     return out
 
 
 def gen_affix_inputs_device(d_base: int, n: int, stride: int, first_index: int, seed: int, alphabet: bytes, body: bytes,
                             prefixes: Sequence[bytes], suffixes: Sequence[bytes], every: int = 2, stream: int = 0, body2: Optional[bytes] = None):
-    lib = load_library()
-    a, b = _gen_args(alphabet, body)
-    b2 = np.frombuffer(bytes(body2), dtype=np.uint8).copy() if body2 else None
-    p, s = pack_affixes(prefixes), pack_affixes(suffixes)
-    C.set_errno(0)
-    r = lib.fsm_hip_gen_affix2_inputs_device(C.c_void_p(d_base), C.c_size_t(stride), C.c_size_t(n), C.c_uint64(first_index),
-                                             C.c_uint64(seed), _ptr(a), C.c_uint(len(a)), _ptr(b), C.c_uint(len(b)),
-                                             _ptr(b2), C.c_uint(len(b2) if b2 is not None else 0),
-                                             _ptr(p), C.c_uint(len(p)), _ptr(s), C.c_uint(len(s)), C.c_uint(every),
-                                             C.c_void_p(stream or None))
-    if r != 0:
-        raise _oserr("fsm_hip_gen_affix2_inputs_device")
+    _call("fsm_hip_gen_affix2_inputs_device", d_base, stride, n, first_index, seed, *_affix_args(alphabet, body, body2, prefixes, suffixes, every),
+          stream or None)
 
 
 def stream_read_probe_gbps(d_base: int, nbytes: int, d_scratch4: int, reps: int = 3, stream: int = 0) -> float:
     """GB/s of a trivially coalesced read-only kernel over the same buffer (measured HBM ceiling)."""
-    lib = load_library()
-    lib.fsm_hip_stream_read_probe_ms.restype = C.c_double
-    ms = lib.fsm_hip_stream_read_probe_ms(C.c_void_p(d_base), C.c_size_t(nbytes), C.c_void_p(d_scratch4), C.c_int(reps), C.c_void_p(stream or None))
+    ms = load_library().fsm_hip_stream_read_probe_ms(d_base, nbytes, d_scratch4, reps, stream or None)
     if ms <= 0:
         raise _oserr("fsm_hip_stream_read_probe_ms")
     return nbytes / (ms * 1e-3) / 1e9
@@ -1414,18 +1153,8 @@ def stream_read_probe_gbps(d_base: int, nbytes: int, d_scratch4: int, reps: int 
 
 def identity_byte(flat: FlatDfa, byte: int) -> FlatDfa:
     """fsm_hip_desc_identity_byte: a copy of the description in which `byte` is a self-loop of every state (host arithmetic)."""
-    lib = load_library()
-    lib.fsm_hip_desc_identity_byte.restype = C.POINTER(_Desc)
-    lib.fsm_hip_desc_identity_byte.argtypes = [C.POINTER(_Desc), C.c_int]
     d = flat.desc()
-    C.set_errno(0)
-    t = lib.fsm_hip_desc_identity_byte(C.byref(d), int(byte))
-    if not t:
-        raise _oserr("fsm_hip_desc_identity_byte")
-    try:
-        return FlatDfa.from_desc(t.contents)
-    finally:
-        lib.fsm_hip_desc_free(t)
+    return FlatDfa._take(_call("fsm_hip_desc_identity_byte", C.byref(d), int(byte)))
 
 
 class LinesDfa:
@@ -1434,14 +1163,9 @@ class LinesDfa:
 
     def __init__(self, flat: FlatDfa, delim: int = 0x0A, flags: int = 0):
         self._lib = load_library()
-        self._lib.fsm_hip_lines_dfa_create.restype = C.c_void_p
-        self._lib.fsm_hip_lines_dfa_inner.restype = C.c_void_p
         d = flat.desc()
-        C.set_errno(0)
-        self._h = self._lib.fsm_hip_lines_dfa_create(C.byref(d), C.c_int(delim), C.c_uint(flags))
-        if not self._h:
-            raise _oserr("fsm_hip_lines_dfa_create")
-        self.inner = HipDfa(handle=self._lib.fsm_hip_lines_dfa_inner(C.c_void_p(self._h)), borrowed=True)
+        self._h = _call("fsm_hip_lines_dfa_create", C.byref(d), delim, flags)
+        self.inner = HipDfa(handle=self._lib.fsm_hip_lines_dfa_inner(self._h), borrowed=True)
 
     @property
     def handle(self):
@@ -1449,12 +1173,12 @@ class LinesDfa:
 
     @property
     def delim(self) -> int:
-        return int(self._lib.fsm_hip_lines_dfa_delim(C.c_void_p(self._h)))
+        return int(self._lib.fsm_hip_lines_dfa_delim(self._h))
 
     def close(self):
         if getattr(self, "_h", None):
             self.inner._h = None
-            self._lib.fsm_hip_lines_dfa_free(C.c_void_p(self._h))
+            self._lib.fsm_hip_lines_dfa_free(self._h)
             self._h = None
 
     __del__ = close
@@ -1467,46 +1191,27 @@ class HipText:
     d_text either a device address (borrowed, with nfiles=) or an array-like that is copied to the device and kept."""
 
     def __init__(self, data=None, delim: int = 0x0A, *, d_text: int = 0, nbytes: int = 0, stream: int = 0, file_off=None, nfiles: int = 0):
-        self._lib = lib = load_library()
-        lib.fsm_hip_text_open.restype = C.c_void_p
-        lib.fsm_hip_text_open_device.restype = C.c_void_p
-        lib.fsm_hip_text_lines.restype = C.c_size_t
-        lib.fsm_hip_text_offsets_device.restype = C.c_void_p
-        lib.fsm_hip_text_scan_ms.restype = C.c_double
-        lib.fsm_hip_text_open_files.restype = C.c_void_p
-        lib.fsm_hip_text_open_files_device.restype = C.c_void_p
-        lib.fsm_hip_text_files.restype = C.c_size_t
-        lib.fsm_hip_text_file_lines_device.restype = C.c_void_p
-        lib.fsm_hip_text_files_ms.restype = C.c_double
-        C.set_errno(0)
+        self._lib = load_library()
         if data is not None:
             buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data, dtype=np.uint8)
         if data is not None and file_off is not None:
             fo = np.ascontiguousarray(file_off, dtype=np.uint64)
-            self._h = lib.fsm_hip_text_open_files(_ptr(buf) if buf.size else None, C.c_size_t(buf.size), C.c_int(delim),
-                                                  _ptr(fo) if fo.size else None, C.c_size_t(max(fo.size, 1) - 1))
-            what = "fsm_hip_text_open_files"
+            self._h = _call("fsm_hip_text_open_files", _ptr0(buf), buf.size, delim, _ptr0(fo), max(fo.size, 1) - 1)
         elif data is not None:
-            self._h = lib.fsm_hip_text_open(_ptr(buf) if buf.size else None, C.c_size_t(buf.size), C.c_int(delim))
-            what = "fsm_hip_text_open"
+            self._h = _call("fsm_hip_text_open", _ptr0(buf), buf.size, delim)
         elif file_off is not None:
             if not isinstance(file_off, (int, np.integer)):   # a host array: its device copy lives as long as the text
                 import torch
                 fo = np.ascontiguousarray(file_off, dtype=np.uint64)
                 self._file_off = torch.from_numpy(fo.view(np.int64).copy()).cuda() if fo.size else None
                 file_off, nfiles = (self._file_off.data_ptr() if fo.size else 0), max(fo.size, 1) - 1
-            self._h = lib.fsm_hip_text_open_files_device(C.c_void_p(d_text or None), C.c_size_t(nbytes), C.c_int(delim), C.c_void_p(int(file_off) or None),
-                                                         C.c_size_t(nfiles), C.c_void_p(stream or None))
-            what = "fsm_hip_text_open_files_device"
+            self._h = _call("fsm_hip_text_open_files_device", d_text or None, nbytes, delim, int(file_off) or None, nfiles, stream or None)
         else:
-            self._h = lib.fsm_hip_text_open_device(C.c_void_p(d_text or None), C.c_size_t(nbytes), C.c_int(delim), C.c_void_p(stream or None))
-            what = "fsm_hip_text_open_device"
-        if not self._h:
-            raise _oserr(what)
+            self._h = _call("fsm_hip_text_open_device", d_text or None, nbytes, delim, stream or None)
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.fsm_hip_text_free(C.c_void_p(self._h))
+            self._lib.fsm_hip_text_free(self._h)
             self._h = None
 
     __del__ = close
@@ -1517,111 +1222,71 @@ class HipText:
 
     @property
     def lines(self) -> int:
-        return int(self._lib.fsm_hip_text_lines(C.c_void_p(self._h)))
+        return int(self._lib.fsm_hip_text_lines(self._h))
 
     @property
     def d_off(self) -> int:
-        return int(self._lib.fsm_hip_text_offsets_device(C.c_void_p(self._h)) or 0)
+        return int(self._lib.fsm_hip_text_offsets_device(self._h) or 0)
 
     def offsets(self) -> np.ndarray:
         off = np.empty(self.lines + 1, np.uint64)
-        C.set_errno(0)
-        if self._lib.fsm_hip_text_offsets(C.c_void_p(self._h), _ptr(off)) != 0:
-            raise _oserr("fsm_hip_text_offsets")
+        _call("fsm_hip_text_offsets", self._h, _ptr(off))
         return off
 
     def scan_ms(self) -> float:
-        return float(self._lib.fsm_hip_text_scan_ms(C.c_void_p(self._h)))
+        return float(self._lib.fsm_hip_text_scan_ms(self._h))
 
     @property
     def files(self) -> int:
         """fsm_hip_text_files: 0 for a plain text"""
-        return int(self._lib.fsm_hip_text_files(C.c_void_p(self._h)))
+        return int(self._lib.fsm_hip_text_files(self._h))
 
     @property
     def file_lines_ptr(self) -> int:
-        return int(self._lib.fsm_hip_text_file_lines_device(C.c_void_p(self._h)) or 0)
+        return int(self._lib.fsm_hip_text_file_lines_device(self._h) or 0)
 
     def file_lines(self) -> np.ndarray:
         """fsm_hip_text_file_lines: the files + 1 line indices at which the files begin (raises EINVAL on a plain text)"""
         out = np.empty(self.files + 1, np.uint64)
-        C.set_errno(0)
-        if self._lib.fsm_hip_text_file_lines(C.c_void_p(self._h), _ptr(out)) != 0:
-            raise _oserr("fsm_hip_text_file_lines")
+        _call("fsm_hip_text_file_lines", self._h, _ptr(out))
         return out
 
     def files_ms(self) -> float:
-        return float(self._lib.fsm_hip_text_files_ms(C.c_void_p(self._h)))
+        return float(self._lib.fsm_hip_text_files_ms(self._h))
 
     def exec(self, ld: LinesDfa, ids_mode: int = 0, want_end=True, want_bitmap=False, want_eager=False, out: Optional[dict] = None):
         """fsm_hip_text_exec: dict(end=, bitmap=, ids=, eager=) with the outputs asked for (out: arrays to write into instead)."""
         n = self.lines
         if out is None:
-            out = {"end": np.empty(n, np.uint32) if want_end else None, "bitmap": np.zeros((n + 63) // 64, np.uint64) if want_bitmap else None,
-                   "ids": np.empty(n, np.uint32) if ids_mode else None,
+            end, bm = _outputs(n, want_end, want_bitmap)
+            out = {"end": end, "bitmap": bm, "ids": np.empty(n, np.uint32) if ids_mode else None,
                    "eager": np.zeros((n, ld.inner.eager_words()), np.uint64) if want_eager else None}
-        C.set_errno(0)
-        if self._lib.fsm_hip_text_exec(C.c_void_p(ld.handle), C.c_void_p(self._h), _ptr(out.get("end")), _ptr(out.get("bitmap")), C.c_int(ids_mode),
-                                       _ptr(out.get("ids")), _ptr(out.get("eager"))) != 0:
-            raise _oserr("fsm_hip_text_exec")
+        _call("fsm_hip_text_exec", ld.handle, self._h, _ptr(out.get("end")), _ptr(out.get("bitmap")), ids_mode, _ptr(out.get("ids")), _ptr(out.get("eager")))
         return out
 
     def exec_device(self, ld: LinesDfa, d_end: int = 0, d_bitmap: int = 0, ids_mode: int = 0, d_ids: int = 0, d_eager: int = 0, stream: int = 0):
-        C.set_errno(0)
-        vp = C.c_void_p
-        if self._lib.fsm_hip_text_exec_device(vp(ld.handle), vp(self._h), vp(d_end or None), vp(d_bitmap or None), C.c_int(ids_mode), vp(d_ids or None),
-                                              vp(d_eager or None), vp(stream or None)) != 0:
-            raise _oserr("fsm_hip_text_exec_device")
+        _call("fsm_hip_text_exec_device", ld.handle, self._h, d_end or None, d_bitmap or None, ids_mode, d_ids or None, d_eager or None, stream or None)
 
     def hits(self, ld: LinesDfa, invert: bool = False, want_bytes: bool = True) -> "HipHits":
         """fsm_hip_text_hits: walk the text with ld and select the accepted lines (invert: the others)."""
-        lib = self._lib
-        lib.fsm_hip_text_hits.restype = C.c_void_p
-        C.set_errno(0)
-        h = lib.fsm_hip_text_hits(C.c_void_p(ld.handle), C.c_void_p(self._h), C.c_uint(hits_flags(invert, want_bytes)))
-        if not h:
-            raise _oserr("fsm_hip_text_hits")
-        return HipHits(h, self)
+        return HipHits(_call("fsm_hip_text_hits", ld.handle, self._h, hits_flags(invert, want_bytes)), self)
 
     def hits_device(self, d_bitmap: int, invert: bool = False, want_bytes: bool = True, stream: int = 0, flags: Optional[int] = None) -> "HipHits":
         """fsm_hip_text_hits_device: select by a caller-made bitmap on the device (ceil(n / 64) words, bit i = line i), enqueued on
         `stream`.  flags: the raw flag word instead of invert / want_bytes."""
-        lib = self._lib
-        lib.fsm_hip_text_hits_device.restype = C.c_void_p
-        C.set_errno(0)
-        h = lib.fsm_hip_text_hits_device(C.c_void_p(self._h), C.c_void_p(d_bitmap or None),
-                                         C.c_uint(hits_flags(invert, want_bytes) if flags is None else flags), C.c_void_p(stream or None))
-        if not h:
-            raise _oserr("fsm_hip_text_hits_device")
-        return HipHits(h, self)
+        flags = hits_flags(invert, want_bytes) if flags is None else flags
+        return HipHits(_call("fsm_hip_text_hits_device", self._h, d_bitmap or None, flags, stream or None), self)
 
     def hits_context(self, ld: LinesDfa, before: int, after: int, invert: bool = False, want_bytes: bool = True) -> "HipHits":
         """fsm_hip_text_hits_context: the hits of the lines within `before` / `after` lines of an accepted line of the same file
         (grep -B / -A; any value below 2 ** 64), with the core and group marks."""
-        lib = self._lib
-        lib.fsm_hip_text_hits_context.restype = C.c_void_p
-        C.set_errno(0)
-        h = lib.fsm_hip_text_hits_context(C.c_void_p(ld.handle), C.c_void_p(self._h), C.c_uint(hits_flags(invert, want_bytes)),
-                                          C.c_uint64(before), C.c_uint64(after))
-        if not h:
-            raise _oserr("fsm_hip_text_hits_context")
-        return HipHits(h, self)
+        return HipHits(_call("fsm_hip_text_hits_context", ld.handle, self._h, hits_flags(invert, want_bytes), before, after), self)
 
     def hits_context_device(self, d_bitmap: int, before: int, after: int, invert: bool = False, want_bytes: bool = True, stream: int = 0,
                             flags: Optional[int] = None) -> "HipHits":
         """fsm_hip_text_hits_context_device: as hits_device, widened by the context."""
-        lib = self._lib
-        lib.fsm_hip_text_hits_context_device.restype = C.c_void_p
-        C.set_errno(0)
-        h = lib.fsm_hip_text_hits_context_device(C.c_void_p(self._h), C.c_void_p(d_bitmap or None),
-                                                 C.c_uint(hits_flags(invert, want_bytes) if flags is None else flags),
-                                                 C.c_uint64(before), C.c_uint64(after), C.c_void_p(stream or None))
-        if not h:
-            raise _oserr("fsm_hip_text_hits_context_device")
-        return HipHits(h, self)
-
-
-HITS_INVERT, HITS_NO_BYTES = 1, 2
+        flags = hits_flags(invert, want_bytes) if flags is None else flags
+        return HipHits(_call("fsm_hip_text_hits_context_device", self._h, d_bitmap or None, flags, before, after, stream or None), self)
 
 
 def hits_flags(invert: bool, want_bytes: bool) -> int:
@@ -1633,21 +1298,12 @@ class HipHits:
     alive: the hits must be freed first."""
 
     def __init__(self, handle, text: HipText):
-        self._lib = lib = load_library()
+        self._lib = load_library()
         self._h, self._text = handle, text
-        for f in ("count", "nbytes", "core_count", "groups"):
-            getattr(lib, "fsm_hip_text_hits_" + f).restype = C.c_size_t
-        for f in ("lines_device", "offsets_device", "bytes_device", "core_device", "group_device"):
-            getattr(lib, "fsm_hip_text_hits_" + f).restype = C.c_void_p
-        lib.fsm_hip_text_hits_ms.restype = C.c_double
-        lib.fsm_hip_text_hits_gather_ms.restype = C.c_double
-        lib.fsm_hip_text_hits_file_first_device.restype = C.c_void_p
-        lib.fsm_hip_text_hits_file_first_ms.restype = C.c_double
-        lib.fsm_hip_text_hits_context_ms.restype = C.c_double
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.fsm_hip_text_hits_free(C.c_void_p(self._h))
+            self._lib.fsm_hip_text_hits_free(self._h)
             self._h = None
             self._text = None
 
@@ -1659,28 +1315,26 @@ class HipHits:
 
     @property
     def count(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_count(C.c_void_p(self._h)))
+        return int(self._lib.fsm_hip_text_hits_count(self._h))
 
     @property
     def nbytes(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_nbytes(C.c_void_p(self._h)))
+        return int(self._lib.fsm_hip_text_hits_nbytes(self._h))
 
     @property
     def lines_device(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_lines_device(C.c_void_p(self._h)) or 0)
+        return int(self._lib.fsm_hip_text_hits_lines_device(self._h) or 0)
 
     @property
     def offsets_device(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_offsets_device(C.c_void_p(self._h)) or 0)
+        return int(self._lib.fsm_hip_text_hits_offsets_device(self._h) or 0)
 
     @property
     def bytes_device(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_bytes_device(C.c_void_p(self._h)) or 0)
+        return int(self._lib.fsm_hip_text_hits_bytes_device(self._h) or 0)
 
     def _copy(self, lines=None, off=None, data=None):
-        C.set_errno(0)
-        if self._lib.fsm_hip_text_hits_copy(C.c_void_p(self._h), _ptr(lines), _ptr(off), _ptr(data)) != 0:
-            raise _oserr("fsm_hip_text_hits_copy")
+        _call("fsm_hip_text_hits_copy", self._h, _ptr(lines), _ptr(off), _ptr(data))
 
     def lines(self) -> np.ndarray:
         out = np.empty(self.count, np.uint64)
@@ -1698,50 +1352,46 @@ class HipHits:
         return out
 
     def ms(self) -> float:
-        return float(self._lib.fsm_hip_text_hits_ms(C.c_void_p(self._h)))
+        return float(self._lib.fsm_hip_text_hits_ms(self._h))
 
     def gather_ms(self) -> float:
-        return float(self._lib.fsm_hip_text_hits_gather_ms(C.c_void_p(self._h)))
+        return float(self._lib.fsm_hip_text_hits_gather_ms(self._h))
 
     @property
     def file_first_ptr(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_file_first_device(C.c_void_p(self._h)) or 0)
+        return int(self._lib.fsm_hip_text_hits_file_first_device(self._h) or 0)
 
     def file_first(self) -> np.ndarray:
         """fsm_hip_text_hits_file_first: files + 1 entries, the hits of file j are [file_first[j], file_first[j + 1])"""
         out = np.empty(self._text.files + 1, np.uint64)
-        C.set_errno(0)
-        if self._lib.fsm_hip_text_hits_file_first(C.c_void_p(self._h), _ptr(out)) != 0:
-            raise _oserr("fsm_hip_text_hits_file_first")
+        _call("fsm_hip_text_hits_file_first", self._h, _ptr(out))
         return out
 
     def file_first_ms(self) -> float:
-        return float(self._lib.fsm_hip_text_hits_file_first_ms(C.c_void_p(self._h)))
+        return float(self._lib.fsm_hip_text_hits_file_first_ms(self._h))
 
     # hits with context (HipText.hits_context*); on plain hits: 0 from the pointers and the counts, EINVAL from the copies
     @property
     def core_ptr(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_core_device(C.c_void_p(self._h)) or 0)
+        return int(self._lib.fsm_hip_text_hits_core_device(self._h) or 0)
 
     @property
     def group_ptr(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_group_device(C.c_void_p(self._h)) or 0)
+        return int(self._lib.fsm_hip_text_hits_group_device(self._h) or 0)
 
     @property
     def core_count(self) -> int:
         """fsm_hip_text_hits_core_count: the selected lines, context left out (grep -c)"""
-        return int(self._lib.fsm_hip_text_hits_core_count(C.c_void_p(self._h)))
+        return int(self._lib.fsm_hip_text_hits_core_count(self._h))
 
     @property
     def groups(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_groups(C.c_void_p(self._h)))
+        return int(self._lib.fsm_hip_text_hits_groups(self._h))
 
     def _marks(self, which: int) -> np.ndarray:
         m = self.count
-        words = np.zeros((m + 63) // 64, np.uint64)
-        C.set_errno(0)
-        if self._lib.fsm_hip_text_hits_marks(C.c_void_p(self._h), _ptr(words) if which == 0 else None, _ptr(words) if which == 1 else None) != 0:
-            raise _oserr("fsm_hip_text_hits_marks")
+        words = _outputs(m, False)[1]
+        _call("fsm_hip_text_hits_marks", self._h, _ptr(words) if which == 0 else None, _ptr(words) if which == 1 else None)
         return np.unpackbits(words.view(np.uint8), bitorder="little")[:m].astype(bool)
 
     def core(self) -> np.ndarray:
@@ -1754,82 +1404,52 @@ class HipHits:
 
     def marks_words(self):
         """fsm_hip_text_hits_marks as it is: (core, group), ceil(m / 64) words each"""
-        core, group = np.zeros((self.count + 63) // 64, np.uint64), np.zeros((self.count + 63) // 64, np.uint64)
-        C.set_errno(0)
-        if self._lib.fsm_hip_text_hits_marks(C.c_void_p(self._h), _ptr(core), _ptr(group)) != 0:
-            raise _oserr("fsm_hip_text_hits_marks")
+        core, group = _outputs(self.count, False)[1], _outputs(self.count, False)[1]
+        _call("fsm_hip_text_hits_marks", self._h, _ptr(core), _ptr(group))
         return core, group
 
     def context_ms(self) -> float:
-        return float(self._lib.fsm_hip_text_hits_context_ms(C.c_void_p(self._h)))
-
+        return float(self._lib.fsm_hip_text_hits_context_ms(self._h))
 
 
 def text_block_bytes() -> int:
     """fsm_hip_text_block_bytes: bytes one workgroup of the delimiter scan covers per step."""
-    lib = load_library()
-    lib.fsm_hip_text_block_bytes.restype = C.c_size_t
-    return int(lib.fsm_hip_text_block_bytes())
+    return int(load_library().fsm_hip_text_block_bytes())
 
 
 def text_max_workgroups() -> int:
     """fsm_hip_text_max_workgroups: the most workgroups a scan launches on the current device."""
-    lib = load_library()
-    lib.fsm_hip_text_max_workgroups.restype = C.c_size_t
-    return int(lib.fsm_hip_text_max_workgroups())
+    return int(load_library().fsm_hip_text_max_workgroups())
 
 
 def text_hits_block_lines() -> int:
     """fsm_hip_text_hits_block_lines: lines one workgroup of the select covers per step."""
-    lib = load_library()
-    lib.fsm_hip_text_hits_block_lines.restype = C.c_size_t
-    return int(lib.fsm_hip_text_hits_block_lines())
+    return int(load_library().fsm_hip_text_hits_block_lines())
 
 
 def text_hits_block_bytes() -> int:
     """fsm_hip_text_hits_block_bytes: output bytes one workgroup of the gather covers per step."""
-    lib = load_library()
-    lib.fsm_hip_text_hits_block_bytes.restype = C.c_size_t
-    return int(lib.fsm_hip_text_hits_block_bytes())
+    return int(load_library().fsm_hip_text_hits_block_bytes())
 
 
 def text_files_block() -> int:
     """fsm_hip_text_files_block: file ends one round of the files scan takes."""
-    lib = load_library()
-    lib.fsm_hip_text_files_block.restype = C.c_size_t
-    return int(lib.fsm_hip_text_files_block())
+    return int(load_library().fsm_hip_text_files_block())
 
 
 def text_context_scan_block() -> int:
     """fsm_hip_text_context_scan_block: blocks of lines one round of the context scan takes."""
-    lib = load_library()
-    lib.fsm_hip_text_context_scan_block.restype = C.c_size_t
-    return int(lib.fsm_hip_text_context_scan_block())
+    return int(load_library().fsm_hip_text_context_scan_block())
 
 
 # ---- match positions: first / last accepting offset, spans of a text's hits (include/fsm_hip.h, "match positions") ----
-
-NO_POS = 0xFFFFFFFFFFFFFFFF
-POS_BACKWARD = 1
-
-
-class PosBatch(C.Structure):
-    """struct fsm_hip_pos_batch"""
-    _fields_ = [("base", C.c_void_p), ("off", C.c_void_p), ("n", C.c_size_t), ("pick", C.c_void_p), ("m", C.c_size_t),
-                ("from_", C.c_void_p), ("to", C.c_void_p), ("trim_byte", C.c_int), ("flags", C.c_uint),
-                ("first_out", C.c_void_p), ("last_out", C.c_void_p), ("limit", C.c_uint64)]
-
 
 class PosDfa:
     """struct fsm_hip_pos_dfa *: the device image of a HipDfa for the accept-position walk (the dfa may be closed afterwards)."""
 
     def __init__(self, dfa: "HipDfa"):
-        self._lib = lib = load_library()
-        lib.fsm_hip_pos_dfa_create.restype = C.c_void_p
-        C.set_errno(0)
-        self._h = lib.fsm_hip_pos_dfa_create(C.c_void_p(dfa.handle if dfa is not None else None))
-        if not self._h:
-            raise _oserr("fsm_hip_pos_dfa_create")
+        self._lib = load_library()
+        self._h = _call("fsm_hip_pos_dfa_create", dfa.handle if dfa is not None else None)
 
     @classmethod
     def from_flat(cls, flat: FlatDfa) -> "PosDfa":
@@ -1846,11 +1466,11 @@ class PosDfa:
 
     @property
     def in_lds(self) -> bool:
-        return bool(self._lib.fsm_hip_pos_dfa_in_lds(C.c_void_p(self._h)))
+        return bool(self._lib.fsm_hip_pos_dfa_in_lds(self._h))
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.fsm_hip_pos_dfa_free(C.c_void_p(self._h))
+            self._lib.fsm_hip_pos_dfa_free(self._h)
             self._h = None
 
     __del__ = close
@@ -1868,11 +1488,8 @@ class PosDfa:
         if pick is not None and m == 0:
             pick = np.zeros(1, np.uint64)   # an empty pick is still a pick: a non-NULL address
         first, last = out if out is not None else (np.empty(m, np.uint64) if want_first else None, np.empty(m, np.uint64) if want_last else None)
-        b = PosBatch(_ptr(base) if base.size else None, _ptr(off), n, _ptr(pick) if pick is not None else None, m, _ptr(frm), _ptr(to), trim_byte,
-                     POS_BACKWARD if backward else 0, _ptr(first), _ptr(last), 0)
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_accept_pos(C.c_void_p(self._h), C.byref(b)) != 0:
-            raise _oserr("fsm_hip_exec_accept_pos")
+        b = PosBatch(_ptr0(base), _ptr(off), n, _ptr(pick), m, _ptr(frm), _ptr(to), trim_byte, POS_BACKWARD if backward else 0, _ptr(first), _ptr(last), 0)
+        _call("fsm_hip_exec_accept_pos", self._h, C.byref(b))
         return first, last
 
     def accept_pos_device(self, d_base: int, d_off: int, n: int, d_first: int = 0, d_last: int = 0, d_pick: int = 0, m: int = 0, d_from: int = 0,
@@ -1880,9 +1497,7 @@ class PosDfa:
         """fsm_hip_exec_accept_pos_device: device addresses, asynchronous on `stream`"""
         b = PosBatch(d_base or None, d_off or None, n, d_pick or None, m, d_from or None, d_to or None, trim_byte, POS_BACKWARD if backward else 0,
                      d_first or None, d_last or None, limit)
-        C.set_errno(0)
-        if self._lib.fsm_hip_exec_accept_pos_device(C.c_void_p(self._h), C.byref(b), C.c_void_p(stream or None)) != 0:
-            raise _oserr("fsm_hip_exec_accept_pos_device")
+        _call("fsm_hip_exec_accept_pos_device", self._h, C.byref(b), stream or None)
 
 
 class HipSpans:
@@ -1890,23 +1505,14 @@ class HipSpans:
     the two images alive: the spans must be freed first."""
 
     def __init__(self, hits: "HipHits", starts: PosDfa, ends: PosDfa, stream: int = 0):
-        self._lib = lib = load_library()
-        lib.fsm_hip_text_hits_spans.restype = C.c_void_p
-        lib.fsm_hip_text_spans_count.restype = C.c_size_t
-        lib.fsm_hip_text_spans_start_device.restype = C.c_void_p
-        lib.fsm_hip_text_spans_end_device.restype = C.c_void_p
-        lib.fsm_hip_text_spans_ms.restype = C.c_double
+        self._lib = load_library()
         self._keep = (hits, hits._text, starts, ends)
         self._m = hits.count
-        C.set_errno(0)
-        self._h = lib.fsm_hip_text_hits_spans(C.c_void_p(hits.handle), C.c_void_p(hits._text.handle), C.c_void_p(starts.handle),
-                                              C.c_void_p(ends.handle), C.c_void_p(stream or None))
-        if not self._h:
-            raise _oserr("fsm_hip_text_hits_spans")
+        self._h = _call("fsm_hip_text_hits_spans", hits.handle, hits._text.handle, starts.handle, ends.handle, stream or None)
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.fsm_hip_text_spans_free(C.c_void_p(self._h))
+            self._lib.fsm_hip_text_spans_free(self._h)
             self._h = None
             self._keep = None
 
@@ -1914,30 +1520,26 @@ class HipSpans:
 
     def next(self) -> None:
         """fsm_hip_text_spans_next: every hit's search position moves behind its match; the two walks run again"""
-        C.set_errno(0)
-        if self._lib.fsm_hip_text_spans_next(C.c_void_p(self._h)) != 0:
-            raise _oserr("fsm_hip_text_spans_next")
+        _call("fsm_hip_text_spans_next", self._h)
 
     @property
     def count(self) -> int:
         """the hits with a span in the current round (one wait)"""
-        return int(self._lib.fsm_hip_text_spans_count(C.c_void_p(self._h)))
+        return int(self._lib.fsm_hip_text_spans_count(self._h))
 
     @property
     def start_ptr(self) -> int:
-        return int(self._lib.fsm_hip_text_spans_start_device(C.c_void_p(self._h)) or 0)
+        return int(self._lib.fsm_hip_text_spans_start_device(self._h) or 0)
 
     @property
     def end_ptr(self) -> int:
-        return int(self._lib.fsm_hip_text_spans_end_device(C.c_void_p(self._h)) or 0)
+        return int(self._lib.fsm_hip_text_spans_end_device(self._h) or 0)
 
     def copy(self):
         """-> (start, end), u64 [m] each, NO_POS where the hit has no span in this round"""
         start, end = np.empty(self._m, np.uint64), np.empty(self._m, np.uint64)
-        C.set_errno(0)
-        if self._lib.fsm_hip_text_spans_copy(C.c_void_p(self._h), _ptr(start), _ptr(end)) != 0:
-            raise _oserr("fsm_hip_text_spans_copy")
+        _call("fsm_hip_text_spans_copy", self._h, _ptr(start), _ptr(end))
         return start, end
 
     def ms(self) -> float:
-        return float(self._lib.fsm_hip_text_spans_ms(C.c_void_p(self._h)))
+        return float(self._lib.fsm_hip_text_spans_ms(self._h))

@@ -71,7 +71,6 @@ def test_empty_submission_is_zero(lib):
     out = C.c_void_p()
     assert lib.fsm_hip_multi_prepare_eager(None, None, C.c_size_t(0), C.c_int(1), C.byref(out)) == 0
     assert out.value
-    lib.fsm_hip_multi_prepared_free.restype = None
     lib.fsm_hip_multi_prepared_free(out)
     import libfsm_amd as hip
     assert hip.exec_multi_eager([], []) == []

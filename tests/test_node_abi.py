@@ -89,7 +89,6 @@ def test_null_arguments_are_einval_without_a_device(lib):
 
 
 def test_null_node_shard_queries(lib):
-    lib.fsm_hip_node_bitmap_words.restype = C.c_size_t
     f, c = C.c_size_t(7), C.c_size_t(7)
     lib.fsm_hip_node_shard(None, C.c_size_t(1000), C.c_int(0), C.byref(f), C.byref(c))
     assert (f.value, c.value) == (0, 0)

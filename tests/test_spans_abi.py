@@ -19,12 +19,6 @@ SYMBOLS = ("fsm_hip_pos_dfa_create", "fsm_hip_pos_dfa_free", "fsm_hip_pos_dfa_in
 def lib_of():
     from libfsm_amd import load_library
     lib = load_library()
-    lib.fsm_hip_pos_dfa_create.restype = C.c_void_p
-    lib.fsm_hip_text_hits_spans.restype = C.c_void_p
-    lib.fsm_hip_text_spans_count.restype = C.c_size_t
-    lib.fsm_hip_text_spans_start_device.restype = C.c_void_p
-    lib.fsm_hip_text_spans_end_device.restype = C.c_void_p
-    lib.fsm_hip_text_spans_ms.restype = C.c_double
     return lib
 
 

@@ -13,8 +13,6 @@ ALL = 2 ** 64 - 1
 def lib_of():
     from libfsm_amd import load_library
     lib = load_library()
-    lib.fsm_hip_text_hits_context.restype = C.c_void_p
-    lib.fsm_hip_text_hits_context_device.restype = C.c_void_p
     return lib
 
 
@@ -129,12 +127,6 @@ def test_no_context_hits_without_a_device(built):
 def test_accessors_take_null(built):
     import libfsm_amd
     lib = lib_of()
-    lib.fsm_hip_text_hits_core_device.restype = C.c_void_p
-    lib.fsm_hip_text_hits_group_device.restype = C.c_void_p
-    lib.fsm_hip_text_hits_core_count.restype = C.c_size_t
-    lib.fsm_hip_text_hits_groups.restype = C.c_size_t
-    lib.fsm_hip_text_hits_context_ms.restype = C.c_double
-    lib.fsm_hip_text_context_scan_block.restype = C.c_size_t
     out = np.zeros(4, np.uint64)
     assert lib.fsm_hip_text_hits_core_device(None) is None and lib.fsm_hip_text_hits_group_device(None) is None
     assert lib.fsm_hip_text_hits_core_count(None) == 0 and lib.fsm_hip_text_hits_groups(None) == 0

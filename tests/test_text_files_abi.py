@@ -11,8 +11,6 @@ import pytest
 def lib_of():
     from libfsm_amd import load_library
     lib = load_library()
-    lib.fsm_hip_text_open_files.restype = C.c_void_p
-    lib.fsm_hip_text_open_files_device.restype = C.c_void_p
     return lib
 
 
@@ -85,12 +83,6 @@ def test_no_files_text_without_a_device(built):
 
 def test_accessors_take_null(built):
     lib = lib_of()
-    lib.fsm_hip_text_files.restype = C.c_size_t
-    lib.fsm_hip_text_files_block.restype = C.c_size_t
-    lib.fsm_hip_text_file_lines_device.restype = C.c_void_p
-    lib.fsm_hip_text_hits_file_first_device.restype = C.c_void_p
-    lib.fsm_hip_text_files_ms.restype = C.c_double
-    lib.fsm_hip_text_hits_file_first_ms.restype = C.c_double
     out = np.zeros(4, np.uint64)
     assert lib.fsm_hip_text_files(None) == 0
     assert lib.fsm_hip_text_file_lines_device(None) is None and lib.fsm_hip_text_hits_file_first_device(None) is None

@@ -9,8 +9,6 @@ import numpy as np
 def lib_of():
     from libfsm_amd import load_library
     lib = load_library()
-    lib.fsm_hip_text_hits.restype = C.c_void_p
-    lib.fsm_hip_text_hits_device.restype = C.c_void_p
     return lib
 
 
@@ -44,18 +42,13 @@ def test_python_front_raises_without_a_device(built):
 
 def test_accessors_take_null(built):
     lib = lib_of()
-    lib.fsm_hip_text_hits_count.restype = C.c_size_t
-    lib.fsm_hip_text_hits_nbytes.restype = C.c_size_t
     assert lib.fsm_hip_text_hits_count(None) == 0 and lib.fsm_hip_text_hits_nbytes(None) == 0
     for f in ("lines_device", "offsets_device", "bytes_device"):
         fn = getattr(lib, "fsm_hip_text_hits_" + f)
-        fn.restype = C.c_void_p
         assert fn(None) is None
     out = np.zeros(4, np.uint64)
     C.set_errno(0)
     assert lib.fsm_hip_text_hits_copy(None, out.ctypes.data_as(C.c_void_p), None, None) == -1 and C.get_errno() == errno.EINVAL
-    lib.fsm_hip_text_hits_ms.restype = C.c_double
-    lib.fsm_hip_text_hits_gather_ms.restype = C.c_double
     C.set_errno(0)
     assert lib.fsm_hip_text_hits_ms(None) == -1.0 and C.get_errno() == errno.EINVAL
     assert lib.fsm_hip_text_hits_gather_ms(None) == -1.0

@@ -18,7 +18,6 @@ def main():
     flat = hip.FlatDfa.load(os.path.join(ROOT, "tests", "golden", "c1.npz"))
     dfa = hip.HipDfa(flat)
     s = b"xxLibfsmsmyy"
-    lib.fsm_hip_match_buffer.restype = C.c_int
     for _ in range(20):
         assert lib.fsm_hip_match_buffer(C.c_void_p(dfa._h), s, len(s)) == 1
     k = 2000

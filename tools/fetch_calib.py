@@ -27,7 +27,6 @@ def run():
     import torch
     import libfsm_amd as hip
     lib = hip.load_library()
-    lib.fsm_hip_gather_probe_ms.restype = C.c_double
     buf = torch.empty(BYTES, dtype=torch.uint8, device="cuda")
     buf.fill_(1)
     scratch = torch.zeros(4, dtype=torch.int32, device="cuda")
