@@ -56,6 +56,9 @@ enum {
 	                                  * straight-line record probes; 0 the chain loop over state ids (A/B measurement)   */
 	FSM_HIP_KNOB_LAZY_DYN      = 21, /* the lazy walk: 1 (default) wavefronts claim their tiles from a device counter, 0 static striding */
 	FSM_HIP_KNOB_LAZY_LINES    = 22, /* the lazy walk also serves variable-length / unaligned / resumed batches (walk_lazy_lines): 1 (default), 0 off (A/B) */
+	FSM_HIP_KNOB_PACK          = 23, /* the LDS-DMA walk that packs the rows which outlive their first segment across tiles (walk_ldsdma_pack):
+	                                  * -1 (default) where the per-lane load skip is on (bit 1 of the early-retire set), 0 never, 1 wherever
+	                                  * the kernel exists: plain walks, 128-byte segments, rows of 256 bytes and more, fewer than 2^32 rows */
 	FSM_HIP_KNOB_DMA_BUFS      = 15, /* retired (accepted, ignored): two DMA tiles per wave measured slower than one */
 	FSM_HIP_KNOB_RAGGED_ALIGN  = 14  /* retired (accepted, ignored): the ragged kernel fetches from the inputs' own byte addresses */
 };

@@ -100,6 +100,7 @@ struct fsm_hip_dfa {
 	int knob_seg = 0;            /* 0 auto (128) */
 	int knob_prefetch = -1;      /* -1 auto (on) */
 	int knob_nt = -1;            /* -1 auto */
+	int knob_pack = -1;          /* walk_ldsdma_pack: -1 auto (with the per-lane load skip), 0 never, 1 wherever the kernel exists */
 	int knob_rows = 0;           /* the lazy walk's inputs per lane; 0 auto */
 	int knob_waves = 0;          /* 0 auto */
 	int knob_blocks_per_cu = 0;  /* 0 auto */
@@ -613,6 +614,9 @@ static LaunchCfg pick_cfg(const fsm_hip_dfa *d, bool fast_ok, uint64_t stride, i
 		}
 	}
 	c.mode = mode;
+	/* the packing LDS-DMA walk exists for plain walks from the start state, 128-byte segments, rows of two segments and more, 32-bit
+	 * row indexes; launch_walk drops it again where the per-lane load skip is off (FSM_HIP_KNOB_PACK = -1) */
+	c.pack = mode == IN_LDSDMA && c.seg == 128 && !eager && !resumed && stride >= 256u && !many && d->knob_pack != 0;
 	const uint32_t per_wave = mode == IN_LDSDMA ? 64u * (uint32_t)c.seg : mode == IN_RAGGED ? ragged_wave_lds : 0u;
 	/* waves per block: as many behind one table copy as LDS holds, 16 at most: the tiny layouts keep a
 	 * 64 KiB column table (one private copy per lane / bank), which leaves 12 x 8 KiB tiles of the 160 KiB.
@@ -625,6 +629,7 @@ static LaunchCfg pick_cfg(const fsm_hip_dfa *d, bool fast_ok, uint64_t stride, i
 	else if (eager && mode == IN_LDSDMA) wmax = ((layout == FSM_HIP_LAYOUT_TINY && d->plan.tiny5_col.empty()) || layout == FSM_HIP_LAYOUT_COMB ||
 		                                            layout == FSM_HIP_LAYOUT_COMBSELF || layout == FSM_HIP_LAYOUT_LDSSELF) ? 12 : 16;   /* launch.h eager_dma_threads */
 	else if (layout == FSM_HIP_LAYOUT_COMBSELF && mode == IN_LDSDMA) wmax = 12;
+	else if (layout == FSM_HIP_LAYOUT_SPARSE && c.pack) wmax = 12;   /* launch.h ldsdma_pack_threads */
 	/* the plain row table behind LDS-DMA: its walk keeps the LDS array ~85 % busy (two reads per byte, the table read
 	 * replayed for bank conflicts: profiles/r04f_pmc_eager_lds.txt); 14 waves measured 4.24 / 4.01 TB/s where 16 gave
 	 * 3.77 / 3.71 and 12 4.01 / 3.99 (354- and 1132-state tables, 8e6 x 1 KiB: profiles/r04h_eager_probe_8M.txt).  The
@@ -636,7 +641,7 @@ static LaunchCfg pick_cfg(const fsm_hip_dfa *d, bool fast_ok, uint64_t stride, i
 	else if (layout == FSM_HIP_LAYOUT_TINY && mode == IN_GENERIC && !eager) wmax = 12;
 	int waves = d->knob_waves > 0 && d->knob_waves < wmax ? d->knob_waves : wmax;
 	if (!eager && mode != IN_RAGGED && d->knob_waves > wmax && d->knob_waves <= 16 &&
-	    !(layout == FSM_HIP_LAYOUT_COMBSELF && mode == IN_LDSDMA)) waves = d->knob_waves;   /* that kernel is compiled for 12 */
+	    !(layout == FSM_HIP_LAYOUT_COMBSELF && mode == IN_LDSDMA) && !(layout == FSM_HIP_LAYOUT_SPARSE && c.pack)) waves = d->knob_waves;   /* those kernels are compiled for 12 */
 	while (waves > 1 && d->table_lds + (uint32_t)waves * per_wave > d->lds_limit) waves -= (waves > 8 && mode != IN_RAGGED ? 2 : 1);
 	c.waves = waves;
 	c.lds = d->table_lds + (uint32_t)waves * per_wave;
@@ -768,7 +773,7 @@ static int launch_walk(const fsm_hip_dfa *d, WalkArgs a, bool fast_ok, hipStream
 	const int keager = eager != 0 && a.state_io != nullptr ? eager + 2 : eager;
 	const bool varlen = a.off != nullptr || a.off32 != nullptr || a.len != nullptr;
 	const uint64_t known_bytes = hint.bytes != 0 ? hint.bytes : !varlen ? (uint64_t)a.n * a.stride : 0;
-	const LaunchCfg c = pick_cfg(d, fast_ok, a.stride, eager, hint.short_mean, known_bytes >= ((uint64_t)1 << 36), a.state_io != nullptr, a.n >= ((uint64_t)1 << 32));
+	LaunchCfg c = pick_cfg(d, fast_ok, a.stride, eager, hint.short_mean, known_bytes >= ((uint64_t)1 << 36), a.state_io != nullptr, a.n >= ((uint64_t)1 << 32));
 	const uint64_t ntiles = (a.n + 63u) / 64u;
 	const uint64_t lazy_tile = 64u * (uint64_t)(c.lazy_rows > 0 ? c.lazy_rows : 2);      /* inputs per wavefront of the fixed-stride lazy walk */
 	uint64_t nblocks = c.mode == IN_LAZY ? ((a.n + lazy_tile - 1u) / lazy_tile + c.waves - 1) / c.waves
@@ -781,6 +786,7 @@ static int launch_walk(const fsm_hip_dfa *d, WalkArgs a, bool fast_ok, hipStream
 	if (d->knob_early >= 0) a.early = (uint32_t)d->knob_early;
 	else if (eager != 0 || a.state_io != nullptr) a.early &= ~2u;
 	if (d->knob_noskip > 0) a.early |= 4u;
+	if (!(a.early & 2u) && d->knob_pack < 1) c.pack = 0;   /* (bit 1 already says that an absorbing state can be reached) */
 
 	/* Variable-length inputs (the retest / rx front).  Short ones (mean < 96 bytes) walk fastest one per lane with per-lane
 	 * loads (walk_generic; a plain walk of a packed batch below 4 GiB: its 32-bit form walk_lines32), long ones in 128-byte
@@ -816,8 +822,8 @@ static int launch_walk(const fsm_hip_dfa *d, WalkArgs a, bool fast_ok, hipStream
 	fsm_hip_dfa *md = const_cast<fsm_hip_dfa *>(d);
 	DfaLock lk(md->mu);   /* the timing events, the flag ring and the tile-base block are per dfa */
 	hipError_t e = hipSuccess;
-	/* the ragged kernel sets bitmap bits one input at a time */
-	if ((c.mode == IN_RAGGED || c.mode == IN_LAZY_LINES) && a.bitmap != nullptr) e = zero_async(a.bitmap, ntiles * sizeof(uint64_t), s);
+	/* the ragged kernel sets bitmap bits one input at a time, the packing LDS-DMA walk ORs in the words of its packed tiles */
+	if ((c.mode == IN_RAGGED || c.mode == IN_LAZY_LINES || c.pack) && a.bitmap != nullptr) e = zero_async(a.bitmap, ntiles * sizeof(uint64_t), s);
 	if (e == hipSuccess && ((c.mode == IN_LAZY && d->knob_lazy_dyn) || c.mode == IN_LAZY_LINES) && d->d_lazy_ctr != nullptr) {
 		a.tile_ctr = d->d_lazy_ctr + (md->lazy_ctr_next++ % LAZY_CTRS);
 		e = zero_async(a.tile_ctr, sizeof(uint32_t), s);
@@ -1518,6 +1524,7 @@ extern "C" int fsm_hip_dfa_tune(struct fsm_hip_dfa *d, int knob, int value)
 	case FSM_HIP_KNOB_SEG: d->knob_seg = value; break;
 	case FSM_HIP_KNOB_PREFETCH: d->knob_prefetch = value; break;
 	case FSM_HIP_KNOB_NT: d->knob_nt = value; break;
+	case FSM_HIP_KNOB_PACK: d->knob_pack = value < 0 ? -1 : value != 0; break;
 	case FSM_HIP_KNOB_HOT_BYTES:
 		if (d->plan.layout != FSM_HIP_LAYOUT_GLOBAL || value < 0) { errno = EINVAL; return -1; }
 		set_hot_bytes(d, (uint32_t)value);

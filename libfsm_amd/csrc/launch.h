@@ -20,6 +20,7 @@ struct LaunchCfg {
 	int seg;             /* LDS-DMA: 64 or 128 */
 	int prefetch;        /* direct: register double-buffer (0: <= 64 VGPRs, occupancy instead) */
 	int nt;              /* LDS-DMA, 128-byte segments: nontemporal loads */
+	int pack;            /* LDS-DMA, 128-byte segments, plain walk: the kernel that packs surviving rows across tiles (walk_ldsdma_pack) */
 	int sparse_fast;     /* sparse layout, per-lane loads, plain walk: the entry-as-state policy (SparseFastPol) */
 	int lazy_abs;        /* IN_LAZY: an absorbing state is reachable (the kernel variant that tests for one) */
 	int lazy_rows;       /* IN_LAZY: inputs per lane (3, or 2 / 4 by FSM_HIP_KNOB_ROWS: A/B) */
@@ -66,6 +67,12 @@ static inline hipError_t launch_fn(walk_fn k, const LaunchCfg &c, const WalkArgs
 template <class Pol> struct ldsdma_threads { static constexpr int value = 1024; };
 template <> struct ldsdma_threads<CombSelfPol> { static constexpr int value = 768; };
 
+/* ... and of the packing LDS-DMA kernel: the sparse layout's record probes and the 64-bit columns want more than 128 registers
+ * next to the queue */
+template <class Pol> struct ldsdma_pack_threads { static constexpr int value = ldsdma_threads<Pol>::value; };
+template <> struct ldsdma_pack_threads<SparsePol> { static constexpr int value = 768; };
+template <> struct ldsdma_pack_threads<TinyPol<uint64_t>> { static constexpr int value = 768; };   /* (its 64 KiB table leaves room for 12 tiles anyway) */
+
 /* plain walk: every input path */
 template <class Pol>
 static hipError_t launch_pol(const LaunchCfg &c, const WalkArgs &a, dim3 grid, dim3 block, hipStream_t s)
@@ -91,7 +98,8 @@ static hipError_t launch_pol(const LaunchCfg &c, const WalkArgs &a, dim3 grid, d
 		} else k = walk_generic<Pol>;
 		break;
 	case IN_LDSDMA:
-		if (c.seg == 128) k = c.nt ? walk_ldsdma<Pol, 128, 2, ldsdma_threads<Pol>::value> : walk_ldsdma<Pol, 128, 0, ldsdma_threads<Pol>::value>;
+		if (c.seg == 128 && c.pack) k = c.nt ? walk_ldsdma_pack<Pol, 2, ldsdma_pack_threads<Pol>::value> : walk_ldsdma_pack<Pol, 0, ldsdma_pack_threads<Pol>::value>;
+		else if (c.seg == 128) k = c.nt ? walk_ldsdma<Pol, 128, 2, ldsdma_threads<Pol>::value> : walk_ldsdma<Pol, 128, 0, ldsdma_threads<Pol>::value>;
 		else k = walk_ldsdma<Pol, 64, 0, ldsdma_threads<Pol>::value>;
 		break;
 	default:

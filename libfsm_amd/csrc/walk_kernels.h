@@ -38,6 +38,8 @@
  *                global_load_lds_dwordx4 straight into a 4 / 8 KiB per-wave LDS tile, piece-rotated so
  *                that the row-per-lane ds_read_b128 that follows is bank-conflict-free; no VGPR
  *                staging, no ds_write.
+ *   walk_ldsdma_pack  the same (128-byte segments) for batches in which many rows die early: the rows that outlive
+ *                their first segment are queued in registers and walked 64 at a time as packed tiles.
  *   walk_direct  every lane reads its own row 16 bytes at a time, NB = 4 or 8 chunks in flight;
  *   walk_direct_np  the same without the register double-buffer (<= 64 VGPRs, occupancy instead).
  * Any length / alignment / packed offsets:
@@ -53,6 +55,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+
+#include "pack_queue.h"
 
 namespace fsmhip {
 
@@ -1469,6 +1473,82 @@ typedef __attribute__((address_space(1))) const void glb_void_t;
  * AUX = 2 marks the DMA loads nontemporal: every input line is used exactly once (SEG = 128), so
  * it need not displace the transition table from L2.
  */
+#ifndef FSMHIP_AHEAD0
+#define FSMHIP_AHEAD0 1
+#endif
+
+/* the tile has landed: every reader lane takes its row's SEG bytes into registers; the slot is reusable on return */
+template <int SEG>
+__device__ __forceinline__ void ldsdma_read_tile(u32x4 (&w)[SEG / 16][1], const unsigned char *rd, uint32_t rot)
+{
+	constexpr uint32_t PIECES = SEG / 16u;
+	__builtin_amdgcn_s_waitcnt(0x0F70); /* vmcnt(0): the tile has landed */
+	__asm__ volatile("" ::: "memory");
+#pragma unroll
+	for (uint32_t p = 0; p < PIECES; p++)
+		w[p][0] = *reinterpret_cast<const u32x4 *>(rd + ((p + rot) & (PIECES - 1u)) * 16u);
+	__builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0): tile is in registers, slot reusable */
+	__asm__ volatile("" ::: "memory");
+}
+
+/* ask for the SEG bytes at `off` of the tile's rows */
+template <class Pol, int SEG, int AUX>
+__device__ __forceinline__ void ldsdma_request(const WalkArgs &a, const typename Pol::S &st, const unsigned char *const (&src)[SEG / 16], uint64_t off,
+                                               unsigned char *stg, uint32_t lr)
+{
+	constexpr uint32_t NDMA = SEG / 16u, RPI = 64u / NDMA;
+	if (a.early & 2u) {
+		/* A lane in an absorbing state stops reading its row, as fsm_exec stops pulling bytes at a
+		 * missing edge (exec.c:133-138): the rows of the lanes that are absorbing NOW are left out of
+		 * the next tile (their slots keep stale bytes, which an absorbing state ignores -- and which
+		 * pass every chunk-level skip test, an absorbing state looping on all 256 bytes). */
+		const uint64_t mine = __ballot(Pol::code(st) >= a.abs_min) >> lr;   /* bit j * RPI: row j * RPI + lr */
+#pragma unroll
+		for (uint32_t j = 0; j < NDMA; j++)
+			if (!((mine >> (j * RPI)) & 1u))
+				__builtin_amdgcn_global_load_lds((glb_void_t *)(src[j] + off), (lds_void_t *)(stg + j * 1024u), 16, 0, AUX);
+	} else {
+#pragma unroll
+		for (uint32_t j = 0; j < NDMA; j++)
+			__builtin_amdgcn_global_load_lds((glb_void_t *)(src[j] + off), (lds_void_t *)(stg + j * 1024u), 16, 0, AUX);
+	}
+}
+
+/* The rounds s0 .. nseg - 1 of one tile, segment s0 requested by the caller: wait, read the tile, request the next segment, walk.
+ * Shared by walk_ldsdma (FIRST: from the tile's first segment, with its AHEAD0 rule) and walk_ldsdma_pack (from the second). */
+template <class Pol, int SEG, int AUX, bool FIRST>
+__device__ __forceinline__ void ldsdma_rounds(const Pol &pol, const WalkArgs &a, typename Pol::S (&st)[1], const unsigned char *const (&src)[SEG / 16],
+                                              unsigned char *stg, const unsigned char *rd, uint32_t rot, uint32_t lr, uint32_t s0, uint32_t nseg)
+{
+	constexpr uint32_t PIECES = SEG / 16u;
+	constexpr uint32_t AHEAD0 = FSMHIP_AHEAD0 < PIECES ? FSMHIP_AHEAD0 : PIECES;   /* pieces of a row's first segment walked before its second is requested */
+	for (uint32_t s = s0; s < nseg; s++) {
+		u32x4 w[PIECES][1];
+		ldsdma_read_tile<SEG>(w, rd, rot);
+		/* The first segment under the per-lane load skip: its first AHEAD0 pieces are walked BEFORE the second segment is asked
+		 * for, so that a row which dies in its first 16 * AHEAD0 bytes (random text against anchored patterns: every such row)
+		 * costs one segment, not two, and a tile whose 64 rows all die there 8 KiB, not 16.  The tile is in registers by now;
+		 * what the request waits for is one piece's walk.  From the second segment on the request goes out first, as before. */
+		const bool ahead = FIRST && AHEAD0 != 0u && s == 0 && (a.early & 2u);
+		if (ahead) {
+#pragma unroll
+			for (uint32_t p = 0; p < AHEAD0; p++) step16<Pol, 1>(pol, st, w[p]);
+		}
+		if (s + 1 < nseg) ldsdma_request<Pol, SEG, AUX>(a, st[0], src, (uint64_t)(s + 1) * SEG, stg, lr);
+		if (ahead) {
+#pragma unroll
+			for (uint32_t p = AHEAD0; p < PIECES; p++) step16<Pol, 1>(pol, st, w[p]);
+		} else {
+#pragma unroll
+			for (uint32_t p = 0; p < PIECES; p++) step16<Pol, 1>(pol, st, w[p]);
+		}
+		if ((a.early & 1u) && __all(Pol::code(st[0]) >= a.abs_min)) {
+			__builtin_amdgcn_s_waitcnt(0x0F70); /* drain the prefetch before the tile is reused */
+			break;
+		}
+	}
+}
+
 template <class Pol, int SEG, int AUX, int MAXT = 1024>
 __global__ void __launch_bounds__(MAXT)
 walk_ldsdma(const WalkArgs a)
@@ -1478,10 +1558,6 @@ walk_ldsdma(const WalkArgs a)
 	constexpr uint32_t NDMA = PIECES;           /* DMA instructions per tile: 4 | 8 */
 	constexpr uint32_t ROTSH = SEG == 64 ? 2u : 1u;
 	constexpr uint32_t TILE = 64u * SEG;
-#ifndef FSMHIP_AHEAD0
-#define FSMHIP_AHEAD0 1
-#endif
-	constexpr uint32_t AHEAD0 = FSMHIP_AHEAD0 < PIECES ? FSMHIP_AHEAD0 : PIECES;   /* pieces of a row's first segment walked before its second is requested */
 
 	extern __shared__ __align__(16) unsigned char lds[];
 	Pol pol;
@@ -1517,57 +1593,173 @@ walk_ldsdma(const WalkArgs a)
 #pragma unroll
 		for (uint32_t j = 0; j < NDMA; j++)
 			__builtin_amdgcn_global_load_lds((glb_void_t *)(src[j]), (lds_void_t *)(stg + j * 1024u), 16, 0, AUX);
-		for (uint32_t s = 0; s < nseg; s++) {
-			__builtin_amdgcn_s_waitcnt(0x0F70); /* vmcnt(0): the tile has landed */
-			__asm__ volatile("" ::: "memory");
-			u32x4 w[PIECES][1];
-#pragma unroll
-			for (uint32_t p = 0; p < PIECES; p++)
-				w[p][0] = *reinterpret_cast<const u32x4 *>(rd + ((p + rot) & (PIECES - 1u)) * 16u);
-			__builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0): tile is in registers, slot reusable */
-			__asm__ volatile("" ::: "memory");
-			/* The first segment under the per-lane load skip: its first AHEAD0 pieces are walked BEFORE the second segment is asked
-			 * for, so that a row which dies in its first 16 * AHEAD0 bytes (random text against anchored patterns: every such row)
-			 * costs one segment, not two, and a tile whose 64 rows all die there 8 KiB, not 16.  The tile is in registers by now;
-			 * what the request waits for is one piece's walk.  From the second segment on the request goes out first, as before. */
-			const bool ahead = AHEAD0 != 0u && s == 0 && (a.early & 2u);
-			if (ahead) {
-#pragma unroll
-				for (uint32_t p = 0; p < AHEAD0; p++) step16<Pol, 1>(pol, st, w[p]);
-			}
-			if (s + 1 < nseg) {
-				if (a.early & 2u) {
-					/* A lane in an absorbing state stops reading its row, as fsm_exec stops pulling bytes at a
-					 * missing edge (exec.c:133-138): the rows of the lanes that are absorbing NOW are left out of
-					 * the next tile (their slots keep stale bytes, which an absorbing state ignores -- and which
-					 * pass every chunk-level skip test, an absorbing state looping on all 256 bytes). */
-					const uint64_t mine = __ballot(Pol::code(st[0]) >= a.abs_min) >> lr;   /* bit j * RPI: row j * RPI + lr */
-#pragma unroll
-					for (uint32_t j = 0; j < NDMA; j++)
-						if (!((mine >> (j * RPI)) & 1u))
-							__builtin_amdgcn_global_load_lds((glb_void_t *)(src[j] + (uint64_t)(s + 1) * SEG),
-							                                 (lds_void_t *)(stg + j * 1024u), 16, 0, AUX);
-				} else {
-#pragma unroll
-					for (uint32_t j = 0; j < NDMA; j++)
-						__builtin_amdgcn_global_load_lds((glb_void_t *)(src[j] + (uint64_t)(s + 1) * SEG),
-						                                 (lds_void_t *)(stg + j * 1024u), 16, 0, AUX);
-				}
-			}
-			if (ahead) {
-#pragma unroll
-				for (uint32_t p = AHEAD0; p < PIECES; p++) step16<Pol, 1>(pol, st, w[p]);
-			} else {
-#pragma unroll
-				for (uint32_t p = 0; p < PIECES; p++) step16<Pol, 1>(pol, st, w[p]);
-			}
-			if ((a.early & 1u) && __all(Pol::code(st[0]) >= a.abs_min)) {
-				__builtin_amdgcn_s_waitcnt(0x0F70); /* drain the prefetch before the tile is reused */
-				break;
-			}
-		}
+		ldsdma_rounds<Pol, SEG, AUX, true>(pol, a, st, src, stg, rd, rot, lr, 0u, nseg);
 		write_result(a, tile, i, valid, Pol::code(st[0]));
 		finish_state(pol, a, i, valid, st[0], 0);
+	}
+}
+
+/*
+ * walk_ldsdma_pack: walk_ldsdma for batches in which many rows die early (plain walks under the per-lane load skip, 128-byte
+ * segments, rows of two segments and more, n < 2^32: launch_walk decides).  A tile whose rows mostly live is walked IN PLACE
+ * by walk_ldsdma's own rounds.  Of any other tile only the first segment is walked in place; the rows that outlive it go,
+ * as (row index, state code), into a queue the wavefront keeps in registers (pack_queue.h), and whenever 64 are pending they
+ * are walked from their second segment on as one PACKED tile: 64 live rows, a full 8 KiB in flight, where the in-place walk
+ * would go through all its rounds with the dead lanes idle.  What is left after the wavefront's last tile is walked as one
+ * packed tile whose idle lanes walk a copy of entry 0 and write nothing.
+ *
+ * The queue is filled at ONE point per tile, through the wavefront's own LDS tile (free then: read into registers, nothing
+ * requested): survivors write their entry at count + rank, every lane reads positions lane and 64 + lane.  The rows of a
+ * packed tile come from several source tiles, so their accept bits are ORed into a bitmap the launch zeroed, one atomic per
+ * distinct word: the word's bits are gathered through 64 flags in the LDS tile.  A tile walked in place stores its word.
+ * Plain policies only (init() is pure, finish() empty): the state travels as its code.
+ */
+template <class Pol, int AUX, int MAXT = 1024>
+__global__ void __launch_bounds__(MAXT)
+walk_ldsdma_pack(const WalkArgs a)
+{
+	constexpr int SEG = 128;
+	constexpr uint32_t PIECES = SEG / 16u, RPI = 64u / PIECES, NDMA = PIECES, ROTSH = 1u, TILE = 64u * SEG;
+	typedef __attribute__((address_space(3))) volatile uint32_t lds_vu32_t;
+
+	extern __shared__ __align__(16) unsigned char lds[];
+	Pol pol;
+	pol.setup(lds, a);
+	__syncthreads();
+
+	const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), nw = blockDim.x >> 6;
+	unsigned char *stg = lds + Pol::lds_bytes(a.tab_bytes) + wave * TILE;
+	lds_vu32_t *scr = (lds_vu32_t *)(lds_void_t *)stg;   /* the tile as scratch, while no request is out and its bytes are in registers */
+	const uint64_t ntiles = (a.n + 63u) / 64u;
+	const uint32_t nseg = (uint32_t)(a.stride / SEG); /* host guarantees stride % SEG == 0 and nseg >= 2 */
+
+	const uint32_t lr = lane / PIECES, lq = lane % PIECES;          /* loader role */
+	const uint32_t rj = lane / RPI, rr = lane % RPI;                /* reader role */
+	const unsigned char *rd = stg + rj * 1024u + rr * SEG;
+	const uint32_t rot = (lane >> ROTSH) & (PIECES - 1u);
+
+	uint32_t qrow[2] = { 0u, 0u }, qcode[2] = { a.start, a.start };   /* the pending queue: positions lane and 64 + lane */
+	uint32_t count = 0;                                               /* wave-uniform */
+
+	uint64_t tile = (uint64_t)blockIdx.x * nw + wave;
+	for (bool more = true; more; tile += (uint64_t)gridDim.x * nw) {
+		const uint64_t i = tile * 64u + lane;
+		const bool valid = i < a.n;
+		const unsigned char *src[NDMA];
+		typename Pol::S st[1];
+		bool in_place = false;
+		uint32_t take = 0;   /* queue entries walked this turn: 0, 64, or what is left at the end */
+		if (tile < ntiles) {
+			const uint64_t row0 = tile * 64u;
+#pragma unroll
+			for (uint32_t j = 0; j < NDMA; j++) {
+				const uint32_t ri = j * RPI + lr;
+				uint64_t row = row0 + ri;
+				if (row >= a.n) row = a.n - 1;
+				const uint32_t piece = (lq - ((ri >> ROTSH) & (PIECES - 1u))) & (PIECES - 1u);
+				src[j] = a.base + row * a.stride + piece * 16u;
+			}
+			st[0] = pol.init(a.start);
+#pragma unroll
+			for (uint32_t j = 0; j < NDMA; j++)
+				__builtin_amdgcn_global_load_lds((glb_void_t *)(src[j]), (lds_void_t *)(stg + j * 1024u), 16, 0, AUX);
+			u32x4 w[PIECES][1];
+			ldsdma_read_tile<SEG>(w, rd, rot);
+			step16<Pol, 1>(pol, st, w[0]);
+			in_place = pack_in_place(__ballot(valid && Pol::code(st[0]) < a.abs_min));
+			if (in_place) ldsdma_request<Pol, SEG, AUX>(a, st[0], src, SEG, stg, lr);
+#pragma unroll
+			for (uint32_t p = 1; p < PIECES; p++) step16<Pol, 1>(pol, st, w[p]);
+			if (!in_place) {
+				/* the one packing point: rows that are absorbing now are finished, the others queue up */
+				const uint32_t code = Pol::code(st[0]);
+				const bool fin = valid && code >= a.abs_min;
+				const uint64_t live = __ballot(valid && code < a.abs_min);
+				uint32_t end = FSMHIP_NO_MATCH;
+				const uint32_t idx = fin_index(a, code);
+				if (fin) end = a.fin[idx];
+				if (fin && a.end_out != nullptr) a.end_out[i] = end;
+				if (fin && a.out2 != nullptr) a.out2[i] = a.fin2[idx];
+				const uint64_t m = __ballot(fin && end != FSMHIP_NO_MATCH);
+				if (a.bitmap != nullptr && lane == 0 && m != 0)
+					__hip_atomic_fetch_or(a.bitmap + tile, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				if (live != 0) {
+					if (valid && code < a.abs_min) {
+						const uint32_t pos = pack_pos(count, live, lane);
+						scr[pos] = (uint32_t)i;
+						scr[128u + pos] = code;
+					}
+					const uint32_t r0 = scr[lane], r1 = scr[64u + lane], c0 = scr[128u + lane], c1 = scr[192u + lane];
+					__builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0): the scratch has been read before the tile is requested into again */
+					__asm__ volatile("" ::: "memory");
+					const uint32_t ncount = pack_push(count, live);
+					if (lane >= count && lane < ncount) { qrow[0] = r0; qcode[0] = c0; }
+					if (64u + lane < ncount) { qrow[1] = r1; qcode[1] = c1; }
+					count = ncount;
+				}
+				if (pack_fires(count)) take = PACK_TILE;
+			}
+		} else {
+			take = count;
+			more = false;
+		}
+		if (!in_place) {
+			if (take == 0) continue;
+			/* a packed tile of queue positions 0 .. take - 1; idle lanes (the last turn only) walk a copy of entry 0 */
+			const uint32_t row_e0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)qrow[0]), code_e0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)qcode[0]);
+			if (lane >= take) {
+				qrow[0] = row_e0;
+				qcode[0] = code_e0;
+			}
+#pragma unroll
+			for (uint32_t j = 0; j < NDMA; j++) {
+				const uint32_t ri = j * RPI + lr;   /* the reader lane this loader loads for: its row comes from that lane's entry */
+				const uint32_t row = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(ri * 4u), (int)qrow[0]);
+				const uint32_t piece = (lq - ((ri >> ROTSH) & (PIECES - 1u))) & (PIECES - 1u);
+				src[j] = a.base + (uint64_t)row * a.stride + piece * 16u;
+			}
+			st[0] = pol.init(qcode[0]);
+#pragma unroll
+			for (uint32_t j = 0; j < NDMA; j++)
+				__builtin_amdgcn_global_load_lds((glb_void_t *)(src[j] + SEG), (lds_void_t *)(stg + j * 1024u), 16, 0, AUX);
+		}
+		if (in_place && (a.early & 1u) && __all(Pol::code(st[0]) >= a.abs_min))
+			__builtin_amdgcn_s_waitcnt(0x0F70); /* drain the prefetch before the tile is reused */
+		else
+			ldsdma_rounds<Pol, SEG, AUX, false>(pol, a, st, src, stg, rd, rot, lr, 1u, nseg);
+		if (in_place) {
+			write_result(a, tile, i, valid, Pol::code(st[0]));
+			continue;
+		}
+		const uint32_t row = qrow[0];
+		const bool act = lane < take;
+		uint32_t end = FSMHIP_NO_MATCH;
+		const uint32_t idx = fin_index(a, Pol::code(st[0]));
+		if (act) end = a.fin[idx];
+		if (act && a.end_out != nullptr) a.end_out[row] = end;
+		if (act && a.out2 != nullptr) a.out2[row] = a.fin2[idx];
+		if (a.bitmap != nullptr) {
+			/* one atomic per distinct bitmap word: the word's lanes raise flag row % 64 in the tile, a ballot reads the 64 flags */
+			const bool hit = act && end != FSMHIP_NO_MATCH;
+			const uint32_t wd = row >> 6;
+			uint64_t rem = __ballot(hit);
+			while (rem != 0) {
+				const uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)wd, (int)__builtin_ctzll(rem));
+				const bool same = hit && wd == w0;
+				scr[lane] = 0u;
+				if (same) scr[row & 63u] = 1u;
+				const uint64_t bits = __ballot(scr[lane] != 0u);
+				if (lane == 0) __hip_atomic_fetch_or(a.bitmap + w0, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				rem &= ~__ballot(same);
+			}
+			__builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0) */
+			__asm__ volatile("" ::: "memory");
+		}
+		if (take == PACK_TILE) {
+			qrow[0] = qrow[1];
+			qcode[0] = qcode[1];
+			count = pack_pop(count);
+		} else count = 0;
 	}
 }
 
