@@ -1,6 +1,6 @@
 """GPU (-m gpu), round 6: the whole-device front for ONE big input (file.hip), the record walk back on the 32-bit lines
 kernel under the harness that once showed it losing a state, and the checks of what the round changed underneath (the
-queue-based lazy walk of packed lines, the 2-byte global table)."""
+2-byte global table; the queue-based lazy walk of packed lines has its own file: tests/test_gpu_lazy_front.py)."""
 import os
 import subprocess
 import sys
