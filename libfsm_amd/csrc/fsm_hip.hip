@@ -22,6 +22,7 @@
 #include "../../include/fsm_hip.h"
 #include "../../include/fsm_hip_plan.h"
 #include "plan.h"
+#include "image.h"
 #include "dfa_access.h"
 #include "launch.h"
 #include "gen_kernels.h"
@@ -48,15 +49,13 @@ struct fsm_hip_dfa {
 	unsigned lazy_ctr_next = 0;
 	int knob_lazy_lines = 1;                         /* the lazy walk also serves the variable-length fronts and resumed walks (0: walk_ragged / walk_generic over the records, for A/B runs) */
 	int knob_lazy_dyn = 1;                           /* the lazy walk's wavefronts claim their tiles from a counter (0: static striding) */
+	Image img;                                       /* what the layout's tables were uploaded from (image.h): built with the upload */
 	/* device end-id delivery (built on first use) */
-	std::vector<uint32_t> fin_host;                 /* copy of the fin table uploaded to d_fin */
 	DevBuf<uint32_t> d_fin_earliest, d_fin_ret;
-	std::vector<uint32_t> ret_off, ret_ids;          /* de-duplicated id sets, CSR */
+	IdTables ids;                                    /* (its by-fin-index tables go once they are on the device) */
 	bool ids_ready = false;
-	uint32_t ids_conflict = FSM_HIP_NO_MATCH;        /* lowest end state carrying more than one id */
 	/* resume tables (built on first use) */
 	DevBuf<uint32_t> d_enc_of, d_orig_of;
-	std::vector<uint32_t> enc_host;                  /* [S1] encoded state per renumbered state */
 	bool resume_ready = false;
 	DevBuf<uint64_t> d_emask;                        /* eager-output masks, indexed like fin */
 	DevBuf<uint32_t> d_ew_off, d_ew_word;            /* wide eager sets (> 64 ids) */
@@ -94,9 +93,6 @@ struct fsm_hip_dfa {
 	/* tuning knobs (fsm_hip_dfa_tune) */
 	int knob_input_mode = -1;    /* -1 auto */
 	int knob_nb = 0;             /* 0 auto */
-	uint32_t glob_row_bytes = 4;
-	bool glob16 = false;         /* GLOBAL layout, <= 65 535 states: 2-byte entries (Glob16Pol) */
-	uint64_t glob_tab_bytes = 0;
 	int knob_seg = 0;            /* 0 auto (128) */
 	int knob_prefetch = -1;      /* -1 auto (on) */
 	int knob_nt = -1;            /* -1 auto */
@@ -125,21 +121,24 @@ struct fsm_hip_dfa {
  * keeps in LDS.  The walk is bound by L2 gather requests and every lookup served from LDS is one
  * less: on a 6.7 MB table 0 / 40 / 80 / 120 KiB of hot rows measured 265 / 314 / 350 / 360 GB/s
  * (profiles/r01_c5_global_hot.txt), so the default takes what LDS offers. */
+static uint32_t layout_lds_bytes(const fsm_hip_dfa *d, uint32_t tab_bytes);   /* (beside launch_layout()) */
+
 static void set_hot_bytes(fsm_hip_dfa *d, uint32_t want)
 {
+	const Image &g = d->img;
 	uint64_t hot = want;
-	if (hot > d->glob_tab_bytes) hot = d->glob_tab_bytes;
+	if (hot > g.glob_tab_bytes) hot = g.glob_tab_bytes;
 	/* (the 4-byte table leaves room for eight wavefronts' LDS-DMA tiles; the 2-byte one is walked with per-lane loads and takes
 	 * all of LDS: every row there is a step that stays out of L2) */
-	const uint32_t keep = d->glob16 ? 64u : 8u * 4096u;
+	const uint32_t keep = g.glob16 ? 64u : 8u * 4096u;
 	if (hot + lds_bytes_btab() + keep > d->lds_limit) hot = d->lds_limit - lds_bytes_btab() - keep;
-	hot -= hot % d->glob_row_bytes;
+	hot -= hot % g.glob_row_bytes;
 	/* never less than one row: a lane whose row is beyond the head still issues its LDS read, at offset 0 of the head
 	 * (GlobPol::next, Glob16Pol::next / next2), and with no head at all that address is the first byte PAST what the
 	 * per-lane kernels allocate (lds_bytes(0), no tiles behind it) */
-	if (hot < d->glob_row_bytes) hot = d->glob_row_bytes < d->glob_tab_bytes ? d->glob_row_bytes : d->glob_tab_bytes;
+	if (hot < g.glob_row_bytes) hot = g.glob_row_bytes < g.glob_tab_bytes ? g.glob_row_bytes : g.glob_tab_bytes;
 	d->proto.tab_bytes = (uint32_t)hot;
-	d->table_lds = GlobPol::lds_bytes((uint32_t)hot);
+	d->table_lds = layout_lds_bytes(d, (uint32_t)hot);
 }
 
 static const unsigned LAZY_CTRS = 64, PICK_FLAGS = 64;
@@ -167,275 +166,71 @@ int dfa_ncu(const fsm_hip_dfa *d) { return d->ncu; }
 /* create / free / info                                               */
 /* ------------------------------------------------------------------ */
 
-/* the layout's table: its element type differs per layout */
-template <class T>
-static hipError_t upload_tab(fsm_hip_dfa *d, const std::vector<T> &src)
-{
-	return d->d_tab.upload_bytes(src.data(), src.size() * sizeof(T), sizeof(T));
-}
-
 /* the layout's device image + the per-dfa launch resources (events, private stream).  fsm_hip_dfa_create does this at once
  * unless FSM_HIP_DEFER_UPLOAD asks to wait for the first call that needs it: a dfa that is only ever used through
  * fsm_hip_exec_multi (retest: a new DFA per record, a few lines each) never needs it -- its plain table rides in that call's
  * one host-to-device copy */
 static int dfa_upload_all(fsm_hip_dfa *d)
 {
-	const unsigned flags = d->flags;
-	{
-		Plan &p = d->plan;
-		WalkArgs &a = d->proto;
-		memset(&a, 0, sizeof a);
-		std::vector<uint32_t> btab(256);
-		switch (p.layout) {
-		case FSM_HIP_LAYOUT_TINY: {
-			if (!p.tiny5_col.empty()) {   /* <= 6 states: Tiny5Pol, state code = 5 * state */
-				if (!HIP_OK(upload_tab(d, p.tiny5_col))) return -1;
-				if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
-				a.tab_bytes = 256 * 4;
-				a.start = p.start * 5u;
-				a.abs_min = p.abs_min * 5u;
-				a.fin_div = 5;
-				d->table_lds = Tiny5Pol::lds_bytes(0);
-				break;
-			}
-			if (!HIP_OK(upload_tab(d, p.tiny_col))) return -1;
-			if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
-			a.tab_bytes = 256 * 8;
-			a.start = p.start;
-			a.abs_min = p.abs_min;
-			a.fin_div = 1;
-			/* 7..16 states: 64-bit columns; a 32-bit format for <= 8 states measured slower on the same box
-			 * (4.95-5.06 vs 5.10-5.61 TB/s, profiles/r01_tiny_by_states.txt) and was dropped */
-			d->table_lds = TinyPol<uint64_t>::lds_bytes(0);
-			break;
-		}
-		case FSM_HIP_LAYOUT_COMBSELF: {
-			/* image: comb64[n] = {entry, smask(next)}, dsm[32] (mask of each class's default state), rng16[n]
-			 * (self-loop byte range by row offset) -- these three parts go to LDS (tab_bytes) -- then smask[n]
-			 * by row offset (global only: seeds a walk) */
-			const size_t n = p.comb.size(), rw = (n + 1) / 2;   /* rng16[n] in u32 words */
-			std::vector<uint32_t> img(2 * n + 64 + rw + n, 0);
-			for (size_t k = 0; k < n; k++) {
-				img[2 * k] = p.comb[k];
-				const uint32_t nxt = p.comb[k] & 0xffffu;
-				img[2 * k + 1] = (p.comb[k] >> 16) != 0xFFFFu && nxt < n ? p.comb_smask[nxt] : 0u;
-			}
-			for (uint32_t c = 0; c < p.C; c++) {
-				img[2 * n + 2 * c] = p.comb_dflt[c];
-				img[2 * n + 2 * c + 1] = p.comb_smask[p.comb_dflt[c]];
-			}
-			for (size_t k = 0; k < n; k++) img[2 * n + 64 + k / 2] |= (uint32_t)p.comb_rng[k] << (16 * (k & 1));
-			for (size_t k = 0; k < n; k++) img[2 * n + 64 + rw + k] = p.comb_smask[k];
-			if (!HIP_OK(upload_tab(d, img))) return -1;
-			if (!HIP_OK(d->d_fin.upload(p.comb_fin))) return -1;
-			for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
-			a.tab_bytes = (uint32_t)((2 * n + 64 + rw) * 4);
-			a.dflt = (uint32_t)n;   /* entries: tells the kernel where dsm[] and rng16[] start */
-			a.start = p.comb_off[p.start];
-			a.abs_min = p.comb_abs_min_off;
-			a.fin_div = 1;
-			d->table_lds = CombSelfPol::lds_bytes(a.tab_bytes);
-			break;
-		}
-		case FSM_HIP_LAYOUT_COMB256: {
-			if (!HIP_OK(upload_tab(d, p.comb256))) return -1;
-			if (!HIP_OK(d->d_fin.upload(p.comb256_fin))) return -1;
-			a.tab_bytes = (uint32_t)(p.comb256.size() * 4);
-			a.start = p.comb256_off[p.start];
-			a.abs_min = p.comb256_abs_min_off;
-			a.dflt = p.comb256_dflt;
-			a.fin_div = 1;
-			d->table_lds = Comb256Pol::lds_bytes(a.tab_bytes);
-			break;
-		}
-		case FSM_HIP_LAYOUT_LDS: {
-			if (!HIP_OK(upload_tab(d, p.lds_tab))) return -1;
-			if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
-			for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
-			a.tab_bytes = (uint32_t)(p.lds_tab.size() * 2);
-			a.start = p.start * p.row_bytes;
-			a.abs_min = p.abs_min * p.row_bytes;
-			a.fin_div = p.row_bytes;
-			d->table_lds = lds_bytes_btab() + ((a.tab_bytes + 15u) & ~15u);
-			break;
-		}
-		case FSM_HIP_LAYOUT_LDS2: {
-			if (!HIP_OK(upload_tab(d, p.lds_tab))) return -1;
-			if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
-			for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
-			const uint32_t row = p.lds2_c1 * p.lds2_c1;      /* entries per state: the walk's state is state * row */
-			a.tab_bytes = (uint32_t)(p.lds_tab.size() * 2);
-			a.start = p.start * row;
-			a.abs_min = p.abs_min * row;
-			a.fin_div = row;
-			a.dflt = p.lds2_c1;
-			d->table_lds = Lds2Pol::lds_bytes(a.tab_bytes);
-			break;
-		}
-		case FSM_HIP_LAYOUT_LDSSELF: {
-			if (!HIP_OK(upload_tab(d, p.lds_tab))) return -1;
-			if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
-			for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
-			a.tab_bytes = (uint32_t)(p.lds_tab.size() * 2);
-			a.start = p.start * p.row_bytes;
-			a.abs_min = p.abs_min * p.row_bytes;
-			a.fin_div = p.row_bytes;
-			d->table_lds = LdsSelfPol::lds_bytes(a.tab_bytes);
-			break;
-		}
-		case FSM_HIP_LAYOUT_COMB: {
-			std::vector<uint32_t> img(p.comb);               /* image = comb[n], dflt[256] */
-			img.resize(p.comb.size() + 256, 0);
-			for (uint32_t c = 0; c < p.C; c++) img[p.comb.size() + c] = p.comb_dflt[c];
-			if (!HIP_OK(upload_tab(d, img))) return -1;
-			if (!HIP_OK(d->d_fin.upload(p.comb_fin))) return -1;
-			for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
-			a.tab_bytes = (uint32_t)(img.size() * 4);
-			a.start = p.comb_off[p.start];
-			a.abs_min = p.comb_abs_min_off;
-			a.fin_div = 1;
-			d->table_lds = lds_bytes_btab() + ((a.tab_bytes + 15u) & ~15u);
-			break;
-		}
-		case FSM_HIP_LAYOUT_GLOBAL: {
-			if (!p.glob_tab16.empty()) {
-				/* <= 65 535 states: 2-byte entries = the next state's index (Glob16Pol) */
-				if (!HIP_OK(upload_tab(d, p.glob_tab16))) return -1;
-				if (!HIP_OK(d->d_fin.upload(p.glob16_fin))) return -1;      /* rows in visit-frequency order (plan.cpp): fin follows */
-				for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
-				a.start = p.glob16_rank.empty() ? p.start : p.glob16_rank[p.start];
-				a.abs_min = p.abs_min;
-				a.fin_div = 1;
-				a.dflt = p.C * 2u;          /* bytes per row */
-				d->glob16 = true;
-				d->glob_row_bytes = p.C * 2u;
-				d->glob_tab_bytes = (uint64_t)p.glob_tab16.size() * 2u;
-				set_hot_bytes(d, 160u * 1024u);
-				break;
-			}
-			if (!HIP_OK(upload_tab(d, p.glob_tab))) return -1;
-			if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
-			for (int b = 0; b < 256; b++) btab[b] = p.cls[b];
-			a.start = p.start * p.C * 4u;
-			a.abs_min = p.abs_min * p.C * 4u;
-			a.fin_div = p.C * 4u;
-			d->glob_row_bytes = p.C * 4u;
-			d->glob_tab_bytes = (uint64_t)p.glob_tab.size() * 4u;
-			set_hot_bytes(d, 120u * 1024u);
-			break;
-		}
-		case FSM_HIP_LAYOUT_SPARSE: {
-			if (!HIP_OK(upload_tab(d, p.sparse_img))) return -1;
-			if (!HIP_OK(d->d_fin.upload(p.fin))) return -1;
-			a.tab_bytes = p.sparse_lds_bytes;
-			a.start = p.start;
-			a.abs_min = p.abs_min;
-			a.fin_div = 1;
-			d->table_lds = SparsePol::lds_bytes(a.tab_bytes);
-			{
-				/* SparseFastPol::enter builds a record's address from a 32-bit low half: the record array must not cross
-				 * a 4 GiB boundary (hipMalloc hands out 2 MiB-aligned blocks, the array is a few MB: practically never) */
-				const uint64_t g = reinterpret_cast<uint64_t>(d->d_tab.p) + p.sparse_img[5], bytes = (uint64_t)p.S1 * 16u;
-				if ((g >> 32) != ((g + bytes) >> 32)) d->sparse_fast_ok = false;
-			}
-			if (p.lazy_lds_bytes != 0 && ((p.lazy_lds_bytes + 15u) & ~15u) + FSMHIP_LAZY_QBYTES <= d->lds_limit) {
-				if (!HIP_OK(d->d_lazy.upload(p.lazy_img))) return -1;
-				if (!HIP_OK(d->d_lazy_ctr.alloc(LAZY_CTRS))) return -1;
-				a.lazy = d->d_lazy;
-				/* the default where it pays: few states beyond the LDS set whose own record sends hits the exact way
-				 * (img[10]) or that carry nothing (img[9]) -- on the 1e5-literal automaton 4.5 % of them, deep in the trie */
-				const uint64_t deep = p.abs_min > p.lazy_img[1] ? p.abs_min - p.lazy_img[1] : 0;
-				if (((uint64_t)p.lazy_img[9] + p.lazy_img[10]) * 10u <= deep) d->knob_sparse_fast = 3;
-			}
-			break;
-		}
-		default:
-			errno = EINVAL;
-			return -1;
-		}
-		if (!HIP_OK(d->d_btab.upload(btab))) return -1;
-		d->enc_host.resize(p.S1);
-		for (uint32_t n2 = 0; n2 < p.S1; n2++) {
-			switch (p.layout) {
-			case FSM_HIP_LAYOUT_TINY: d->enc_host[n2] = p.tiny5_col.empty() ? n2 : n2 * 5u; break;
-			case FSM_HIP_LAYOUT_SPARSE: d->enc_host[n2] = n2; break;
-			case FSM_HIP_LAYOUT_LDS:
-			case FSM_HIP_LAYOUT_LDSSELF: d->enc_host[n2] = n2 * p.row_bytes; break;
-			case FSM_HIP_LAYOUT_LDS2: d->enc_host[n2] = n2 * p.lds2_c1 * p.lds2_c1; break;
-			case FSM_HIP_LAYOUT_COMB:
-			case FSM_HIP_LAYOUT_COMBSELF: d->enc_host[n2] = p.comb_off[n2]; break;
-			case FSM_HIP_LAYOUT_COMB256: d->enc_host[n2] = p.comb256_off[n2]; break;
-			default: d->enc_host[n2] = !p.glob_tab16.empty() ? (p.glob16_rank.empty() ? n2 : p.glob16_rank[n2]) : n2 * p.C * 4u; break;   /* global: the row's byte offset, or (2-byte entries) its row */
-			}
-		}
-		d->fin_host = (p.layout == FSM_HIP_LAYOUT_COMB || p.layout == FSM_HIP_LAYOUT_COMBSELF) ? p.comb_fin
-			: p.layout == FSM_HIP_LAYOUT_COMB256 ? p.comb256_fin : (p.layout == FSM_HIP_LAYOUT_GLOBAL && !p.glob_tab16.empty()) ? p.glob16_fin : p.fin;
-		if (!p.emask.empty()) {
-			/* eager masks indexed like fin; thresholds in encoded-state units */
-			const size_t F = d->fin_host.size();
-			std::vector<uint64_t> em(F, 0);
-			std::vector<uint32_t> state_of(F, 0xFFFFFFFFu);   /* fin index -> renumbered state */
-			for (uint32_t n2 = 0; n2 < p.S1; n2++) {
-				em[d->enc_host[n2] / a.fin_div] = p.emask[n2];
-				state_of[d->enc_host[n2] / a.fin_div] = n2;
-			}
-			if (!HIP_OK(d->d_emask.upload(em))) return -1;
-			a.emask = d->d_emask;
-			switch (p.layout) {
-			case FSM_HIP_LAYOUT_COMB:
-			case FSM_HIP_LAYOUT_COMBSELF:   /* rows placed region by region: thresholds on row offsets (plan.cpp build_comb) */
-				a.eager_lo_end = p.comb_eager_lo_off;
-				a.eager_hi_begin = p.comb_eager_hi_off;
-				break;
-			case FSM_HIP_LAYOUT_COMB256:
-				a.eager_lo_end = p.comb256_eager_lo_off;
-				a.eager_hi_begin = p.comb256_eager_hi_off;
-				break;
-			default:
-				a.eager_lo_end = p.eager_lo_end < p.S1 ? d->enc_host[p.eager_lo_end] : 0xFFFFFFFFu;
-				a.eager_hi_begin = p.eager_hi_begin < p.S1 ? d->enc_host[p.eager_hi_begin] : 0xFFFFFFFFu;
-				break;
-			}
-			a.eager_words = p.eager_words;
-			if (p.eager_words > 1) {
-				/* wide sets: the (word, mask) runs re-laid in fin-index order (= renumbered state except in
-				 * the comb layouts, whose fin index is the row offset) */
-				std::vector<uint32_t> off(F + 1, 0), w;
-				std::vector<uint64_t> m;
-				for (size_t i = 0; i < F; i++) {
-					off[i] = (uint32_t)w.size();
-					const uint32_t n2 = state_of[i];
-					if (n2 == 0xFFFFFFFFu) continue;
-					w.insert(w.end(), p.ew_word.begin() + p.ew_off[n2], p.ew_word.begin() + p.ew_off[n2 + 1]);
-					m.insert(m.end(), p.ew_mask.begin() + p.ew_off[n2], p.ew_mask.begin() + p.ew_off[n2 + 1]);
-				}
-				off[F] = (uint32_t)w.size();
-				if (w.empty()) { w.push_back(0); m.push_back(0); }
-				if (!HIP_OK(d->d_ew_off.upload(off))) return -1;
-				if (!HIP_OK(d->d_ew_word.upload(w))) return -1;
-				if (!HIP_OK(d->d_ew_mask.upload(m))) return -1;
-				a.ew_off = d->d_ew_off;
-				a.ew_word = d->d_ew_word;
-				a.ew_mask = d->d_ew_mask;
-			}
-		}
-		/* fin_index(): code / fin_div as a multiply where that is exact for every code the walk can produce */
-		a.fin_mul = 0;
-		if (a.fin_div > 1u) {
-			uint32_t maxcode = 0;
-			for (uint32_t n2 = 0; n2 < p.S1; n2++) maxcode = d->enc_host[n2] > maxcode ? d->enc_host[n2] : maxcode;
-			if ((uint64_t)maxcode * a.fin_div < ((uint64_t)1 << 32)) a.fin_mul = (uint32_t)((((uint64_t)1 << 32) / a.fin_div) + 1u);
-		}
-		/* the spare class of the self-loop-mask layouts (plan.cpp sets bit 31 in every mask when there are <= 31 classes) */
-		a.ident_class = ((p.layout == FSM_HIP_LAYOUT_COMBSELF || p.layout == FSM_HIP_LAYOUT_LDSSELF) && p.C <= 31u) ? 31u : 0xFFFFFFFFu;
-		a.tab = d->d_tab;
-		a.fin = d->d_fin;
-		a.btab = d->d_btab;
-		/* bit 0: a wavefront retires once all its lanes are absorbing; bit 1: an absorbing lane stops fetching its row (what
-		 * fsm_exec does at a missing edge, exec.c:133-138).  Bit 1 costs a ballot per tile: set only where an absorbing
-		 * state can be reached at all (launch_walk clears it again for the eager and the resumed walks) */
-		a.early = (flags & FSM_HIP_NO_EARLY_RETIRE) ? 0u : p.abs_reachable ? 3u : 1u;
+	const Plan &p = d->plan;
+	Image &im = d->img;
+	WalkArgs &a = d->proto;
+	/* 1. the image: everything that needs no device (image.cpp) */
+	const int r = build_image(p, im);
+	if (r != 0) { errno = r; return -1; }
+	/* 2. its parts go to the device and the prototype points at them */
+	memset(&a, 0, sizeof a);
+	if (!HIP_OK(d->d_tab.upload_bytes(im.tab, im.tab_size, im.tab_elem))) return -1;
+	if (!HIP_OK(d->d_fin.upload(*im.fin))) return -1;
+	if (!HIP_OK(d->d_btab.upload(im.btab))) return -1;
+	a.tab = d->d_tab;
+	a.fin = d->d_fin;
+	a.btab = d->d_btab;
+	if (!im.emask.empty()) {
+		if (!HIP_OK(d->d_emask.upload(im.emask))) return -1;
+		a.emask = d->d_emask;
 	}
+	if (!im.ew_off.empty()) {
+		if (!HIP_OK(d->d_ew_off.upload(im.ew_off))) return -1;
+		if (!HIP_OK(d->d_ew_word.upload(im.ew_word))) return -1;
+		if (!HIP_OK(d->d_ew_mask.upload(im.ew_mask))) return -1;
+		a.ew_off = d->d_ew_off;
+		a.ew_word = d->d_ew_word;
+		a.ew_mask = d->d_ew_mask;
+	}
+	a.tab_bytes = im.s.tab_bytes;
+	a.start = im.s.start;
+	a.abs_min = im.s.abs_min;
+	a.fin_div = im.s.fin_div;
+	a.fin_mul = im.s.fin_mul;
+	a.dflt = im.s.dflt;
+	a.ident_class = im.s.ident_class;
+	a.eager_lo_end = im.s.eager_lo_end;
+	a.eager_hi_begin = im.s.eager_hi_begin;
+	a.eager_words = im.s.eager_words;
+	im.drop_upload_parts();
+	/* 3. what the device decides */
+	if (p.layout == FSM_HIP_LAYOUT_GLOBAL) set_hot_bytes(d, im.glob16 ? 160u * 1024u : 120u * 1024u);
+	else d->table_lds = layout_lds_bytes(d, a.tab_bytes);
+	if (p.layout == FSM_HIP_LAYOUT_SPARSE) {
+		/* SparseFastPol::enter builds a record's address from a 32-bit low half: the record array must not cross
+		 * a 4 GiB boundary (hipMalloc hands out 2 MiB-aligned blocks, the array is a few MB: practically never) */
+		const uint64_t g = reinterpret_cast<uint64_t>(d->d_tab.p) + p.sparse_img[5], bytes = (uint64_t)p.S1 * 16u;
+		if ((g >> 32) != ((g + bytes) >> 32)) d->sparse_fast_ok = false;
+		if (p.lazy_lds_bytes != 0 && ((p.lazy_lds_bytes + 15u) & ~15u) + FSMHIP_LAZY_QBYTES <= d->lds_limit) {
+			if (!HIP_OK(d->d_lazy.upload(p.lazy_img))) return -1;
+			if (!HIP_OK(d->d_lazy_ctr.alloc(LAZY_CTRS))) return -1;
+			a.lazy = d->d_lazy;
+			/* the default where it pays: few states beyond the LDS set whose own record sends hits the exact way
+			 * (img[10]) or that carry nothing (img[9]) -- on the 1e5-literal automaton 4.5 % of them, deep in the trie */
+			const uint64_t deep = p.abs_min > p.lazy_img[1] ? p.abs_min - p.lazy_img[1] : 0;
+			if (((uint64_t)p.lazy_img[9] + p.lazy_img[10]) * 10u <= deep) d->knob_sparse_fast = 3;
+		}
+	}
+	/* bit 0: a wavefront retires once all its lanes are absorbing; bit 1: an absorbing lane stops fetching its row (what
+	 * fsm_exec does at a missing edge, exec.c:133-138).  Bit 1 costs a ballot per tile: set only where an absorbing
+	 * state can be reached at all (launch_walk clears it again for the eager and the resumed walks) */
+	a.early = (d->flags & FSM_HIP_NO_EARLY_RETIRE) ? 0u : p.abs_reachable ? 3u : 1u;
 	if (!HIP_OK(d->d_pick.alloc(PICK_FLAGS))) return -1;
 	if (!HIP_OK(d->tb_scratch_ev.create(hipEventDisableTiming))) return -1;
 	if (!HIP_OK(d->ev0.create())) return -1;
@@ -562,7 +357,7 @@ static LaunchCfg pick_cfg(const fsm_hip_dfa *d, bool fast_ok, uint64_t stride, i
 		if (m == IN_DIRECT) {
 			/* the sparse layout waits on gathers, not on its input: 4 chunks keep it under 64 VGPRs;
 			 * the eager kernel is instantiated for 4 chunks only */
-			c.nb = d->knob_nb == 4 || d->knob_nb == 8 ? d->knob_nb : (layout == FSM_HIP_LAYOUT_SPARSE || d->glob16 ? 4 : 8);   /* (the 2-byte global table: 4 chunks x TWO inputs per lane, kern_glob16.hip) */
+			c.nb = d->knob_nb == 4 || d->knob_nb == 8 ? d->knob_nb : (layout == FSM_HIP_LAYOUT_SPARSE || d->img.glob16 ? 4 : 8);   /* (the 2-byte global table: 4 chunks x TWO inputs per lane, kern_glob16.hip) */
 			if (eager || !c.prefetch) c.nb = 4;
 			if ((stride / 16u) % 8u != 0) c.nb = 4;
 			if ((stride / 16u) % 4u != 0) m = -1;   /* rows shorter than / not a multiple of 64 bytes */
@@ -674,7 +469,24 @@ static hipError_t launch_layout(const fsm_hip_dfa *d, int eager, const LaunchCfg
 	case FSM_HIP_LAYOUT_COMB256:  return launch_comb(POL_COMB256, eager, c, a, grid, block, s);
 	case FSM_HIP_LAYOUT_COMBSELF: return launch_comb(POL_COMBSELF, eager, c, a, grid, block, s);
 	case FSM_HIP_LAYOUT_SPARSE:   return launch_glob(POL_SPARSE, eager, c, a, grid, block, s);
-	default:                      return d->glob16 ? launch_glob16(eager, c, a, grid, block, s) : launch_glob(POL_GLOB, eager, c, a, grid, block, s);
+	default:                      return d->img.glob16 ? launch_glob16(eager, c, a, grid, block, s) : launch_glob(POL_GLOB, eager, c, a, grid, block, s);
+	}
+}
+
+/* LDS bytes of the layout's tables, as its policy counts them (tab_bytes: WalkArgs::tab_bytes) */
+static uint32_t layout_lds_bytes(const fsm_hip_dfa *d, uint32_t tab_bytes)
+{
+	const Plan &p = d->plan;
+	switch (p.layout) {
+	case FSM_HIP_LAYOUT_TINY:     return p.tiny5_col.empty() ? TinyPol<uint64_t>::lds_bytes(tab_bytes) : Tiny5Pol::lds_bytes(tab_bytes);
+	case FSM_HIP_LAYOUT_LDS:      return LdsPol::lds_bytes(tab_bytes);
+	case FSM_HIP_LAYOUT_LDSSELF:  return LdsSelfPol::lds_bytes(tab_bytes);
+	case FSM_HIP_LAYOUT_LDS2:     return Lds2Pol::lds_bytes(tab_bytes);
+	case FSM_HIP_LAYOUT_COMB:     return CombPol::lds_bytes(tab_bytes);
+	case FSM_HIP_LAYOUT_COMB256:  return Comb256Pol::lds_bytes(tab_bytes);
+	case FSM_HIP_LAYOUT_COMBSELF: return CombSelfPol::lds_bytes(tab_bytes);
+	case FSM_HIP_LAYOUT_SPARSE:   return SparsePol::lds_bytes(tab_bytes);
+	default:                      return d->img.glob16 ? Glob16Pol::lds_bytes(tab_bytes) : GlobPol::lds_bytes(tab_bytes);
 	}
 }
 
@@ -1111,7 +923,7 @@ static int walk_device(const fsm_hip_dfa *dc, const Inputs &in, Outputs out, voi
 		if (out.ids_mode == FSM_HIP_IDS_ERROR) {
 			/* AMBIG_ERROR: an end state with more than one id is refused (print/c.c:67-72 fails the
 			 * print with EINVAL); without such a state it is AMBIG_EARLIEST */
-			if (d->ids_conflict != FSM_HIP_NO_MATCH) { errno = EINVAL; return -1; }
+			if (d->ids.conflict != FSM_HIP_NO_MATCH) { errno = EINVAL; return -1; }
 			out.ids_mode = FSM_HIP_IDS_EARLIEST;
 		}
 	}
@@ -1491,17 +1303,9 @@ extern "C" int fsm_hip_dfa_info(const struct fsm_hip_dfa *d, struct fsm_hip_dfa_
 	out->nclasses = p.C;
 	out->layout = p.layout;
 	out->nabsorbing = p.nabsorbing;
-	switch (p.layout) {
-	case FSM_HIP_LAYOUT_TINY: out->table_bytes = p.tiny5_col.empty() ? 256 * 8 : 256 * 4; break;
-	case FSM_HIP_LAYOUT_LDS:
-	case FSM_HIP_LAYOUT_LDS2:
-	case FSM_HIP_LAYOUT_LDSSELF: out->table_bytes = p.lds_tab.size() * 2; break;
-	case FSM_HIP_LAYOUT_COMB: out->table_bytes = p.comb.size() * 4 + 1024; break;
-	case FSM_HIP_LAYOUT_COMB256: out->table_bytes = p.comb256.size() * 4; break;
-	case FSM_HIP_LAYOUT_COMBSELF: out->table_bytes = p.comb.size() * 10 + 256; break;
-	case FSM_HIP_LAYOUT_SPARSE: out->table_bytes = p.sparse_img.size() * 4; break;
-	default: out->table_bytes = p.glob_tab16.empty() ? p.glob_tab.size() * 4 : p.glob_tab16.size() * 2; break;
-	}
+	/* the uploaded table's bytes; COMBSELF has always reported comb64[n] + rng16[n] + dsm[32] with neither padding nor the
+	 * trailing smask[n], and keeps doing so */
+	out->table_bytes = p.layout == FSM_HIP_LAYOUT_COMBSELF ? p.comb.size() * 10 + 256 : d->img.tab_size;
 	LaunchCfg c = pick_cfg(d, true, 1024, 0);
 	out->lds_bytes = c.lds;
 	out->waves_per_block = (uint32_t)c.waves;
@@ -1894,88 +1698,19 @@ extern "C" double fsm_hip_gather_probe_ms(const void *d_base, size_t bytes, size
 /* end-ids delivered by the device                                    */
 /* ------------------------------------------------------------------ */
 
-#include <algorithm>
-#include <map>
-
-/* Build, once, the per-encoded-state tables the kernel copies into id_out[]:
- *   earliest: lowest end-id of the state (AMBIG_EARLIEST, src/libfsm/print/c.c:67-85)
- *   ret:      index of the state's id set in the de-duplicated list of sets, ordered by
- *             count, then memcmp of the id arrays -- the order build_retlist() produces
- *             (src/libfsm/vm/retlist.c:93-138, cmp_ret). */
-typedef std::vector<uint32_t> IdSet;
-/* the de-duplicated id sets of the end states in build_retlist()'s order (src/libfsm/vm/retlist.c:93-138), from the plan alone */
-static void build_ret_sets(const Plan &p, std::vector<uint32_t> &ret_off, std::vector<uint32_t> &ret_ids, std::map<IdSet, uint32_t> &index)
-{
-	typedef IdSet Set;
-	std::vector<Set> sets;
-	/* end states = those appearing in fin */
-	std::vector<uint8_t> is_end(p.nstates, 0);
-	for (uint32_t v : p.fin) if (v != FSM_HIP_NO_MATCH) is_end[v] = 1;
-	for (uint32_t s = 0; s < p.nstates; s++)
-		if (is_end[s]) sets.emplace_back(p.endids.begin() + p.endid_off[s], p.endids.begin() + p.endid_off[s + 1]);
-	/* cmp_ret (src/libfsm/vm/retlist.c:63-79): by count, then memcmp over the raw id array -- byte-wise,
-	 * i.e. NOT numeric for ids >= 256 on a little-endian host ({256} sorts before {1}) */
-	std::sort(sets.begin(), sets.end(), [](const Set &a, const Set &b) {
-		if (a.size() != b.size()) return a.size() < b.size();
-		return !a.empty() && memcmp(a.data(), b.data(), a.size() * sizeof(uint32_t)) < 0;
-	});
-	sets.erase(std::unique(sets.begin(), sets.end()), sets.end());
-	ret_off.assign(1, 0);
-	ret_ids.clear();
-	index.clear();
-	for (uint32_t k = 0; k < sets.size(); k++) {
-		index[sets[k]] = k;
-		ret_ids.insert(ret_ids.end(), sets[k].begin(), sets[k].end());
-		ret_off.push_back((uint32_t)ret_ids.size());
-	}
-}
-
-/* for multi.hip (dfa_access.h): what fsm_hip_exec_batch_ids writes for an input that ends in renumbered state n (Plan::dense's
- * numbering), mode EARLIEST or RET, from the plan alone -- a dfa created with FSM_HIP_DEFER_UPLOAD stays without tables of its
- * own.  *conflict: the lowest caller's end state with more than one id, or NO_MATCH (what FSM_HIP_IDS_ERROR refuses). */
-namespace fsmhip {
-int dfa_ids_by_state(const fsm_hip_dfa *d, int mode, std::vector<uint32_t> &out, uint32_t *conflict)
-{
-	const Plan &p = d->plan;
-	std::vector<uint32_t> ro, ri;
-	std::map<IdSet, uint32_t> index;
-	if (mode == FSM_HIP_IDS_RET) build_ret_sets(p, ro, ri, index);
-	out.assign(p.S1, FSM_HIP_NO_MATCH);
-	uint32_t cf = FSM_HIP_NO_MATCH;
-	for (uint32_t n = 0; n < p.S1; n++) {
-		const uint32_t s = p.fin[n];
-		if (s == FSM_HIP_NO_MATCH) continue;
-		const uint32_t a = p.endid_off[s], b = p.endid_off[s + 1];
-		if (b - a > 1 && s < cf) cf = s;
-		out[n] = mode == FSM_HIP_IDS_RET ? index[IdSet(p.endids.begin() + a, p.endids.begin() + b)] : (b > a ? p.endids[a] : FSM_HIP_NO_ID);
-	}
-	if (conflict) *conflict = cf;
-	return 0;
-}
-}
-
+/* the per-encoded-state tables the kernel copies into id_out[] (image.cpp build_id_tables), once */
 static int ensure_ids(fsm_hip_dfa *d)
 {
 	if (ensure_uploaded(d) != 0) return -1;
 	DfaLock lk(d->mu);
 	if (d->ids_ready) return 0;
-	const Plan &p = d->plan;
-	typedef IdSet Set;
-	std::map<Set, uint32_t> index;
-	build_ret_sets(p, d->ret_off, d->ret_ids, index);
-	std::vector<uint32_t> fe(d->fin_host.size(), FSM_HIP_NO_MATCH), fr(d->fin_host.size(), FSM_HIP_NO_MATCH);
-	for (size_t i = 0; i < d->fin_host.size(); i++) {
-		const uint32_t s = d->fin_host[i];
-		if (s == FSM_HIP_NO_MATCH) continue;
-		const uint32_t a = p.endid_off[s], b = p.endid_off[s + 1];
-		fe[i] = b > a ? p.endids[a] : FSM_HIP_NO_ID;
-		if (b - a > 1 && s < d->ids_conflict) d->ids_conflict = s;
-		fr[i] = index[Set(p.endids.begin() + a, p.endids.begin() + b)];
-	}
+	build_id_tables(d->plan, d->img, d->ids);
 	DevGuard dg(d->device);
 	if (!dg.ok()) { errno = ENODEV; return -1; }
-	if (!HIP_OK(d->d_fin_earliest.upload(fe))) return -1;
-	if (!HIP_OK(d->d_fin_ret.upload(fr))) return -1;
+	if (!HIP_OK(d->d_fin_earliest.upload(d->ids.earliest))) return -1;
+	if (!HIP_OK(d->d_fin_ret.upload(d->ids.ret))) return -1;
+	std::vector<uint32_t>().swap(d->ids.earliest);
+	std::vector<uint32_t>().swap(d->ids.ret);
 	d->ids_ready = true;
 	return 0;
 }
@@ -2025,8 +1760,8 @@ extern "C" int fsm_hip_ids_conflict(const struct fsm_hip_dfa *dc, fsm_state_t *s
 	fsm_hip_dfa *d = const_cast<fsm_hip_dfa *>(dc);
 	if (d == nullptr) { errno = EINVAL; return -1; }
 	if (ensure_ids(d) != 0) return -1;
-	if (d->ids_conflict == FSM_HIP_NO_MATCH) return 0;
-	if (state != nullptr) *state = d->ids_conflict;
+	if (d->ids.conflict == FSM_HIP_NO_MATCH) return 0;
+	if (state != nullptr) *state = d->ids.conflict;
 	return 1;
 }
 
@@ -2034,18 +1769,18 @@ extern "C" size_t fsm_hip_ret_count(const struct fsm_hip_dfa *dc)
 {
 	fsm_hip_dfa *d = const_cast<fsm_hip_dfa *>(dc);
 	if (d == nullptr || ensure_ids(d) != 0) return 0;
-	return d->ret_off.size() - 1;
+	return d->ids.ret_off.size() - 1;
 }
 
 extern "C" int fsm_hip_ret_get(const struct fsm_hip_dfa *dc, uint32_t ret_index, const uint32_t **ids, size_t *count)
 {
 	fsm_hip_dfa *d = const_cast<fsm_hip_dfa *>(dc);
-	if (d == nullptr || ids == nullptr || count == nullptr || ensure_ids(d) != 0 || ret_index + 1 >= d->ret_off.size()) {
+	if (d == nullptr || ids == nullptr || count == nullptr || ensure_ids(d) != 0 || ret_index + 1 >= d->ids.ret_off.size()) {
 		errno = EINVAL;
 		return -1;
 	}
-	*ids = d->ret_ids.data() + d->ret_off[ret_index];
-	*count = d->ret_off[ret_index + 1] - d->ret_off[ret_index];
+	*ids = d->ids.ret_ids.data() + d->ids.ret_off[ret_index];
+	*count = d->ids.ret_off[ret_index + 1] - d->ids.ret_off[ret_index];
 	return 0;
 }
 
@@ -2058,17 +1793,12 @@ static int ensure_resume(fsm_hip_dfa *d)
 	if (ensure_uploaded(d) != 0) return -1;
 	DfaLock lk(d->mu);
 	if (d->resume_ready) return 0;
-	const Plan &p = d->plan;
-	/* caller id (+ nstates = DEAD) -> encoded state */
-	std::vector<uint32_t> enc(p.nstates + 1);
-	for (uint32_t o = 0; o <= p.nstates; o++) enc[o] = d->enc_host[p.old2new[o]];
-	/* encoded index (as used for fin) -> caller id, DEAD marker for the synthetic state */
-	std::vector<uint32_t> orig(d->fin_host.size(), FSMHIP_STATE_DEAD);
-	for (uint32_t n2 = 0; n2 + 1 < p.S1; n2++) orig[d->enc_host[n2] / d->proto.fin_div] = p.new2old[n2];
+	ResumeTables t;
+	build_resume_tables(d->plan, d->img, t);
 	DevGuard dg(d->device);
 	if (!dg.ok()) { errno = ENODEV; return -1; }
-	if (!HIP_OK(d->d_enc_of.upload(enc))) return -1;
-	if (!HIP_OK(d->d_orig_of.upload(orig))) return -1;
+	if (!HIP_OK(d->d_enc_of.upload(t.enc_of))) return -1;
+	if (!HIP_OK(d->d_orig_of.upload(t.orig_of))) return -1;
 	d->resume_ready = true;
 	return 0;
 }
@@ -2266,29 +1996,14 @@ static int ensure_trace(fsm_hip_dfa *d)
 	if (d->trace_ready) return 0;
 	const Plan &p = d->plan;
 	if (p.dense.size() != (size_t)p.S1 * p.C) { errno = ENOTSUP; return -1; }
-	/* id lists per renumbered state, ascending (fsm_eager_output_get order: eager_output.c:317-329) */
-	std::vector<uint32_t> eoff(p.S1 + 1, 0), eids;
-	for (uint32_t n = 0; n < p.S1; n++) {
-		if (!p.emask.empty() && p.emask[n] != 0) {
-			if (p.eager_words <= 1) {
-				for (unsigned b = 0; b < 64; b++) if (p.emask[n] >> b & 1u) eids.push_back(p.eager_ids[b]);
-			} else {
-				const size_t first = eids.size();
-				for (uint32_t k = p.ew_off[n]; k < p.ew_off[n + 1]; k++)
-					for (unsigned b = 0; b < 64; b++) if (p.ew_mask[k] >> b & 1u) eids.push_back(p.eager_ids[(size_t)p.ew_word[k] * 64u + b]);
-				std::sort(eids.begin() + (ptrdiff_t)first, eids.end());
-			}
-		}
-		eoff[n + 1] = (uint32_t)eids.size();
-	}
-	std::vector<uint32_t> cls4(64, 0);
-	for (unsigned b = 0; b < 256; b++) cls4[b >> 2] |= (uint32_t)p.cls[b] << ((b & 3u) * 8u);
+	TraceTables t;
+	build_trace_tables(p, t);
 	DevGuard dg(d->device);
 	if (!dg.ok()) { errno = ENODEV; return -1; }
 	if (!HIP_OK(d->d_tr_dense.upload(p.dense))) return -1;
-	if (!HIP_OK(d->d_tr_cls4.upload(cls4))) return -1;
-	if (!HIP_OK(d->d_tr_eoff.upload(eoff))) return -1;
-	if (!HIP_OK(d->d_tr_eids.upload(eids))) return -1;
+	if (!HIP_OK(d->d_tr_cls4.upload(t.cls4))) return -1;
+	if (!HIP_OK(d->d_tr_eoff.upload(t.eoff))) return -1;
+	if (!HIP_OK(d->d_tr_eids.upload(t.eids))) return -1;
 	if (!HIP_OK(d->d_tr_fin.upload(p.fin))) return -1;
 	d->trace_ready = true;
 	return 0;

@@ -34,6 +34,7 @@
 
 #include "../../include/fsm_hip.h"
 #include "dfa_access.h"
+#include "image.h"
 #include "hip_host.h"
 
 using namespace fsmhip;
@@ -444,9 +445,7 @@ void fill_tables(unsigned char *pin, unsigned char *dev, const Lay &L, size_t f,
 {
 	const size_t none = (size_t)-1;
 	memcpy(pin + L.dense[f], p->dense.data(), p->dense.size() * 4u);
-	uint32_t *c4 = reinterpret_cast<uint32_t *>(pin + L.cls[f]);
-	for (unsigned w = 0; w < 64; w++)
-		c4[w] = (uint32_t)p->cls[4 * w] | ((uint32_t)p->cls[4 * w + 1] << 8) | ((uint32_t)p->cls[4 * w + 2] << 16) | ((uint32_t)p->cls[4 * w + 3] << 24);
+	pack_cls4(p->cls, reinterpret_cast<uint32_t *>(pin + L.cls[f]));
 	memcpy(pin + L.fin[f], p->fin.data(), (size_t)p->S1 * 4u);
 	if (L.fid[f] != none) memcpy(pin + L.fid[f], fid.data(), (size_t)p->S1 * 4u);
 	memset(&j, 0, sizeof j);
@@ -551,7 +550,7 @@ int run_device_group(int device, const struct fsm_hip_dfa *const *dfa, const Job
 		if (tiles > 0x7FFFFFFFu) { errno = EINVAL; return -1; }
 		fids.resize(kf);
 		for (size_t f = 0; f < kf; f++)
-			if (b[fj[f]].id_out != nullptr && dfa_ids_by_state(dfa[fj[f]], ids_mode, fids[f], nullptr) != 0) return -1;
+			if (b[fj[f]].id_out != nullptr) ids_by_state(*dfa_plan(dfa[fj[f]]), ids_mode, fids[f], nullptr);
 		size_t o = lay_head(L, kf, tiles, eager);
 		for (size_t f = 0; f < kf; f++) {
 			const size_t q = fj[f];
@@ -659,7 +658,8 @@ int check_jobs(const struct fsm_hip_dfa *const *dfa, const JobView *b, int *ids_
 			for (size_t q = 0; q < k; q++) {
 				uint32_t cf = FSM_HIP_NO_MATCH;
 				if (dfa[q] == nullptr) { errno = EINVAL; return -1; }
-				if (b[q].id_out != nullptr && (dfa_ids_by_state(dfa[q], FSM_HIP_IDS_EARLIEST, tmp, &cf) != 0 || cf != FSM_HIP_NO_MATCH)) { errno = EINVAL; return -1; }
+				if (b[q].id_out != nullptr) ids_by_state(*dfa_plan(dfa[q]), FSM_HIP_IDS_EARLIEST, tmp, &cf);
+				if (cf != FSM_HIP_NO_MATCH) { errno = EINVAL; return -1; }
 			}
 			ids_mode = FSM_HIP_IDS_EARLIEST;
 		}
@@ -796,7 +796,7 @@ static int multi_prepare(const struct fsm_hip_dfa *const *dfa, const std::vector
 		if (tiles > 0x7FFFFFFFu) { errno = EINVAL; return -1; }
 		std::vector<std::vector<uint32_t>> fids(kf);
 		for (size_t f = 0; f < kf; f++)
-			if (v[fj[f]].id_out != nullptr && dfa_ids_by_state(dfa[fj[f]], ids_mode, fids[f], nullptr) != 0) return -1;
+			if (v[fj[f]].id_out != nullptr) ids_by_state(*dfa_plan(dfa[fj[f]]), ids_mode, fids[f], nullptr);
 		Lay L;
 		size_t o = lay_head(L, kf, tiles, eager);
 		for (size_t f = 0; f < kf; f++) o = lay_tables(L, f, dfa_plan(dfa[fj[f]]), !fids[f].empty(), v[fj[f]].eager_out != nullptr, o);
