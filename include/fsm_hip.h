@@ -960,6 +960,83 @@ double fsm_hip_text_spans_ms(const struct fsm_hip_text_spans *sp);
 void fsm_hip_text_spans_free(struct fsm_hip_text_spans *sp);
 
 /* ------------------------------------------------------------------ */
+/* tokens: every line cut into longest-match tokens with end-ids       */
+/* ------------------------------------------------------------------ */
+
+/* The loop around a DFA in a lexer, for every line at once and in one launch per pass: a token is the longest prefix at a
+ * cursor that the automaton accepts, with the end-id of the state it was accepted in; after a token the cursor moves behind it
+ * and the same happens again until the line ends.
+ *   Input j is line pick[j] of a packed text: base, off[n + 1], pick / m or NULL, trim_byte, limit exactly as in struct
+ *   fsm_hip_pos_batch; len is the trimmed length; positions are byte boundaries relative to the line's first byte.
+ *   The cursor p starts at 0.  While p < len:
+ *   1. Walk the automaton from its start state over bytes p, p + 1, ...  The walk stops at a missing edge (DEAD), at len, or on
+ *      entering an absorbing state (one whose every byte leads back to it).  stop is the number of bytes consumed when it
+ *      stops, counted from the line's first byte; the byte with the missing edge is not consumed.
+ *   2. Longest-match rule (the default): e is the largest position in (p, len] at which the walk's state is an end state.  The
+ *      start state before any byte does not count: tokens are never empty.  An absorbing end state accepts at every later
+ *      position, so there e = len, and the bytes are not read.  q is the state at e.
+ *   3. FSM_HIP_TOKENS_NO_BACKTRACK: the token is (stop, the state at stop) if stop > p and that state is an end state;
+ *      otherwise there is none.  This is what lx's generated lexers do: they push back one character and never return to an
+ *      earlier accept.
+ *   4. A token: (end = e, id = id(q)) is emitted and p = e.  id() follows the image's ids mode: FSM_HIP_IDS_EARLIEST the lowest
+ *      end-id of q (a lower id is a higher rule priority), FSM_HIP_IDS_RET the index of its id set (the dfa's fsm_hip_ret_*
+ *      tables); an end state without ids gives FSM_HIP_NO_ID under EARLIEST.  FSM_HIP_IDS_ERROR is refused at create (EINVAL)
+ *      when fsm_hip_ids_conflict says so, and is EARLIEST otherwise.
+ *   5. No token at p: err[j] is the first such p (FSM_HIP_NO_POS if there is none).  By default the line stops there.  With
+ *      FSM_HIP_TOKENS_SKIP_BAD the one-byte token (p + 1, FSM_HIP_NO_MATCH) is emitted and the loop continues at p + 1.
+ *   Token t of a line starts where token t - 1 ended, the first at 0: only end and id are stored.  The tokens of a line tile
+ *   [0, err) by default and the whole line under SKIP_BAD.
+ * Cost: the bytes WALKED, which includes every overrun -- the bytes walked past e before the walk stopped are walked again
+ * from the next cursor.  The worst case is quadratic in the line's length.  Every step of the loop moves p forward by at least
+ * one byte or ends the line.
+ * struct fsm_hip_tok_dfa is the device image of a dfa for this walk, made from its host-side plan as fsm_hip_pos_dfa_create
+ * makes its own (a FSM_HIP_DEFER_UPLOAD dfa serves; the dfa may be freed afterwards), with one id per state under ids_mode.
+ * fsm_hip_tokens_run_device takes device pointers and hip_stream: a count pass, a scan of the counts, ONE wait for the total
+ * (as the hits have), the allocation, the emit pass, which is in flight at return.  A pick[j] >= n has no tokens and nothing is
+ * read for it; no byte outside [base, base + limit) is read whatever the offsets hold (limit == 0: off[n], read on the device).
+ * fsm_hip_tokens_run takes host pointers, stages them and waits; decreasing offsets and a pick[j] >= n are EINVAL before any
+ * launch; `limit` is ignored.  The object owns, on the device: off[m + 1] (the exclusive scan of the lines' token counts; off[m]
+ * = total), end[total] u64, id[total] u32, err[m].  _count is m.  _copy copies out whichever of off / end / id / err are not
+ * NULL and waits; _ms: the two walks and the scan by HIP events.  m == 0 or total == 0 gives a valid object and launches
+ * nothing that stores (the pointers of empty arrays are NULL, but off is always there).
+ * fsm_hip_text_tokens tokenises every line of a text object, or (hits != NULL) the lines of its hits in their order, with
+ * trim_byte = the text's delimiter: it takes the ORIGINAL automaton, as the spans do.  Its work is enqueued on hip_stream after
+ * the text's (the hits') last event.  The tokens must be freed before the image, and before the text where they came from one.
+ * NULL + errno: ENODEV (checked first: there is no CPU path), EINVAL (an argument NULL, off NULL, base NULL with bytes to read,
+ * an unknown flag bit, trim_byte outside -1 .. 255, an image on another device than the text), ENOMEM. */
+#define FSM_HIP_TOKENS_NO_BACKTRACK 1u
+#define FSM_HIP_TOKENS_SKIP_BAD 2u
+struct fsm_hip_tok_dfa;
+struct fsm_hip_tokens;
+struct fsm_hip_tok_batch {
+	const void *base;          /* the text's bytes */
+	const uint64_t *off;       /* n + 1 line offsets into base */
+	size_t n;                  /* lines */
+	const uint64_t *pick;      /* m line indices, or NULL: every line in order */
+	size_t m;                  /* inputs; ignored (n) when pick == NULL */
+	int trim_byte;             /* -1: none */
+	unsigned flags;            /* FSM_HIP_TOKENS_* */
+	uint64_t limit;            /* device form: bytes of base that may be read; 0: off[n] */
+};
+struct fsm_hip_tok_dfa *fsm_hip_tok_dfa_create(const struct fsm_hip_dfa *dfa, int ids_mode);
+void fsm_hip_tok_dfa_free(struct fsm_hip_tok_dfa *td);
+int fsm_hip_tok_dfa_in_lds(const struct fsm_hip_tok_dfa *td);   /* 1: the table is walked from LDS (S1 * C <= 16 384 entries); 0: from device memory, or NULL */
+struct fsm_hip_tokens *fsm_hip_tokens_run(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *batch);
+struct fsm_hip_tokens *fsm_hip_tokens_run_device(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *d_batch, void *hip_stream);
+struct fsm_hip_tokens *fsm_hip_text_tokens(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_text *t, const struct fsm_hip_text_hits *hits,
+	unsigned flags, void *hip_stream);
+size_t fsm_hip_tokens_count(const struct fsm_hip_tokens *tk);    /* m: the inputs */
+size_t fsm_hip_tokens_total(const struct fsm_hip_tokens *tk);    /* the tokens of all inputs */
+const uint64_t *fsm_hip_tokens_off_device(const struct fsm_hip_tokens *tk);    /* m + 1 */
+const uint64_t *fsm_hip_tokens_end_device(const struct fsm_hip_tokens *tk);    /* total; NULL when total == 0 */
+const uint32_t *fsm_hip_tokens_id_device(const struct fsm_hip_tokens *tk);     /* total; NULL when total == 0 */
+const uint64_t *fsm_hip_tokens_err_device(const struct fsm_hip_tokens *tk);    /* m; NULL when m == 0 */
+int fsm_hip_tokens_copy(const struct fsm_hip_tokens *tk, uint64_t *off, uint64_t *end, uint32_t *id, uint64_t *err);
+double fsm_hip_tokens_ms(const struct fsm_hip_tokens *tk);
+double fsm_hip_tokens_pass_ms(const struct fsm_hip_tokens *tk, int pass);      /* 0: the count pass, 1: the scan, 2: the emit pass */
+void fsm_hip_tokens_free(struct fsm_hip_tokens *tk);
+
+/* ------------------------------------------------------------------ */
 /* synthetic input generator (benchmarks and parity tests)            */
 /* ------------------------------------------------------------------ */
 

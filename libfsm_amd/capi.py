@@ -39,6 +39,8 @@ IN_DIRECT, IN_LDSDMA, IN_GENERIC, IN_RAGGED = 0, 1, 2, 3
 HITS_INVERT, HITS_NO_BYTES = 1, 2
 NO_POS = 0xFFFFFFFFFFFFFFFF
 POS_BACKWARD = 1
+TOKENS_NO_BACKTRACK, TOKENS_SKIP_BAD = 1, 2
+IDS_EARLIEST, IDS_RET, IDS_ERROR = 1, 2, 3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfsm_hip.so")
@@ -87,6 +89,11 @@ class PosBatch(C.Structure):
     """struct fsm_hip_pos_batch"""
     _fields_ = [("base", P), ("off", P), ("n", S), ("pick", P), ("m", S), ("from_", P), ("to", P), ("trim_byte", I), ("flags", U),
                 ("first_out", P), ("last_out", P), ("limit", U64)]
+
+
+class TokBatch(C.Structure):
+    """struct fsm_hip_tok_batch"""
+    _fields_ = [("base", P), ("off", P), ("n", S), ("pick", P), ("m", S), ("trim_byte", I), ("flags", U), ("limit", U64)]
 
 
 # ---- the ABI: every function the two headers declare, fsm_hip_<name>: (restype, argtypes) ------------------------------------
@@ -198,6 +205,18 @@ PROTOTYPES = {"fsm_hip_" + name: (restype, args) for restype, names, *args in (
     (P, "text_spans_start_device text_spans_end_device", P),
     (I, "text_spans_copy", P, P, P),
     (D, "text_spans_ms", P),
+    # tokens
+    (P, "tok_dfa_create", P, I),
+    (None, "tok_dfa_free tokens_free", P),
+    (I, "tok_dfa_in_lds", P),
+    (P, "tokens_run", P, P),
+    (P, "tokens_run_device", P, P, P),
+    (P, "text_tokens", P, P, P, U, P),
+    (S, "tokens_count tokens_total", P),
+    (P, "tokens_off_device tokens_end_device tokens_id_device tokens_err_device", P),
+    (I, "tokens_copy", P, P, P, P, P),
+    (D, "tokens_ms", P),
+    (D, "tokens_pass_ms", P, I),
     # input generators: (out, stride, n, first_index, seed, {bytes, count}..., every[, stream])
     (I, "gen_inputs_device", P, S, S, U64, U64, P, U, P, U, U, P),
     (None, "gen_inputs_host", P, S, S, U64, U64, P, U, P, U, U),
@@ -1543,3 +1562,122 @@ class HipSpans:
 
     def ms(self) -> float:
         return float(self._lib.fsm_hip_text_spans_ms(self._h))
+
+
+# ---- tokens: every line cut into longest-match tokens with end-ids (include/fsm_hip.h, "tokens") ----
+
+class TokDfa:
+    """struct fsm_hip_tok_dfa *: the device image of a HipDfa for the tokeniser's walk, one id per state under ids_mode (the dfa
+    may be closed afterwards)."""
+
+    def __init__(self, dfa: "HipDfa", ids_mode: int = IDS_EARLIEST):
+        self._lib = load_library()
+        self._h = _call("fsm_hip_tok_dfa_create", dfa.handle if dfa is not None else None, ids_mode)
+
+    @classmethod
+    def from_flat(cls, flat: FlatDfa, ids_mode: int = IDS_EARLIEST) -> "TokDfa":
+        """the image of a description: planned with DEFER_UPLOAD, so no other table goes to the device"""
+        dfa = HipDfa(flat, DEFER_UPLOAD)
+        try:
+            return cls(dfa, ids_mode)
+        finally:
+            dfa.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def in_lds(self) -> bool:
+        return bool(self._lib.fsm_hip_tok_dfa_in_lds(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.fsm_hip_tok_dfa_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def tokens(self, base: np.ndarray, off: np.ndarray, pick=None, trim_byte: int = -1, flags: int = 0) -> "HipTokens":
+        """fsm_hip_tokens_run on host arrays"""
+        base = np.ascontiguousarray(base, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        pick = None if pick is None else np.ascontiguousarray(pick, np.uint64)
+        n = len(off) - 1
+        m = n if pick is None else len(pick)
+        if pick is not None and m == 0:
+            pick = np.zeros(1, np.uint64)   # an empty pick is still a pick: a non-NULL address
+        b = TokBatch(_ptr0(base), _ptr(off), n, _ptr(pick), m, trim_byte, flags, 0)
+        return HipTokens(_call("fsm_hip_tokens_run", self._h, C.byref(b)), (self,))
+
+    def tokens_device(self, d_base: int, d_off: int, n: int, d_pick: int = 0, m: int = 0, trim_byte: int = -1, flags: int = 0, limit: int = 0,
+                      stream: int = 0) -> "HipTokens":
+        """fsm_hip_tokens_run_device: device addresses; the emit pass is in flight on `stream` at return"""
+        b = TokBatch(d_base or None, d_off or None, n, d_pick or None, m, trim_byte, flags, limit)
+        return HipTokens(_call("fsm_hip_tokens_run_device", self._h, C.byref(b), stream or None), (self,))
+
+    def text_tokens(self, text: "HipText", hits: Optional["HipHits"] = None, flags: int = 0, stream: int = 0) -> "HipTokens":
+        """fsm_hip_text_tokens: every line of a text, or the lines of its hits"""
+        return HipTokens(_call("fsm_hip_text_tokens", self._h, text.handle, hits.handle if hits is not None else None, flags, stream or None),
+                         (self, text, hits))
+
+
+class HipTokens:
+    """struct fsm_hip_tokens *: off[m + 1], end[total], id[total], err[m] on the device.  Keeps its image (and its text and
+    hits) alive: the tokens must be freed first."""
+
+    def __init__(self, handle, keep=()):
+        self._lib = load_library()
+        self._h, self._keep = handle, keep
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.fsm_hip_tokens_free(self._h)
+            self._h = None
+            self._keep = None
+
+    __del__ = close
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def count(self) -> int:
+        return int(self._lib.fsm_hip_tokens_count(self._h))
+
+    @property
+    def total(self) -> int:
+        return int(self._lib.fsm_hip_tokens_total(self._h))
+
+    @property
+    def off_ptr(self) -> int:
+        return int(self._lib.fsm_hip_tokens_off_device(self._h) or 0)
+
+    @property
+    def end_ptr(self) -> int:
+        return int(self._lib.fsm_hip_tokens_end_device(self._h) or 0)
+
+    @property
+    def id_ptr(self) -> int:
+        return int(self._lib.fsm_hip_tokens_id_device(self._h) or 0)
+
+    @property
+    def err_ptr(self) -> int:
+        return int(self._lib.fsm_hip_tokens_err_device(self._h) or 0)
+
+    def copy(self, extra: int = 0, fill: int = 0):
+        """-> (off u64 [m + 1], end u64 [total], id u32 [total], err u64 [m]); extra: that many more entries in each array,
+        pre-filled with `fill` and left alone by the library"""
+        m, total = self.count, self.total
+        off, end = np.full(m + 1 + extra, fill, np.uint64), np.full(total + extra, fill, np.uint64)
+        ids, err = np.full(total + extra, fill & 0xFFFFFFFF, np.uint32), np.full(m + extra, fill, np.uint64)
+        _call("fsm_hip_tokens_copy", self._h, _ptr(off), _ptr(end), _ptr(ids), _ptr(err))
+        return off, end, ids, err
+
+    def ms(self) -> float:
+        return float(self._lib.fsm_hip_tokens_ms(self._h))
+
+    def pass_ms(self, which: int) -> float:
+        """0: the count pass, 1: the scan, 2: the emit pass"""
+        return float(self._lib.fsm_hip_tokens_pass_ms(self._h, which))

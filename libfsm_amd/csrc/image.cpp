@@ -270,6 +270,41 @@ void ids_by_state(const Plan &p, int mode, std::vector<uint32_t> &out, uint32_t 
 	} else by_state(p, nullptr, out, conflict);
 }
 
+int build_tok_image(const Plan &p, int ids_mode, TokImage &im)
+{
+	im = TokImage();
+	const uint64_t entries = (uint64_t)p.S1 * p.C;
+	if (entries == 0 || p.S1 > 0x7fffffffu || entries > 0xffffffffu) return EINVAL;
+	if (ids_mode != FSM_HIP_IDS_EARLIEST && ids_mode != FSM_HIP_IDS_RET && ids_mode != FSM_HIP_IDS_ERROR) return EINVAL;
+	std::vector<uint32_t> by;
+	uint32_t conflict = FSM_HIP_NO_MATCH;
+	ids_by_state(p, ids_mode == FSM_HIP_IDS_RET ? FSM_HIP_IDS_RET : FSM_HIP_IDS_EARLIEST, by, &conflict);
+	if (ids_mode == FSM_HIP_IDS_ERROR && conflict != FSM_HIP_NO_MATCH) return EINVAL;
+	im.in_lds = entries <= TOK_LDS_ENTRIES;
+	im.entries = (uint32_t)entries;
+	im.C = p.C;
+	auto is_end = [&](uint32_t n) { return p.fin[n] != FSM_HIP_NO_MATCH ? 1u : 0u; };
+	im.col.resize(256);
+	if (im.in_lds) {
+		const uint32_t unit = p.C * 2u;          /* a row's bytes: (S1 - 1) * unit < 2^15, bit 0 is free */
+		im.tab16.resize(entries);
+		for (uint64_t e = 0; e < entries; e++) im.tab16[e] = (uint16_t)(p.dense[e] * unit | is_end(p.dense[e]));
+		for (uint32_t b = 0; b < 256u; b++) im.col[b] = (uint16_t)(p.cls[b] * 2u);
+		im.start = p.start * unit | is_end(p.start);
+		im.ids.assign(entries, FSM_HIP_NO_MATCH);
+	} else {
+		im.tab32.resize(entries);
+		for (uint64_t e = 0; e < entries; e++) im.tab32[e] = p.dense[e] | is_end(p.dense[e]) << 31;
+		for (uint32_t b = 0; b < 256u; b++) im.col[b] = p.cls[b];
+		im.start = p.start | is_end(p.start) << 31;
+		im.ids.assign(p.S1, FSM_HIP_NO_MATCH);
+	}
+	im.abs_min = im.code_of(p.abs_min);
+	im.dead = im.code_of(p.S1 - 1u);
+	for (uint32_t n = 0; n < p.S1; n++) im.ids[im.id_index(im.code_of(n))] = by[n];
+	return 0;
+}
+
 void build_id_tables(const Plan &p, const Image &img, IdTables &t)
 {
 	RetSets rs(p);

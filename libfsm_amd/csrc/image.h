@@ -62,6 +62,30 @@ int build_image(const Plan &p, Image &out);
  * (optional): the lowest caller's end state that carries more than one id, or FSM_HIP_NO_MATCH */
 void ids_by_state(const Plan &p, int mode, std::vector<uint32_t> &out, uint32_t *conflict);
 
+/* the tokeniser's image (tok.hip, walk_tok): the table in the two forms of the accept-position walk -- up to TOK_LDS_ENTRIES
+ * (state, class) entries a u16 row offset in bytes with "the target is an end state" in bit 0, walked from LDS; otherwise the
+ * u32 index of the target with that bit in bit 31, walked from device memory -- and one u32 id per state, read once per token.
+ * A state as the walk carries it ("code") is an entry of the table; id_index() is where its id lies in `ids`: the row's first
+ * entry in the LDS form (code >> 1, no division on the device; the other entries of `ids` hold FSM_HIP_NO_MATCH), the state
+ * itself otherwise. */
+constexpr uint32_t TOK_LDS_ENTRIES = 16384;
+struct TokImage {
+	bool in_lds = false;
+	uint32_t entries = 0, C = 0;
+	uint32_t start = 0;          /* code, its end bit folded in */
+	uint32_t abs_min = 0;        /* code (no end bit): states from here up are absorbing */
+	uint32_t dead = 0;           /* code of DEAD, the last state */
+	std::vector<uint16_t> tab16; /* [entries], LDS form */
+	std::vector<uint32_t> tab32; /* [entries], global form */
+	std::vector<uint16_t> col;   /* [256]: LDS form 2 * class (the byte offset of the byte's column), else the class */
+	std::vector<uint32_t> ids;   /* what a token accepted in a state gets, by id_index() */
+	uint32_t code_of(uint32_t n) const { return in_lds ? n * C * 2u : n; }
+	uint32_t id_index(uint32_t code) const { return in_lds ? code >> 1 : code & 0x7fffffffu; }
+};
+/* 0; EINVAL for an empty or oversized table, an unknown ids_mode, and for FSM_HIP_IDS_ERROR on an automaton with an end state
+ * of more than one id (a conflict-free one is built as FSM_HIP_IDS_EARLIEST) */
+int build_tok_image(const Plan &p, int ids_mode, TokImage &out);
+
 struct IdTables {
 	std::vector<uint32_t> earliest, ret;     /* by fin index: ids_by_state() carried through enc / fin_div */
 	std::vector<uint32_t> ret_off, ret_ids;  /* the de-duplicated id sets (CSR), ordered by count, then memcmp */

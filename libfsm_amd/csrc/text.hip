@@ -31,6 +31,7 @@
 #include "../../include/fsm_hip.h"
 #include "hip_host.h"
 #include "span.h"
+#include "tok.h"
 
 namespace {
 
@@ -1629,4 +1630,234 @@ extern "C" double fsm_hip_text_spans_ms(const struct fsm_hip_text_spans *sp)
 {
 	if (sp == nullptr) { errno = EINVAL; return -1.0; }
 	return elapsed_ms(sp->device, sp->ev[1], {{sp->ev[0], sp->ev[1]}});
+}
+
+/* ---- tokens: every line cut into longest-match tokens (tok.hip, walk_tok) ------------------------------------------------
+ * count pass -> exclusive scan of the counts by one workgroup -> ONE wait for the total -> allocation -> emit pass.  The counts
+ * are scanned in place: d_off is count[m] first, tok_off[m + 1] afterwards (the total lands in its last entry). */
+namespace {
+
+constexpr uint32_t TOK_SCAN_PER = 4;                        /* counts a thread of the scan takes a round: 4 096 lines a round trip */
+
+__global__ void __launch_bounds__(1024)
+tokens_scan(uint64_t *cnt, uint64_t m)
+{
+	sum_scan<1024, 1, TOK_SCAN_PER>(cnt, m, cnt + m);
+}
+
+}   // namespace
+
+struct __attribute__((visibility("hidden"))) fsm_hip_tokens {
+	int device = 0;
+	size_t m = 0, total = 0;
+	DevBuf<uint64_t> d_off;                  /* m + 1 */
+	DevBuf<uint64_t> d_err;                  /* m */
+	DevBuf<uint64_t> d_end;                  /* total */
+	DevBuf<uint32_t> d_id;                   /* total */
+	DevEvent ev[6];                          /* around the count pass, the scan, the emit pass; ev[5]: all is there */
+};
+
+extern "C" void fsm_hip_tokens_free(struct fsm_hip_tokens *tk)
+{
+	if (tk == nullptr) return;
+	const int e = errno;
+	{
+		DevGuard dg(tk->device);
+		if (tk->ev[5] != nullptr) (void)hipEventSynchronize(tk->ev[5]);
+		delete tk;
+	}
+	errno = e;
+}
+
+/* the passes on stream s into *tk, the image's device current; r: the inputs (its outputs are set here) */
+static int tokens_passes(struct fsm_hip_tokens *tk, const struct fsm_hip_tok_dfa *td, fsmhip::TokRun r, hipStream_t s)
+{
+	const uint64_t m = r.m;
+	uint64_t total = 0;
+	for (DevEvent &ev : tk->ev)
+		if (!HIP_OK(ev.create())) return -1;
+	if (!HIP_OK(tk->d_off.alloc(m + 1u))) return -1;
+	if (m != 0 && !HIP_OK(tk->d_err.alloc(m))) return -1;
+	r.count = tk->d_off;
+	r.err = tk->d_err;
+	if (!HIP_OK(hipEventRecord(tk->ev[0], s))) return -1;
+	if (m != 0 && fsmhip::tok_launch(td, r, false, s) != 0) return -1;
+	if (!HIP_OK(hipEventRecord(tk->ev[1], s)) || !HIP_OK(hipEventRecord(tk->ev[2], s))) return -1;
+	if (m != 0) {
+		hipLaunchKernelGGL(tokens_scan, dim3(1), dim3(1024), 0, s, tk->d_off.p, m);
+		if (!HIP_OK(hipGetLastError())) return -1;
+	} else if (!HIP_OK(hipMemsetAsync(tk->d_off, 0, sizeof(uint64_t), s))) {
+		return -1;
+	}
+	if (!HIP_OK(hipEventRecord(tk->ev[3], s))) return -1;
+	if (m != 0) {   /* the one wait: the total sizes the arrays */
+		if (!HIP_OK(hipMemcpyAsync(&total, tk->d_off + m, sizeof total, hipMemcpyDeviceToHost, s))) return -1;
+		if (!HIP_OK(hipStreamSynchronize(s))) return -1;
+	}
+	tk->total = (size_t)total;
+	if (total != 0 && (!HIP_OK(tk->d_end.alloc(total)) || !HIP_OK(tk->d_id.alloc(total)))) return -1;
+	if (!HIP_OK(hipEventRecord(tk->ev[4], s))) return -1;
+	if (total != 0) {
+		r.tok_off = tk->d_off;
+		r.end_out = tk->d_end;
+		r.id_out = tk->d_id;
+		if (fsmhip::tok_launch(td, r, true, s) != 0) return -1;
+	}
+	return HIP_OK(hipEventRecord(tk->ev[5], s)) ? 0 : -1;
+}
+
+/* the tokens object of a run on stream s; when the run fails, the stream is made idle before what it has launched on is released */
+static struct fsm_hip_tokens *tokens_new(const struct fsm_hip_tok_dfa *td, const fsmhip::TokRun &r, hipStream_t s)
+{
+	if ((r.m + fsmhip::TOK_THREADS - 1u) / fsmhip::TOK_THREADS > 0x7fffffffu) { errno = ENOMEM; return nullptr; }
+	struct fsm_hip_tokens *tk = new (std::nothrow) struct fsm_hip_tokens;
+	if (tk == nullptr) { errno = ENOMEM; return nullptr; }
+	tk->device = fsmhip::tok_dfa_device(td);
+	tk->m = (size_t)r.m;
+	if (tokens_passes(tk, td, r, s) == 0) return tk;
+	const int e = errno;
+	(void)hipStreamSynchronize(s);
+	fsm_hip_tokens_free(tk);
+	errno = e;
+	return nullptr;
+}
+
+/* the arguments both forms refuse alike; *m: the inputs */
+static int tokens_check(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *b, uint64_t *m)
+{
+	if (!have_device()) { errno = ENODEV; return -1; }
+	if (td == nullptr || b == nullptr || (b->flags & ~(FSM_HIP_TOKENS_NO_BACKTRACK | FSM_HIP_TOKENS_SKIP_BAD)) != 0u || b->trim_byte < -1 ||
+	    b->trim_byte > 255) {
+		errno = EINVAL;
+		return -1;
+	}
+	*m = b->pick != nullptr ? (uint64_t)b->m : (uint64_t)b->n;
+	if (*m != 0 && b->off == nullptr) { errno = EINVAL; return -1; }
+	return 0;
+}
+
+static fsmhip::TokRun tokens_run_of(const struct fsm_hip_tok_batch *b, uint64_t m)
+{
+	fsmhip::TokRun r;
+	r.base = b->base;
+	r.off = b->off;
+	r.pick = b->pick;
+	r.n = b->n;
+	r.m = m;
+	r.limit = b->limit;
+	r.has_limit = b->limit != 0u || b->base == nullptr;   /* no text: no byte may be read */
+	r.trim = b->trim_byte;
+	r.flags = b->flags;
+	return r;
+}
+
+extern "C" struct fsm_hip_tokens *fsm_hip_tokens_run_device(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *b, void *hip_stream)
+{
+	uint64_t m = 0;
+	if (tokens_check(td, b, &m) != 0) return nullptr;
+	if (b->base == nullptr && b->limit != 0u) { errno = EINVAL; return nullptr; }
+	DevGuard dg(fsmhip::tok_dfa_device(td));
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	return tokens_new(td, tokens_run_of(b, m), static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" struct fsm_hip_tokens *fsm_hip_tokens_run(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *b)
+{
+	uint64_t m = 0;
+	if (tokens_check(td, b, &m) != 0) return nullptr;
+	const uint64_t n = b->n;
+	if (m != 0) {
+		for (uint64_t i = 0; i < n; i++)
+			if (b->off[i] > b->off[i + 1u]) { errno = EINVAL; return nullptr; }
+		if (b->base == nullptr && b->off[n] != 0u) { errno = EINVAL; return nullptr; }
+		if (b->pick != nullptr)
+			for (uint64_t j = 0; j < m; j++)
+				if (b->pick[j] >= n) { errno = EINVAL; return nullptr; }
+	}
+	DevGuard dg(fsmhip::tok_dfa_device(td));
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	DevStream own;                                   /* never the NULL stream */
+	if (!HIP_OK(own.create(hipStreamNonBlocking))) return nullptr;
+	hipStream_t s = own;
+	fsmhip::TokRun r = tokens_run_of(b, m);
+	DevBuf<unsigned char> d;                         /* everything staged in one allocation, each piece at a multiple of 16 bytes */
+	if (m != 0) {
+		auto up16 = [](uint64_t x) { return (x + 15u) & ~(uint64_t)15u; };
+		const uint64_t nbytes = b->off[n], n_off = (n + 1u) * 8u, n_m = m * 8u;
+		const uint64_t at_off = up16(nbytes), at_pick = at_off + up16(n_off), all = at_pick + (b->pick ? up16(n_m) : 0u);
+		if (!HIP_OK(d.alloc(all))) return nullptr;
+		bool ok = nbytes == 0 || HIP_OK(hipMemcpyAsync(d, b->base, nbytes, hipMemcpyHostToDevice, s));
+		ok = ok && HIP_OK(hipMemcpyAsync(d + at_off, b->off, n_off, hipMemcpyHostToDevice, s));
+		ok = ok && (b->pick == nullptr || HIP_OK(hipMemcpyAsync(d + at_pick, b->pick, n_m, hipMemcpyHostToDevice, s)));
+		if (!ok) {   /* the stream idle before the staging memory goes */
+			const int e = errno;
+			(void)hipStreamSynchronize(s);
+			errno = e;
+			return nullptr;
+		}
+		r.base = nbytes != 0 ? d.p : nullptr;
+		r.limit = nbytes;
+		r.has_limit = true;
+		r.off = (const uint64_t *)(d + at_off);
+		r.pick = b->pick ? (const uint64_t *)(d + at_pick) : nullptr;
+	}
+	struct fsm_hip_tokens *tk = tokens_new(td, r, s);
+	if (tk == nullptr) return nullptr;               /* (tokens_new left the stream idle) */
+	if (!HIP_OK(hipStreamSynchronize(s))) {          /* the emit pass has read the staged text */
+		const int e = errno;
+		fsm_hip_tokens_free(tk);
+		errno = e;
+		return nullptr;
+	}
+	return tk;
+}
+
+extern "C" struct fsm_hip_tokens *fsm_hip_text_tokens(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_text *t, const struct fsm_hip_text_hits *h,
+	unsigned flags, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (td == nullptr || t == nullptr || (flags & ~(FSM_HIP_TOKENS_NO_BACKTRACK | FSM_HIP_TOKENS_SKIP_BAD)) != 0u) { errno = EINVAL; return nullptr; }
+	if (fsmhip::tok_dfa_device(td) != t->device || (h != nullptr && h->device != t->device)) { errno = EINVAL; return nullptr; }
+	DevGuard dg(t->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	/* the hits' lines (and, behind them, the text's offsets) first */
+	if (!HIP_OK(hipStreamWaitEvent(s, h != nullptr ? h->ev[5] : t->ev[3], 0))) return nullptr;
+	fsmhip::TokRun r;
+	r.base = t->d_text;
+	r.off = t->d_off;
+	r.n = t->n;
+	r.pick = h != nullptr ? h->d_lines.p : nullptr;
+	r.m = h != nullptr ? h->m : t->n;
+	r.limit = t->nbytes;
+	r.has_limit = true;
+	r.trim = t->delim;
+	r.flags = flags;
+	return tokens_new(td, r, s);
+}
+
+extern "C" size_t fsm_hip_tokens_count(const struct fsm_hip_tokens *tk) { return tk == nullptr ? 0 : tk->m; }
+extern "C" size_t fsm_hip_tokens_total(const struct fsm_hip_tokens *tk) { return tk == nullptr ? 0 : tk->total; }
+extern "C" const uint64_t *fsm_hip_tokens_off_device(const struct fsm_hip_tokens *tk) { return tk == nullptr ? nullptr : tk->d_off.p; }
+extern "C" const uint64_t *fsm_hip_tokens_end_device(const struct fsm_hip_tokens *tk) { return tk == nullptr ? nullptr : tk->d_end.p; }
+extern "C" const uint32_t *fsm_hip_tokens_id_device(const struct fsm_hip_tokens *tk) { return tk == nullptr ? nullptr : tk->d_id.p; }
+extern "C" const uint64_t *fsm_hip_tokens_err_device(const struct fsm_hip_tokens *tk) { return tk == nullptr ? nullptr : tk->d_err.p; }
+
+extern "C" int fsm_hip_tokens_copy(const struct fsm_hip_tokens *tk, uint64_t *off, uint64_t *end, uint32_t *id, uint64_t *err)
+{
+	if (tk == nullptr) { errno = EINVAL; return -1; }
+	return copy_out(tk->device, tk->ev[5], {{off, tk->d_off, (tk->m + 1u) * sizeof(uint64_t)}, {end, tk->d_end, tk->total * sizeof(uint64_t)},
+	                                        {id, tk->d_id, tk->total * sizeof(uint32_t)}, {err, tk->d_err, tk->m * sizeof(uint64_t)}});
+}
+
+extern "C" double fsm_hip_tokens_ms(const struct fsm_hip_tokens *tk)
+{
+	if (tk == nullptr) { errno = EINVAL; return -1.0; }
+	return elapsed_ms(tk->device, tk->ev[5], {{tk->ev[0], tk->ev[1]}, {tk->ev[2], tk->ev[3]}, {tk->ev[4], tk->ev[5]}});
+}
+
+extern "C" double fsm_hip_tokens_pass_ms(const struct fsm_hip_tokens *tk, int pass)
+{
+	if (tk == nullptr || pass < 0 || pass > 2) { errno = EINVAL; return -1.0; }
+	return elapsed_ms(tk->device, tk->ev[5], {{tk->ev[2 * pass], tk->ev[2 * pass + 1]}});
 }

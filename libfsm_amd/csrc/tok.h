@@ -1,0 +1,40 @@
+/*
+ * tok.h -- what text.hip may know about a struct fsm_hip_tok_dfa (defined in tok.hip): its device, and how one pass of the
+ * tokeniser's walk is launched.  The fronts (the tokens object, its scan) are in text.hip.  Not part of the C ABI.
+ */
+#ifndef FSMHIP_CSRC_TOK_H
+#define FSMHIP_CSRC_TOK_H
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+
+struct fsm_hip_tok_dfa;
+
+namespace fsmhip {
+
+constexpr uint32_t TOK_THREADS = 256;        /* inputs per workgroup, one per lane */
+
+/* one pass over m inputs; every pointer is device memory */
+struct TokRun {
+	const void *base = nullptr;
+	const uint64_t *off = nullptr;           /* n + 1 */
+	const uint64_t *pick = nullptr;          /* m, or null: input j is line j */
+	uint64_t n = 0, m = 0;
+	uint64_t limit = 0;                      /* has_limit: the bytes of base that may be read; else off[n] is */
+	bool has_limit = false;
+	int trim = -1;
+	unsigned flags = 0;                      /* FSM_HIP_TOKENS_* */
+	uint64_t *count = nullptr, *err = nullptr;           /* the count pass writes them: m each */
+	const uint64_t *tok_off = nullptr;                   /* the emit pass reads it: m + 1 */
+	uint64_t *end_out = nullptr;                         /* ... and stores at tok_off[j] + t */
+	uint32_t *id_out = nullptr;
+};
+
+__attribute__((visibility("hidden"))) int tok_dfa_device(const fsm_hip_tok_dfa *td);
+/* walk_tok<emit> on stream s, td's device current; 0, or -1 + errno */
+__attribute__((visibility("hidden"))) int tok_launch(const fsm_hip_tok_dfa *td, const TokRun &r, bool emit, hipStream_t s);
+
+}
+
+#endif
