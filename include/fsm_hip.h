@@ -1037,6 +1037,86 @@ double fsm_hip_tokens_pass_ms(const struct fsm_hip_tokens *tk, int pass);      /
 void fsm_hip_tokens_free(struct fsm_hip_tokens *tk);
 
 /* ------------------------------------------------------------------ */
+/* matches: every match of every line: start, end, end-id, in one call */
+/* ------------------------------------------------------------------ */
+
+/* All occurrences of a pattern in every line, without a host round per match: what grep -o, --color and a scanner with a union
+ * of rules need, and which rule it was.  The caller gives two images: `starts`, a struct fsm_hip_pos_dfa, walked backward, and
+ * `ends`, a struct fsm_hip_tok_dfa, walked forward; `ends` carries the end bit of every state, the start state included, and one
+ * id per state under its ids mode.
+ *   Input j is line pick[j] of a packed text: base, off[n + 1], pick / m or NULL, trim_byte, limit exactly as in struct
+ *   fsm_hip_tok_batch; len is the trimmed length; positions are byte boundaries relative to the line's first byte.
+ *   M(s), for s in [0, len]: the state of `starts` after walking bytes len - 1 down to s from its start state is an end state.
+ *   s = len is the start state, before any byte.  DEAD after a missing edge is sticky; once the walk is in an absorbing end state
+ *   every smaller s has M(s).
+ *   The cursor p starts at 0.  While p <= len:
+ *   1. start = the smallest s in [p, len] with M(s).  If there is none the input is done.
+ *   2. Walk `ends` from its start state over bytes start, start + 1, ...  The walk stops at a missing edge (DEAD), at len, or on
+ *      entering an absorbing state.
+ *   3. end = the largest e in [start, len] at which the walk's state is an end state.  e = start counts (the start state before
+ *      any byte): an empty match.  An absorbing end state accepts at every later position, so there end = len, and the bytes are
+ *      not read.  q is the state at end.
+ *   4. If there is no such e the input is done: a hit without a span stays without one (the rule of the rounds).
+ *   5. The match (start, end, id(q)) is emitted; id() follows the `ends` image's ids mode, as for tokens.
+ *   6. With FSM_HIP_MATCHES_DROP_EMPTY a match with end == start is not emitted (what grep does); the cursor moves the same.
+ *   7. p = end if end > start, else end + 1.
+ *   This is the sequence the rounds of fsm_hip_text_hits_spans / fsm_hip_text_spans_next deliver for the same two automata:
+ *   per input, round after round up to the first FSM_HIP_NO_POS.  When `starts` accepts the reversal of pat preceded by anything
+ *   and `ends` accepts exactly pat it is POSIX leftmost-longest, non-overlapping.  The library does not check that the two belong
+ *   together: the result is defined for any pair.
+ * Cost: `starts` walks every byte of a line at most ONCE however many matches the line has, and leaves one bit per position
+ * (the marks: internal to the object, len / 8 bytes of a walked line are written, addressed from the line's offset so that no
+ * scan is needed and no offsets can make a store leave the array; the array itself is sized by the limit, not by the lines that
+ * are walked -- limit / 8 + 2 n bytes, 128 MiB for a text of 1 GiB even for a single hit -- and is freed with the object); a lane
+ * then goes from mark to mark, sixteen positions a load, and never takes a position behind len.
+ * `ends` walks the bytes of every match and its overrun -- the bytes walked past end before the walk stopped are walked again
+ * from a later start, as for tokens.  Every step of the loop moves p forward by at least one byte or ends the input.
+ * fsm_hip_matches_run_device takes device pointers and hip_stream: the marks pass, a count pass, a scan of the counts, ONE wait
+ * for the total, the allocation, the emit pass, which is in flight at return.  The marks are sized by the bytes that may be
+ * read, so limit == 0 costs a second, short wait up front in which off[n] is read: give the limit.  A pick[j] >= n has no match
+ * and nothing is read for it; no byte outside [base, base + limit) is read whatever the offsets hold.  Offsets that decrease can
+ * give wrong matches, never a store outside the object's arrays.
+ * fsm_hip_matches_run takes host pointers, stages them and waits; decreasing offsets and a pick[j] >= n are EINVAL before any
+ * launch; `limit` is ignored.  The object owns, on the device: off[m + 1] (the exclusive scan of the inputs' match counts; off[m]
+ * = total), start[total] and end[total] u64, id[total] u32.  _count is m.  _copy copies out whichever of off / start / end / id
+ * are not NULL and waits; _ms: the four passes by HIP events; _pass_ms: one of them.  m == 0 or total == 0 gives a valid object
+ * and launches nothing that stores into its arrays (the pointers of empty arrays are NULL, but off is always there).
+ * fsm_hip_text_matches covers every line of a text object, or (hits != NULL) the lines of its hits in their order -- every kind
+ * of hits, FSM_HIP_HITS_NO_BYTES too: the text is read -- with trim_byte = the text's delimiter: both images are of ORIGINAL
+ * automata, as for the spans.  Its work is enqueued on hip_stream after the text's (the hits') last event.  The matches must be
+ * freed before both images, and before the text where they came from one.
+ * NULL + errno: ENODEV (checked first: there is no CPU path), EINVAL (an argument NULL, off NULL, base NULL with bytes to read,
+ * an unknown flag bit, trim_byte outside -1 .. 255, the two images or the text on different devices), ENOMEM. */
+#define FSM_HIP_MATCHES_DROP_EMPTY 1u
+struct fsm_hip_matches;
+struct fsm_hip_match_batch {
+	const void *base;          /* the text's bytes */
+	const uint64_t *off;       /* n + 1 line offsets into base */
+	size_t n;                  /* lines */
+	const uint64_t *pick;      /* m line indices, or NULL: every line in order */
+	size_t m;                  /* inputs; ignored (n) when pick == NULL */
+	int trim_byte;             /* -1: none */
+	unsigned flags;            /* FSM_HIP_MATCHES_* */
+	uint64_t limit;            /* device form: bytes of base that may be read; 0: off[n] */
+};
+struct fsm_hip_matches *fsm_hip_matches_run(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
+	const struct fsm_hip_match_batch *batch);
+struct fsm_hip_matches *fsm_hip_matches_run_device(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
+	const struct fsm_hip_match_batch *d_batch, void *hip_stream);
+struct fsm_hip_matches *fsm_hip_text_matches(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
+	const struct fsm_hip_text *t, const struct fsm_hip_text_hits *hits, unsigned flags, void *hip_stream);
+size_t fsm_hip_matches_count(const struct fsm_hip_matches *mt);    /* m: the inputs */
+size_t fsm_hip_matches_total(const struct fsm_hip_matches *mt);    /* the matches of all inputs */
+const uint64_t *fsm_hip_matches_off_device(const struct fsm_hip_matches *mt);      /* m + 1 */
+const uint64_t *fsm_hip_matches_start_device(const struct fsm_hip_matches *mt);    /* total; NULL when total == 0 */
+const uint64_t *fsm_hip_matches_end_device(const struct fsm_hip_matches *mt);      /* total; NULL when total == 0 */
+const uint32_t *fsm_hip_matches_id_device(const struct fsm_hip_matches *mt);       /* total; NULL when total == 0 */
+int fsm_hip_matches_copy(const struct fsm_hip_matches *mt, uint64_t *off, uint64_t *start, uint64_t *end, uint32_t *id);
+double fsm_hip_matches_ms(const struct fsm_hip_matches *mt);
+double fsm_hip_matches_pass_ms(const struct fsm_hip_matches *mt, int pass);        /* 0: the marks, 1: the count pass, 2: the scan, 3: the emit pass */
+void fsm_hip_matches_free(struct fsm_hip_matches *mt);
+
+/* ------------------------------------------------------------------ */
 /* synthetic input generator (benchmarks and parity tests)            */
 /* ------------------------------------------------------------------ */
 

@@ -13,4 +13,5 @@ from .capi import (  # noqa: F401
     HipHits, HITS_INVERT, HITS_NO_BYTES, text_hits_block_lines, text_hits_block_bytes, text_files_block, text_context_scan_block,
     NO_POS, POS_BACKWARD, PosBatch, PosDfa, HipSpans,
     TOKENS_NO_BACKTRACK, TOKENS_SKIP_BAD, IDS_EARLIEST, IDS_RET, IDS_ERROR, TokBatch, TokDfa, HipTokens,
+    MATCHES_DROP_EMPTY, MatchBatch, HipMatches,
 )

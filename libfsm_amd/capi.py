@@ -40,6 +40,7 @@ HITS_INVERT, HITS_NO_BYTES = 1, 2
 NO_POS = 0xFFFFFFFFFFFFFFFF
 POS_BACKWARD = 1
 TOKENS_NO_BACKTRACK, TOKENS_SKIP_BAD = 1, 2
+MATCHES_DROP_EMPTY = 1
 IDS_EARLIEST, IDS_RET, IDS_ERROR = 1, 2, 3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -93,6 +94,11 @@ class PosBatch(C.Structure):
 
 class TokBatch(C.Structure):
     """struct fsm_hip_tok_batch"""
+    _fields_ = [("base", P), ("off", P), ("n", S), ("pick", P), ("m", S), ("trim_byte", I), ("flags", U), ("limit", U64)]
+
+
+class MatchBatch(C.Structure):
+    """struct fsm_hip_match_batch"""
     _fields_ = [("base", P), ("off", P), ("n", S), ("pick", P), ("m", S), ("trim_byte", I), ("flags", U), ("limit", U64)]
 
 
@@ -217,6 +223,16 @@ PROTOTYPES = {"fsm_hip_" + name: (restype, args) for restype, names, *args in (
     (I, "tokens_copy", P, P, P, P, P),
     (D, "tokens_ms", P),
     (D, "tokens_pass_ms", P, I),
+    # matches
+    (P, "matches_run", P, P, P),
+    (P, "matches_run_device", P, P, P, P),
+    (P, "text_matches", P, P, P, P, U, P),
+    (None, "matches_free", P),
+    (S, "matches_count matches_total", P),
+    (P, "matches_off_device matches_start_device matches_end_device matches_id_device", P),
+    (I, "matches_copy", P, P, P, P, P),
+    (D, "matches_ms", P),
+    (D, "matches_pass_ms", P, I),
     # input generators: (out, stride, n, first_index, seed, {bytes, count}..., every[, stream])
     (I, "gen_inputs_device", P, S, S, U64, U64, P, U, P, U, U, P),
     (None, "gen_inputs_host", P, S, S, U64, U64, P, U, P, U, U),
@@ -1621,6 +1637,11 @@ class TokDfa:
         return HipTokens(_call("fsm_hip_text_tokens", self._h, text.handle, hits.handle if hits is not None else None, flags, stream or None),
                          (self, text, hits))
 
+    def text_matches(self, starts: PosDfa, text: "HipText", hits: Optional["HipHits"] = None, flags: int = 0, stream: int = 0) -> "HipMatches":
+        """fsm_hip_text_matches with this image as `ends`: every match of every line of a text, or of the lines of its hits"""
+        return HipMatches(_call("fsm_hip_text_matches", starts.handle, self._h, text.handle, hits.handle if hits is not None else None, flags,
+                                stream or None), (starts, self, text, hits))
+
 
 class HipTokens:
     """struct fsm_hip_tokens *: off[m + 1], end[total], id[total], err[m] on the device.  Keeps its image (and its text and
@@ -1681,3 +1702,87 @@ class HipTokens:
     def pass_ms(self, which: int) -> float:
         """0: the count pass, 1: the scan, 2: the emit pass"""
         return float(self._lib.fsm_hip_tokens_pass_ms(self._h, which))
+
+
+# ---- matches: every match of every line, start / end / end-id, in one call (include/fsm_hip.h, "matches") ----
+
+class HipMatches:
+    """struct fsm_hip_matches *: off[m + 1], start[total], end[total], id[total] on the device.  Keeps its two images (and its
+    text and hits) alive: the matches must be freed first."""
+
+    def __init__(self, handle, keep=()):
+        self._lib = load_library()
+        self._h, self._keep = handle, keep
+
+    @classmethod
+    def run(cls, starts: PosDfa, ends: TokDfa, base: np.ndarray, off: np.ndarray, pick=None, trim_byte: int = -1, flags: int = 0) -> "HipMatches":
+        """fsm_hip_matches_run on host arrays"""
+        base = np.ascontiguousarray(base, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        pick = None if pick is None else np.ascontiguousarray(pick, np.uint64)
+        n = len(off) - 1
+        m = n if pick is None else len(pick)
+        if pick is not None and m == 0:
+            pick = np.zeros(1, np.uint64)   # an empty pick is still a pick: a non-NULL address
+        b = MatchBatch(_ptr0(base), _ptr(off), n, _ptr(pick), m, trim_byte, flags, 0)
+        return cls(_call("fsm_hip_matches_run", starts.handle, ends.handle, C.byref(b)), (starts, ends))
+
+    @classmethod
+    def run_device(cls, starts: PosDfa, ends: TokDfa, d_base: int, d_off: int, n: int, d_pick: int = 0, m: int = 0, trim_byte: int = -1,
+                   flags: int = 0, limit: int = 0, stream: int = 0) -> "HipMatches":
+        """fsm_hip_matches_run_device: device addresses; the emit pass is in flight on `stream` at return"""
+        b = MatchBatch(d_base or None, d_off or None, n, d_pick or None, m, trim_byte, flags, limit)
+        return cls(_call("fsm_hip_matches_run_device", starts.handle, ends.handle, C.byref(b), stream or None), (starts, ends))
+
+    def free(self):
+        if getattr(self, "_h", None):
+            self._lib.fsm_hip_matches_free(self._h)
+            self._h = None
+            self._keep = None
+
+    close = free
+    __del__ = free
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def count(self) -> int:
+        return int(self._lib.fsm_hip_matches_count(self._h))
+
+    @property
+    def total(self) -> int:
+        return int(self._lib.fsm_hip_matches_total(self._h))
+
+    @property
+    def off_ptr(self) -> int:
+        return int(self._lib.fsm_hip_matches_off_device(self._h) or 0)
+
+    @property
+    def start_ptr(self) -> int:
+        return int(self._lib.fsm_hip_matches_start_device(self._h) or 0)
+
+    @property
+    def end_ptr(self) -> int:
+        return int(self._lib.fsm_hip_matches_end_device(self._h) or 0)
+
+    @property
+    def id_ptr(self) -> int:
+        return int(self._lib.fsm_hip_matches_id_device(self._h) or 0)
+
+    def copy(self, extra: int = 0, fill: int = 0):
+        """-> (off u64 [m + 1], start u64 [total], end u64 [total], id u32 [total]); extra: that many more entries in each array,
+        pre-filled with `fill` and left alone by the library"""
+        m, total = self.count, self.total
+        off, start = np.full(m + 1 + extra, fill, np.uint64), np.full(total + extra, fill, np.uint64)
+        end, ids = np.full(total + extra, fill, np.uint64), np.full(total + extra, fill & 0xFFFFFFFF, np.uint32)
+        _call("fsm_hip_matches_copy", self._h, _ptr(off), _ptr(start), _ptr(end), _ptr(ids))
+        return off, start, end, ids
+
+    def ms(self) -> float:
+        return float(self._lib.fsm_hip_matches_ms(self._h))
+
+    def pass_ms(self, which: int) -> float:
+        """0: the marks, 1: the count pass, 2: the scan, 3: the emit pass"""
+        return float(self._lib.fsm_hip_matches_pass_ms(self._h, which))

@@ -37,7 +37,6 @@ using namespace fsmhip;
 
 namespace {
 
-constexpr uint32_t POS_LDS_ENTRIES = 16384;            /* a table of up to this many (state, class) entries is walked from LDS */
 constexpr uint32_t POS_WAVES = 4;                      /* wavefronts per workgroup: POS_WAVES * 64 consecutive inputs share a table copy */
 constexpr uint32_t POS_THREADS = POS_WAVES * 64u;
 static_assert(POS_THREADS == 256, "one thread per byte value copies the class map");
@@ -221,6 +220,19 @@ struct __attribute__((visibility("hidden"))) fsm_hip_pos_dfa {
 
 namespace fsmhip {
 int pos_dfa_device(const fsm_hip_pos_dfa *pd) { return pd->device; }
+
+PosView pos_dfa_view(const fsm_hip_pos_dfa *pd)
+{
+	PosView v;
+	v.tab = pd->d_tab.p;
+	v.col = pd->d_col.p;
+	v.entries = pd->entries;
+	v.C = pd->C;
+	v.start = pd->start;
+	v.abs_min = pd->abs_min;
+	v.in_lds = pd->in_lds;
+	return v;
+}
 }
 
 extern "C" struct fsm_hip_pos_dfa *fsm_hip_pos_dfa_create(const struct fsm_hip_dfa *dfa)

@@ -30,6 +30,8 @@
 
 #include "../../include/fsm_hip.h"
 #include "hip_host.h"
+#include "match.h"
+#include "match_marks.h"
 #include "span.h"
 #include "tok.h"
 
@@ -1860,4 +1862,239 @@ extern "C" double fsm_hip_tokens_pass_ms(const struct fsm_hip_tokens *tk, int pa
 {
 	if (tk == nullptr || pass < 0 || pass > 2) { errno = EINVAL; return -1.0; }
 	return elapsed_ms(tk->device, tk->ev[5], {{tk->ev[2 * pass], tk->ev[2 * pass + 1]}});
+}
+
+/* ---- matches: every match of every line (match.hip, walk_mark / walk_match) -------------------------------------------------
+ * marks pass -> count pass -> exclusive scan of the counts by one workgroup -> ONE wait for the total -> allocation -> emit
+ * pass.  The counts are scanned in place, as the tokens' are: d_off is count[m] first, match_off[m + 1] afterwards. */
+struct __attribute__((visibility("hidden"))) fsm_hip_matches {
+	int device = 0;
+	size_t m = 0, total = 0;
+	DevBuf<uint16_t> d_marks;                /* marks_words(limit, n): internal */
+	DevBuf<uint64_t> d_off;                  /* m + 1 */
+	DevBuf<uint64_t> d_start, d_end;         /* total each */
+	DevBuf<uint32_t> d_id;                   /* total */
+	DevEvent ev[8];                          /* around the marks pass, the count pass, the scan, the emit pass; ev[7]: all is there */
+};
+
+extern "C" void fsm_hip_matches_free(struct fsm_hip_matches *mt)
+{
+	if (mt == nullptr) return;
+	const int e = errno;
+	{
+		DevGuard dg(mt->device);
+		if (mt->ev[7] != nullptr) (void)hipEventSynchronize(mt->ev[7]);
+		delete mt;
+	}
+	errno = e;
+}
+
+/* the passes on stream s into *mt, the images' device current; r: the inputs, its limit given (its outputs are set here) */
+static int matches_passes(struct fsm_hip_matches *mt, const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, fsmhip::MatchRun r,
+	hipStream_t s)
+{
+	const uint64_t m = r.m;
+	uint64_t total = 0;
+	for (DevEvent &ev : mt->ev)
+		if (!HIP_OK(ev.create())) return -1;
+	if (!HIP_OK(mt->d_off.alloc(m + 1u))) return -1;
+	r.nwords = fsmhip::marks_words(r.limit, r.n);
+	if (m != 0 && !HIP_OK(mt->d_marks.alloc(r.nwords))) return -1;
+	r.marks = mt->d_marks;
+	r.count = mt->d_off;
+	if (!HIP_OK(hipEventRecord(mt->ev[0], s))) return -1;
+	if (m != 0 && fsmhip::match_launch_mark(starts, r, s) != 0) return -1;
+	if (!HIP_OK(hipEventRecord(mt->ev[1], s)) || !HIP_OK(hipEventRecord(mt->ev[2], s))) return -1;
+	if (m != 0 && fsmhip::match_launch(ends, r, false, s) != 0) return -1;
+	if (!HIP_OK(hipEventRecord(mt->ev[3], s)) || !HIP_OK(hipEventRecord(mt->ev[4], s))) return -1;
+	if (m != 0) {
+		hipLaunchKernelGGL(tokens_scan, dim3(1), dim3(1024), 0, s, mt->d_off.p, m);
+		if (!HIP_OK(hipGetLastError())) return -1;
+	} else if (!HIP_OK(hipMemsetAsync(mt->d_off, 0, sizeof(uint64_t), s))) {
+		return -1;
+	}
+	if (!HIP_OK(hipEventRecord(mt->ev[5], s))) return -1;
+	if (m != 0) {   /* the one wait: the total sizes the arrays */
+		if (!HIP_OK(hipMemcpyAsync(&total, mt->d_off + m, sizeof total, hipMemcpyDeviceToHost, s))) return -1;
+		if (!HIP_OK(hipStreamSynchronize(s))) return -1;
+	}
+	mt->total = (size_t)total;
+	if (total != 0 && (!HIP_OK(mt->d_start.alloc(total)) || !HIP_OK(mt->d_end.alloc(total)) || !HIP_OK(mt->d_id.alloc(total)))) return -1;
+	if (!HIP_OK(hipEventRecord(mt->ev[6], s))) return -1;
+	if (total != 0) {
+		r.match_off = mt->d_off;
+		r.start_out = mt->d_start;
+		r.end_out = mt->d_end;
+		r.id_out = mt->d_id;
+		if (fsmhip::match_launch(ends, r, true, s) != 0) return -1;
+	}
+	return HIP_OK(hipEventRecord(mt->ev[7], s)) ? 0 : -1;
+}
+
+/* the matches object of a run on stream s; when the run fails, the stream is made idle before what it has launched on is released */
+static struct fsm_hip_matches *matches_new(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, const fsmhip::MatchRun &r,
+	hipStream_t s)
+{
+	if (!fsmhip::match_grid_fits(r.m)) { errno = ENOMEM; return nullptr; }
+	struct fsm_hip_matches *mt = new (std::nothrow) struct fsm_hip_matches;
+	if (mt == nullptr) { errno = ENOMEM; return nullptr; }
+	mt->device = fsmhip::tok_dfa_device(ends);
+	mt->m = (size_t)r.m;
+	if (matches_passes(mt, starts, ends, r, s) == 0) return mt;
+	const int e = errno;
+	(void)hipStreamSynchronize(s);
+	fsm_hip_matches_free(mt);
+	errno = e;
+	return nullptr;
+}
+
+/* the arguments both forms refuse alike; *m: the inputs */
+static int matches_check(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, const struct fsm_hip_match_batch *b, uint64_t *m)
+{
+	if (!have_device()) { errno = ENODEV; return -1; }
+	if (starts == nullptr || ends == nullptr || b == nullptr || (b->flags & ~FSM_HIP_MATCHES_DROP_EMPTY) != 0u || b->trim_byte < -1 ||
+	    b->trim_byte > 255) {
+		errno = EINVAL;
+		return -1;
+	}
+	if (fsmhip::pos_dfa_device(starts) != fsmhip::tok_dfa_device(ends)) { errno = EINVAL; return -1; }
+	*m = b->pick != nullptr ? (uint64_t)b->m : (uint64_t)b->n;
+	if (*m != 0 && b->off == nullptr) { errno = EINVAL; return -1; }
+	return 0;
+}
+
+static fsmhip::MatchRun matches_run_of(const struct fsm_hip_match_batch *b, uint64_t m)
+{
+	fsmhip::MatchRun r;
+	r.base = b->base;
+	r.off = b->off;
+	r.pick = b->pick;
+	r.n = b->n;
+	r.m = m;
+	r.limit = b->limit;
+	r.trim = b->trim_byte;
+	r.flags = b->flags;
+	return r;
+}
+
+extern "C" struct fsm_hip_matches *fsm_hip_matches_run_device(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
+	const struct fsm_hip_match_batch *b, void *hip_stream)
+{
+	uint64_t m = 0;
+	if (matches_check(starts, ends, b, &m) != 0) return nullptr;
+	if (b->base == nullptr && b->limit != 0u) { errno = EINVAL; return nullptr; }
+	DevGuard dg(fsmhip::tok_dfa_device(ends));
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	fsmhip::MatchRun r = matches_run_of(b, m);
+	if (m != 0 && b->limit == 0u && b->base != nullptr) {   /* the marks are sized by the limit: off[n], a short wait of its own */
+		uint64_t last = 0;
+		if (!HIP_OK(hipMemcpyAsync(&last, b->off + b->n, sizeof last, hipMemcpyDeviceToHost, s)) || !HIP_OK(hipStreamSynchronize(s))) return nullptr;
+		r.limit = last;
+	}
+	return matches_new(starts, ends, r, s);
+}
+
+extern "C" struct fsm_hip_matches *fsm_hip_matches_run(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
+	const struct fsm_hip_match_batch *b)
+{
+	uint64_t m = 0;
+	if (matches_check(starts, ends, b, &m) != 0) return nullptr;
+	const uint64_t n = b->n;
+	if (m != 0) {
+		for (uint64_t i = 0; i < n; i++)
+			if (b->off[i] > b->off[i + 1u]) { errno = EINVAL; return nullptr; }
+		if (b->base == nullptr && b->off[n] != 0u) { errno = EINVAL; return nullptr; }
+		if (b->pick != nullptr)
+			for (uint64_t j = 0; j < m; j++)
+				if (b->pick[j] >= n) { errno = EINVAL; return nullptr; }
+	}
+	DevGuard dg(fsmhip::tok_dfa_device(ends));
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	DevStream own;                                   /* never the NULL stream */
+	if (!HIP_OK(own.create(hipStreamNonBlocking))) return nullptr;
+	hipStream_t s = own;
+	fsmhip::MatchRun r = matches_run_of(b, m);
+	r.limit = 0;
+	DevBuf<unsigned char> d;                         /* everything staged in one allocation, each piece at a multiple of 16 bytes */
+	if (m != 0) {
+		auto up16 = [](uint64_t x) { return (x + 15u) & ~(uint64_t)15u; };
+		const uint64_t nbytes = b->off[n], n_off = (n + 1u) * 8u, n_m = m * 8u;
+		const uint64_t at_off = up16(nbytes), at_pick = at_off + up16(n_off), all = at_pick + (b->pick ? up16(n_m) : 0u);
+		if (!HIP_OK(d.alloc(all))) return nullptr;
+		bool ok = nbytes == 0 || HIP_OK(hipMemcpyAsync(d, b->base, nbytes, hipMemcpyHostToDevice, s));
+		ok = ok && HIP_OK(hipMemcpyAsync(d + at_off, b->off, n_off, hipMemcpyHostToDevice, s));
+		ok = ok && (b->pick == nullptr || HIP_OK(hipMemcpyAsync(d + at_pick, b->pick, n_m, hipMemcpyHostToDevice, s)));
+		if (!ok) {   /* the stream idle before the staging memory goes */
+			const int e = errno;
+			(void)hipStreamSynchronize(s);
+			errno = e;
+			return nullptr;
+		}
+		r.base = nbytes != 0 ? d.p : nullptr;
+		r.limit = nbytes;
+		r.off = (const uint64_t *)(d + at_off);
+		r.pick = b->pick ? (const uint64_t *)(d + at_pick) : nullptr;
+	}
+	struct fsm_hip_matches *mt = matches_new(starts, ends, r, s);
+	if (mt == nullptr) return nullptr;               /* (matches_new left the stream idle) */
+	if (!HIP_OK(hipStreamSynchronize(s))) {          /* the emit pass has read the staged text */
+		const int e = errno;
+		fsm_hip_matches_free(mt);
+		errno = e;
+		return nullptr;
+	}
+	return mt;
+}
+
+extern "C" struct fsm_hip_matches *fsm_hip_text_matches(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
+	const struct fsm_hip_text *t, const struct fsm_hip_text_hits *h, unsigned flags, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (starts == nullptr || ends == nullptr || t == nullptr || (flags & ~FSM_HIP_MATCHES_DROP_EMPTY) != 0u) { errno = EINVAL; return nullptr; }
+	if (fsmhip::pos_dfa_device(starts) != t->device || fsmhip::tok_dfa_device(ends) != t->device || (h != nullptr && h->device != t->device)) {
+		errno = EINVAL;
+		return nullptr;
+	}
+	DevGuard dg(t->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	/* the hits' lines (and, behind them, the text's offsets) first */
+	if (!HIP_OK(hipStreamWaitEvent(s, h != nullptr ? h->ev[5] : t->ev[3], 0))) return nullptr;
+	fsmhip::MatchRun r;
+	r.base = t->d_text;
+	r.off = t->d_off;
+	r.n = t->n;
+	r.pick = h != nullptr ? h->d_lines.p : nullptr;
+	r.m = h != nullptr ? h->m : t->n;
+	r.limit = t->nbytes;
+	r.trim = t->delim;
+	r.flags = flags;
+	return matches_new(starts, ends, r, s);
+}
+
+extern "C" size_t fsm_hip_matches_count(const struct fsm_hip_matches *mt) { return mt == nullptr ? 0 : mt->m; }
+extern "C" size_t fsm_hip_matches_total(const struct fsm_hip_matches *mt) { return mt == nullptr ? 0 : mt->total; }
+extern "C" const uint64_t *fsm_hip_matches_off_device(const struct fsm_hip_matches *mt) { return mt == nullptr ? nullptr : mt->d_off.p; }
+extern "C" const uint64_t *fsm_hip_matches_start_device(const struct fsm_hip_matches *mt) { return mt == nullptr ? nullptr : mt->d_start.p; }
+extern "C" const uint64_t *fsm_hip_matches_end_device(const struct fsm_hip_matches *mt) { return mt == nullptr ? nullptr : mt->d_end.p; }
+extern "C" const uint32_t *fsm_hip_matches_id_device(const struct fsm_hip_matches *mt) { return mt == nullptr ? nullptr : mt->d_id.p; }
+
+extern "C" int fsm_hip_matches_copy(const struct fsm_hip_matches *mt, uint64_t *off, uint64_t *start, uint64_t *end, uint32_t *id)
+{
+	if (mt == nullptr) { errno = EINVAL; return -1; }
+	return copy_out(mt->device, mt->ev[7], {{off, mt->d_off, (mt->m + 1u) * sizeof(uint64_t)}, {start, mt->d_start, mt->total * sizeof(uint64_t)},
+	                                        {end, mt->d_end, mt->total * sizeof(uint64_t)}, {id, mt->d_id, mt->total * sizeof(uint32_t)}});
+}
+
+extern "C" double fsm_hip_matches_ms(const struct fsm_hip_matches *mt)
+{
+	if (mt == nullptr) { errno = EINVAL; return -1.0; }
+	return elapsed_ms(mt->device, mt->ev[7], {{mt->ev[0], mt->ev[1]}, {mt->ev[2], mt->ev[3]}, {mt->ev[4], mt->ev[5]}, {mt->ev[6], mt->ev[7]}});
+}
+
+extern "C" double fsm_hip_matches_pass_ms(const struct fsm_hip_matches *mt, int pass)
+{
+	if (mt == nullptr || pass < 0 || pass > 3) { errno = EINVAL; return -1.0; }
+	return elapsed_ms(mt->device, mt->ev[7], {{mt->ev[2 * pass], mt->ev[2 * pass + 1]}});
 }

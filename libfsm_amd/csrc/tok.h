@@ -31,7 +31,18 @@ struct TokRun {
 	uint32_t *id_out = nullptr;
 };
 
+/* the image as walk_tok reads it (image.h, TokImage), for match.hip; every pointer is device memory and lives as long as the image */
+struct TokView {
+	const void *tab = nullptr;               /* [entries]: u16 (LDS form) or u32, the end-state bit of the target folded in */
+	const uint16_t *col = nullptr;           /* [256] */
+	const uint32_t *ids = nullptr;           /* by TokImage::id_index() */
+	uint32_t entries = 0, C = 0;
+	uint32_t start = 0, abs_min = 0;         /* in the walk's unit */
+	uint32_t in_lds = 0;
+};
+
 __attribute__((visibility("hidden"))) int tok_dfa_device(const fsm_hip_tok_dfa *td);
+__attribute__((visibility("hidden"))) TokView tok_dfa_view(const fsm_hip_tok_dfa *td);
 /* walk_tok<emit> on stream s, td's device current; 0, or -1 + errno */
 __attribute__((visibility("hidden"))) int tok_launch(const fsm_hip_tok_dfa *td, const TokRun &r, bool emit, hipStream_t s);
 

@@ -254,6 +254,20 @@ namespace fsmhip {
 
 int tok_dfa_device(const fsm_hip_tok_dfa *td) { return td->device; }
 
+TokView tok_dfa_view(const fsm_hip_tok_dfa *td)
+{
+	TokView v;
+	v.tab = td->d_tab.p;
+	v.col = td->d_col.p;
+	v.ids = td->d_ids.p;
+	v.entries = td->entries;
+	v.C = td->C;
+	v.start = td->start;
+	v.abs_min = td->abs_min;
+	v.in_lds = td->in_lds;
+	return v;
+}
+
 int tok_launch(const fsm_hip_tok_dfa *td, const TokRun &r, bool emit, hipStream_t s)
 {
 	if (r.m == 0) return 0;

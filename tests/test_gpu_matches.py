@@ -1,0 +1,608 @@
+"""GPU: matches (libfsm_amd/csrc/match.hip: walk_mark, walk_match<false>, walk_match<true>; the fronts in text.hip).
+
+Every answer -- count, match_off, start, end, id, total -- is compared with tests/matches_ref.py, the definition of
+include/fsm_hip.h ("matches") restated in Python over the automata's own formulas, never with the rounds on the device or with
+anything else derived from the code under test.  The automata are global_ref.affine's (those of tests/test_gpu_spans.py),
+span_ref's variants of them and its Python Aho-Corasick; the inputs are the 1 500 rows of tests/test_gpu_spans.py, rebuilt
+here."""
+import ctypes as C
+import errno
+
+import numpy as np
+import pytest
+
+import matches_ref
+import span_ref
+import tokens_ref
+from global_ref import affine, packed
+from matches_ref import DROP_EMPTY
+from tokens_ref import EARLIEST, RET
+
+pytestmark = pytest.mark.gpu
+
+FILL = 0xA5A5A5A5A5A5A5A5
+LEAD = 5                                     # off[0]: the text does not begin at base
+# name -> (S, K, keyword arguments, the start state is an end state too, walked from LDS)
+AUTOMATA = {
+    "s15_start": (15, 4, {}, True, True),
+    "s200_dying": (200, 4, dict(holes=16, sinks=3), False, True),
+    "lds_full": (1023, 16, {}, False, True),                        # 1024 * 16 = 16 384 entries: the largest LDS image
+    "glob_first": (1024, 16, {}, False, False),                     # 1025 * 16 = 16 400 entries: the first global image
+    "dying1023": (1023, 16, dict(holes=8, sinks=4), False, True),
+}
+SIZES = (1, 63, 64, 65, 255, 256, 257, 1500)
+WORDS = [b"ab", b"abc", b"ca", b"d", b"bdb"]
+
+
+@pytest.fixture(scope="module")
+def hip(built):
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a MI355X"
+    torch.cuda.set_device(0)
+    import libfsm_amd
+    libfsm_amd.load_library()   # raises if the HIP extension is missing: no silent fallback
+    return libfsm_amd
+
+
+def device_u64(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()
+
+
+def device_u8(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, np.uint8).copy()).cuda()
+
+
+def make_inputs():
+    """1 500 rows of 300 random bytes; lengths 0, 1, 15, 16, 17, 31, 32, 33, then odd rows 0-12 and even rows 0-300"""
+    rng = np.random.RandomState(11)
+    rows = rng.randint(0, 256, (1500, 300)).astype(np.uint8)
+    lens = np.where(np.arange(1500) % 2 == 1, rng.randint(0, 13, 1500), rng.randint(0, 301, 1500)).astype(np.int64)
+    lens[:8] = [0, 1, 15, 16, 17, 31, 32, 33]
+    return rows, lens
+
+
+def keyword_inputs():
+    """the same 1 500 lengths, the lines built from the keywords and a filler letter now and then; line 8: 300 times d"""
+    rng = np.random.RandomState(19)
+    _, lens = make_inputs()
+    pieces = WORDS + [b"x", b"a", b"b"]
+    rows = np.zeros((1500, 300), np.uint8)
+    for i in range(1500):
+        line = b"".join(pieces[k] for k in rng.randint(0, len(pieces), 300))[:300]
+        rows[i] = np.frombuffer(line, np.uint8)
+    lens = lens.copy()
+    lens[8] = 300
+    rows[8] = ord("d")
+    return rows, lens
+
+
+def lead_packed(rows, lens, lead=LEAD):
+    """the lines packed behind `lead` bytes that belong to no line: (bytes of exactly off[n], off with off[0] = lead)"""
+    data, off = packed(rows, lens)
+    return np.concatenate([np.full(lead, 0x5A, np.uint8), data]), off + np.uint64(lead)
+
+
+_inputs, _autos, _starts, _ends, _marks, _longest, _refs = {}, {}, {}, {}, {}, {}, {}
+
+
+def inputs_of(name):
+    kind = "keywords" if name.startswith("kw") else "random"
+    if kind not in _inputs:
+        _inputs[kind] = keyword_inputs() if kind == "keywords" else make_inputs()
+        for a in _inputs[kind]:
+            a.setflags(write=False)
+    return _inputs[kind]
+
+
+def auto_of(name):
+    """name -> (auto, {state: ids} or None, walked from LDS or None: not asserted)"""
+    if name not in _autos:
+        if name in AUTOMATA:
+            S, K, kw, start_ends, in_lds = AUTOMATA[name]
+            auto = affine(S, K, endids=True, **kw)
+            if start_ends:     # (with_is_end drops the ids: such an `ends` gives FSM_HIP_NO_ID everywhere)
+                auto = span_ref.start_accepting_of(auto)
+            from libfsm_amd import Plan
+            plan = Plan(auto[0])
+            assert (plan.S1, plan.C) == (S + 1, K) and (plan.S1 * plan.C <= 16384) == in_lds
+            _autos[name] = (auto, None, in_lds)
+        elif name == "kw_starts":
+            _autos[name] = (span_ref.starts_of(WORDS), None, None)
+        elif name == "kw_starts_everywhere":
+            _autos[name] = (span_ref.everywhere_of(span_ref.starts_of(WORDS)), None, None)
+        elif name in ("kw_ends", "kw_ends_two"):
+            auto, sets = tokens_ref.trie_lexer(WORDS)
+            if name == "kw_ends_two":           # a union where the state of "ab" carries two ids
+                from libfsm_amd import FlatDfa
+                sets = {s: ([3, 9] if v == [0] else [v[0] + 10]) for s, v in sets.items()}
+                auto = (FlatDfa.from_dense(auto[1], 0, np.asarray(auto[0].is_end, np.uint8), endids=sets), auto[1], auto[2])
+            _autos[name] = (auto, sets, None)
+        elif name == "sink_one":                # one accepting state, every byte leads back to it: an absorbing START state
+            _autos[name] = (span_ref._auto(np.zeros((1, 256), np.int64), [True]), None, None)
+        else:
+            assert name == "kw_ends_empty"
+            _autos[name] = (span_ref.ends_of(WORDS, empty=True), None, None)
+        assert _autos[name][0][0].start == 0
+    return _autos[name]
+
+
+def starts_image(name):
+    if name not in _starts:
+        from libfsm_amd import PosDfa
+        auto, _, in_lds = auto_of(name)
+        pd = PosDfa.from_flat(auto[0])
+        assert in_lds is None or pd.in_lds == in_lds       # the form, before any launch
+        _starts[name] = pd
+    return _starts[name]
+
+
+def ends_image(name, mode=EARLIEST):
+    if (name, mode) not in _ends:
+        from libfsm_amd import TokDfa
+        auto, _, in_lds = auto_of(name)
+        td = TokDfa.from_flat(auto[0], mode)
+        assert in_lds is None or td.in_lds == in_lds
+        _ends[name, mode] = td
+    return _ends[name, mode]
+
+
+def state_ids(name, mode):
+    """the id of every state of an `ends` (an automaton without ids: NO_ID under EARLIEST, the one empty set under RET)"""
+    auto, sets, _ = auto_of(name)
+    return tokens_ref.state_ids(auto, mode, sets)
+
+
+def reference(starts, ends, flags=0, mode=EARLIEST):
+    """the judge's answer for all 1 500 inputs of a pair, computed once and left unchanged; the marks of a `starts` and the
+    longest ends of an `ends` are shared by the pairs they are part of"""
+    key = (starts, ends, flags, mode)
+    if key not in _refs:
+        rows, lens = inputs_of(ends)
+        assert inputs_of(starts) is inputs_of(ends)
+        if starts not in _marks:
+            _marks[starts] = matches_ref.marks(auto_of(starts)[0], rows, lens)
+        if ends not in _longest:
+            _longest[ends] = matches_ref.longest_from(auto_of(ends)[0], rows, lens)
+        res = matches_ref.matches(None, None, rows, lens, flags, ids=state_ids(ends, mode), tables=(_marks[starts],) + _longest[ends])
+        for v in res.values():
+            v.setflags(write=False)
+        _refs[key] = res
+    return _refs[key]
+
+
+def judged(starts, ends, rows, lens, flags=0, mode=EARLIEST):
+    """the judge on other lines than the 1 500: (off, start, end, id)"""
+    r = matches_ref.matches(auto_of(starts)[0], auto_of(ends)[0], rows, lens, flags, ids=state_ids(ends, mode))
+    return r["off"], r["start"], r["end"], r["id"]
+
+
+def check(mt, want, what, m=None):
+    """a matches object against (off, start, end, id); the copies are pre-filled and two entries too long: nothing behind total
+    or behind m + 1 was written"""
+    w_off, w_start, w_end, w_id = want
+    m = len(w_off) - 1 if m is None else m
+    total = int(w_off[-1])
+    assert mt.count == m, (what, "m")
+    assert mt.total == total, (what, "total", mt.total, total)
+    assert mt.off_ptr != 0 and (mt.start_ptr != 0) == (total != 0) and (mt.end_ptr != 0) == (total != 0) and (mt.id_ptr != 0) == (total != 0), what
+    off, start, end, ids = mt.copy(extra=2, fill=FILL)
+    assert (off[m + 1:] == FILL).all() and (start[total:] == FILL).all() and (end[total:] == FILL).all() and (ids[total:] == FILL & 0xFFFFFFFF).all(), what
+    assert int(off[m]) == total, (what, "match_off[m] == total")
+    for nm, got, exp in (("match_off", off[:m + 1], w_off), ("start", start[:total], w_start), ("end", end[:total], w_end), ("id", ids[:total], w_id)):
+        bad = np.flatnonzero(got != exp)
+        assert len(bad) == 0, (what, nm, bad[:5], got[bad[:5]], exp[bad[:5]])
+    assert mt.ms() >= 0.0 and all(mt.pass_ms(k) >= 0.0 for k in range(4))
+    mt.free()
+
+
+NONE = (np.zeros(1, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint32))
+
+
+def run_device(hip, pd, td, data, off, flags=0, pick=None, trim_byte=-1, limit=None):
+    """matches_run_device over a text of exactly len(data) bytes; limit None: the text's length, given"""
+    import torch
+    d_data = device_u8(data) if len(data) else None
+    d_off = device_u64(off)
+    d_pick = device_u64(pick if len(pick) else np.zeros(1, np.uint64)) if pick is not None else None
+    mt = hip.HipMatches.run_device(pd, td, d_data.data_ptr() if d_data is not None else 0, d_off.data_ptr(), len(off) - 1,
+                                   d_pick=d_pick.data_ptr() if d_pick is not None else 0, m=len(pick) if pick is not None else 0,
+                                   trim_byte=trim_byte, flags=flags, limit=len(data) if limit is None else limit)
+    torch.cuda.synchronize()
+    mt._keep = (mt._keep, d_data, d_off, d_pick)
+    return mt
+
+
+def both_forms(hip, starts, ends, n, flags=0, mode=EARLIEST, host=True):
+    rows, lens = inputs_of(ends)
+    pd, td = starts_image(starts), ends_image(ends, mode)
+    data, off = lead_packed(rows[:n], lens[:n])
+    assert len(data) == int(off[n]) and int(off[0]) == LEAD
+    want = matches_ref.head(reference(starts, ends, flags, mode), n)
+    check(run_device(hip, pd, td, data, off, flags), want, (starts, ends, n, flags, "device"))
+    if host:
+        check(hip.HipMatches.run(pd, td, data, off, flags=flags), want, (starts, ends, n, flags, "host"))
+
+
+# ---- group 1: every input, the four combinations of the images' forms ------------------------------------------------------
+
+@pytest.mark.parametrize("starts", ["lds_full", "glob_first"])
+@pytest.mark.parametrize("ends", ["lds_full", "glob_first"])
+def test_every_input_both_forms_of_both_images(hip, starts, ends):
+    res = reference(starts, ends)
+    cnt = np.diff(res["off"].astype(np.int64))
+    print(starts, ends, "lines with a match, with two:", (cnt >= 1).mean(), (cnt >= 2).mean(), "matches over 16 bytes:",
+          ((res["end"] - res["start"]) > 16).mean())
+    assert (cnt >= 1).mean() >= 0.3 and (cnt == 0).mean() >= 0.1 and ((res["end"] - res["start"]) > 16).mean() >= 0.2
+    for n in SIZES:
+        both_forms(hip, starts, ends, n)
+
+
+# ---- group 2: any pair -----------------------------------------------------------------------------------------------------
+
+def stops_of(name, back):
+    """the state in which the walk of every line as a whole stopped (-1: DEAD), by span_ref"""
+    rows, lens = inputs_of(name)
+    return span_ref.accept_pos(auto_of(name)[0], rows, lens, back=back, detail=True)[2]
+
+
+@pytest.mark.parametrize("starts,ends", [("s200_dying", "dying1023"), ("dying1023", "s200_dying")])
+def test_pairs_with_holes_and_sinks(hip, starts, ends):
+    """both walks meet DEAD and absorbing end states: the marks are filled with zeros and with ones, a match ends at len"""
+    S, sinks = AUTOMATA[starts][0], AUTOMATA[starts][2]["sinks"]
+    stop = stops_of(starts, True)
+    print(starts, "backward: DEAD", (stop == -1).mean(), "sink", (stop >= S - sinks).mean())
+    assert (stop == -1).mean() >= 0.1 and (stop >= S - sinks).mean() >= 0.09      # (dying1023: 149 of the 1 500)
+    _, lens = inputs_of(ends)
+    res = reference(starts, ends)
+    off = res["off"].astype(np.int64)
+    cnt = np.diff(off)
+    line_of = np.repeat(np.arange(1500), cnt)
+    S2, sinks2 = AUTOMATA[ends][0], AUTOMATA[ends][2]["sinks"]
+    in_sink = res["state"] >= S2 - sinks2
+    print(ends, "forward: matches ending in a sink", in_sink.mean(), "lines with two matches", (cnt >= 2).mean())
+    assert in_sink.mean() >= 0.05 and (res["end"][in_sink] == lens[line_of[in_sink]].astype(np.uint64)).all()
+    assert (cnt >= 2).mean() >= 0.05 and (cnt == 0).mean() >= 0.05
+    for n in (257, 1500):
+        both_forms(hip, starts, ends, n)
+        both_forms(hip, starts, ends, n, DROP_EMPTY)        # no empty match here: the same answer
+    assert np.array_equal(reference(starts, ends, DROP_EMPTY)["off"], res["off"])
+
+
+def test_start_states_that_are_end_states(hip):
+    """`starts` with an accepting start state: M(len).  `ends` with one: empty matches and the end + 1 step, kept and dropped"""
+    _, lens = inputs_of("s15_start")
+    reference("s15_start", "s200_dying")
+    assert _marks["s15_start"][np.arange(1500), lens].all()             # every line has M(len)
+    for n in (257, 1500):
+        both_forms(hip, "s15_start", "s200_dying", n)
+    kept, dropped = reference("s200_dying", "s15_start"), reference("s200_dying", "s15_start", DROP_EMPTY)
+    empty = kept["end"] == kept["start"]
+    print("empty matches:", empty.mean(), "of", len(empty))
+    assert empty.sum() >= 200 and (~empty).sum() >= 200 and len(dropped["start"]) == int((~empty).sum())
+    for n in (257, 1500):
+        both_forms(hip, "s200_dying", "s15_start", n)
+        both_forms(hip, "s200_dying", "s15_start", n, DROP_EMPTY)
+    # ... and with every position marked, an empty match at every position where no word begins
+    kept = reference("kw_starts_everywhere", "kw_ends_empty")
+    assert ((kept["end"] == kept["start"]).sum() >= 1000)
+    both_forms(hip, "kw_starts_everywhere", "kw_ends_empty", 1500)
+    both_forms(hip, "kw_starts_everywhere", "kw_ends_empty", 1500, DROP_EMPTY)
+
+
+def test_absorbing_start_states(hip):
+    """a one-state accepting sink.  As `starts` nothing is looked up and every position is marked, the top word only up to len
+    (walk_mark's branch behind its loop); as `ends` the walk has sunk before its first byte: end = len from the start state"""
+    _, lens = inputs_of("sink_one")
+    reference("sink_one", "s200_dying")
+    M = _marks["sink_one"]
+    assert (M == (np.arange(M.shape[1])[None, :] <= lens[:, None])).all()
+    both = reference("sink_one", "sink_one")                 # (0, len), then the empty match at len
+    assert np.array_equal(np.diff(both["off"].astype(np.int64)), np.where(lens > 0, 2, 1))
+    off = both["off"].astype(np.int64)
+    assert (both["start"][off[:-1]] == 0).all() and np.array_equal(both["end"][off[:-1]], lens.astype(np.uint64))
+    assert (both["id"] == tokens_ref.NO_ID).all()
+    dropped = reference("sink_one", "sink_one", DROP_EMPTY)
+    assert np.array_equal(np.diff(dropped["off"].astype(np.int64)), (lens > 0).astype(np.int64))
+    sunk = reference("s200_dying", "sink_one")               # every match runs to the line's end
+    so = sunk["off"].astype(np.int64)
+    assert (np.diff(so) >= 1).mean() >= 0.5 and np.array_equal(sunk["end"], np.repeat(lens, np.diff(so)).astype(np.uint64))
+    for starts, ends in (("sink_one", "s200_dying"), ("s200_dying", "sink_one"), ("sink_one", "sink_one"), ("sink_one", "glob_first")):
+        for n in (257, 1500):
+            both_forms(hip, starts, ends, n)
+            both_forms(hip, starts, ends, n, DROP_EMPTY)
+
+
+# ---- group 3: many matches in one line, ids --------------------------------------------------------------------------------
+
+def test_many_matches_in_one_line_are_leftmost_longest(hip):
+    rows, lens = inputs_of("kw_ends")
+    res = reference("kw_starts", "kw_ends")
+    off = res["off"].astype(np.int64)
+    assert int(lens[8]) == 300 and off[9] - off[8] == 300               # 300 times d: 300 matches from one call
+    assert res["start"][off[8]:off[9]].tolist() == list(range(300)) and (res["id"][off[8]:off[9]] == WORDS.index(b"d")).all()
+    for i in (2, 4, 8, 100, 640, 1498):                                 # the judge against the brute force, and the ids against the words
+        line = bytes(rows[i, :lens[i]])
+        got = list(zip(res["start"][off[i]:off[i + 1]].tolist(), res["end"][off[i]:off[i + 1]].tolist()))
+        assert got == span_ref.leftmost_longest(WORDS, line)
+        assert [WORDS[int(k)] for k in res["id"][off[i]:off[i + 1]]] == [line[s:e] for s, e in got]
+    cnt = np.diff(off)
+    print("matches a line:", cnt.mean(), "most:", cnt.max(), "bytes a match:", lens.sum() / cnt.sum())
+    assert cnt.max() == 300 and (cnt >= 16).mean() >= 0.3
+    for n in SIZES:
+        both_forms(hip, "kw_starts", "kw_ends", n, host=n in (1, 257, 1500))
+
+
+def test_earliest_against_ret(hip):
+    """a union where one state carries two ids: EARLIEST gives the lower, RET the index of its set"""
+    e, r = reference("kw_starts", "kw_ends_two", 0, EARLIEST), reference("kw_starts", "kw_ends_two", 0, RET)
+    assert np.array_equal(e["start"], r["start"]) and np.array_equal(e["end"], r["end"])
+    is_ab = (e["end"] - e["start"] == 2) & (e["id"] == 3)
+    assert is_ab.sum() >= 1000 and (r["id"][is_ab] == len(WORDS) - 1).all() and set(e["id"].tolist()) == {3, 11, 12, 13, 14}
+    assert set(r["id"].tolist()) == set(range(len(WORDS)))
+    for mode in (EARLIEST, RET):
+        both_forms(hip, "kw_starts", "kw_ends_two", 1500, 0, mode)
+
+
+# ---- group 4: pick, trim, limit, edges -------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("starts,ends", [("s200_dying", "dying1023"), ("glob_first", "glob_first"), ("kw_starts", "kw_ends")])
+def test_pick(hip, starts, ends):
+    rows, lens = inputs_of(ends)
+    pd, td = starts_image(starts), ends_image(ends)
+    n = 700
+    data, off = lead_packed(rows[:n], lens[:n])
+    rng = np.random.RandomState(12)
+    pick = np.concatenate([rng.permutation(n)[:300], [7, 7, 7, 0, n - 1, n - 1, 8, 8], rng.randint(0, n, 100), np.arange(n)[::-1][:50]]).astype(np.uint64)
+    res = reference(starts, ends)
+    want = matches_ref.select(res, pick)
+    check(run_device(hip, pd, td, data, off, pick=pick), want, (starts, ends, "device"))
+    check(hip.HipMatches.run(pd, td, data, off, pick=pick), want, (starts, ends, "host"))
+    # an empty pick: a valid object, nothing launched that stores
+    check(run_device(hip, pd, td, data, off, pick=np.zeros(0, np.uint64)), NONE, (starts, ends, "m == 0 device"), m=0)
+    check(hip.HipMatches.run(pd, td, data, off, pick=np.zeros(0, np.uint64)), NONE, (starts, ends, "m == 0 host"), m=0)
+    # an index at or beyond n: no match on the device form, its neighbours right; EINVAL on the host form, before any launch
+    wild = pick.copy()
+    at = [0, 5, 255, 256, len(wild) - 1]
+    wild[at] = [n, n + 1, 2 ** 40, 0xFFFFFFFFFFFFFFFF, n]
+    check(run_device(hip, pd, td, data, off, pick=wild), matches_ref.select(res, wild, n), (starts, ends, "wild"))
+    with pytest.raises(OSError) as ei:
+        hip.HipMatches.run(pd, td, data, off, pick=wild)
+    assert ei.value.errno == errno.EINVAL
+    check(hip.HipMatches.run(pd, td, data, off, pick=pick), want, (starts, ends, "the next call answers"))
+
+
+@pytest.mark.parametrize("starts,ends", [("s200_dying", "dying1023"), ("glob_first", "lds_full")])
+def test_trim(hip, starts, ends):
+    rows, lens = inputs_of(ends)
+    pd, td = starts_image(starts), ends_image(ends)
+    n, trim = 600, 0x0A
+    rows = rows[:n].copy()
+    lens = lens[:n].copy()
+    idx = np.arange(n)
+    ends_in = (idx % 3 == 0) & (lens > 0)
+    rows[idx[ends_in], lens[ends_in] - 1] = trim                       # lines ending in the byte
+    other = ~ends_in & (lens > 0)
+    rows[idx[other], lens[other] - 1] = np.where(rows[idx[other], lens[other] - 1] == trim, 0x41, rows[idx[other], lens[other] - 1])
+    lens[10], lens[11] = 1, 0                                          # a line of that byte alone, the empty line
+    rows[10, 0] = trim
+    ends_in[10], ends_in[11] = True, False
+    shorter = lens - ends_in
+    assert ends_in.sum() > 100 and (lens == 0).sum() > 5 and (~ends_in & (lens > 0)).sum() > 100
+    data, off = lead_packed(rows, lens)
+    want = judged(starts, ends, rows, shorter)
+    check(run_device(hip, pd, td, data, off, trim_byte=trim), want, (starts, ends, "device"))
+    check(hip.HipMatches.run(pd, td, data, off, trim_byte=trim), want, (starts, ends, "host"))
+    check(run_device(hip, pd, td, data, off), judged(starts, ends, rows, lens), (starts, ends, "untrimmed"))   # the byte is walked like any other
+
+
+def test_limit_given_or_read_on_the_device(hip):
+    """limit = 0 is limit = off[n]; a limit inside the text clips the lines that cross it, and the bytes behind it -- which would
+    lengthen and move matches if they were read -- are not: the answer is the judge's on the clipped text"""
+    starts, ends = "s200_dying", "dying1023"
+    rows, lens = inputs_of(ends)
+    pd, td = starts_image(starts), ends_image(ends)
+    n = 257
+    data, off = lead_packed(rows[:n], lens[:n])
+    whole = matches_ref.head(reference(starts, ends), n)
+    check(run_device(hip, pd, td, data, off, limit=0), whole, "limit = 0")
+    cut = int(off[200]) + 7
+    clipped = np.clip(cut - off[:n].astype(np.int64), 0, lens[:n])
+    assert (clipped != lens[:n]).sum() > 10
+    want = judged(starts, ends, rows[:n], clipped)
+    at = int(whole[0][200])
+    assert int(want[0][-1]) < int(whole[0][-1]) and not np.array_equal(want[1][at:at + 3], whole[1][at:at + 3])
+    check(run_device(hip, pd, td, data, off, limit=cut), want, "limit inside")
+    # the keywords, cut inside a word: "abc" behind the limit is "ab" in front of it
+    lines = [b"xxabcab", b"abcabc", b"dd"]
+    r, l = span_ref.rows_of(lines)
+    data, off = lead_packed(r, l, 3)
+    kpd, ktd = starts_image("kw_starts"), ends_image("kw_ends")
+    cut = int(off[1]) + 5
+    want = judged("kw_starts", "kw_ends", r, np.array([7, 5, 0]))
+    assert list(zip(want[1].tolist(), want[2].tolist())) == [(2, 5), (5, 7), (0, 3), (3, 5)]
+    check(run_device(hip, kpd, ktd, data, off, limit=cut), want, "keywords, limit inside a word")
+
+
+@pytest.mark.parametrize("starts,ends", [("s15_start", "dying1023"), ("glob_first", "glob_first"), ("kw_starts", "kw_ends")])
+def test_edge_chunks_at_the_head_and_the_tail_of_the_text(hip, starts, ends):
+    """lines of 1 to 15 bytes at the head and at the very end of a text with leads 0 .. 3, the limit exactly the text's length:
+    the chunk that would end behind the limit is assembled from byte loads, in both walks"""
+    rows, _ = inputs_of(ends)
+    pd, td = starts_image(starts), ends_image(ends)
+    for lead in (0, 1, 2, 3):
+        for L in (1, 2, 7, 11, 15 - lead, 15):
+            lens = np.array([L, 20, 33, 16 - L, L], np.int64)
+            sub = rows[100:105]
+            data, off = lead_packed(sub, lens, lead)
+            want = judged(starts, ends, sub, lens)
+            check(run_device(hip, pd, td, data, off), want, (starts, ends, lead, L, "device"))
+            check(hip.HipMatches.run(pd, td, data, off), want, (starts, ends, lead, L, "host"))
+
+
+# ---- group 5: the text front -----------------------------------------------------------------------------------------------
+
+def text_lines(rng):
+    """400 lines of 0-60 bytes over abcdx and, every third, over xyzw: a third without any word; the last without a newline"""
+    out = []
+    for i in range(400):
+        alpha = b"abcdx" if i % 3 else b"xyzw"
+        out.append(bytes(rng.choice(list(alpha), rng.randint(0, 61)).astype(np.uint8)))
+    out[-1] = b"xxabcabd"
+    return out
+
+
+def test_text_matches_over_a_text_and_its_hits(hip):
+    pd, td = starts_image("kw_starts"), ends_image("kw_ends")
+    lines = text_lines(np.random.RandomState(18))
+    blob = b"".join(x + b"\n" for x in lines)[:-1]
+    text = hip.HipText(blob, 0x0A)
+    assert text.lines == len(lines)
+    rows, lens = span_ref.rows_of(lines)
+    res = matches_ref.matches(auto_of("kw_starts")[0], auto_of("kw_ends")[0], rows, lens, ids=state_ids("kw_ends", EARLIEST))
+    want = (res["off"], res["start"], res["end"], res["id"])
+    off_last = res["off"].astype(np.int64)
+    assert list(zip(res["start"][off_last[-2]:].tolist(), res["end"][off_last[-2]:].tolist())) == [(2, 5), (5, 7), (7, 8)]   # no delimiter at the text's end
+    off = np.zeros(len(lines) + 1, np.uint64)
+    off[1:] = np.cumsum([len(x) + 1 for x in lines])
+    off[-1] -= 1
+    check(td.text_matches(pd, text), want, "text")
+    # ... is the primitive over the text's own offsets with the delimiter trimmed
+    check(hip.HipMatches.run(pd, td, np.frombuffer(blob, np.uint8), off, trim_byte=0x0A), want, "primitive")
+    ld = hip.LinesDfa(span_ref.line_matcher_of(WORDS)[0], 0x0A)
+    kinds = {"plain": text.hits(ld), "no bytes": text.hits(ld, want_bytes=False), "inverted": text.hits(ld, invert=True)}
+    assert 100 < kinds["plain"].count < 300 and kinds["plain"].count + kinds["inverted"].count == len(lines)
+    for what, hits in kinds.items():
+        picks = hits.lines()
+        sel = matches_ref.select(res, picks)
+        check(td.text_matches(pd, text, hits), sel, what)
+        check(hip.HipMatches.run(pd, td, np.frombuffer(blob, np.uint8), off, pick=picks, trim_byte=0x0A), sel, (what, "the picks form"))
+        cnt = np.diff(sel[0].astype(np.int64))
+        assert (cnt == 0).all() if what == "inverted" else (cnt > 0).all()      # the pair belongs to the line matcher
+    mt = td.text_matches(pd, text, kinds["inverted"])                           # total == 0: nothing that stores, off is valid
+    assert mt.total == 0 and mt.start_ptr == 0 and mt.end_ptr == 0 and mt.id_ptr == 0 and mt.off_ptr != 0
+    check(mt, matches_ref.select(res, kinds["inverted"].lines()), "total == 0")
+    check(td.text_matches(pd, text, flags=DROP_EMPTY), want, "DROP_EMPTY on a text")
+
+
+def test_empty_text_and_no_hits(hip):
+    pd, td = starts_image("kw_starts"), ends_image("kw_ends")
+    text = hip.HipText(b"", 0x0A)
+    assert text.lines == 0
+    mt = td.text_matches(pd, text)
+    assert mt.start_ptr == 0 and mt.end_ptr == 0 and mt.id_ptr == 0 and mt.off_ptr != 0
+    check(mt, NONE, "empty text", m=0)
+    check(hip.HipMatches.run(pd, td, np.zeros(0, np.uint8), np.zeros(1, np.uint64)), NONE, "n == 0 host", m=0)
+    check(run_device(hip, pd, td, np.zeros(0, np.uint8), np.zeros(1, np.uint64)), NONE, "n == 0 device", m=0)
+    text = hip.HipText(b"xx\n\nabd\n", 0x0A)
+    hits = text.hits(hip.LinesDfa(span_ref.line_matcher_of([b"qqqq"])[0], 0x0A))
+    assert hits.count == 0
+    check(td.text_matches(pd, text, hits), NONE, "no hits", m=0)
+    # empty lines alone, with an `ends` that accepts the empty string: one empty match a line, none when they are dropped
+    epd, etd = starts_image("kw_starts_everywhere"), ends_image("kw_ends_empty")
+    text = hip.HipText(b"\n\n\n", 0x0A)
+    check(etd.text_matches(epd, text), (np.arange(4, dtype=np.uint64), np.zeros(3, np.uint64), np.zeros(3, np.uint64),
+                                        np.full(3, tokens_ref.NO_ID, np.uint32)), "empty lines")
+    check(etd.text_matches(epd, text, flags=DROP_EMPTY), (np.zeros(4, np.uint64),) + NONE[1:], "empty lines, dropped")
+
+
+# ---- group 6: refusals -----------------------------------------------------------------------------------------------------
+
+def test_refusals_with_a_device(hip):
+    """EINVAL, and the next call answers"""
+    from libfsm_amd import MatchBatch
+    starts, ends = "s200_dying", "dying1023"
+    rows, lens = inputs_of(ends)
+    pd, td = starts_image(starts), ends_image(ends)
+    lib = hip.load_library()
+    n = 64
+    data, off = lead_packed(rows[:n], lens[:n])
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    good = dict(base=ptr(data), off=ptr(off), n=n, trim_byte=-1)
+    bad_off = off.copy()
+    bad_off[10] = bad_off[11] + np.uint64(1)
+    P, T = C.c_void_p(pd.handle), C.c_void_p(td.handle)
+    for change in (dict(off=None), dict(base=None), dict(flags=2), dict(flags=0x80000000), dict(trim_byte=256), dict(trim_byte=-2), dict(off=ptr(bad_off))):
+        b = MatchBatch(**dict(good, **change))
+        C.set_errno(0)
+        assert lib.fsm_hip_matches_run(P, T, C.byref(b)) is None and C.get_errno() == errno.EINVAL, change
+    b = MatchBatch(**good)
+    for args in ((None, T, C.byref(b)), (P, None, C.byref(b)), (P, T, None)):
+        C.set_errno(0)
+        assert lib.fsm_hip_matches_run(*args) is None and C.get_errno() == errno.EINVAL
+    d_off = device_u64(off)
+    b = MatchBatch(base=None, off=d_off.data_ptr(), n=n, trim_byte=-1, limit=int(off[n]))    # nothing is launched
+    C.set_errno(0)
+    assert lib.fsm_hip_matches_run_device(P, T, C.byref(b), None) is None and C.get_errno() == errno.EINVAL
+    text = hip.HipText(b"ab\ncd\n", 0x0A)
+    for args in ((None, td.handle, text.handle, None, 0, None), (pd.handle, None, text.handle, None, 0, None), (pd.handle, td.handle, None, None, 0, None),
+                 (pd.handle, td.handle, text.handle, None, 2, None)):
+        C.set_errno(0)
+        assert lib.fsm_hip_text_matches(*args) is None and C.get_errno() == errno.EINVAL, args
+    check(hip.HipMatches.run(pd, td, data, off), matches_ref.head(reference(starts, ends), n), "the next call answers")
+
+
+# ---- group 7: the example --------------------------------------------------------------------------------------------------
+
+def test_example_prints_the_judges_matches(hip, tmp_path):
+    """examples/hipscan.c over three files (the last line without a newline) against the judge: LINE:START-END:ID per match"""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rng = np.random.RandomState(16)
+    files = []
+    for k in (60, 1, 90):
+        files.append([bytes(rng.choice(list(b"abcdxyzw" if i % 2 == 0 else b"xyzwba"), rng.randint(0, 25)).astype(np.uint8)) for i in range(k)])
+    files[2][-1] = b"xxabcabd"
+    tables = []
+    for nm, auto in (("lines", span_ref.line_matcher_of(WORDS)), ("starts", auto_of("kw_starts")[0]), ("ends", auto_of("kw_ends")[0]),
+                     ("ends_empty", auto_of("kw_ends_empty")[0]), ("starts_everywhere", auto_of("kw_starts_everywhere")[0])):
+        tables.append(str(tmp_path / (nm + ".fsmhip")))
+        auto[0].write_c(tables[-1])
+    names = []
+    for j, ls in enumerate(files):
+        data = b"".join(x + b"\n" for x in ls)
+        p = tmp_path / ("f%d.txt" % j)
+        p.write_bytes(data[:-1] if j == 2 else data)
+        names.append(str(p))
+    env = dict(os.environ, LD_LIBRARY_PATH="/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
+    exe = str(tmp_path / "hipscan")
+    subprocess.check_call(["gcc", "-std=c99", "-O2", "-Wall", "-I" + os.path.join(root, "include"), os.path.join(root, "examples", "hipscan.c"),
+                           "-o", exe, "-L" + os.path.join(root, "libfsm_amd"), "-lfsm_hip", "-Wl,-rpath," + os.path.join(root, "libfsm_amd")])
+
+    def run(*opts, tabs=tables[:3], fs=names):
+        r = subprocess.run([exe, *opts, *tabs, *fs], capture_output=True, env=env, timeout=120)
+        return r.returncode, r.stdout
+
+    def compose(starts="kw_starts", ends="kw_ends", flags=DROP_EMPTY, byte=False, number=False, name=False):
+        out, first = b"", 0
+        ids = state_ids(ends, EARLIEST)
+        for nm, ls in zip(names, files):
+            rows, lens = span_ref.rows_of(ls)
+            res = matches_ref.matches(auto_of(starts)[0], auto_of(ends)[0], rows, lens, flags, ids=ids)
+            off, at = res["off"].astype(np.int64), 0
+            for i, x in enumerate(ls):
+                for k in range(off[i], off[i + 1]):
+                    if span_ref.leftmost_longest(WORDS, x):         # a hit of the line matcher
+                        add = at if byte else 0
+                        idv = b"-" if int(res["id"][k]) == tokens_ref.NO_ID else b"%d" % int(res["id"][k])
+                        out += (nm.encode() + b":" if name else b"") + b"%d:%d-%d:" % ((i if number else first + i) + 1, int(res["start"][k]) + add,
+                                                                                       int(res["end"][k]) + add) + idv + b"\n"
+                at += len(x) + 1
+            first += len(ls)
+        return out
+
+    assert compose().count(b"\n") >= 100 and compose().endswith(b"151:2-5:1\n151:5-7:0\n151:7-8:3\n")
+    assert run() == (0, compose())
+    assert run("-b") == (0, compose(byte=True))
+    assert run("-n") == (0, compose(number=True))
+    assert run("-H", "-n", "-b") == (0, compose(byte=True, number=True, name=True))
+    assert run("-e") == (0, compose(flags=0))                  # no empty match with this pair: the same
+    tabs = [tables[0], tables[4], tables[3]]                   # every position a start, the empty string accepted: ids -
+    assert run("-e", tabs=tabs) == (0, compose("kw_starts_everywhere", "kw_ends_empty", 0))
+    assert run(tabs=tabs) == (0, compose("kw_starts_everywhere", "kw_ends_empty", DROP_EMPTY))
+    assert compose("kw_starts_everywhere", "kw_ends_empty", 0).count(b"\n") > 2 * compose("kw_starts_everywhere", "kw_ends_empty", DROP_EMPTY).count(b"\n")
+    quiet = tmp_path / "none.txt"
+    quiet.write_bytes(b"xyz\nwwww\n\n")
+    assert run(fs=[str(quiet)]) == (1, b"")                    # nothing matched: grep's 1
