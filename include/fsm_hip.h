@@ -1117,6 +1117,81 @@ double fsm_hip_matches_pass_ms(const struct fsm_hip_matches *mt, int pass);     
 void fsm_hip_matches_free(struct fsm_hip_matches *mt);
 
 /* ------------------------------------------------------------------ */
+/* replace: every match replaced by its rule's replacement, on the device */
+/* ------------------------------------------------------------------ */
+
+/* sed 's/pat/repl/g' for a union of rules, redaction, normalising: the matches are on the device and so is the text; the result
+ * is a fresh packed text there, without a host loop over bytes.
+ *   Input j is line pick[j] of a packed text: base, off, n, pick, m, trim_byte and limit exactly as in struct fsm_hip_match_batch.
+ *   raw is the line's byte count and len its trimmed length, so raw - len is 0 or 1.  Its matches are entries moff[j] .. moff[j + 1]
+ *   of a struct fsm_hip_matches, which must have been made from the same batch: m must equal fsm_hip_matches_count (EINVAL), the
+ *   rest is the caller's word.  The batch's flags are not read.
+ *   A replacement table holds nrepl byte strings, R[i] = bytes[roff[i] .. roff[i + 1]).
+ *   The output line is built from these pieces, in order:
+ *   - the bytes [0, start_0);
+ *   - then, for each match k in order, X_k followed by the bytes [end_k, start_{k+1}); the last match is followed by
+ *     [end_last, len);
+ *   - then the bytes [len, raw): the trimmed delimiter is copied, so replacing in every line of a text yields a text with the
+ *     same delimiters.  (The output therefore does not depend on trim_byte, and nothing reads it.)
+ *   X_k:
+ *   - default table: X_k = R[id_k] if id_k < nrepl; otherwise the match's own bytes -- a rule without a replacement,
+ *     FSM_HIP_NO_ID and FSM_HIP_NO_MATCH: the text stays.
+ *   - an empty match (end == start, present when the matches were made without FSM_HIP_MATCHES_DROP_EMPTY) inserts R[id], as
+ *     sed does.
+ *   - a table made with FSM_HIP_REPL_MASK: X_k has the match's length and its byte t is R[id][t mod |R[id]|]; if |R[id]| == 0 or
+ *     id >= nrepl the match stays.  Lengths never change under this flag: the redaction case.
+ *   The result is again a packed text, out_off[m + 1] with out_off[0] = 0 plus bytes[out_off[m]], so it can be fed to any device
+ *   front of the library.
+ * A pick[j] >= n (device form) gives an empty output line and nothing is read.  No byte outside [base, base + limit) is read and
+ * no store leaves the object's arrays, whatever the offsets or the match arrays hold: line extents are clamped to the limit by
+ * the helper the matches' passes use, so lengths agree; a match is taken inside its line and behind its predecessor.  Wrong
+ * arrays may give wrong bytes, never a wild access.
+ * Passes: the lengths (per input its output length, per match its place in the output line, per block of
+ * fsm_hip_replaced_block_lines() inputs the block's bytes), a scan of the BLOCK sums by one workgroup -- m / block_lines records,
+ * not m --, ONE wait for the total, the allocation, the offsets (the block's own scan redone; an index per block of
+ * fsm_hip_replaced_block_bytes() output bytes, sized by the total, which is why this pass follows the wait), the write pass: a lane
+ * owns 16 output bytes and finds their line and their match by two searches.  The offsets and the write pass are in flight at
+ * return.  The table's bytes and offsets are read from LDS when nrepl <= fsm_hip_repl_lds_rules() and its bytes <=
+ * fsm_hip_repl_lds_bytes() (fsm_hip_repl_in_lds), from device memory otherwise.
+ * fsm_hip_repl_create takes host pointers and leaves the table on the current device, reusable across calls; nrepl == 0 is valid
+ * and gives the identity.  fsm_hip_matches_replace takes host pointers, stages them and waits; decreasing offsets and a
+ * pick[j] >= n are EINVAL before any launch; `limit` is ignored.  fsm_hip_matches_replace_device takes device pointers and
+ * hip_stream; limit == 0 costs a second, short wait in which off[n] is read, as for the matches.  fsm_hip_text_replace covers
+ * every line of a text object or (hits != NULL) the lines of its hits, as fsm_hip_text_matches, whose result for the same text
+ * and hits it takes.  The work is enqueued behind the matches' last event, and behind the text's or the hits' for the text form.
+ * The replaced object must be freed before the matches, the table and the text.  It owns, on the device: off[m + 1] and the
+ * bytes (NULL when there are none).  m == 0 or zero output bytes gives a valid object and launches nothing that stores into bytes.
+ * _copy copies out whichever of off / bytes are not NULL and waits; _ms: the four passes by HIP events; _pass_ms: one of them.
+ * NULL + errno: ENODEV (checked first: there is no CPU path), EINVAL (an argument NULL, roff NULL with nrepl > 0, roff that
+ * decreases, bytes NULL with bytes to copy, an unknown flag bit, m that is not the matches', objects on different devices; host
+ * form: offsets that decrease, a pick[j] >= n), ENOMEM. */
+#define FSM_HIP_REPL_MASK 1u
+struct fsm_hip_repl;       /* a replacement table resident on the current device, reusable across calls */
+struct fsm_hip_repl *fsm_hip_repl_create(const void *bytes, const uint64_t *roff, size_t nrepl, unsigned flags);
+void fsm_hip_repl_free(struct fsm_hip_repl *rp);
+int fsm_hip_repl_in_lds(const struct fsm_hip_repl *rp);            /* 1: the write pass reads the table from LDS */
+size_t fsm_hip_repl_lds_bytes(void);
+size_t fsm_hip_repl_lds_rules(void);
+
+struct fsm_hip_replaced;
+struct fsm_hip_replaced *fsm_hip_matches_replace(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *batch,
+	const struct fsm_hip_repl *rp);
+struct fsm_hip_replaced *fsm_hip_matches_replace_device(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *d_batch,
+	const struct fsm_hip_repl *rp, void *hip_stream);
+struct fsm_hip_replaced *fsm_hip_text_replace(const struct fsm_hip_matches *mt, const struct fsm_hip_text *t,
+	const struct fsm_hip_text_hits *hits, const struct fsm_hip_repl *rp, void *hip_stream);
+size_t fsm_hip_replaced_count(const struct fsm_hip_replaced *r);               /* m */
+uint64_t fsm_hip_replaced_nbytes(const struct fsm_hip_replaced *r);            /* out_off[m] */
+const uint64_t *fsm_hip_replaced_off_device(const struct fsm_hip_replaced *r); /* m + 1, always there */
+const unsigned char *fsm_hip_replaced_bytes_device(const struct fsm_hip_replaced *r); /* NULL when nbytes == 0 */
+int fsm_hip_replaced_copy(const struct fsm_hip_replaced *r, uint64_t *off, void *bytes);
+double fsm_hip_replaced_ms(const struct fsm_hip_replaced *r);
+double fsm_hip_replaced_pass_ms(const struct fsm_hip_replaced *r, int pass);   /* 0: lengths, 1: scan of the block sums, 2: offsets, 3: write */
+size_t fsm_hip_replaced_block_lines(void);     /* inputs of a block of the lengths and the offsets pass */
+size_t fsm_hip_replaced_block_bytes(void);     /* output bytes of a block of the write pass */
+void fsm_hip_replaced_free(struct fsm_hip_replaced *r);
+
+/* ------------------------------------------------------------------ */
 /* synthetic input generator (benchmarks and parity tests)            */
 /* ------------------------------------------------------------------ */
 

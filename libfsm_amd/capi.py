@@ -41,6 +41,7 @@ NO_POS = 0xFFFFFFFFFFFFFFFF
 POS_BACKWARD = 1
 TOKENS_NO_BACKTRACK, TOKENS_SKIP_BAD = 1, 2
 MATCHES_DROP_EMPTY = 1
+REPL_MASK = 1
 IDS_EARLIEST, IDS_RET, IDS_ERROR = 1, 2, 3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -233,6 +234,20 @@ PROTOTYPES = {"fsm_hip_" + name: (restype, args) for restype, names, *args in (
     (I, "matches_copy", P, P, P, P, P),
     (D, "matches_ms", P),
     (D, "matches_pass_ms", P, I),
+    # replace
+    (P, "repl_create", P, P, S, U),
+    (None, "repl_free replaced_free", P),
+    (I, "repl_in_lds", P),
+    (S, "repl_lds_bytes repl_lds_rules replaced_block_lines replaced_block_bytes"),
+    (P, "matches_replace", P, P, P),
+    (P, "matches_replace_device", P, P, P, P),
+    (P, "text_replace", P, P, P, P, P),
+    (S, "replaced_count", P),
+    (U64, "replaced_nbytes", P),
+    (P, "replaced_off_device replaced_bytes_device", P),
+    (I, "replaced_copy", P, P, P),
+    (D, "replaced_ms", P),
+    (D, "replaced_pass_ms", P, I),
     # input generators: (out, stride, n, first_index, seed, {bytes, count}..., every[, stream])
     (I, "gen_inputs_device", P, S, S, U64, U64, P, U, P, U, U, P),
     (None, "gen_inputs_host", P, S, S, U64, U64, P, U, P, U, U),
@@ -1780,9 +1795,139 @@ class HipMatches:
         _call("fsm_hip_matches_copy", self._h, _ptr(off), _ptr(start), _ptr(end), _ptr(ids))
         return off, start, end, ids
 
+    def replace(self, repl: "HipRepl", base: np.ndarray, off: np.ndarray, pick=None, trim_byte: int = -1) -> "HipReplaced":
+        """fsm_hip_matches_replace on host arrays: the batch these matches were made from"""
+        base = np.ascontiguousarray(base, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        pick = None if pick is None else np.ascontiguousarray(pick, np.uint64)
+        n = len(off) - 1
+        m = n if pick is None else len(pick)
+        if pick is not None and m == 0:
+            pick = np.zeros(1, np.uint64)   # an empty pick is still a pick: a non-NULL address
+        b = MatchBatch(_ptr0(base), _ptr(off), n, _ptr(pick), m, trim_byte, 0, 0)
+        return HipReplaced(_call("fsm_hip_matches_replace", self._h, C.byref(b), repl.handle), (self, repl))
+
+    def replace_device(self, repl: "HipRepl", d_base: int, d_off: int, n: int, d_pick: int = 0, m: int = 0, trim_byte: int = -1, limit: int = 0,
+                       stream: int = 0) -> "HipReplaced":
+        """fsm_hip_matches_replace_device: device addresses; the offsets and the write pass are in flight on `stream` at return"""
+        b = MatchBatch(d_base or None, d_off or None, n, d_pick or None, m, trim_byte, 0, limit)
+        return HipReplaced(_call("fsm_hip_matches_replace_device", self._h, C.byref(b), repl.handle, stream or None), (self, repl))
+
+    def text_replace(self, repl: "HipRepl", text: "HipText", hits: Optional["HipHits"] = None, stream: int = 0) -> "HipReplaced":
+        """fsm_hip_text_replace: these matches are fsm_hip_text_matches' of the same text and hits"""
+        return HipReplaced(_call("fsm_hip_text_replace", self._h, text.handle, hits.handle if hits is not None else None, repl.handle,
+                                 stream or None), (self, repl, text, hits))
+
     def ms(self) -> float:
         return float(self._lib.fsm_hip_matches_ms(self._h))
 
     def pass_ms(self, which: int) -> float:
         """0: the marks, 1: the count pass, 2: the scan, 3: the emit pass"""
         return float(self._lib.fsm_hip_matches_pass_ms(self._h, which))
+
+
+# ---- replace: every match replaced by its rule's replacement, a fresh packed text (include/fsm_hip.h, "replace") ----
+
+class HipRepl:
+    """struct fsm_hip_repl *: a replacement table on the current device, R[i] = table[i]; flags: REPL_MASK"""
+
+    def __init__(self, table: Sequence[bytes], flags: int = 0):
+        self._lib = load_library()
+        table = [bytes(r) for r in table]
+        data = np.frombuffer(b"".join(table), np.uint8)
+        roff = np.zeros(len(table) + 1, np.uint64)
+        if table:
+            roff[1:] = np.cumsum([len(r) for r in table])
+        self._h = _call("fsm_hip_repl_create", _ptr0(data), _ptr(roff) if table else None, len(table), flags)
+        self.nrepl, self.flags = len(table), flags
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def in_lds(self) -> bool:
+        return bool(self._lib.fsm_hip_repl_in_lds(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.fsm_hip_repl_free(self._h)
+            self._h = None
+
+    free = close
+    __del__ = close
+
+
+class HipReplaced:
+    """struct fsm_hip_replaced *: out_off[m + 1] and the bytes on the device.  Keeps its matches and its table (and its text and
+    hits) alive: the replaced object must be freed first."""
+
+    def __init__(self, handle, keep=()):
+        self._lib = load_library()
+        self._h, self._keep = handle, keep
+
+    def free(self):
+        if getattr(self, "_h", None):
+            self._lib.fsm_hip_replaced_free(self._h)
+            self._h = None
+            self._keep = None
+
+    close = free
+    __del__ = free
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def count(self) -> int:
+        return int(self._lib.fsm_hip_replaced_count(self._h))
+
+    @property
+    def nbytes(self) -> int:
+        return int(self._lib.fsm_hip_replaced_nbytes(self._h))
+
+    @property
+    def off_ptr(self) -> int:
+        return int(self._lib.fsm_hip_replaced_off_device(self._h) or 0)
+
+    @property
+    def bytes_ptr(self) -> int:
+        return int(self._lib.fsm_hip_replaced_bytes_device(self._h) or 0)
+
+    def copy(self, extra: int = 0, fill: int = 0):
+        """-> (off u64 [m + 1], bytes u8 [nbytes]); extra: that many more entries in each array, pre-filled with `fill` and left
+        alone by the library"""
+        off, data = np.full(self.count + 1 + extra, fill, np.uint64), np.full(self.nbytes + extra, fill & 0xFF, np.uint8)
+        _call("fsm_hip_replaced_copy", self._h, _ptr(off), _ptr(data))
+        return off, data
+
+    def off(self) -> np.ndarray:
+        return self.copy()[0]
+
+    def bytes(self) -> bytes:
+        return self.copy()[1].tobytes()
+
+    @property
+    def ms(self) -> float:
+        return float(self._lib.fsm_hip_replaced_ms(self._h))
+
+    def pass_ms(self, which: int) -> float:
+        """0: the lengths, 1: the scan of the block sums, 2: the offsets, 3: the write pass"""
+        return float(self._lib.fsm_hip_replaced_pass_ms(self._h, which))
+
+
+def replaced_block_lines() -> int:
+    return int(load_library().fsm_hip_replaced_block_lines())
+
+
+def replaced_block_bytes() -> int:
+    return int(load_library().fsm_hip_replaced_block_bytes())
+
+
+def repl_lds_bytes() -> int:
+    return int(load_library().fsm_hip_repl_lds_bytes())
+
+
+def repl_lds_rules() -> int:
+    return int(load_library().fsm_hip_repl_lds_rules())

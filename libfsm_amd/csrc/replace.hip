@@ -1,0 +1,339 @@
+/*
+ * replace.hip -- replace every match by a per-rule replacement: the splice of a text and a table into a fresh packed text, on
+ * the device.  include/fsm_hip.h, section "replace", is the definition; replace_seg.h holds the arithmetic of one line, shared
+ * with tests/c/test_replace_seg.cpp.
+ *
+ * The matches (start, end, id per match, match_off per input) are on the device already, and so is the text.  Four passes, of
+ * which the second is text.hip's (its sum_scan):
+ *     repl_lengths  one lane per input walks its matches: mpos[k], xlen[k] (replace_seg.h) per match, the output length per
+ *                   input, the sum of a block of REPL_LINES inputs per workgroup
+ *     (scan)        the exclusive scan of the BLOCK sums by one workgroup; the total for the host
+ *     repl_offsets  out_off[j] = the block's base + the block's own exclusive scan, redone (a wave scan and an LDS exchange);
+ *                   first[g] = the input whose output covers byte g * REPL_BLOCK.  Only an input with output covers anything, so
+ *                   runs of empty output lines leave no entry and need none
+ *     repl_write    partitions the OUTPUT: a workgroup owns blocks of REPL_BLOCK bytes, a lane 16-byte chunks.  The chunk's
+ *                   first byte p belongs to the LAST input j with out_off[j] <= p -- empty output lines share their offset with
+ *                   their successor and are stepped over by the search itself -- found between first[g] and first[g + 1];
+ *                   inside the line, to the last match with mpos <= p - out_off[j].  A chunk that lies in one copied stretch
+ *                   of one line is one 16-byte load of any alignment; every other chunk is assembled stretch by stretch -- a
+ *                   16-byte window per stretch, placed so that the stretch's bytes fall where they belong, and masked -- with
+ *                   a new lookup whenever a stretch, a replacement or a line ends.
+ * No line belongs to a lane in the write pass: a line of 64 MiB is 4 096 blocks like any other 64 MiB.  In the lengths pass a lane
+ * walks ITS line's matches alone, so a line of many matches holds its wavefront for that long.
+ * Every global access names its address space (no FLAT instruction), every index read from an array is clamped to the array it
+ * is used on, every text byte lies below the clipped line's end and with it below the limit (marks_clip, as in match.hip), every
+ * store is below the counted sizes: arrays that changed between the passes give wrong bytes, not an overrun.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cerrno>
+#include <cstdint>
+
+#include "../../include/fsm_hip.h"
+#include "hip_host.h"
+#include "match_marks.h"
+#include "replace.h"
+#include "replace_seg.h"
+
+using namespace fsmhip;
+
+namespace {
+
+constexpr uint32_t REPL_WAVES = REPL_THREADS / 64u;
+
+typedef uint32_t u32x4r __attribute__((ext_vector_type(4)));
+typedef u32x4r __attribute__((aligned(1))) u32x4r_any;
+typedef const u32x4r_any __attribute__((address_space(1))) *g_chunkp;
+typedef const u32x4r __attribute__((address_space(1))) *g_chunk16p;
+typedef u32x4r __attribute__((address_space(1))) *g_chunkw;
+typedef const uint8_t __attribute__((address_space(1))) *g_u8p;
+typedef const uint32_t __attribute__((address_space(1))) *g_u32p;
+typedef const uint64_t __attribute__((address_space(1))) *g_u64p;
+typedef uint64_t __attribute__((address_space(1))) *g_u64w;
+typedef const uint8_t __attribute__((address_space(3))) *l_u8p;
+typedef const uint32_t __attribute__((address_space(3))) *l_u32p;
+typedef const u32x4r_any __attribute__((address_space(3))) *l_chunkp;
+
+__device__ __forceinline__ uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+
+/* the n lowest bytes of a word, n in 0 .. 8 */
+__device__ __forceinline__ uint64_t low_bytes(uint32_t n) { return n >= 8u ? ~(uint64_t)0 : ((uint64_t)1 << (8u * n)) - 1u; }
+
+/* byte k (0 .. 15) of the sixteen bytes (x0, x1) */
+__device__ __forceinline__ void put_byte(uint64_t *x0, uint64_t *x1, uint32_t k, uint32_t b)
+{
+	const uint64_t bits = (uint64_t)b << ((k & 7u) * 8u);
+	*x0 |= k < 8u ? bits : 0u;
+	*x1 |= k < 8u ? 0u : bits;
+}
+
+/* the matches of input j: [k0, k0 + nm) of the match arrays, whatever match_off holds */
+__device__ __forceinline__ void matches_of(g_u64p moff, uint64_t j, uint64_t nmatch, uint64_t *k0, uint64_t *nm)
+{
+	const uint64_t a = min64(moff[j], nmatch), b = min64(moff[j + 1u], nmatch);
+	*k0 = a;
+	*nm = b > a ? b - a : 0u;
+}
+
+/* the line of input j: its first byte from base and its bytes, clipped to the limit; a pick beyond the lines: nothing */
+__device__ __forceinline__ void line_of(const ReplRun &a, uint64_t j, uint64_t *beg, uint64_t *raw)
+{
+	uint64_t i = j;
+	if (a.pick != nullptr) i = ((g_u64p)(uintptr_t)a.pick)[j];
+	*beg = 0;
+	*raw = 0;
+	if (i < a.n) marks_clip(((g_u64p)(uintptr_t)a.off)[i], ((g_u64p)(uintptr_t)a.off)[i + 1u], a.limit, beg, raw);
+}
+
+/* pass 1: workgroup b takes inputs [b * REPL_LINES, (b + 1) * REPL_LINES), one per lane.  out_off[j] = the output length of input
+ * j (the offsets pass turns it into the offset), sums[b] = the block's bytes; mpos and xlen of every match. */
+__global__ void __launch_bounds__(REPL_THREADS)
+repl_lengths(const ReplRun a)
+{
+	__shared__ uint64_t wtot[REPL_WAVES];
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	const uint64_t j = (uint64_t)blockIdx.x * REPL_LINES + threadIdx.x;
+	const bool mask = (a.flags & FSM_HIP_REPL_MASK) != 0u;
+	const g_u64p start = (g_u64p)(uintptr_t)a.start, end = (g_u64p)(uintptr_t)a.end, roff = (g_u64p)(uintptr_t)a.roff;
+	const g_u32p id = (g_u32p)(uintptr_t)a.id;
+	const g_u64w mpos = (g_u64w)(uintptr_t)a.mpos, xlen = (g_u64w)(uintptr_t)a.xlen;
+	uint64_t outlen = 0;
+	if (j < a.m) {
+		uint64_t beg, raw, k0, nm;
+		line_of(a, j, &beg, &raw);
+		matches_of((g_u64p)(uintptr_t)a.moff, j, a.nmatch, &k0, &nm);
+		uint64_t delta = 0, floor = 0;               /* (delta wraps where a line shrinks; outlen does not: repl_clamp_match) */
+		for (uint64_t k = k0; k < k0 + nm; k++) {
+			uint64_t st = start[k], en = end[k];
+			repl_clamp_match(floor, raw, &st, &en);
+			const uint64_t i = id[k], mlen = en - st;
+			uint64_t rlen = 0;
+			if (i < a.nrepl) {
+				const uint64_t r0 = roff[i], r1 = roff[i + 1u];
+				rlen = r1 > r0 ? r1 - r0 : 0u;
+			}
+			const uint64_t xl = repl_xlen(mlen, repl_uses_table(i, a.nrepl, rlen, mask), rlen, mask);
+			mpos[k] = st + delta;
+			xlen[k] = xl;
+			delta += xl - mlen;
+			floor = en;
+		}
+		outlen = raw + delta;
+		((g_u64w)(uintptr_t)a.out_off)[j] = outlen;
+	}
+	uint64_t s = outlen;
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+	if (lane == 0) wtot[wave] = s;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		uint64_t all = 0;
+#pragma unroll
+		for (uint32_t w = 0; w < REPL_WAVES; w++) all += wtot[w];
+		((g_u64w)(uintptr_t)a.sums)[blockIdx.x] = all;
+	}
+}
+
+/* pass 3: out_off[j] = sums[b] (scanned: the bytes of the blocks before b) + the lengths of the block's inputs before j.
+ * first[g] = j for every block boundary g * REPL_BLOCK inside j's output: inputs with output tile the output, so exactly one of
+ * them covers a boundary below the total, and an input without output covers none. */
+__global__ void __launch_bounds__(REPL_THREADS)
+repl_offsets(const ReplRun a)
+{
+	__shared__ uint64_t wtot[REPL_WAVES];
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	const uint64_t j = (uint64_t)blockIdx.x * REPL_LINES + threadIdx.x;
+	const g_u64w oo = (g_u64w)(uintptr_t)a.out_off, fi = (g_u64w)(uintptr_t)a.first;
+	const bool valid = j < a.m;
+	const uint64_t len = valid ? oo[j] : 0u;
+	uint64_t x = len;                                /* inclusive over the wave */
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const uint64_t y = __shfl_up(x, d, 64);
+		if (lane >= (uint32_t)d) x += y;
+	}
+	if (lane == 63u) wtot[wave] = x;
+	__syncthreads();
+	uint64_t p = ((g_u64p)(uintptr_t)a.sums)[blockIdx.x] + (x - len);
+#pragma unroll
+	for (uint32_t w = 0; w < REPL_WAVES; w++) p += w < wave ? wtot[w] : 0u;
+	if (valid) {
+		oo[j] = p;
+		if (a.first != nullptr)
+			for (uint64_t g = (p + REPL_BLOCK - 1u) / REPL_BLOCK; g < a.ngb && g * REPL_BLOCK < p + len; g++) fi[g] = j;
+	}
+	if (blockIdx.x == 0 && threadIdx.x == 0) {
+		oo[a.m] = a.total;
+		if (a.first != nullptr) fi[a.ngb] = a.m;      /* the search's upper end in the last block */
+	}
+}
+
+/* an input as the write pass sees it */
+struct ReplLine {
+	uint64_t o0, o1;         /* its output range */
+	uint64_t beg, raw;       /* its bytes in the text */
+	uint64_t k0, nm;         /* its matches */
+};
+
+__device__ __forceinline__ void open_line(const ReplRun &a, uint64_t j, ReplLine *L)
+{
+	const g_u64p oo = (g_u64p)(uintptr_t)a.out_off;
+	L->o0 = oo[j];
+	L->o1 = oo[j + 1u];
+	line_of(a, j, &L->beg, &L->raw);
+	matches_of((g_u64p)(uintptr_t)a.moff, j, a.nmatch, &L->k0, &L->nm);
+}
+
+/* the last j in [lo, hi] with out_off[j] <= p (lo, when there is none) */
+__device__ __forceinline__ uint64_t line_at(g_u64p oo, uint64_t lo, uint64_t hi, uint64_t p)
+{
+	while (lo < hi) {
+		const uint64_t mid = lo + (hi - lo + 1u) / 2u;
+		if (oo[mid] <= p) lo = mid; else hi = mid - 1u;
+	}
+	return lo;
+}
+
+/* pass 4.  IN_LDS: the table's bytes and its offsets (as u32) are copied to LDS first: the dynamic region, its base 16-byte
+ * aligned, no static LDS in front of it. */
+template <bool IN_LDS>
+__global__ void __launch_bounds__(REPL_THREADS)
+repl_write(const ReplRun a)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char repl_smem[];
+	const uint32_t roff_at = ((uint32_t)a.rbytes + 15u) & ~15u;
+	if (IN_LDS) {
+		__attribute__((address_space(3))) u32x4r *dst = (__attribute__((address_space(3))) u32x4r *)repl_smem;
+		for (uint32_t c = threadIdx.x; c < roff_at / 16u; c += REPL_THREADS) dst[c] = ((g_chunk16p)(uintptr_t)a.rbytes_p)[c];
+		__attribute__((address_space(3))) uint32_t *ro = (__attribute__((address_space(3))) uint32_t *)(repl_smem + roff_at);
+		for (uint32_t e = threadIdx.x; e <= (uint32_t)a.nrepl; e += REPL_THREADS)
+			ro[e] = (uint32_t)min64(((g_u64p)(uintptr_t)a.roff)[e], a.rbytes);
+		__syncthreads();
+	}
+	const l_u8p tab_lds = (l_u8p)(__attribute__((address_space(3))) unsigned char *)repl_smem;
+	const l_u32p roff_lds = (l_u32p)(__attribute__((address_space(3))) unsigned char *)(repl_smem + roff_at);
+	const g_u8p tab_glb = (g_u8p)(uintptr_t)a.rbytes_p;
+	const g_u64p roff_glb = (g_u64p)(uintptr_t)a.roff;
+	const g_u64p oo = (g_u64p)(uintptr_t)a.out_off, fi = (g_u64p)(uintptr_t)a.first;
+	const g_u64p mpos = (g_u64p)(uintptr_t)a.mpos, xlen = (g_u64p)(uintptr_t)a.xlen;
+	const g_u64p start = (g_u64p)(uintptr_t)a.start, end = (g_u64p)(uintptr_t)a.end;
+	const g_u32p id = (g_u32p)(uintptr_t)a.id;
+	const uint64_t tx = (uint64_t)(uintptr_t)a.base, ox = (uint64_t)(uintptr_t)a.out;
+	const uint64_t m = a.m, total = a.total, limit = a.limit;
+	const bool mask = (a.flags & FSM_HIP_REPL_MASK) != 0u;
+
+	auto source = [&](const ReplLine &L, uint64_t p) {
+		const uint64_t outlen = L.o1 > L.o0 ? L.o1 - L.o0 : 0u;
+		if (IN_LDS)
+			return repl_at(mpos + L.k0, xlen + L.k0, start + L.k0, end + L.k0, id + L.k0, L.nm, roff_lds, a.nrepl, a.rbytes, mask, p - L.o0,
+			               outlen, L.raw);
+		return repl_at(mpos + L.k0, xlen + L.k0, start + L.k0, end + L.k0, id + L.k0, L.nm, roff_glb, a.nrepl, a.rbytes, mask, p - L.o0, outlen,
+		               L.raw);
+	};
+
+	uint64_t g = (uint64_t)blockIdx.x * a.per;
+	const uint64_t gend = g + a.per < a.ngb ? g + a.per : a.ngb;
+	for (; g < gend; g++) {
+		uint64_t j = min64(fi[g], m - 1u);
+		const uint64_t hi = min64(fi[g + 1u], m - 1u);
+#pragma unroll 1
+		for (uint32_t u = 0; u < REPL_TILES; u++) {
+			const uint64_t p = g * REPL_BLOCK + (uint64_t)u * REPL_TILE + 16u * threadIdx.x;
+			if (p >= total) break;
+			j = line_at(oo, j, hi, p);                   /* the tiles of a lane ascend, so j only grows */
+			ReplLine L;
+			open_line(a, j, &L);
+			ReplAt s = source(L, p);
+			u32x4r v;
+			if (s.from == REPL_FROM_TEXT && s.run >= 16u && L.beg + s.at + 16u <= limit) {
+				v = *(g_chunkp)(tx + L.beg + s.at);      /* the whole chunk in one copied stretch of one line: any alignment */
+			} else {
+				uint64_t w0 = 0, w1 = 0, jj = j;
+				uint32_t t = 0;
+#pragma unroll 1
+				while (t < 16u && p + t < total) {
+					const uint64_t pos = p + t;
+					if (s.run == 0u) {                   /* a stretch, a replacement or the line ended: look again */
+						if (pos >= L.o1 && jj < hi) {    /* the next line WITH output: the search steps over the empty ones */
+							jj = line_at(oo, jj + 1u, hi, pos);
+							open_line(a, jj, &L);
+						}
+						s = source(L, pos);
+					}
+					const uint32_t cnt = s.run < 16u - t ? (uint32_t)s.run : 16u - t;   /* this stretch's bytes in the chunk: 1 .. 16 */
+					/* a window of 16 bytes whose byte t is the source byte at s.at: one load where the window lies inside the
+					 * readable bytes (of the text: outside the line, inside the limit), byte loads at the two edges */
+					uint64_t x0 = 0, x1 = 0;
+					if (s.from == REPL_FROM_TEXT) {
+						const uint64_t src = L.beg + s.at;
+						if (src >= t && src - t + 16u <= limit) {
+							const u32x4r y = *(g_chunkp)(tx + src - t);
+							x0 = y.x | (uint64_t)y.y << 32;
+							x1 = y.z | (uint64_t)y.w << 32;
+						} else {
+							for (uint32_t k = 0; k < cnt; k++)
+								if (src + k < limit) put_byte(&x0, &x1, t + k, ((g_u8p)tx)[src + k]);
+						}
+					} else if (s.from == REPL_FROM_TABLE) {
+						if (s.at >= t && s.at - t + 16u <= roff_at) {    /* (both copies of the table are whole sixteens) */
+							const u32x4r y = IN_LDS ? *(l_chunkp)(tab_lds + (s.at - t)) : *(g_chunkp)((uint64_t)(uintptr_t)a.rbytes_p + (s.at - t));
+							x0 = y.x | (uint64_t)y.y << 32;
+							x1 = y.z | (uint64_t)y.w << 32;
+						} else {
+							for (uint32_t k = 0; k < cnt; k++)
+								if (s.at + k < a.rbytes) put_byte(&x0, &x1, t + k, IN_LDS ? (uint32_t)tab_lds[s.at + k] : (uint32_t)tab_glb[s.at + k]);
+						}
+					}
+					const uint32_t e = t + cnt;
+					w0 |= x0 & low_bytes(e < 8u ? e : 8u) & ~low_bytes(t < 8u ? t : 8u);
+					w1 |= x1 & low_bytes(e > 8u ? e - 8u : 0u) & ~low_bytes(t > 8u ? t - 8u : 0u);
+					t = e;
+					s.at += cnt;
+					s.run -= cnt;
+				}
+				v = u32x4r{(uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32)};
+			}
+			*(g_chunkw)(ox + p) = v;                     /* the buffer is whole blocks: the last chunk is stored whole */
+		}
+	}
+}
+
+}   // namespace
+
+namespace fsmhip {
+
+int repl_launch_lengths(const ReplRun &r, hipStream_t s)
+{
+	if (r.m == 0) return 0;
+	if (!repl_grid_fits(r.m)) { errno = ENOMEM; return -1; }
+	const dim3 grid((unsigned)((r.m + REPL_LINES - 1u) / REPL_LINES)), block(REPL_THREADS);
+	hipLaunchKernelGGL(repl_lengths, grid, block, 0, s, r);
+	return HIP_OK(hipGetLastError()) ? 0 : -1;
+}
+
+int repl_launch_offsets(const ReplRun &r, hipStream_t s)
+{
+	if (r.m == 0) return 0;
+	if (!repl_grid_fits(r.m)) { errno = ENOMEM; return -1; }
+	const dim3 grid((unsigned)((r.m + REPL_LINES - 1u) / REPL_LINES)), block(REPL_THREADS);
+	hipLaunchKernelGGL(repl_offsets, grid, block, 0, s, r);
+	return HIP_OK(hipGetLastError()) ? 0 : -1;
+}
+
+int repl_launch_write(const ReplRun &r, hipStream_t s)
+{
+	if (r.m == 0 || r.total == 0 || r.ngb == 0) return 0;
+	if (r.wgs == 0 || r.wgs > 0x7fffffffu) { errno = ENOMEM; return -1; }
+	const dim3 grid((unsigned)r.wgs), block(REPL_THREADS);
+	if (r.table_in_lds) {
+		if (!repl_table_fits_lds(r.nrepl, r.rbytes)) { errno = EINVAL; return -1; }
+		const size_t lds = (((size_t)r.rbytes + 15u) & ~(size_t)15u) + 4u * ((size_t)r.nrepl + 1u);
+		hipLaunchKernelGGL(repl_write<true>, grid, block, lds, s, r);
+	} else {
+		hipLaunchKernelGGL(repl_write<false>, grid, block, 0, s, r);
+	}
+	return HIP_OK(hipGetLastError()) ? 0 : -1;
+}
+
+}   // namespace fsmhip

@@ -32,6 +32,7 @@
 #include "hip_host.h"
 #include "match.h"
 #include "match_marks.h"
+#include "replace.h"
 #include "span.h"
 #include "tok.h"
 
@@ -2097,4 +2098,307 @@ extern "C" double fsm_hip_matches_pass_ms(const struct fsm_hip_matches *mt, int 
 {
 	if (mt == nullptr || pass < 0 || pass > 3) { errno = EINVAL; return -1.0; }
 	return elapsed_ms(mt->device, mt->ev[7], {{mt->ev[2 * pass], mt->ev[2 * pass + 1]}});
+}
+
+/* ---- replace: every match replaced by its rule's replacement, a fresh packed text (replace.hip) --------------------------------
+ * lengths pass (per input, per match, per block of REPL_LINES inputs) -> exclusive scan of the BLOCK sums by one workgroup -> ONE
+ * wait for the total -> allocation -> offsets pass (the block's own scan redone, first[]) -> write pass.  The scan runs over
+ * m / REPL_LINES records, not over m: a text of short lines does not pay the one-workgroup scan per line that the tokens and
+ * the matches pay.  first[] has an entry per block of the output, so the offsets pass that fills it follows the wait; it and the
+ * write pass are in flight at return. */
+namespace {
+
+constexpr uint32_t REPL_SCAN_PER = 4;                       /* sums a thread of the scan takes a round: 4 096 blocks, 1 Mi inputs */
+
+__global__ void __launch_bounds__(1024)
+repl_scan(uint64_t *sums, uint64_t nblocks)
+{
+	sum_scan<1024, 1, REPL_SCAN_PER>(sums, nblocks, sums + nblocks);
+}
+
+}   // namespace
+
+struct __attribute__((visibility("hidden"))) fsm_hip_repl {
+	int device = 0;
+	size_t nrepl = 0;
+	uint64_t rbytes = 0;
+	unsigned flags = 0;
+	bool in_lds = false;
+	DevBuf<unsigned char> d_bytes;           /* rbytes, rounded up to 16 and never nothing */
+	DevBuf<uint64_t> d_roff;                 /* nrepl + 1 */
+};
+
+extern "C" struct fsm_hip_repl *fsm_hip_repl_create(const void *bytes, const uint64_t *roff, size_t nrepl, unsigned flags)
+{
+	int dev = 0;
+	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
+	if ((flags & ~FSM_HIP_REPL_MASK) != 0u || (roff == nullptr && nrepl != 0)) { errno = EINVAL; return nullptr; }
+	for (size_t i = 0; i < nrepl; i++)
+		if (roff[i] > roff[i + 1u]) { errno = EINVAL; return nullptr; }
+	const uint64_t rbytes = nrepl != 0 ? roff[nrepl] : 0u;
+	if (rbytes != 0 && bytes == nullptr) { errno = EINVAL; return nullptr; }
+	struct fsm_hip_repl *rp = new (std::nothrow) struct fsm_hip_repl;
+	if (rp == nullptr) { errno = ENOMEM; return nullptr; }
+	rp->device = dev;
+	rp->nrepl = nrepl;
+	rp->rbytes = rbytes;
+	rp->flags = flags;
+	rp->in_lds = fsmhip::repl_table_fits_lds(nrepl, rbytes);
+	const uint64_t zero = 0;
+	if (HIP_OK(rp->d_bytes.upload_bytes(bytes, (size_t)rbytes, 16)) &&
+	    HIP_OK(rp->d_roff.upload_bytes(nrepl != 0 ? roff : &zero, (nrepl + 1u) * sizeof(uint64_t), sizeof(uint64_t))))
+		return rp;
+	const int e = errno;
+	delete rp;
+	errno = e;
+	return nullptr;
+}
+
+extern "C" void fsm_hip_repl_free(struct fsm_hip_repl *rp)
+{
+	if (rp == nullptr) return;
+	const int e = errno;
+	{
+		DevGuard dg(rp->device);
+		delete rp;
+	}
+	errno = e;
+}
+
+extern "C" int fsm_hip_repl_in_lds(const struct fsm_hip_repl *rp) { return rp != nullptr && rp->in_lds ? 1 : 0; }
+extern "C" size_t fsm_hip_repl_lds_bytes(void) { return fsmhip::REPL_LDS_BYTES; }
+extern "C" size_t fsm_hip_repl_lds_rules(void) { return fsmhip::REPL_LDS_RULES; }
+extern "C" size_t fsm_hip_replaced_block_lines(void) { return fsmhip::REPL_LINES; }
+extern "C" size_t fsm_hip_replaced_block_bytes(void) { return fsmhip::REPL_BLOCK; }
+
+struct __attribute__((visibility("hidden"))) fsm_hip_replaced {
+	int device = 0;
+	size_t m = 0;
+	uint64_t nbytes = 0;
+	DevBuf<uint64_t> d_off;                  /* m + 1 */
+	DevBuf<uint64_t> d_mpos, d_xlen;         /* one per match: internal */
+	DevBuf<uint64_t> d_sums;                 /* per block of inputs, + the total: internal */
+	DevBuf<uint64_t> d_first;                /* per block of the output, + 1: internal */
+	DevBuf<unsigned char> d_bytes;           /* nbytes, in whole blocks */
+	DevEvent ev[8];                          /* around the lengths, the scan, the offsets, the write pass; ev[7]: all is there */
+};
+
+extern "C" void fsm_hip_replaced_free(struct fsm_hip_replaced *r)
+{
+	if (r == nullptr) return;
+	const int e = errno;
+	{
+		DevGuard dg(r->device);
+		if (r->ev[7] != nullptr) (void)hipEventSynchronize(r->ev[7]);
+		delete r;
+	}
+	errno = e;
+}
+
+/* the passes on stream s into *rd, the objects' device current; r: the batch, the matches and the table (its outputs are set here) */
+static int replaced_passes(struct fsm_hip_replaced *rd, fsmhip::ReplRun r, hipStream_t s)
+{
+	const uint64_t m = r.m, nblocks = (m + fsmhip::REPL_LINES - 1u) / fsmhip::REPL_LINES;
+	uint64_t total = 0;
+	for (DevEvent &ev : rd->ev)
+		if (!HIP_OK(ev.create())) return -1;
+	if (!HIP_OK(rd->d_off.alloc(m + 1u))) return -1;
+	if (m != 0 && !HIP_OK(rd->d_sums.alloc(nblocks + 1u))) return -1;
+	if (m != 0 && r.nmatch != 0 && (!HIP_OK(rd->d_mpos.alloc(r.nmatch)) || !HIP_OK(rd->d_xlen.alloc(r.nmatch)))) return -1;
+	r.out_off = rd->d_off;
+	r.sums = rd->d_sums;
+	r.mpos = rd->d_mpos;
+	r.xlen = rd->d_xlen;
+	if (!HIP_OK(hipEventRecord(rd->ev[0], s))) return -1;
+	if (fsmhip::repl_launch_lengths(r, s) != 0) return -1;
+	if (!HIP_OK(hipEventRecord(rd->ev[1], s)) || !HIP_OK(hipEventRecord(rd->ev[2], s))) return -1;
+	if (m != 0) {
+		hipLaunchKernelGGL(repl_scan, dim3(1), dim3(1024), 0, s, rd->d_sums.p, nblocks);
+		if (!HIP_OK(hipGetLastError())) return -1;
+	} else if (!HIP_OK(hipMemsetAsync(rd->d_off, 0, sizeof(uint64_t), s))) {
+		return -1;
+	}
+	if (!HIP_OK(hipEventRecord(rd->ev[3], s))) return -1;
+	if (m != 0) {   /* the one wait: the total sizes the bytes and first[] */
+		if (!HIP_OK(hipMemcpyAsync(&total, rd->d_sums + nblocks, sizeof total, hipMemcpyDeviceToHost, s))) return -1;
+		if (!HIP_OK(hipStreamSynchronize(s))) return -1;
+	}
+	rd->nbytes = total;
+	r.total = total;
+	r.ngb = (total + fsmhip::REPL_BLOCK - 1u) / fsmhip::REPL_BLOCK;
+	if (total != 0 && (!HIP_OK(rd->d_bytes.alloc(r.ngb * fsmhip::REPL_BLOCK)) || !HIP_OK(rd->d_first.alloc(r.ngb + 1u)))) return -1;
+	r.out = rd->d_bytes;
+	r.first = rd->d_first;
+	const Grid g = grid_of(r.ngb, rd->device);
+	r.wgs = g.wgs;
+	r.per = g.per;
+	if (!HIP_OK(hipEventRecord(rd->ev[4], s))) return -1;
+	if (fsmhip::repl_launch_offsets(r, s) != 0) return -1;
+	if (!HIP_OK(hipEventRecord(rd->ev[5], s)) || !HIP_OK(hipEventRecord(rd->ev[6], s))) return -1;
+	if (fsmhip::repl_launch_write(r, s) != 0) return -1;
+	return HIP_OK(hipEventRecord(rd->ev[7], s)) ? 0 : -1;
+}
+
+/* the replaced object of a run on stream s; when the run fails, the stream is made idle before what it has launched on is released */
+static struct fsm_hip_replaced *replaced_new(const struct fsm_hip_matches *mt, const struct fsm_hip_repl *rp, fsmhip::ReplRun r, hipStream_t s)
+{
+	if (!fsmhip::repl_grid_fits(r.m)) { errno = ENOMEM; return nullptr; }
+	struct fsm_hip_replaced *rd = new (std::nothrow) struct fsm_hip_replaced;
+	if (rd == nullptr) { errno = ENOMEM; return nullptr; }
+	rd->device = mt->device;
+	rd->m = (size_t)r.m;
+	r.moff = mt->d_off;
+	r.start = mt->d_start;
+	r.end = mt->d_end;
+	r.id = mt->d_id;
+	r.nmatch = mt->total;
+	r.rbytes_p = rp->d_bytes;
+	r.roff = rp->d_roff;
+	r.nrepl = rp->nrepl;
+	r.rbytes = rp->rbytes;
+	r.flags = rp->flags;
+	r.table_in_lds = rp->in_lds;
+	if (HIP_OK(hipStreamWaitEvent(s, mt->ev[7], 0)) && replaced_passes(rd, r, s) == 0) return rd;   /* behind the matches' emit pass */
+	const int e = errno;
+	(void)hipStreamSynchronize(s);
+	fsm_hip_replaced_free(rd);
+	errno = e;
+	return nullptr;
+}
+
+/* the arguments both forms refuse alike; *m: the inputs */
+static int replaced_check(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b, const struct fsm_hip_repl *rp, uint64_t *m)
+{
+	if (!have_device()) { errno = ENODEV; return -1; }
+	if (mt == nullptr || b == nullptr || rp == nullptr || rp->device != mt->device) { errno = EINVAL; return -1; }
+	*m = b->pick != nullptr ? (uint64_t)b->m : (uint64_t)b->n;
+	if (*m != (uint64_t)mt->m || (*m != 0 && b->off == nullptr)) { errno = EINVAL; return -1; }
+	return 0;
+}
+
+static fsmhip::ReplRun replaced_run_of(const struct fsm_hip_match_batch *b, uint64_t m)
+{
+	fsmhip::ReplRun r;
+	r.base = b->base;
+	r.off = b->off;
+	r.pick = b->pick;
+	r.n = b->n;
+	r.m = m;
+	r.limit = b->limit;
+	return r;
+}
+
+extern "C" struct fsm_hip_replaced *fsm_hip_matches_replace_device(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b,
+	const struct fsm_hip_repl *rp, void *hip_stream)
+{
+	uint64_t m = 0;
+	if (replaced_check(mt, b, rp, &m) != 0) return nullptr;
+	if (b->base == nullptr && b->limit != 0u) { errno = EINVAL; return nullptr; }
+	DevGuard dg(mt->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	fsmhip::ReplRun r = replaced_run_of(b, m);
+	if (m != 0 && b->limit == 0u && b->base != nullptr) {   /* as the matches: limit 0 is off[n], a short wait of its own */
+		uint64_t last = 0;
+		if (!HIP_OK(hipMemcpyAsync(&last, b->off + b->n, sizeof last, hipMemcpyDeviceToHost, s)) || !HIP_OK(hipStreamSynchronize(s))) return nullptr;
+		r.limit = last;
+	}
+	return replaced_new(mt, rp, r, s);
+}
+
+extern "C" struct fsm_hip_replaced *fsm_hip_matches_replace(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b,
+	const struct fsm_hip_repl *rp)
+{
+	uint64_t m = 0;
+	if (replaced_check(mt, b, rp, &m) != 0) return nullptr;
+	const uint64_t n = b->n;
+	if (m != 0) {
+		for (uint64_t i = 0; i < n; i++)
+			if (b->off[i] > b->off[i + 1u]) { errno = EINVAL; return nullptr; }
+		if (b->base == nullptr && b->off[n] != 0u) { errno = EINVAL; return nullptr; }
+		if (b->pick != nullptr)
+			for (uint64_t j = 0; j < m; j++)
+				if (b->pick[j] >= n) { errno = EINVAL; return nullptr; }
+	}
+	DevGuard dg(mt->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	DevStream own;                                   /* never the NULL stream */
+	if (!HIP_OK(own.create(hipStreamNonBlocking))) return nullptr;
+	hipStream_t s = own;
+	fsmhip::ReplRun r = replaced_run_of(b, m);
+	r.limit = 0;
+	DevBuf<unsigned char> d;                         /* everything staged in one allocation, each piece at a multiple of 16 bytes */
+	if (m != 0) {
+		auto up16 = [](uint64_t x) { return (x + 15u) & ~(uint64_t)15u; };
+		const uint64_t nbytes = b->off[n], n_off = (n + 1u) * 8u, n_m = m * 8u;
+		const uint64_t at_off = up16(nbytes), at_pick = at_off + up16(n_off), all = at_pick + (b->pick ? up16(n_m) : 0u);
+		if (!HIP_OK(d.alloc(all))) return nullptr;
+		bool ok = nbytes == 0 || HIP_OK(hipMemcpyAsync(d, b->base, nbytes, hipMemcpyHostToDevice, s));
+		ok = ok && HIP_OK(hipMemcpyAsync(d + at_off, b->off, n_off, hipMemcpyHostToDevice, s));
+		ok = ok && (b->pick == nullptr || HIP_OK(hipMemcpyAsync(d + at_pick, b->pick, n_m, hipMemcpyHostToDevice, s)));
+		if (!ok) {   /* the stream idle before the staging memory goes */
+			const int e = errno;
+			(void)hipStreamSynchronize(s);
+			errno = e;
+			return nullptr;
+		}
+		r.base = nbytes != 0 ? d.p : nullptr;
+		r.limit = nbytes;
+		r.off = (const uint64_t *)(d + at_off);
+		r.pick = b->pick ? (const uint64_t *)(d + at_pick) : nullptr;
+	}
+	struct fsm_hip_replaced *rd = replaced_new(mt, rp, r, s);
+	if (rd == nullptr) return nullptr;               /* (replaced_new left the stream idle) */
+	if (!HIP_OK(hipStreamSynchronize(s))) {          /* the write pass has read the staged text */
+		const int e = errno;
+		fsm_hip_replaced_free(rd);
+		errno = e;
+		return nullptr;
+	}
+	return rd;
+}
+
+extern "C" struct fsm_hip_replaced *fsm_hip_text_replace(const struct fsm_hip_matches *mt, const struct fsm_hip_text *t,
+	const struct fsm_hip_text_hits *h, const struct fsm_hip_repl *rp, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (mt == nullptr || t == nullptr || rp == nullptr) { errno = EINVAL; return nullptr; }
+	if (mt->device != t->device || rp->device != t->device || (h != nullptr && h->device != t->device)) { errno = EINVAL; return nullptr; }
+	if (mt->m != (h != nullptr ? h->m : t->n)) { errno = EINVAL; return nullptr; }
+	DevGuard dg(t->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	/* the hits' lines (and, behind them, the text's offsets) first */
+	if (!HIP_OK(hipStreamWaitEvent(s, h != nullptr ? h->ev[5] : t->ev[3], 0))) return nullptr;
+	fsmhip::ReplRun r;
+	r.base = t->d_text;
+	r.off = t->d_off;
+	r.n = t->n;
+	r.pick = h != nullptr ? h->d_lines.p : nullptr;
+	r.m = h != nullptr ? h->m : t->n;
+	r.limit = t->nbytes;
+	return replaced_new(mt, rp, r, s);
+}
+
+extern "C" size_t fsm_hip_replaced_count(const struct fsm_hip_replaced *r) { return r == nullptr ? 0 : r->m; }
+extern "C" uint64_t fsm_hip_replaced_nbytes(const struct fsm_hip_replaced *r) { return r == nullptr ? 0 : r->nbytes; }
+extern "C" const uint64_t *fsm_hip_replaced_off_device(const struct fsm_hip_replaced *r) { return r == nullptr ? nullptr : r->d_off.p; }
+extern "C" const unsigned char *fsm_hip_replaced_bytes_device(const struct fsm_hip_replaced *r) { return r == nullptr ? nullptr : r->d_bytes.p; }
+
+extern "C" int fsm_hip_replaced_copy(const struct fsm_hip_replaced *r, uint64_t *off, void *bytes)
+{
+	if (r == nullptr) { errno = EINVAL; return -1; }
+	return copy_out(r->device, r->ev[7], {{off, r->d_off, (r->m + 1u) * sizeof(uint64_t)}, {bytes, r->d_bytes, (size_t)r->nbytes}});
+}
+
+extern "C" double fsm_hip_replaced_ms(const struct fsm_hip_replaced *r)
+{
+	if (r == nullptr) { errno = EINVAL; return -1.0; }
+	return elapsed_ms(r->device, r->ev[7], {{r->ev[0], r->ev[1]}, {r->ev[2], r->ev[3]}, {r->ev[4], r->ev[5]}, {r->ev[6], r->ev[7]}});
+}
+
+extern "C" double fsm_hip_replaced_pass_ms(const struct fsm_hip_replaced *r, int pass)
+{
+	if (r == nullptr || pass < 0 || pass > 3) { errno = EINVAL; return -1.0; }
+	return elapsed_ms(r->device, r->ev[7], {{r->ev[2 * pass], r->ev[2 * pass + 1]}});
 }
