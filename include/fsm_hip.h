@@ -1125,7 +1125,7 @@ void fsm_hip_matches_free(struct fsm_hip_matches *mt);
  *   Input j is line pick[j] of a packed text: base, off, n, pick, m, trim_byte and limit exactly as in struct fsm_hip_match_batch.
  *   raw is the line's byte count and len its trimmed length, so raw - len is 0 or 1.  Its matches are entries moff[j] .. moff[j + 1]
  *   of a struct fsm_hip_matches, which must have been made from the same batch: m must equal fsm_hip_matches_count (EINVAL), the
- *   rest is the caller's word.  The batch's flags are not read.
+ *   rest is the caller's word.  The batch's flags are not used, but they and trim_byte must be what the matches accept.
  *   A replacement table holds nrepl byte strings, R[i] = bytes[roff[i] .. roff[i + 1]).
  *   The output line is built from these pieces, in order:
  *   - the bytes [0, start_0);
@@ -1163,8 +1163,8 @@ void fsm_hip_matches_free(struct fsm_hip_matches *mt);
  * bytes (NULL when there are none).  m == 0 or zero output bytes gives a valid object and launches nothing that stores into bytes.
  * _copy copies out whichever of off / bytes are not NULL and waits; _ms: the four passes by HIP events; _pass_ms: one of them.
  * NULL + errno: ENODEV (checked first: there is no CPU path), EINVAL (an argument NULL, roff NULL with nrepl > 0, roff that
- * decreases, bytes NULL with bytes to copy, an unknown flag bit, m that is not the matches', objects on different devices; host
- * form: offsets that decrease, a pick[j] >= n), ENOMEM. */
+ * decreases, bytes NULL with bytes to copy, an unknown flag bit, trim_byte outside -1 .. 255, m that is not the matches', objects
+ * on different devices; host form: offsets that decrease, a pick[j] >= n), ENOMEM. */
 #define FSM_HIP_REPL_MASK 1u
 struct fsm_hip_repl;       /* a replacement table resident on the current device, reusable across calls */
 struct fsm_hip_repl *fsm_hip_repl_create(const void *bytes, const uint64_t *roff, size_t nrepl, unsigned flags);

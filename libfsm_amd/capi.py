@@ -297,6 +297,18 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     return lib
 
 
+def _line_arrays(base, off, pick):
+    """the host arrays of a batch of lines as the library takes them -> (base u8, off u64 [n + 1], pick u64 [m] or None, n, m)"""
+    base = np.ascontiguousarray(base, np.uint8)
+    off = np.ascontiguousarray(off, np.uint64)
+    pick = None if pick is None else np.ascontiguousarray(pick, np.uint64)
+    n = len(off) - 1
+    m = n if pick is None else len(pick)
+    if pick is not None and m == 0:
+        pick = np.zeros(1, np.uint64)   # an empty pick is still a pick: a non-NULL address
+    return base, off, pick, n, m
+
+
 def _oserr(what: str):
     e = C.get_errno()
     return OSError(e, f"{what}: {os.strerror(e)}")
@@ -1529,14 +1541,9 @@ class PosDfa:
                    want_first: bool = True, want_last: bool = True, out: Optional[tuple] = None):
         """fsm_hip_exec_accept_pos on host arrays -> (first, last), u64 [m] each (None for the one not asked for).  out: the
         (first, last) arrays to write into instead."""
-        base = np.ascontiguousarray(base, np.uint8)
-        off = np.ascontiguousarray(off, np.uint64)
+        base, off, pick, n, m = _line_arrays(base, off, pick)
         u64 = lambda a: None if a is None else np.ascontiguousarray(a, np.uint64)   # noqa: E731
-        pick, frm, to = u64(pick), u64(frm), u64(to)
-        n = len(off) - 1
-        m = n if pick is None else len(pick)
-        if pick is not None and m == 0:
-            pick = np.zeros(1, np.uint64)   # an empty pick is still a pick: a non-NULL address
+        frm, to = u64(frm), u64(to)
         first, last = out if out is not None else (np.empty(m, np.uint64) if want_first else None, np.empty(m, np.uint64) if want_last else None)
         b = PosBatch(_ptr0(base), _ptr(off), n, _ptr(pick), m, _ptr(frm), _ptr(to), trim_byte, POS_BACKWARD if backward else 0, _ptr(first), _ptr(last), 0)
         _call("fsm_hip_exec_accept_pos", self._h, C.byref(b))
@@ -1631,13 +1638,7 @@ class TokDfa:
 
     def tokens(self, base: np.ndarray, off: np.ndarray, pick=None, trim_byte: int = -1, flags: int = 0) -> "HipTokens":
         """fsm_hip_tokens_run on host arrays"""
-        base = np.ascontiguousarray(base, np.uint8)
-        off = np.ascontiguousarray(off, np.uint64)
-        pick = None if pick is None else np.ascontiguousarray(pick, np.uint64)
-        n = len(off) - 1
-        m = n if pick is None else len(pick)
-        if pick is not None and m == 0:
-            pick = np.zeros(1, np.uint64)   # an empty pick is still a pick: a non-NULL address
+        base, off, pick, n, m = _line_arrays(base, off, pick)
         b = TokBatch(_ptr0(base), _ptr(off), n, _ptr(pick), m, trim_byte, flags, 0)
         return HipTokens(_call("fsm_hip_tokens_run", self._h, C.byref(b)), (self,))
 
@@ -1732,13 +1733,7 @@ class HipMatches:
     @classmethod
     def run(cls, starts: PosDfa, ends: TokDfa, base: np.ndarray, off: np.ndarray, pick=None, trim_byte: int = -1, flags: int = 0) -> "HipMatches":
         """fsm_hip_matches_run on host arrays"""
-        base = np.ascontiguousarray(base, np.uint8)
-        off = np.ascontiguousarray(off, np.uint64)
-        pick = None if pick is None else np.ascontiguousarray(pick, np.uint64)
-        n = len(off) - 1
-        m = n if pick is None else len(pick)
-        if pick is not None and m == 0:
-            pick = np.zeros(1, np.uint64)   # an empty pick is still a pick: a non-NULL address
+        base, off, pick, n, m = _line_arrays(base, off, pick)
         b = MatchBatch(_ptr0(base), _ptr(off), n, _ptr(pick), m, trim_byte, flags, 0)
         return cls(_call("fsm_hip_matches_run", starts.handle, ends.handle, C.byref(b)), (starts, ends))
 
@@ -1797,13 +1792,7 @@ class HipMatches:
 
     def replace(self, repl: "HipRepl", base: np.ndarray, off: np.ndarray, pick=None, trim_byte: int = -1) -> "HipReplaced":
         """fsm_hip_matches_replace on host arrays: the batch these matches were made from"""
-        base = np.ascontiguousarray(base, np.uint8)
-        off = np.ascontiguousarray(off, np.uint64)
-        pick = None if pick is None else np.ascontiguousarray(pick, np.uint64)
-        n = len(off) - 1
-        m = n if pick is None else len(pick)
-        if pick is not None and m == 0:
-            pick = np.zeros(1, np.uint64)   # an empty pick is still a pick: a non-NULL address
+        base, off, pick, n, m = _line_arrays(base, off, pick)
         b = MatchBatch(_ptr0(base), _ptr(off), n, _ptr(pick), m, trim_byte, 0, 0)
         return HipReplaced(_call("fsm_hip_matches_replace", self._h, C.byref(b), repl.handle), (self, repl))
 

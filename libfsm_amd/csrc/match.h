@@ -1,7 +1,7 @@
 /*
  * match.h -- how text.hip launches the passes of the matches (match.hip): walk_mark over a struct fsm_hip_pos_dfa, then
  * walk_match<false> / walk_match<true> over a struct fsm_hip_tok_dfa.  The fronts (the matches object, its scan) are in
- * text.hip.  Not part of the C ABI.
+ * text.hip; the batch a pass runs over is line_batch.h's.  Not part of the C ABI.
  */
 #ifndef FSMHIP_CSRC_MATCH_H
 #define FSMHIP_CSRC_MATCH_H
@@ -9,6 +9,8 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
+
+#include "line_batch.h"
 
 struct fsm_hip_pos_dfa;
 struct fsm_hip_tok_dfa;
@@ -22,13 +24,7 @@ inline bool match_grid_fits(uint64_t m) { return (m + MATCH_THREADS - 1u) / MATC
 
 /* one pass over m inputs; every pointer is device memory */
 struct MatchRun {
-	const void *base = nullptr;
-	const uint64_t *off = nullptr;           /* n + 1 */
-	const uint64_t *pick = nullptr;          /* m, or null: input j is line j */
-	uint64_t n = 0, m = 0;
-	uint64_t limit = 0;                      /* the bytes of base that may be read: always given (the marks are sized by it) */
-	int trim = -1;
-	unsigned flags = 0;                      /* FSM_HIP_MATCHES_* */
+	LineBatch in;                            /* its limit always given (the marks are sized by it); flags: FSM_HIP_MATCHES_* */
 	uint16_t *marks = nullptr;               /* marks_words(limit, n) words (match_marks.h): walk_mark writes, walk_match reads */
 	uint64_t nwords = 0;
 	uint64_t *count = nullptr;               /* the count pass writes it: m */

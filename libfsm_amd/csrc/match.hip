@@ -356,22 +356,22 @@ MatchArgs args_of(const MatchRun &r)
 	a.tab = nullptr;
 	a.col = nullptr;
 	a.ids = nullptr;
-	a.base = static_cast<const uint8_t *>(r.base);
-	a.off = r.off;
-	a.pick = r.pick;
+	a.base = static_cast<const uint8_t *>(r.in.base);
+	a.off = r.in.off;
+	a.pick = r.in.pick;
 	a.marks = r.marks;
 	a.count = r.count;
 	a.match_off = r.match_off;
 	a.start_out = r.start_out;
 	a.end_out = r.end_out;
 	a.id_out = r.id_out;
-	a.n = r.n;
-	a.m = r.m;
-	a.limit = r.limit;
+	a.n = r.in.n;
+	a.m = r.in.m;
+	a.limit = r.in.limit;
 	a.nwords = r.nwords;
 	a.entries = a.C = a.start = a.abs_min = a.in_lds = 0;
-	a.flags = r.flags;
-	a.trim = r.trim;
+	a.flags = r.in.flags;
+	a.trim = r.in.trim;
 	return a;
 }
 
@@ -381,8 +381,8 @@ namespace fsmhip {
 
 int match_launch_mark(const fsm_hip_pos_dfa *starts, const MatchRun &r, hipStream_t s)
 {
-	if (r.m == 0) return 0;
-	if (!match_grid_fits(r.m)) { errno = ENOMEM; return -1; }
+	if (r.in.m == 0) return 0;
+	if (!match_grid_fits(r.in.m)) { errno = ENOMEM; return -1; }
 	const PosView v = pos_dfa_view(starts);
 	if (v.in_lds != 0u && v.entries > MATCH_LDS_ENTRIES) { errno = EINVAL; return -1; }
 	MatchArgs a = args_of(r);
@@ -393,15 +393,15 @@ int match_launch_mark(const fsm_hip_pos_dfa *starts, const MatchRun &r, hipStrea
 	a.start = v.start;
 	a.abs_min = v.abs_min;
 	a.in_lds = v.in_lds;
-	const dim3 grid((unsigned)((r.m + MATCH_THREADS - 1u) / MATCH_THREADS)), block(MATCH_THREADS);
+	const dim3 grid((unsigned)((r.in.m + MATCH_THREADS - 1u) / MATCH_THREADS)), block(MATCH_THREADS);
 	hipLaunchKernelGGL(walk_mark, grid, block, 0, s, a);
 	return HIP_OK(hipGetLastError()) ? 0 : -1;
 }
 
 int match_launch(const fsm_hip_tok_dfa *ends, const MatchRun &r, bool emit, hipStream_t s)
 {
-	if (r.m == 0) return 0;
-	if (!match_grid_fits(r.m)) { errno = ENOMEM; return -1; }
+	if (r.in.m == 0) return 0;
+	if (!match_grid_fits(r.in.m)) { errno = ENOMEM; return -1; }
 	const TokView v = tok_dfa_view(ends);
 	if (v.in_lds != 0u && v.entries > MATCH_LDS_ENTRIES) { errno = EINVAL; return -1; }
 	MatchArgs a = args_of(r);
@@ -413,7 +413,7 @@ int match_launch(const fsm_hip_tok_dfa *ends, const MatchRun &r, bool emit, hipS
 	a.start = v.start;
 	a.abs_min = v.abs_min;
 	a.in_lds = v.in_lds;
-	const dim3 grid((unsigned)((r.m + MATCH_THREADS - 1u) / MATCH_THREADS)), block(MATCH_THREADS);
+	const dim3 grid((unsigned)((r.in.m + MATCH_THREADS - 1u) / MATCH_THREADS)), block(MATCH_THREADS);
 	if (emit) hipLaunchKernelGGL(walk_match<true>, grid, block, 0, s, a);
 	else hipLaunchKernelGGL(walk_match<false>, grid, block, 0, s, a);
 	return HIP_OK(hipGetLastError()) ? 0 : -1;

@@ -26,7 +26,8 @@ inline bool repl_table_fits_lds(uint64_t nrepl, uint64_t rbytes) { return nrepl 
 /* m inputs fit one launch's grid */
 inline bool repl_grid_fits(uint64_t m) { return (m + REPL_LINES - 1u) / REPL_LINES <= 0x7fffffffu; }
 
-/* the passes' arguments; every pointer is device memory */
+/* the passes' arguments; every pointer is device memory.  The kernels take this struct itself, so it spells the batch's fields
+ * out where TokRun and MatchRun carry a LineBatch (line_batch.h): text.hip copies them from one. */
 struct ReplRun {
 	/* the batch */
 	const void *base = nullptr;

@@ -31,6 +31,7 @@
 #include "../../include/fsm_hip.h"
 #include "dfa_access.h"
 #include "hip_host.h"
+#include "line_batch.h"
 #include "span.h"
 
 using namespace fsmhip;
@@ -290,81 +291,62 @@ extern "C" void fsm_hip_pos_dfa_free(struct fsm_hip_pos_dfa *pd)
 
 extern "C" int fsm_hip_pos_dfa_in_lds(const struct fsm_hip_pos_dfa *pd) { return pd != nullptr && pd->in_lds != 0u ? 1 : 0; }
 
-/* the arguments both forms refuse alike; *m: the inputs */
-static int pos_check(const struct fsm_hip_pos_dfa *pd, const struct fsm_hip_pos_batch *b, uint64_t *m)
+/* the arguments both forms refuse alike; *in: the batch as given */
+static int pos_check(const struct fsm_hip_pos_dfa *pd, const struct fsm_hip_pos_batch *b, fsmhip::LineBatch *in)
 {
 	if (!pos_have_device()) { errno = ENODEV; return -1; }
-	if (pd == nullptr || b == nullptr || (b->flags & ~(unsigned)FSM_HIP_POS_BACKWARD) != 0u || b->trim_byte < -1 || b->trim_byte > 255) {
-		errno = EINVAL;
-		return -1;
-	}
-	*m = b->pick != nullptr ? (uint64_t)b->m : (uint64_t)b->n;
-	if (*m != 0 && b->off == nullptr) { errno = EINVAL; return -1; }
-	if ((*m + POS_THREADS - 1u) / POS_THREADS > 0x7fffffffu) { errno = ENOMEM; return -1; }
+	if (pd == nullptr) { errno = EINVAL; return -1; }
+	if (!fsmhip::batch_shape(b, FSM_HIP_POS_BACKWARD, in)) return -1;
+	if ((in->m + POS_THREADS - 1u) / POS_THREADS > 0x7fffffffu) { errno = ENOMEM; return -1; }
 	return 0;
 }
 
 extern "C" int fsm_hip_exec_accept_pos_device(const struct fsm_hip_pos_dfa *pd, const struct fsm_hip_pos_batch *b, void *hip_stream)
 {
-	uint64_t m = 0;
-	if (pos_check(pd, b, &m) != 0) return -1;
-	if (b->base == nullptr && b->limit != 0u) { errno = EINVAL; return -1; }
-	if (m == 0 || (b->first_out == nullptr && b->last_out == nullptr)) return 0;
+	fsmhip::LineBatch in;
+	if (pos_check(pd, b, &in) != 0 || !fsmhip::batch_device_ok(in)) return -1;
+	if (in.m == 0 || (b->first_out == nullptr && b->last_out == nullptr)) return 0;
 	DevGuard dg(pd->device);
 	if (!dg.ok()) { errno = ENODEV; return -1; }
 	PosArgs a;
 	a.tab = pd->d_tab.p;
 	a.col = pd->d_col.p;
-	a.base = static_cast<const uint8_t *>(b->base);
-	a.off = b->off;
-	a.pick = b->pick;
+	a.base = static_cast<const uint8_t *>(in.base);
+	a.off = in.off;
+	a.pick = in.pick;
 	a.from = b->from;
 	a.to = b->to;
 	a.first_out = b->first_out;
 	a.last_out = b->last_out;
-	a.n = b->n;
-	a.m = m;
-	a.limit = b->limit;
-	a.has_limit = b->limit != 0u || b->base == nullptr ? 1u : 0u;   /* no text: no byte may be read */
+	a.n = in.n;
+	a.m = in.m;
+	a.limit = in.limit;
+	a.has_limit = in.has_limit ? 1u : 0u;
 	a.entries = pd->entries;
 	a.C = pd->C;
 	a.start = pd->start;
 	a.abs_min = pd->abs_min;
 	a.in_lds = pd->in_lds;
-	a.trim = b->trim_byte;
-	const dim3 grid((unsigned)((m + POS_THREADS - 1u) / POS_THREADS)), block(POS_THREADS);
+	a.trim = in.trim;
+	const dim3 grid((unsigned)((in.m + POS_THREADS - 1u) / POS_THREADS)), block(POS_THREADS);
 	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	if ((b->flags & FSM_HIP_POS_BACKWARD) != 0u) hipLaunchKernelGGL(walk_pos<true>, grid, block, 0, s, a);
+	if ((in.flags & FSM_HIP_POS_BACKWARD) != 0u) hipLaunchKernelGGL(walk_pos<true>, grid, block, 0, s, a);
 	else hipLaunchKernelGGL(walk_pos<false>, grid, block, 0, s, a);
 	return HIP_OK(hipGetLastError()) ? 0 : -1;
 }
 
 extern "C" int fsm_hip_exec_accept_pos(const struct fsm_hip_pos_dfa *pd, const struct fsm_hip_pos_batch *b)
 {
-	uint64_t m = 0;
-	if (pos_check(pd, b, &m) != 0) return -1;
-	const uint64_t n = b->n;
-	if (m != 0) {
-		for (uint64_t i = 0; i < n; i++)
-			if (b->off[i] > b->off[i + 1u]) { errno = EINVAL; return -1; }
-		if (b->base == nullptr && b->off[n] != 0u) { errno = EINVAL; return -1; }
-		if (b->pick != nullptr)
-			for (uint64_t j = 0; j < m; j++)
-				if (b->pick[j] >= n) { errno = EINVAL; return -1; }
-	}
-	if (m == 0 || (b->first_out == nullptr && b->last_out == nullptr)) return 0;
+	fsmhip::LineBatch host, in;
+	if (pos_check(pd, b, &host) != 0 || !fsmhip::batch_host_arrays_ok(host)) return -1;
+	if (host.m == 0 || (b->first_out == nullptr && b->last_out == nullptr)) return 0;
 	DevGuard dg(pd->device);
 	if (!dg.ok()) { errno = ENODEV; return -1; }
-	/* everything staged one after the other in one allocation, each piece at a multiple of 16 bytes */
-	auto up16 = [](uint64_t x) { return (x + 15u) & ~(uint64_t)15u; };
-	const uint64_t nbytes = b->off[n], n_off = (n + 1u) * 8u, n_m = m * 8u;
-	const uint64_t at_off = up16(nbytes), at_pick = at_off + up16(n_off), at_from = at_pick + (b->pick ? up16(n_m) : 0u),
-	               at_to = at_from + (b->from ? up16(n_m) : 0u), at_first = at_to + (b->to ? up16(n_m) : 0u),
-	               at_last = at_first + (b->first_out ? up16(n_m) : 0u), all = at_last + (b->last_out ? up16(n_m) : 0u);
 	std::lock_guard<std::mutex> lock(pd->mu);
 	hipStream_t s = pd->own;
-	DevBuf<unsigned char> d;
-	if (!HIP_OK(d.alloc(all))) return -1;
+	/* the batch staged in one allocation, from / to and room for the two outputs behind it */
+	fsmhip::StagedBatch staged;
+	if (!staged.stage(host, s, &in, {{b->from}, {b->to}, {b->first_out, false}, {b->last_out, false}})) return -1;
 	auto fail = [&] {   /* the stream idle before the staging memory goes */
 		const int e = errno;
 		(void)hipStreamSynchronize(s);
@@ -372,19 +354,15 @@ extern "C" int fsm_hip_exec_accept_pos(const struct fsm_hip_pos_dfa *pd, const s
 		return -1;
 	};
 	struct fsm_hip_pos_batch db = *b;
-	db.base = nbytes != 0 ? d.p : nullptr;
-	db.limit = nbytes;
-	db.off = (const uint64_t *)(d + at_off);
-	db.pick = b->pick ? (const uint64_t *)(d + at_pick) : nullptr;
-	db.from = b->from ? (const uint64_t *)(d + at_from) : nullptr;
-	db.to = b->to ? (const uint64_t *)(d + at_to) : nullptr;
-	db.first_out = b->first_out ? (uint64_t *)(d + at_first) : nullptr;
-	db.last_out = b->last_out ? (uint64_t *)(d + at_last) : nullptr;
-	if (nbytes != 0 && !HIP_OK(hipMemcpyAsync(d, b->base, nbytes, hipMemcpyHostToDevice, s))) return fail();
-	if (!HIP_OK(hipMemcpyAsync(d + at_off, b->off, n_off, hipMemcpyHostToDevice, s))) return fail();
-	if (b->pick && !HIP_OK(hipMemcpyAsync(d + at_pick, b->pick, n_m, hipMemcpyHostToDevice, s))) return fail();
-	if (b->from && !HIP_OK(hipMemcpyAsync(d + at_from, b->from, n_m, hipMemcpyHostToDevice, s))) return fail();
-	if (b->to && !HIP_OK(hipMemcpyAsync(d + at_to, b->to, n_m, hipMemcpyHostToDevice, s))) return fail();
+	db.base = in.base;
+	db.limit = in.limit;
+	db.off = in.off;
+	db.pick = in.pick;
+	db.from = staged.extra(0);
+	db.to = staged.extra(1);
+	db.first_out = staged.extra(2);
+	db.last_out = staged.extra(3);
+	const uint64_t n_m = host.m * 8u;
 	if (fsm_hip_exec_accept_pos_device(pd, &db, s) != 0) return fail();
 	if (b->first_out && !HIP_OK(hipMemcpyAsync(b->first_out, db.first_out, n_m, hipMemcpyDeviceToHost, s))) return fail();
 	if (b->last_out && !HIP_OK(hipMemcpyAsync(b->last_out, db.last_out, n_m, hipMemcpyDeviceToHost, s))) return fail();

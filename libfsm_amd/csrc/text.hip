@@ -27,9 +27,11 @@
 #include <cstring>
 #include <initializer_list>
 #include <new>
+#include <optional>
 
 #include "../../include/fsm_hip.h"
 #include "hip_host.h"
+#include "line_batch.h"
 #include "match.h"
 #include "match_marks.h"
 #include "replace.h"
@@ -328,19 +330,20 @@ int copy_out(int device, hipEvent_t done, std::initializer_list<OutCopy> copies)
 struct EventPair {
 	hipEvent_t from, to;
 };
-double elapsed_ms(int device, hipEvent_t done, std::initializer_list<EventPair> pairs)
+double elapsed_ms(int device, hipEvent_t done, const EventPair *pairs, size_t npairs)
 {
 	double ms = 0.0;
 	DevGuard dg(device);
 	if (!dg.ok()) { errno = ENODEV; return -1.0; }
 	if (!HIP_OK(hipEventSynchronize(done))) return -1.0;
-	for (const EventPair &p : pairs) {
+	for (size_t k = 0; k < npairs; k++) {
 		float one = 0.f;
-		if (!HIP_OK(hipEventElapsedTime(&one, p.from, p.to))) return -1.0;
+		if (!HIP_OK(hipEventElapsedTime(&one, pairs[k].from, pairs[k].to))) return -1.0;
 		ms += (double)one;
 	}
 	return ms;
 }
+double elapsed_ms(int device, hipEvent_t done, std::initializer_list<EventPair> pairs) { return elapsed_ms(device, done, pairs.begin(), pairs.size()); }
 
 }   // namespace
 
@@ -1635,184 +1638,206 @@ extern "C" double fsm_hip_text_spans_ms(const struct fsm_hip_text_spans *sp)
 	return elapsed_ms(sp->device, sp->ev[1], {{sp->ev[0], sp->ev[1]}});
 }
 
-/* ---- tokens: every line cut into longest-match tokens (tok.hip, walk_tok) ------------------------------------------------
- * count pass -> exclusive scan of the counts by one workgroup -> ONE wait for the total -> allocation -> emit pass.  The counts
- * are scanned in place: d_off is count[m] first, tok_off[m + 1] afterwards (the total lands in its last entry). */
-namespace {
+/* ---- what the tokens, the matches and the replacement share: the object's skeleton, the scan, the batch of a text --------------
+ * Each is an object of NPASS passes on a stream with ONE wait in the middle: the passes before it leave counts, one workgroup
+ * scans them, the host reads the total and sizes the arrays by it, the passes after it fill them and are in flight at return.
+ * Their input is one LineBatch (line_batch.h), whichever of the three entry forms it came through. */
 
-constexpr uint32_t TOK_SCAN_PER = 4;                        /* counts a thread of the scan takes a round: 4 096 lines a round trip */
-
-__global__ void __launch_bounds__(1024)
-tokens_scan(uint64_t *cnt, uint64_t m)
-{
-	sum_scan<1024, 1, TOK_SCAN_PER>(cnt, m, cnt + m);
-}
-
-}   // namespace
-
-struct __attribute__((visibility("hidden"))) fsm_hip_tokens {
+/* what every such object begins with: events ev[2p], ev[2p + 1] around pass p; the last one: all is there */
+template <int NPASS>
+struct __attribute__((visibility("hidden"))) RunObject {
+	static constexpr int npass = NPASS;
 	int device = 0;
-	size_t m = 0, total = 0;
-	DevBuf<uint64_t> d_off;                  /* m + 1 */
-	DevBuf<uint64_t> d_err;                  /* m */
-	DevBuf<uint64_t> d_end;                  /* total */
-	DevBuf<uint32_t> d_id;                   /* total */
-	DevEvent ev[6];                          /* around the count pass, the scan, the emit pass; ev[5]: all is there */
+	size_t m = 0;
+	DevEvent ev[2 * NPASS];
+	hipEvent_t done() const { return ev[2 * NPASS - 1]; }
+	bool begin(int pass, hipStream_t s) { return HIP_OK(hipEventRecord(ev[2 * pass], s)); }
+	bool end(int pass, hipStream_t s) { return HIP_OK(hipEventRecord(ev[2 * pass + 1], s)); }
 };
 
-extern "C" void fsm_hip_tokens_free(struct fsm_hip_tokens *tk)
+namespace {
+
+constexpr uint32_t SCAN_PER = 4;                            /* counts a thread of the scan takes a round: 4 096 a round trip */
+
+__global__ void __launch_bounds__(1024)
+counts_scan(uint64_t *cnt, uint64_t k)
 {
-	if (tk == nullptr) return;
+	sum_scan<1024, 1, SCAN_PER>(cnt, k, cnt + k);
+}
+
+template <typename T>
+void run_free(T *o)
+{
+	if (o == nullptr) return;
 	const int e = errno;
 	{
-		DevGuard dg(tk->device);
-		if (tk->ev[5] != nullptr) (void)hipEventSynchronize(tk->ev[5]);
-		delete tk;
+		DevGuard dg(o->device);
+		if (o->done() != nullptr) (void)hipEventSynchronize(o->done());
+		delete o;
 	}
 	errno = e;
 }
 
+/* the object of a run of passes(o) on stream s over m inputs, `device` current; when the run fails, the stream is made idle
+ * before what it has launched on is released */
+template <typename T, typename Passes>
+T *run_new(int device, uint64_t m, bool grid_fits, hipStream_t s, Passes passes)
+{
+	if (!grid_fits) { errno = ENOMEM; return nullptr; }
+	T *o = new (std::nothrow) T;
+	if (o == nullptr) { errno = ENOMEM; return nullptr; }
+	o->device = device;
+	o->m = (size_t)m;
+	bool ok = true;
+	for (DevEvent &ev : o->ev) ok = ok && HIP_OK(ev.create());
+	if (ok && passes(o) == 0) return o;
+	const int e = errno;
+	(void)hipStreamSynchronize(s);
+	run_free(o);
+	errno = e;
+	return nullptr;
+}
+
+/* A host form behind its checks: the batch staged on a stream of its own (never the NULL stream), the object of make(batch on
+ * the device, stream), and a last wait, since the stream and the staged batch go at return: the last pass has read them. */
+template <typename Make>
+auto run_host(int device, const fsmhip::LineBatch &host, Make make) -> decltype(make(host, hipStream_t()))
+{
+	DevGuard dg(device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	DevStream own;
+	if (!HIP_OK(own.create(hipStreamNonBlocking))) return nullptr;
+	fsmhip::StagedBatch staged;
+	fsmhip::LineBatch in;
+	if (!staged.stage(host, own, &in)) return nullptr;
+	auto *o = make(in, own);
+	if (o == nullptr || HIP_OK(hipStreamSynchronize(own))) return o;   /* (null: run_new left the stream idle) */
+	const int e = errno;
+	run_free(o);
+	errno = e;
+	return nullptr;
+}
+
+/* passes from .. to by the object's events, summed */
+template <typename T>
+double run_ms(const T *o, int from, int to)
+{
+	if (o == nullptr || from < 0 || to >= T::npass) { errno = EINVAL; return -1.0; }
+	EventPair pairs[T::npass];
+	for (int p = from; p <= to; p++) pairs[p - from] = {o->ev[2 * p], o->ev[2 * p + 1]};
+	return elapsed_ms(o->device, o->done(), pairs, (size_t)(to - from + 1));
+}
+
+/* The scan pass and the ONE wait of a run: cnt[0 .. k) scanned in place, exclusive, by one workgroup, the total in cnt[k] (k ==
+ * 0: cnt[0] is cleared and nothing waits), `after` recorded, the total read back. */
+int scan_total(uint64_t *cnt, uint64_t k, hipEvent_t after, hipStream_t s, uint64_t *total)
+{
+	*total = 0;
+	if (k != 0) {
+		hipLaunchKernelGGL(counts_scan, dim3(1), dim3(1024), 0, s, cnt, k);
+		if (!HIP_OK(hipGetLastError())) return -1;
+	} else if (!HIP_OK(hipMemsetAsync(cnt, 0, sizeof(uint64_t), s))) {
+		return -1;
+	}
+	if (!HIP_OK(hipEventRecord(after, s))) return -1;
+	if (k == 0) return 0;
+	if (!HIP_OK(hipMemcpyAsync(total, cnt + k, sizeof *total, hipMemcpyDeviceToHost, s))) return -1;
+	return HIP_OK(hipStreamSynchronize(s)) ? 0 : -1;
+}
+
+/* The lines of a text, or (h != null) of its hits, as a batch for a front on stream s: every object of `devices` is on the
+ * text's device, which *dg makes current for the caller; the stream waits for the hits' lines (and, behind them, the text's
+ * offsets).  false + errno. */
+bool text_batch(const struct fsm_hip_text *t, const struct fsm_hip_text_hits *h, std::initializer_list<int> devices, hipStream_t s,
+	std::optional<DevGuard> *dg, fsmhip::LineBatch *in)
+{
+	for (int d : devices)
+		if (d != t->device) { errno = EINVAL; return false; }
+	if (h != nullptr && h->device != t->device) { errno = EINVAL; return false; }
+	dg->emplace(t->device);
+	if (!(*dg)->ok()) { errno = ENODEV; return false; }
+	if (!HIP_OK(hipStreamWaitEvent(s, h != nullptr ? h->ev[5] : t->ev[3], 0))) return false;
+	in->base = t->d_text;
+	in->off = t->d_off;
+	in->n = t->n;
+	in->pick = h != nullptr ? h->d_lines.p : nullptr;
+	in->m = h != nullptr ? h->m : t->n;
+	in->limit = t->nbytes;
+	in->has_limit = true;
+	in->trim = t->delim;
+	return true;
+}
+
+}   // namespace
+
+/* ---- tokens: every line cut into longest-match tokens (tok.hip, walk_tok) ------------------------------------------------
+ * count pass -> exclusive scan of the counts by one workgroup -> ONE wait for the total -> allocation -> emit pass.  The counts
+ * are scanned in place: d_off is count[m] first, tok_off[m + 1] afterwards (the total lands in its last entry). */
+struct __attribute__((visibility("hidden"))) fsm_hip_tokens : RunObject<3> {   /* the count pass, the scan, the emit pass */
+	size_t total = 0;
+	DevBuf<uint64_t> d_off;                  /* m + 1 */
+	DevBuf<uint64_t> d_err;                  /* m */
+	DevBuf<uint64_t> d_end;                  /* total */
+	DevBuf<uint32_t> d_id;                   /* total */
+};
+
+extern "C" void fsm_hip_tokens_free(struct fsm_hip_tokens *tk) { run_free(tk); }
+
 /* the passes on stream s into *tk, the image's device current; r: the inputs (its outputs are set here) */
 static int tokens_passes(struct fsm_hip_tokens *tk, const struct fsm_hip_tok_dfa *td, fsmhip::TokRun r, hipStream_t s)
 {
-	const uint64_t m = r.m;
+	const uint64_t m = r.in.m;
 	uint64_t total = 0;
-	for (DevEvent &ev : tk->ev)
-		if (!HIP_OK(ev.create())) return -1;
 	if (!HIP_OK(tk->d_off.alloc(m + 1u))) return -1;
 	if (m != 0 && !HIP_OK(tk->d_err.alloc(m))) return -1;
 	r.count = tk->d_off;
 	r.err = tk->d_err;
-	if (!HIP_OK(hipEventRecord(tk->ev[0], s))) return -1;
+	if (!tk->begin(0, s)) return -1;
 	if (m != 0 && fsmhip::tok_launch(td, r, false, s) != 0) return -1;
-	if (!HIP_OK(hipEventRecord(tk->ev[1], s)) || !HIP_OK(hipEventRecord(tk->ev[2], s))) return -1;
-	if (m != 0) {
-		hipLaunchKernelGGL(tokens_scan, dim3(1), dim3(1024), 0, s, tk->d_off.p, m);
-		if (!HIP_OK(hipGetLastError())) return -1;
-	} else if (!HIP_OK(hipMemsetAsync(tk->d_off, 0, sizeof(uint64_t), s))) {
-		return -1;
-	}
-	if (!HIP_OK(hipEventRecord(tk->ev[3], s))) return -1;
-	if (m != 0) {   /* the one wait: the total sizes the arrays */
-		if (!HIP_OK(hipMemcpyAsync(&total, tk->d_off + m, sizeof total, hipMemcpyDeviceToHost, s))) return -1;
-		if (!HIP_OK(hipStreamSynchronize(s))) return -1;
-	}
+	if (!tk->end(0, s) || !tk->begin(1, s)) return -1;
+	if (scan_total(tk->d_off, m, tk->ev[3], s, &total) != 0) return -1;   /* the total sizes the arrays */
 	tk->total = (size_t)total;
 	if (total != 0 && (!HIP_OK(tk->d_end.alloc(total)) || !HIP_OK(tk->d_id.alloc(total)))) return -1;
-	if (!HIP_OK(hipEventRecord(tk->ev[4], s))) return -1;
+	if (!tk->begin(2, s)) return -1;
 	if (total != 0) {
 		r.tok_off = tk->d_off;
 		r.end_out = tk->d_end;
 		r.id_out = tk->d_id;
 		if (fsmhip::tok_launch(td, r, true, s) != 0) return -1;
 	}
-	return HIP_OK(hipEventRecord(tk->ev[5], s)) ? 0 : -1;
+	return tk->end(2, s) ? 0 : -1;
 }
 
-/* the tokens object of a run on stream s; when the run fails, the stream is made idle before what it has launched on is released */
-static struct fsm_hip_tokens *tokens_new(const struct fsm_hip_tok_dfa *td, const fsmhip::TokRun &r, hipStream_t s)
-{
-	if ((r.m + fsmhip::TOK_THREADS - 1u) / fsmhip::TOK_THREADS > 0x7fffffffu) { errno = ENOMEM; return nullptr; }
-	struct fsm_hip_tokens *tk = new (std::nothrow) struct fsm_hip_tokens;
-	if (tk == nullptr) { errno = ENOMEM; return nullptr; }
-	tk->device = fsmhip::tok_dfa_device(td);
-	tk->m = (size_t)r.m;
-	if (tokens_passes(tk, td, r, s) == 0) return tk;
-	const int e = errno;
-	(void)hipStreamSynchronize(s);
-	fsm_hip_tokens_free(tk);
-	errno = e;
-	return nullptr;
-}
-
-/* the arguments both forms refuse alike; *m: the inputs */
-static int tokens_check(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *b, uint64_t *m)
-{
-	if (!have_device()) { errno = ENODEV; return -1; }
-	if (td == nullptr || b == nullptr || (b->flags & ~(FSM_HIP_TOKENS_NO_BACKTRACK | FSM_HIP_TOKENS_SKIP_BAD)) != 0u || b->trim_byte < -1 ||
-	    b->trim_byte > 255) {
-		errno = EINVAL;
-		return -1;
-	}
-	*m = b->pick != nullptr ? (uint64_t)b->m : (uint64_t)b->n;
-	if (*m != 0 && b->off == nullptr) { errno = EINVAL; return -1; }
-	return 0;
-}
-
-static fsmhip::TokRun tokens_run_of(const struct fsm_hip_tok_batch *b, uint64_t m)
+static struct fsm_hip_tokens *tokens_new(const struct fsm_hip_tok_dfa *td, const fsmhip::LineBatch &in, hipStream_t s)
 {
 	fsmhip::TokRun r;
-	r.base = b->base;
-	r.off = b->off;
-	r.pick = b->pick;
-	r.n = b->n;
-	r.m = m;
-	r.limit = b->limit;
-	r.has_limit = b->limit != 0u || b->base == nullptr;   /* no text: no byte may be read */
-	r.trim = b->trim_byte;
-	r.flags = b->flags;
-	return r;
+	r.in = in;
+	return run_new<struct fsm_hip_tokens>(fsmhip::tok_dfa_device(td), in.m, (in.m + fsmhip::TOK_THREADS - 1u) / fsmhip::TOK_THREADS <= 0x7fffffffu, s,
+	                                      [&](struct fsm_hip_tokens *tk) { return tokens_passes(tk, td, r, s); });
+}
+
+/* the arguments both forms refuse alike; *in: the batch as given */
+static bool tokens_check(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *b, fsmhip::LineBatch *in)
+{
+	if (!have_device()) { errno = ENODEV; return false; }
+	if (td == nullptr) { errno = EINVAL; return false; }
+	return fsmhip::batch_shape(b, FSM_HIP_TOKENS_NO_BACKTRACK | FSM_HIP_TOKENS_SKIP_BAD, in);
 }
 
 extern "C" struct fsm_hip_tokens *fsm_hip_tokens_run_device(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *b, void *hip_stream)
 {
-	uint64_t m = 0;
-	if (tokens_check(td, b, &m) != 0) return nullptr;
-	if (b->base == nullptr && b->limit != 0u) { errno = EINVAL; return nullptr; }
+	fsmhip::LineBatch in;
+	if (!tokens_check(td, b, &in) || !fsmhip::batch_device_ok(in)) return nullptr;
 	DevGuard dg(fsmhip::tok_dfa_device(td));
 	if (!dg.ok()) { errno = ENODEV; return nullptr; }
-	return tokens_new(td, tokens_run_of(b, m), static_cast<hipStream_t>(hip_stream));
+	return tokens_new(td, in, static_cast<hipStream_t>(hip_stream));
 }
 
 extern "C" struct fsm_hip_tokens *fsm_hip_tokens_run(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *b)
 {
-	uint64_t m = 0;
-	if (tokens_check(td, b, &m) != 0) return nullptr;
-	const uint64_t n = b->n;
-	if (m != 0) {
-		for (uint64_t i = 0; i < n; i++)
-			if (b->off[i] > b->off[i + 1u]) { errno = EINVAL; return nullptr; }
-		if (b->base == nullptr && b->off[n] != 0u) { errno = EINVAL; return nullptr; }
-		if (b->pick != nullptr)
-			for (uint64_t j = 0; j < m; j++)
-				if (b->pick[j] >= n) { errno = EINVAL; return nullptr; }
-	}
-	DevGuard dg(fsmhip::tok_dfa_device(td));
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
-	DevStream own;                                   /* never the NULL stream */
-	if (!HIP_OK(own.create(hipStreamNonBlocking))) return nullptr;
-	hipStream_t s = own;
-	fsmhip::TokRun r = tokens_run_of(b, m);
-	DevBuf<unsigned char> d;                         /* everything staged in one allocation, each piece at a multiple of 16 bytes */
-	if (m != 0) {
-		auto up16 = [](uint64_t x) { return (x + 15u) & ~(uint64_t)15u; };
-		const uint64_t nbytes = b->off[n], n_off = (n + 1u) * 8u, n_m = m * 8u;
-		const uint64_t at_off = up16(nbytes), at_pick = at_off + up16(n_off), all = at_pick + (b->pick ? up16(n_m) : 0u);
-		if (!HIP_OK(d.alloc(all))) return nullptr;
-		bool ok = nbytes == 0 || HIP_OK(hipMemcpyAsync(d, b->base, nbytes, hipMemcpyHostToDevice, s));
-		ok = ok && HIP_OK(hipMemcpyAsync(d + at_off, b->off, n_off, hipMemcpyHostToDevice, s));
-		ok = ok && (b->pick == nullptr || HIP_OK(hipMemcpyAsync(d + at_pick, b->pick, n_m, hipMemcpyHostToDevice, s)));
-		if (!ok) {   /* the stream idle before the staging memory goes */
-			const int e = errno;
-			(void)hipStreamSynchronize(s);
-			errno = e;
-			return nullptr;
-		}
-		r.base = nbytes != 0 ? d.p : nullptr;
-		r.limit = nbytes;
-		r.has_limit = true;
-		r.off = (const uint64_t *)(d + at_off);
-		r.pick = b->pick ? (const uint64_t *)(d + at_pick) : nullptr;
-	}
-	struct fsm_hip_tokens *tk = tokens_new(td, r, s);
-	if (tk == nullptr) return nullptr;               /* (tokens_new left the stream idle) */
-	if (!HIP_OK(hipStreamSynchronize(s))) {          /* the emit pass has read the staged text */
-		const int e = errno;
-		fsm_hip_tokens_free(tk);
-		errno = e;
-		return nullptr;
-	}
-	return tk;
+	fsmhip::LineBatch host;
+	if (!tokens_check(td, b, &host) || !fsmhip::batch_host_arrays_ok(host)) return nullptr;
+	return run_host(fsmhip::tok_dfa_device(td), host, [&](const fsmhip::LineBatch &in, hipStream_t s) { return tokens_new(td, in, s); });
 }
 
 extern "C" struct fsm_hip_tokens *fsm_hip_text_tokens(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_text *t, const struct fsm_hip_text_hits *h,
@@ -1820,23 +1845,12 @@ extern "C" struct fsm_hip_tokens *fsm_hip_text_tokens(const struct fsm_hip_tok_d
 {
 	if (!have_device()) { errno = ENODEV; return nullptr; }
 	if (td == nullptr || t == nullptr || (flags & ~(FSM_HIP_TOKENS_NO_BACKTRACK | FSM_HIP_TOKENS_SKIP_BAD)) != 0u) { errno = EINVAL; return nullptr; }
-	if (fsmhip::tok_dfa_device(td) != t->device || (h != nullptr && h->device != t->device)) { errno = EINVAL; return nullptr; }
-	DevGuard dg(t->device);
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
 	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	/* the hits' lines (and, behind them, the text's offsets) first */
-	if (!HIP_OK(hipStreamWaitEvent(s, h != nullptr ? h->ev[5] : t->ev[3], 0))) return nullptr;
-	fsmhip::TokRun r;
-	r.base = t->d_text;
-	r.off = t->d_off;
-	r.n = t->n;
-	r.pick = h != nullptr ? h->d_lines.p : nullptr;
-	r.m = h != nullptr ? h->m : t->n;
-	r.limit = t->nbytes;
-	r.has_limit = true;
-	r.trim = t->delim;
-	r.flags = flags;
-	return tokens_new(td, r, s);
+	std::optional<DevGuard> dg;
+	fsmhip::LineBatch in;
+	if (!text_batch(t, h, {fsmhip::tok_dfa_device(td)}, s, &dg, &in)) return nullptr;
+	in.flags = flags;
+	return tokens_new(td, in, s);
 }
 
 extern "C" size_t fsm_hip_tokens_count(const struct fsm_hip_tokens *tk) { return tk == nullptr ? 0 : tk->m; }
@@ -1849,79 +1863,46 @@ extern "C" const uint64_t *fsm_hip_tokens_err_device(const struct fsm_hip_tokens
 extern "C" int fsm_hip_tokens_copy(const struct fsm_hip_tokens *tk, uint64_t *off, uint64_t *end, uint32_t *id, uint64_t *err)
 {
 	if (tk == nullptr) { errno = EINVAL; return -1; }
-	return copy_out(tk->device, tk->ev[5], {{off, tk->d_off, (tk->m + 1u) * sizeof(uint64_t)}, {end, tk->d_end, tk->total * sizeof(uint64_t)},
-	                                        {id, tk->d_id, tk->total * sizeof(uint32_t)}, {err, tk->d_err, tk->m * sizeof(uint64_t)}});
+	return copy_out(tk->device, tk->done(), {{off, tk->d_off, (tk->m + 1u) * sizeof(uint64_t)}, {end, tk->d_end, tk->total * sizeof(uint64_t)},
+	                                         {id, tk->d_id, tk->total * sizeof(uint32_t)}, {err, tk->d_err, tk->m * sizeof(uint64_t)}});
 }
 
-extern "C" double fsm_hip_tokens_ms(const struct fsm_hip_tokens *tk)
-{
-	if (tk == nullptr) { errno = EINVAL; return -1.0; }
-	return elapsed_ms(tk->device, tk->ev[5], {{tk->ev[0], tk->ev[1]}, {tk->ev[2], tk->ev[3]}, {tk->ev[4], tk->ev[5]}});
-}
-
-extern "C" double fsm_hip_tokens_pass_ms(const struct fsm_hip_tokens *tk, int pass)
-{
-	if (tk == nullptr || pass < 0 || pass > 2) { errno = EINVAL; return -1.0; }
-	return elapsed_ms(tk->device, tk->ev[5], {{tk->ev[2 * pass], tk->ev[2 * pass + 1]}});
-}
+extern "C" double fsm_hip_tokens_ms(const struct fsm_hip_tokens *tk) { return run_ms(tk, 0, 2); }
+extern "C" double fsm_hip_tokens_pass_ms(const struct fsm_hip_tokens *tk, int pass) { return run_ms(tk, pass, pass); }
 
 /* ---- matches: every match of every line (match.hip, walk_mark / walk_match) -------------------------------------------------
  * marks pass -> count pass -> exclusive scan of the counts by one workgroup -> ONE wait for the total -> allocation -> emit
  * pass.  The counts are scanned in place, as the tokens' are: d_off is count[m] first, match_off[m + 1] afterwards. */
-struct __attribute__((visibility("hidden"))) fsm_hip_matches {
-	int device = 0;
-	size_t m = 0, total = 0;
+struct __attribute__((visibility("hidden"))) fsm_hip_matches : RunObject<4> {   /* the marks pass, the count pass, the scan, the emit pass */
+	size_t total = 0;
 	DevBuf<uint16_t> d_marks;                /* marks_words(limit, n): internal */
 	DevBuf<uint64_t> d_off;                  /* m + 1 */
 	DevBuf<uint64_t> d_start, d_end;         /* total each */
 	DevBuf<uint32_t> d_id;                   /* total */
-	DevEvent ev[8];                          /* around the marks pass, the count pass, the scan, the emit pass; ev[7]: all is there */
 };
 
-extern "C" void fsm_hip_matches_free(struct fsm_hip_matches *mt)
-{
-	if (mt == nullptr) return;
-	const int e = errno;
-	{
-		DevGuard dg(mt->device);
-		if (mt->ev[7] != nullptr) (void)hipEventSynchronize(mt->ev[7]);
-		delete mt;
-	}
-	errno = e;
-}
+extern "C" void fsm_hip_matches_free(struct fsm_hip_matches *mt) { run_free(mt); }
 
-/* the passes on stream s into *mt, the images' device current; r: the inputs, its limit given (its outputs are set here) */
+/* the passes on stream s into *mt, the images' device current; r: the inputs, their limit given (its outputs are set here) */
 static int matches_passes(struct fsm_hip_matches *mt, const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, fsmhip::MatchRun r,
 	hipStream_t s)
 {
-	const uint64_t m = r.m;
+	const uint64_t m = r.in.m;
 	uint64_t total = 0;
-	for (DevEvent &ev : mt->ev)
-		if (!HIP_OK(ev.create())) return -1;
 	if (!HIP_OK(mt->d_off.alloc(m + 1u))) return -1;
-	r.nwords = fsmhip::marks_words(r.limit, r.n);
+	r.nwords = fsmhip::marks_words(r.in.limit, r.in.n);
 	if (m != 0 && !HIP_OK(mt->d_marks.alloc(r.nwords))) return -1;
 	r.marks = mt->d_marks;
 	r.count = mt->d_off;
-	if (!HIP_OK(hipEventRecord(mt->ev[0], s))) return -1;
+	if (!mt->begin(0, s)) return -1;
 	if (m != 0 && fsmhip::match_launch_mark(starts, r, s) != 0) return -1;
-	if (!HIP_OK(hipEventRecord(mt->ev[1], s)) || !HIP_OK(hipEventRecord(mt->ev[2], s))) return -1;
+	if (!mt->end(0, s) || !mt->begin(1, s)) return -1;
 	if (m != 0 && fsmhip::match_launch(ends, r, false, s) != 0) return -1;
-	if (!HIP_OK(hipEventRecord(mt->ev[3], s)) || !HIP_OK(hipEventRecord(mt->ev[4], s))) return -1;
-	if (m != 0) {
-		hipLaunchKernelGGL(tokens_scan, dim3(1), dim3(1024), 0, s, mt->d_off.p, m);
-		if (!HIP_OK(hipGetLastError())) return -1;
-	} else if (!HIP_OK(hipMemsetAsync(mt->d_off, 0, sizeof(uint64_t), s))) {
-		return -1;
-	}
-	if (!HIP_OK(hipEventRecord(mt->ev[5], s))) return -1;
-	if (m != 0) {   /* the one wait: the total sizes the arrays */
-		if (!HIP_OK(hipMemcpyAsync(&total, mt->d_off + m, sizeof total, hipMemcpyDeviceToHost, s))) return -1;
-		if (!HIP_OK(hipStreamSynchronize(s))) return -1;
-	}
+	if (!mt->end(1, s) || !mt->begin(2, s)) return -1;
+	if (scan_total(mt->d_off, m, mt->ev[5], s, &total) != 0) return -1;   /* the total sizes the arrays */
 	mt->total = (size_t)total;
 	if (total != 0 && (!HIP_OK(mt->d_start.alloc(total)) || !HIP_OK(mt->d_end.alloc(total)) || !HIP_OK(mt->d_id.alloc(total)))) return -1;
-	if (!HIP_OK(hipEventRecord(mt->ev[6], s))) return -1;
+	if (!mt->begin(3, s)) return -1;
 	if (total != 0) {
 		r.match_off = mt->d_off;
 		r.start_out = mt->d_start;
@@ -1929,123 +1910,45 @@ static int matches_passes(struct fsm_hip_matches *mt, const struct fsm_hip_pos_d
 		r.id_out = mt->d_id;
 		if (fsmhip::match_launch(ends, r, true, s) != 0) return -1;
 	}
-	return HIP_OK(hipEventRecord(mt->ev[7], s)) ? 0 : -1;
+	return mt->end(3, s) ? 0 : -1;
 }
 
-/* the matches object of a run on stream s; when the run fails, the stream is made idle before what it has launched on is released */
-static struct fsm_hip_matches *matches_new(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, const fsmhip::MatchRun &r,
+static struct fsm_hip_matches *matches_new(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, const fsmhip::LineBatch &in,
 	hipStream_t s)
 {
-	if (!fsmhip::match_grid_fits(r.m)) { errno = ENOMEM; return nullptr; }
-	struct fsm_hip_matches *mt = new (std::nothrow) struct fsm_hip_matches;
-	if (mt == nullptr) { errno = ENOMEM; return nullptr; }
-	mt->device = fsmhip::tok_dfa_device(ends);
-	mt->m = (size_t)r.m;
-	if (matches_passes(mt, starts, ends, r, s) == 0) return mt;
-	const int e = errno;
-	(void)hipStreamSynchronize(s);
-	fsm_hip_matches_free(mt);
-	errno = e;
-	return nullptr;
-}
-
-/* the arguments both forms refuse alike; *m: the inputs */
-static int matches_check(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, const struct fsm_hip_match_batch *b, uint64_t *m)
-{
-	if (!have_device()) { errno = ENODEV; return -1; }
-	if (starts == nullptr || ends == nullptr || b == nullptr || (b->flags & ~FSM_HIP_MATCHES_DROP_EMPTY) != 0u || b->trim_byte < -1 ||
-	    b->trim_byte > 255) {
-		errno = EINVAL;
-		return -1;
-	}
-	if (fsmhip::pos_dfa_device(starts) != fsmhip::tok_dfa_device(ends)) { errno = EINVAL; return -1; }
-	*m = b->pick != nullptr ? (uint64_t)b->m : (uint64_t)b->n;
-	if (*m != 0 && b->off == nullptr) { errno = EINVAL; return -1; }
-	return 0;
-}
-
-static fsmhip::MatchRun matches_run_of(const struct fsm_hip_match_batch *b, uint64_t m)
-{
 	fsmhip::MatchRun r;
-	r.base = b->base;
-	r.off = b->off;
-	r.pick = b->pick;
-	r.n = b->n;
-	r.m = m;
-	r.limit = b->limit;
-	r.trim = b->trim_byte;
-	r.flags = b->flags;
-	return r;
+	r.in = in;
+	return run_new<struct fsm_hip_matches>(fsmhip::tok_dfa_device(ends), in.m, fsmhip::match_grid_fits(in.m), s,
+	                                       [&](struct fsm_hip_matches *mt) { return matches_passes(mt, starts, ends, r, s); });
+}
+
+/* the arguments both forms refuse alike; *in: the batch as given */
+static bool matches_check(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, const struct fsm_hip_match_batch *b,
+	fsmhip::LineBatch *in)
+{
+	if (!have_device()) { errno = ENODEV; return false; }
+	if (starts == nullptr || ends == nullptr || fsmhip::pos_dfa_device(starts) != fsmhip::tok_dfa_device(ends)) { errno = EINVAL; return false; }
+	return fsmhip::batch_shape(b, FSM_HIP_MATCHES_DROP_EMPTY, in);
 }
 
 extern "C" struct fsm_hip_matches *fsm_hip_matches_run_device(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
 	const struct fsm_hip_match_batch *b, void *hip_stream)
 {
-	uint64_t m = 0;
-	if (matches_check(starts, ends, b, &m) != 0) return nullptr;
-	if (b->base == nullptr && b->limit != 0u) { errno = EINVAL; return nullptr; }
+	fsmhip::LineBatch in;
+	if (!matches_check(starts, ends, b, &in) || !fsmhip::batch_device_ok(in)) return nullptr;
 	DevGuard dg(fsmhip::tok_dfa_device(ends));
 	if (!dg.ok()) { errno = ENODEV; return nullptr; }
 	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	fsmhip::MatchRun r = matches_run_of(b, m);
-	if (m != 0 && b->limit == 0u && b->base != nullptr) {   /* the marks are sized by the limit: off[n], a short wait of its own */
-		uint64_t last = 0;
-		if (!HIP_OK(hipMemcpyAsync(&last, b->off + b->n, sizeof last, hipMemcpyDeviceToHost, s)) || !HIP_OK(hipStreamSynchronize(s))) return nullptr;
-		r.limit = last;
-	}
-	return matches_new(starts, ends, r, s);
+	if (!fsmhip::batch_read_limit(&in, s)) return nullptr;   /* the marks are sized by the limit */
+	return matches_new(starts, ends, in, s);
 }
 
 extern "C" struct fsm_hip_matches *fsm_hip_matches_run(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
 	const struct fsm_hip_match_batch *b)
 {
-	uint64_t m = 0;
-	if (matches_check(starts, ends, b, &m) != 0) return nullptr;
-	const uint64_t n = b->n;
-	if (m != 0) {
-		for (uint64_t i = 0; i < n; i++)
-			if (b->off[i] > b->off[i + 1u]) { errno = EINVAL; return nullptr; }
-		if (b->base == nullptr && b->off[n] != 0u) { errno = EINVAL; return nullptr; }
-		if (b->pick != nullptr)
-			for (uint64_t j = 0; j < m; j++)
-				if (b->pick[j] >= n) { errno = EINVAL; return nullptr; }
-	}
-	DevGuard dg(fsmhip::tok_dfa_device(ends));
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
-	DevStream own;                                   /* never the NULL stream */
-	if (!HIP_OK(own.create(hipStreamNonBlocking))) return nullptr;
-	hipStream_t s = own;
-	fsmhip::MatchRun r = matches_run_of(b, m);
-	r.limit = 0;
-	DevBuf<unsigned char> d;                         /* everything staged in one allocation, each piece at a multiple of 16 bytes */
-	if (m != 0) {
-		auto up16 = [](uint64_t x) { return (x + 15u) & ~(uint64_t)15u; };
-		const uint64_t nbytes = b->off[n], n_off = (n + 1u) * 8u, n_m = m * 8u;
-		const uint64_t at_off = up16(nbytes), at_pick = at_off + up16(n_off), all = at_pick + (b->pick ? up16(n_m) : 0u);
-		if (!HIP_OK(d.alloc(all))) return nullptr;
-		bool ok = nbytes == 0 || HIP_OK(hipMemcpyAsync(d, b->base, nbytes, hipMemcpyHostToDevice, s));
-		ok = ok && HIP_OK(hipMemcpyAsync(d + at_off, b->off, n_off, hipMemcpyHostToDevice, s));
-		ok = ok && (b->pick == nullptr || HIP_OK(hipMemcpyAsync(d + at_pick, b->pick, n_m, hipMemcpyHostToDevice, s)));
-		if (!ok) {   /* the stream idle before the staging memory goes */
-			const int e = errno;
-			(void)hipStreamSynchronize(s);
-			errno = e;
-			return nullptr;
-		}
-		r.base = nbytes != 0 ? d.p : nullptr;
-		r.limit = nbytes;
-		r.off = (const uint64_t *)(d + at_off);
-		r.pick = b->pick ? (const uint64_t *)(d + at_pick) : nullptr;
-	}
-	struct fsm_hip_matches *mt = matches_new(starts, ends, r, s);
-	if (mt == nullptr) return nullptr;               /* (matches_new left the stream idle) */
-	if (!HIP_OK(hipStreamSynchronize(s))) {          /* the emit pass has read the staged text */
-		const int e = errno;
-		fsm_hip_matches_free(mt);
-		errno = e;
-		return nullptr;
-	}
-	return mt;
+	fsmhip::LineBatch host;
+	if (!matches_check(starts, ends, b, &host) || !fsmhip::batch_host_arrays_ok(host)) return nullptr;
+	return run_host(fsmhip::tok_dfa_device(ends), host, [&](const fsmhip::LineBatch &in, hipStream_t s) { return matches_new(starts, ends, in, s); });
 }
 
 extern "C" struct fsm_hip_matches *fsm_hip_text_matches(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
@@ -2053,25 +1956,12 @@ extern "C" struct fsm_hip_matches *fsm_hip_text_matches(const struct fsm_hip_pos
 {
 	if (!have_device()) { errno = ENODEV; return nullptr; }
 	if (starts == nullptr || ends == nullptr || t == nullptr || (flags & ~FSM_HIP_MATCHES_DROP_EMPTY) != 0u) { errno = EINVAL; return nullptr; }
-	if (fsmhip::pos_dfa_device(starts) != t->device || fsmhip::tok_dfa_device(ends) != t->device || (h != nullptr && h->device != t->device)) {
-		errno = EINVAL;
-		return nullptr;
-	}
-	DevGuard dg(t->device);
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
 	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	/* the hits' lines (and, behind them, the text's offsets) first */
-	if (!HIP_OK(hipStreamWaitEvent(s, h != nullptr ? h->ev[5] : t->ev[3], 0))) return nullptr;
-	fsmhip::MatchRun r;
-	r.base = t->d_text;
-	r.off = t->d_off;
-	r.n = t->n;
-	r.pick = h != nullptr ? h->d_lines.p : nullptr;
-	r.m = h != nullptr ? h->m : t->n;
-	r.limit = t->nbytes;
-	r.trim = t->delim;
-	r.flags = flags;
-	return matches_new(starts, ends, r, s);
+	std::optional<DevGuard> dg;
+	fsmhip::LineBatch in;
+	if (!text_batch(t, h, {fsmhip::pos_dfa_device(starts), fsmhip::tok_dfa_device(ends)}, s, &dg, &in)) return nullptr;
+	in.flags = flags;
+	return matches_new(starts, ends, in, s);
 }
 
 extern "C" size_t fsm_hip_matches_count(const struct fsm_hip_matches *mt) { return mt == nullptr ? 0 : mt->m; }
@@ -2084,21 +1974,12 @@ extern "C" const uint32_t *fsm_hip_matches_id_device(const struct fsm_hip_matche
 extern "C" int fsm_hip_matches_copy(const struct fsm_hip_matches *mt, uint64_t *off, uint64_t *start, uint64_t *end, uint32_t *id)
 {
 	if (mt == nullptr) { errno = EINVAL; return -1; }
-	return copy_out(mt->device, mt->ev[7], {{off, mt->d_off, (mt->m + 1u) * sizeof(uint64_t)}, {start, mt->d_start, mt->total * sizeof(uint64_t)},
-	                                        {end, mt->d_end, mt->total * sizeof(uint64_t)}, {id, mt->d_id, mt->total * sizeof(uint32_t)}});
+	return copy_out(mt->device, mt->done(), {{off, mt->d_off, (mt->m + 1u) * sizeof(uint64_t)}, {start, mt->d_start, mt->total * sizeof(uint64_t)},
+	                                         {end, mt->d_end, mt->total * sizeof(uint64_t)}, {id, mt->d_id, mt->total * sizeof(uint32_t)}});
 }
 
-extern "C" double fsm_hip_matches_ms(const struct fsm_hip_matches *mt)
-{
-	if (mt == nullptr) { errno = EINVAL; return -1.0; }
-	return elapsed_ms(mt->device, mt->ev[7], {{mt->ev[0], mt->ev[1]}, {mt->ev[2], mt->ev[3]}, {mt->ev[4], mt->ev[5]}, {mt->ev[6], mt->ev[7]}});
-}
-
-extern "C" double fsm_hip_matches_pass_ms(const struct fsm_hip_matches *mt, int pass)
-{
-	if (mt == nullptr || pass < 0 || pass > 3) { errno = EINVAL; return -1.0; }
-	return elapsed_ms(mt->device, mt->ev[7], {{mt->ev[2 * pass], mt->ev[2 * pass + 1]}});
-}
+extern "C" double fsm_hip_matches_ms(const struct fsm_hip_matches *mt) { return run_ms(mt, 0, 3); }
+extern "C" double fsm_hip_matches_pass_ms(const struct fsm_hip_matches *mt, int pass) { return run_ms(mt, pass, pass); }
 
 /* ---- replace: every match replaced by its rule's replacement, a fresh packed text (replace.hip) --------------------------------
  * lengths pass (per input, per match, per block of REPL_LINES inputs) -> exclusive scan of the BLOCK sums by one workgroup -> ONE
@@ -2106,18 +1987,6 @@ extern "C" double fsm_hip_matches_pass_ms(const struct fsm_hip_matches *mt, int 
  * m / REPL_LINES records, not over m: a text of short lines does not pay the one-workgroup scan per line that the tokens and
  * the matches pay.  first[] has an entry per block of the output, so the offsets pass that fills it follows the wait; it and the
  * write pass are in flight at return. */
-namespace {
-
-constexpr uint32_t REPL_SCAN_PER = 4;                       /* sums a thread of the scan takes a round: 4 096 blocks, 1 Mi inputs */
-
-__global__ void __launch_bounds__(1024)
-repl_scan(uint64_t *sums, uint64_t nblocks)
-{
-	sum_scan<1024, 1, REPL_SCAN_PER>(sums, nblocks, sums + nblocks);
-}
-
-}   // namespace
-
 struct __attribute__((visibility("hidden"))) fsm_hip_repl {
 	int device = 0;
 	size_t nrepl = 0;
@@ -2171,37 +2040,22 @@ extern "C" size_t fsm_hip_repl_lds_rules(void) { return fsmhip::REPL_LDS_RULES; 
 extern "C" size_t fsm_hip_replaced_block_lines(void) { return fsmhip::REPL_LINES; }
 extern "C" size_t fsm_hip_replaced_block_bytes(void) { return fsmhip::REPL_BLOCK; }
 
-struct __attribute__((visibility("hidden"))) fsm_hip_replaced {
-	int device = 0;
-	size_t m = 0;
+struct __attribute__((visibility("hidden"))) fsm_hip_replaced : RunObject<4> {   /* the lengths, the scan, the offsets, the write pass */
 	uint64_t nbytes = 0;
 	DevBuf<uint64_t> d_off;                  /* m + 1 */
 	DevBuf<uint64_t> d_mpos, d_xlen;         /* one per match: internal */
 	DevBuf<uint64_t> d_sums;                 /* per block of inputs, + the total: internal */
 	DevBuf<uint64_t> d_first;                /* per block of the output, + 1: internal */
 	DevBuf<unsigned char> d_bytes;           /* nbytes, in whole blocks */
-	DevEvent ev[8];                          /* around the lengths, the scan, the offsets, the write pass; ev[7]: all is there */
 };
 
-extern "C" void fsm_hip_replaced_free(struct fsm_hip_replaced *r)
-{
-	if (r == nullptr) return;
-	const int e = errno;
-	{
-		DevGuard dg(r->device);
-		if (r->ev[7] != nullptr) (void)hipEventSynchronize(r->ev[7]);
-		delete r;
-	}
-	errno = e;
-}
+extern "C" void fsm_hip_replaced_free(struct fsm_hip_replaced *r) { run_free(r); }
 
 /* the passes on stream s into *rd, the objects' device current; r: the batch, the matches and the table (its outputs are set here) */
 static int replaced_passes(struct fsm_hip_replaced *rd, fsmhip::ReplRun r, hipStream_t s)
 {
 	const uint64_t m = r.m, nblocks = (m + fsmhip::REPL_LINES - 1u) / fsmhip::REPL_LINES;
 	uint64_t total = 0;
-	for (DevEvent &ev : rd->ev)
-		if (!HIP_OK(ev.create())) return -1;
 	if (!HIP_OK(rd->d_off.alloc(m + 1u))) return -1;
 	if (m != 0 && !HIP_OK(rd->d_sums.alloc(nblocks + 1u))) return -1;
 	if (m != 0 && r.nmatch != 0 && (!HIP_OK(rd->d_mpos.alloc(r.nmatch)) || !HIP_OK(rd->d_xlen.alloc(r.nmatch)))) return -1;
@@ -2209,20 +2063,11 @@ static int replaced_passes(struct fsm_hip_replaced *rd, fsmhip::ReplRun r, hipSt
 	r.sums = rd->d_sums;
 	r.mpos = rd->d_mpos;
 	r.xlen = rd->d_xlen;
-	if (!HIP_OK(hipEventRecord(rd->ev[0], s))) return -1;
+	if (!rd->begin(0, s)) return -1;
 	if (fsmhip::repl_launch_lengths(r, s) != 0) return -1;
-	if (!HIP_OK(hipEventRecord(rd->ev[1], s)) || !HIP_OK(hipEventRecord(rd->ev[2], s))) return -1;
-	if (m != 0) {
-		hipLaunchKernelGGL(repl_scan, dim3(1), dim3(1024), 0, s, rd->d_sums.p, nblocks);
-		if (!HIP_OK(hipGetLastError())) return -1;
-	} else if (!HIP_OK(hipMemsetAsync(rd->d_off, 0, sizeof(uint64_t), s))) {
-		return -1;
-	}
-	if (!HIP_OK(hipEventRecord(rd->ev[3], s))) return -1;
-	if (m != 0) {   /* the one wait: the total sizes the bytes and first[] */
-		if (!HIP_OK(hipMemcpyAsync(&total, rd->d_sums + nblocks, sizeof total, hipMemcpyDeviceToHost, s))) return -1;
-		if (!HIP_OK(hipStreamSynchronize(s))) return -1;
-	}
+	if (!rd->end(0, s) || !rd->begin(1, s)) return -1;
+	/* the total sizes the bytes and first[]; without inputs there are no sums, and out_off[0] is cleared */
+	if (scan_total(m != 0 ? rd->d_sums.p : rd->d_off.p, nblocks, rd->ev[3], s, &total) != 0) return -1;
 	rd->nbytes = total;
 	r.total = total;
 	r.ngb = (total + fsmhip::REPL_BLOCK - 1u) / fsmhip::REPL_BLOCK;
@@ -2232,21 +2077,22 @@ static int replaced_passes(struct fsm_hip_replaced *rd, fsmhip::ReplRun r, hipSt
 	const Grid g = grid_of(r.ngb, rd->device);
 	r.wgs = g.wgs;
 	r.per = g.per;
-	if (!HIP_OK(hipEventRecord(rd->ev[4], s))) return -1;
+	if (!rd->begin(2, s)) return -1;
 	if (fsmhip::repl_launch_offsets(r, s) != 0) return -1;
-	if (!HIP_OK(hipEventRecord(rd->ev[5], s)) || !HIP_OK(hipEventRecord(rd->ev[6], s))) return -1;
+	if (!rd->end(2, s) || !rd->begin(3, s)) return -1;
 	if (fsmhip::repl_launch_write(r, s) != 0) return -1;
-	return HIP_OK(hipEventRecord(rd->ev[7], s)) ? 0 : -1;
+	return rd->end(3, s) ? 0 : -1;
 }
 
-/* the replaced object of a run on stream s; when the run fails, the stream is made idle before what it has launched on is released */
-static struct fsm_hip_replaced *replaced_new(const struct fsm_hip_matches *mt, const struct fsm_hip_repl *rp, fsmhip::ReplRun r, hipStream_t s)
+static struct fsm_hip_replaced *replaced_new(const struct fsm_hip_matches *mt, const struct fsm_hip_repl *rp, const fsmhip::LineBatch &in, hipStream_t s)
 {
-	if (!fsmhip::repl_grid_fits(r.m)) { errno = ENOMEM; return nullptr; }
-	struct fsm_hip_replaced *rd = new (std::nothrow) struct fsm_hip_replaced;
-	if (rd == nullptr) { errno = ENOMEM; return nullptr; }
-	rd->device = mt->device;
-	rd->m = (size_t)r.m;
+	fsmhip::ReplRun r;
+	r.base = in.base;
+	r.off = in.off;
+	r.pick = in.pick;
+	r.n = in.n;
+	r.m = in.m;
+	r.limit = in.limit;
 	r.moff = mt->d_off;
 	r.start = mt->d_start;
 	r.end = mt->d_end;
@@ -2258,126 +2104,51 @@ static struct fsm_hip_replaced *replaced_new(const struct fsm_hip_matches *mt, c
 	r.rbytes = rp->rbytes;
 	r.flags = rp->flags;
 	r.table_in_lds = rp->in_lds;
-	if (HIP_OK(hipStreamWaitEvent(s, mt->ev[7], 0)) && replaced_passes(rd, r, s) == 0) return rd;   /* behind the matches' emit pass */
-	const int e = errno;
-	(void)hipStreamSynchronize(s);
-	fsm_hip_replaced_free(rd);
-	errno = e;
-	return nullptr;
+	return run_new<struct fsm_hip_replaced>(mt->device, in.m, fsmhip::repl_grid_fits(in.m), s, [&](struct fsm_hip_replaced *rd) {
+		return HIP_OK(hipStreamWaitEvent(s, mt->done(), 0)) ? replaced_passes(rd, r, s) : -1;   /* behind the matches' emit pass */
+	});
 }
 
-/* the arguments both forms refuse alike; *m: the inputs */
-static int replaced_check(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b, const struct fsm_hip_repl *rp, uint64_t *m)
+/* the arguments both forms refuse alike; *in: the batch as given, which is the matches' own: it passes what theirs passed */
+static bool replaced_check(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b, const struct fsm_hip_repl *rp, fsmhip::LineBatch *in)
 {
-	if (!have_device()) { errno = ENODEV; return -1; }
-	if (mt == nullptr || b == nullptr || rp == nullptr || rp->device != mt->device) { errno = EINVAL; return -1; }
-	*m = b->pick != nullptr ? (uint64_t)b->m : (uint64_t)b->n;
-	if (*m != (uint64_t)mt->m || (*m != 0 && b->off == nullptr)) { errno = EINVAL; return -1; }
-	return 0;
-}
-
-static fsmhip::ReplRun replaced_run_of(const struct fsm_hip_match_batch *b, uint64_t m)
-{
-	fsmhip::ReplRun r;
-	r.base = b->base;
-	r.off = b->off;
-	r.pick = b->pick;
-	r.n = b->n;
-	r.m = m;
-	r.limit = b->limit;
-	return r;
+	if (!have_device()) { errno = ENODEV; return false; }
+	if (mt == nullptr || rp == nullptr || rp->device != mt->device) { errno = EINVAL; return false; }
+	if (!fsmhip::batch_shape(b, FSM_HIP_MATCHES_DROP_EMPTY, in)) return false;
+	if (in->m != (uint64_t)mt->m) { errno = EINVAL; return false; }
+	return true;
 }
 
 extern "C" struct fsm_hip_replaced *fsm_hip_matches_replace_device(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b,
 	const struct fsm_hip_repl *rp, void *hip_stream)
 {
-	uint64_t m = 0;
-	if (replaced_check(mt, b, rp, &m) != 0) return nullptr;
-	if (b->base == nullptr && b->limit != 0u) { errno = EINVAL; return nullptr; }
+	fsmhip::LineBatch in;
+	if (!replaced_check(mt, b, rp, &in) || !fsmhip::batch_device_ok(in)) return nullptr;
 	DevGuard dg(mt->device);
 	if (!dg.ok()) { errno = ENODEV; return nullptr; }
 	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	fsmhip::ReplRun r = replaced_run_of(b, m);
-	if (m != 0 && b->limit == 0u && b->base != nullptr) {   /* as the matches: limit 0 is off[n], a short wait of its own */
-		uint64_t last = 0;
-		if (!HIP_OK(hipMemcpyAsync(&last, b->off + b->n, sizeof last, hipMemcpyDeviceToHost, s)) || !HIP_OK(hipStreamSynchronize(s))) return nullptr;
-		r.limit = last;
-	}
-	return replaced_new(mt, rp, r, s);
+	if (!fsmhip::batch_read_limit(&in, s)) return nullptr;   /* as the matches: line extents are clamped to the limit */
+	return replaced_new(mt, rp, in, s);
 }
 
 extern "C" struct fsm_hip_replaced *fsm_hip_matches_replace(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b,
 	const struct fsm_hip_repl *rp)
 {
-	uint64_t m = 0;
-	if (replaced_check(mt, b, rp, &m) != 0) return nullptr;
-	const uint64_t n = b->n;
-	if (m != 0) {
-		for (uint64_t i = 0; i < n; i++)
-			if (b->off[i] > b->off[i + 1u]) { errno = EINVAL; return nullptr; }
-		if (b->base == nullptr && b->off[n] != 0u) { errno = EINVAL; return nullptr; }
-		if (b->pick != nullptr)
-			for (uint64_t j = 0; j < m; j++)
-				if (b->pick[j] >= n) { errno = EINVAL; return nullptr; }
-	}
-	DevGuard dg(mt->device);
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
-	DevStream own;                                   /* never the NULL stream */
-	if (!HIP_OK(own.create(hipStreamNonBlocking))) return nullptr;
-	hipStream_t s = own;
-	fsmhip::ReplRun r = replaced_run_of(b, m);
-	r.limit = 0;
-	DevBuf<unsigned char> d;                         /* everything staged in one allocation, each piece at a multiple of 16 bytes */
-	if (m != 0) {
-		auto up16 = [](uint64_t x) { return (x + 15u) & ~(uint64_t)15u; };
-		const uint64_t nbytes = b->off[n], n_off = (n + 1u) * 8u, n_m = m * 8u;
-		const uint64_t at_off = up16(nbytes), at_pick = at_off + up16(n_off), all = at_pick + (b->pick ? up16(n_m) : 0u);
-		if (!HIP_OK(d.alloc(all))) return nullptr;
-		bool ok = nbytes == 0 || HIP_OK(hipMemcpyAsync(d, b->base, nbytes, hipMemcpyHostToDevice, s));
-		ok = ok && HIP_OK(hipMemcpyAsync(d + at_off, b->off, n_off, hipMemcpyHostToDevice, s));
-		ok = ok && (b->pick == nullptr || HIP_OK(hipMemcpyAsync(d + at_pick, b->pick, n_m, hipMemcpyHostToDevice, s)));
-		if (!ok) {   /* the stream idle before the staging memory goes */
-			const int e = errno;
-			(void)hipStreamSynchronize(s);
-			errno = e;
-			return nullptr;
-		}
-		r.base = nbytes != 0 ? d.p : nullptr;
-		r.limit = nbytes;
-		r.off = (const uint64_t *)(d + at_off);
-		r.pick = b->pick ? (const uint64_t *)(d + at_pick) : nullptr;
-	}
-	struct fsm_hip_replaced *rd = replaced_new(mt, rp, r, s);
-	if (rd == nullptr) return nullptr;               /* (replaced_new left the stream idle) */
-	if (!HIP_OK(hipStreamSynchronize(s))) {          /* the write pass has read the staged text */
-		const int e = errno;
-		fsm_hip_replaced_free(rd);
-		errno = e;
-		return nullptr;
-	}
-	return rd;
+	fsmhip::LineBatch host;
+	if (!replaced_check(mt, b, rp, &host) || !fsmhip::batch_host_arrays_ok(host)) return nullptr;
+	return run_host(mt->device, host, [&](const fsmhip::LineBatch &in, hipStream_t s) { return replaced_new(mt, rp, in, s); });
 }
 
 extern "C" struct fsm_hip_replaced *fsm_hip_text_replace(const struct fsm_hip_matches *mt, const struct fsm_hip_text *t,
 	const struct fsm_hip_text_hits *h, const struct fsm_hip_repl *rp, void *hip_stream)
 {
 	if (!have_device()) { errno = ENODEV; return nullptr; }
-	if (mt == nullptr || t == nullptr || rp == nullptr) { errno = EINVAL; return nullptr; }
-	if (mt->device != t->device || rp->device != t->device || (h != nullptr && h->device != t->device)) { errno = EINVAL; return nullptr; }
-	if (mt->m != (h != nullptr ? h->m : t->n)) { errno = EINVAL; return nullptr; }
-	DevGuard dg(t->device);
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	if (mt == nullptr || t == nullptr || rp == nullptr || mt->m != (h != nullptr ? h->m : t->n)) { errno = EINVAL; return nullptr; }
 	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	/* the hits' lines (and, behind them, the text's offsets) first */
-	if (!HIP_OK(hipStreamWaitEvent(s, h != nullptr ? h->ev[5] : t->ev[3], 0))) return nullptr;
-	fsmhip::ReplRun r;
-	r.base = t->d_text;
-	r.off = t->d_off;
-	r.n = t->n;
-	r.pick = h != nullptr ? h->d_lines.p : nullptr;
-	r.m = h != nullptr ? h->m : t->n;
-	r.limit = t->nbytes;
-	return replaced_new(mt, rp, r, s);
+	std::optional<DevGuard> dg;
+	fsmhip::LineBatch in;
+	if (!text_batch(t, h, {mt->device, rp->device}, s, &dg, &in)) return nullptr;
+	return replaced_new(mt, rp, in, s);
 }
 
 extern "C" size_t fsm_hip_replaced_count(const struct fsm_hip_replaced *r) { return r == nullptr ? 0 : r->m; }
@@ -2388,17 +2159,8 @@ extern "C" const unsigned char *fsm_hip_replaced_bytes_device(const struct fsm_h
 extern "C" int fsm_hip_replaced_copy(const struct fsm_hip_replaced *r, uint64_t *off, void *bytes)
 {
 	if (r == nullptr) { errno = EINVAL; return -1; }
-	return copy_out(r->device, r->ev[7], {{off, r->d_off, (r->m + 1u) * sizeof(uint64_t)}, {bytes, r->d_bytes, (size_t)r->nbytes}});
+	return copy_out(r->device, r->done(), {{off, r->d_off, (r->m + 1u) * sizeof(uint64_t)}, {bytes, r->d_bytes, (size_t)r->nbytes}});
 }
 
-extern "C" double fsm_hip_replaced_ms(const struct fsm_hip_replaced *r)
-{
-	if (r == nullptr) { errno = EINVAL; return -1.0; }
-	return elapsed_ms(r->device, r->ev[7], {{r->ev[0], r->ev[1]}, {r->ev[2], r->ev[3]}, {r->ev[4], r->ev[5]}, {r->ev[6], r->ev[7]}});
-}
-
-extern "C" double fsm_hip_replaced_pass_ms(const struct fsm_hip_replaced *r, int pass)
-{
-	if (r == nullptr || pass < 0 || pass > 3) { errno = EINVAL; return -1.0; }
-	return elapsed_ms(r->device, r->ev[7], {{r->ev[2 * pass], r->ev[2 * pass + 1]}});
-}
+extern "C" double fsm_hip_replaced_ms(const struct fsm_hip_replaced *r) { return run_ms(r, 0, 3); }
+extern "C" double fsm_hip_replaced_pass_ms(const struct fsm_hip_replaced *r, int pass) { return run_ms(r, pass, pass); }

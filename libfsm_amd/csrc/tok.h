@@ -1,6 +1,7 @@
 /*
  * tok.h -- what text.hip may know about a struct fsm_hip_tok_dfa (defined in tok.hip): its device, and how one pass of the
- * tokeniser's walk is launched.  The fronts (the tokens object, its scan) are in text.hip.  Not part of the C ABI.
+ * tokeniser's walk is launched.  The fronts (the tokens object, its scan) are in text.hip; the batch a pass runs over is
+ * line_batch.h's.  Not part of the C ABI.
  */
 #ifndef FSMHIP_CSRC_TOK_H
 #define FSMHIP_CSRC_TOK_H
@@ -8,6 +9,8 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
+
+#include "line_batch.h"
 
 struct fsm_hip_tok_dfa;
 
@@ -17,14 +20,7 @@ constexpr uint32_t TOK_THREADS = 256;        /* inputs per workgroup, one per la
 
 /* one pass over m inputs; every pointer is device memory */
 struct TokRun {
-	const void *base = nullptr;
-	const uint64_t *off = nullptr;           /* n + 1 */
-	const uint64_t *pick = nullptr;          /* m, or null: input j is line j */
-	uint64_t n = 0, m = 0;
-	uint64_t limit = 0;                      /* has_limit: the bytes of base that may be read; else off[n] is */
-	bool has_limit = false;
-	int trim = -1;
-	unsigned flags = 0;                      /* FSM_HIP_TOKENS_* */
+	LineBatch in;                            /* flags: FSM_HIP_TOKENS_* */
 	uint64_t *count = nullptr, *err = nullptr;           /* the count pass writes them: m each */
 	const uint64_t *tok_off = nullptr;                   /* the emit pass reads it: m + 1 */
 	uint64_t *end_out = nullptr;                         /* ... and stores at tok_off[j] + t */

@@ -270,33 +270,33 @@ TokView tok_dfa_view(const fsm_hip_tok_dfa *td)
 
 int tok_launch(const fsm_hip_tok_dfa *td, const TokRun &r, bool emit, hipStream_t s)
 {
-	if (r.m == 0) return 0;
-	if ((r.m + TOK_THREADS - 1u) / TOK_THREADS > 0x7fffffffu) { errno = ENOMEM; return -1; }
+	if (r.in.m == 0) return 0;
+	if ((r.in.m + TOK_THREADS - 1u) / TOK_THREADS > 0x7fffffffu) { errno = ENOMEM; return -1; }
 	TokArgs a;
 	a.tab = td->d_tab.p;
 	a.col = td->d_col.p;
 	a.ids = td->d_ids.p;
-	a.base = static_cast<const uint8_t *>(r.base);
-	a.off = r.off;
-	a.pick = r.pick;
+	a.base = static_cast<const uint8_t *>(r.in.base);
+	a.off = r.in.off;
+	a.pick = r.in.pick;
 	a.count = r.count;
 	a.err = r.err;
 	a.tok_off = r.tok_off;
 	a.end_out = r.end_out;
 	a.id_out = r.id_out;
-	a.n = r.n;
-	a.m = r.m;
-	a.limit = r.limit;
+	a.n = r.in.n;
+	a.m = r.in.m;
+	a.limit = r.in.limit;
 	a.entries = td->entries;
 	a.C = td->C;
 	a.start = td->start;
 	a.abs_min = td->abs_min;
 	a.dead = td->dead;
 	a.in_lds = td->in_lds;
-	a.has_limit = r.has_limit ? 1u : 0u;
-	a.flags = r.flags;
-	a.trim = r.trim;
-	const dim3 grid((unsigned)((r.m + TOK_THREADS - 1u) / TOK_THREADS)), block(TOK_THREADS);
+	a.has_limit = r.in.has_limit ? 1u : 0u;
+	a.flags = r.in.flags;
+	a.trim = r.in.trim;
+	const dim3 grid((unsigned)((r.in.m + TOK_THREADS - 1u) / TOK_THREADS)), block(TOK_THREADS);
 	if (emit) hipLaunchKernelGGL(walk_tok<true>, grid, block, 0, s, a);
 	else hipLaunchKernelGGL(walk_tok<false>, grid, block, 0, s, a);
 	return HIP_OK(hipGetLastError()) ? 0 : -1;
