@@ -1192,6 +1192,76 @@ size_t fsm_hip_replaced_block_bytes(void);     /* output bytes of a block of the
 void fsm_hip_replaced_free(struct fsm_hip_replaced *r);
 
 /* ------------------------------------------------------------------ */
+/* extract: every kept match's bytes as a record of a packed text, on the device */
+/* ------------------------------------------------------------------ */
+
+/* grep -o for a union of rules, or the first half of "extract, then match the extracts against a second automaton": the
+ * complement of replace.  Replace keeps the text around the matches; extraction keeps the matches and drops the text around them.
+ * The matches are on the device and so is the text; the result is a fresh packed text there, one record per kept match, without
+ * a host loop over bytes.
+ *   Input j is line pick[j] of a packed text: base, off, n, pick, m, trim_byte and limit exactly as in struct fsm_hip_match_batch.
+ *   The line is clipped to the limit by the helper the matches' and the replacement's passes use; raw is its clipped byte count.
+ *   Its matches are entries moff[j] .. moff[j + 1] of a struct fsm_hip_matches, which must have been made from the same batch: m
+ *   must equal fsm_hip_matches_count (EINVAL), the rest is the caller's word.  The batch's flags are not used, but they and
+ *   trim_byte must be what the matches accept.
+ *   Every match k is clamped on its own: en = min(end_k, raw), st = min(start_k, en).  Records do not depend on each other, so
+ *   there is no "behind its predecessor" rule as in replace.  Indices read from moff are clamped to the matches' total.
+ *   A rule set says which matches are kept: a bitmap of nrules bits, rule i = bit (i & 7) of byte i >> 3 of `bits`, made once
+ *   from host memory by fsm_hip_rules_create, resident on the current device and reusable across calls.  keep == NULL keeps every
+ *   match.  Otherwise match k is kept when id_k < nrules and bit id_k is set; a set made with FSM_HIP_RULES_KEEP_OTHER also keeps
+ *   the matches with id_k >= nrules: rules beyond the set, FSM_HIP_NO_ID and FSM_HIP_NO_MATCH.  nrules == 0 is valid.
+ *   Record r is the r-th kept match in the order of k.  Its bytes are the text's [beg + st, beg + en), beg the line's first byte,
+ *   followed by the one byte sep_byte if sep_byte >= 0; -1 means no separator.  With '\n' the bytes are what grep -o prints.
+ *   Without a separator, empty matches (present when the matches were made without FSM_HIP_MATCHES_DROP_EMPTY) give empty records.
+ *   The result is again a packed text, off[R + 1] with off[0] = 0 plus bytes[off[R]], so it can be fed to any device front of
+ *   the library (with trim_byte = sep_byte where there is a separator); line[R] is the input j of each record and match[R] its
+ *   index k into the matches' arrays, so start, end and id are a gather away.
+ * No byte outside [base, base + limit) is read and no store leaves the object's arrays, whatever the offsets or the match arrays
+ * hold.  Wrong arrays may give wrong bytes, never a wild access.
+ * Passes: the lengths (one lane per MATCH: kept or not, the record's bytes, its first byte, its input, found in moff between the
+ * inputs of the block's first and last match; per block of fsm_hip_extracted_block_matches() matches the pair records / bytes), a
+ * scan of the BLOCK pairs by one workgroup -- total / block_matches records --, ONE wait for R and the bytes, the allocation, the
+ * offsets (the block's own scan redone, the compaction into off / line / match, an index per block of
+ * fsm_hip_extracted_block_bytes() output bytes), the write pass: a lane owns 16 output bytes, finds the record of the first by one
+ * search and walks on from record to record.  The offsets and the write pass are in flight at return.
+ * fsm_hip_matches_extract takes host pointers, stages them and waits; decreasing offsets and a pick[j] >= n are EINVAL before any
+ * launch; `limit` is ignored.  fsm_hip_matches_extract_device takes device pointers and hip_stream; a pick[j] >= n has no match
+ * and gives no record; limit == 0 costs a second, short wait in which off[n] is read, as for the matches.  fsm_hip_text_extract
+ * covers every line of a text object or (hits != NULL, every kind of hits) the lines of its hits, as fsm_hip_text_replace, and
+ * takes fsm_hip_text_matches' result for the same text and hits.  The work is enqueued behind the matches' last event, and behind
+ * the text's or the hits' for the text form.  The extracted object must be freed before the matches, the set and the text.  It
+ * owns, on the device: off[R + 1], the bytes (NULL when there are none), line[R] and match[R] (NULL when R == 0).  R == 0 gives a
+ * valid object and launches nothing that stores into the record arrays; off is always there.  _count is R.  _copy copies out
+ * whichever of off / bytes / line / match are not NULL and waits; _ms: the four passes by HIP events; _pass_ms: one of them.
+ * NULL + errno: ENODEV (checked first: there is no CPU path), EINVAL (an argument other than keep NULL, bits NULL with nrules > 0,
+ * an unknown flag bit, sep_byte or trim_byte outside -1 .. 255, m that is not the matches', objects on different devices; host
+ * form: offsets that decrease, a pick[j] >= n), ENOMEM. */
+#define FSM_HIP_RULES_KEEP_OTHER 1u
+struct fsm_hip_rules;      /* a set of rules resident on the current device, reusable across calls */
+struct fsm_hip_rules *fsm_hip_rules_create(const void *bits, size_t nrules, unsigned flags);
+void fsm_hip_rules_free(struct fsm_hip_rules *rs);
+
+struct fsm_hip_extracted;
+struct fsm_hip_extracted *fsm_hip_matches_extract(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *batch,
+	const struct fsm_hip_rules *keep, int sep_byte);
+struct fsm_hip_extracted *fsm_hip_matches_extract_device(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *d_batch,
+	const struct fsm_hip_rules *keep, int sep_byte, void *hip_stream);
+struct fsm_hip_extracted *fsm_hip_text_extract(const struct fsm_hip_matches *mt, const struct fsm_hip_text *t,
+	const struct fsm_hip_text_hits *hits, const struct fsm_hip_rules *keep, int sep_byte, void *hip_stream);
+size_t fsm_hip_extracted_count(const struct fsm_hip_extracted *x);              /* R: the records */
+uint64_t fsm_hip_extracted_nbytes(const struct fsm_hip_extracted *x);           /* off[R] */
+const uint64_t *fsm_hip_extracted_off_device(const struct fsm_hip_extracted *x);   /* R + 1, always there */
+const unsigned char *fsm_hip_extracted_bytes_device(const struct fsm_hip_extracted *x);   /* NULL when nbytes == 0 */
+const uint64_t *fsm_hip_extracted_line_device(const struct fsm_hip_extracted *x);  /* R; NULL when R == 0 */
+const uint64_t *fsm_hip_extracted_match_device(const struct fsm_hip_extracted *x); /* R; NULL when R == 0 */
+int fsm_hip_extracted_copy(const struct fsm_hip_extracted *x, uint64_t *off, void *bytes, uint64_t *line, uint64_t *match);
+double fsm_hip_extracted_ms(const struct fsm_hip_extracted *x);
+double fsm_hip_extracted_pass_ms(const struct fsm_hip_extracted *x, int pass);  /* 0: lengths, 1: scan of the block pairs, 2: offsets, 3: write */
+size_t fsm_hip_extracted_block_matches(void);  /* matches of a block of the lengths and the offsets pass */
+size_t fsm_hip_extracted_block_bytes(void);    /* output bytes of a block of the write pass */
+void fsm_hip_extracted_free(struct fsm_hip_extracted *x);
+
+/* ------------------------------------------------------------------ */
 /* synthetic input generator (benchmarks and parity tests)            */
 /* ------------------------------------------------------------------ */
 

@@ -42,6 +42,7 @@ POS_BACKWARD = 1
 TOKENS_NO_BACKTRACK, TOKENS_SKIP_BAD = 1, 2
 MATCHES_DROP_EMPTY = 1
 REPL_MASK = 1
+RULES_KEEP_OTHER = 1
 IDS_EARLIEST, IDS_RET, IDS_ERROR = 1, 2, 3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -248,6 +249,19 @@ PROTOTYPES = {"fsm_hip_" + name: (restype, args) for restype, names, *args in (
     (I, "replaced_copy", P, P, P),
     (D, "replaced_ms", P),
     (D, "replaced_pass_ms", P, I),
+    # extract
+    (P, "rules_create", P, S, U),
+    (None, "rules_free extracted_free", P),
+    (S, "extracted_block_matches extracted_block_bytes"),
+    (P, "matches_extract", P, P, P, I),
+    (P, "matches_extract_device", P, P, P, I, P),
+    (P, "text_extract", P, P, P, P, I, P),
+    (S, "extracted_count", P),
+    (U64, "extracted_nbytes", P),
+    (P, "extracted_off_device extracted_bytes_device extracted_line_device extracted_match_device", P),
+    (I, "extracted_copy", P, P, P, P, P),
+    (D, "extracted_ms", P),
+    (D, "extracted_pass_ms", P, I),
     # input generators: (out, stride, n, first_index, seed, {bytes, count}..., every[, stream])
     (I, "gen_inputs_device", P, S, S, U64, U64, P, U, P, U, U, P),
     (None, "gen_inputs_host", P, S, S, U64, U64, P, U, P, U, U),
@@ -1807,6 +1821,26 @@ class HipMatches:
         return HipReplaced(_call("fsm_hip_text_replace", self._h, text.handle, hits.handle if hits is not None else None, repl.handle,
                                  stream or None), (self, repl, text, hits))
 
+    def extract(self, base: np.ndarray, off: np.ndarray, pick=None, trim_byte: int = -1, keep: Optional["HipRules"] = None,
+                sep_byte: int = -1) -> "HipExtracted":
+        """fsm_hip_matches_extract on host arrays: the batch these matches were made from"""
+        base, off, pick, n, m = _line_arrays(base, off, pick)
+        b = MatchBatch(_ptr0(base), _ptr(off), n, _ptr(pick), m, trim_byte, 0, 0)
+        return HipExtracted(_call("fsm_hip_matches_extract", self._h, C.byref(b), keep.handle if keep is not None else None, sep_byte), (self, keep))
+
+    def extract_device(self, d_base: int, d_off: int, n: int, d_pick: int = 0, m: int = 0, trim_byte: int = -1, limit: int = 0,
+                       keep: Optional["HipRules"] = None, sep_byte: int = -1, stream: int = 0) -> "HipExtracted":
+        """fsm_hip_matches_extract_device: device addresses; the offsets and the write pass are in flight on `stream` at return"""
+        b = MatchBatch(d_base or None, d_off or None, n, d_pick or None, m, trim_byte, 0, limit)
+        return HipExtracted(_call("fsm_hip_matches_extract_device", self._h, C.byref(b), keep.handle if keep is not None else None, sep_byte,
+                                  stream or None), (self, keep))
+
+    def text_extract(self, text: "HipText", hits: Optional["HipHits"] = None, keep: Optional["HipRules"] = None, sep_byte: int = -1,
+                     stream: int = 0) -> "HipExtracted":
+        """fsm_hip_text_extract: these matches are fsm_hip_text_matches' of the same text and hits"""
+        return HipExtracted(_call("fsm_hip_text_extract", self._h, text.handle, hits.handle if hits is not None else None,
+                                  keep.handle if keep is not None else None, sep_byte, stream or None), (self, keep, text, hits))
+
     def ms(self) -> float:
         return float(self._lib.fsm_hip_matches_ms(self._h))
 
@@ -1920,3 +1954,106 @@ def repl_lds_bytes() -> int:
 
 def repl_lds_rules() -> int:
     return int(load_library().fsm_hip_repl_lds_rules())
+
+
+# ---- extract: every kept match's bytes as a record of a fresh packed text (include/fsm_hip.h, "extract") ----
+
+class HipRules:
+    """struct fsm_hip_rules *: a set of rules on the current device; rules: the ids that are kept, all below nrules; flags:
+    RULES_KEEP_OTHER"""
+
+    def __init__(self, rules: Sequence[int], nrules: int, flags: int = 0):
+        self._lib = load_library()
+        bits = np.zeros((nrules + 7) // 8, np.uint8)
+        for i in rules:
+            if not 0 <= i < nrules:
+                raise ValueError("rule %d outside the set of %d" % (i, nrules))
+            bits[i >> 3] |= 1 << (i & 7)
+        self._h = _call("fsm_hip_rules_create", _ptr(bits) if nrules else None, nrules, flags)
+        self.nrules, self.flags = nrules, flags
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.fsm_hip_rules_free(self._h)
+            self._h = None
+
+    free = close
+    __del__ = close
+
+
+class HipExtracted:
+    """struct fsm_hip_extracted *: off[R + 1], the bytes, line[R] and match[R] on the device.  Keeps its matches and its set (and
+    its text and hits) alive: the extracted object must be freed first."""
+
+    def __init__(self, handle, keep=()):
+        self._lib = load_library()
+        self._h, self._keep = handle, keep
+
+    def free(self):
+        if getattr(self, "_h", None):
+            self._lib.fsm_hip_extracted_free(self._h)
+            self._h = None
+            self._keep = None
+
+    close = free
+    __del__ = free
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def count(self) -> int:
+        return int(self._lib.fsm_hip_extracted_count(self._h))
+
+    @property
+    def nbytes(self) -> int:
+        return int(self._lib.fsm_hip_extracted_nbytes(self._h))
+
+    @property
+    def off_ptr(self) -> int:
+        return int(self._lib.fsm_hip_extracted_off_device(self._h) or 0)
+
+    @property
+    def bytes_ptr(self) -> int:
+        return int(self._lib.fsm_hip_extracted_bytes_device(self._h) or 0)
+
+    @property
+    def line_ptr(self) -> int:
+        return int(self._lib.fsm_hip_extracted_line_device(self._h) or 0)
+
+    @property
+    def match_ptr(self) -> int:
+        return int(self._lib.fsm_hip_extracted_match_device(self._h) or 0)
+
+    def copy(self, extra: int = 0, fill: int = 0):
+        """-> (off u64 [R + 1], bytes u8 [nbytes], line u64 [R], match u64 [R]); extra: that many more entries in each array,
+        pre-filled with `fill` and left alone by the library"""
+        R = self.count
+        off, data = np.full(R + 1 + extra, fill, np.uint64), np.full(self.nbytes + extra, fill & 0xFF, np.uint8)
+        line, match = np.full(R + extra, fill, np.uint64), np.full(R + extra, fill, np.uint64)
+        _call("fsm_hip_extracted_copy", self._h, _ptr(off), _ptr(data), _ptr(line), _ptr(match))
+        return off, data, line, match
+
+    def bytes(self) -> bytes:
+        return self.copy()[1].tobytes()
+
+    @property
+    def ms(self) -> float:
+        return float(self._lib.fsm_hip_extracted_ms(self._h))
+
+    def pass_ms(self, which: int) -> float:
+        """0: the lengths, 1: the scan of the block pairs, 2: the offsets, 3: the write pass"""
+        return float(self._lib.fsm_hip_extracted_pass_ms(self._h, which))
+
+
+def extracted_block_matches() -> int:
+    return int(load_library().fsm_hip_extracted_block_matches())
+
+
+def extracted_block_bytes() -> int:
+    return int(load_library().fsm_hip_extracted_block_bytes())
