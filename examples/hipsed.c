@@ -2,7 +2,7 @@
  * examples/hipsed.c -- sed 's/pat/repl/g' for a union of rules over many files, spliced on the device: no host loop over bytes
  * and none over matches:
  *
- *     hipsed [-m] LINES.fsmhip STARTS.fsmhip ENDS.fsmhip REPL... -- FILE...
+ *     hipsed [-m | -t] LINES.fsmhip STARTS.fsmhip ENDS.fsmhip REPL... -- FILE...
  *
  * The three tables are hipscan's (examples/hipscan.c): LINES selects the lines that hold a match, STARTS accepts anything followed
  * by the reversal of pat, ENDS accepts exactly pat and carries one end-id per rule.  The i-th REPL replaces every match of rule
@@ -10,6 +10,9 @@
  * EVERY line -- not only of the hits, so lines without one pass through unchanged --, fsm_hip_text_replace() builds the new text
  * on the device, and the files' text comes out on stdout, delimiters and a missing last newline as they were.
  *     -m         mask (FSM_HIP_REPL_MASK): a match keeps its length and is filled with its REPL, repeated; an empty REPL leaves it
+ *     -t         template (fsm_hip_repl_create_template): every REPL is a sed replacement -- & is the match itself, \& and \\ are
+ *                the literals & and \, a backslash before anything else stands for itself, a REPL may not end in one.
+ *                s/[0-9]+/(&)/g, grep --color.  Not together with -m
  * Exit status: 0 if some line held a match (LINES), 1 if none did (the text is written all the same), 2 on error.  Plain C against
  * include/fsm_hip.h only.
  */
@@ -71,23 +74,28 @@ main(int argc, char **argv)
 	struct fsm_hip_matches *matches;
 	struct fsm_hip_replaced *replaced;
 	unsigned char *buf = NULL, *rbytes = NULL, *out = NULL;
-	uint64_t *file_off, *roff, nout;
-	size_t cap = 0, len = 0, got, nfiles, nrepl, j, rlen = 0, nhits;
+	uint64_t *file_off, *roff, *ioff = NULL, *ins = NULL, nout;
+	size_t cap = 0, len = 0, got, nfiles, nrepl, j, k, rlen = 0, nhits;
 	unsigned flags = 0;
-	int a, sep;
+	int a, sep, tmpl = 0;
+	const char *arg;
 	char **names;
 	FILE *f;
 
 	a = 1;
-	if (a < argc && strcmp(argv[a], "-m") == 0) {
-		flags = FSM_HIP_REPL_MASK;
+	while (a < argc && (strcmp(argv[a], "-m") == 0 || strcmp(argv[a], "-t") == 0)) {
+		if (argv[a][1] == 'm') {
+			flags = FSM_HIP_REPL_MASK;
+		} else {
+			tmpl = 1;
+		}
 		a++;
 	}
 	for (sep = a + 3; sep < argc && strcmp(argv[sep], "--") != 0; sep++) {
 		;
 	}
-	if (a + 3 > argc || sep >= argc - 1) {
-		fprintf(stderr, "usage: hipsed [-m] LINES.fsmhip STARTS.fsmhip ENDS.fsmhip REPL... -- FILE...\n");
+	if (a + 3 > argc || sep >= argc - 1 || (tmpl && flags != 0)) {
+		fprintf(stderr, "usage: hipsed [-m | -t] LINES.fsmhip STARTS.fsmhip ENDS.fsmhip REPL... -- FILE...\n");
 		return 2;
 	}
 	desc = read_desc(argv[a]);
@@ -124,13 +132,45 @@ main(int argc, char **argv)
 		return 2;
 	}
 	roff[0] = 0;
-	for (j = 0; j < nrepl; j++) {
-		memcpy(rbytes + roff[j], argv[a + 3 + j], strlen(argv[a + 3 + j]));
-		roff[j + 1] = roff[j] + strlen(argv[a + 3 + j]);
+	if (!tmpl) {
+		for (j = 0; j < nrepl; j++) {
+			memcpy(rbytes + roff[j], argv[a + 3 + j], strlen(argv[a + 3 + j]));
+			roff[j + 1] = roff[j] + strlen(argv[a + 3 + j]);
+		}
+		repl = fsm_hip_repl_create(rbytes, roff, nrepl, flags);
+	} else {
+		/* -t: the literal bytes of every REPL, and per & the count of literal bytes in front of it (no REPL has more of
+		 * either than it has bytes) */
+		ioff = malloc((nrepl + 1) * sizeof *ioff);
+		ins = malloc((rlen + 1) * sizeof *ins);
+		if (ioff == NULL || ins == NULL) {
+			perror("malloc");
+			return 2;
+		}
+		ioff[0] = 0;
+		for (j = 0; j < nrepl; j++) {
+			arg = argv[a + 3 + j];
+			roff[j + 1] = roff[j];
+			ioff[j + 1] = ioff[j];
+			for (k = 0; arg[k] != '\0'; k++) {
+				if (arg[k] == '&') {
+					ins[ioff[j + 1]++] = roff[j + 1] - roff[j];
+					continue;
+				}
+				if (arg[k] == '\\' && arg[k + 1] == '\0') {
+					fprintf(stderr, "hipsed: REPL %zu ends in a backslash\n", j + 1);
+					return 2;
+				}
+				if (arg[k] == '\\' && (arg[k + 1] == '&' || arg[k + 1] == '\\')) {
+					k++;
+				}
+				rbytes[roff[j + 1]++] = (unsigned char)arg[k];
+			}
+		}
+		repl = fsm_hip_repl_create_template(rbytes, roff, nrepl, ins, ioff, 0);
 	}
-	repl = fsm_hip_repl_create(rbytes, roff, nrepl, flags);
 	if (repl == NULL) {
-		perror("fsm_hip_repl_create");
+		perror(tmpl ? "fsm_hip_repl_create_template" : "fsm_hip_repl_create");
 		return 2;
 	}
 
@@ -219,6 +259,8 @@ main(int argc, char **argv)
 	fsm_hip_lines_dfa_free(ld);
 	free(file_off);
 	free(roff);
+	free(ioff);
+	free(ins);
 	free(rbytes);
 	free(out);
 	free(buf);

@@ -1140,6 +1140,16 @@ void fsm_hip_matches_free(struct fsm_hip_matches *mt);
  *     sed does.
  *   - a table made with FSM_HIP_REPL_MASK: X_k has the match's length and its byte t is R[id][t mod |R[id]|]; if |R[id]| == 0 or
  *     id >= nrepl the match stays.  Lengths never change under this flag: the redaction case.
+ *   - a TEMPLATE table (fsm_hip_repl_create_template) puts the match itself inside its replacement: sed's `&`.  Besides the nrepl
+ *     literal strings R[i] it holds, per rule, a list of insert positions ins[ioff[i] .. ioff[i + 1]): each an index into R[i] in
+ *     0 .. |R[i]|, relative to the rule's own first byte, ascending, equal entries allowed (`&&`), at most
+ *     fsm_hip_repl_max_inserts() = 255 of them per rule.  For a match with id i < nrepl, own bytes M and the c inserts
+ *     a_0 <= ... <= a_{c-1} of its rule
+ *         X_k = R[i][0:a_0]  M  R[i][a_0:a_1]  M  ...  M  R[i][a_{c-1}:|R[i]|]          |X_k| = |R[i]| + c * |M|
+ *     c = 0 is the plain replacement; an empty R[i] with one insert at 0 is the identity for that rule; an empty match gives
+ *     X_k = R[i]; id >= nrepl: the match stays.  The cap is an interface condition: |X_k| <= |R[i]| + 255 * raw, so no output
+ *     length wraps a uint64_t, and a rule's insert count fits a byte.  A template table takes no flag: a template repeated to the
+ *     match's length (MASK) has no meaning.  Captures and numbered groups are not built: the whole match needs none.
  *   The result is again a packed text, out_off[m + 1] with out_off[0] = 0 plus bytes[out_off[m]], so it can be fed to any device
  *   front of the library.
  * A pick[j] >= n (device form) gives an empty output line and nothing is read.  No byte outside [base, base + limit) is read and
@@ -1152,7 +1162,11 @@ void fsm_hip_matches_free(struct fsm_hip_matches *mt);
  * fsm_hip_replaced_block_bytes() output bytes, sized by the total, which is why this pass follows the wait), the write pass: a lane
  * owns 16 output bytes and finds their line and their match by two searches.  The offsets and the write pass are in flight at
  * return.  The table's bytes and offsets are read from LDS when nrepl <= fsm_hip_repl_lds_rules() and its bytes <=
- * fsm_hip_repl_lds_bytes() (fsm_hip_repl_in_lds), from device memory otherwise.
+ * fsm_hip_repl_lds_bytes() (fsm_hip_repl_in_lds), from device memory otherwise.  A template table with inserts keeps its insert
+ * offsets and its positions there too, two bytes each, and their room comes out of the bytes' budget: it is read from LDS when
+ * nrepl <= fsm_hip_repl_lds_rules() and (its bytes rounded up to 16) + 2 * (nrepl + 1) + 2 * fsm_hip_repl_inserts() <=
+ * fsm_hip_repl_lds_bytes().  A template table without any insert (ioff == NULL, or every rule with none) is a plain table in
+ * every respect: the same kernels, the same rule, byte for byte the output of fsm_hip_repl_create(bytes, roff, nrepl, 0).
  * fsm_hip_repl_create takes host pointers and leaves the table on the current device, reusable across calls; nrepl == 0 is valid
  * and gives the identity.  fsm_hip_matches_replace takes host pointers, stages them and waits; decreasing offsets and a
  * pick[j] >= n are EINVAL before any launch; `limit` is ignored.  fsm_hip_matches_replace_device takes device pointers and
@@ -1164,7 +1178,9 @@ void fsm_hip_matches_free(struct fsm_hip_matches *mt);
  * _copy copies out whichever of off / bytes are not NULL and waits; _ms: the four passes by HIP events; _pass_ms: one of them.
  * NULL + errno: ENODEV (checked first: there is no CPU path), EINVAL (an argument NULL, roff NULL with nrepl > 0, roff that
  * decreases, bytes NULL with bytes to copy, an unknown flag bit, trim_byte outside -1 .. 255, m that is not the matches', objects
- * on different devices; host form: offsets that decrease, a pick[j] >= n), ENOMEM. */
+ * on different devices; host form: offsets that decrease, a pick[j] >= n; fsm_hip_repl_create_template: any flag, MASK included,
+ * ioff[0] != 0, ioff that decreases, ins NULL with ioff[nrepl] > 0, a position above |R[i]|, positions of one rule that decrease,
+ * more than fsm_hip_repl_max_inserts() inserts in one rule -- all before any upload), ENOMEM. */
 #define FSM_HIP_REPL_MASK 1u
 struct fsm_hip_repl;       /* a replacement table resident on the current device, reusable across calls */
 struct fsm_hip_repl *fsm_hip_repl_create(const void *bytes, const uint64_t *roff, size_t nrepl, unsigned flags);
@@ -1172,6 +1188,11 @@ void fsm_hip_repl_free(struct fsm_hip_repl *rp);
 int fsm_hip_repl_in_lds(const struct fsm_hip_repl *rp);            /* 1: the write pass reads the table from LDS */
 size_t fsm_hip_repl_lds_bytes(void);
 size_t fsm_hip_repl_lds_rules(void);
+/* a template table: ins[ioff[i] .. ioff[i + 1]) are rule i's insert positions; ioff == NULL: no rule has an insert */
+struct fsm_hip_repl *fsm_hip_repl_create_template(const void *bytes, const uint64_t *roff, size_t nrepl,
+	const uint64_t *ins, const uint64_t *ioff, unsigned flags);
+size_t fsm_hip_repl_inserts(const struct fsm_hip_repl *rp);        /* ioff[nrepl]; 0 for NULL and for a plain table */
+size_t fsm_hip_repl_max_inserts(void);                             /* per rule: 255 */
 
 struct fsm_hip_replaced;
 struct fsm_hip_replaced *fsm_hip_matches_replace(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *batch,

@@ -14,6 +14,6 @@ from .capi import (  # noqa: F401
     NO_POS, POS_BACKWARD, PosBatch, PosDfa, HipSpans,
     TOKENS_NO_BACKTRACK, TOKENS_SKIP_BAD, IDS_EARLIEST, IDS_RET, IDS_ERROR, TokBatch, TokDfa, HipTokens,
     MATCHES_DROP_EMPTY, MatchBatch, HipMatches,
-    REPL_MASK, HipRepl, HipReplaced, replaced_block_lines, replaced_block_bytes, repl_lds_bytes, repl_lds_rules,
+    REPL_MASK, HipRepl, HipReplaced, replaced_block_lines, replaced_block_bytes, repl_lds_bytes, repl_lds_rules, repl_max_inserts,
     RULES_KEEP_OTHER, HipRules, HipExtracted, extracted_block_matches, extracted_block_bytes,
 )

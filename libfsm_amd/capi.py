@@ -237,6 +237,9 @@ PROTOTYPES = {"fsm_hip_" + name: (restype, args) for restype, names, *args in (
     (D, "matches_pass_ms", P, I),
     # replace
     (P, "repl_create", P, P, S, U),
+    (P, "repl_create_template", P, P, S, P, P, U),
+    (S, "repl_inserts", P),
+    (S, "repl_max_inserts"),
     (None, "repl_free replaced_free", P),
     (I, "repl_in_lds", P),
     (S, "repl_lds_bytes repl_lds_rules replaced_block_lines replaced_block_bytes"),
@@ -1864,6 +1867,57 @@ class HipRepl:
         self._h = _call("fsm_hip_repl_create", _ptr0(data), _ptr(roff) if table else None, len(table), flags)
         self.nrepl, self.flags = len(table), flags
 
+    @classmethod
+    def template(cls, table: Sequence[bytes], inserts: Optional[Sequence[Sequence[int]]], flags: int = 0) -> "HipRepl":
+        """fsm_hip_repl_create_template: inserts[i] = the positions in table[i] at which the match itself is put (sed's &), ascending,
+        each 0 .. len(table[i]); inserts None: no rule has one (ioff NULL)"""
+        self = cls.__new__(cls)
+        self._lib = load_library()
+        table = [bytes(r) for r in table]
+        data = np.frombuffer(b"".join(table), np.uint8)
+        roff = np.zeros(len(table) + 1, np.uint64)
+        if table:
+            roff[1:] = np.cumsum([len(r) for r in table])
+        ins = ioff = None
+        if inserts is not None:
+            if len(inserts) != len(table):
+                raise ValueError("one list of insert positions per rule")
+            ioff = np.zeros(len(table) + 1, np.uint64)
+            if table:
+                ioff[1:] = np.cumsum([len(a) for a in inserts])
+            ins = np.array([int(x) for a in inserts for x in a], np.uint64)
+        self._h = _call("fsm_hip_repl_create_template", _ptr0(data), _ptr(roff) if table else None, len(table),
+                        _ptr(ins) if ins is not None and len(ins) else None, _ptr(ioff) if ioff is not None else None, flags)
+        self.nrepl, self.flags = len(table), flags
+        return self
+
+    @staticmethod
+    def parse_sed(text: bytes):
+        """a sed replacement -> (literal bytes, insert positions): & is an insert, \\& and \\\\ are the literals & and \\, and
+        nothing else is read: a backslash before any other byte stands for itself, as that byte does (no \\n, no \\1).  A trailing
+        backslash is a ValueError"""
+        text = bytes(text)
+        lit, ins, i = bytearray(), [], 0
+        while i < len(text):
+            c = text[i:i + 1]
+            if c == b"&":
+                ins.append(len(lit))
+            elif c == b"\\" and i + 1 == len(text):
+                raise ValueError("a replacement cannot end in a backslash: %r" % (text,))
+            elif c == b"\\" and text[i + 1:i + 2] in (b"&", b"\\"):
+                i += 1
+                lit += text[i:i + 1]
+            else:
+                lit += c
+            i += 1
+        return bytes(lit), ins
+
+    @classmethod
+    def from_sed(cls, strings: Sequence[bytes]) -> "HipRepl":
+        """a template table from sed replacements (parse_sed), one per rule"""
+        parsed = [cls.parse_sed(x) for x in strings]
+        return cls.template([p[0] for p in parsed], [p[1] for p in parsed])
+
     @property
     def handle(self):
         return self._h
@@ -1871,6 +1925,16 @@ class HipRepl:
     @property
     def in_lds(self) -> bool:
         return bool(self._lib.fsm_hip_repl_in_lds(self._h))
+
+    @property
+    def inserts(self) -> int:
+        """the table's inserts, over all rules; 0 for a plain table"""
+        return int(self._lib.fsm_hip_repl_inserts(self._h))
+
+    @staticmethod
+    def max_inserts() -> int:
+        """fsm_hip_repl_max_inserts: per rule"""
+        return int(load_library().fsm_hip_repl_max_inserts())
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1954,6 +2018,10 @@ def repl_lds_bytes() -> int:
 
 def repl_lds_rules() -> int:
     return int(load_library().fsm_hip_repl_lds_rules())
+
+
+def repl_max_inserts() -> int:
+    return int(load_library().fsm_hip_repl_max_inserts())
 
 
 # ---- extract: every kept match's bytes as a record of a fresh packed text (include/fsm_hip.h, "extract") ----

@@ -22,6 +22,12 @@ constexpr uint32_t REPL_LDS_BYTES = 16384;
 constexpr uint32_t REPL_LDS_RULES = 1023;
 
 inline bool repl_table_fits_lds(uint64_t nrepl, uint64_t rbytes) { return nrepl <= REPL_LDS_RULES && rbytes <= REPL_LDS_BYTES; }
+/* a table with nins inserts: its insert offsets and its positions, two bytes each, take their room out of the 16 KiB of bytes, behind
+ * the table's bytes rounded up to 16 -- so every position and every insert offset fits a u16 */
+inline bool repl_tmpl_fits_lds(uint64_t nrepl, uint64_t rbytes, uint64_t nins)
+{
+	return repl_table_fits_lds(nrepl, rbytes) && nins <= REPL_LDS_BYTES && ((rbytes + 15u) & ~(uint64_t)15u) + 2u * (nrepl + 1u) + 2u * nins <= REPL_LDS_BYTES;
+}
 
 /* m inputs fit one launch's grid */
 inline bool repl_grid_fits(uint64_t m) { return (m + REPL_LINES - 1u) / REPL_LINES <= 0x7fffffffu; }
@@ -53,7 +59,14 @@ struct ReplRun {
 	unsigned char *out = nullptr;            /* ngb * REPL_BLOCK */
 	uint64_t total = 0, ngb = 0;             /* known after the scan */
 	uint64_t wgs = 1, per = 1;               /* the write pass's grid: wgs workgroups of `per` consecutive output blocks */
+	/* the table's inserts (a template table with at least one): last, so that the fields above stay where the plain kernels read them */
+	const uint64_t *ioff = nullptr;          /* nrepl + 1, or null: no rule has an insert */
+	const uint64_t *ins = nullptr;           /* nins positions */
+	uint64_t nins = 0;
 };
+
+/* the table has inserts: the template kernels run, for every other table the plain ones */
+inline bool repl_is_template(const ReplRun &r) { return r.nins != 0 && r.ioff != nullptr && r.ins != nullptr; }
 
 /* each on stream s, the objects' device current; 0, or -1 + errno */
 __attribute__((visibility("hidden"))) int repl_launch_lengths(const ReplRun &r, hipStream_t s);

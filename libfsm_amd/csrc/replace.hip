@@ -18,6 +18,9 @@
  *                   of one line is one 16-byte load of any alignment; every other chunk is assembled stretch by stretch -- a
  *                   16-byte window per stretch, placed so that the stretch's bytes fall where they belong, and masked -- with
  *                   a new lookup whenever a stretch, a replacement or a line ends.
+ * A template table (fsm_hip_repl_create_template: insert positions per rule, at which the match's own bytes stand inside the
+ * replacement) runs repl_lengths<true> and repl_write<., true>: another repl_at(), in which a copy of the match is one more text
+ * stretch; every other table runs the <false> kernels, which hold nothing of it.
  * No line belongs to a lane in the write pass: a line of 64 MiB is 4 096 blocks like any other 64 MiB.  In the lengths pass a lane
  * walks ITS line's matches alone, so a line of many matches holds its wavefront for that long.
  * Every global access names its address space (no FLAT instruction), every index read from an array is clamped to the array it
@@ -52,6 +55,7 @@ typedef const uint64_t __attribute__((address_space(1))) *g_u64p;
 typedef uint64_t __attribute__((address_space(1))) *g_u64w;
 typedef const uint8_t __attribute__((address_space(3))) *l_u8p;
 typedef const uint32_t __attribute__((address_space(3))) *l_u32p;
+typedef const uint16_t __attribute__((address_space(3))) *l_u16p;
 typedef const u32x4r_any __attribute__((address_space(3))) *l_chunkp;
 
 __device__ __forceinline__ uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
@@ -86,7 +90,9 @@ __device__ __forceinline__ void line_of(const ReplRun &a, uint64_t j, uint64_t *
 }
 
 /* pass 1: workgroup b takes inputs [b * REPL_LINES, (b + 1) * REPL_LINES), one per lane.  out_off[j] = the output length of input
- * j (the offsets pass turns it into the offset), sums[b] = the block's bytes; mpos and xlen of every match. */
+ * j (the offsets pass turns it into the offset), sums[b] = the block's bytes; mpos and xlen of every match.  TMPL: the table has
+ * inserts (never under MASK), and a rule's count of them is read from ioff. */
+template <bool TMPL>
 __global__ void __launch_bounds__(REPL_THREADS)
 repl_lengths(const ReplRun a)
 {
@@ -112,7 +118,11 @@ repl_lengths(const ReplRun a)
 				const uint64_t r0 = roff[i], r1 = roff[i + 1u];
 				rlen = r1 > r0 ? r1 - r0 : 0u;
 			}
-			const uint64_t xl = repl_xlen(mlen, repl_uses_table(i, a.nrepl, rlen, mask), rlen, mask);
+			uint64_t xl = repl_xlen(mlen, repl_uses_table(i, a.nrepl, rlen, mask), rlen, mask);
+			if (TMPL && i < a.nrepl) {
+				uint64_t i0;
+				xl = repl_xlen(mlen, rlen, repl_inserts_of((g_u64p)(uintptr_t)a.ioff, i, a.nrepl, a.nins, &i0));
+			}
 			mpos[k] = st + delta;
 			xlen[k] = xl;
 			delta += xl - mlen;
@@ -196,23 +206,36 @@ __device__ __forceinline__ uint64_t line_at(g_u64p oo, uint64_t lo, uint64_t hi,
 }
 
 /* pass 4.  IN_LDS: the table's bytes and its offsets (as u32) are copied to LDS first: the dynamic region, its base 16-byte
- * aligned, no static LDS in front of it. */
-template <bool IN_LDS>
+ * aligned, no static LDS in front of it.  TMPL: the table has inserts, and a stretch inside X_k may be the match's own bytes --
+ * a text stretch like any other (replace_seg.h); in LDS the insert offsets and the positions follow the offsets, as u16
+ * (repl_tmpl_fits_lds: both fit). */
+template <bool IN_LDS, bool TMPL>
 __global__ void __launch_bounds__(REPL_THREADS)
 repl_write(const ReplRun a)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char repl_smem[];
 	const uint32_t roff_at = ((uint32_t)a.rbytes + 15u) & ~15u;
+	const uint32_t ioff_at = roff_at + 4u * ((uint32_t)a.nrepl + 1u), ins_at = ioff_at + 2u * ((uint32_t)a.nrepl + 1u);
 	if (IN_LDS) {
 		__attribute__((address_space(3))) u32x4r *dst = (__attribute__((address_space(3))) u32x4r *)repl_smem;
 		for (uint32_t c = threadIdx.x; c < roff_at / 16u; c += REPL_THREADS) dst[c] = ((g_chunk16p)(uintptr_t)a.rbytes_p)[c];
 		__attribute__((address_space(3))) uint32_t *ro = (__attribute__((address_space(3))) uint32_t *)(repl_smem + roff_at);
 		for (uint32_t e = threadIdx.x; e <= (uint32_t)a.nrepl; e += REPL_THREADS)
 			ro[e] = (uint32_t)min64(((g_u64p)(uintptr_t)a.roff)[e], a.rbytes);
+		if (TMPL) {
+			__attribute__((address_space(3))) uint16_t *io = (__attribute__((address_space(3))) uint16_t *)(repl_smem + ioff_at);
+			__attribute__((address_space(3))) uint16_t *in = (__attribute__((address_space(3))) uint16_t *)(repl_smem + ins_at);
+			for (uint32_t e = threadIdx.x; e <= (uint32_t)a.nrepl; e += REPL_THREADS)
+				io[e] = (uint16_t)min64(((g_u64p)(uintptr_t)a.ioff)[e], a.nins);
+			for (uint32_t e = threadIdx.x; e < (uint32_t)a.nins; e += REPL_THREADS)
+				in[e] = (uint16_t)min64(((g_u64p)(uintptr_t)a.ins)[e], a.rbytes);
+		}
 		__syncthreads();
 	}
 	const l_u8p tab_lds = (l_u8p)(__attribute__((address_space(3))) unsigned char *)repl_smem;
 	const l_u32p roff_lds = (l_u32p)(__attribute__((address_space(3))) unsigned char *)(repl_smem + roff_at);
+	const l_u16p ioff_lds = (l_u16p)(__attribute__((address_space(3))) unsigned char *)(repl_smem + ioff_at);
+	const l_u16p ins_lds = (l_u16p)(__attribute__((address_space(3))) unsigned char *)(repl_smem + ins_at);
 	const g_u8p tab_glb = (g_u8p)(uintptr_t)a.rbytes_p;
 	const g_u64p roff_glb = (g_u64p)(uintptr_t)a.roff;
 	const g_u64p oo = (g_u64p)(uintptr_t)a.out_off, fi = (g_u64p)(uintptr_t)a.first;
@@ -225,6 +248,12 @@ repl_write(const ReplRun a)
 
 	auto source = [&](const ReplLine &L, uint64_t p) {
 		const uint64_t outlen = L.o1 > L.o0 ? L.o1 - L.o0 : 0u;
+		if (TMPL && IN_LDS)
+			return repl_at(mpos + L.k0, xlen + L.k0, start + L.k0, end + L.k0, id + L.k0, L.nm, roff_lds, ioff_lds, ins_lds, a.nrepl, a.rbytes,
+			               a.nins, p - L.o0, outlen, L.raw);
+		if (TMPL)
+			return repl_at(mpos + L.k0, xlen + L.k0, start + L.k0, end + L.k0, id + L.k0, L.nm, roff_glb, (g_u64p)(uintptr_t)a.ioff,
+			               (g_u64p)(uintptr_t)a.ins, a.nrepl, a.rbytes, a.nins, p - L.o0, outlen, L.raw);
 		if (IN_LDS)
 			return repl_at(mpos + L.k0, xlen + L.k0, start + L.k0, end + L.k0, id + L.k0, L.nm, roff_lds, a.nrepl, a.rbytes, mask, p - L.o0,
 			               outlen, L.raw);
@@ -308,7 +337,8 @@ int repl_launch_lengths(const ReplRun &r, hipStream_t s)
 	if (r.m == 0) return 0;
 	if (!repl_grid_fits(r.m)) { errno = ENOMEM; return -1; }
 	const dim3 grid((unsigned)((r.m + REPL_LINES - 1u) / REPL_LINES)), block(REPL_THREADS);
-	hipLaunchKernelGGL(repl_lengths, grid, block, 0, s, r);
+	if (repl_is_template(r)) hipLaunchKernelGGL(repl_lengths<true>, grid, block, 0, s, r);
+	else hipLaunchKernelGGL(repl_lengths<false>, grid, block, 0, s, r);
 	return HIP_OK(hipGetLastError()) ? 0 : -1;
 }
 
@@ -326,12 +356,16 @@ int repl_launch_write(const ReplRun &r, hipStream_t s)
 	if (r.m == 0 || r.total == 0 || r.ngb == 0) return 0;
 	if (r.wgs == 0 || r.wgs > 0x7fffffffu) { errno = ENOMEM; return -1; }
 	const dim3 grid((unsigned)r.wgs), block(REPL_THREADS);
+	const bool tmpl = repl_is_template(r);
+	if (tmpl && (r.flags & FSM_HIP_REPL_MASK) != 0u) { errno = EINVAL; return -1; }
 	if (r.table_in_lds) {
-		if (!repl_table_fits_lds(r.nrepl, r.rbytes)) { errno = EINVAL; return -1; }
+		if (!(tmpl ? repl_tmpl_fits_lds(r.nrepl, r.rbytes, r.nins) : repl_table_fits_lds(r.nrepl, r.rbytes))) { errno = EINVAL; return -1; }
 		const size_t lds = (((size_t)r.rbytes + 15u) & ~(size_t)15u) + 4u * ((size_t)r.nrepl + 1u);
-		hipLaunchKernelGGL(repl_write<true>, grid, block, lds, s, r);
+		if (tmpl) hipLaunchKernelGGL((repl_write<true, true>), grid, block, lds + 2u * ((size_t)r.nrepl + 1u) + 2u * (size_t)r.nins, s, r);
+		else hipLaunchKernelGGL((repl_write<true, false>), grid, block, lds, s, r);
 	} else {
-		hipLaunchKernelGGL(repl_write<false>, grid, block, 0, s, r);
+		if (tmpl) hipLaunchKernelGGL((repl_write<false, true>), grid, block, 0, s, r);
+		else hipLaunchKernelGGL((repl_write<false, false>), grid, block, 0, s, r);
 	}
 	return HIP_OK(hipGetLastError()) ? 0 : -1;
 }

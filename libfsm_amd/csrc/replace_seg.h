@@ -14,6 +14,8 @@
  * below `rbytes` (table) or no source at all, and a run of at least one byte -- wrong arrays give wrong bytes, never a wild access
  * and never a loop that does not advance.  The arrays are read through [] alone, so the kernel passes pointers that name their
  * address space (global or LDS) and the CPU test plain ones.
+ * A template table (the match itself inside its replacement) has a repl_at() and a repl_xlen() of its own at the end of this file,
+ * with the same promises; tests/c/test_replace_tmpl.cpp checks them.
  */
 #ifndef FSMHIP_CSRC_REPLACE_SEG_H
 #define FSMHIP_CSRC_REPLACE_SEG_H
@@ -92,6 +94,119 @@ FSMHIP_REPL_FN ReplAt repl_at(U64A mpos, U64A xlen, U64B start, U64B end, U32A i
 					r.run = 1u;
 				} else if (rlen - t < r.run) {
 					r.run = rlen - t;                /* MASK: the table's bytes begin again */
+				}
+				return r;
+			}
+			r.at = (uint64_t)start[k] + d;           /* the match stays */
+		} else {
+			r.at = (uint64_t)end[k] + (d - xl);
+		}
+	}
+	if (r.at >= raw) {
+		r.from = REPL_FROM_NONE;
+		r.run = 1u;
+	} else if (raw - r.at < r.run) {
+		r.run = raw - r.at;
+	}
+	return r;
+}
+
+/* ---- templates: the match itself inside its replacement (include/fsm_hip.h, "replace", templates) --------------------------------
+ * Rule i has c inserts at the ascending positions a_0 <= ... <= a_{c-1} of R[i], each at most |R[i]|, and a match of L bytes gives
+ *     X = R[i][0:a_0]  M  R[i][a_0:a_1]  M ... M  R[i][a_{c-1}:|R[i]|],      |X| = |R[i]| + c * L
+ * The s-th copy of M begins at byte a_s + s * L of X, which does not decrease in s: byte d of X lies behind the LAST s with
+ * a_s + s * L <= d, in that copy when d - (a_s + s * L) < L and in the literal behind it otherwise.  A table without MASK only. */
+
+constexpr uint64_t REPL_MAX_INSERTS = 255;   /* per rule: an interface condition (fsm_hip_repl_max_inserts) */
+
+/* the inserts of rule `id`: [*i0, *i0 + c) of the nins positions, whatever ioff holds; c <= REPL_MAX_INSERTS; none beyond the table */
+template <typename IOFF>
+FSMHIP_REPL_FN uint64_t repl_inserts_of(IOFF ioff, uint64_t id, uint64_t nrepl, uint64_t nins, uint64_t *i0)
+{
+	*i0 = 0;
+	if (id >= nrepl) return 0u;
+	uint64_t a = (uint64_t)ioff[id], b = (uint64_t)ioff[id + 1u];
+	if (a > nins) a = nins;
+	if (b > nins) b = nins;
+	*i0 = a;
+	const uint64_t c = b > a ? b - a : 0u;
+	return c < REPL_MAX_INSERTS ? c : REPL_MAX_INSERTS;
+}
+
+/* |X| of a match of mlen bytes whose rule is in the table (id < nrepl) and has c inserts: mlen <= the line's bytes and
+ * c <= REPL_MAX_INSERTS, so nothing wraps */
+FSMHIP_REPL_FN uint64_t repl_xlen(uint64_t mlen, uint64_t rlen, uint64_t c) { return rlen + c * mlen; }
+
+/* repl_at() for a template table: ioff, the table's nrepl + 1 insert offsets, ins its nins positions.  Where no rule of the line
+ * has an insert the answer is repl_at()'s for mask = false.  The match's length is taken from xlen, as the lengths pass left it:
+ * L = (xlen - |R|) / c. */
+template <typename U64A, typename U64B, typename U32A, typename ROFF, typename IOFF, typename INS>
+FSMHIP_REPL_FN ReplAt repl_at(U64A mpos, U64A xlen, U64B start, U64B end, U32A id, uint64_t nm, ROFF roff, IOFF ioff, INS ins, uint64_t nrepl,
+                              uint64_t rbytes, uint64_t nins, uint64_t q, uint64_t outlen, uint64_t raw)
+{
+	uint64_t lo = 0, hi = nm;                        /* the first match with mpos > q */
+	while (lo < hi) {
+		const uint64_t mid = lo + (hi - lo) / 2u;
+		if ((uint64_t)mpos[mid] <= q) lo = mid + 1u; else hi = mid;
+	}
+	const uint64_t next = lo < nm ? (uint64_t)mpos[lo] : outlen;
+	ReplAt r;
+	r.from = REPL_FROM_TEXT;
+	r.k = nm;
+	r.at = q;
+	r.run = next > q ? next - q : 1u;
+	if (lo != 0u) {
+		const uint64_t k = lo - 1u, d = q - (uint64_t)mpos[k], xl = (uint64_t)xlen[k];
+		r.k = k;
+		if (d < xl) {                                /* inside X_k */
+			const uint64_t i = (uint64_t)id[k];
+			if (xl - d < r.run) r.run = xl - d;
+			if (i < nrepl) {
+				const uint64_t r0 = (uint64_t)roff[i], r1 = (uint64_t)roff[i + 1u];
+				const uint64_t rlen = r1 > r0 ? r1 - r0 : 0u;
+				uint64_t i0;
+				const uint64_t c = repl_inserts_of(ioff, i, nrepl, nins, &i0);
+				const uint64_t L = c != 0u && xl > rlen ? (xl - rlen) / c : 0u;
+				uint64_t t = d, upto = rlen;         /* the literal's byte and where its stretch ends: L == 0 is X = R[i] */
+				if (L != 0u) {
+					uint64_t slo = 0, shi = c;       /* the first insert whose copy begins behind d (s * L <= xl: no wrap) */
+					while (slo < shi) {
+						const uint64_t mid = slo + (shi - slo) / 2u;
+						uint64_t a = (uint64_t)ins[i0 + mid];
+						if (a > rlen) a = rlen;
+						if (a + mid * L <= d) slo = mid + 1u; else shi = mid;
+					}
+					if (slo < c) {
+						upto = (uint64_t)ins[i0 + slo];
+						if (upto > rlen) upto = rlen;
+					}
+					if (slo != 0u) {
+						uint64_t a = (uint64_t)ins[i0 + slo - 1u];
+						if (a > rlen) a = rlen;
+						const uint64_t e = d - (a + (slo - 1u) * L);
+						if (e < L) {                 /* in the copy of the match: text again */
+							if (L - e < r.run) r.run = L - e;
+							r.at = (uint64_t)start[k] + e;
+							if (r.at >= raw) {
+								r.from = REPL_FROM_NONE;
+								r.run = 1u;
+							} else if (raw - r.at < r.run) {
+								r.run = raw - r.at;
+							}
+							return r;
+						}
+						t = a + (e - L);
+					}
+				}
+				r.from = REPL_FROM_TABLE;
+				r.at = r0 + t;
+				if (r.at >= rbytes || t >= rlen) {
+					r.from = REPL_FROM_NONE;
+					r.run = 1u;
+				} else {
+					const uint64_t left = upto > t ? upto - t : 1u;
+					if (left < r.run) r.run = left;
+					if (rbytes - r.at < r.run) r.run = rbytes - r.at;
 				}
 				return r;
 			}

@@ -37,6 +37,7 @@
 #include "match.h"
 #include "match_marks.h"
 #include "replace.h"
+#include "replace_seg.h"
 #include "span.h"
 #include "tok.h"
 
@@ -1997,32 +1998,71 @@ struct __attribute__((visibility("hidden"))) fsm_hip_repl {
 	bool in_lds = false;
 	DevBuf<unsigned char> d_bytes;           /* rbytes, rounded up to 16 and never nothing */
 	DevBuf<uint64_t> d_roff;                 /* nrepl + 1 */
+	uint64_t nins = 0;                       /* a template table's inserts; 0: a plain table, and the two arrays below are not there */
+	DevBuf<uint64_t> d_ioff;                 /* nrepl + 1 */
+	DevBuf<uint64_t> d_ins;                  /* nins */
 };
 
-extern "C" struct fsm_hip_repl *fsm_hip_repl_create(const void *bytes, const uint64_t *roff, size_t nrepl, unsigned flags)
+/* the table on device `dev`; the arguments are checked.  nins != 0: ioff[nrepl + 1] and ins[nins] go along */
+static struct fsm_hip_repl *repl_new(int dev, const void *bytes, const uint64_t *roff, size_t nrepl, const uint64_t *ins, const uint64_t *ioff,
+	uint64_t nins, unsigned flags)
 {
-	int dev = 0;
-	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
-	if ((flags & ~FSM_HIP_REPL_MASK) != 0u || (roff == nullptr && nrepl != 0)) { errno = EINVAL; return nullptr; }
-	for (size_t i = 0; i < nrepl; i++)
-		if (roff[i] > roff[i + 1u]) { errno = EINVAL; return nullptr; }
 	const uint64_t rbytes = nrepl != 0 ? roff[nrepl] : 0u;
-	if (rbytes != 0 && bytes == nullptr) { errno = EINVAL; return nullptr; }
 	struct fsm_hip_repl *rp = new (std::nothrow) struct fsm_hip_repl;
 	if (rp == nullptr) { errno = ENOMEM; return nullptr; }
 	rp->device = dev;
 	rp->nrepl = nrepl;
 	rp->rbytes = rbytes;
 	rp->flags = flags;
-	rp->in_lds = fsmhip::repl_table_fits_lds(nrepl, rbytes);
+	rp->nins = nins;
+	rp->in_lds = nins != 0 ? fsmhip::repl_tmpl_fits_lds(nrepl, rbytes, nins) : fsmhip::repl_table_fits_lds(nrepl, rbytes);
 	const uint64_t zero = 0;
 	if (HIP_OK(rp->d_bytes.upload_bytes(bytes, (size_t)rbytes, 16)) &&
-	    HIP_OK(rp->d_roff.upload_bytes(nrepl != 0 ? roff : &zero, (nrepl + 1u) * sizeof(uint64_t), sizeof(uint64_t))))
+	    HIP_OK(rp->d_roff.upload_bytes(nrepl != 0 ? roff : &zero, (nrepl + 1u) * sizeof(uint64_t), sizeof(uint64_t))) &&
+	    (nins == 0 || (HIP_OK(rp->d_ioff.upload_bytes(ioff, (nrepl + 1u) * sizeof(uint64_t), sizeof(uint64_t))) &&
+	                   HIP_OK(rp->d_ins.upload_bytes(ins, (size_t)nins * sizeof(uint64_t), sizeof(uint64_t))))))
 		return rp;
 	const int e = errno;
 	delete rp;
 	errno = e;
 	return nullptr;
+}
+
+/* what both kinds of table refuse: roff NULL with rules, roff that decreases, bytes NULL with bytes to copy */
+static bool repl_table_ok(const void *bytes, const uint64_t *roff, size_t nrepl)
+{
+	if (roff == nullptr && nrepl != 0) return false;
+	for (size_t i = 0; i < nrepl; i++)
+		if (roff[i] > roff[i + 1u]) return false;
+	return !(nrepl != 0 && roff[nrepl] != 0 && bytes == nullptr);
+}
+
+extern "C" struct fsm_hip_repl *fsm_hip_repl_create(const void *bytes, const uint64_t *roff, size_t nrepl, unsigned flags)
+{
+	int dev = 0;
+	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
+	if ((flags & ~FSM_HIP_REPL_MASK) != 0u || !repl_table_ok(bytes, roff, nrepl)) { errno = EINVAL; return nullptr; }
+	return repl_new(dev, bytes, roff, nrepl, nullptr, nullptr, 0, flags);
+}
+
+extern "C" struct fsm_hip_repl *fsm_hip_repl_create_template(const void *bytes, const uint64_t *roff, size_t nrepl, const uint64_t *ins,
+	const uint64_t *ioff, unsigned flags)
+{
+	int dev = 0;
+	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
+	if (flags != 0u || !repl_table_ok(bytes, roff, nrepl)) { errno = EINVAL; return nullptr; }
+	uint64_t nins = 0;
+	if (ioff != nullptr) {
+		if (ioff[0] != 0u) { errno = EINVAL; return nullptr; }
+		for (size_t i = 0; i < nrepl; i++) {
+			if (ioff[i] > ioff[i + 1u] || ioff[i + 1u] - ioff[i] > fsmhip::REPL_MAX_INSERTS || (ins == nullptr && ioff[i + 1u] != 0u)) { errno = EINVAL; return nullptr; }
+			const uint64_t rlen = roff[i + 1u] - roff[i];
+			for (uint64_t x = ioff[i]; x < ioff[i + 1u]; x++)
+				if (ins[x] > rlen || (x > ioff[i] && ins[x] < ins[x - 1u])) { errno = EINVAL; return nullptr; }
+		}
+		nins = ioff[nrepl];
+	}
+	return repl_new(dev, bytes, roff, nrepl, ins, ioff, nins, 0u);
 }
 
 extern "C" void fsm_hip_repl_free(struct fsm_hip_repl *rp)
@@ -2039,6 +2079,8 @@ extern "C" void fsm_hip_repl_free(struct fsm_hip_repl *rp)
 extern "C" int fsm_hip_repl_in_lds(const struct fsm_hip_repl *rp) { return rp != nullptr && rp->in_lds ? 1 : 0; }
 extern "C" size_t fsm_hip_repl_lds_bytes(void) { return fsmhip::REPL_LDS_BYTES; }
 extern "C" size_t fsm_hip_repl_lds_rules(void) { return fsmhip::REPL_LDS_RULES; }
+extern "C" size_t fsm_hip_repl_inserts(const struct fsm_hip_repl *rp) { return rp != nullptr ? (size_t)rp->nins : 0u; }
+extern "C" size_t fsm_hip_repl_max_inserts(void) { return fsmhip::REPL_MAX_INSERTS; }
 extern "C" size_t fsm_hip_replaced_block_lines(void) { return fsmhip::REPL_LINES; }
 extern "C" size_t fsm_hip_replaced_block_bytes(void) { return fsmhip::REPL_BLOCK; }
 
@@ -2106,6 +2148,11 @@ static struct fsm_hip_replaced *replaced_new(const struct fsm_hip_matches *mt, c
 	r.rbytes = rp->rbytes;
 	r.flags = rp->flags;
 	r.table_in_lds = rp->in_lds;
+	if (rp->nins != 0) {
+		r.ioff = rp->d_ioff;
+		r.ins = rp->d_ins;
+		r.nins = rp->nins;
+	}
 	return run_new<struct fsm_hip_replaced>(mt->device, in.m, fsmhip::repl_grid_fits(in.m), s, [&](struct fsm_hip_replaced *rd) {
 		return HIP_OK(hipStreamWaitEvent(s, mt->done(), 0)) ? replaced_passes(rd, r, s) : -1;   /* behind the matches' emit pass */
 	});
