@@ -351,6 +351,59 @@ def _ptr0(a: Optional[np.ndarray]):
     return _ptr(a) if a is not None and a.size else None
 
 
+def _host_batch(struct, base, off, pick, *tail):
+    """a line batch (TokBatch, MatchBatch) over host arrays -> (the struct, the arrays it points into: held until the call is
+    over); tail: the fields behind m"""
+    base, off, pick, n, m = _line_arrays(base, off, pick)
+    return struct(_ptr0(base), _ptr(off), n, _ptr(pick), m, *tail), (base, off, pick)
+
+
+def _device_batch(struct, d_base: int, d_off: int, n: int, d_pick: int, m: int, *tail):
+    """a line batch (PosBatch, TokBatch, MatchBatch) over device addresses, 0: NULL; tail: the fields behind m"""
+    return struct(d_base or None, d_off or None, n, d_pick or None, m, *tail)
+
+
+class _Owned:
+    """One handle of the library and what has to outlive it.  _FREE names the function that frees the handle; close() calls
+    it once, on a half-built object and on a second call it does nothing; dropping the last reference closes."""
+
+    _FREE = None
+
+    def __init__(self, handle, keep=()):
+        self._lib = load_library()
+        self._h, self._keep = handle, keep
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._FREE)(self._h)
+        self._h = self._keep = None
+
+    def __del__(self):
+        self.close()      # (not an alias: a subclass's close is the one that runs)
+
+    @property
+    def handle(self):
+        return self._h
+
+
+class _Freed(_Owned):
+    """an _Owned whose close() is spelt free() as well, as the library spells it: the objects the matches family hands out.  (Not
+    in _Owned: tests/test_gpu_round5.py lists every public method of HipNode.)"""
+
+    def free(self):
+        self.close()
+
+
+def _dev(fn: str):
+    """a property of an _Owned: the device address the library's `fn` answers for the handle, 0 for NULL"""
+    return property(lambda self: int(getattr(self._lib, fn)(self._h) or 0))
+
+
+def _size(fn: str, doc: Optional[str] = None):
+    """a property of an _Owned: the size_t (or uint64_t) the library's `fn` answers for the handle"""
+    return property(lambda self: int(getattr(self._lib, fn)(self._h)), doc=doc)
+
+
 @contextmanager
 def _fopen(path: str, mode: bytes):
     """a FILE * of the C library, closed on the way out"""
@@ -574,8 +627,10 @@ class FlatDfa:
         return self.eager_ids[int(self.eager_off[state]):int(self.eager_off[state + 1])]
 
 
-class Plan:
+class Plan(_Owned):
     """Host-side table plan (fsm_hip_plan_*): inspection only, never executes inputs."""
+
+    _FREE = "fsm_hip_plan_free"
 
     _WHAT = dict(scalars=(0, np.uint32), cls=(1, np.uint8), new2old=(2, np.uint32), fin=(3, np.uint32),
                  dense=(4, np.uint32), tiny_col=(5, np.uint64), lds_tab=(6, np.uint16), comb=(7, np.uint32),
@@ -586,9 +641,8 @@ class Plan:
                  comb_rng=(23, np.uint16), lazy=(24, np.uint32), glob_tab16=(25, np.uint16), glob16_rank=(26, np.uint32), glob16_fin=(27, np.uint32))
 
     def __init__(self, flat: FlatDfa, flags: int = 0, lds_limit: int = 0):
-        self._lib = load_library()
         d = flat.desc()
-        self._h = _call("fsm_hip_plan_create", C.byref(d), flags, lds_limit)
+        super().__init__(_call("fsm_hip_plan_create", C.byref(d), flags, lds_limit))
         s = self.get("scalars")
         (self.nstates, self.S1, self.start, self.C, self.abs_min, self.nabsorbing, self.layout, self.row_bytes,
          self.comb_abs_min_off, self.comb256_abs_min_off, self.comb256_dflt, self.eager_lo_end,
@@ -604,23 +658,18 @@ class Plan:
         buf = (C.c_char * (n.value * np.dtype(dt).itemsize)).from_address(p.value)
         return np.frombuffer(buf, dtype=dt).copy()
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._lib.fsm_hip_plan_free(self._h)
-            self._h = None
 
-
-class HipDfa:
+class HipDfa(_Owned):
     """struct fsm_hip_dfa *: a DFA resident on the GPU."""
 
+    _FREE = "fsm_hip_dfa_free"
+
     def __init__(self, flat: Optional[FlatDfa] = None, flags: int = 0, *, handle=None, borrowed: bool = False):
-        self._lib = load_library()
         self._borrowed = borrowed      # a replica owned by a HipNode: never freed from here
-        if handle is not None:
-            self._h = handle
-        else:
+        if handle is None:
             d = flat.desc()
-            self._h = _call("fsm_hip_dfa_create", C.byref(d), flags)
+            handle = _call("fsm_hip_dfa_create", C.byref(d), flags)
+        super().__init__(handle)
 
     @classmethod
     def compile_fsm(cls, fsm_ptr: int, flags: int = 0) -> "HipDfa":
@@ -628,16 +677,9 @@ class HipDfa:
         return cls(handle=_call("fsm_hip_compile", fsm_ptr, flags))
 
     def close(self):
-        if getattr(self, "_h", None):
-            if not getattr(self, "_borrowed", False):
-                self._lib.fsm_hip_dfa_free(self._h)
+        if getattr(self, "_borrowed", False):
             self._h = None
-
-    __del__ = close
-
-    @property
-    def handle(self):
-        return self._h
+        super().close()
 
     def info(self) -> dict:
         i = _Info()
@@ -911,22 +953,16 @@ class HipDfa:
         return buf[:n]
 
 
-class HipNode:
+class HipNode(_Owned):
     """struct fsm_hip_node *: one table replica per device, a batch sharded over them (include/fsm_hip.h)."""
 
+    _FREE = "fsm_hip_node_free"
+
     def __init__(self, flat: FlatDfa, devices: Optional[Sequence[int]] = None, flags: int = 0):
-        self._lib = load_library()
         d = flat.desc()
         devs = (C.c_int * len(devices))(*devices) if devices else None
-        self._h = _call("fsm_hip_node_create", C.byref(d), flags, devs, len(devices) if devices else 0)
+        super().__init__(_call("fsm_hip_node_create", C.byref(d), flags, devs, len(devices) if devices else 0))
         self.ndev = int(self._lib.fsm_hip_node_ndev(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.fsm_hip_node_free(self._h)
-            self._h = None
-
-    __del__ = close
 
     def uses_rccl(self) -> bool:
         return bool(self._lib.fsm_hip_node_uses_rccl(self._h))
@@ -1101,27 +1137,24 @@ def exec_multi_ptrs(dfas: Sequence[Optional["HipDfa"]], jobs: Sequence[tuple], i
           *([ids_mode] if width != 5 else []), *([stream or None] if device else []))
 
 
-class MultiPrepared:
+class MultiPrepared(_Owned):
     """fsm_hip_multi_prepare / _launch / _prepared_free: a device-pointer submission put on the device once; launch() is
     one kernel launch on the stream (capturable into a HIP graph).  jobs[q] = (d_base, d_off, n, d_end, d_bitmap, d_ids), or
     -- every job of the submission -- (d_base, d_off, n, d_end, d_bitmap, d_ids, d_eager): fsm_hip_multi_prepare_eager."""
+
+    _FREE = "fsm_hip_multi_prepared_free"
 
     def __init__(self, dfas: Sequence["HipDfa"], jobs: Sequence[tuple], ids_mode: int = 0):
         eager = len(jobs) != 0 and len(jobs[0]) == 7
         if any(len(j) != (7 if eager else 6) for j in jobs):
             raise ValueError("every job is a 6-tuple, or every job is a 7-tuple")
-        self._keep = list(dfas)
-        self._p = C.c_void_p()
+        p = C.c_void_p()
         _call("fsm_hip_multi_prepare_eager" if eager else "fsm_hip_multi_prepare", *_multi_args(MultiBatchEager if eager else MultiBatchIds, dfas, jobs),
-              ids_mode, C.byref(self._p))
+              ids_mode, C.byref(p))
+        super().__init__(p.value, list(dfas))
 
     def launch(self, stream: int = 0) -> None:
-        _call("fsm_hip_multi_launch", self._p, stream or None)
-
-    def close(self) -> None:
-        if self._p:
-            load_library().fsm_hip_multi_prepared_free(self._p)
-            self._p = C.c_void_p()
+        _call("fsm_hip_multi_launch", self._h, stream or None)
 
 
 def multi_last_launches() -> int:
@@ -1236,76 +1269,56 @@ def identity_byte(flat: FlatDfa, byte: int) -> FlatDfa:
     return FlatDfa._take(_call("fsm_hip_desc_identity_byte", C.byref(d), int(byte)))
 
 
-class LinesDfa:
+class LinesDfa(_Owned):
     """struct fsm_hip_lines_dfa *: the twin automaton in which the delimiter is a self-loop of every state, and that delimiter.
     .inner is the HipDfa to ask for end-ids, ret sets, eager ids, info, the last kernel and tuning (borrowed)."""
 
-    def __init__(self, flat: FlatDfa, delim: int = 0x0A, flags: int = 0):
-        self._lib = load_library()
-        d = flat.desc()
-        self._h = _call("fsm_hip_lines_dfa_create", C.byref(d), delim, flags)
-        self.inner = HipDfa(handle=self._lib.fsm_hip_lines_dfa_inner(self._h), borrowed=True)
+    _FREE = "fsm_hip_lines_dfa_free"
 
-    @property
-    def handle(self):
-        return self._h
+    def __init__(self, flat: FlatDfa, delim: int = 0x0A, flags: int = 0):
+        d = flat.desc()
+        super().__init__(_call("fsm_hip_lines_dfa_create", C.byref(d), delim, flags))
+        self.inner = HipDfa(handle=self._lib.fsm_hip_lines_dfa_inner(self._h), borrowed=True)
 
     @property
     def delim(self) -> int:
         return int(self._lib.fsm_hip_lines_dfa_delim(self._h))
 
     def close(self):
-        if getattr(self, "_h", None):
-            self.inner._h = None
-            self._lib.fsm_hip_lines_dfa_free(self._h)
-            self._h = None
-
-    __del__ = close
+        if getattr(self, "inner", None) is not None:
+            self.inner._h = None      # it dies with the twin
+        super().close()
 
 
-class HipText:
+class HipText(_Owned):
     """struct fsm_hip_text *: bytes on the device plus the offsets of their lines.  data: host bytes (copied once), or
     d_text = a device address with nbytes (borrowed: it must outlive the text; the scan is enqueued on `stream`).
     file_off: the text is files back to back (fsm_hip_text_open_files*): nfiles + 1 byte positions, a host array with `data`, with
     d_text either a device address (borrowed, with nfiles=) or an array-like that is copied to the device and kept."""
 
+    _FREE = "fsm_hip_text_free"
+
     def __init__(self, data=None, delim: int = 0x0A, *, d_text: int = 0, nbytes: int = 0, stream: int = 0, file_off=None, nfiles: int = 0):
-        self._lib = load_library()
         if data is not None:
             buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data, dtype=np.uint8)
         if data is not None and file_off is not None:
             fo = np.ascontiguousarray(file_off, dtype=np.uint64)
-            self._h = _call("fsm_hip_text_open_files", _ptr0(buf), buf.size, delim, _ptr0(fo), max(fo.size, 1) - 1)
+            h = _call("fsm_hip_text_open_files", _ptr0(buf), buf.size, delim, _ptr0(fo), max(fo.size, 1) - 1)
         elif data is not None:
-            self._h = _call("fsm_hip_text_open", _ptr0(buf), buf.size, delim)
+            h = _call("fsm_hip_text_open", _ptr0(buf), buf.size, delim)
         elif file_off is not None:
             if not isinstance(file_off, (int, np.integer)):   # a host array: its device copy lives as long as the text
                 import torch
                 fo = np.ascontiguousarray(file_off, dtype=np.uint64)
                 self._file_off = torch.from_numpy(fo.view(np.int64).copy()).cuda() if fo.size else None
                 file_off, nfiles = (self._file_off.data_ptr() if fo.size else 0), max(fo.size, 1) - 1
-            self._h = _call("fsm_hip_text_open_files_device", d_text or None, nbytes, delim, int(file_off) or None, nfiles, stream or None)
+            h = _call("fsm_hip_text_open_files_device", d_text or None, nbytes, delim, int(file_off) or None, nfiles, stream or None)
         else:
-            self._h = _call("fsm_hip_text_open_device", d_text or None, nbytes, delim, stream or None)
+            h = _call("fsm_hip_text_open_device", d_text or None, nbytes, delim, stream or None)
+        super().__init__(h)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.fsm_hip_text_free(self._h)
-            self._h = None
-
-    __del__ = close
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def lines(self) -> int:
-        return int(self._lib.fsm_hip_text_lines(self._h))
-
-    @property
-    def d_off(self) -> int:
-        return int(self._lib.fsm_hip_text_offsets_device(self._h) or 0)
+    lines = _size("fsm_hip_text_lines")
+    d_off = _dev("fsm_hip_text_offsets_device")
 
     def offsets(self) -> np.ndarray:
         off = np.empty(self.lines + 1, np.uint64)
@@ -1315,14 +1328,8 @@ class HipText:
     def scan_ms(self) -> float:
         return float(self._lib.fsm_hip_text_scan_ms(self._h))
 
-    @property
-    def files(self) -> int:
-        """fsm_hip_text_files: 0 for a plain text"""
-        return int(self._lib.fsm_hip_text_files(self._h))
-
-    @property
-    def file_lines_ptr(self) -> int:
-        return int(self._lib.fsm_hip_text_file_lines_device(self._h) or 0)
+    files = _size("fsm_hip_text_files", "fsm_hip_text_files: 0 for a plain text")
+    file_lines_ptr = _dev("fsm_hip_text_file_lines_device")
 
     def file_lines(self) -> np.ndarray:
         """fsm_hip_text_file_lines: the files + 1 line indices at which the files begin (raises EINVAL on a plain text)"""
@@ -1372,45 +1379,25 @@ def hits_flags(invert: bool, want_bytes: bool) -> int:
     return (HITS_INVERT if invert else 0) | (0 if want_bytes else HITS_NO_BYTES)
 
 
-class HipHits:
+class HipHits(_Owned):
     """struct fsm_hip_text_hits *: the selected lines' numbers, output offsets and bytes, packed on the device.  Keeps its text
     alive: the hits must be freed first."""
 
+    _FREE = "fsm_hip_text_hits_free"
+
     def __init__(self, handle, text: HipText):
-        self._lib = load_library()
-        self._h, self._text = handle, text
+        super().__init__(handle)
+        self._text = text
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.fsm_hip_text_hits_free(self._h)
-            self._h = None
-            self._text = None
+        super().close()
+        self._text = None
 
-    __del__ = close
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def count(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_count(self._h))
-
-    @property
-    def nbytes(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_nbytes(self._h))
-
-    @property
-    def lines_device(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_lines_device(self._h) or 0)
-
-    @property
-    def offsets_device(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_offsets_device(self._h) or 0)
-
-    @property
-    def bytes_device(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_bytes_device(self._h) or 0)
+    count = _size("fsm_hip_text_hits_count")
+    nbytes = _size("fsm_hip_text_hits_nbytes")
+    lines_device = _dev("fsm_hip_text_hits_lines_device")
+    offsets_device = _dev("fsm_hip_text_hits_offsets_device")
+    bytes_device = _dev("fsm_hip_text_hits_bytes_device")
 
     def _copy(self, lines=None, off=None, data=None):
         _call("fsm_hip_text_hits_copy", self._h, _ptr(lines), _ptr(off), _ptr(data))
@@ -1436,9 +1423,7 @@ class HipHits:
     def gather_ms(self) -> float:
         return float(self._lib.fsm_hip_text_hits_gather_ms(self._h))
 
-    @property
-    def file_first_ptr(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_file_first_device(self._h) or 0)
+    file_first_ptr = _dev("fsm_hip_text_hits_file_first_device")
 
     def file_first(self) -> np.ndarray:
         """fsm_hip_text_hits_file_first: files + 1 entries, the hits of file j are [file_first[j], file_first[j + 1])"""
@@ -1450,22 +1435,10 @@ class HipHits:
         return float(self._lib.fsm_hip_text_hits_file_first_ms(self._h))
 
     # hits with context (HipText.hits_context*); on plain hits: 0 from the pointers and the counts, EINVAL from the copies
-    @property
-    def core_ptr(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_core_device(self._h) or 0)
-
-    @property
-    def group_ptr(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_group_device(self._h) or 0)
-
-    @property
-    def core_count(self) -> int:
-        """fsm_hip_text_hits_core_count: the selected lines, context left out (grep -c)"""
-        return int(self._lib.fsm_hip_text_hits_core_count(self._h))
-
-    @property
-    def groups(self) -> int:
-        return int(self._lib.fsm_hip_text_hits_groups(self._h))
+    core_ptr = _dev("fsm_hip_text_hits_core_device")
+    group_ptr = _dev("fsm_hip_text_hits_group_device")
+    core_count = _size("fsm_hip_text_hits_core_count", "fsm_hip_text_hits_core_count: the selected lines, context left out (grep -c)")
+    groups = _size("fsm_hip_text_hits_groups")
 
     def _marks(self, which: int) -> np.ndarray:
         m = self.count
@@ -1523,12 +1496,13 @@ def text_context_scan_block() -> int:
 
 # ---- match positions: first / last accepting offset, spans of a text's hits (include/fsm_hip.h, "match positions") ----
 
-class PosDfa:
+class PosDfa(_Owned):
     """struct fsm_hip_pos_dfa *: the device image of a HipDfa for the accept-position walk (the dfa may be closed afterwards)."""
 
+    _FREE = "fsm_hip_pos_dfa_free"
+
     def __init__(self, dfa: "HipDfa"):
-        self._lib = load_library()
-        self._h = _call("fsm_hip_pos_dfa_create", dfa.handle if dfa is not None else None)
+        super().__init__(_call("fsm_hip_pos_dfa_create", dfa.handle if dfa is not None else None))
 
     @classmethod
     def from_flat(cls, flat: FlatDfa) -> "PosDfa":
@@ -1540,19 +1514,8 @@ class PosDfa:
             dfa.close()
 
     @property
-    def handle(self):
-        return self._h
-
-    @property
     def in_lds(self) -> bool:
         return bool(self._lib.fsm_hip_pos_dfa_in_lds(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.fsm_hip_pos_dfa_free(self._h)
-            self._h = None
-
-    __del__ = close
 
     def accept_pos(self, base: np.ndarray, off: np.ndarray, pick=None, frm=None, to=None, trim_byte: int = -1, backward: bool = False,
                    want_first: bool = True, want_last: bool = True, out: Optional[tuple] = None):
@@ -1569,45 +1532,29 @@ class PosDfa:
     def accept_pos_device(self, d_base: int, d_off: int, n: int, d_first: int = 0, d_last: int = 0, d_pick: int = 0, m: int = 0, d_from: int = 0,
                           d_to: int = 0, trim_byte: int = -1, backward: bool = False, limit: int = 0, stream: int = 0):
         """fsm_hip_exec_accept_pos_device: device addresses, asynchronous on `stream`"""
-        b = PosBatch(d_base or None, d_off or None, n, d_pick or None, m, d_from or None, d_to or None, trim_byte, POS_BACKWARD if backward else 0,
-                     d_first or None, d_last or None, limit)
+        b = _device_batch(PosBatch, d_base, d_off, n, d_pick, m, d_from or None, d_to or None, trim_byte, POS_BACKWARD if backward else 0,
+                          d_first or None, d_last or None, limit)
         _call("fsm_hip_exec_accept_pos_device", self._h, C.byref(b), stream or None)
 
 
-class HipSpans:
+class HipSpans(_Owned):
     """struct fsm_hip_text_spans *: the leftmost-longest span of every hit, one match per round.  Keeps its hits, its text and
     the two images alive: the spans must be freed first."""
 
+    _FREE = "fsm_hip_text_spans_free"
+
     def __init__(self, hits: "HipHits", starts: PosDfa, ends: PosDfa, stream: int = 0):
-        self._lib = load_library()
-        self._keep = (hits, hits._text, starts, ends)
         self._m = hits.count
-        self._h = _call("fsm_hip_text_hits_spans", hits.handle, hits._text.handle, starts.handle, ends.handle, stream or None)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.fsm_hip_text_spans_free(self._h)
-            self._h = None
-            self._keep = None
-
-    __del__ = close
+        super().__init__(_call("fsm_hip_text_hits_spans", hits.handle, hits._text.handle, starts.handle, ends.handle, stream or None),
+                         (hits, hits._text, starts, ends))
 
     def next(self) -> None:
         """fsm_hip_text_spans_next: every hit's search position moves behind its match; the two walks run again"""
         _call("fsm_hip_text_spans_next", self._h)
 
-    @property
-    def count(self) -> int:
-        """the hits with a span in the current round (one wait)"""
-        return int(self._lib.fsm_hip_text_spans_count(self._h))
-
-    @property
-    def start_ptr(self) -> int:
-        return int(self._lib.fsm_hip_text_spans_start_device(self._h) or 0)
-
-    @property
-    def end_ptr(self) -> int:
-        return int(self._lib.fsm_hip_text_spans_end_device(self._h) or 0)
+    count = _size("fsm_hip_text_spans_count", "the hits with a span in the current round (one wait)")
+    start_ptr = _dev("fsm_hip_text_spans_start_device")
+    end_ptr = _dev("fsm_hip_text_spans_end_device")
 
     def copy(self):
         """-> (start, end), u64 [m] each, NO_POS where the hit has no span in this round"""
@@ -1621,13 +1568,14 @@ class HipSpans:
 
 # ---- tokens: every line cut into longest-match tokens with end-ids (include/fsm_hip.h, "tokens") ----
 
-class TokDfa:
+class TokDfa(_Owned):
     """struct fsm_hip_tok_dfa *: the device image of a HipDfa for the tokeniser's walk, one id per state under ids_mode (the dfa
     may be closed afterwards)."""
 
+    _FREE = "fsm_hip_tok_dfa_free"
+
     def __init__(self, dfa: "HipDfa", ids_mode: int = IDS_EARLIEST):
-        self._lib = load_library()
-        self._h = _call("fsm_hip_tok_dfa_create", dfa.handle if dfa is not None else None, ids_mode)
+        super().__init__(_call("fsm_hip_tok_dfa_create", dfa.handle if dfa is not None else None, ids_mode))
 
     @classmethod
     def from_flat(cls, flat: FlatDfa, ids_mode: int = IDS_EARLIEST) -> "TokDfa":
@@ -1639,30 +1587,18 @@ class TokDfa:
             dfa.close()
 
     @property
-    def handle(self):
-        return self._h
-
-    @property
     def in_lds(self) -> bool:
         return bool(self._lib.fsm_hip_tok_dfa_in_lds(self._h))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.fsm_hip_tok_dfa_free(self._h)
-            self._h = None
-
-    __del__ = close
-
     def tokens(self, base: np.ndarray, off: np.ndarray, pick=None, trim_byte: int = -1, flags: int = 0) -> "HipTokens":
         """fsm_hip_tokens_run on host arrays"""
-        base, off, pick, n, m = _line_arrays(base, off, pick)
-        b = TokBatch(_ptr0(base), _ptr(off), n, _ptr(pick), m, trim_byte, flags, 0)
+        b, _held = _host_batch(TokBatch, base, off, pick, trim_byte, flags, 0)
         return HipTokens(_call("fsm_hip_tokens_run", self._h, C.byref(b)), (self,))
 
     def tokens_device(self, d_base: int, d_off: int, n: int, d_pick: int = 0, m: int = 0, trim_byte: int = -1, flags: int = 0, limit: int = 0,
                       stream: int = 0) -> "HipTokens":
         """fsm_hip_tokens_run_device: device addresses; the emit pass is in flight on `stream` at return"""
-        b = TokBatch(d_base or None, d_off or None, n, d_pick or None, m, trim_byte, flags, limit)
+        b = _device_batch(TokBatch, d_base, d_off, n, d_pick, m, trim_byte, flags, limit)
         return HipTokens(_call("fsm_hip_tokens_run_device", self._h, C.byref(b), stream or None), (self,))
 
     def text_tokens(self, text: "HipText", hits: Optional["HipHits"] = None, flags: int = 0, stream: int = 0) -> "HipTokens":
@@ -1676,49 +1612,17 @@ class TokDfa:
                                 stream or None), (starts, self, text, hits))
 
 
-class HipTokens:
+class HipTokens(_Owned):
     """struct fsm_hip_tokens *: off[m + 1], end[total], id[total], err[m] on the device.  Keeps its image (and its text and
     hits) alive: the tokens must be freed first."""
 
-    def __init__(self, handle, keep=()):
-        self._lib = load_library()
-        self._h, self._keep = handle, keep
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.fsm_hip_tokens_free(self._h)
-            self._h = None
-            self._keep = None
-
-    __del__ = close
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def count(self) -> int:
-        return int(self._lib.fsm_hip_tokens_count(self._h))
-
-    @property
-    def total(self) -> int:
-        return int(self._lib.fsm_hip_tokens_total(self._h))
-
-    @property
-    def off_ptr(self) -> int:
-        return int(self._lib.fsm_hip_tokens_off_device(self._h) or 0)
-
-    @property
-    def end_ptr(self) -> int:
-        return int(self._lib.fsm_hip_tokens_end_device(self._h) or 0)
-
-    @property
-    def id_ptr(self) -> int:
-        return int(self._lib.fsm_hip_tokens_id_device(self._h) or 0)
-
-    @property
-    def err_ptr(self) -> int:
-        return int(self._lib.fsm_hip_tokens_err_device(self._h) or 0)
+    _FREE = "fsm_hip_tokens_free"
+    count = _size("fsm_hip_tokens_count")
+    total = _size("fsm_hip_tokens_total")
+    off_ptr = _dev("fsm_hip_tokens_off_device")
+    end_ptr = _dev("fsm_hip_tokens_end_device")
+    id_ptr = _dev("fsm_hip_tokens_id_device")
+    err_ptr = _dev("fsm_hip_tokens_err_device")
 
     def copy(self, extra: int = 0, fill: int = 0):
         """-> (off u64 [m + 1], end u64 [total], id u32 [total], err u64 [m]); extra: that many more entries in each array,
@@ -1739,64 +1643,31 @@ class HipTokens:
 
 # ---- matches: every match of every line, start / end / end-id, in one call (include/fsm_hip.h, "matches") ----
 
-class HipMatches:
+class HipMatches(_Freed):
     """struct fsm_hip_matches *: off[m + 1], start[total], end[total], id[total] on the device.  Keeps its two images (and its
     text and hits) alive: the matches must be freed first."""
 
-    def __init__(self, handle, keep=()):
-        self._lib = load_library()
-        self._h, self._keep = handle, keep
+    _FREE = "fsm_hip_matches_free"
 
     @classmethod
     def run(cls, starts: PosDfa, ends: TokDfa, base: np.ndarray, off: np.ndarray, pick=None, trim_byte: int = -1, flags: int = 0) -> "HipMatches":
         """fsm_hip_matches_run on host arrays"""
-        base, off, pick, n, m = _line_arrays(base, off, pick)
-        b = MatchBatch(_ptr0(base), _ptr(off), n, _ptr(pick), m, trim_byte, flags, 0)
+        b, _held = _host_batch(MatchBatch, base, off, pick, trim_byte, flags, 0)
         return cls(_call("fsm_hip_matches_run", starts.handle, ends.handle, C.byref(b)), (starts, ends))
 
     @classmethod
     def run_device(cls, starts: PosDfa, ends: TokDfa, d_base: int, d_off: int, n: int, d_pick: int = 0, m: int = 0, trim_byte: int = -1,
                    flags: int = 0, limit: int = 0, stream: int = 0) -> "HipMatches":
         """fsm_hip_matches_run_device: device addresses; the emit pass is in flight on `stream` at return"""
-        b = MatchBatch(d_base or None, d_off or None, n, d_pick or None, m, trim_byte, flags, limit)
+        b = _device_batch(MatchBatch, d_base, d_off, n, d_pick, m, trim_byte, flags, limit)
         return cls(_call("fsm_hip_matches_run_device", starts.handle, ends.handle, C.byref(b), stream or None), (starts, ends))
 
-    def free(self):
-        if getattr(self, "_h", None):
-            self._lib.fsm_hip_matches_free(self._h)
-            self._h = None
-            self._keep = None
-
-    close = free
-    __del__ = free
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def count(self) -> int:
-        return int(self._lib.fsm_hip_matches_count(self._h))
-
-    @property
-    def total(self) -> int:
-        return int(self._lib.fsm_hip_matches_total(self._h))
-
-    @property
-    def off_ptr(self) -> int:
-        return int(self._lib.fsm_hip_matches_off_device(self._h) or 0)
-
-    @property
-    def start_ptr(self) -> int:
-        return int(self._lib.fsm_hip_matches_start_device(self._h) or 0)
-
-    @property
-    def end_ptr(self) -> int:
-        return int(self._lib.fsm_hip_matches_end_device(self._h) or 0)
-
-    @property
-    def id_ptr(self) -> int:
-        return int(self._lib.fsm_hip_matches_id_device(self._h) or 0)
+    count = _size("fsm_hip_matches_count")
+    total = _size("fsm_hip_matches_total")
+    off_ptr = _dev("fsm_hip_matches_off_device")
+    start_ptr = _dev("fsm_hip_matches_start_device")
+    end_ptr = _dev("fsm_hip_matches_end_device")
+    id_ptr = _dev("fsm_hip_matches_id_device")
 
     def copy(self, extra: int = 0, fill: int = 0):
         """-> (off u64 [m + 1], start u64 [total], end u64 [total], id u32 [total]); extra: that many more entries in each array,
@@ -1809,14 +1680,13 @@ class HipMatches:
 
     def replace(self, repl: "HipRepl", base: np.ndarray, off: np.ndarray, pick=None, trim_byte: int = -1) -> "HipReplaced":
         """fsm_hip_matches_replace on host arrays: the batch these matches were made from"""
-        base, off, pick, n, m = _line_arrays(base, off, pick)
-        b = MatchBatch(_ptr0(base), _ptr(off), n, _ptr(pick), m, trim_byte, 0, 0)
+        b, _held = _host_batch(MatchBatch, base, off, pick, trim_byte, 0, 0)
         return HipReplaced(_call("fsm_hip_matches_replace", self._h, C.byref(b), repl.handle), (self, repl))
 
     def replace_device(self, repl: "HipRepl", d_base: int, d_off: int, n: int, d_pick: int = 0, m: int = 0, trim_byte: int = -1, limit: int = 0,
                        stream: int = 0) -> "HipReplaced":
         """fsm_hip_matches_replace_device: device addresses; the offsets and the write pass are in flight on `stream` at return"""
-        b = MatchBatch(d_base or None, d_off or None, n, d_pick or None, m, trim_byte, 0, limit)
+        b = _device_batch(MatchBatch, d_base, d_off, n, d_pick, m, trim_byte, 0, limit)
         return HipReplaced(_call("fsm_hip_matches_replace_device", self._h, C.byref(b), repl.handle, stream or None), (self, repl))
 
     def text_replace(self, repl: "HipRepl", text: "HipText", hits: Optional["HipHits"] = None, stream: int = 0) -> "HipReplaced":
@@ -1827,14 +1697,13 @@ class HipMatches:
     def extract(self, base: np.ndarray, off: np.ndarray, pick=None, trim_byte: int = -1, keep: Optional["HipRules"] = None,
                 sep_byte: int = -1) -> "HipExtracted":
         """fsm_hip_matches_extract on host arrays: the batch these matches were made from"""
-        base, off, pick, n, m = _line_arrays(base, off, pick)
-        b = MatchBatch(_ptr0(base), _ptr(off), n, _ptr(pick), m, trim_byte, 0, 0)
+        b, _held = _host_batch(MatchBatch, base, off, pick, trim_byte, 0, 0)
         return HipExtracted(_call("fsm_hip_matches_extract", self._h, C.byref(b), keep.handle if keep is not None else None, sep_byte), (self, keep))
 
     def extract_device(self, d_base: int, d_off: int, n: int, d_pick: int = 0, m: int = 0, trim_byte: int = -1, limit: int = 0,
                        keep: Optional["HipRules"] = None, sep_byte: int = -1, stream: int = 0) -> "HipExtracted":
         """fsm_hip_matches_extract_device: device addresses; the offsets and the write pass are in flight on `stream` at return"""
-        b = MatchBatch(d_base or None, d_off or None, n, d_pick or None, m, trim_byte, 0, limit)
+        b = _device_batch(MatchBatch, d_base, d_off, n, d_pick, m, trim_byte, 0, limit)
         return HipExtracted(_call("fsm_hip_matches_extract_device", self._h, C.byref(b), keep.handle if keep is not None else None, sep_byte,
                                   stream or None), (self, keep))
 
@@ -1854,17 +1723,18 @@ class HipMatches:
 
 # ---- replace: every match replaced by its rule's replacement, a fresh packed text (include/fsm_hip.h, "replace") ----
 
-class HipRepl:
+class HipRepl(_Freed):
     """struct fsm_hip_repl *: a replacement table on the current device, R[i] = table[i]; flags: REPL_MASK"""
 
+    _FREE = "fsm_hip_repl_free"
+
     def __init__(self, table: Sequence[bytes], flags: int = 0):
-        self._lib = load_library()
         table = [bytes(r) for r in table]
         data = np.frombuffer(b"".join(table), np.uint8)
         roff = np.zeros(len(table) + 1, np.uint64)
         if table:
             roff[1:] = np.cumsum([len(r) for r in table])
-        self._h = _call("fsm_hip_repl_create", _ptr0(data), _ptr(roff) if table else None, len(table), flags)
+        super().__init__(_call("fsm_hip_repl_create", _ptr0(data), _ptr(roff) if table else None, len(table), flags))
         self.nrepl, self.flags = len(table), flags
 
     @classmethod
@@ -1872,7 +1742,6 @@ class HipRepl:
         """fsm_hip_repl_create_template: inserts[i] = the positions in table[i] at which the match itself is put (sed's &), ascending,
         each 0 .. len(table[i]); inserts None: no rule has one (ioff NULL)"""
         self = cls.__new__(cls)
-        self._lib = load_library()
         table = [bytes(r) for r in table]
         data = np.frombuffer(b"".join(table), np.uint8)
         roff = np.zeros(len(table) + 1, np.uint64)
@@ -1886,8 +1755,8 @@ class HipRepl:
             if table:
                 ioff[1:] = np.cumsum([len(a) for a in inserts])
             ins = np.array([int(x) for a in inserts for x in a], np.uint64)
-        self._h = _call("fsm_hip_repl_create_template", _ptr0(data), _ptr(roff) if table else None, len(table),
-                        _ptr(ins) if ins is not None and len(ins) else None, _ptr(ioff) if ioff is not None else None, flags)
+        _Owned.__init__(self, _call("fsm_hip_repl_create_template", _ptr0(data), _ptr(roff) if table else None, len(table),
+                                    _ptr(ins) if ins is not None and len(ins) else None, _ptr(ioff) if ioff is not None else None, flags))
         self.nrepl, self.flags = len(table), flags
         return self
 
@@ -1919,68 +1788,26 @@ class HipRepl:
         return cls.template([p[0] for p in parsed], [p[1] for p in parsed])
 
     @property
-    def handle(self):
-        return self._h
-
-    @property
     def in_lds(self) -> bool:
         return bool(self._lib.fsm_hip_repl_in_lds(self._h))
 
-    @property
-    def inserts(self) -> int:
-        """the table's inserts, over all rules; 0 for a plain table"""
-        return int(self._lib.fsm_hip_repl_inserts(self._h))
+    inserts = _size("fsm_hip_repl_inserts", "the table's inserts, over all rules; 0 for a plain table")
 
     @staticmethod
     def max_inserts() -> int:
         """fsm_hip_repl_max_inserts: per rule"""
         return int(load_library().fsm_hip_repl_max_inserts())
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.fsm_hip_repl_free(self._h)
-            self._h = None
 
-    free = close
-    __del__ = close
-
-
-class HipReplaced:
+class HipReplaced(_Freed):
     """struct fsm_hip_replaced *: out_off[m + 1] and the bytes on the device.  Keeps its matches and its table (and its text and
     hits) alive: the replaced object must be freed first."""
 
-    def __init__(self, handle, keep=()):
-        self._lib = load_library()
-        self._h, self._keep = handle, keep
-
-    def free(self):
-        if getattr(self, "_h", None):
-            self._lib.fsm_hip_replaced_free(self._h)
-            self._h = None
-            self._keep = None
-
-    close = free
-    __del__ = free
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def count(self) -> int:
-        return int(self._lib.fsm_hip_replaced_count(self._h))
-
-    @property
-    def nbytes(self) -> int:
-        return int(self._lib.fsm_hip_replaced_nbytes(self._h))
-
-    @property
-    def off_ptr(self) -> int:
-        return int(self._lib.fsm_hip_replaced_off_device(self._h) or 0)
-
-    @property
-    def bytes_ptr(self) -> int:
-        return int(self._lib.fsm_hip_replaced_bytes_device(self._h) or 0)
+    _FREE = "fsm_hip_replaced_free"
+    count = _size("fsm_hip_replaced_count")
+    nbytes = _size("fsm_hip_replaced_nbytes")
+    off_ptr = _dev("fsm_hip_replaced_off_device")
+    bytes_ptr = _dev("fsm_hip_replaced_bytes_device")
 
     def copy(self, extra: int = 0, fill: int = 0):
         """-> (off u64 [m + 1], bytes u8 [nbytes]); extra: that many more entries in each array, pre-filled with `fill` and left
@@ -2026,77 +1853,33 @@ def repl_max_inserts() -> int:
 
 # ---- extract: every kept match's bytes as a record of a fresh packed text (include/fsm_hip.h, "extract") ----
 
-class HipRules:
+class HipRules(_Freed):
     """struct fsm_hip_rules *: a set of rules on the current device; rules: the ids that are kept, all below nrules; flags:
     RULES_KEEP_OTHER"""
 
+    _FREE = "fsm_hip_rules_free"
+
     def __init__(self, rules: Sequence[int], nrules: int, flags: int = 0):
-        self._lib = load_library()
         bits = np.zeros((nrules + 7) // 8, np.uint8)
         for i in rules:
             if not 0 <= i < nrules:
                 raise ValueError("rule %d outside the set of %d" % (i, nrules))
             bits[i >> 3] |= 1 << (i & 7)
-        self._h = _call("fsm_hip_rules_create", _ptr(bits) if nrules else None, nrules, flags)
+        super().__init__(_call("fsm_hip_rules_create", _ptr(bits) if nrules else None, nrules, flags))
         self.nrules, self.flags = nrules, flags
 
-    @property
-    def handle(self):
-        return self._h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.fsm_hip_rules_free(self._h)
-            self._h = None
-
-    free = close
-    __del__ = close
-
-
-class HipExtracted:
+class HipExtracted(_Freed):
     """struct fsm_hip_extracted *: off[R + 1], the bytes, line[R] and match[R] on the device.  Keeps its matches and its set (and
     its text and hits) alive: the extracted object must be freed first."""
 
-    def __init__(self, handle, keep=()):
-        self._lib = load_library()
-        self._h, self._keep = handle, keep
-
-    def free(self):
-        if getattr(self, "_h", None):
-            self._lib.fsm_hip_extracted_free(self._h)
-            self._h = None
-            self._keep = None
-
-    close = free
-    __del__ = free
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def count(self) -> int:
-        return int(self._lib.fsm_hip_extracted_count(self._h))
-
-    @property
-    def nbytes(self) -> int:
-        return int(self._lib.fsm_hip_extracted_nbytes(self._h))
-
-    @property
-    def off_ptr(self) -> int:
-        return int(self._lib.fsm_hip_extracted_off_device(self._h) or 0)
-
-    @property
-    def bytes_ptr(self) -> int:
-        return int(self._lib.fsm_hip_extracted_bytes_device(self._h) or 0)
-
-    @property
-    def line_ptr(self) -> int:
-        return int(self._lib.fsm_hip_extracted_line_device(self._h) or 0)
-
-    @property
-    def match_ptr(self) -> int:
-        return int(self._lib.fsm_hip_extracted_match_device(self._h) or 0)
+    _FREE = "fsm_hip_extracted_free"
+    count = _size("fsm_hip_extracted_count")
+    nbytes = _size("fsm_hip_extracted_nbytes")
+    off_ptr = _dev("fsm_hip_extracted_off_device")
+    bytes_ptr = _dev("fsm_hip_extracted_bytes_device")
+    line_ptr = _dev("fsm_hip_extracted_line_device")
+    match_ptr = _dev("fsm_hip_extracted_match_device")
 
     def copy(self, extra: int = 0, fill: int = 0):
         """-> (off u64 [R + 1], bytes u8 [nbytes], line u64 [R], match u64 [R]); extra: that many more entries in each array,

@@ -2,9 +2,9 @@
 of the block pairs in text.hip).
 
 off, every byte, line and match are compared with tests/extract_ref.py, the definition of include/fsm_hip.h ("extract") restated
-in Python, over the matches of tests/matches_ref.py -- never over matches or offsets that came from the device.  The inputs are
-those of tests/test_gpu_replace.py, rebuilt here: 1 500 rows of at most 300 bytes with lengths 0, 1, 15, 16, 17, 31, 32, 33, ...,
-line 8 = 300 times d, and LEAD = 5 bytes in front of the text that belong to no line."""
+in Python, over the matches of tests/matches_ref.py -- never over matches or offsets that came from the device.  The inputs, the
+automata and the matches' judge are tests/line_inputs.py's: 1 500 rows of at most 300 bytes with lengths 0, 1, 15, 16, 17, 31, 32,
+33, ..., line 8 = 300 times d, and LEAD = 5 bytes in front of the text that belong to no line."""
 import ctypes as C
 import errno
 import os
@@ -16,25 +16,15 @@ import pytest
 import extract_ref
 import matches_ref
 import span_ref
-import tokens_ref
 from extract_ref import KEEP_OTHER
-from global_ref import affine, packed
+from line_inputs import (EMPTY_RULE, FILL, KEYWORDS, LEAD, SIZES, auto_of, device_u64, device_u8, ends_image, inputs_of, judged, lead_packed, reference,
+                         starts_image, state_ids)
 from matches_ref import DROP_EMPTY
-from tokens_ref import EARLIEST
 
 pytestmark = pytest.mark.gpu
 
-FILL = 0xA5A5A5A5A5A5A5A5
-LEAD = 5
 NL = 0x0A
-AUTOMATA = {            # name -> (S, K, the start state is an end state too, walked from LDS)
-    "s15_start": (15, 4, True, True),
-    "glob_first": (1024, 16, False, False),
-}
-SIZES = (1, 63, 64, 65, 255, 256, 257, 1500)
 SEPS = (-1, NL, 0)
-WORDS = [b"ab", b"abc", b"ca", b"d", b"bdb"]
-EMPTY_RULE = len(WORDS)                  # the id of the empty string in kw_ends_empty_ids
 NO_ID = 0xFFFFFFFE
 
 
@@ -46,130 +36,6 @@ def hip(built):
     import libfsm_amd
     libfsm_amd.load_library()   # raises if the HIP extension is missing: no silent fallback
     return libfsm_amd
-
-
-def device_u64(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()
-
-
-def device_u8(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint8).copy()).cuda()
-
-
-def make_inputs():
-    """1 500 rows of 300 random bytes; lengths 0, 1, 15, 16, 17, 31, 32, 33, then odd rows 0-12 and even rows 0-300"""
-    rng = np.random.RandomState(11)
-    rows = rng.randint(0, 256, (1500, 300)).astype(np.uint8)
-    lens = np.where(np.arange(1500) % 2 == 1, rng.randint(0, 13, 1500), rng.randint(0, 301, 1500)).astype(np.int64)
-    lens[:8] = [0, 1, 15, 16, 17, 31, 32, 33]
-    return rows, lens
-
-
-def keyword_inputs():
-    """the same 1 500 lengths, the lines built from the keywords and a filler letter now and then; line 8: 300 times d"""
-    rng = np.random.RandomState(19)
-    _, lens = make_inputs()
-    pieces = WORDS + [b"x", b"a", b"b"]
-    rows = np.zeros((1500, 300), np.uint8)
-    for i in range(1500):
-        line = b"".join(pieces[k] for k in rng.randint(0, len(pieces), 300))[:300]
-        rows[i] = np.frombuffer(line, np.uint8)
-    lens = lens.copy()
-    lens[8] = 300
-    rows[8] = ord("d")
-    return rows, lens
-
-
-def lead_packed(rows, lens, lead=LEAD):
-    """the lines packed behind `lead` bytes that belong to no line: (bytes of exactly off[n], off with off[0] = lead)"""
-    data, off = packed(rows, lens)
-    return np.concatenate([np.full(lead, 0x5A, np.uint8), data]), off + np.uint64(lead)
-
-
-_inputs, _autos, _starts, _ends, _refs = {}, {}, {}, {}, {}
-
-
-def inputs_of(name):
-    kind = "keywords" if name.startswith("kw") else "random"
-    if kind not in _inputs:
-        _inputs[kind] = keyword_inputs() if kind == "keywords" else make_inputs()
-        for a in _inputs[kind]:
-            a.setflags(write=False)
-    return _inputs[kind]
-
-
-def auto_of(name):
-    """name -> (auto, {state: ids} or None)"""
-    if name not in _autos:
-        from libfsm_amd import FlatDfa
-        if name in AUTOMATA:
-            S, K, start_ends, _ = AUTOMATA[name]
-            auto = affine(S, K, endids=True)
-            if start_ends:
-                auto = span_ref.start_accepting_of(auto)
-            _autos[name] = (auto, None)
-        elif name == "kw_starts":
-            _autos[name] = (span_ref.starts_of(WORDS), None)
-        elif name == "kw_starts_everywhere":
-            _autos[name] = (span_ref.everywhere_of(span_ref.starts_of(WORDS)), None)
-        elif name == "kw_ends":
-            _autos[name] = tokens_ref.trie_lexer(WORDS)
-        elif name == "d_starts":
-            _autos[name] = (span_ref.starts_of([b"d"]), None)
-        elif name == "d_plus":                      # d+, rule 0
-            dense = np.full((2, 256), -1, np.int64)
-            dense[0, ord("d")] = dense[1, ord("d")] = 1
-            sets = {1: [0]}
-            _autos[name] = ((FlatDfa.from_dense(dense, 0, np.array([0, 1], np.uint8), endids=sets), dense, np.arange(256, dtype=np.int64)), sets)
-        else:
-            assert name == "kw_ends_empty_ids"      # the keywords and, as rule EMPTY_RULE, the empty string
-            auto, sets = tokens_ref.trie_lexer(WORDS)
-            sets = dict(sets)
-            sets[0] = [EMPTY_RULE]
-            is_end = np.asarray(auto[0].is_end, np.uint8).copy()
-            is_end[0] = 1
-            _autos[name] = ((FlatDfa.from_dense(auto[1], 0, is_end, endids=sets), auto[1], auto[2]), sets)
-    return _autos[name]
-
-
-def starts_image(name):
-    if name not in _starts:
-        from libfsm_amd import PosDfa
-        _starts[name] = PosDfa.from_flat(auto_of(name)[0][0])
-    return _starts[name]
-
-
-def ends_image(name):
-    if name not in _ends:
-        from libfsm_amd import TokDfa
-        _ends[name] = TokDfa.from_flat(auto_of(name)[0][0], EARLIEST)
-    return _ends[name]
-
-
-def state_ids(name):
-    auto, sets = auto_of(name)
-    return tokens_ref.state_ids(auto, EARLIEST, sets)
-
-
-def reference(starts, ends, flags=0):
-    """the matches' judge for all 1 500 inputs of a pair, computed once and left unchanged"""
-    key = (starts, ends, flags)
-    if key not in _refs:
-        rows, lens = inputs_of(ends)
-        assert inputs_of(starts) is inputs_of(ends)
-        res = matches_ref.matches(auto_of(starts)[0], auto_of(ends)[0], rows, lens, flags, ids=state_ids(ends))
-        for v in res.values():
-            v.setflags(write=False)
-        _refs[key] = res
-    return _refs[key]
-
-
-def judged(starts, ends, rows, lens, flags=0):
-    """the matches' judge on other lines than the 1 500: (off, start, end, id)"""
-    r = matches_ref.matches(auto_of(starts)[0], auto_of(ends)[0], rows, lens, flags, ids=state_ids(ends))
-    return r["off"], r["start"], r["end"], r["id"]
 
 
 def rules_of(hip, keep, other=False):
@@ -237,8 +103,8 @@ def host_form(hip, mt, b, keep=None, sep=-1, trim_byte=-1):
 def kw_sets():
     """(the judge's keep, keep_other) of the keyword pair: no set, each single rule, an empty set, a set with and without
     KEEP_OTHER whose nrules leaves rules 3 and 4 beyond it"""
-    sets = [(None, False)] + [((len(WORDS), {i}), False) for i in range(len(WORDS))]
-    return sets + [((len(WORDS), set()), False), ((3, {0, 2}), False), ((3, {0, 2}), True), ((0, set()), True)]
+    sets = [(None, False)] + [((len(KEYWORDS), {i}), False) for i in range(len(KEYWORDS))]
+    return sets + [((len(KEYWORDS), set()), False), ((3, {0, 2}), False), ((3, {0, 2}), True), ((0, set()), True)]
 
 
 # ---- group 1: every size, every separator, every kind of set -----------------------------------------------------------------
@@ -315,10 +181,10 @@ def test_kept_records_around_a_block_of_matches(hip):
         b = Batch(*lead_packed(rows, lens))
         mt = device_matches(hip, pd, td, b)
         for sep in SEPS:
-            want = extract_ref.extract(rows, lens, lens, mt_ref, (len(WORDS), {3}), False, sep)
+            want = extract_ref.extract(rows, lens, lens, mt_ref, (len(KEYWORDS), {3}), False, sep)
             assert len(want[2]) == R and len(mt_ref[1]) >= R + 3
             assert bytes(want[1]) == (b"d" + bytes([sep]) if sep >= 0 else b"d") * R
-            check(device_form(hip, mt, b, rules_of(hip, (len(WORDS), {3})), sep), want, ("set", R, sep))
+            check(device_form(hip, mt, b, rules_of(hip, (len(KEYWORDS), {3})), sep), want, ("set", R, sep))
         # ... and by m: the same lines without those of ab hold exactly R matches, every one kept
         lines = [x for x in lines if b"ab" not in x]
         rows, lens = span_ref.rows_of(lines)
@@ -340,7 +206,7 @@ def test_pick_and_limit(hip, starts, ends):
     rng = np.random.RandomState(12)
     pick = np.concatenate([rng.permutation(n)[:300], [7, 7, 7, 0, n - 1, n - 1, 8, 8], rng.randint(0, n, 100), np.arange(n)[::-1][:50]]).astype(np.uint64)
     res = reference(starts, ends)
-    keep = (len(WORDS), {0, 3}) if ends == "kw_ends" else (int(np.median(res["id"][res["id"] < NO_ID])) + 1, set(range(0, 4000, 3)))
+    keep = (len(KEYWORDS), {0, 3}) if ends == "kw_ends" else (int(np.median(res["id"][res["id"] < NO_ID])) + 1, set(range(0, 4000, 3)))
     keep = (keep[0], {i for i in keep[1] if i < keep[0]})
 
     def want_of(p, k, other, sep, nlines=n):
@@ -402,13 +268,13 @@ def test_trim_byte_set_and_unset(hip):
     trimmed, plain = judged("kw_starts", "kw_ends", rows, shorter), matches_ref.head(reference("kw_starts", "kw_ends"), n)
     assert len(trimmed[1]) < len(plain[1])
     for sep in (-1, NL):
-        want = extract_ref.extract(rows, shorter, lens, trimmed, (len(WORDS), {0, 3, 4}), False, sep)
-        check(device_form(hip, device_matches(hip, pd, td, b, trim_byte=trim), b, rules_of(hip, (len(WORDS), {0, 3, 4})), sep, trim_byte=trim), want,
+        want = extract_ref.extract(rows, shorter, lens, trimmed, (len(KEYWORDS), {0, 3, 4}), False, sep)
+        check(device_form(hip, device_matches(hip, pd, td, b, trim_byte=trim), b, rules_of(hip, (len(KEYWORDS), {0, 3, 4})), sep, trim_byte=trim), want,
               ("trim, device", sep))
-        check(host_form(hip, host_matches(hip, pd, td, b, trim_byte=trim), b, rules_of(hip, (len(WORDS), {0, 3, 4})), sep, trim_byte=trim), want,
+        check(host_form(hip, host_matches(hip, pd, td, b, trim_byte=trim), b, rules_of(hip, (len(KEYWORDS), {0, 3, 4})), sep, trim_byte=trim), want,
               ("trim, host", sep))
-        want = extract_ref.extract(rows, lens, lens, plain, (len(WORDS), {0, 3, 4}), False, sep)
-        check(device_form(hip, device_matches(hip, pd, td, b), b, rules_of(hip, (len(WORDS), {0, 3, 4})), sep), want, ("no trim", sep))
+        want = extract_ref.extract(rows, lens, lens, plain, (len(KEYWORDS), {0, 3, 4}), False, sep)
+        check(device_form(hip, device_matches(hip, pd, td, b), b, rules_of(hip, (len(KEYWORDS), {0, 3, 4})), sep), want, ("no trim", sep))
 
 
 # ---- group 3: one long record, runs of empty records -------------------------------------------------------------------------
@@ -539,7 +405,7 @@ def test_text_extract_over_a_text_and_its_hits_and_the_result_fed_back(hip):
     raw_rows, raws = span_ref.rows_of(with_nl)
     mt_ref = judged("kw_starts", "kw_ends", rows, lens)
     res = dict(off=mt_ref[0], start=mt_ref[1], end=mt_ref[2], id=mt_ref[3])
-    keep = (len(WORDS), {1, 2, 3})
+    keep = (len(KEYWORDS), {1, 2, 3})
     rs = rules_of(hip, keep)
     for k, r, sep in ((None, None, NL), (keep, rs, NL), (keep, rs, -1)):
         want = extract_ref.extract(raw_rows, lens, raws, mt_ref, k, False, sep)
@@ -551,7 +417,7 @@ def test_text_extract_over_a_text_and_its_hits_and_the_result_fed_back(hip):
     want = extract_ref.extract(raw_rows, lens, raws, mt_ref, keep, False, NL)
     check(host_form(hip, host_matches(hip, pd, td, b, trim_byte=NL), b, rs, NL, trim_byte=NL), want, "primitive, host")
     check(device_form(hip, device_matches(hip, pd, td, b, trim_byte=NL), b, rs, NL, trim_byte=NL), want, "primitive, device")
-    ld = hip.LinesDfa(span_ref.line_matcher_of(WORDS)[0], NL)
+    ld = hip.LinesDfa(span_ref.line_matcher_of(KEYWORDS)[0], NL)
     kinds = {"plain": text.hits(ld), "no bytes": text.hits(ld, want_bytes=False), "inverted": text.hits(ld, invert=True)}
     assert 100 < kinds["plain"].count < 300
     for what, hits in kinds.items():
@@ -599,11 +465,11 @@ def test_refusals_with_a_device(hip):
     n = 64
     data, off = lead_packed(rows[:n], lens[:n])
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
-    bits = extract_ref.pack_rules({0, 3}, len(WORDS))
+    bits = extract_ref.pack_rules({0, 3}, len(KEYWORDS))
     for args in ((None, 5, 0), (ptr(bits), 5, 2), (ptr(bits), 5, 0x80000000)):
         C.set_errno(0)
         assert lib.fsm_hip_rules_create(*args) is None and C.get_errno() == errno.EINVAL, args
-    rs = hip.HipRules([0, 3], len(WORDS))
+    rs = hip.HipRules([0, 3], len(KEYWORDS))
     none = hip.HipRules([], 0)                                              # nrules == 0 is valid
     mt = hip.HipMatches.run(pd, td, data, off)
     good = dict(base=ptr(data), off=ptr(off), n=n, trim_byte=-1)
@@ -634,7 +500,7 @@ def test_refusals_with_a_device(hip):
         C.set_errno(0)
         assert lib.fsm_hip_text_extract(*args) is None and C.get_errno() == errno.EINVAL, args
     mt_ref = matches_ref.head(reference("kw_starts", "kw_ends"), n)
-    want = extract_ref.extract(rows[:n], lens[:n], lens[:n], mt_ref, (len(WORDS), {0, 3}), False, NL)
+    want = extract_ref.extract(rows[:n], lens[:n], lens[:n], mt_ref, (len(KEYWORDS), {0, 3}), False, NL)
     check(mt.extract(data, off, keep=rs, sep_byte=NL), want, "the next call answers")
     check(mt.extract(data, off, keep=none, sep_byte=NL), extract_ref.extract(rows[:n], lens[:n], lens[:n], mt_ref, (0, set()), False, NL), "an empty set")
     got = tm.text_extract(text, keep=None, sep_byte=NL)
@@ -651,7 +517,7 @@ def test_example_prints_what_grep_o_prints(hip, tmp_path):
     files = [[bytes(rng.choice(list(b"abcdxyzw" if i % 2 == 0 else b"xyzwba"), rng.randint(0, 25)).astype(np.uint8)) for i in range(k)] for k in (70, 40, 25)]
     files[2][-1] = b"xxabcabd"
     tables = []
-    for nm, auto in (("lines", span_ref.line_matcher_of(WORDS)), ("starts", auto_of("kw_starts")[0]), ("ends", auto_of("kw_ends")[0])):
+    for nm, auto in (("lines", span_ref.line_matcher_of(KEYWORDS)), ("starts", auto_of("kw_starts")[0]), ("ends", auto_of("kw_ends")[0])):
         tables.append(str(tmp_path / (nm + ".fsmhip")))
         auto[0].write_c(tables[-1])
     names = []
@@ -685,7 +551,7 @@ def test_example_prints_what_grep_o_prints(hip, tmp_path):
         return out
 
     want = compose()
-    assert want.count(b"\n") > 100 and want.endswith(b"abc\nab\nd\n") and {b"ab", b"abc", b"ca", b"d", b""} <= set(want.split(b"\n")) <= set(WORDS) | {b""}
+    assert want.count(b"\n") > 100 and want.endswith(b"abc\nab\nd\n") and {b"ab", b"abc", b"ca", b"d", b""} <= set(want.split(b"\n")) <= set(KEYWORDS) | {b""}
     assert run() == (0, want)
     assert run("-H", "-n", "-b") == (0, compose(None, True, True, True))
     assert run("-n") == (0, compose(None, number=True))

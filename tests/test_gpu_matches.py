@@ -3,8 +3,7 @@
 Every answer -- count, match_off, start, end, id, total -- is compared with tests/matches_ref.py, the definition of
 include/fsm_hip.h ("matches") restated in Python over the automata's own formulas, never with the rounds on the device or with
 anything else derived from the code under test.  The automata are global_ref.affine's (those of tests/test_gpu_spans.py),
-span_ref's variants of them and its Python Aho-Corasick; the inputs are the 1 500 rows of tests/test_gpu_spans.py, rebuilt
-here."""
+span_ref's variants of them and its Python Aho-Corasick; inputs, automata and the judge's cache are tests/line_inputs.py's."""
 import ctypes as C
 import errno
 
@@ -14,24 +13,12 @@ import pytest
 import matches_ref
 import span_ref
 import tokens_ref
-from global_ref import affine, packed
+from line_inputs import (AUTOMATA, FILL, KEYWORDS, LEAD, SIZES, auto_of, device_u64, device_u8, ends_image, inputs_of, judged, lead_packed, marks_of,
+                         reference, starts_image, state_ids)
 from matches_ref import DROP_EMPTY
 from tokens_ref import EARLIEST, RET
 
 pytestmark = pytest.mark.gpu
-
-FILL = 0xA5A5A5A5A5A5A5A5
-LEAD = 5                                     # off[0]: the text does not begin at base
-# name -> (S, K, keyword arguments, the start state is an end state too, walked from LDS)
-AUTOMATA = {
-    "s15_start": (15, 4, {}, True, True),
-    "s200_dying": (200, 4, dict(holes=16, sinks=3), False, True),
-    "lds_full": (1023, 16, {}, False, True),                        # 1024 * 16 = 16 384 entries: the largest LDS image
-    "glob_first": (1024, 16, {}, False, False),                     # 1025 * 16 = 16 400 entries: the first global image
-    "dying1023": (1023, 16, dict(holes=8, sinks=4), False, True),
-}
-SIZES = (1, 63, 64, 65, 255, 256, 257, 1500)
-WORDS = [b"ab", b"abc", b"ca", b"d", b"bdb"]
 
 
 @pytest.fixture(scope="module")
@@ -42,140 +29,6 @@ def hip(built):
     import libfsm_amd
     libfsm_amd.load_library()   # raises if the HIP extension is missing: no silent fallback
     return libfsm_amd
-
-
-def device_u64(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()
-
-
-def device_u8(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint8).copy()).cuda()
-
-
-def make_inputs():
-    """1 500 rows of 300 random bytes; lengths 0, 1, 15, 16, 17, 31, 32, 33, then odd rows 0-12 and even rows 0-300"""
-    rng = np.random.RandomState(11)
-    rows = rng.randint(0, 256, (1500, 300)).astype(np.uint8)
-    lens = np.where(np.arange(1500) % 2 == 1, rng.randint(0, 13, 1500), rng.randint(0, 301, 1500)).astype(np.int64)
-    lens[:8] = [0, 1, 15, 16, 17, 31, 32, 33]
-    return rows, lens
-
-
-def keyword_inputs():
-    """the same 1 500 lengths, the lines built from the keywords and a filler letter now and then; line 8: 300 times d"""
-    rng = np.random.RandomState(19)
-    _, lens = make_inputs()
-    pieces = WORDS + [b"x", b"a", b"b"]
-    rows = np.zeros((1500, 300), np.uint8)
-    for i in range(1500):
-        line = b"".join(pieces[k] for k in rng.randint(0, len(pieces), 300))[:300]
-        rows[i] = np.frombuffer(line, np.uint8)
-    lens = lens.copy()
-    lens[8] = 300
-    rows[8] = ord("d")
-    return rows, lens
-
-
-def lead_packed(rows, lens, lead=LEAD):
-    """the lines packed behind `lead` bytes that belong to no line: (bytes of exactly off[n], off with off[0] = lead)"""
-    data, off = packed(rows, lens)
-    return np.concatenate([np.full(lead, 0x5A, np.uint8), data]), off + np.uint64(lead)
-
-
-_inputs, _autos, _starts, _ends, _marks, _longest, _refs = {}, {}, {}, {}, {}, {}, {}
-
-
-def inputs_of(name):
-    kind = "keywords" if name.startswith("kw") else "random"
-    if kind not in _inputs:
-        _inputs[kind] = keyword_inputs() if kind == "keywords" else make_inputs()
-        for a in _inputs[kind]:
-            a.setflags(write=False)
-    return _inputs[kind]
-
-
-def auto_of(name):
-    """name -> (auto, {state: ids} or None, walked from LDS or None: not asserted)"""
-    if name not in _autos:
-        if name in AUTOMATA:
-            S, K, kw, start_ends, in_lds = AUTOMATA[name]
-            auto = affine(S, K, endids=True, **kw)
-            if start_ends:     # (with_is_end drops the ids: such an `ends` gives FSM_HIP_NO_ID everywhere)
-                auto = span_ref.start_accepting_of(auto)
-            from libfsm_amd import Plan
-            plan = Plan(auto[0])
-            assert (plan.S1, plan.C) == (S + 1, K) and (plan.S1 * plan.C <= 16384) == in_lds
-            _autos[name] = (auto, None, in_lds)
-        elif name == "kw_starts":
-            _autos[name] = (span_ref.starts_of(WORDS), None, None)
-        elif name == "kw_starts_everywhere":
-            _autos[name] = (span_ref.everywhere_of(span_ref.starts_of(WORDS)), None, None)
-        elif name in ("kw_ends", "kw_ends_two"):
-            auto, sets = tokens_ref.trie_lexer(WORDS)
-            if name == "kw_ends_two":           # a union where the state of "ab" carries two ids
-                from libfsm_amd import FlatDfa
-                sets = {s: ([3, 9] if v == [0] else [v[0] + 10]) for s, v in sets.items()}
-                auto = (FlatDfa.from_dense(auto[1], 0, np.asarray(auto[0].is_end, np.uint8), endids=sets), auto[1], auto[2])
-            _autos[name] = (auto, sets, None)
-        elif name == "sink_one":                # one accepting state, every byte leads back to it: an absorbing START state
-            _autos[name] = (span_ref._auto(np.zeros((1, 256), np.int64), [True]), None, None)
-        else:
-            assert name == "kw_ends_empty"
-            _autos[name] = (span_ref.ends_of(WORDS, empty=True), None, None)
-        assert _autos[name][0][0].start == 0
-    return _autos[name]
-
-
-def starts_image(name):
-    if name not in _starts:
-        from libfsm_amd import PosDfa
-        auto, _, in_lds = auto_of(name)
-        pd = PosDfa.from_flat(auto[0])
-        assert in_lds is None or pd.in_lds == in_lds       # the form, before any launch
-        _starts[name] = pd
-    return _starts[name]
-
-
-def ends_image(name, mode=EARLIEST):
-    if (name, mode) not in _ends:
-        from libfsm_amd import TokDfa
-        auto, _, in_lds = auto_of(name)
-        td = TokDfa.from_flat(auto[0], mode)
-        assert in_lds is None or td.in_lds == in_lds
-        _ends[name, mode] = td
-    return _ends[name, mode]
-
-
-def state_ids(name, mode):
-    """the id of every state of an `ends` (an automaton without ids: NO_ID under EARLIEST, the one empty set under RET)"""
-    auto, sets, _ = auto_of(name)
-    return tokens_ref.state_ids(auto, mode, sets)
-
-
-def reference(starts, ends, flags=0, mode=EARLIEST):
-    """the judge's answer for all 1 500 inputs of a pair, computed once and left unchanged; the marks of a `starts` and the
-    longest ends of an `ends` are shared by the pairs they are part of"""
-    key = (starts, ends, flags, mode)
-    if key not in _refs:
-        rows, lens = inputs_of(ends)
-        assert inputs_of(starts) is inputs_of(ends)
-        if starts not in _marks:
-            _marks[starts] = matches_ref.marks(auto_of(starts)[0], rows, lens)
-        if ends not in _longest:
-            _longest[ends] = matches_ref.longest_from(auto_of(ends)[0], rows, lens)
-        res = matches_ref.matches(None, None, rows, lens, flags, ids=state_ids(ends, mode), tables=(_marks[starts],) + _longest[ends])
-        for v in res.values():
-            v.setflags(write=False)
-        _refs[key] = res
-    return _refs[key]
-
-
-def judged(starts, ends, rows, lens, flags=0, mode=EARLIEST):
-    """the judge on other lines than the 1 500: (off, start, end, id)"""
-    r = matches_ref.matches(auto_of(starts)[0], auto_of(ends)[0], rows, lens, flags, ids=state_ids(ends, mode))
-    return r["off"], r["start"], r["end"], r["id"]
 
 
 def check(mt, want, what, m=None):
@@ -273,8 +126,7 @@ def test_pairs_with_holes_and_sinks(hip, starts, ends):
 def test_start_states_that_are_end_states(hip):
     """`starts` with an accepting start state: M(len).  `ends` with one: empty matches and the end + 1 step, kept and dropped"""
     _, lens = inputs_of("s15_start")
-    reference("s15_start", "s200_dying")
-    assert _marks["s15_start"][np.arange(1500), lens].all()             # every line has M(len)
+    assert marks_of("s15_start")[np.arange(1500), lens].all()             # every line has M(len)
     for n in (257, 1500):
         both_forms(hip, "s15_start", "s200_dying", n)
     kept, dropped = reference("s200_dying", "s15_start"), reference("s200_dying", "s15_start", DROP_EMPTY)
@@ -295,8 +147,7 @@ def test_absorbing_start_states(hip):
     """a one-state accepting sink.  As `starts` nothing is looked up and every position is marked, the top word only up to len
     (walk_mark's branch behind its loop); as `ends` the walk has sunk before its first byte: end = len from the start state"""
     _, lens = inputs_of("sink_one")
-    reference("sink_one", "s200_dying")
-    M = _marks["sink_one"]
+    M = marks_of("sink_one")
     assert (M == (np.arange(M.shape[1])[None, :] <= lens[:, None])).all()
     both = reference("sink_one", "sink_one")                 # (0, len), then the empty match at len
     assert np.array_equal(np.diff(both["off"].astype(np.int64)), np.where(lens > 0, 2, 1))
@@ -321,12 +172,12 @@ def test_many_matches_in_one_line_are_leftmost_longest(hip):
     res = reference("kw_starts", "kw_ends")
     off = res["off"].astype(np.int64)
     assert int(lens[8]) == 300 and off[9] - off[8] == 300               # 300 times d: 300 matches from one call
-    assert res["start"][off[8]:off[9]].tolist() == list(range(300)) and (res["id"][off[8]:off[9]] == WORDS.index(b"d")).all()
+    assert res["start"][off[8]:off[9]].tolist() == list(range(300)) and (res["id"][off[8]:off[9]] == KEYWORDS.index(b"d")).all()
     for i in (2, 4, 8, 100, 640, 1498):                                 # the judge against the brute force, and the ids against the words
         line = bytes(rows[i, :lens[i]])
         got = list(zip(res["start"][off[i]:off[i + 1]].tolist(), res["end"][off[i]:off[i + 1]].tolist()))
-        assert got == span_ref.leftmost_longest(WORDS, line)
-        assert [WORDS[int(k)] for k in res["id"][off[i]:off[i + 1]]] == [line[s:e] for s, e in got]
+        assert got == span_ref.leftmost_longest(KEYWORDS, line)
+        assert [KEYWORDS[int(k)] for k in res["id"][off[i]:off[i + 1]]] == [line[s:e] for s, e in got]
     cnt = np.diff(off)
     print("matches a line:", cnt.mean(), "most:", cnt.max(), "bytes a match:", lens.sum() / cnt.sum())
     assert cnt.max() == 300 and (cnt >= 16).mean() >= 0.3
@@ -339,8 +190,8 @@ def test_earliest_against_ret(hip):
     e, r = reference("kw_starts", "kw_ends_two", 0, EARLIEST), reference("kw_starts", "kw_ends_two", 0, RET)
     assert np.array_equal(e["start"], r["start"]) and np.array_equal(e["end"], r["end"])
     is_ab = (e["end"] - e["start"] == 2) & (e["id"] == 3)
-    assert is_ab.sum() >= 1000 and (r["id"][is_ab] == len(WORDS) - 1).all() and set(e["id"].tolist()) == {3, 11, 12, 13, 14}
-    assert set(r["id"].tolist()) == set(range(len(WORDS)))
+    assert is_ab.sum() >= 1000 and (r["id"][is_ab] == len(KEYWORDS) - 1).all() and set(e["id"].tolist()) == {3, 11, 12, 13, 14}
+    assert set(r["id"].tolist()) == set(range(len(KEYWORDS)))
     for mode in (EARLIEST, RET):
         both_forms(hip, "kw_starts", "kw_ends_two", 1500, 0, mode)
 
@@ -470,7 +321,7 @@ def test_text_matches_over_a_text_and_its_hits(hip):
     check(td.text_matches(pd, text), want, "text")
     # ... is the primitive over the text's own offsets with the delimiter trimmed
     check(hip.HipMatches.run(pd, td, np.frombuffer(blob, np.uint8), off, trim_byte=0x0A), want, "primitive")
-    ld = hip.LinesDfa(span_ref.line_matcher_of(WORDS)[0], 0x0A)
+    ld = hip.LinesDfa(span_ref.line_matcher_of(KEYWORDS)[0], 0x0A)
     kinds = {"plain": text.hits(ld), "no bytes": text.hits(ld, want_bytes=False), "inverted": text.hits(ld, invert=True)}
     assert 100 < kinds["plain"].count < 300 and kinds["plain"].count + kinds["inverted"].count == len(lines)
     for what, hits in kinds.items():
@@ -556,7 +407,7 @@ def test_example_prints_the_judges_matches(hip, tmp_path):
         files.append([bytes(rng.choice(list(b"abcdxyzw" if i % 2 == 0 else b"xyzwba"), rng.randint(0, 25)).astype(np.uint8)) for i in range(k)])
     files[2][-1] = b"xxabcabd"
     tables = []
-    for nm, auto in (("lines", span_ref.line_matcher_of(WORDS)), ("starts", auto_of("kw_starts")[0]), ("ends", auto_of("kw_ends")[0]),
+    for nm, auto in (("lines", span_ref.line_matcher_of(KEYWORDS)), ("starts", auto_of("kw_starts")[0]), ("ends", auto_of("kw_ends")[0]),
                      ("ends_empty", auto_of("kw_ends_empty")[0]), ("starts_everywhere", auto_of("kw_starts_everywhere")[0])):
         tables.append(str(tmp_path / (nm + ".fsmhip")))
         auto[0].write_c(tables[-1])
@@ -584,7 +435,7 @@ def test_example_prints_the_judges_matches(hip, tmp_path):
             off, at = res["off"].astype(np.int64), 0
             for i, x in enumerate(ls):
                 for k in range(off[i], off[i + 1]):
-                    if span_ref.leftmost_longest(WORDS, x):         # a hit of the line matcher
+                    if span_ref.leftmost_longest(KEYWORDS, x):         # a hit of the line matcher
                         add = at if byte else 0
                         idv = b"-" if int(res["id"][k]) == tokens_ref.NO_ID else b"%d" % int(res["id"][k])
                         out += (nm.encode() + b":" if name else b"") + b"%d:%d-%d:" % ((i if number else first + i) + 1, int(res["start"][k]) + add,

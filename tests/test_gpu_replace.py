@@ -2,9 +2,9 @@
 the scan of the block sums in text.hip).
 
 out_off and every output byte are compared with tests/replace_ref.py, the definition of include/fsm_hip.h ("replace") restated
-in Python, over the matches of tests/matches_ref.py -- never over matches or offsets that came from the device.  The inputs are
-those of tests/test_gpu_matches.py, rebuilt here: 1 500 rows of at most 300 bytes with lengths 0, 1, 15, 16, 17, 31, 32, 33, ...,
-line 8 = 300 times d, and LEAD = 5 bytes in front of the text that belong to no line."""
+in Python, over the matches of tests/matches_ref.py -- never over matches or offsets that came from the device.  The inputs, the
+automata and the matches' judge are tests/line_inputs.py's: 1 500 rows of at most 300 bytes with lengths 0, 1, 15, 16, 17, 31, 32,
+33, ..., line 8 = 300 times d, and LEAD = 5 bytes in front of the text that belong to no line."""
 import ctypes as C
 import errno
 import os
@@ -16,25 +16,14 @@ import pytest
 import matches_ref
 import replace_ref
 import span_ref
-import tokens_ref
-from global_ref import affine, packed
+from line_inputs import (EMPTY_RULE, FILL, KEYWORDS, SIZES, auto_of, device_u64, device_u8, ends_image, inputs_of, judged, lead_packed, reference,
+                         starts_image)
 from matches_ref import DROP_EMPTY
 from replace_ref import MASK
-from tokens_ref import EARLIEST
 
 pytestmark = pytest.mark.gpu
 
-FILL = 0xA5A5A5A5A5A5A5A5
-LEAD = 5
-AUTOMATA = {            # name -> (S, K, the start state is an end state too, walked from LDS)
-    "s15_start": (15, 4, True, True),
-    "lds_full": (1023, 16, False, True),
-    "glob_first": (1024, 16, False, False),
-}
-SIZES = (1, 63, 64, 65, 255, 256, 257, 1500)
-WORDS = [b"ab", b"abc", b"ca", b"d", b"bdb"]
 TABLE_LENS = (0, 1, 15, 16, 17, 40)     # per rule, mixed in one table: chunks straddle every kind of boundary, lines grow and shrink
-EMPTY_RULE = len(WORDS)                  # the id of the empty string in kw_ends_empty_ids
 
 
 @pytest.fixture(scope="module")
@@ -45,127 +34,6 @@ def hip(built):
     import libfsm_amd
     libfsm_amd.load_library()   # raises if the HIP extension is missing: no silent fallback
     return libfsm_amd
-
-
-def device_u64(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()
-
-
-def device_u8(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint8).copy()).cuda()
-
-
-def make_inputs():
-    """1 500 rows of 300 random bytes; lengths 0, 1, 15, 16, 17, 31, 32, 33, then odd rows 0-12 and even rows 0-300"""
-    rng = np.random.RandomState(11)
-    rows = rng.randint(0, 256, (1500, 300)).astype(np.uint8)
-    lens = np.where(np.arange(1500) % 2 == 1, rng.randint(0, 13, 1500), rng.randint(0, 301, 1500)).astype(np.int64)
-    lens[:8] = [0, 1, 15, 16, 17, 31, 32, 33]
-    return rows, lens
-
-
-def keyword_inputs():
-    """the same 1 500 lengths, the lines built from the keywords and a filler letter now and then; line 8: 300 times d"""
-    rng = np.random.RandomState(19)
-    _, lens = make_inputs()
-    pieces = WORDS + [b"x", b"a", b"b"]
-    rows = np.zeros((1500, 300), np.uint8)
-    for i in range(1500):
-        line = b"".join(pieces[k] for k in rng.randint(0, len(pieces), 300))[:300]
-        rows[i] = np.frombuffer(line, np.uint8)
-    lens = lens.copy()
-    lens[8] = 300
-    rows[8] = ord("d")
-    return rows, lens
-
-
-def lead_packed(rows, lens, lead=LEAD):
-    """the lines packed behind `lead` bytes that belong to no line: (bytes of exactly off[n], off with off[0] = lead)"""
-    data, off = packed(rows, lens)
-    return np.concatenate([np.full(lead, 0x5A, np.uint8), data]), off + np.uint64(lead)
-
-
-_inputs, _autos, _starts, _ends, _refs = {}, {}, {}, {}, {}
-
-
-def inputs_of(name):
-    kind = "keywords" if name.startswith("kw") else "random"
-    if kind not in _inputs:
-        _inputs[kind] = keyword_inputs() if kind == "keywords" else make_inputs()
-        for a in _inputs[kind]:
-            a.setflags(write=False)
-    return _inputs[kind]
-
-
-def auto_of(name):
-    """name -> (auto, {state: ids} or None)"""
-    if name not in _autos:
-        if name in AUTOMATA:
-            S, K, start_ends, _ = AUTOMATA[name]
-            auto = affine(S, K, endids=True)
-            if start_ends:
-                auto = span_ref.start_accepting_of(auto)
-            _autos[name] = (auto, None)
-        elif name == "kw_starts":
-            _autos[name] = (span_ref.starts_of(WORDS), None)
-        elif name == "kw_starts_everywhere":
-            _autos[name] = (span_ref.everywhere_of(span_ref.starts_of(WORDS)), None)
-        elif name == "kw_ends":
-            _autos[name] = tokens_ref.trie_lexer(WORDS)
-        else:
-            assert name == "kw_ends_empty_ids"      # the keywords and, as rule EMPTY_RULE, the empty string
-            from libfsm_amd import FlatDfa
-            auto, sets = tokens_ref.trie_lexer(WORDS)
-            sets = dict(sets)
-            sets[0] = [EMPTY_RULE]
-            is_end = np.asarray(auto[0].is_end, np.uint8).copy()
-            is_end[0] = 1
-            _autos[name] = ((FlatDfa.from_dense(auto[1], 0, is_end, endids=sets), auto[1], auto[2]), sets)
-    return _autos[name]
-
-
-def starts_image(name):
-    if name not in _starts:
-        from libfsm_amd import PosDfa
-        _starts[name] = PosDfa.from_flat(auto_of(name)[0][0])
-        if name in AUTOMATA:
-            assert _starts[name].in_lds == AUTOMATA[name][3]
-    return _starts[name]
-
-
-def ends_image(name):
-    if name not in _ends:
-        from libfsm_amd import TokDfa
-        _ends[name] = TokDfa.from_flat(auto_of(name)[0][0], EARLIEST)
-        if name in AUTOMATA:
-            assert _ends[name].in_lds == AUTOMATA[name][3]
-    return _ends[name]
-
-
-def state_ids(name):
-    auto, sets = auto_of(name)
-    return tokens_ref.state_ids(auto, EARLIEST, sets)
-
-
-def reference(starts, ends, flags=0):
-    """the matches' judge for all 1 500 inputs of a pair, computed once and left unchanged"""
-    key = (starts, ends, flags)
-    if key not in _refs:
-        rows, lens = inputs_of(ends)
-        assert inputs_of(starts) is inputs_of(ends)
-        res = matches_ref.matches(auto_of(starts)[0], auto_of(ends)[0], rows, lens, flags, ids=state_ids(ends))
-        for v in res.values():
-            v.setflags(write=False)
-        _refs[key] = res
-    return _refs[key]
-
-
-def judged(starts, ends, rows, lens, flags=0):
-    """the matches' judge on other lines than the 1 500: (off, start, end, id)"""
-    r = matches_ref.matches(auto_of(starts)[0], auto_of(ends)[0], rows, lens, flags, ids=state_ids(ends))
-    return r["off"], r["start"], r["end"], r["id"]
 
 
 def mixed_table(nrepl, seed=0, shift=0):
@@ -248,7 +116,7 @@ def both_forms(hip, starts, ends, n, table, flags=0, mflags=0, host=True):
 @pytest.mark.parametrize("starts,ends", [("lds_full", "glob_first"), ("glob_first", "lds_full"), ("s15_start", "lds_full"), ("kw_starts", "kw_ends")])
 def test_every_size_with_a_mixed_table(hip, starts, ends):
     res = reference(starts, ends)
-    table = mixed_table(len(WORDS)) if ends == "kw_ends" else table_for(res)
+    table = mixed_table(len(KEYWORDS)) if ends == "kw_ends" else table_for(res)
     replaced = (res["id"] < len(table)).mean()
     _, lens = inputs_of(ends)
     for n in SIZES:
@@ -271,7 +139,7 @@ def test_every_size_with_a_mixed_table(hip, starts, ends):
 
 def test_every_rule_empty_lines_vanish(hip):
     rows, lens = inputs_of("kw_ends")
-    table = [b""] * len(WORDS)
+    table = [b""] * len(KEYWORDS)
     off, data = both_forms(hip, "kw_starts", "kw_ends", 1500, table)
     out = np.diff(off.astype(np.int64))
     gone = (out == 0) & (lens > 0)
@@ -316,7 +184,7 @@ def test_more_lines_than_a_block_of_the_offsets_pass(hip):
         else:
             lines.append(bytes(rng.choice(list(b"abcdxy"), k).astype(np.uint8)))
     r, l = span_ref.rows_of(lines)
-    table = [b""] * len(WORDS)
+    table = [b""] * len(KEYWORDS)
     mt = judged("kw_starts", "kw_ends", r, l)
     want = replace_ref.replace(r, l, l, mt, table)
     out = np.diff(want[0].astype(np.int64))
@@ -326,7 +194,7 @@ def test_more_lines_than_a_block_of_the_offsets_pass(hip):
     b = Batch(*lead_packed(r, l))
     check(device_form(hip, pd, td, b, table), want, "three blocks + 1, device")
     check(host_form(hip, pd, td, b, table), want, "three blocks + 1, host")
-    grow = mixed_table(len(WORDS), 3)
+    grow = mixed_table(len(KEYWORDS), 3)
     check(device_form(hip, pd, td, b, grow), replace_ref.replace(r, l, l, mt, grow), "three blocks + 1, mixed table")
 
 
@@ -353,12 +221,12 @@ def test_empty_matches_insert_or_are_dropped(hip):
     kept, dropped = reference(starts, ends), reference(starts, ends, DROP_EMPTY)
     empty = kept["end"] == kept["start"]
     assert empty.sum() >= 1000 and (kept["id"][empty] == EMPTY_RULE).all() and len(dropped["start"]) == int((~empty).sum())
-    table = mixed_table(len(WORDS)) + [b"<>"]
+    table = mixed_table(len(KEYWORDS)) + [b"<>"]
     for n in (65, 1500):
         a, _ = both_forms(hip, starts, ends, n, table)
         d, _ = both_forms(hip, starts, ends, n, table, mflags=DROP_EMPTY)
         assert int(a[-1]) >= int(d[-1]) + 2 * int(empty[:int(kept["off"][n])].sum())
-    both_forms(hip, starts, ends, 257, table[:len(WORDS)])                  # the empty rule beyond nrepl: nothing is inserted
+    both_forms(hip, starts, ends, 257, table[:len(KEYWORDS)])                  # the empty rule beyond nrepl: nothing is inserted
     both_forms(hip, starts, ends, 257, [b"", b"", b"", b"", b"", b"-"])      # only inserts are left where words were
     both_forms(hip, starts, ends, 257, table, MASK)                         # an empty match has no byte to mask
 
@@ -393,7 +261,7 @@ def test_trim_byte_is_copied(hip):
     shorter = lens - ends_in
     assert ends_in.sum() > 100 and (~ends_in & (lens > 0)).sum() > 100
     b = Batch(*lead_packed(rows, lens))
-    table = mixed_table(len(WORDS), 5)
+    table = mixed_table(len(KEYWORDS), 5)
     mt = judged("kw_starts", "kw_ends", rows, shorter)
     want = replace_ref.replace(rows, shorter, lens, mt, table)
     assert bytes(want[1]).count(b"\n") == int(ends_in.sum())
@@ -413,7 +281,7 @@ def test_pick_and_limit(hip, starts, ends):
     rng = np.random.RandomState(12)
     pick = np.concatenate([rng.permutation(n)[:300], [7, 7, 7, 0, n - 1, n - 1, 8, 8], rng.randint(0, n, 100), np.arange(n)[::-1][:50]]).astype(np.uint64)
     res = reference(starts, ends)
-    table = mixed_table(len(WORDS)) if ends == "kw_ends" else table_for(res)
+    table = mixed_table(len(KEYWORDS)) if ends == "kw_ends" else table_for(res)
 
     def want_of(p, nlines=n):
         ok = p < nlines
@@ -455,7 +323,7 @@ def test_pick_and_limit(hip, starts, ends):
 def test_table_under_and_over_the_lds_bound(hip):
     rows, lens = inputs_of("kw_ends")
     n = 600
-    words = mixed_table(len(WORDS), 9)
+    words = mixed_table(len(KEYWORDS), 9)
     bound, rules = hip.repl_lds_bytes(), hip.repl_lds_rules()
     assert (bound, rules) == (16384, 1023)
     room = bound - sum(len(x) for x in words)
@@ -509,7 +377,7 @@ def test_text_replace_over_a_text_and_its_hits_and_the_result_fed_back(hip):
     raw_rows, raws = span_ref.rows_of(with_nl)
     mt_ref = judged("kw_starts", "kw_ends", rows, lens)
     res = dict(off=mt_ref[0], start=mt_ref[1], end=mt_ref[2], id=mt_ref[3])
-    table = mixed_table(len(WORDS), 2)
+    table = mixed_table(len(KEYWORDS), 2)
     rp = hip.HipRepl(table)
     want = replace_ref.replace(raw_rows, lens, raws, mt_ref, table)
     assert bytes(want[1]).count(b"\n") == len(lines) - 1 and not bytes(want[1]).endswith(b"\n")
@@ -520,7 +388,7 @@ def test_text_replace_over_a_text_and_its_hits_and_the_result_fed_back(hip):
     b = Batch(np.frombuffer(blob, np.uint8), off)
     check(host_form(hip, pd, td, b, table, trim_byte=0x0A), want, "primitive, host")
     check(device_form(hip, pd, td, b, rp, trim_byte=0x0A), want, "primitive, device")
-    ld = hip.LinesDfa(span_ref.line_matcher_of(WORDS)[0], 0x0A)
+    ld = hip.LinesDfa(span_ref.line_matcher_of(KEYWORDS)[0], 0x0A)
     kinds = {"plain": text.hits(ld), "no bytes": text.hits(ld, want_bytes=False), "inverted": text.hits(ld, invert=True)}
     assert 100 < kinds["plain"].count < 300
     for what, hits in kinds.items():
@@ -566,7 +434,7 @@ def test_refusals_with_a_device(hip):
     n = 64
     data, off = lead_packed(rows[:n], lens[:n])
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
-    table = mixed_table(len(WORDS))
+    table = mixed_table(len(KEYWORDS))
     tb, roff = replace_ref.pack_table(table)
     bad_roff = roff.copy()
     bad_roff[2] = bad_roff[3] + np.uint64(1)
@@ -611,7 +479,7 @@ def test_example_writes_the_judges_text(hip, tmp_path):
     files = [[bytes(rng.choice(list(b"abcdxyzw" if i % 2 == 0 else b"xyzwba"), rng.randint(0, 25)).astype(np.uint8)) for i in range(k)] for k in (70, 40)]
     files[1][-1] = b"xxabcabd"
     tables = []
-    for nm, auto in (("lines", span_ref.line_matcher_of(WORDS)), ("starts", auto_of("kw_starts")[0]), ("ends", auto_of("kw_ends")[0])):
+    for nm, auto in (("lines", span_ref.line_matcher_of(KEYWORDS)), ("starts", auto_of("kw_starts")[0]), ("ends", auto_of("kw_ends")[0])):
         tables.append(str(tmp_path / (nm + ".fsmhip")))
         auto[0].write_c(tables[-1])
     names = []

@@ -12,13 +12,12 @@ import numpy as np
 import pytest
 
 import span_ref
-from global_ref import affine, packed
+from global_ref import affine
+from line_inputs import FILL, LEAD, SIZES, device_u64, device_u8, lead_packed, make_inputs
 from span_ref import NO_POS
 
 pytestmark = pytest.mark.gpu
 
-FILL = 0xA5A5A5A5A5A5A5A5
-LEAD = 5                                     # off[0]: the text does not begin at base
 # name -> (S, K, keyword arguments, the start state is an end state too, walked from LDS)
 AUTOMATA = {
     "s15": (15, 4, {}, False, True),
@@ -28,7 +27,6 @@ AUTOMATA = {
     "glob_first": (1024, 16, {}, False, False),                     # 1025 * 16 = 16 400 entries: the first global image
     "dying1023": (1023, 16, dict(holes=8, sinks=4), False, True),
 }
-SIZES = (1, 63, 64, 65, 255, 256, 257, 1500)
 
 
 @pytest.fixture(scope="module")
@@ -41,34 +39,14 @@ def hip(built):
     return libfsm_amd
 
 
-def device_u64(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()
-
-
-def device_u8(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint8).copy()).cuda()
-
-
 def host_u64(t):
     return t.cpu().numpy().view(np.uint64)
 
 
 @pytest.fixture(scope="module")
 def inputs():
-    """1 500 rows of 300 random bytes; lengths 0, 1, 15, 16, 17, 31, 32, 33, then odd rows 0-12 and even rows 0-300"""
-    rng = np.random.RandomState(11)
-    rows = rng.randint(0, 256, (1500, 300)).astype(np.uint8)
-    lens = np.where(np.arange(1500) % 2 == 1, rng.randint(0, 13, 1500), rng.randint(0, 301, 1500)).astype(np.int64)
-    lens[:8] = [0, 1, 15, 16, 17, 31, 32, 33]
-    return rows, lens
-
-
-def lead_packed(rows, lens, lead=LEAD):
-    """the lines packed behind `lead` bytes that belong to no line: (bytes of exactly off[n], off with off[0] = lead)"""
-    data, off = packed(rows, lens)
-    return np.concatenate([np.full(lead, 0x5A, np.uint8), data]), off + np.uint64(lead)
+    """the 1 500 rows of tests/line_inputs.py: 300 random bytes; lengths 0, 1, 15, 16, 17, 31, 32, 33, then odd rows 0-12 and even rows 0-300"""
+    return make_inputs()
 
 
 _made = {}

@@ -3,10 +3,11 @@ repl_write<LDS / global table, true>; fsm_hip_repl_create_template in text.hip).
 
 out_off and every output byte are compared with tests/template_ref.py, the definition of include/fsm_hip.h ("replace", the template
 table) restated in Python, over the matches of tests/matches_ref.py -- never over matches or offsets that came from the device.  The
-inputs are the 1 500 keyword lines and the automata of tests/test_gpu_replace.py, rebuilt here: rows of at most 300 bytes with
+inputs are the 1 500 keyword lines of tests/line_inputs.py, as are the automata and the matches' judge: rows of at most 300 bytes with
 lengths 0, 1, 15, 16, 17, 31, 32, 33, ..., line 8 = 300 times d, and LEAD = 5 bytes in front of the text that belong to no line."""
 import ctypes as C
 import errno
+import functools
 import os
 import subprocess
 
@@ -17,19 +18,13 @@ import matches_ref
 import replace_ref
 import span_ref
 import template_ref
-import tokens_ref
-from global_ref import packed
+from line_inputs import (EMPTY_RULE, FILL, KEYWORDS, SIZES, auto_of, device_u64, device_u8, ends_image, inputs_of, judged, lead_packed, reference,
+                         starts_image, state_ids)
 from matches_ref import DROP_EMPTY
-from tokens_ref import EARLIEST
 
 pytestmark = pytest.mark.gpu
 
-FILL = 0xA5A5A5A5A5A5A5A5
-LEAD = 5
 BLOCK = 16384
-SIZES = (1, 63, 64, 65, 255, 256, 257, 1500)
-WORDS = [b"ab", b"abc", b"ca", b"d", b"bdb"]
-EMPTY_RULE = len(WORDS)                  # the id of the empty string in kw_ends_empty_ids
 # one table over the five keyword rules: & alone, <&>, &&, 17 literal bytes + & + 40 literal bytes, a rule without an insert
 SEVENTEEN, FORTY = bytes(range(0x30, 0x30 + 17)), bytes(range(0x50, 0x50 + 40))
 MIXED = [b"&", b"<&>", b"&&", SEVENTEEN + b"&" + FORTY, b"plain"]
@@ -44,117 +39,6 @@ def hip(built):
     import libfsm_amd
     libfsm_amd.load_library()   # raises if the HIP extension is missing: no silent fallback
     return libfsm_amd
-
-
-def device_u64(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()
-
-
-def device_u8(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint8).copy()).cuda()
-
-
-def keyword_inputs():
-    """1 500 lines built from the keywords and a filler letter now and then; lengths 0, 1, 15, 16, 17, 31, 32, 33, then odd rows
-    0-12 and even rows 0-300; line 8: 300 times d"""
-    rng = np.random.RandomState(11)
-    rng.randint(0, 256, (1500, 300))
-    lens = np.where(np.arange(1500) % 2 == 1, rng.randint(0, 13, 1500), rng.randint(0, 301, 1500)).astype(np.int64)
-    lens[:8] = [0, 1, 15, 16, 17, 31, 32, 33]
-    rng = np.random.RandomState(19)
-    pieces = WORDS + [b"x", b"a", b"b"]
-    rows = np.zeros((1500, 300), np.uint8)
-    for i in range(1500):
-        line = b"".join(pieces[k] for k in rng.randint(0, len(pieces), 300))[:300]
-        rows[i] = np.frombuffer(line, np.uint8)
-    lens[8] = 300
-    rows[8] = ord("d")
-    return rows, lens
-
-
-def lead_packed(rows, lens, lead=LEAD):
-    """the lines packed behind `lead` bytes that belong to no line: (bytes of exactly off[n], off with off[0] = lead)"""
-    data, off = packed(rows, lens)
-    return np.concatenate([np.full(lead, 0x5A, np.uint8), data]), off + np.uint64(lead)
-
-
-_cache = {}
-
-
-def once(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
-
-
-def inputs():
-    def make():
-        rows, lens = keyword_inputs()
-        rows.setflags(write=False)
-        lens.setflags(write=False)
-        return rows, lens
-    return once("inputs", make)
-
-
-def auto_of(name):
-    """name -> (auto, {state: ids} or None)"""
-    def make():
-        if name == "kw_starts":
-            return span_ref.starts_of(WORDS), None
-        if name == "kw_starts_everywhere":
-            return span_ref.everywhere_of(span_ref.starts_of(WORDS)), None
-        if name == "kw_ends":
-            return tokens_ref.trie_lexer(WORDS)
-        if name == "run_starts":                     # a match begins wherever a d stands ...
-            return span_ref.starts_of([b"d"]), None
-        if name == "run_ends":                       # ... and ends behind the last d of its run (d+): a run of d is ONE match, rule 0
-            dense = np.full((2, 256), -1, np.int64)
-            dense[:, ord("d")] = 1
-            from libfsm_amd import FlatDfa
-            return (FlatDfa.from_dense(dense, 0, np.array([0, 1], np.uint8), endids={1: [0]}), dense, np.arange(256, dtype=np.int64)), {1: [0]}
-        assert name == "kw_ends_empty_ids"           # the keywords and, as rule EMPTY_RULE, the empty string
-        from libfsm_amd import FlatDfa
-        auto, sets = tokens_ref.trie_lexer(WORDS)
-        sets = dict(sets)
-        sets[0] = [EMPTY_RULE]
-        is_end = np.asarray(auto[0].is_end, np.uint8).copy()
-        is_end[0] = 1
-        return (FlatDfa.from_dense(auto[1], 0, is_end, endids=sets), auto[1], auto[2]), sets
-    return once(("auto", name), make)
-
-
-def starts_image(name):
-    from libfsm_amd import PosDfa
-    return once(("pd", name), lambda: PosDfa.from_flat(auto_of(name)[0][0]))
-
-
-def ends_image(name):
-    from libfsm_amd import TokDfa
-    return once(("td", name), lambda: TokDfa.from_flat(auto_of(name)[0][0], EARLIEST))
-
-
-def state_ids(name):
-    auto, sets = auto_of(name)
-    return tokens_ref.state_ids(auto, EARLIEST, sets)
-
-
-def reference(starts, ends, flags=0):
-    """the matches' judge for all 1 500 inputs of a pair, computed once and left unchanged"""
-    def make():
-        rows, lens = inputs()
-        res = matches_ref.matches(auto_of(starts)[0], auto_of(ends)[0], rows, lens, flags, ids=state_ids(ends))
-        for v in res.values():
-            v.setflags(write=False)
-        return res
-    return once(("ref", starts, ends, flags), make)
-
-
-def judged(starts, ends, rows, lens, flags=0):
-    """the matches' judge on other lines than the 1 500: (off, start, end, id)"""
-    r = matches_ref.matches(auto_of(starts)[0], auto_of(ends)[0], rows, lens, flags, ids=state_ids(ends))
-    return r["off"], r["start"], r["end"], r["id"]
 
 
 def parsed(seds):
@@ -212,7 +96,7 @@ def host_form(hip, pd, td, b, rp, mflags=0):
 
 
 def both_forms(hip, starts, ends, n, table, inserts, mflags=0, host=True, rp=None):
-    rows, lens = inputs()
+    rows, lens = inputs_of("kw_ends")
     pd, td = starts_image(starts), ends_image(ends)
     b = Batch(*lead_packed(rows[:n], lens[:n]))
     rp = hip.HipRepl.template(table, inserts) if rp is None else rp
@@ -230,7 +114,7 @@ def test_every_size_with_a_mixed_template(hip):
     assert inserts == [[0], [1], [0, 0], [17], []] and [len(x) for x in table] == [0, 2, 0, 57, 5]
     rp = hip.HipRepl.from_sed(MIXED)                                        # the binding's parser: the same table
     assert rp.inserts == 5 and rp.in_lds and rp.nrepl == 5
-    _, lens = inputs()
+    _, lens = inputs_of("kw_ends")
     for n in SIZES:
         off, _ = both_forms(hip, "kw_starts", "kw_ends", n, table, inserts, host=n in (1, 257, 1500), rp=rp)
     out = np.diff(off.astype(np.int64))
@@ -262,7 +146,7 @@ def test_text_replace_over_a_text_and_its_hits(hip):
     want = template_ref.replace(raw_rows, lens, raws, mt_ref, table, inserts)
     assert bytes(want[1]).count(b"\n") == len(lines) - 1 and bytes(want[1]).endswith(b"xx<abc>ab" + SEVENTEEN + b"d" + FORTY)
     check(td.text_matches(pd, text).text_replace(rp, text), want, "text")
-    ld = hip.LinesDfa(span_ref.line_matcher_of(WORDS)[0], 0x0A)
+    ld = hip.LinesDfa(span_ref.line_matcher_of(KEYWORDS)[0], 0x0A)
     hits = text.hits(ld)
     assert 100 < hits.count < 300
     picks = hits.lines().astype(np.int64)
@@ -294,39 +178,38 @@ def test_an_empty_match_gives_the_literal(hip):
 
 # ---- group 3: one match longer than two output blocks; the edges of the text --------------------------------------------------
 
+@functools.lru_cache(maxsize=None)
 def long_line_matches():
-    """(lines, rows, lens, matches) of three lines whose middle one is LONG times d, ONE match of the pair run_starts / run_ends.
+    """(lines, rows, lens, matches) of three lines whose middle one is LONG times d, ONE match of the pair d_starts / d_plus.
     The matches' judge walks `ends` from every start to the line's end, which is quadratic in the line: for the long line its
     table E (the farthest end from every start) is stated instead, by the law that the judge itself shows on a line of 200: d+ has
     one live state that loops, so from every s < len the farthest end is len, and from len there is none.  M (the starts) is the
     judge's own, and so is the cursor loop over M and E."""
-    def make():
-        starts, ends = auto_of("run_starts")[0], auto_of("run_ends")[0]
-        ids = state_ids("run_ends")
-        r, l = span_ref.rows_of([b"d" * 200])
-        E, Q = matches_ref.longest_from(ends, r, l)
-        assert (E[0, :200] == 200).all() and E[0, 200] == -1 and (Q[0, :200] == 1).all()
-        r, l = span_ref.rows_of([b"d" * LONG])
-        E = np.full((1, LONG + 1), LONG, np.int64)
-        E[0, LONG] = -1
-        Q = np.where(E >= 0, 1, -1)
-        big = matches_ref.matches(starts, ends, r, l, ids=ids, tables=(matches_ref.marks(starts, r, l), E, Q))
-        assert big["start"].tolist() == [0] and big["end"].tolist() == [LONG] and big["id"].tolist() == [0]
-        lines = [b"xddxdxx", b"d" * LONG, b"dxxdd"]
-        rows, lens = span_ref.rows_of(lines)
-        small = [matches_ref.matches(starts, ends, *span_ref.rows_of([x]), ids=ids) for x in (lines[0], lines[2])]
-        parts = [small[0], big, small[1]]
-        off = np.r_[0, np.cumsum([len(p["start"]) for p in parts])].astype(np.uint64)
-        mt = (off,) + tuple(np.concatenate([p[k] for p in parts]) for k in ("start", "end", "id"))
-        assert off.tolist() == [0, 2, 3, 5]
-        return lines, rows, lens, mt, (big["off"], big["start"], big["end"], big["id"])
-    return once("long", make)
+    starts, ends = auto_of("d_starts")[0], auto_of("d_plus")[0]
+    ids = state_ids("d_plus")
+    r, l = span_ref.rows_of([b"d" * 200])
+    E, Q = matches_ref.longest_from(ends, r, l)
+    assert (E[0, :200] == 200).all() and E[0, 200] == -1 and (Q[0, :200] == 1).all()
+    r, l = span_ref.rows_of([b"d" * LONG])
+    E = np.full((1, LONG + 1), LONG, np.int64)
+    E[0, LONG] = -1
+    Q = np.where(E >= 0, 1, -1)
+    big = matches_ref.matches(starts, ends, r, l, ids=ids, tables=(matches_ref.marks(starts, r, l), E, Q))
+    assert big["start"].tolist() == [0] and big["end"].tolist() == [LONG] and big["id"].tolist() == [0]
+    lines = [b"xddxdxx", b"d" * LONG, b"dxxdd"]
+    rows, lens = span_ref.rows_of(lines)
+    small = [matches_ref.matches(starts, ends, *span_ref.rows_of([x]), ids=ids) for x in (lines[0], lines[2])]
+    parts = [small[0], big, small[1]]
+    off = np.r_[0, np.cumsum([len(p["start"]) for p in parts])].astype(np.uint64)
+    mt = (off,) + tuple(np.concatenate([p[k] for p in parts]) for k in ("start", "end", "id"))
+    assert off.tolist() == [0, 2, 3, 5]
+    return lines, rows, lens, mt, (big["off"], big["start"], big["end"], big["id"])
 
 
 def test_one_match_longer_than_two_blocks(hip):
     """[&|&] around 40 000 bytes: chunks wholly inside the match's copies cross block boundaries, and the seam between the copies"""
     lines, rows, lens, mt, _ = long_line_matches()
-    pd, td = starts_image("run_starts"), ends_image("run_ends")
+    pd, td = starts_image("d_starts"), ends_image("d_plus")
     table, inserts = parsed([b"[&|&]"])
     want = template_ref.replace(rows, lens, lens, mt, table, inserts)
     out = template_ref.lines_of(*want)
@@ -348,7 +231,7 @@ def test_the_match_is_the_whole_text(hip):
     the windows of the stretches at both ends of each copy would leave the text: the byte loads under `limit`"""
     _, _, _, _, mt = long_line_matches()
     rows, lens = span_ref.rows_of([b"d" * LONG])
-    pd, td = starts_image("run_starts"), ends_image("run_ends")
+    pd, td = starts_image("d_starts"), ends_image("d_plus")
     data, off = lead_packed(rows, lens, lead=0)
     assert len(data) == LONG and off.tolist() == [0, LONG]
     for seds in ([b"[&|&]"], [b"&&"], [b"&<\\&>&"]):
@@ -360,7 +243,7 @@ def test_the_match_is_the_whole_text(hip):
         rows, lens = span_ref.rows_of([b"d" * k])
         data, off = lead_packed(rows, lens, lead=0)
         table, inserts = parsed([b"&-&&"])
-        want = template_ref.replace(rows, lens, lens, judged("run_starts", "run_ends", rows, lens), table, inserts)
+        want = template_ref.replace(rows, lens, lens, judged("d_starts", "d_plus", rows, lens), table, inserts)
         assert bytes(want[1]) == b"d" * k + b"-" + b"d" * 2 * k
         check(device_form(hip, pd, td, Batch(data, off), hip.HipRepl.template(table, inserts)), want, ("whole text", k))
 
@@ -368,12 +251,12 @@ def test_the_match_is_the_whole_text(hip):
 def test_three_inserts_in_an_empty_literal(hip):
     """&&& on lines of 8-12 bytes: a chunk of 16 output bytes holds the copies of several matches"""
     rng = np.random.RandomState(23)
-    pieces = WORDS + [b"x"]
+    pieces = KEYWORDS + [b"x"]
     lines = [b"".join(pieces[k] for k in rng.randint(0, len(pieces), 12))[:rng.randint(8, 13)] for _ in range(300)]
     rows, lens = span_ref.rows_of(lines)
     mt = judged("kw_starts", "kw_ends", rows, lens)
     assert len(mt[1]) >= 3 * len(lines)
-    table, inserts = parsed([b"&&&"] * len(WORDS))
+    table, inserts = parsed([b"&&&"] * len(KEYWORDS))
     assert table == [b""] * 5 and inserts == [[0, 0, 0]] * 5
     want = template_ref.replace(rows, lens, lens, mt, table, inserts)
     assert template_ref.lines_of(*want)[:300] and int(want[0][-1]) > 2 * int(lens.sum())
@@ -387,7 +270,7 @@ def test_three_inserts_in_an_empty_literal(hip):
 # ---- group 4: the table from LDS and from device memory ---------------------------------------------------------------------
 
 def test_template_table_in_lds_and_in_device_memory(hip):
-    rows, lens = inputs()
+    rows, lens = inputs_of("kw_ends")
     n = 600
     table, inserts = parsed(MIXED)
     bound, rules = hip.repl_lds_bytes(), hip.repl_lds_rules()
@@ -429,7 +312,7 @@ def test_template_table_in_lds_and_in_device_memory(hip):
 
 
 def test_a_template_table_without_inserts_is_the_plain_table(hip):
-    rows, lens = inputs()
+    rows, lens = inputs_of("kw_ends")
     table = [b"<AB>", b"", b"c", bytes(range(0x30, 0x30 + 40)), b"seventeen bytes.."]
     pd, td = starts_image("kw_starts"), ends_image("kw_ends")
     b = Batch(*lead_packed(rows, lens))
@@ -450,7 +333,7 @@ def test_a_template_table_without_inserts_is_the_plain_table(hip):
 
 def test_refusals_with_a_device(hip):
     """EINVAL before any upload, and the next call answers"""
-    rows, lens = inputs()
+    rows, lens = inputs_of("kw_ends")
     lib = hip.load_library()
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
     u64 = lambda *a: np.array(a, np.uint64)           # noqa: E731
@@ -504,7 +387,7 @@ def test_example_with_templates(hip, tmp_path):
     files = [[bytes(rng.choice(list(b"abcdxyzw" if i % 2 == 0 else b"xyzwba"), rng.randint(0, 25)).astype(np.uint8)) for i in range(k)] for k in (70, 40, 25)]
     files[1][-1] = b"xxabcabd"
     tables = []
-    for nm, auto in (("lines", span_ref.line_matcher_of(WORDS)), ("starts", auto_of("kw_starts")[0]), ("ends", auto_of("kw_ends")[0])):
+    for nm, auto in (("lines", span_ref.line_matcher_of(KEYWORDS)), ("starts", auto_of("kw_starts")[0]), ("ends", auto_of("kw_ends")[0])):
         tables.append(str(tmp_path / (nm + ".fsmhip")))
         auto[0].write_c(tables[-1])
     names = []

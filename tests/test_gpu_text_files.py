@@ -14,6 +14,7 @@ import pytest
 from common import GOLDEN, Golden
 from files_ref import files_ref, hits_ref_off, join_files
 from hits_ref import pack_bits
+from line_inputs import device_u64
 from text_ref import lines_of, newline_dfa, oracle_answers, split_ref
 
 pytestmark = pytest.mark.gpu
@@ -38,11 +39,6 @@ def to_device(buf, lead=0, pad=0, fill=0):
     host[lead + pad:lead + pad + len(buf)] = buf
     t = torch.from_numpy(host).cuda()
     return t, t.data_ptr() + lead + pad
-
-
-def device_u64(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()
 
 
 def random_text(nbytes, delim, density, rng):

@@ -3,7 +3,7 @@
 Every answer -- count, tok_off, end, id, err, total -- is compared with tests/tokens_ref.py, the definition of include/fsm_hip.h
 ("tokens") restated in plain Python over the automaton's own formula, never with anything derived from the code under test.  The
 automata are global_ref.affine's, span_ref's variants of them and a word lexer (a trie); the inputs are the 1 500 rows of
-tests/test_gpu_spans.py, rebuilt here."""
+tests/line_inputs.py."""
 import ctypes as C
 import errno
 import os
@@ -15,13 +15,12 @@ import pytest
 
 import span_ref
 import tokens_ref
-from global_ref import affine, packed
+from global_ref import affine
+from line_inputs import FILL, LEAD, SIZES, device_u64, device_u8, lead_packed, make_inputs
 from tokens_ref import EARLIEST, ERROR, NO_BACKTRACK, NO_MATCH, NO_POS, RET, SKIP_BAD
 
 pytestmark = pytest.mark.gpu
 
-FILL = 0xA5A5A5A5A5A5A5A5
-LEAD = 5                                     # off[0]: the text does not begin at base
 # name -> (S, K, keyword arguments, walked from LDS)
 AFFINE = {
     "s15": (15, 4, {}, True),
@@ -31,7 +30,6 @@ AFFINE = {
 }
 FURTHER = ("s15_start", "s200_everywhere", "words")
 WORDS = [w.encode() for w in "a ab abcda b bc bcdab c ca cab d dd ddabc".split()]
-SIZES = (1, 63, 64, 65, 255, 256, 257, 1500)
 COMBOS = (0, NO_BACKTRACK, SKIP_BAD, NO_BACKTRACK | SKIP_BAD)
 
 
@@ -45,37 +43,12 @@ def hip(built):
     return libfsm_amd
 
 
-def device_u64(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()
-
-
-def device_u8(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint8).copy()).cuda()
-
-
-def make_inputs():
-    """1 500 rows of 300 random bytes; lengths 0, 1, 15, 16, 17, 31, 32, 33, then odd rows 0-12 and even rows 0-300"""
-    rng = np.random.RandomState(11)
-    rows = rng.randint(0, 256, (1500, 300)).astype(np.uint8)
-    lens = np.where(np.arange(1500) % 2 == 1, rng.randint(0, 13, 1500), rng.randint(0, 301, 1500)).astype(np.int64)
-    lens[:8] = [0, 1, 15, 16, 17, 31, 32, 33]
-    return rows, lens
-
-
 def word_inputs():
     """the same 1 500 lengths over abcdx, x rare: lines a word lexer cuts into many tokens"""
     rng = np.random.RandomState(17)
     _, lens = make_inputs()
     rows = np.frombuffer(b"abcdx", np.uint8)[rng.choice(5, (1500, 300), p=[.24, .24, .24, .24, .04])]
     return np.ascontiguousarray(rows), lens
-
-
-def lead_packed(rows, lens, lead=LEAD):
-    """the lines packed behind `lead` bytes that belong to no line: (bytes of exactly off[n], off with off[0] = lead)"""
-    data, off = packed(rows, lens)
-    return np.concatenate([np.full(lead, 0x5A, np.uint8), data]), off + np.uint64(lead)
 
 
 _made = {}
