@@ -1283,6 +1283,70 @@ size_t fsm_hip_extracted_block_bytes(void);    /* output bytes of a block of the
 void fsm_hip_extracted_free(struct fsm_hip_extracted *x);
 
 /* ------------------------------------------------------------------ */
+/* tally: matches and lines per rule and per group, counted on the device */
+/* ------------------------------------------------------------------ */
+
+/* Which rules of a union fired, how often, in how many lines, in which files: one reduction over the off[m + 1] and id[total] that
+ * a matches object and a tokens object own, without bringing either array to the host.
+ *   Input.  off[m + 1] (input j owns entries off[j] .. off[j + 1]), id[total], nrules.
+ *   Columns.  C = nrules + 1.  col(x) = x if x < nrules, else nrules: the last column is "other" -- rules beyond nrules,
+ *   FSM_HIP_NO_ID, and FSM_HIP_NO_MATCH, which the tokens of FSM_HIP_TOKENS_SKIP_BAD carry.  nrules == 0 is valid: one column.
+ *   Groups.  group_off[G + 1] holds input indices; group g is the inputs [group_off[g], group_off[g + 1]).  Equal neighbours are an
+ *   empty group.  group_off == NULL means G = 1 and the one group is every input (ngroups is then ignored).  Inputs below
+ *   group_off[0] or at or above group_off[G] are counted nowhere.
+ *   count[g * C + c] is the number of entries k of the inputs of group g with col(id[k]) == c.
+ *   lines[g * C + c] is the number of inputs j of group g that own at least one entry k with col(id[k]) == c: an input counts
+ *   once per column however often the column occurs in it.  Per file this is grep -c for one rule of a union.
+ *   Both tables are the caller's memory, G * C entries each, row-major.  Either may be NULL, not both.  They are cleared first,
+ *   unless FSM_HIP_TALLY_ADD is given: then the new counts are added to what is there -- totals over many texts or calls, or tokens
+ *   and matches into one table.
+ * Nothing is allocated for the caller and there is no object.  The device forms wait for nothing and are in flight at return.
+ * fsm_hip_tally_ids_device is the reduction itself over any arrays of that shape on the current device: id[k] is read for k <
+ * total only, an entry of off above total is treated as total, and the group of input j is the last g in [0, G) with group_off[g]
+ * <= j, provided j < group_off[G].  Arrays that do not ascend give wrong counts; they never cause a load outside off[0 .. m],
+ * id[0 .. total), group_off[0 .. G], and never a store outside the two tables.
+ * fsm_hip_matches_tally_device / fsm_hip_tokens_tally_device: the same over the object's own arrays, enqueued behind the object's
+ * last event, as extraction is.  fsm_hip_matches_tally / fsm_hip_tokens_tally take host arrays in and out, stage them and wait; a
+ * group_off that decreases or whose last entry exceeds m is EINVAL before any launch; with FSM_HIP_TALLY_ADD the host tables are
+ * read and added to.  fsm_hip_text_matches_tally / fsm_hip_text_tokens_tally: the groups are the files of the text -- its
+ * file_lines when hits == NULL, the hits' file_first otherwise -- so the counts are per file without the caller touching either
+ * array; a plain text is one group.  EINVAL when the object's m is not the text's n, or the hits' m, as in fsm_hip_text_extract.
+ * The kernel: a workgroup takes a contiguous span of inputs, whole granules of fsm_hip_tally_span_inputs(), and goes through the
+ * span's entries in windows of fsm_hip_tally_window(), one lane per entry; two wavefronts find the inputs of the window's ends by a
+ * 64-ary search, a lane finds its input between them by the bounded search of the extraction, then its group.  While C <=
+ * fsm_hip_tally_lds_columns() the counters are u32 in LDS, flushed to the tables by one atomic add per non-zero bin at every
+ * change of group, at the end of the span and before one could wrap; above it only the last column, "other", has such a counter,
+ * and every other entry, like every entry of a window that spans a group boundary, adds to the table itself.  Equal destinations
+ * of a wavefront are combined first.  For lines an entry counts iff no earlier entry of its input has its column: a backward look
+ * through the window, of at most window - 1 steps, and, for the one input that may continue from the window before, a bitmap of
+ * fsm_hip_tally_max_line_columns() bits.  No lane's work grows with the entries of an input beyond the window.  Integer adds only:
+ * the result is exact and the same on every run.
+ * 0, or -1 + errno: ENODEV (checked first: there is no CPU path), EINVAL (an object NULL, both tables NULL, an unknown flag bit,
+ * ngroups == 0 with group_off != NULL, the objects and the text on different devices, m that is not the text's; host forms: a
+ * group_off that decreases or exceeds m), EOVERFLOW (G * C * 8 does not fit size_t), ENOTSUP (lines asked for and C above
+ * fsm_hip_tally_max_line_columns()).  m == 0 or total == 0 is valid: the tables are cleared, unless they are added to, and
+ * nothing else is launched. */
+#define FSM_HIP_TALLY_ADD 1u
+int fsm_hip_tally_ids_device(const uint64_t *d_off, const uint32_t *d_id, size_t m, size_t total, const uint64_t *d_group_off,
+	size_t ngroups, size_t nrules, unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream);
+int fsm_hip_matches_tally_device(const struct fsm_hip_matches *mt, const uint64_t *d_group_off, size_t ngroups, size_t nrules,
+	unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream);
+int fsm_hip_tokens_tally_device(const struct fsm_hip_tokens *tk, const uint64_t *d_group_off, size_t ngroups, size_t nrules,
+	unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream);
+int fsm_hip_matches_tally(const struct fsm_hip_matches *mt, const uint64_t *group_off, size_t ngroups, size_t nrules, unsigned flags,
+	uint64_t *count, uint64_t *lines);
+int fsm_hip_tokens_tally(const struct fsm_hip_tokens *tk, const uint64_t *group_off, size_t ngroups, size_t nrules, unsigned flags,
+	uint64_t *count, uint64_t *lines);
+int fsm_hip_text_matches_tally(const struct fsm_hip_matches *mt, const struct fsm_hip_text *t, const struct fsm_hip_text_hits *hits,
+	size_t nrules, unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream);
+int fsm_hip_text_tokens_tally(const struct fsm_hip_tokens *tk, const struct fsm_hip_text *t, const struct fsm_hip_text_hits *hits,
+	size_t nrules, unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream);
+size_t fsm_hip_tally_span_inputs(void);        /* inputs of a granule: a workgroup takes whole granules */
+size_t fsm_hip_tally_window(void);             /* entries a workgroup takes a step, one per lane */
+size_t fsm_hip_tally_lds_columns(void);        /* columns (nrules + 1) up to which the counters are kept in LDS */
+size_t fsm_hip_tally_max_line_columns(void);   /* columns up to which lines can be counted */
+
+/* ------------------------------------------------------------------ */
 /* synthetic input generator (benchmarks and parity tests)            */
 /* ------------------------------------------------------------------ */
 

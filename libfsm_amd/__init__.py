@@ -16,4 +16,5 @@ from .capi import (  # noqa: F401
     MATCHES_DROP_EMPTY, MatchBatch, HipMatches,
     REPL_MASK, HipRepl, HipReplaced, replaced_block_lines, replaced_block_bytes, repl_lds_bytes, repl_lds_rules, repl_max_inserts,
     RULES_KEEP_OTHER, HipRules, HipExtracted, extracted_block_matches, extracted_block_bytes,
+    TALLY_ADD, tally_ids_device, tally_span_inputs, tally_window, tally_lds_columns, tally_max_line_columns,
 )

@@ -43,6 +43,7 @@ TOKENS_NO_BACKTRACK, TOKENS_SKIP_BAD = 1, 2
 MATCHES_DROP_EMPTY = 1
 REPL_MASK = 1
 RULES_KEEP_OTHER = 1
+TALLY_ADD = 1
 IDS_EARLIEST, IDS_RET, IDS_ERROR = 1, 2, 3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -265,6 +266,12 @@ PROTOTYPES = {"fsm_hip_" + name: (restype, args) for restype, names, *args in (
     (I, "extracted_copy", P, P, P, P, P),
     (D, "extracted_ms", P),
     (D, "extracted_pass_ms", P, I),
+    # tally: (object | off, id, m, total), (group_off, ngroups | text, hits), nrules, flags, count, lines[, stream]
+    (I, "tally_ids_device", P, P, S, S, P, S, S, U, P, P, P),
+    (I, "matches_tally_device tokens_tally_device", P, P, S, S, U, P, P, P),
+    (I, "matches_tally tokens_tally", P, P, S, S, U, P, P),
+    (I, "text_matches_tally text_tokens_tally", P, P, P, S, U, P, P, P),
+    (S, "tally_span_inputs tally_window tally_lds_columns tally_max_line_columns"),
     # input generators: (out, stride, n, first_index, seed, {bytes, count}..., every[, stream])
     (I, "gen_inputs_device", P, S, S, U64, U64, P, U, P, U, U, P),
     (None, "gen_inputs_host", P, S, S, U64, U64, P, U, P, U, U),
@@ -1612,11 +1619,66 @@ class TokDfa(_Owned):
                                 stream or None), (starts, self, text, hits))
 
 
-class HipTokens(_Owned):
+class _Tally:
+    """the three forms of the tally (include/fsm_hip.h, "tally") over the off and id arrays an object owns; _TALLY: its name in
+    the library's functions"""
+
+    _TALLY = None
+
+    def tally(self, group_off=None, nrules: int = 0, lines: bool = True, add_to=None):
+        """fsm_hip_<object>_tally on host arrays -> (count, lines), each (G, nrules + 1) u64, lines None when not asked for;
+        add_to: a (count, lines) pair of such arrays, or of None, that the new counts are added to"""
+        goff = None if group_off is None else np.ascontiguousarray(group_off, np.uint64)
+        G = 1 if goff is None else len(goff) - 1
+        shape = (max(G, 0), nrules + 1)
+        if add_to is not None:
+            count, lin = (None if a is None else np.ascontiguousarray(a, np.uint64).reshape(shape).copy() for a in add_to)
+        else:
+            count, lin = np.zeros(shape, np.uint64), np.zeros(shape, np.uint64) if lines else None
+        _call("fsm_hip_%s_tally" % self._TALLY, self._h, _ptr(goff), max(G, 0), nrules, TALLY_ADD if add_to is not None else 0, _ptr(count), _ptr(lin))
+        return count, lin
+
+    def tally_device(self, d_group_off: int, ngroups: int, nrules: int, d_count: int, d_lines: int, flags: int = 0, stream: int = 0) -> None:
+        """fsm_hip_<object>_tally_device: device addresses, 0: NULL; in flight on `stream` at return"""
+        _call("fsm_hip_%s_tally_device" % self._TALLY, self._h, d_group_off or None, ngroups, nrules, flags, d_count or None, d_lines or None,
+              stream or None)
+
+    def text_tally(self, text: "HipText", hits: Optional["HipHits"] = None, nrules: int = 0, d_count: int = 0, d_lines: int = 0, flags: int = 0,
+                   stream: int = 0) -> None:
+        """fsm_hip_text_<object>_tally: the groups are the files of the text (of its hits); tables of max(files, 1) rows on the device"""
+        _call("fsm_hip_text_%s_tally" % self._TALLY, self._h, text.handle if text is not None else None, hits.handle if hits is not None else None,
+              nrules, flags, d_count or None, d_lines or None, stream or None)
+
+
+def tally_ids_device(d_off: int, d_id: int, m: int, total: int, d_group_off: int, ngroups: int, nrules: int, d_count: int, d_lines: int,
+                     flags: int = 0, stream: int = 0) -> None:
+    """fsm_hip_tally_ids_device: the reduction over any off[m + 1] / id[total] on the current device"""
+    _call("fsm_hip_tally_ids_device", d_off or None, d_id or None, m, total, d_group_off or None, ngroups, nrules, flags, d_count or None,
+          d_lines or None, stream or None)
+
+
+def tally_span_inputs() -> int:
+    return int(load_library().fsm_hip_tally_span_inputs())
+
+
+def tally_window() -> int:
+    return int(load_library().fsm_hip_tally_window())
+
+
+def tally_lds_columns() -> int:
+    return int(load_library().fsm_hip_tally_lds_columns())
+
+
+def tally_max_line_columns() -> int:
+    return int(load_library().fsm_hip_tally_max_line_columns())
+
+
+class HipTokens(_Owned, _Tally):
     """struct fsm_hip_tokens *: off[m + 1], end[total], id[total], err[m] on the device.  Keeps its image (and its text and
     hits) alive: the tokens must be freed first."""
 
     _FREE = "fsm_hip_tokens_free"
+    _TALLY = "tokens"
     count = _size("fsm_hip_tokens_count")
     total = _size("fsm_hip_tokens_total")
     off_ptr = _dev("fsm_hip_tokens_off_device")
@@ -1643,11 +1705,12 @@ class HipTokens(_Owned):
 
 # ---- matches: every match of every line, start / end / end-id, in one call (include/fsm_hip.h, "matches") ----
 
-class HipMatches(_Freed):
+class HipMatches(_Freed, _Tally):
     """struct fsm_hip_matches *: off[m + 1], start[total], end[total], id[total] on the device.  Keeps its two images (and its
     text and hits) alive: the matches must be freed first."""
 
     _FREE = "fsm_hip_matches_free"
+    _TALLY = "matches"
 
     @classmethod
     def run(cls, starts: PosDfa, ends: TokDfa, base: np.ndarray, off: np.ndarray, pick=None, trim_byte: int = -1, flags: int = 0) -> "HipMatches":
