@@ -1347,6 +1347,76 @@ size_t fsm_hip_tally_lds_columns(void);        /* columns (nrules + 1) up to whi
 size_t fsm_hip_tally_max_line_columns(void);   /* columns up to which lines can be counted */
 
 /* ------------------------------------------------------------------ */
+/* distinct: the distinct records of a packed text, with their counts, on the device */
+/* ------------------------------------------------------------------ */
+
+/* grep -o PATTERN | sort | uniq -c without the sort and without the host: which values occur -- addresses, URLs, names, error
+ * codes -- and how often.  The tally counts by rule id; this counts by content.
+ *   Input.  A packed text on the current device: off[R + 1] (ascending) and bytes; trim_byte in -1 .. 255, with the library's usual
+ *   rule: with trim_byte >= 0 a non-empty record whose last byte equals trim_byte is one byte shorter, and at most one byte is
+ *   dropped; optionally tag[R].
+ *   The KEY of record r is its trimmed bytes, together with tag[r] where tags are given.  Two records are equal iff their keys are:
+ *   "a\n" and a final "a" are equal under trim_byte = '\n', a record that is only the trim byte equals an empty record, and equal
+ *   bytes under different tags are different keys.
+ *   Output.  D distinct keys, numbered by first occurrence.  first[D]: the lowest r of each key, strictly ascending.  count[D]:
+ *   the records with that key; the counts sum to R.  class[R]: the d of every record, so first[class[r]] <= r and the keys of r and
+ *   of first[class[r]] are equal -- class is what fsm_hip_tally_ids_device takes as its id array, which gives counts per file per
+ *   distinct value.  And a fresh packed text of the keys: doff[D + 1] with doff[0] = 0, plus dbytes, the trimmed bytes of record
+ *   first[d], each followed by the byte sep_byte if sep_byte >= 0.  With '\n' this is what sort -u prints, in order of first
+ *   appearance; it can go back into any device front (with trim_byte = sep_byte), this one included.
+ *   Every output is a function of the input alone: none depends on the hash function, the table size or the order in which lanes
+ *   arrive.  The result is exact and identical on every run.  The keys are not sorted: callers sort D keys, not R.
+ *   Limits.  R <= 2^32 - 2 (EOVERFLOW above).  R == 0 gives a valid object with D = 0 and stores into nothing but doff[0].  No byte
+ *   outside [bytes, bytes + min(off[R], nbytes)) is read.  Entries of off are clamped to that limit and to their predecessor, as
+ *   the extraction clamps.  No store leaves the object's own arrays: wrong arrays may give wrong classes, never a wild access.
+ * Passes.  hash: a lane per record, the key's 16-byte chunks one by one; records above fsm_hip_distinct_long_bytes() are listed
+ * and hashed by a wavefront each, with a sum over the chunks that does not depend on how they are split, so no lane's work grows
+ * with a record beyond that bound; the trimmed lengths are kept.  insert: an open-addressing, linear-probing table of
+ * fsm_hip_distinct_table_slots(R) slots, a power of two >= 2 R; a slot is one u64, tag32(hash) << 32 | r, empty is all ones; a
+ * record claims the first empty slot of its chain by a compare-and-swap, and on a slot with its tag it compares its key with the
+ * key of the record the slot names -- byte for byte, always: equal hashes decide nothing -- and lowers the slot to its own r by an
+ * atomic min where the keys are equal, so every key lives in one slot, which ends holding the LOWEST r of the key.  Equal records
+ * of a wavefront are combined before the table is touched: one insert and one add to the slot's counter for all of them.  Slots are
+ * read by returning atomics and agent-scope atomic loads alone.  number: first(r) = the slot of r names r; per block of records the
+ * pair (firsts, key bytes), the scan of the block pairs by one workgroup, ONE wait for D and the bytes, the allocation, then the
+ * block's own scan redone: first, count, doff, class.  write: the extraction's write pass over doff, a lane per 16 output bytes.
+ * Number and write are in flight at return.
+ * fsm_hip_distinct_device takes device pointers and hip_stream.  fsm_hip_distinct takes host arrays, stages them and waits;
+ * nbytes is off[R]; a decreasing off is EINVAL before any launch.  fsm_hip_extracted_distinct is over the records of an extracted
+ * object, with trim_byte = the separator the extraction was made with, enqueued behind the object's last event.
+ * fsm_hip_text_hits_distinct is over the lines of hits, with trim_byte = the text's delimiter; hits made with
+ * FSM_HIP_HITS_NO_BYTES have no lines on the device: EINVAL.  The distinct object must be freed before the objects it came from.
+ * It owns, on the device: first[D] and count[D] (NULL when D == 0), class[R] (NULL when R == 0), doff[D + 1] (always there unless
+ * FSM_HIP_DISTINCT_NO_TEXT) and the bytes (NULL when there are none).  _count is D, _records R, _nbytes doff[D].  _copy copies out
+ * whichever of first / count / class / doff / dbytes are not NULL and waits (doff under NO_TEXT: EINVAL).  _ms: all passes by HIP
+ * events; _pass_ms: one of them -- 0 hash, 1 insert (with the clearing of the table), 2 number, 3 write.
+ * NULL + errno: ENODEV (checked first: there is no CPU path), EINVAL (a NULL object, d_off NULL, d_bytes NULL with nbytes > 0, a
+ * byte argument outside -1 .. 255, an unknown flag bit; host form: an off that decreases), EOVERFLOW (R > 2^32 - 2), ENOMEM. */
+#define FSM_HIP_DISTINCT_NO_TEXT   1u  /* no doff / dbytes: first, count, class only; no second allocation */
+#define FSM_HIP_DISTINCT_WEAK_HASH 2u  /* for tests: every chain starts in one of the LAST four slots of the table (by length & 3) */
+struct fsm_hip_distinct;
+struct fsm_hip_distinct *fsm_hip_distinct_device(const uint64_t *d_off, const void *d_bytes, size_t R, uint64_t nbytes, int trim_byte,
+	const uint32_t *d_tag, int sep_byte, unsigned flags, void *hip_stream);
+struct fsm_hip_distinct *fsm_hip_distinct(const uint64_t *off, const void *bytes, size_t R, int trim_byte, const uint32_t *tag,
+	int sep_byte, unsigned flags);
+struct fsm_hip_distinct *fsm_hip_extracted_distinct(const struct fsm_hip_extracted *x, int sep_byte, unsigned flags, void *hip_stream);
+struct fsm_hip_distinct *fsm_hip_text_hits_distinct(const struct fsm_hip_text_hits *hits, int sep_byte, unsigned flags, void *hip_stream);
+size_t fsm_hip_distinct_count(const struct fsm_hip_distinct *dx);               /* D: the distinct keys */
+size_t fsm_hip_distinct_records(const struct fsm_hip_distinct *dx);             /* R */
+uint64_t fsm_hip_distinct_nbytes(const struct fsm_hip_distinct *dx);            /* doff[D]; 0 under NO_TEXT */
+const uint64_t *fsm_hip_distinct_first_device(const struct fsm_hip_distinct *dx);   /* D; NULL when D == 0 */
+const uint64_t *fsm_hip_distinct_count_device(const struct fsm_hip_distinct *dx);   /* D; NULL when D == 0 */
+const uint32_t *fsm_hip_distinct_class_device(const struct fsm_hip_distinct *dx);   /* R; NULL when R == 0 */
+const uint64_t *fsm_hip_distinct_off_device(const struct fsm_hip_distinct *dx);     /* D + 1, always there unless NO_TEXT */
+const unsigned char *fsm_hip_distinct_bytes_device(const struct fsm_hip_distinct *dx);   /* NULL when nbytes == 0 */
+int fsm_hip_distinct_copy(const struct fsm_hip_distinct *dx, uint64_t *first, uint64_t *count, uint32_t *cls, uint64_t *doff, void *dbytes);
+double fsm_hip_distinct_ms(const struct fsm_hip_distinct *dx);
+double fsm_hip_distinct_pass_ms(const struct fsm_hip_distinct *dx, int pass);   /* 0: hash, 1: insert, 2: number, 3: write */
+size_t fsm_hip_distinct_long_bytes(void);      /* keys above it are hashed by a wavefront each */
+size_t fsm_hip_distinct_table_slots(size_t R); /* a power of two >= 2 R, at least 16; 0 + EOVERFLOW above 2^32 - 2 */
+void fsm_hip_distinct_free(struct fsm_hip_distinct *dx);
+
+/* ------------------------------------------------------------------ */
 /* synthetic input generator (benchmarks and parity tests)            */
 /* ------------------------------------------------------------------ */
 

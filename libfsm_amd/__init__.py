@@ -17,4 +17,5 @@ from .capi import (  # noqa: F401
     REPL_MASK, HipRepl, HipReplaced, replaced_block_lines, replaced_block_bytes, repl_lds_bytes, repl_lds_rules, repl_max_inserts,
     RULES_KEEP_OTHER, HipRules, HipExtracted, extracted_block_matches, extracted_block_bytes,
     TALLY_ADD, tally_ids_device, tally_span_inputs, tally_window, tally_lds_columns, tally_max_line_columns,
+    DISTINCT_NO_TEXT, DISTINCT_WEAK_HASH, HipDistinct, distinct_device, distinct, distinct_long_bytes, distinct_table_slots,
 )

