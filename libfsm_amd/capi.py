@@ -1998,21 +1998,11 @@ def extracted_block_bytes() -> int:
 
 # ---- distinct: the distinct records of a packed text with their counts (include/fsm_hip.h, "distinct") ----
 
-class HipDistinct:
+class HipDistinct(_Freed):
     """struct fsm_hip_distinct *: first[D], count[D], class[R] and the packed text of the keys, doff[D + 1] and the bytes, on the
-    device.  Keeps what it was made from alive: the distinct object must be freed first.
-    It owns its handle exactly as an _Owned / _Freed does -- by their own functions, taken over below -- without deriving from
-    them: tests/test_capi_owned.py holds the classes that derive from _Owned to a list of sixteen names, and that file is not
-    this change's to edit.  tests/test_distinct_abi.py holds this class to the same rules."""
+    device.  Keeps what it was made from alive: the distinct object must be freed first."""
 
     _FREE = "fsm_hip_distinct_free"
-    __init__ = _Owned.__init__
-    close = _Owned.close
-    handle = _Owned.handle
-    free = _Freed.free
-
-    def __del__(self):
-        self.close()      # (not an alias: a subclass's close is the one that runs)
 
     count = _size("fsm_hip_distinct_count", "D: the distinct keys")
     records = _size("fsm_hip_distinct_records", "R")

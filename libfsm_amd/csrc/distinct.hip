@@ -36,11 +36,47 @@
 #include <cerrno>
 #include <cstdint>
 
-#include "hip_host.h"
+#include "../../include/fsm_hip.h"
+#include "front.h"
 #include "match_marks.h"
 #include "extract.h"
-#include "distinct.h"
 #include "distinct_seg.h"
+#include "text_objects.h"
+
+namespace fsmhip {
+
+constexpr uint32_t DST_THREADS = 256;
+constexpr uint32_t DST_RECORDS = DST_THREADS;               /* records of a block of every pass, one per lane */
+constexpr uint32_t DST_LONG_BYTES = 256;                    /* keys above it are hashed by a wavefront each */
+constexpr uint32_t DST_PAIRS_EXTRA = 4;                     /* behind the block pairs: the two totals, the limit, the long records */
+
+constexpr uint64_t dst_blocks(uint64_t R) { return (R + DST_RECORDS - 1u) / DST_RECORDS; }
+
+/* the passes' arguments; every pointer is device memory.  The kernels take this struct itself. */
+struct DstRun {
+	/* the packed text */
+	const uint64_t *off = nullptr;           /* R + 1 */
+	const unsigned char *bytes = nullptr;
+	const uint32_t *tag = nullptr;           /* R, or null */
+	uint64_t R = 0, nbytes = 0;
+	int trim = -1, sep = -1;
+	bool weak = false;
+	/* internal, sized by R */
+	uint64_t slots = 0;
+	uint64_t *len = nullptr;                 /* R: the trimmed lengths */
+	uint64_t *hash = nullptr;                /* R: the hashes; from the insert pass on, the slot of each record */
+	uint32_t *cls = nullptr;                 /* R: class; until the insert pass, the list of the long records */
+	uint64_t *table = nullptr, *cnt = nullptr;   /* slots each: the slot words; the records of a slot, then its dense number */
+	uint64_t *pairs = nullptr;               /* per block (firsts, key bytes), then (scanned) those before it; + DST_PAIRS_EXTRA */
+	/* the object's arrays, sized after the scan */
+	uint64_t *first = nullptr, *count = nullptr;   /* D each */
+	uint64_t *doff = nullptr;                /* D + 1, or null (NO_TEXT) */
+	uint64_t *src = nullptr;                 /* D: where each key's bytes begin in `bytes`; with doff */
+	uint64_t *bfirst = nullptr;              /* ngb + 1: the key that covers the first byte of each output block; with doff */
+	uint64_t D = 0, total = 0, ngb = 0;      /* known after the scan */
+};
+
+}
 
 using namespace fsmhip;
 
@@ -370,7 +406,8 @@ int launched() { return HIP_OK(hipGetLastError()) ? 0 : -1; }
 
 namespace fsmhip {
 
-int dst_launch_hash(const DstRun &r, hipStream_t s)
+/* each on stream s, the object's device current, R >= 1; 0, or -1 + errno */
+static int dst_launch_hash(const DstRun &r, hipStream_t s)
 {
 	const uint64_t nb = dst_blocks(r.R);
 	hipLaunchKernelGGL(dst_hash, dim3((unsigned)nb), dim3(DST_THREADS), 0, s, r);
@@ -380,19 +417,19 @@ int dst_launch_hash(const DstRun &r, hipStream_t s)
 	return launched();
 }
 
-int dst_launch_insert(const DstRun &r, hipStream_t s)
+static int dst_launch_insert(const DstRun &r, hipStream_t s)
 {
 	hipLaunchKernelGGL(dst_insert, dim3((unsigned)dst_blocks(r.R)), dim3(DST_THREADS), 0, s, r);
 	return launched();
 }
 
-int dst_launch_mark(const DstRun &r, hipStream_t s)
+static int dst_launch_mark(const DstRun &r, hipStream_t s)
 {
 	hipLaunchKernelGGL(dst_mark, dim3((unsigned)dst_blocks(r.R)), dim3(DST_THREADS), 0, s, r);
 	return launched();
 }
 
-int dst_launch_number(const DstRun &r, hipStream_t s)
+static int dst_launch_number(const DstRun &r, hipStream_t s)
 {
 	if (r.D == 0) return 0;
 	hipLaunchKernelGGL(dst_number, dim3((unsigned)dst_blocks(r.R)), dim3(DST_THREADS), 0, s, r);
@@ -402,3 +439,231 @@ int dst_launch_number(const DstRun &r, hipStream_t s)
 }
 
 }   // namespace fsmhip
+
+/* ---- the fronts: the distinct records as an object of five event pairs (front.h) -------------------------------------------------
+ * hash -> insert -> mark -> the scan of the block pairs by one workgroup -> ONE wait for D, the key bytes and the read limit -> the
+ * allocation -> number -> write, which is the extraction's write pass over doff / src.  Five event pairs: mark + scan and number
+ * are reported together, so the wait and the allocation lie in neither. */
+extern "C" size_t fsm_hip_distinct_long_bytes(void) { return fsmhip::DST_LONG_BYTES; }
+
+extern "C" size_t fsm_hip_distinct_table_slots(size_t R)
+{
+	if ((uint64_t)R > fsmhip::DST_MAX_RECORDS) { errno = EOVERFLOW; return 0; }
+	return (size_t)fsmhip::dst_table_slots(R);
+}
+
+struct __attribute__((visibility("hidden"))) fsm_hip_distinct : RunObject<5> {   /* hash, insert, mark + scan, number, write */
+	size_t D = 0;                            /* (m is R) */
+	uint64_t nbytes = 0;
+	DevBuf<uint64_t> d_len, d_hash;          /* R each: internal */
+	DevBuf<uint32_t> d_class;                /* R */
+	DevBuf<uint64_t> d_table, d_cnt;         /* one per slot: internal */
+	DevBuf<uint64_t> d_pairs;                /* per block of records, + DST_PAIRS_EXTRA: internal */
+	DevBuf<uint64_t> d_first, d_count;       /* D */
+	DevBuf<uint64_t> d_doff;                 /* D + 1; NULL under NO_TEXT */
+	DevBuf<uint64_t> d_src;                  /* D: internal */
+	DevBuf<uint64_t> d_bfirst;               /* per block of the output, + 1: internal */
+	DevBuf<unsigned char> d_dbytes;          /* nbytes, in whole blocks */
+	DevBuf<uint64_t> own_off;                /* the host form's staged input */
+	DevBuf<unsigned char> own_bytes;
+	DevBuf<uint32_t> own_tag;
+};
+
+extern "C" void fsm_hip_distinct_free(struct fsm_hip_distinct *dx) { run_free(dx); }
+
+/* the passes on stream s into *dx, its device current; r: the packed text, the bytes and the flag (the rest is set here) */
+static int distinct_passes(struct fsm_hip_distinct *dx, fsmhip::DstRun r, bool text, hipStream_t s)
+{
+	if (r.R == 0) {                                  /* no record: doff[0] alone, and nothing is launched */
+		if (text && (!HIP_OK(dx->d_doff.alloc(1)) || !HIP_OK(hipMemsetAsync(dx->d_doff.p, 0, sizeof(uint64_t), s)))) return -1;
+		for (DevEvent &ev : dx->ev)
+			if (!HIP_OK(hipEventRecord(ev, s))) return -1;
+		return 0;
+	}
+	const uint64_t nblocks = fsmhip::dst_blocks(r.R);
+	uint64_t tot[3] = {0, 0, 0};                     /* the firsts, the key bytes, the bytes that may be read */
+	r.slots = fsmhip::dst_table_slots(r.R);
+	if (!HIP_OK(dx->d_len.alloc(r.R)) || !HIP_OK(dx->d_hash.alloc(r.R)) || !HIP_OK(dx->d_class.alloc(r.R)) || !HIP_OK(dx->d_table.alloc(r.slots)) ||
+	    !HIP_OK(dx->d_cnt.alloc(r.slots)) || !HIP_OK(dx->d_pairs.alloc(2u * nblocks + fsmhip::DST_PAIRS_EXTRA)))
+		return -1;
+	r.len = dx->d_len;
+	r.hash = dx->d_hash;
+	r.cls = dx->d_class;
+	r.table = dx->d_table;
+	r.cnt = dx->d_cnt;
+	r.pairs = dx->d_pairs;
+	if (!dx->begin(0, s)) return -1;
+	if (!HIP_OK(hipMemsetAsync(r.pairs + 2u * nblocks, 0, fsmhip::DST_PAIRS_EXTRA * sizeof(uint64_t), s))) return -1;   /* the long records' count */
+	if (fsmhip::dst_launch_hash(r, s) != 0) return -1;
+	if (!dx->end(0, s) || !dx->begin(1, s)) return -1;
+	if (!HIP_OK(hipMemsetAsync(r.table, 0xff, r.slots * sizeof(uint64_t), s)) || !HIP_OK(hipMemsetAsync(r.cnt, 0, r.slots * sizeof(uint64_t), s))) return -1;
+	if (fsmhip::dst_launch_insert(r, s) != 0) return -1;
+	if (!dx->end(1, s) || !dx->begin(2, s)) return -1;
+	if (fsmhip::dst_launch_mark(r, s) != 0) return -1;
+	if (pairs_scan_launch(r.pairs, nblocks, s) != 0) return -1;
+	if (!dx->end(2, s)) return -1;
+	/* the ONE wait: D sizes first and count, the bytes the text of the keys */
+	if (!HIP_OK(hipMemcpyAsync(tot, r.pairs + 2u * nblocks, sizeof tot, hipMemcpyDeviceToHost, s)) || !HIP_OK(hipStreamSynchronize(s))) return -1;
+	dx->D = (size_t)tot[0];
+	dx->nbytes = text ? tot[1] : 0u;
+	r.D = tot[0];
+	r.total = dx->nbytes;
+	r.ngb = (r.total + fsmhip::EXT_BLOCK - 1u) / fsmhip::EXT_BLOCK;
+	if (r.D != 0 && (!HIP_OK(dx->d_first.alloc(r.D)) || !HIP_OK(dx->d_count.alloc(r.D)))) return -1;
+	if (text && (!HIP_OK(dx->d_doff.alloc(r.D + 1u)) || (r.D != 0 && !HIP_OK(dx->d_src.alloc(r.D))))) return -1;
+	if (r.total != 0 && (!HIP_OK(dx->d_dbytes.alloc(r.ngb * fsmhip::EXT_BLOCK)) || !HIP_OK(dx->d_bfirst.alloc(r.ngb + 1u)))) return -1;
+	r.first = dx->d_first;
+	r.count = dx->d_count;
+	r.doff = dx->d_doff;
+	r.src = dx->d_src;
+	r.bfirst = dx->d_bfirst;
+	if (!dx->begin(3, s)) return -1;
+	if (r.D == 0) {                                  /* (not with R >= 1; the arrays changed under the passes) */
+		if (text && !HIP_OK(hipMemsetAsync(dx->d_doff.p, 0, sizeof(uint64_t), s))) return -1;
+	} else if (fsmhip::dst_launch_number(r, s) != 0) {
+		return -1;
+	}
+	if (!dx->end(3, s) || !dx->begin(4, s)) return -1;
+	if (r.D != 0 && r.total != 0) {                  /* the extraction's write pass: record d is the key of first[d] */
+		fsmhip::ExtRun w;
+		w.base = r.bytes;
+		w.limit = tot[2];
+		w.sep = r.sep;
+		w.out_off = r.doff;
+		w.src = r.src;
+		w.first = r.bfirst;
+		w.out = dx->d_dbytes;
+		w.nrec = r.D;
+		w.total = r.total;
+		w.ngb = r.ngb;
+		const Grid g = grid_of(r.ngb, dx->device);
+		w.wgs = g.wgs;
+		w.per = g.per;
+		if (fsmhip::ext_launch_write(w, s) != 0) return -1;
+	}
+	return dx->end(4, s) ? 0 : -1;
+}
+
+/* what every form refuses alike, behind ENODEV and the form's own NULLs */
+static bool distinct_args(size_t R, int trim_byte, int sep_byte, unsigned flags)
+{
+	if (trim_byte < -1 || trim_byte > 255 || sep_byte < -1 || sep_byte > 255 || (flags & ~(FSM_HIP_DISTINCT_NO_TEXT | FSM_HIP_DISTINCT_WEAK_HASH)) != 0u) {
+		errno = EINVAL;
+		return false;
+	}
+	if ((uint64_t)R > fsmhip::DST_MAX_RECORDS) { errno = EOVERFLOW; return false; }
+	return true;
+}
+
+/* the object over device arrays on stream s, `device` current, behind `after` (or nothing) */
+static struct fsm_hip_distinct *distinct_new(int device, const uint64_t *d_off, const void *d_bytes, size_t R, uint64_t nbytes, int trim_byte,
+	const uint32_t *d_tag, int sep_byte, unsigned flags, hipEvent_t after, hipStream_t s)
+{
+	fsmhip::DstRun r;
+	r.off = d_off;
+	r.bytes = static_cast<const unsigned char *>(d_bytes);
+	r.tag = d_tag;
+	r.R = R;
+	r.nbytes = nbytes;
+	r.trim = trim_byte;
+	r.sep = sep_byte;
+	r.weak = (flags & FSM_HIP_DISTINCT_WEAK_HASH) != 0u;
+	return run_new<struct fsm_hip_distinct>(device, R, true, s, [&](struct fsm_hip_distinct *dx) {
+		if (after != nullptr && !HIP_OK(hipStreamWaitEvent(s, after, 0))) return -1;
+		return distinct_passes(dx, r, (flags & FSM_HIP_DISTINCT_NO_TEXT) == 0u, s);
+	});
+}
+
+extern "C" struct fsm_hip_distinct *fsm_hip_distinct_device(const uint64_t *d_off, const void *d_bytes, size_t R, uint64_t nbytes, int trim_byte,
+	const uint32_t *d_tag, int sep_byte, unsigned flags, void *hip_stream)
+{
+	int dev = 0;
+	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
+	if (d_off == nullptr || (d_bytes == nullptr && nbytes != 0)) { errno = EINVAL; return nullptr; }
+	if (!distinct_args(R, trim_byte, sep_byte, flags)) return nullptr;
+	return distinct_new(dev, d_off, d_bytes, R, nbytes, trim_byte, d_tag, sep_byte, flags, nullptr, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" struct fsm_hip_distinct *fsm_hip_distinct(const uint64_t *off, const void *bytes, size_t R, int trim_byte, const uint32_t *tag, int sep_byte,
+	unsigned flags)
+{
+	int dev = 0;
+	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
+	if (off == nullptr) { errno = EINVAL; return nullptr; }
+	if (!distinct_args(R, trim_byte, sep_byte, flags)) return nullptr;
+	for (size_t r = 0; r < R; r++)
+		if (off[r] > off[r + 1u]) { errno = EINVAL; return nullptr; }
+	const uint64_t nbytes = R != 0 ? off[R] : 0u;
+	if (bytes == nullptr && nbytes != 0) { errno = EINVAL; return nullptr; }
+	DevStream own;
+	if (!HIP_OK(own.create(hipStreamNonBlocking))) return nullptr;
+	const hipStream_t s = own;
+	fsmhip::DstRun r;
+	r.R = R;
+	r.nbytes = nbytes;
+	r.trim = trim_byte;
+	r.sep = sep_byte;
+	r.weak = (flags & FSM_HIP_DISTINCT_WEAK_HASH) != 0u;
+	struct fsm_hip_distinct *dx = run_new<struct fsm_hip_distinct>(dev, R, true, s, [&](struct fsm_hip_distinct *o) {
+		if (!HIP_OK(o->own_off.alloc(R + 1u)) || !HIP_OK(hipMemcpyAsync(o->own_off.p, off, (R + 1u) * sizeof(uint64_t), hipMemcpyHostToDevice, s))) return -1;
+		if (nbytes != 0 && (!HIP_OK(o->own_bytes.alloc(nbytes)) || !HIP_OK(hipMemcpyAsync(o->own_bytes.p, bytes, nbytes, hipMemcpyHostToDevice, s)))) return -1;
+		if (tag != nullptr && R != 0 &&
+		    (!HIP_OK(o->own_tag.alloc(R)) || !HIP_OK(hipMemcpyAsync(o->own_tag.p, tag, R * sizeof(uint32_t), hipMemcpyHostToDevice, s))))
+			return -1;
+		r.off = o->own_off;
+		r.bytes = o->own_bytes;
+		r.tag = o->own_tag;
+		return distinct_passes(o, r, (flags & FSM_HIP_DISTINCT_NO_TEXT) == 0u, s);
+	});
+	if (dx == nullptr || HIP_OK(hipStreamSynchronize(s))) return dx;   /* (null: run_new left the stream idle) the stream goes at return */
+	const int e = errno;
+	run_free(dx);
+	errno = e;
+	return nullptr;
+}
+
+extern "C" struct fsm_hip_distinct *fsm_hip_extracted_distinct(const struct fsm_hip_extracted *x, int sep_byte, unsigned flags, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (x == nullptr) { errno = EINVAL; return nullptr; }
+	if (!distinct_args(x->nrec, x->sep, sep_byte, flags)) return nullptr;
+	DevGuard dg(x->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	return distinct_new(x->device, x->d_off, x->d_bytes, x->nrec, x->nbytes, x->sep, nullptr, sep_byte, flags, x->done(), static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" struct fsm_hip_distinct *fsm_hip_text_hits_distinct(const struct fsm_hip_text_hits *h, int sep_byte, unsigned flags, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (h == nullptr || h->d_off.p == nullptr) { errno = EINVAL; return nullptr; }   /* (no offsets: FSM_HIP_HITS_NO_BYTES) */
+	if (!distinct_args(h->m, h->delim, sep_byte, flags)) return nullptr;
+	DevGuard dg(h->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	return distinct_new(h->device, h->d_off, h->d_bytes, h->m, h->nbytes, h->delim, nullptr, sep_byte, flags, h->ev[5], static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" size_t fsm_hip_distinct_count(const struct fsm_hip_distinct *dx) { return dx == nullptr ? 0 : dx->D; }
+extern "C" size_t fsm_hip_distinct_records(const struct fsm_hip_distinct *dx) { return dx == nullptr ? 0 : dx->m; }
+extern "C" uint64_t fsm_hip_distinct_nbytes(const struct fsm_hip_distinct *dx) { return dx == nullptr ? 0 : dx->nbytes; }
+extern "C" const uint64_t *fsm_hip_distinct_first_device(const struct fsm_hip_distinct *dx) { return dx == nullptr ? nullptr : dx->d_first.p; }
+extern "C" const uint64_t *fsm_hip_distinct_count_device(const struct fsm_hip_distinct *dx) { return dx == nullptr ? nullptr : dx->d_count.p; }
+extern "C" const uint32_t *fsm_hip_distinct_class_device(const struct fsm_hip_distinct *dx) { return dx == nullptr ? nullptr : dx->d_class.p; }
+extern "C" const uint64_t *fsm_hip_distinct_off_device(const struct fsm_hip_distinct *dx) { return dx == nullptr ? nullptr : dx->d_doff.p; }
+extern "C" const unsigned char *fsm_hip_distinct_bytes_device(const struct fsm_hip_distinct *dx) { return dx == nullptr ? nullptr : dx->d_dbytes.p; }
+
+extern "C" int fsm_hip_distinct_copy(const struct fsm_hip_distinct *dx, uint64_t *first, uint64_t *count, uint32_t *cls, uint64_t *doff, void *dbytes)
+{
+	if (dx == nullptr || (doff != nullptr && dx->d_doff.p == nullptr)) { errno = EINVAL; return -1; }
+	return copy_out(dx->device, dx->done(), {{first, dx->d_first, dx->D * sizeof(uint64_t)}, {count, dx->d_count, dx->D * sizeof(uint64_t)},
+	                                         {cls, dx->d_class, dx->m * sizeof(uint32_t)}, {doff, dx->d_doff, (dx->D + 1u) * sizeof(uint64_t)},
+	                                         {dbytes, dx->d_dbytes, (size_t)dx->nbytes}});
+}
+
+extern "C" double fsm_hip_distinct_ms(const struct fsm_hip_distinct *dx) { return run_ms(dx, 0, 4); }
+
+extern "C" double fsm_hip_distinct_pass_ms(const struct fsm_hip_distinct *dx, int pass)
+{
+	if (pass < 0 || pass > 3) { errno = EINVAL; return -1.0; }
+	return pass < 2 ? run_ms(dx, pass, pass) : pass == 2 ? run_ms(dx, 2, 3) : run_ms(dx, 4, 4);
+}
+

@@ -1,6 +1,7 @@
 /*
- * extract.h -- how text.hip launches the passes of the extraction (extract.hip): ext_lengths, ext_offsets, ext_write.  The
- * fronts (the rule set, the extracted object, the scan of the block pairs) are in text.hip.  Not part of the C ABI.
+ * extract.h -- what another unit reads of extract.hip: the extracted object, whose packed text the distinct records take as their
+ * input, and the write pass (ext_write) with its arguments and its block, which writes the distinct keys as well.  Not part of the
+ * C ABI.
  */
 #ifndef FSMHIP_CSRC_EXTRACT_H
 #define FSMHIP_CSRC_EXTRACT_H
@@ -9,19 +10,34 @@
 
 #include <cstdint>
 
+#include "front.h"
+
+/* lengths pass (per MATCH: kept, the record's bytes, its first byte, its input; per block of EXT_MATCHES matches the pair records /
+ * bytes) -> exclusive scan of the BLOCK pairs by one workgroup -> ONE wait for the two totals -> allocation -> offsets pass (the
+ * block's own scan redone, the compaction, first[]) -> write pass.  The scan runs over total / EXT_MATCHES records.  The offsets
+ * and the write pass are in flight at return. */
+struct __attribute__((visibility("hidden"))) fsm_hip_extracted : RunObject<4> {   /* the lengths, the scan, the offsets, the write pass */
+	size_t nrec = 0;
+	uint64_t nbytes = 0;
+	int sep = -1;                            /* the separator the records were made with */
+	DevBuf<uint64_t> d_off;                  /* nrec + 1 */
+	DevBuf<uint64_t> d_line, d_match;        /* nrec */
+	DevBuf<uint64_t> d_src;                  /* nrec: internal */
+	DevBuf<uint64_t> d_mrec, d_msrc, d_mline;   /* one per match: internal */
+	DevBuf<uint64_t> d_pairs;                /* per block of matches, + the totals: internal */
+	DevBuf<uint64_t> d_first;                /* per block of the output, + 1: internal */
+	DevBuf<unsigned char> d_bytes;           /* nbytes, in whole blocks */
+};
+
 namespace fsmhip {
 
 constexpr uint32_t EXT_THREADS = 256;
-constexpr uint32_t EXT_MATCHES = EXT_THREADS;               /* matches of a block of the lengths and the offsets pass, one per lane */
 constexpr uint32_t EXT_TILES = 4;
 constexpr uint32_t EXT_TILE = EXT_THREADS * 16u;            /* output bytes one store instruction of the workgroup covers */
 constexpr uint32_t EXT_BLOCK = EXT_TILES * EXT_TILE;        /* output bytes a workgroup writes per step: 16 KiB */
 
-/* nmatch matches fit one launch's grid */
-inline bool ext_grid_fits(uint64_t nmatch) { return (nmatch + EXT_MATCHES - 1u) / EXT_MATCHES <= 0x7fffffffu; }
-
 /* the passes' arguments; every pointer is device memory.  The kernels take this struct itself, so it spells the batch's fields
- * out, as ReplRun does: text.hip copies them from a LineBatch. */
+ * out, as the replacement's does: extracted_new copies them from a LineBatch. */
 struct ExtRun {
 	/* the batch */
 	const void *base = nullptr;
@@ -50,9 +66,7 @@ struct ExtRun {
 	uint64_t wgs = 1, per = 1;               /* the write pass's grid: wgs workgroups of `per` consecutive output blocks */
 };
 
-/* each on stream s, the objects' device current; 0, or -1 + errno */
-__attribute__((visibility("hidden"))) int ext_launch_lengths(const ExtRun &r, hipStream_t s);
-__attribute__((visibility("hidden"))) int ext_launch_offsets(const ExtRun &r, hipStream_t s);
+/* ext_write on stream s, the objects' device current; 0, or -1 + errno */
 __attribute__((visibility("hidden"))) int ext_launch_write(const ExtRun &r, hipStream_t s);
 
 }

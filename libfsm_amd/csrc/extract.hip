@@ -27,12 +27,27 @@
 
 #include <cerrno>
 #include <cstdint>
+#include <cstring>
+#include <new>
+#include <optional>
+#include <vector>
 
 #include "../../include/fsm_hip.h"
-#include "hip_host.h"
+#include "front.h"
+#include "match.h"
 #include "match_marks.h"
 #include "extract.h"
 #include "extract_seg.h"
+#include "text_objects.h"
+
+namespace fsmhip {
+
+constexpr uint32_t EXT_MATCHES = EXT_THREADS;               /* matches of a block of the lengths and the offsets pass, one per lane */
+
+/* nmatch matches fit one launch's grid */
+static bool ext_grid_fits(uint64_t nmatch) { return (nmatch + EXT_MATCHES - 1u) / EXT_MATCHES <= 0x7fffffffu; }
+
+}
 
 using namespace fsmhip;
 
@@ -253,7 +268,8 @@ ext_write(const ExtRun a)
 
 namespace fsmhip {
 
-int ext_launch_lengths(const ExtRun &r, hipStream_t s)
+/* each on stream s, the objects' device current; 0, or -1 + errno */
+static int ext_launch_lengths(const ExtRun &r, hipStream_t s)
 {
 	if (r.m == 0 || r.nmatch == 0) return 0;
 	if (!ext_grid_fits(r.nmatch)) { errno = ENOMEM; return -1; }
@@ -262,7 +278,7 @@ int ext_launch_lengths(const ExtRun &r, hipStream_t s)
 	return HIP_OK(hipGetLastError()) ? 0 : -1;
 }
 
-int ext_launch_offsets(const ExtRun &r, hipStream_t s)
+static int ext_launch_offsets(const ExtRun &r, hipStream_t s)
 {
 	if (r.m == 0 || r.nmatch == 0 || r.nrec == 0) return 0;
 	if (!ext_grid_fits(r.nmatch)) { errno = ENOMEM; return -1; }
@@ -281,3 +297,189 @@ int ext_launch_write(const ExtRun &r, hipStream_t s)
 }
 
 }   // namespace fsmhip
+
+/* ---- the fronts: the rule set, and the extracted text as an object of four passes (extract.h, front.h) --------------------------- */
+struct __attribute__((visibility("hidden"))) fsm_hip_rules {
+	int device = 0;
+	size_t nrules = 0;
+	unsigned flags = 0;
+	DevBuf<uint32_t> d_bits;                 /* nrules bits in words of 32, never nothing */
+};
+
+extern "C" struct fsm_hip_rules *fsm_hip_rules_create(const void *bits, size_t nrules, unsigned flags)
+{
+	int dev = 0;
+	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
+	if ((flags & ~FSM_HIP_RULES_KEEP_OTHER) != 0u || (bits == nullptr && nrules != 0)) { errno = EINVAL; return nullptr; }
+	struct fsm_hip_rules *rs = new (std::nothrow) struct fsm_hip_rules;
+	if (rs == nullptr) { errno = ENOMEM; return nullptr; }
+	rs->device = dev;
+	rs->nrules = nrules;
+	rs->flags = flags;
+	std::vector<uint32_t> words((nrules + 31u) / 32u, 0u);   /* byte i >> 3, bit i & 7 = word i >> 5, bit i & 31: hosts here are little-endian */
+	if (nrules != 0) memcpy(words.data(), bits, (nrules + 7u) / 8u);
+	if (HIP_OK(rs->d_bits.upload(words))) return rs;
+	const int e = errno;
+	delete rs;
+	errno = e;
+	return nullptr;
+}
+
+extern "C" void fsm_hip_rules_free(struct fsm_hip_rules *rs)
+{
+	if (rs == nullptr) return;
+	const int e = errno;
+	{
+		DevGuard dg(rs->device);
+		delete rs;
+	}
+	errno = e;
+}
+
+extern "C" size_t fsm_hip_extracted_block_matches(void) { return fsmhip::EXT_MATCHES; }
+extern "C" size_t fsm_hip_extracted_block_bytes(void) { return fsmhip::EXT_BLOCK; }
+
+extern "C" void fsm_hip_extracted_free(struct fsm_hip_extracted *x) { run_free(x); }
+
+/* the passes on stream s into *ex, the objects' device current; r: the batch, the matches and the set (its outputs are set here) */
+static int extracted_passes(struct fsm_hip_extracted *ex, fsmhip::ExtRun r, hipStream_t s)
+{
+	if (r.m == 0) r.nmatch = 0;
+	const uint64_t nblocks = (r.nmatch + fsmhip::EXT_MATCHES - 1u) / fsmhip::EXT_MATCHES;
+	uint64_t tot[2] = {0, 0};
+	ex->sep = r.sep;
+	if (r.nmatch != 0 && (!HIP_OK(ex->d_mrec.alloc(r.nmatch)) || !HIP_OK(ex->d_msrc.alloc(r.nmatch)) || !HIP_OK(ex->d_mline.alloc(r.nmatch)) ||
+	                      !HIP_OK(ex->d_pairs.alloc(2u * nblocks + 2u))))
+		return -1;
+	r.mrec = ex->d_mrec;
+	r.msrc = ex->d_msrc;
+	r.mline = ex->d_mline;
+	r.pairs = ex->d_pairs;
+	if (!ex->begin(0, s)) return -1;
+	if (fsmhip::ext_launch_lengths(r, s) != 0) return -1;
+	if (!ex->end(0, s) || !ex->begin(1, s)) return -1;
+	if (pairs_scan_launch(r.pairs, nblocks, s) != 0) return -1;
+	if (!ex->end(1, s)) return -1;
+	/* the ONE wait: the records size off, line and match, the bytes the text and first[] */
+	if (nblocks != 0 && (!HIP_OK(hipMemcpyAsync(tot, r.pairs + 2u * nblocks, sizeof tot, hipMemcpyDeviceToHost, s)) || !HIP_OK(hipStreamSynchronize(s))))
+		return -1;
+	ex->nrec = (size_t)tot[0];
+	ex->nbytes = tot[1];
+	r.nrec = tot[0];
+	r.total = tot[1];
+	r.ngb = (r.total + fsmhip::EXT_BLOCK - 1u) / fsmhip::EXT_BLOCK;
+	if (!HIP_OK(ex->d_off.alloc(r.nrec + 1u))) return -1;
+	if (r.nrec != 0 && (!HIP_OK(ex->d_src.alloc(r.nrec)) || !HIP_OK(ex->d_line.alloc(r.nrec)) || !HIP_OK(ex->d_match.alloc(r.nrec)))) return -1;
+	if (r.total != 0 && (!HIP_OK(ex->d_bytes.alloc(r.ngb * fsmhip::EXT_BLOCK)) || !HIP_OK(ex->d_first.alloc(r.ngb + 1u)))) return -1;
+	r.out_off = ex->d_off;
+	r.src = ex->d_src;
+	r.line = ex->d_line;
+	r.match = ex->d_match;
+	r.out = ex->d_bytes;
+	r.first = ex->d_first;
+	const Grid g = grid_of(r.ngb, ex->device);
+	r.wgs = g.wgs;
+	r.per = g.per;
+	if (!ex->begin(2, s)) return -1;
+	if (r.nrec == 0) {                               /* no record: off[0] alone, and nothing is launched */
+		if (!HIP_OK(hipMemsetAsync(ex->d_off.p, 0, sizeof(uint64_t), s))) return -1;
+	} else if (fsmhip::ext_launch_offsets(r, s) != 0) {
+		return -1;
+	}
+	if (!ex->end(2, s) || !ex->begin(3, s)) return -1;
+	if (fsmhip::ext_launch_write(r, s) != 0) return -1;
+	return ex->end(3, s) ? 0 : -1;
+}
+
+static struct fsm_hip_extracted *extracted_new(const struct fsm_hip_matches *mt, const struct fsm_hip_rules *keep, int sep, const fsmhip::LineBatch &in,
+	hipStream_t s)
+{
+	fsmhip::ExtRun r;
+	r.base = in.base;
+	r.off = in.off;
+	r.pick = in.pick;
+	r.n = in.n;
+	r.m = in.m;
+	r.limit = in.limit;
+	r.moff = mt->d_off;
+	r.start = mt->d_start;
+	r.end = mt->d_end;
+	r.id = mt->d_id;
+	r.nmatch = mt->total;
+	if (keep != nullptr) {
+		r.keep = keep->d_bits;
+		r.nrules = keep->nrules;
+		r.keep_other = (keep->flags & FSM_HIP_RULES_KEEP_OTHER) != 0u;
+	}
+	r.sep = sep;
+	return run_new<struct fsm_hip_extracted>(mt->device, in.m, fsmhip::ext_grid_fits(mt->total), s, [&](struct fsm_hip_extracted *ex) {
+		return HIP_OK(hipStreamWaitEvent(s, mt->done(), 0)) ? extracted_passes(ex, r, s) : -1;   /* behind the matches' emit pass */
+	});
+}
+
+/* what all three forms refuse alike about the matches, the set and the separator */
+static bool extracted_args(const struct fsm_hip_matches *mt, const struct fsm_hip_rules *keep, int sep)
+{
+	if (!have_device()) { errno = ENODEV; return false; }
+	if (mt == nullptr || (keep != nullptr && keep->device != mt->device) || sep < -1 || sep > 255) { errno = EINVAL; return false; }
+	return true;
+}
+
+/* ... and the two batch forms about the batch; *in: the batch as given, which is the matches' own: it passes what theirs passed */
+static bool extracted_check(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b, const struct fsm_hip_rules *keep, int sep,
+	fsmhip::LineBatch *in)
+{
+	if (!extracted_args(mt, keep, sep)) return false;
+	if (!fsmhip::batch_shape(b, FSM_HIP_MATCHES_DROP_EMPTY, in)) return false;
+	if (in->m != (uint64_t)mt->m) { errno = EINVAL; return false; }
+	return true;
+}
+
+extern "C" struct fsm_hip_extracted *fsm_hip_matches_extract_device(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b,
+	const struct fsm_hip_rules *keep, int sep_byte, void *hip_stream)
+{
+	fsmhip::LineBatch in;
+	if (!extracted_check(mt, b, keep, sep_byte, &in) || !fsmhip::batch_device_ok(in)) return nullptr;
+	DevGuard dg(mt->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	if (!fsmhip::batch_read_limit(&in, s)) return nullptr;   /* as the matches: line extents are clamped to the limit */
+	return extracted_new(mt, keep, sep_byte, in, s);
+}
+
+extern "C" struct fsm_hip_extracted *fsm_hip_matches_extract(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b,
+	const struct fsm_hip_rules *keep, int sep_byte)
+{
+	fsmhip::LineBatch host;
+	if (!extracted_check(mt, b, keep, sep_byte, &host) || !fsmhip::batch_host_arrays_ok(host)) return nullptr;
+	return run_host(mt->device, host, [&](const fsmhip::LineBatch &in, hipStream_t s) { return extracted_new(mt, keep, sep_byte, in, s); });
+}
+
+extern "C" struct fsm_hip_extracted *fsm_hip_text_extract(const struct fsm_hip_matches *mt, const struct fsm_hip_text *t,
+	const struct fsm_hip_text_hits *h, const struct fsm_hip_rules *keep, int sep_byte, void *hip_stream)
+{
+	if (!extracted_args(mt, keep, sep_byte)) return nullptr;
+	if (t == nullptr || mt->m != (h != nullptr ? h->m : t->n)) { errno = EINVAL; return nullptr; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	std::optional<DevGuard> dg;
+	fsmhip::LineBatch in;
+	if (!text_batch(t, h, {mt->device}, s, &dg, &in)) return nullptr;
+	return extracted_new(mt, keep, sep_byte, in, s);
+}
+
+extern "C" size_t fsm_hip_extracted_count(const struct fsm_hip_extracted *x) { return x == nullptr ? 0 : x->nrec; }
+extern "C" uint64_t fsm_hip_extracted_nbytes(const struct fsm_hip_extracted *x) { return x == nullptr ? 0 : x->nbytes; }
+extern "C" const uint64_t *fsm_hip_extracted_off_device(const struct fsm_hip_extracted *x) { return x == nullptr ? nullptr : x->d_off.p; }
+extern "C" const unsigned char *fsm_hip_extracted_bytes_device(const struct fsm_hip_extracted *x) { return x == nullptr ? nullptr : x->d_bytes.p; }
+extern "C" const uint64_t *fsm_hip_extracted_line_device(const struct fsm_hip_extracted *x) { return x == nullptr ? nullptr : x->d_line.p; }
+extern "C" const uint64_t *fsm_hip_extracted_match_device(const struct fsm_hip_extracted *x) { return x == nullptr ? nullptr : x->d_match.p; }
+
+extern "C" int fsm_hip_extracted_copy(const struct fsm_hip_extracted *x, uint64_t *off, void *bytes, uint64_t *line, uint64_t *match)
+{
+	if (x == nullptr) { errno = EINVAL; return -1; }
+	return copy_out(x->device, x->done(), {{off, x->d_off, (x->nrec + 1u) * sizeof(uint64_t)}, {bytes, x->d_bytes, (size_t)x->nbytes},
+	                                       {line, x->d_line, x->nrec * sizeof(uint64_t)}, {match, x->d_match, x->nrec * sizeof(uint64_t)}});
+}
+
+extern "C" double fsm_hip_extracted_ms(const struct fsm_hip_extracted *x) { return run_ms(x, 0, 3); }
+extern "C" double fsm_hip_extracted_pass_ms(const struct fsm_hip_extracted *x, int pass) { return run_ms(x, pass, pass); }

@@ -25,14 +25,36 @@
 
 #include <cerrno>
 #include <cstdint>
+#include <optional>
 
 #include "../../include/fsm_hip.h"
-#include "hip_host.h"
+#include "front.h"
 #include "image.h"
 #include "match.h"
 #include "match_marks.h"
 #include "span.h"
+#include "text_objects.h"
 #include "tok.h"
+
+namespace fsmhip {
+
+constexpr uint32_t MATCH_THREADS = 256;      /* inputs per workgroup, one per lane */
+
+/* m inputs fit one launch's grid */
+static bool match_grid_fits(uint64_t m) { return (m + MATCH_THREADS - 1u) / MATCH_THREADS <= 0x7fffffffu; }
+
+/* one pass over m inputs; every pointer is device memory */
+struct MatchRun {
+	LineBatch in;                            /* its limit always given (the marks are sized by it); flags: FSM_HIP_MATCHES_* */
+	uint16_t *marks = nullptr;               /* marks_words(limit, n) words (match_marks.h): walk_mark writes, walk_match reads */
+	uint64_t nwords = 0;
+	uint64_t *count = nullptr;               /* the count pass writes it: m */
+	const uint64_t *match_off = nullptr;     /* the emit pass reads it: m + 1 */
+	uint64_t *start_out = nullptr, *end_out = nullptr;   /* ... and stores at match_off[j] + t */
+	uint32_t *id_out = nullptr;
+};
+
+}
 
 using namespace fsmhip;
 
@@ -379,7 +401,8 @@ MatchArgs args_of(const MatchRun &r)
 
 namespace fsmhip {
 
-int match_launch_mark(const fsm_hip_pos_dfa *starts, const MatchRun &r, hipStream_t s)
+/* walk_mark on stream s, the image's device current; 0, or -1 + errno */
+static int match_launch_mark(const fsm_hip_pos_dfa *starts, const MatchRun &r, hipStream_t s)
 {
 	if (r.in.m == 0) return 0;
 	if (!match_grid_fits(r.in.m)) { errno = ENOMEM; return -1; }
@@ -398,7 +421,8 @@ int match_launch_mark(const fsm_hip_pos_dfa *starts, const MatchRun &r, hipStrea
 	return HIP_OK(hipGetLastError()) ? 0 : -1;
 }
 
-int match_launch(const fsm_hip_tok_dfa *ends, const MatchRun &r, bool emit, hipStream_t s)
+/* walk_match<emit> */
+static int match_launch(const fsm_hip_tok_dfa *ends, const MatchRun &r, bool emit, hipStream_t s)
 {
 	if (r.in.m == 0) return 0;
 	if (!match_grid_fits(r.in.m)) { errno = ENOMEM; return -1; }
@@ -420,3 +444,104 @@ int match_launch(const fsm_hip_tok_dfa *ends, const MatchRun &r, bool emit, hipS
 }
 
 }   // namespace fsmhip
+
+/* ---- the matches object (match.h): marks pass -> count pass -> scan -> ONE wait for the total -> allocation -> emit pass --------- */
+extern "C" void fsm_hip_matches_free(struct fsm_hip_matches *mt) { run_free(mt); }
+
+/* the passes on stream s into *mt, the images' device current; r: the inputs, their limit given (its outputs are set here) */
+static int matches_passes(struct fsm_hip_matches *mt, const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, fsmhip::MatchRun r,
+	hipStream_t s)
+{
+	const uint64_t m = r.in.m;
+	uint64_t total = 0;
+	if (!HIP_OK(mt->d_off.alloc(m + 1u))) return -1;
+	r.nwords = fsmhip::marks_words(r.in.limit, r.in.n);
+	if (m != 0 && !HIP_OK(mt->d_marks.alloc(r.nwords))) return -1;
+	r.marks = mt->d_marks;
+	r.count = mt->d_off;
+	if (!mt->begin(0, s)) return -1;
+	if (m != 0 && fsmhip::match_launch_mark(starts, r, s) != 0) return -1;
+	if (!mt->end(0, s) || !mt->begin(1, s)) return -1;
+	if (m != 0 && fsmhip::match_launch(ends, r, false, s) != 0) return -1;
+	if (!mt->end(1, s) || !mt->begin(2, s)) return -1;
+	if (scan_total(mt->d_off, m, mt->ev[5], s, &total) != 0) return -1;   /* the total sizes the arrays */
+	mt->total = (size_t)total;
+	if (total != 0 && (!HIP_OK(mt->d_start.alloc(total)) || !HIP_OK(mt->d_end.alloc(total)) || !HIP_OK(mt->d_id.alloc(total)))) return -1;
+	if (!mt->begin(3, s)) return -1;
+	if (total != 0) {
+		r.match_off = mt->d_off;
+		r.start_out = mt->d_start;
+		r.end_out = mt->d_end;
+		r.id_out = mt->d_id;
+		if (fsmhip::match_launch(ends, r, true, s) != 0) return -1;
+	}
+	return mt->end(3, s) ? 0 : -1;
+}
+
+static struct fsm_hip_matches *matches_new(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, const fsmhip::LineBatch &in,
+	hipStream_t s)
+{
+	fsmhip::MatchRun r;
+	r.in = in;
+	return run_new<struct fsm_hip_matches>(fsmhip::tok_dfa_device(ends), in.m, fsmhip::match_grid_fits(in.m), s,
+	                                       [&](struct fsm_hip_matches *mt) { return matches_passes(mt, starts, ends, r, s); });
+}
+
+/* the arguments both forms refuse alike; *in: the batch as given */
+static bool matches_check(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, const struct fsm_hip_match_batch *b,
+	fsmhip::LineBatch *in)
+{
+	if (!have_device()) { errno = ENODEV; return false; }
+	if (starts == nullptr || ends == nullptr || fsmhip::pos_dfa_device(starts) != fsmhip::tok_dfa_device(ends)) { errno = EINVAL; return false; }
+	return fsmhip::batch_shape(b, FSM_HIP_MATCHES_DROP_EMPTY, in);
+}
+
+extern "C" struct fsm_hip_matches *fsm_hip_matches_run_device(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
+	const struct fsm_hip_match_batch *b, void *hip_stream)
+{
+	fsmhip::LineBatch in;
+	if (!matches_check(starts, ends, b, &in) || !fsmhip::batch_device_ok(in)) return nullptr;
+	DevGuard dg(fsmhip::tok_dfa_device(ends));
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	if (!fsmhip::batch_read_limit(&in, s)) return nullptr;   /* the marks are sized by the limit */
+	return matches_new(starts, ends, in, s);
+}
+
+extern "C" struct fsm_hip_matches *fsm_hip_matches_run(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
+	const struct fsm_hip_match_batch *b)
+{
+	fsmhip::LineBatch host;
+	if (!matches_check(starts, ends, b, &host) || !fsmhip::batch_host_arrays_ok(host)) return nullptr;
+	return run_host(fsmhip::tok_dfa_device(ends), host, [&](const fsmhip::LineBatch &in, hipStream_t s) { return matches_new(starts, ends, in, s); });
+}
+
+extern "C" struct fsm_hip_matches *fsm_hip_text_matches(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
+	const struct fsm_hip_text *t, const struct fsm_hip_text_hits *h, unsigned flags, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (starts == nullptr || ends == nullptr || t == nullptr || (flags & ~FSM_HIP_MATCHES_DROP_EMPTY) != 0u) { errno = EINVAL; return nullptr; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	std::optional<DevGuard> dg;
+	fsmhip::LineBatch in;
+	if (!text_batch(t, h, {fsmhip::pos_dfa_device(starts), fsmhip::tok_dfa_device(ends)}, s, &dg, &in)) return nullptr;
+	in.flags = flags;
+	return matches_new(starts, ends, in, s);
+}
+
+extern "C" size_t fsm_hip_matches_count(const struct fsm_hip_matches *mt) { return mt == nullptr ? 0 : mt->m; }
+extern "C" size_t fsm_hip_matches_total(const struct fsm_hip_matches *mt) { return mt == nullptr ? 0 : mt->total; }
+extern "C" const uint64_t *fsm_hip_matches_off_device(const struct fsm_hip_matches *mt) { return mt == nullptr ? nullptr : mt->d_off.p; }
+extern "C" const uint64_t *fsm_hip_matches_start_device(const struct fsm_hip_matches *mt) { return mt == nullptr ? nullptr : mt->d_start.p; }
+extern "C" const uint64_t *fsm_hip_matches_end_device(const struct fsm_hip_matches *mt) { return mt == nullptr ? nullptr : mt->d_end.p; }
+extern "C" const uint32_t *fsm_hip_matches_id_device(const struct fsm_hip_matches *mt) { return mt == nullptr ? nullptr : mt->d_id.p; }
+
+extern "C" int fsm_hip_matches_copy(const struct fsm_hip_matches *mt, uint64_t *off, uint64_t *start, uint64_t *end, uint32_t *id)
+{
+	if (mt == nullptr) { errno = EINVAL; return -1; }
+	return copy_out(mt->device, mt->done(), {{off, mt->d_off, (mt->m + 1u) * sizeof(uint64_t)}, {start, mt->d_start, mt->total * sizeof(uint64_t)},
+	                                         {end, mt->d_end, mt->total * sizeof(uint64_t)}, {id, mt->d_id, mt->total * sizeof(uint32_t)}});
+}
+
+extern "C" double fsm_hip_matches_ms(const struct fsm_hip_matches *mt) { return run_ms(mt, 0, 3); }
+extern "C" double fsm_hip_matches_pass_ms(const struct fsm_hip_matches *mt, int pass) { return run_ms(mt, pass, pass); }

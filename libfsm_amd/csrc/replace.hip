@@ -31,12 +31,76 @@
 
 #include <cerrno>
 #include <cstdint>
+#include <new>
+#include <optional>
 
 #include "../../include/fsm_hip.h"
-#include "hip_host.h"
+#include "front.h"
+#include "match.h"
 #include "match_marks.h"
-#include "replace.h"
 #include "replace_seg.h"
+#include "text_objects.h"
+
+namespace fsmhip {
+
+constexpr uint32_t REPL_THREADS = 256;
+constexpr uint32_t REPL_LINES = REPL_THREADS;               /* inputs of a block of the lengths and the offsets pass, one per lane */
+constexpr uint32_t REPL_TILES = 4;
+constexpr uint32_t REPL_TILE = REPL_THREADS * 16u;          /* output bytes one store instruction of the workgroup covers */
+constexpr uint32_t REPL_BLOCK = REPL_TILES * REPL_TILE;     /* output bytes a workgroup writes per step: 16 KiB */
+/* the table is read from LDS by the write pass when its bytes and its rules are both within these: 16 KiB + 4 KiB of a CU's
+ * 160 KiB, so eight workgroups still fit a CU */
+constexpr uint32_t REPL_LDS_BYTES = 16384;
+constexpr uint32_t REPL_LDS_RULES = 1023;
+
+static bool repl_table_fits_lds(uint64_t nrepl, uint64_t rbytes) { return nrepl <= REPL_LDS_RULES && rbytes <= REPL_LDS_BYTES; }
+/* a table with nins inserts: its insert offsets and its positions, two bytes each, take their room out of the 16 KiB of bytes, behind
+ * the table's bytes rounded up to 16 -- so every position and every insert offset fits a u16 */
+static bool repl_tmpl_fits_lds(uint64_t nrepl, uint64_t rbytes, uint64_t nins)
+{
+	return repl_table_fits_lds(nrepl, rbytes) && nins <= REPL_LDS_BYTES && ((rbytes + 15u) & ~(uint64_t)15u) + 2u * (nrepl + 1u) + 2u * nins <= REPL_LDS_BYTES;
+}
+
+/* m inputs fit one launch's grid */
+static bool repl_grid_fits(uint64_t m) { return (m + REPL_LINES - 1u) / REPL_LINES <= 0x7fffffffu; }
+
+/* the passes' arguments; every pointer is device memory.  The kernels take this struct itself, so it spells the batch's fields
+ * out where TokRun and MatchRun carry a LineBatch (line_batch.h): replaced_new copies them from one. */
+struct ReplRun {
+	/* the batch */
+	const void *base = nullptr;
+	const uint64_t *off = nullptr;           /* n + 1 */
+	const uint64_t *pick = nullptr;          /* m, or null: input j is line j */
+	uint64_t n = 0, m = 0, limit = 0;
+	/* the matches */
+	const uint64_t *moff = nullptr;          /* m + 1 */
+	const uint64_t *start = nullptr, *end = nullptr;   /* nmatch */
+	const uint32_t *id = nullptr;
+	uint64_t nmatch = 0;
+	/* the table */
+	const unsigned char *rbytes_p = nullptr;
+	const uint64_t *roff = nullptr;          /* nrepl + 1 */
+	uint64_t nrepl = 0, rbytes = 0;
+	unsigned flags = 0;                      /* FSM_HIP_REPL_* */
+	bool table_in_lds = false;
+	/* the object's arrays */
+	uint64_t *out_off = nullptr;             /* m + 1: the lengths pass leaves the lengths, the offsets pass the offsets */
+	uint64_t *mpos = nullptr, *xlen = nullptr;   /* nmatch each */
+	uint64_t *sums = nullptr;                /* blocks of REPL_LINES inputs: their bytes, then (scanned) the bytes before them */
+	uint64_t *first = nullptr;               /* ngb + 1 */
+	unsigned char *out = nullptr;            /* ngb * REPL_BLOCK */
+	uint64_t total = 0, ngb = 0;             /* known after the scan */
+	uint64_t wgs = 1, per = 1;               /* the write pass's grid: wgs workgroups of `per` consecutive output blocks */
+	/* the table's inserts (a template table with at least one): last, so that the fields above stay where the plain kernels read them */
+	const uint64_t *ioff = nullptr;          /* nrepl + 1, or null: no rule has an insert */
+	const uint64_t *ins = nullptr;           /* nins positions */
+	uint64_t nins = 0;
+};
+
+/* the table has inserts: the template kernels run, for every other table the plain ones */
+static bool repl_is_template(const ReplRun &r) { return r.nins != 0 && r.ioff != nullptr && r.ins != nullptr; }
+
+}
 
 using namespace fsmhip;
 
@@ -332,7 +396,8 @@ repl_write(const ReplRun a)
 
 namespace fsmhip {
 
-int repl_launch_lengths(const ReplRun &r, hipStream_t s)
+/* each on stream s, the objects' device current; 0, or -1 + errno */
+static int repl_launch_lengths(const ReplRun &r, hipStream_t s)
 {
 	if (r.m == 0) return 0;
 	if (!repl_grid_fits(r.m)) { errno = ENOMEM; return -1; }
@@ -342,7 +407,7 @@ int repl_launch_lengths(const ReplRun &r, hipStream_t s)
 	return HIP_OK(hipGetLastError()) ? 0 : -1;
 }
 
-int repl_launch_offsets(const ReplRun &r, hipStream_t s)
+static int repl_launch_offsets(const ReplRun &r, hipStream_t s)
 {
 	if (r.m == 0) return 0;
 	if (!repl_grid_fits(r.m)) { errno = ENOMEM; return -1; }
@@ -351,7 +416,7 @@ int repl_launch_offsets(const ReplRun &r, hipStream_t s)
 	return HIP_OK(hipGetLastError()) ? 0 : -1;
 }
 
-int repl_launch_write(const ReplRun &r, hipStream_t s)
+static int repl_launch_write(const ReplRun &r, hipStream_t s)
 {
 	if (r.m == 0 || r.total == 0 || r.ngb == 0) return 0;
 	if (r.wgs == 0 || r.wgs > 0x7fffffffu) { errno = ENOMEM; return -1; }
@@ -371,3 +436,233 @@ int repl_launch_write(const ReplRun &r, hipStream_t s)
 }
 
 }   // namespace fsmhip
+
+/* ---- the fronts: the table, and the replaced text as an object of four passes (front.h) -------------------------------------------
+ * lengths pass (per input, per match, per block of REPL_LINES inputs) -> exclusive scan of the BLOCK sums by one workgroup -> ONE
+ * wait for the total -> allocation -> offsets pass (the block's own scan redone, first[]) -> write pass.  The scan runs over
+ * m / REPL_LINES records, not over m: a text of short lines does not pay the one-workgroup scan per line that the tokens and
+ * the matches pay.  first[] has an entry per block of the output, so the offsets pass that fills it follows the wait; it and the
+ * write pass are in flight at return. */
+struct __attribute__((visibility("hidden"))) fsm_hip_repl {
+	int device = 0;
+	size_t nrepl = 0;
+	uint64_t rbytes = 0;
+	unsigned flags = 0;
+	bool in_lds = false;
+	DevBuf<unsigned char> d_bytes;           /* rbytes, rounded up to 16 and never nothing */
+	DevBuf<uint64_t> d_roff;                 /* nrepl + 1 */
+	uint64_t nins = 0;                       /* a template table's inserts; 0: a plain table, and the two arrays below are not there */
+	DevBuf<uint64_t> d_ioff;                 /* nrepl + 1 */
+	DevBuf<uint64_t> d_ins;                  /* nins */
+};
+
+/* the table on device `dev`; the arguments are checked.  nins != 0: ioff[nrepl + 1] and ins[nins] go along */
+static struct fsm_hip_repl *repl_new(int dev, const void *bytes, const uint64_t *roff, size_t nrepl, const uint64_t *ins, const uint64_t *ioff,
+	uint64_t nins, unsigned flags)
+{
+	const uint64_t rbytes = nrepl != 0 ? roff[nrepl] : 0u;
+	struct fsm_hip_repl *rp = new (std::nothrow) struct fsm_hip_repl;
+	if (rp == nullptr) { errno = ENOMEM; return nullptr; }
+	rp->device = dev;
+	rp->nrepl = nrepl;
+	rp->rbytes = rbytes;
+	rp->flags = flags;
+	rp->nins = nins;
+	rp->in_lds = nins != 0 ? fsmhip::repl_tmpl_fits_lds(nrepl, rbytes, nins) : fsmhip::repl_table_fits_lds(nrepl, rbytes);
+	const uint64_t zero = 0;
+	if (HIP_OK(rp->d_bytes.upload_bytes(bytes, (size_t)rbytes, 16)) &&
+	    HIP_OK(rp->d_roff.upload_bytes(nrepl != 0 ? roff : &zero, (nrepl + 1u) * sizeof(uint64_t), sizeof(uint64_t))) &&
+	    (nins == 0 || (HIP_OK(rp->d_ioff.upload_bytes(ioff, (nrepl + 1u) * sizeof(uint64_t), sizeof(uint64_t))) &&
+	                   HIP_OK(rp->d_ins.upload_bytes(ins, (size_t)nins * sizeof(uint64_t), sizeof(uint64_t))))))
+		return rp;
+	const int e = errno;
+	delete rp;
+	errno = e;
+	return nullptr;
+}
+
+/* what both kinds of table refuse: roff NULL with rules, roff that decreases, bytes NULL with bytes to copy */
+static bool repl_table_ok(const void *bytes, const uint64_t *roff, size_t nrepl)
+{
+	if (roff == nullptr && nrepl != 0) return false;
+	for (size_t i = 0; i < nrepl; i++)
+		if (roff[i] > roff[i + 1u]) return false;
+	return !(nrepl != 0 && roff[nrepl] != 0 && bytes == nullptr);
+}
+
+extern "C" struct fsm_hip_repl *fsm_hip_repl_create(const void *bytes, const uint64_t *roff, size_t nrepl, unsigned flags)
+{
+	int dev = 0;
+	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
+	if ((flags & ~FSM_HIP_REPL_MASK) != 0u || !repl_table_ok(bytes, roff, nrepl)) { errno = EINVAL; return nullptr; }
+	return repl_new(dev, bytes, roff, nrepl, nullptr, nullptr, 0, flags);
+}
+
+extern "C" struct fsm_hip_repl *fsm_hip_repl_create_template(const void *bytes, const uint64_t *roff, size_t nrepl, const uint64_t *ins,
+	const uint64_t *ioff, unsigned flags)
+{
+	int dev = 0;
+	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
+	if (flags != 0u || !repl_table_ok(bytes, roff, nrepl)) { errno = EINVAL; return nullptr; }
+	uint64_t nins = 0;
+	if (ioff != nullptr) {
+		if (ioff[0] != 0u) { errno = EINVAL; return nullptr; }
+		for (size_t i = 0; i < nrepl; i++) {
+			if (ioff[i] > ioff[i + 1u] || ioff[i + 1u] - ioff[i] > fsmhip::REPL_MAX_INSERTS || (ins == nullptr && ioff[i + 1u] != 0u)) { errno = EINVAL; return nullptr; }
+			const uint64_t rlen = roff[i + 1u] - roff[i];
+			for (uint64_t x = ioff[i]; x < ioff[i + 1u]; x++)
+				if (ins[x] > rlen || (x > ioff[i] && ins[x] < ins[x - 1u])) { errno = EINVAL; return nullptr; }
+		}
+		nins = ioff[nrepl];
+	}
+	return repl_new(dev, bytes, roff, nrepl, ins, ioff, nins, 0u);
+}
+
+extern "C" void fsm_hip_repl_free(struct fsm_hip_repl *rp)
+{
+	if (rp == nullptr) return;
+	const int e = errno;
+	{
+		DevGuard dg(rp->device);
+		delete rp;
+	}
+	errno = e;
+}
+
+extern "C" int fsm_hip_repl_in_lds(const struct fsm_hip_repl *rp) { return rp != nullptr && rp->in_lds ? 1 : 0; }
+extern "C" size_t fsm_hip_repl_lds_bytes(void) { return fsmhip::REPL_LDS_BYTES; }
+extern "C" size_t fsm_hip_repl_lds_rules(void) { return fsmhip::REPL_LDS_RULES; }
+extern "C" size_t fsm_hip_repl_inserts(const struct fsm_hip_repl *rp) { return rp != nullptr ? (size_t)rp->nins : 0u; }
+extern "C" size_t fsm_hip_repl_max_inserts(void) { return fsmhip::REPL_MAX_INSERTS; }
+extern "C" size_t fsm_hip_replaced_block_lines(void) { return fsmhip::REPL_LINES; }
+extern "C" size_t fsm_hip_replaced_block_bytes(void) { return fsmhip::REPL_BLOCK; }
+
+struct __attribute__((visibility("hidden"))) fsm_hip_replaced : RunObject<4> {   /* the lengths, the scan, the offsets, the write pass */
+	uint64_t nbytes = 0;
+	DevBuf<uint64_t> d_off;                  /* m + 1 */
+	DevBuf<uint64_t> d_mpos, d_xlen;         /* one per match: internal */
+	DevBuf<uint64_t> d_sums;                 /* per block of inputs, + the total: internal */
+	DevBuf<uint64_t> d_first;                /* per block of the output, + 1: internal */
+	DevBuf<unsigned char> d_bytes;           /* nbytes, in whole blocks */
+};
+
+extern "C" void fsm_hip_replaced_free(struct fsm_hip_replaced *r) { run_free(r); }
+
+/* the passes on stream s into *rd, the objects' device current; r: the batch, the matches and the table (its outputs are set here) */
+static int replaced_passes(struct fsm_hip_replaced *rd, fsmhip::ReplRun r, hipStream_t s)
+{
+	const uint64_t m = r.m, nblocks = (m + fsmhip::REPL_LINES - 1u) / fsmhip::REPL_LINES;
+	uint64_t total = 0;
+	if (!HIP_OK(rd->d_off.alloc(m + 1u))) return -1;
+	if (m != 0 && !HIP_OK(rd->d_sums.alloc(nblocks + 1u))) return -1;
+	if (m != 0 && r.nmatch != 0 && (!HIP_OK(rd->d_mpos.alloc(r.nmatch)) || !HIP_OK(rd->d_xlen.alloc(r.nmatch)))) return -1;
+	r.out_off = rd->d_off;
+	r.sums = rd->d_sums;
+	r.mpos = rd->d_mpos;
+	r.xlen = rd->d_xlen;
+	if (!rd->begin(0, s)) return -1;
+	if (fsmhip::repl_launch_lengths(r, s) != 0) return -1;
+	if (!rd->end(0, s) || !rd->begin(1, s)) return -1;
+	/* the total sizes the bytes and first[]; without inputs there are no sums, and out_off[0] is cleared */
+	if (scan_total(m != 0 ? rd->d_sums.p : rd->d_off.p, nblocks, rd->ev[3], s, &total) != 0) return -1;
+	rd->nbytes = total;
+	r.total = total;
+	r.ngb = (total + fsmhip::REPL_BLOCK - 1u) / fsmhip::REPL_BLOCK;
+	if (total != 0 && (!HIP_OK(rd->d_bytes.alloc(r.ngb * fsmhip::REPL_BLOCK)) || !HIP_OK(rd->d_first.alloc(r.ngb + 1u)))) return -1;
+	r.out = rd->d_bytes;
+	r.first = rd->d_first;
+	const Grid g = grid_of(r.ngb, rd->device);
+	r.wgs = g.wgs;
+	r.per = g.per;
+	if (!rd->begin(2, s)) return -1;
+	if (fsmhip::repl_launch_offsets(r, s) != 0) return -1;
+	if (!rd->end(2, s) || !rd->begin(3, s)) return -1;
+	if (fsmhip::repl_launch_write(r, s) != 0) return -1;
+	return rd->end(3, s) ? 0 : -1;
+}
+
+static struct fsm_hip_replaced *replaced_new(const struct fsm_hip_matches *mt, const struct fsm_hip_repl *rp, const fsmhip::LineBatch &in, hipStream_t s)
+{
+	fsmhip::ReplRun r;
+	r.base = in.base;
+	r.off = in.off;
+	r.pick = in.pick;
+	r.n = in.n;
+	r.m = in.m;
+	r.limit = in.limit;
+	r.moff = mt->d_off;
+	r.start = mt->d_start;
+	r.end = mt->d_end;
+	r.id = mt->d_id;
+	r.nmatch = mt->total;
+	r.rbytes_p = rp->d_bytes;
+	r.roff = rp->d_roff;
+	r.nrepl = rp->nrepl;
+	r.rbytes = rp->rbytes;
+	r.flags = rp->flags;
+	r.table_in_lds = rp->in_lds;
+	if (rp->nins != 0) {
+		r.ioff = rp->d_ioff;
+		r.ins = rp->d_ins;
+		r.nins = rp->nins;
+	}
+	return run_new<struct fsm_hip_replaced>(mt->device, in.m, fsmhip::repl_grid_fits(in.m), s, [&](struct fsm_hip_replaced *rd) {
+		return HIP_OK(hipStreamWaitEvent(s, mt->done(), 0)) ? replaced_passes(rd, r, s) : -1;   /* behind the matches' emit pass */
+	});
+}
+
+/* the arguments both forms refuse alike; *in: the batch as given, which is the matches' own: it passes what theirs passed */
+static bool replaced_check(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b, const struct fsm_hip_repl *rp, fsmhip::LineBatch *in)
+{
+	if (!have_device()) { errno = ENODEV; return false; }
+	if (mt == nullptr || rp == nullptr || rp->device != mt->device) { errno = EINVAL; return false; }
+	if (!fsmhip::batch_shape(b, FSM_HIP_MATCHES_DROP_EMPTY, in)) return false;
+	if (in->m != (uint64_t)mt->m) { errno = EINVAL; return false; }
+	return true;
+}
+
+extern "C" struct fsm_hip_replaced *fsm_hip_matches_replace_device(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b,
+	const struct fsm_hip_repl *rp, void *hip_stream)
+{
+	fsmhip::LineBatch in;
+	if (!replaced_check(mt, b, rp, &in) || !fsmhip::batch_device_ok(in)) return nullptr;
+	DevGuard dg(mt->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	if (!fsmhip::batch_read_limit(&in, s)) return nullptr;   /* as the matches: line extents are clamped to the limit */
+	return replaced_new(mt, rp, in, s);
+}
+
+extern "C" struct fsm_hip_replaced *fsm_hip_matches_replace(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b,
+	const struct fsm_hip_repl *rp)
+{
+	fsmhip::LineBatch host;
+	if (!replaced_check(mt, b, rp, &host) || !fsmhip::batch_host_arrays_ok(host)) return nullptr;
+	return run_host(mt->device, host, [&](const fsmhip::LineBatch &in, hipStream_t s) { return replaced_new(mt, rp, in, s); });
+}
+
+extern "C" struct fsm_hip_replaced *fsm_hip_text_replace(const struct fsm_hip_matches *mt, const struct fsm_hip_text *t,
+	const struct fsm_hip_text_hits *h, const struct fsm_hip_repl *rp, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (mt == nullptr || t == nullptr || rp == nullptr || mt->m != (h != nullptr ? h->m : t->n)) { errno = EINVAL; return nullptr; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	std::optional<DevGuard> dg;
+	fsmhip::LineBatch in;
+	if (!text_batch(t, h, {mt->device, rp->device}, s, &dg, &in)) return nullptr;
+	return replaced_new(mt, rp, in, s);
+}
+
+extern "C" size_t fsm_hip_replaced_count(const struct fsm_hip_replaced *r) { return r == nullptr ? 0 : r->m; }
+extern "C" uint64_t fsm_hip_replaced_nbytes(const struct fsm_hip_replaced *r) { return r == nullptr ? 0 : r->nbytes; }
+extern "C" const uint64_t *fsm_hip_replaced_off_device(const struct fsm_hip_replaced *r) { return r == nullptr ? nullptr : r->d_off.p; }
+extern "C" const unsigned char *fsm_hip_replaced_bytes_device(const struct fsm_hip_replaced *r) { return r == nullptr ? nullptr : r->d_bytes.p; }
+
+extern "C" int fsm_hip_replaced_copy(const struct fsm_hip_replaced *r, uint64_t *off, void *bytes)
+{
+	if (r == nullptr) { errno = EINVAL; return -1; }
+	return copy_out(r->device, r->done(), {{off, r->d_off, (r->m + 1u) * sizeof(uint64_t)}, {bytes, r->d_bytes, (size_t)r->nbytes}});
+}
+
+extern "C" double fsm_hip_replaced_ms(const struct fsm_hip_replaced *r) { return run_ms(r, 0, 3); }
+extern "C" double fsm_hip_replaced_pass_ms(const struct fsm_hip_replaced *r, int pass) { return run_ms(r, pass, pass); }

@@ -33,9 +33,35 @@
 #include <cerrno>
 #include <cstdint>
 
-#include "hip_host.h"
-#include "tally.h"
+#include "../../include/fsm_hip.h"
+#include "front.h"
+#include "match.h"
 #include "tally_seg.h"
+#include "text_objects.h"
+#include "tok.h"
+
+namespace fsmhip {
+
+constexpr uint32_t TALLY_THREADS = 256;
+constexpr uint32_t TALLY_WINDOW = TALLY_THREADS;            /* entries a workgroup takes a step, one per lane */
+constexpr uint32_t TALLY_SPAN = 64;                         /* inputs of a granule: a workgroup takes whole granules */
+constexpr uint32_t TALLY_LDS_COLS = 4096;                   /* columns counted in LDS: 2 x 16 KiB of u32, count and lines */
+constexpr uint32_t TALLY_LINE_COLS = 65536;                 /* columns of the bitmap of one input: 8 KiB of LDS */
+constexpr uint32_t TALLY_WG_PER_CU = 3;                     /* 47 KiB of LDS a workgroup: three fit a CU's 160 KiB */
+
+/* the kernel's arguments; every pointer is device memory.  count or lines may be null, not both; group_off null: one group. */
+struct TallyRun {
+	const uint64_t *off = nullptr;           /* m + 1 */
+	const uint32_t *id = nullptr;            /* total */
+	uint64_t m = 0, total = 0;
+	const uint64_t *group_off = nullptr;     /* ngroups + 1, or null */
+	uint64_t ngroups = 1;
+	uint64_t nrules = 0;                     /* nrules + 1 columns */
+	uint64_t *count = nullptr, *lines = nullptr;   /* ngroups * (nrules + 1) each */
+	uint64_t per = 1;                        /* granules of a workgroup; set by the launch */
+};
+
+}
 
 using namespace fsmhip;
 
@@ -209,7 +235,8 @@ tally_spans(const TallyRun a)
 
 namespace fsmhip {
 
-int tally_launch(TallyRun r, int device, hipStream_t s)
+/* on stream s, `device` current; m >= 1 and total >= 1.  0, or -1 + errno */
+static int tally_launch(TallyRun r, int device, hipStream_t s)
 {
 	if (r.m == 0 || r.total == 0) return 0;
 	int ncu = 0;
@@ -224,3 +251,166 @@ int tally_launch(TallyRun r, int device, hipStream_t s)
 }
 
 }   // namespace fsmhip
+
+/* ---- the fronts ---------------------------------------------------------------------------------------------------------------
+ * Nothing is owned and nothing waits in the device forms: the tables are the caller's, cleared on the stream unless
+ * FSM_HIP_TALLY_ADD is given, then ONE launch.  The host forms stage group_off and the tables on a stream of their own and wait. */
+extern "C" size_t fsm_hip_tally_span_inputs(void) { return fsmhip::TALLY_SPAN; }
+extern "C" size_t fsm_hip_tally_window(void) { return fsmhip::TALLY_WINDOW; }
+extern "C" size_t fsm_hip_tally_lds_columns(void) { return fsmhip::TALLY_LDS_COLS; }
+extern "C" size_t fsm_hip_tally_max_line_columns(void) { return fsmhip::TALLY_LINE_COLS; }
+
+/* what every form refuses about the shape alike, behind ENODEV and the form's own EINVALs; *cells = G * C */
+static bool tally_shape(const void *group_off, size_t *ngroups, size_t nrules, unsigned flags, const void *count, const void *lines, size_t *cells)
+{
+	if ((count == nullptr && lines == nullptr) || (flags & ~FSM_HIP_TALLY_ADD) != 0u || (group_off != nullptr && *ngroups == 0)) { errno = EINVAL; return false; }
+	if (group_off == nullptr) *ngroups = 1;
+	if (nrules == SIZE_MAX || *ngroups > SIZE_MAX / sizeof(uint64_t) / (nrules + 1u)) { errno = EOVERFLOW; return false; }
+	if (lines != nullptr && nrules + 1u > fsmhip::TALLY_LINE_COLS) { errno = ENOTSUP; return false; }
+	*cells = *ngroups * (nrules + 1u);
+	return true;
+}
+
+/* the reduction on stream s, `device` current, behind tally_shape: the tables cleared unless they are added to, then the launch */
+static int tally_run(int device, const uint64_t *d_off, const uint32_t *d_id, size_t m, size_t total, const uint64_t *d_group_off, size_t ngroups,
+	size_t nrules, unsigned flags, uint64_t *d_count, uint64_t *d_lines, size_t cells, hipStream_t s)
+{
+	if ((flags & FSM_HIP_TALLY_ADD) == 0u)
+		for (uint64_t *tab : {d_count, d_lines})
+			if (tab != nullptr && !HIP_OK(hipMemsetAsync(tab, 0, cells * sizeof(uint64_t), s))) return -1;
+	fsmhip::TallyRun r;
+	r.off = d_off;
+	r.id = d_id;
+	r.m = m;
+	r.total = total;
+	r.group_off = d_group_off;
+	r.ngroups = ngroups;
+	r.nrules = nrules;
+	r.count = d_count;
+	r.lines = d_lines;
+	return fsmhip::tally_launch(r, device, s);
+}
+
+extern "C" int fsm_hip_tally_ids_device(const uint64_t *d_off, const uint32_t *d_id, size_t m, size_t total, const uint64_t *d_group_off,
+	size_t ngroups, size_t nrules, unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream)
+{
+	int dev = 0;
+	size_t cells = 0;
+	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return -1; }
+	if ((d_off == nullptr && m != 0) || (d_id == nullptr && m != 0 && total != 0)) { errno = EINVAL; return -1; }
+	if (!tally_shape(d_group_off, &ngroups, nrules, flags, d_count, d_lines, &cells)) return -1;
+	return tally_run(dev, d_off, d_id, m, total, d_group_off, ngroups, nrules, flags, d_count, d_lines, cells, static_cast<hipStream_t>(hip_stream));
+}
+
+/* the device form of an object's own arrays (a matches or a tokens object: both have device, m, total, d_off, d_id, done()) */
+template <typename T>
+static int tally_object_device(const T *o, const uint64_t *d_group_off, size_t ngroups, size_t nrules, unsigned flags, uint64_t *d_count,
+	uint64_t *d_lines, void *hip_stream)
+{
+	size_t cells = 0;
+	if (!have_device()) { errno = ENODEV; return -1; }
+	if (o == nullptr) { errno = EINVAL; return -1; }
+	if (!tally_shape(d_group_off, &ngroups, nrules, flags, d_count, d_lines, &cells)) return -1;
+	DevGuard dg(o->device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	if (!HIP_OK(hipStreamWaitEvent(s, o->done(), 0))) return -1;      /* behind the object's emit pass */
+	return tally_run(o->device, o->d_off, o->d_id, o->m, o->total, d_group_off, ngroups, nrules, flags, d_count, d_lines, cells, s);
+}
+
+/* the host form: group_off checked and staged, the tables made on the device (uploaded when they are added to), the device form
+ * on a stream of its own, the tables read back, ONE wait */
+template <typename T>
+static int tally_object_host(const T *o, const uint64_t *group_off, size_t ngroups, size_t nrules, unsigned flags, uint64_t *count, uint64_t *lines)
+{
+	size_t cells = 0;
+	if (!have_device()) { errno = ENODEV; return -1; }
+	if (o == nullptr) { errno = EINVAL; return -1; }
+	if (!tally_shape(group_off, &ngroups, nrules, flags, count, lines, &cells)) return -1;
+	if (group_off != nullptr) {
+		for (size_t g = 0; g < ngroups; g++)
+			if (group_off[g] > group_off[g + 1u]) { errno = EINVAL; return -1; }
+		if (group_off[ngroups] > o->m) { errno = EINVAL; return -1; }
+	}
+	DevGuard dg(o->device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
+	DevStream own;
+	if (!HIP_OK(own.create(hipStreamNonBlocking))) return -1;
+	DevBuf<uint64_t> d_goff, d_tab[2];
+	uint64_t *host[2] = {count, lines};
+	int rc = 0;
+	if (group_off != nullptr && (!HIP_OK(d_goff.alloc(ngroups + 1u)) ||
+	                             !HIP_OK(hipMemcpyAsync(d_goff.p, group_off, (ngroups + 1u) * sizeof(uint64_t), hipMemcpyHostToDevice, own))))
+		rc = -1;
+	for (int i = 0; i < 2 && rc == 0; i++) {
+		if (host[i] == nullptr) continue;
+		if (!HIP_OK(d_tab[i].alloc(cells))) rc = -1;
+		else if ((flags & FSM_HIP_TALLY_ADD) != 0u && !HIP_OK(hipMemcpyAsync(d_tab[i].p, host[i], cells * sizeof(uint64_t), hipMemcpyHostToDevice, own))) rc = -1;
+	}
+	if (rc == 0 && !HIP_OK(hipStreamWaitEvent(own, o->done(), 0))) rc = -1;
+	if (rc == 0) rc = tally_run(o->device, o->d_off, o->d_id, o->m, o->total, d_goff.p, ngroups, nrules, flags, d_tab[0].p, d_tab[1].p, cells, own);
+	for (int i = 0; i < 2 && rc == 0; i++)
+		if (host[i] != nullptr && !HIP_OK(hipMemcpyAsync(host[i], d_tab[i].p, cells * sizeof(uint64_t), hipMemcpyDeviceToHost, own))) rc = -1;
+	const int e = errno;
+	const bool idle = HIP_OK(hipStreamSynchronize(own));                /* also when a step failed: the staged arrays go at return */
+	if (rc != 0) { errno = e; return -1; }
+	return idle ? 0 : -1;
+}
+
+/* the text form: the groups are the text's files -- file_lines, or the hits' file_first -- and a plain text is one group */
+template <typename T>
+static int tally_object_text(const T *o, const struct fsm_hip_text *t, const struct fsm_hip_text_hits *h, size_t nrules, unsigned flags,
+	uint64_t *d_count, uint64_t *d_lines, void *hip_stream)
+{
+	size_t cells = 0;
+	if (!have_device()) { errno = ENODEV; return -1; }
+	if (o == nullptr || t == nullptr || o->m != (h != nullptr ? h->m : t->n) || o->device != t->device || (h != nullptr && h->device != t->device)) {
+		errno = EINVAL;
+		return -1;
+	}
+	const uint64_t *d_goff = t->nfiles == 0 ? nullptr : h != nullptr ? h->d_file_first.p : t->d_file_lines.p;
+	size_t ngroups = t->nfiles;
+	if (t->nfiles != 0 && d_goff == nullptr) { errno = EINVAL; return -1; }   /* hits of another, plain text */
+	if (!tally_shape(d_goff, &ngroups, nrules, flags, d_count, d_lines, &cells)) return -1;
+	DevGuard dg(t->device);
+	if (!dg.ok()) { errno = ENODEV; return -1; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	if (!HIP_OK(hipStreamWaitEvent(s, h != nullptr ? h->ev[5] : t->ev[3], 0)) || !HIP_OK(hipStreamWaitEvent(s, o->done(), 0))) return -1;
+	return tally_run(o->device, o->d_off, o->d_id, o->m, o->total, d_goff, ngroups, nrules, flags, d_count, d_lines, cells, s);
+}
+
+extern "C" int fsm_hip_matches_tally_device(const struct fsm_hip_matches *mt, const uint64_t *d_group_off, size_t ngroups, size_t nrules,
+	unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream)
+{
+	return tally_object_device(mt, d_group_off, ngroups, nrules, flags, d_count, d_lines, hip_stream);
+}
+
+extern "C" int fsm_hip_tokens_tally_device(const struct fsm_hip_tokens *tk, const uint64_t *d_group_off, size_t ngroups, size_t nrules,
+	unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream)
+{
+	return tally_object_device(tk, d_group_off, ngroups, nrules, flags, d_count, d_lines, hip_stream);
+}
+
+extern "C" int fsm_hip_matches_tally(const struct fsm_hip_matches *mt, const uint64_t *group_off, size_t ngroups, size_t nrules, unsigned flags,
+	uint64_t *count, uint64_t *lines)
+{
+	return tally_object_host(mt, group_off, ngroups, nrules, flags, count, lines);
+}
+
+extern "C" int fsm_hip_tokens_tally(const struct fsm_hip_tokens *tk, const uint64_t *group_off, size_t ngroups, size_t nrules, unsigned flags,
+	uint64_t *count, uint64_t *lines)
+{
+	return tally_object_host(tk, group_off, ngroups, nrules, flags, count, lines);
+}
+
+extern "C" int fsm_hip_text_matches_tally(const struct fsm_hip_matches *mt, const struct fsm_hip_text *t, const struct fsm_hip_text_hits *hits,
+	size_t nrules, unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream)
+{
+	return tally_object_text(mt, t, hits, nrules, flags, d_count, d_lines, hip_stream);
+}
+
+extern "C" int fsm_hip_text_tokens_tally(const struct fsm_hip_tokens *tk, const struct fsm_hip_text *t, const struct fsm_hip_text_hits *hits,
+	size_t nrules, unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream)
+{
+	return tally_object_text(tk, t, hits, nrules, flags, d_count, d_lines, hip_stream);
+}

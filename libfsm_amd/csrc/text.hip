@@ -18,6 +18,8 @@
  * Every global access names its address space (no FLAT instruction, as in the walk kernels: tests/test_abi.py), a lane's 16
  * bytes are loaded from the text's own first byte whatever its alignment (gfx950 takes any: tools/probes/unaligned_dma.hip), and
  * no byte outside [text, text + nbytes) is read: the last, partial block assembles its chunks from byte loads.
+ * Behind the text come its hits, their context, the files and the spans; at the end, the two scans that the objects of the other
+ * units run between their passes (front.h declares them): their kernels instantiate the sum_scan of this file.
  */
 #include <hip/hip_runtime.h>
 
@@ -25,24 +27,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <initializer_list>
 #include <new>
-#include <optional>
 #include <vector>
 
 #include "../../include/fsm_hip.h"
-#include "distinct.h"
-#include "distinct_seg.h"
-#include "extract.h"
-#include "hip_host.h"
-#include "line_batch.h"
-#include "match.h"
-#include "match_marks.h"
-#include "replace.h"
-#include "replace_seg.h"
+#include "front.h"
 #include "span.h"
-#include "tally.h"
-#include "tok.h"
+#include "text_objects.h"
 
 namespace {
 
@@ -51,7 +42,6 @@ constexpr uint32_t TEXT_THREADS = TEXT_WAVES * 64u;
 constexpr uint32_t TEXT_TILES = 4;                          /* 16-byte loads a lane keeps in flight */
 constexpr uint32_t TEXT_TILE = TEXT_THREADS * 16u;          /* bytes one load instruction of the workgroup covers */
 constexpr uint32_t TEXT_BLOCK = TEXT_TILES * TEXT_TILE;     /* bytes a workgroup scans per step: 16 KiB */
-constexpr uint32_t TEXT_WG_PER_CU = 8;                      /* 8 x 4 wavefronts: a full CU */
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 __attribute__((aligned(1))) u32x4_any;       /* the text starts at any byte */
@@ -287,92 +277,7 @@ text_offsets(const unsigned char *text, uint64_t nbytes, uint32_t splat, uint64_
 	}
 }
 
-bool have_device()
-{
-	int ndev = 0;
-	return hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
-}
-
-unsigned max_workgroups(int dev)
-{
-	int ncu = 0;
-	if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-	return (unsigned)ncu * TEXT_WG_PER_CU;
-}
-
-/* the grid for nblocks blocks: at most max_workgroups workgroups of `per` consecutive blocks each, none without a block (one
- * workgroup for no block: the kernels that run then do their first thread's work alone) */
-struct Grid {
-	uint64_t wgs = 1, per = 1;
-};
-Grid grid_of(uint64_t nblocks, int dev)
-{
-	Grid g;
-	if (nblocks == 0) return g;
-	g.wgs = max_workgroups(dev);
-	if (g.wgs > nblocks) g.wgs = nblocks;
-	g.per = (nblocks + g.wgs - 1u) / g.wgs;
-	g.wgs = (nblocks + g.per - 1u) / g.per;
-	return g;
-}
-
-/* wait for `done`, then copy every {dst, src, nbytes} with a dst and bytes out of the device */
-struct OutCopy {
-	void *dst;
-	const void *src;
-	size_t nbytes;
-};
-int copy_out(int device, hipEvent_t done, std::initializer_list<OutCopy> copies)
-{
-	DevGuard dg(device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	if (!HIP_OK(hipEventSynchronize(done))) return -1;
-	for (const OutCopy &c : copies)
-		if (c.dst != nullptr && c.nbytes != 0 && !HIP_OK(hipMemcpy(c.dst, c.src, c.nbytes, hipMemcpyDeviceToHost))) return -1;
-	return 0;
-}
-
-/* wait for `done`, then the milliseconds between the events of every pair, summed; -1 when it fails */
-struct EventPair {
-	hipEvent_t from, to;
-};
-double elapsed_ms(int device, hipEvent_t done, const EventPair *pairs, size_t npairs)
-{
-	double ms = 0.0;
-	DevGuard dg(device);
-	if (!dg.ok()) { errno = ENODEV; return -1.0; }
-	if (!HIP_OK(hipEventSynchronize(done))) return -1.0;
-	for (size_t k = 0; k < npairs; k++) {
-		float one = 0.f;
-		if (!HIP_OK(hipEventElapsedTime(&one, pairs[k].from, pairs[k].to))) return -1.0;
-		ms += (double)one;
-	}
-	return ms;
-}
-double elapsed_ms(int device, hipEvent_t done, std::initializer_list<EventPair> pairs) { return elapsed_ms(device, done, pairs.begin(), pairs.size()); }
-
 }   // namespace
-
-/* the types are the library's own: their destructors are no exported symbols */
-struct __attribute__((visibility("hidden"))) fsm_hip_text {
-	int device = 0, delim = 0;
-	size_t nbytes = 0, n = 0;
-	const unsigned char *d_text = nullptr;   /* the caller's bytes (open_device) or `owned` */
-	DevBuf<unsigned char> owned;
-	DevBuf<uint64_t> d_off;                  /* n + 1 */
-	DevBuf<uint64_t> d_cnt;                  /* per block: its delimiters, then their exclusive scan; + the 2 (files: 4) words of meta */
-	DevEvent ev[4];                          /* around count + scan, around offsets; ev[3]: the offsets are there */
-	/* a text of files (fsm_hip_text_open_files*): all NULL / 0 in a plain text */
-	size_t nfiles = 0;
-	const uint64_t *d_file_off = nullptr;    /* nfiles + 1: the caller's (open_files_device) or `owned_file_off` */
-	DevBuf<uint64_t> owned_file_off;
-	DevBuf<uint64_t> d_file_lines;           /* nfiles + 1 */
-	DevBuf<uint64_t> d_plain;                /* the plain offsets the merge reads; the host form frees them once its stream is idle */
-	DevBuf<uint64_t> d_frank;                /* per file end: (added ends before it in its block) << 1 | it adds one */
-	DevBuf<uint64_t> d_fpairs;               /* per block of file ends: (added ends, invalid entries), then their exclusive scan */
-	DevEvent fev[3];                         /* around mark + scan; fev[2]: the plain offsets are there, the merge runs to ev[3] */
-	DevStream own;                           /* the host-pointer forms run here, never on the NULL stream (last: it goes first) */
-};
 
 extern "C" void fsm_hip_text_free(struct fsm_hip_text *t)
 {
@@ -927,31 +832,6 @@ ctx_marks(const uint64_t *lines, uint64_t m, const uint64_t *bitmap, const uint6
 }
 
 }   // namespace
-
-struct __attribute__((visibility("hidden"))) fsm_hip_text_hits {
-	int device = 0, delim = 0;                   /* delim: the text's */
-	size_t m = 0, nbytes = 0;
-	DevBuf<uint64_t> d_pairs;                /* per block of lines: (lines, bytes) selected, then their exclusive scan; + m and the bytes */
-	DevBuf<uint64_t> d_lines;                /* m */
-	DevBuf<uint64_t> d_off;                  /* m + 1 */
-	DevBuf<uint64_t> d_src;                  /* m: where each selected line starts in the text */
-	DevBuf<uint64_t> d_first;                /* per output block + 1: the rank of the line that covers its first byte */
-	DevBuf<unsigned char> d_bytes;           /* nbytes, rounded up to whole blocks */
-	DevEvent ev[6];                          /* around count + scan, emit, gather; ev[5]: all is there */
-	size_t nfiles = 0;                       /* a text of files: its hits per file; 0 / NULL for a plain text */
-	DevBuf<uint64_t> d_file_first;           /* nfiles + 1 */
-	DevEvent fev[2];                         /* around hits_file_first, between emit and gather */
-	/* hits with context (fsm_hip_text_hits_context*): all NULL / 0 in plain hits */
-	bool context = false;
-	size_t core_count = 0;
-	DevBuf<uint64_t> d_wide;                 /* ceil(n / 64): W, the bitmap the select reads */
-	DevBuf<uint64_t> d_fmap;                 /* ceil(n / 64): F, the file starts; NULL for a plain text */
-	DevBuf<uint64_t> d_sum;                  /* per block of lines: its summary, then the carries; + the 2 words of d_cmeta */
-	uint64_t *d_cmeta = nullptr;             /* inside d_sum: (core_count, groups), counted by atomics from 0 */
-	DevBuf<uint64_t> d_core;                 /* ceil(m / 64) */
-	DevBuf<uint64_t> d_group;                /* ceil(m / 64) */
-	DevEvent cev[4];                         /* around the widening, around the marks */
-};
 
 extern "C" void fsm_hip_text_hits_free(struct fsm_hip_text_hits *h)
 {
@@ -1645,23 +1525,7 @@ extern "C" double fsm_hip_text_spans_ms(const struct fsm_hip_text_spans *sp)
 	return elapsed_ms(sp->device, sp->ev[1], {{sp->ev[0], sp->ev[1]}});
 }
 
-/* ---- what the tokens, the matches and the replacement share: the object's skeleton, the scan, the batch of a text --------------
- * Each is an object of NPASS passes on a stream with ONE wait in the middle: the passes before it leave counts, one workgroup
- * scans them, the host reads the total and sizes the arrays by it, the passes after it fill them and are in flight at return.
- * Their input is one LineBatch (line_batch.h), whichever of the three entry forms it came through. */
-
-/* what every such object begins with: events ev[2p], ev[2p + 1] around pass p; the last one: all is there */
-template <int NPASS>
-struct __attribute__((visibility("hidden"))) RunObject {
-	static constexpr int npass = NPASS;
-	int device = 0;
-	size_t m = 0;
-	DevEvent ev[2 * NPASS];
-	hipEvent_t done() const { return ev[2 * NPASS - 1]; }
-	bool begin(int pass, hipStream_t s) { return HIP_OK(hipEventRecord(ev[2 * pass], s)); }
-	bool end(int pass, hipStream_t s) { return HIP_OK(hipEventRecord(ev[2 * pass + 1], s)); }
-};
-
+/* ---- the scans between the passes of the other units' objects (front.h): counts, and pairs of words -------------------------- */
 namespace {
 
 constexpr uint32_t SCAN_PER = 4;                            /* counts a thread of the scan takes a round: 4 096 a round trip */
@@ -1672,71 +1536,14 @@ counts_scan(uint64_t *cnt, uint64_t k)
 	sum_scan<1024, 1, SCAN_PER>(cnt, k, cnt + k);
 }
 
-template <typename T>
-void run_free(T *o)
+__global__ void __launch_bounds__(1024)
+pairs_scan(uint64_t *pairs, uint64_t nblocks)
 {
-	if (o == nullptr) return;
-	const int e = errno;
-	{
-		DevGuard dg(o->device);
-		if (o->done() != nullptr) (void)hipEventSynchronize(o->done());
-		delete o;
-	}
-	errno = e;
+	sum_scan<1024, 2, SCAN_PER>(pairs, nblocks, pairs + 2u * nblocks);
 }
 
-/* the object of a run of passes(o) on stream s over m inputs, `device` current; when the run fails, the stream is made idle
- * before what it has launched on is released */
-template <typename T, typename Passes>
-T *run_new(int device, uint64_t m, bool grid_fits, hipStream_t s, Passes passes)
-{
-	if (!grid_fits) { errno = ENOMEM; return nullptr; }
-	T *o = new (std::nothrow) T;
-	if (o == nullptr) { errno = ENOMEM; return nullptr; }
-	o->device = device;
-	o->m = (size_t)m;
-	bool ok = true;
-	for (DevEvent &ev : o->ev) ok = ok && HIP_OK(ev.create());
-	if (ok && passes(o) == 0) return o;
-	const int e = errno;
-	(void)hipStreamSynchronize(s);
-	run_free(o);
-	errno = e;
-	return nullptr;
-}
+}   // namespace
 
-/* A host form behind its checks: the batch staged on a stream of its own (never the NULL stream), the object of make(batch on
- * the device, stream), and a last wait, since the stream and the staged batch go at return: the last pass has read them. */
-template <typename Make>
-auto run_host(int device, const fsmhip::LineBatch &host, Make make) -> decltype(make(host, hipStream_t()))
-{
-	DevGuard dg(device);
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
-	DevStream own;
-	if (!HIP_OK(own.create(hipStreamNonBlocking))) return nullptr;
-	fsmhip::StagedBatch staged;
-	fsmhip::LineBatch in;
-	if (!staged.stage(host, own, &in)) return nullptr;
-	auto *o = make(in, own);
-	if (o == nullptr || HIP_OK(hipStreamSynchronize(own))) return o;   /* (null: run_new left the stream idle) */
-	const int e = errno;
-	run_free(o);
-	errno = e;
-	return nullptr;
-}
-
-/* passes from .. to by the object's events, summed */
-template <typename T>
-double run_ms(const T *o, int from, int to)
-{
-	if (o == nullptr || from < 0 || to >= T::npass) { errno = EINVAL; return -1.0; }
-	EventPair pairs[T::npass];
-	for (int p = from; p <= to; p++) pairs[p - from] = {o->ev[2 * p], o->ev[2 * p + 1]};
-	return elapsed_ms(o->device, o->done(), pairs, (size_t)(to - from + 1));
-}
-
-/* The scan pass and the ONE wait of a run: cnt[0 .. k) scanned in place, exclusive, by one workgroup, the total in cnt[k] (k ==
- * 0: cnt[0] is cleared and nothing waits), `after` recorded, the total read back. */
 int scan_total(uint64_t *cnt, uint64_t k, hipEvent_t after, hipStream_t s, uint64_t *total)
 {
 	*total = 0;
@@ -1752,1075 +1559,9 @@ int scan_total(uint64_t *cnt, uint64_t k, hipEvent_t after, hipStream_t s, uint6
 	return HIP_OK(hipStreamSynchronize(s)) ? 0 : -1;
 }
 
-/* The lines of a text, or (h != null) of its hits, as a batch for a front on stream s: every object of `devices` is on the
- * text's device, which *dg makes current for the caller; the stream waits for the hits' lines (and, behind them, the text's
- * offsets).  false + errno. */
-bool text_batch(const struct fsm_hip_text *t, const struct fsm_hip_text_hits *h, std::initializer_list<int> devices, hipStream_t s,
-	std::optional<DevGuard> *dg, fsmhip::LineBatch *in)
+int pairs_scan_launch(uint64_t *pairs, uint64_t nblocks, hipStream_t s)
 {
-	for (int d : devices)
-		if (d != t->device) { errno = EINVAL; return false; }
-	if (h != nullptr && h->device != t->device) { errno = EINVAL; return false; }
-	dg->emplace(t->device);
-	if (!(*dg)->ok()) { errno = ENODEV; return false; }
-	if (!HIP_OK(hipStreamWaitEvent(s, h != nullptr ? h->ev[5] : t->ev[3], 0))) return false;
-	in->base = t->d_text;
-	in->off = t->d_off;
-	in->n = t->n;
-	in->pick = h != nullptr ? h->d_lines.p : nullptr;
-	in->m = h != nullptr ? h->m : t->n;
-	in->limit = t->nbytes;
-	in->has_limit = true;
-	in->trim = t->delim;
-	return true;
-}
-
-}   // namespace
-
-/* ---- tokens: every line cut into longest-match tokens (tok.hip, walk_tok) ------------------------------------------------
- * count pass -> exclusive scan of the counts by one workgroup -> ONE wait for the total -> allocation -> emit pass.  The counts
- * are scanned in place: d_off is count[m] first, tok_off[m + 1] afterwards (the total lands in its last entry). */
-struct __attribute__((visibility("hidden"))) fsm_hip_tokens : RunObject<3> {   /* the count pass, the scan, the emit pass */
-	size_t total = 0;
-	DevBuf<uint64_t> d_off;                  /* m + 1 */
-	DevBuf<uint64_t> d_err;                  /* m */
-	DevBuf<uint64_t> d_end;                  /* total */
-	DevBuf<uint32_t> d_id;                   /* total */
-};
-
-extern "C" void fsm_hip_tokens_free(struct fsm_hip_tokens *tk) { run_free(tk); }
-
-/* the passes on stream s into *tk, the image's device current; r: the inputs (its outputs are set here) */
-static int tokens_passes(struct fsm_hip_tokens *tk, const struct fsm_hip_tok_dfa *td, fsmhip::TokRun r, hipStream_t s)
-{
-	const uint64_t m = r.in.m;
-	uint64_t total = 0;
-	if (!HIP_OK(tk->d_off.alloc(m + 1u))) return -1;
-	if (m != 0 && !HIP_OK(tk->d_err.alloc(m))) return -1;
-	r.count = tk->d_off;
-	r.err = tk->d_err;
-	if (!tk->begin(0, s)) return -1;
-	if (m != 0 && fsmhip::tok_launch(td, r, false, s) != 0) return -1;
-	if (!tk->end(0, s) || !tk->begin(1, s)) return -1;
-	if (scan_total(tk->d_off, m, tk->ev[3], s, &total) != 0) return -1;   /* the total sizes the arrays */
-	tk->total = (size_t)total;
-	if (total != 0 && (!HIP_OK(tk->d_end.alloc(total)) || !HIP_OK(tk->d_id.alloc(total)))) return -1;
-	if (!tk->begin(2, s)) return -1;
-	if (total != 0) {
-		r.tok_off = tk->d_off;
-		r.end_out = tk->d_end;
-		r.id_out = tk->d_id;
-		if (fsmhip::tok_launch(td, r, true, s) != 0) return -1;
-	}
-	return tk->end(2, s) ? 0 : -1;
-}
-
-static struct fsm_hip_tokens *tokens_new(const struct fsm_hip_tok_dfa *td, const fsmhip::LineBatch &in, hipStream_t s)
-{
-	fsmhip::TokRun r;
-	r.in = in;
-	return run_new<struct fsm_hip_tokens>(fsmhip::tok_dfa_device(td), in.m, (in.m + fsmhip::TOK_THREADS - 1u) / fsmhip::TOK_THREADS <= 0x7fffffffu, s,
-	                                      [&](struct fsm_hip_tokens *tk) { return tokens_passes(tk, td, r, s); });
-}
-
-/* the arguments both forms refuse alike; *in: the batch as given */
-static bool tokens_check(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *b, fsmhip::LineBatch *in)
-{
-	if (!have_device()) { errno = ENODEV; return false; }
-	if (td == nullptr) { errno = EINVAL; return false; }
-	return fsmhip::batch_shape(b, FSM_HIP_TOKENS_NO_BACKTRACK | FSM_HIP_TOKENS_SKIP_BAD, in);
-}
-
-extern "C" struct fsm_hip_tokens *fsm_hip_tokens_run_device(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *b, void *hip_stream)
-{
-	fsmhip::LineBatch in;
-	if (!tokens_check(td, b, &in) || !fsmhip::batch_device_ok(in)) return nullptr;
-	DevGuard dg(fsmhip::tok_dfa_device(td));
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
-	return tokens_new(td, in, static_cast<hipStream_t>(hip_stream));
-}
-
-extern "C" struct fsm_hip_tokens *fsm_hip_tokens_run(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *b)
-{
-	fsmhip::LineBatch host;
-	if (!tokens_check(td, b, &host) || !fsmhip::batch_host_arrays_ok(host)) return nullptr;
-	return run_host(fsmhip::tok_dfa_device(td), host, [&](const fsmhip::LineBatch &in, hipStream_t s) { return tokens_new(td, in, s); });
-}
-
-extern "C" struct fsm_hip_tokens *fsm_hip_text_tokens(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_text *t, const struct fsm_hip_text_hits *h,
-	unsigned flags, void *hip_stream)
-{
-	if (!have_device()) { errno = ENODEV; return nullptr; }
-	if (td == nullptr || t == nullptr || (flags & ~(FSM_HIP_TOKENS_NO_BACKTRACK | FSM_HIP_TOKENS_SKIP_BAD)) != 0u) { errno = EINVAL; return nullptr; }
-	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	std::optional<DevGuard> dg;
-	fsmhip::LineBatch in;
-	if (!text_batch(t, h, {fsmhip::tok_dfa_device(td)}, s, &dg, &in)) return nullptr;
-	in.flags = flags;
-	return tokens_new(td, in, s);
-}
-
-extern "C" size_t fsm_hip_tokens_count(const struct fsm_hip_tokens *tk) { return tk == nullptr ? 0 : tk->m; }
-extern "C" size_t fsm_hip_tokens_total(const struct fsm_hip_tokens *tk) { return tk == nullptr ? 0 : tk->total; }
-extern "C" const uint64_t *fsm_hip_tokens_off_device(const struct fsm_hip_tokens *tk) { return tk == nullptr ? nullptr : tk->d_off.p; }
-extern "C" const uint64_t *fsm_hip_tokens_end_device(const struct fsm_hip_tokens *tk) { return tk == nullptr ? nullptr : tk->d_end.p; }
-extern "C" const uint32_t *fsm_hip_tokens_id_device(const struct fsm_hip_tokens *tk) { return tk == nullptr ? nullptr : tk->d_id.p; }
-extern "C" const uint64_t *fsm_hip_tokens_err_device(const struct fsm_hip_tokens *tk) { return tk == nullptr ? nullptr : tk->d_err.p; }
-
-extern "C" int fsm_hip_tokens_copy(const struct fsm_hip_tokens *tk, uint64_t *off, uint64_t *end, uint32_t *id, uint64_t *err)
-{
-	if (tk == nullptr) { errno = EINVAL; return -1; }
-	return copy_out(tk->device, tk->done(), {{off, tk->d_off, (tk->m + 1u) * sizeof(uint64_t)}, {end, tk->d_end, tk->total * sizeof(uint64_t)},
-	                                         {id, tk->d_id, tk->total * sizeof(uint32_t)}, {err, tk->d_err, tk->m * sizeof(uint64_t)}});
-}
-
-extern "C" double fsm_hip_tokens_ms(const struct fsm_hip_tokens *tk) { return run_ms(tk, 0, 2); }
-extern "C" double fsm_hip_tokens_pass_ms(const struct fsm_hip_tokens *tk, int pass) { return run_ms(tk, pass, pass); }
-
-/* ---- matches: every match of every line (match.hip, walk_mark / walk_match) -------------------------------------------------
- * marks pass -> count pass -> exclusive scan of the counts by one workgroup -> ONE wait for the total -> allocation -> emit
- * pass.  The counts are scanned in place, as the tokens' are: d_off is count[m] first, match_off[m + 1] afterwards. */
-struct __attribute__((visibility("hidden"))) fsm_hip_matches : RunObject<4> {   /* the marks pass, the count pass, the scan, the emit pass */
-	size_t total = 0;
-	DevBuf<uint16_t> d_marks;                /* marks_words(limit, n): internal */
-	DevBuf<uint64_t> d_off;                  /* m + 1 */
-	DevBuf<uint64_t> d_start, d_end;         /* total each */
-	DevBuf<uint32_t> d_id;                   /* total */
-};
-
-extern "C" void fsm_hip_matches_free(struct fsm_hip_matches *mt) { run_free(mt); }
-
-/* the passes on stream s into *mt, the images' device current; r: the inputs, their limit given (its outputs are set here) */
-static int matches_passes(struct fsm_hip_matches *mt, const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, fsmhip::MatchRun r,
-	hipStream_t s)
-{
-	const uint64_t m = r.in.m;
-	uint64_t total = 0;
-	if (!HIP_OK(mt->d_off.alloc(m + 1u))) return -1;
-	r.nwords = fsmhip::marks_words(r.in.limit, r.in.n);
-	if (m != 0 && !HIP_OK(mt->d_marks.alloc(r.nwords))) return -1;
-	r.marks = mt->d_marks;
-	r.count = mt->d_off;
-	if (!mt->begin(0, s)) return -1;
-	if (m != 0 && fsmhip::match_launch_mark(starts, r, s) != 0) return -1;
-	if (!mt->end(0, s) || !mt->begin(1, s)) return -1;
-	if (m != 0 && fsmhip::match_launch(ends, r, false, s) != 0) return -1;
-	if (!mt->end(1, s) || !mt->begin(2, s)) return -1;
-	if (scan_total(mt->d_off, m, mt->ev[5], s, &total) != 0) return -1;   /* the total sizes the arrays */
-	mt->total = (size_t)total;
-	if (total != 0 && (!HIP_OK(mt->d_start.alloc(total)) || !HIP_OK(mt->d_end.alloc(total)) || !HIP_OK(mt->d_id.alloc(total)))) return -1;
-	if (!mt->begin(3, s)) return -1;
-	if (total != 0) {
-		r.match_off = mt->d_off;
-		r.start_out = mt->d_start;
-		r.end_out = mt->d_end;
-		r.id_out = mt->d_id;
-		if (fsmhip::match_launch(ends, r, true, s) != 0) return -1;
-	}
-	return mt->end(3, s) ? 0 : -1;
-}
-
-static struct fsm_hip_matches *matches_new(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, const fsmhip::LineBatch &in,
-	hipStream_t s)
-{
-	fsmhip::MatchRun r;
-	r.in = in;
-	return run_new<struct fsm_hip_matches>(fsmhip::tok_dfa_device(ends), in.m, fsmhip::match_grid_fits(in.m), s,
-	                                       [&](struct fsm_hip_matches *mt) { return matches_passes(mt, starts, ends, r, s); });
-}
-
-/* the arguments both forms refuse alike; *in: the batch as given */
-static bool matches_check(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends, const struct fsm_hip_match_batch *b,
-	fsmhip::LineBatch *in)
-{
-	if (!have_device()) { errno = ENODEV; return false; }
-	if (starts == nullptr || ends == nullptr || fsmhip::pos_dfa_device(starts) != fsmhip::tok_dfa_device(ends)) { errno = EINVAL; return false; }
-	return fsmhip::batch_shape(b, FSM_HIP_MATCHES_DROP_EMPTY, in);
-}
-
-extern "C" struct fsm_hip_matches *fsm_hip_matches_run_device(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
-	const struct fsm_hip_match_batch *b, void *hip_stream)
-{
-	fsmhip::LineBatch in;
-	if (!matches_check(starts, ends, b, &in) || !fsmhip::batch_device_ok(in)) return nullptr;
-	DevGuard dg(fsmhip::tok_dfa_device(ends));
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
-	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	if (!fsmhip::batch_read_limit(&in, s)) return nullptr;   /* the marks are sized by the limit */
-	return matches_new(starts, ends, in, s);
-}
-
-extern "C" struct fsm_hip_matches *fsm_hip_matches_run(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
-	const struct fsm_hip_match_batch *b)
-{
-	fsmhip::LineBatch host;
-	if (!matches_check(starts, ends, b, &host) || !fsmhip::batch_host_arrays_ok(host)) return nullptr;
-	return run_host(fsmhip::tok_dfa_device(ends), host, [&](const fsmhip::LineBatch &in, hipStream_t s) { return matches_new(starts, ends, in, s); });
-}
-
-extern "C" struct fsm_hip_matches *fsm_hip_text_matches(const struct fsm_hip_pos_dfa *starts, const struct fsm_hip_tok_dfa *ends,
-	const struct fsm_hip_text *t, const struct fsm_hip_text_hits *h, unsigned flags, void *hip_stream)
-{
-	if (!have_device()) { errno = ENODEV; return nullptr; }
-	if (starts == nullptr || ends == nullptr || t == nullptr || (flags & ~FSM_HIP_MATCHES_DROP_EMPTY) != 0u) { errno = EINVAL; return nullptr; }
-	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	std::optional<DevGuard> dg;
-	fsmhip::LineBatch in;
-	if (!text_batch(t, h, {fsmhip::pos_dfa_device(starts), fsmhip::tok_dfa_device(ends)}, s, &dg, &in)) return nullptr;
-	in.flags = flags;
-	return matches_new(starts, ends, in, s);
-}
-
-extern "C" size_t fsm_hip_matches_count(const struct fsm_hip_matches *mt) { return mt == nullptr ? 0 : mt->m; }
-extern "C" size_t fsm_hip_matches_total(const struct fsm_hip_matches *mt) { return mt == nullptr ? 0 : mt->total; }
-extern "C" const uint64_t *fsm_hip_matches_off_device(const struct fsm_hip_matches *mt) { return mt == nullptr ? nullptr : mt->d_off.p; }
-extern "C" const uint64_t *fsm_hip_matches_start_device(const struct fsm_hip_matches *mt) { return mt == nullptr ? nullptr : mt->d_start.p; }
-extern "C" const uint64_t *fsm_hip_matches_end_device(const struct fsm_hip_matches *mt) { return mt == nullptr ? nullptr : mt->d_end.p; }
-extern "C" const uint32_t *fsm_hip_matches_id_device(const struct fsm_hip_matches *mt) { return mt == nullptr ? nullptr : mt->d_id.p; }
-
-extern "C" int fsm_hip_matches_copy(const struct fsm_hip_matches *mt, uint64_t *off, uint64_t *start, uint64_t *end, uint32_t *id)
-{
-	if (mt == nullptr) { errno = EINVAL; return -1; }
-	return copy_out(mt->device, mt->done(), {{off, mt->d_off, (mt->m + 1u) * sizeof(uint64_t)}, {start, mt->d_start, mt->total * sizeof(uint64_t)},
-	                                         {end, mt->d_end, mt->total * sizeof(uint64_t)}, {id, mt->d_id, mt->total * sizeof(uint32_t)}});
-}
-
-extern "C" double fsm_hip_matches_ms(const struct fsm_hip_matches *mt) { return run_ms(mt, 0, 3); }
-extern "C" double fsm_hip_matches_pass_ms(const struct fsm_hip_matches *mt, int pass) { return run_ms(mt, pass, pass); }
-
-/* ---- replace: every match replaced by its rule's replacement, a fresh packed text (replace.hip) --------------------------------
- * lengths pass (per input, per match, per block of REPL_LINES inputs) -> exclusive scan of the BLOCK sums by one workgroup -> ONE
- * wait for the total -> allocation -> offsets pass (the block's own scan redone, first[]) -> write pass.  The scan runs over
- * m / REPL_LINES records, not over m: a text of short lines does not pay the one-workgroup scan per line that the tokens and
- * the matches pay.  first[] has an entry per block of the output, so the offsets pass that fills it follows the wait; it and the
- * write pass are in flight at return. */
-struct __attribute__((visibility("hidden"))) fsm_hip_repl {
-	int device = 0;
-	size_t nrepl = 0;
-	uint64_t rbytes = 0;
-	unsigned flags = 0;
-	bool in_lds = false;
-	DevBuf<unsigned char> d_bytes;           /* rbytes, rounded up to 16 and never nothing */
-	DevBuf<uint64_t> d_roff;                 /* nrepl + 1 */
-	uint64_t nins = 0;                       /* a template table's inserts; 0: a plain table, and the two arrays below are not there */
-	DevBuf<uint64_t> d_ioff;                 /* nrepl + 1 */
-	DevBuf<uint64_t> d_ins;                  /* nins */
-};
-
-/* the table on device `dev`; the arguments are checked.  nins != 0: ioff[nrepl + 1] and ins[nins] go along */
-static struct fsm_hip_repl *repl_new(int dev, const void *bytes, const uint64_t *roff, size_t nrepl, const uint64_t *ins, const uint64_t *ioff,
-	uint64_t nins, unsigned flags)
-{
-	const uint64_t rbytes = nrepl != 0 ? roff[nrepl] : 0u;
-	struct fsm_hip_repl *rp = new (std::nothrow) struct fsm_hip_repl;
-	if (rp == nullptr) { errno = ENOMEM; return nullptr; }
-	rp->device = dev;
-	rp->nrepl = nrepl;
-	rp->rbytes = rbytes;
-	rp->flags = flags;
-	rp->nins = nins;
-	rp->in_lds = nins != 0 ? fsmhip::repl_tmpl_fits_lds(nrepl, rbytes, nins) : fsmhip::repl_table_fits_lds(nrepl, rbytes);
-	const uint64_t zero = 0;
-	if (HIP_OK(rp->d_bytes.upload_bytes(bytes, (size_t)rbytes, 16)) &&
-	    HIP_OK(rp->d_roff.upload_bytes(nrepl != 0 ? roff : &zero, (nrepl + 1u) * sizeof(uint64_t), sizeof(uint64_t))) &&
-	    (nins == 0 || (HIP_OK(rp->d_ioff.upload_bytes(ioff, (nrepl + 1u) * sizeof(uint64_t), sizeof(uint64_t))) &&
-	                   HIP_OK(rp->d_ins.upload_bytes(ins, (size_t)nins * sizeof(uint64_t), sizeof(uint64_t))))))
-		return rp;
-	const int e = errno;
-	delete rp;
-	errno = e;
-	return nullptr;
-}
-
-/* what both kinds of table refuse: roff NULL with rules, roff that decreases, bytes NULL with bytes to copy */
-static bool repl_table_ok(const void *bytes, const uint64_t *roff, size_t nrepl)
-{
-	if (roff == nullptr && nrepl != 0) return false;
-	for (size_t i = 0; i < nrepl; i++)
-		if (roff[i] > roff[i + 1u]) return false;
-	return !(nrepl != 0 && roff[nrepl] != 0 && bytes == nullptr);
-}
-
-extern "C" struct fsm_hip_repl *fsm_hip_repl_create(const void *bytes, const uint64_t *roff, size_t nrepl, unsigned flags)
-{
-	int dev = 0;
-	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
-	if ((flags & ~FSM_HIP_REPL_MASK) != 0u || !repl_table_ok(bytes, roff, nrepl)) { errno = EINVAL; return nullptr; }
-	return repl_new(dev, bytes, roff, nrepl, nullptr, nullptr, 0, flags);
-}
-
-extern "C" struct fsm_hip_repl *fsm_hip_repl_create_template(const void *bytes, const uint64_t *roff, size_t nrepl, const uint64_t *ins,
-	const uint64_t *ioff, unsigned flags)
-{
-	int dev = 0;
-	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
-	if (flags != 0u || !repl_table_ok(bytes, roff, nrepl)) { errno = EINVAL; return nullptr; }
-	uint64_t nins = 0;
-	if (ioff != nullptr) {
-		if (ioff[0] != 0u) { errno = EINVAL; return nullptr; }
-		for (size_t i = 0; i < nrepl; i++) {
-			if (ioff[i] > ioff[i + 1u] || ioff[i + 1u] - ioff[i] > fsmhip::REPL_MAX_INSERTS || (ins == nullptr && ioff[i + 1u] != 0u)) { errno = EINVAL; return nullptr; }
-			const uint64_t rlen = roff[i + 1u] - roff[i];
-			for (uint64_t x = ioff[i]; x < ioff[i + 1u]; x++)
-				if (ins[x] > rlen || (x > ioff[i] && ins[x] < ins[x - 1u])) { errno = EINVAL; return nullptr; }
-		}
-		nins = ioff[nrepl];
-	}
-	return repl_new(dev, bytes, roff, nrepl, ins, ioff, nins, 0u);
-}
-
-extern "C" void fsm_hip_repl_free(struct fsm_hip_repl *rp)
-{
-	if (rp == nullptr) return;
-	const int e = errno;
-	{
-		DevGuard dg(rp->device);
-		delete rp;
-	}
-	errno = e;
-}
-
-extern "C" int fsm_hip_repl_in_lds(const struct fsm_hip_repl *rp) { return rp != nullptr && rp->in_lds ? 1 : 0; }
-extern "C" size_t fsm_hip_repl_lds_bytes(void) { return fsmhip::REPL_LDS_BYTES; }
-extern "C" size_t fsm_hip_repl_lds_rules(void) { return fsmhip::REPL_LDS_RULES; }
-extern "C" size_t fsm_hip_repl_inserts(const struct fsm_hip_repl *rp) { return rp != nullptr ? (size_t)rp->nins : 0u; }
-extern "C" size_t fsm_hip_repl_max_inserts(void) { return fsmhip::REPL_MAX_INSERTS; }
-extern "C" size_t fsm_hip_replaced_block_lines(void) { return fsmhip::REPL_LINES; }
-extern "C" size_t fsm_hip_replaced_block_bytes(void) { return fsmhip::REPL_BLOCK; }
-
-struct __attribute__((visibility("hidden"))) fsm_hip_replaced : RunObject<4> {   /* the lengths, the scan, the offsets, the write pass */
-	uint64_t nbytes = 0;
-	DevBuf<uint64_t> d_off;                  /* m + 1 */
-	DevBuf<uint64_t> d_mpos, d_xlen;         /* one per match: internal */
-	DevBuf<uint64_t> d_sums;                 /* per block of inputs, + the total: internal */
-	DevBuf<uint64_t> d_first;                /* per block of the output, + 1: internal */
-	DevBuf<unsigned char> d_bytes;           /* nbytes, in whole blocks */
-};
-
-extern "C" void fsm_hip_replaced_free(struct fsm_hip_replaced *r) { run_free(r); }
-
-/* the passes on stream s into *rd, the objects' device current; r: the batch, the matches and the table (its outputs are set here) */
-static int replaced_passes(struct fsm_hip_replaced *rd, fsmhip::ReplRun r, hipStream_t s)
-{
-	const uint64_t m = r.m, nblocks = (m + fsmhip::REPL_LINES - 1u) / fsmhip::REPL_LINES;
-	uint64_t total = 0;
-	if (!HIP_OK(rd->d_off.alloc(m + 1u))) return -1;
-	if (m != 0 && !HIP_OK(rd->d_sums.alloc(nblocks + 1u))) return -1;
-	if (m != 0 && r.nmatch != 0 && (!HIP_OK(rd->d_mpos.alloc(r.nmatch)) || !HIP_OK(rd->d_xlen.alloc(r.nmatch)))) return -1;
-	r.out_off = rd->d_off;
-	r.sums = rd->d_sums;
-	r.mpos = rd->d_mpos;
-	r.xlen = rd->d_xlen;
-	if (!rd->begin(0, s)) return -1;
-	if (fsmhip::repl_launch_lengths(r, s) != 0) return -1;
-	if (!rd->end(0, s) || !rd->begin(1, s)) return -1;
-	/* the total sizes the bytes and first[]; without inputs there are no sums, and out_off[0] is cleared */
-	if (scan_total(m != 0 ? rd->d_sums.p : rd->d_off.p, nblocks, rd->ev[3], s, &total) != 0) return -1;
-	rd->nbytes = total;
-	r.total = total;
-	r.ngb = (total + fsmhip::REPL_BLOCK - 1u) / fsmhip::REPL_BLOCK;
-	if (total != 0 && (!HIP_OK(rd->d_bytes.alloc(r.ngb * fsmhip::REPL_BLOCK)) || !HIP_OK(rd->d_first.alloc(r.ngb + 1u)))) return -1;
-	r.out = rd->d_bytes;
-	r.first = rd->d_first;
-	const Grid g = grid_of(r.ngb, rd->device);
-	r.wgs = g.wgs;
-	r.per = g.per;
-	if (!rd->begin(2, s)) return -1;
-	if (fsmhip::repl_launch_offsets(r, s) != 0) return -1;
-	if (!rd->end(2, s) || !rd->begin(3, s)) return -1;
-	if (fsmhip::repl_launch_write(r, s) != 0) return -1;
-	return rd->end(3, s) ? 0 : -1;
-}
-
-static struct fsm_hip_replaced *replaced_new(const struct fsm_hip_matches *mt, const struct fsm_hip_repl *rp, const fsmhip::LineBatch &in, hipStream_t s)
-{
-	fsmhip::ReplRun r;
-	r.base = in.base;
-	r.off = in.off;
-	r.pick = in.pick;
-	r.n = in.n;
-	r.m = in.m;
-	r.limit = in.limit;
-	r.moff = mt->d_off;
-	r.start = mt->d_start;
-	r.end = mt->d_end;
-	r.id = mt->d_id;
-	r.nmatch = mt->total;
-	r.rbytes_p = rp->d_bytes;
-	r.roff = rp->d_roff;
-	r.nrepl = rp->nrepl;
-	r.rbytes = rp->rbytes;
-	r.flags = rp->flags;
-	r.table_in_lds = rp->in_lds;
-	if (rp->nins != 0) {
-		r.ioff = rp->d_ioff;
-		r.ins = rp->d_ins;
-		r.nins = rp->nins;
-	}
-	return run_new<struct fsm_hip_replaced>(mt->device, in.m, fsmhip::repl_grid_fits(in.m), s, [&](struct fsm_hip_replaced *rd) {
-		return HIP_OK(hipStreamWaitEvent(s, mt->done(), 0)) ? replaced_passes(rd, r, s) : -1;   /* behind the matches' emit pass */
-	});
-}
-
-/* the arguments both forms refuse alike; *in: the batch as given, which is the matches' own: it passes what theirs passed */
-static bool replaced_check(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b, const struct fsm_hip_repl *rp, fsmhip::LineBatch *in)
-{
-	if (!have_device()) { errno = ENODEV; return false; }
-	if (mt == nullptr || rp == nullptr || rp->device != mt->device) { errno = EINVAL; return false; }
-	if (!fsmhip::batch_shape(b, FSM_HIP_MATCHES_DROP_EMPTY, in)) return false;
-	if (in->m != (uint64_t)mt->m) { errno = EINVAL; return false; }
-	return true;
-}
-
-extern "C" struct fsm_hip_replaced *fsm_hip_matches_replace_device(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b,
-	const struct fsm_hip_repl *rp, void *hip_stream)
-{
-	fsmhip::LineBatch in;
-	if (!replaced_check(mt, b, rp, &in) || !fsmhip::batch_device_ok(in)) return nullptr;
-	DevGuard dg(mt->device);
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
-	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	if (!fsmhip::batch_read_limit(&in, s)) return nullptr;   /* as the matches: line extents are clamped to the limit */
-	return replaced_new(mt, rp, in, s);
-}
-
-extern "C" struct fsm_hip_replaced *fsm_hip_matches_replace(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b,
-	const struct fsm_hip_repl *rp)
-{
-	fsmhip::LineBatch host;
-	if (!replaced_check(mt, b, rp, &host) || !fsmhip::batch_host_arrays_ok(host)) return nullptr;
-	return run_host(mt->device, host, [&](const fsmhip::LineBatch &in, hipStream_t s) { return replaced_new(mt, rp, in, s); });
-}
-
-extern "C" struct fsm_hip_replaced *fsm_hip_text_replace(const struct fsm_hip_matches *mt, const struct fsm_hip_text *t,
-	const struct fsm_hip_text_hits *h, const struct fsm_hip_repl *rp, void *hip_stream)
-{
-	if (!have_device()) { errno = ENODEV; return nullptr; }
-	if (mt == nullptr || t == nullptr || rp == nullptr || mt->m != (h != nullptr ? h->m : t->n)) { errno = EINVAL; return nullptr; }
-	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	std::optional<DevGuard> dg;
-	fsmhip::LineBatch in;
-	if (!text_batch(t, h, {mt->device, rp->device}, s, &dg, &in)) return nullptr;
-	return replaced_new(mt, rp, in, s);
-}
-
-extern "C" size_t fsm_hip_replaced_count(const struct fsm_hip_replaced *r) { return r == nullptr ? 0 : r->m; }
-extern "C" uint64_t fsm_hip_replaced_nbytes(const struct fsm_hip_replaced *r) { return r == nullptr ? 0 : r->nbytes; }
-extern "C" const uint64_t *fsm_hip_replaced_off_device(const struct fsm_hip_replaced *r) { return r == nullptr ? nullptr : r->d_off.p; }
-extern "C" const unsigned char *fsm_hip_replaced_bytes_device(const struct fsm_hip_replaced *r) { return r == nullptr ? nullptr : r->d_bytes.p; }
-
-extern "C" int fsm_hip_replaced_copy(const struct fsm_hip_replaced *r, uint64_t *off, void *bytes)
-{
-	if (r == nullptr) { errno = EINVAL; return -1; }
-	return copy_out(r->device, r->done(), {{off, r->d_off, (r->m + 1u) * sizeof(uint64_t)}, {bytes, r->d_bytes, (size_t)r->nbytes}});
-}
-
-extern "C" double fsm_hip_replaced_ms(const struct fsm_hip_replaced *r) { return run_ms(r, 0, 3); }
-extern "C" double fsm_hip_replaced_pass_ms(const struct fsm_hip_replaced *r, int pass) { return run_ms(r, pass, pass); }
-
-/* ---- extract: every kept match's bytes as a record of a fresh packed text (extract.hip) -----------------------------------------
- * lengths pass (per MATCH: kept, the record's bytes, its first byte, its input; per block of EXT_MATCHES matches the pair records /
- * bytes) -> exclusive scan of the BLOCK pairs by one workgroup -> ONE wait for the two totals -> allocation -> offsets pass (the
- * block's own scan redone, the compaction, first[]) -> write pass.  The scan runs over total / EXT_MATCHES records.  The offsets
- * and the write pass are in flight at return. */
-struct __attribute__((visibility("hidden"))) fsm_hip_rules {
-	int device = 0;
-	size_t nrules = 0;
-	unsigned flags = 0;
-	DevBuf<uint32_t> d_bits;                 /* nrules bits in words of 32, never nothing */
-};
-
-extern "C" struct fsm_hip_rules *fsm_hip_rules_create(const void *bits, size_t nrules, unsigned flags)
-{
-	int dev = 0;
-	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
-	if ((flags & ~FSM_HIP_RULES_KEEP_OTHER) != 0u || (bits == nullptr && nrules != 0)) { errno = EINVAL; return nullptr; }
-	struct fsm_hip_rules *rs = new (std::nothrow) struct fsm_hip_rules;
-	if (rs == nullptr) { errno = ENOMEM; return nullptr; }
-	rs->device = dev;
-	rs->nrules = nrules;
-	rs->flags = flags;
-	std::vector<uint32_t> words((nrules + 31u) / 32u, 0u);   /* byte i >> 3, bit i & 7 = word i >> 5, bit i & 31: hosts here are little-endian */
-	if (nrules != 0) memcpy(words.data(), bits, (nrules + 7u) / 8u);
-	if (HIP_OK(rs->d_bits.upload(words))) return rs;
-	const int e = errno;
-	delete rs;
-	errno = e;
-	return nullptr;
-}
-
-extern "C" void fsm_hip_rules_free(struct fsm_hip_rules *rs)
-{
-	if (rs == nullptr) return;
-	const int e = errno;
-	{
-		DevGuard dg(rs->device);
-		delete rs;
-	}
-	errno = e;
-}
-
-extern "C" size_t fsm_hip_extracted_block_matches(void) { return fsmhip::EXT_MATCHES; }
-extern "C" size_t fsm_hip_extracted_block_bytes(void) { return fsmhip::EXT_BLOCK; }
-
-struct __attribute__((visibility("hidden"))) fsm_hip_extracted : RunObject<4> {   /* the lengths, the scan, the offsets, the write pass */
-	size_t nrec = 0;
-	uint64_t nbytes = 0;
-	int sep = -1;                            /* the separator the records were made with */
-	DevBuf<uint64_t> d_off;                  /* nrec + 1 */
-	DevBuf<uint64_t> d_line, d_match;        /* nrec */
-	DevBuf<uint64_t> d_src;                  /* nrec: internal */
-	DevBuf<uint64_t> d_mrec, d_msrc, d_mline;   /* one per match: internal */
-	DevBuf<uint64_t> d_pairs;                /* per block of matches, + the totals: internal */
-	DevBuf<uint64_t> d_first;                /* per block of the output, + 1: internal */
-	DevBuf<unsigned char> d_bytes;           /* nbytes, in whole blocks */
-};
-
-extern "C" void fsm_hip_extracted_free(struct fsm_hip_extracted *x) { run_free(x); }
-
-namespace {
-
-__global__ void __launch_bounds__(1024)
-pairs_scan(uint64_t *pairs, uint64_t nblocks)
-{
-	sum_scan<1024, 2, SCAN_PER>(pairs, nblocks, pairs + 2u * nblocks);
-}
-
-}   // namespace
-
-/* the passes on stream s into *ex, the objects' device current; r: the batch, the matches and the set (its outputs are set here) */
-static int extracted_passes(struct fsm_hip_extracted *ex, fsmhip::ExtRun r, hipStream_t s)
-{
-	if (r.m == 0) r.nmatch = 0;
-	const uint64_t nblocks = (r.nmatch + fsmhip::EXT_MATCHES - 1u) / fsmhip::EXT_MATCHES;
-	uint64_t tot[2] = {0, 0};
-	ex->sep = r.sep;
-	if (r.nmatch != 0 && (!HIP_OK(ex->d_mrec.alloc(r.nmatch)) || !HIP_OK(ex->d_msrc.alloc(r.nmatch)) || !HIP_OK(ex->d_mline.alloc(r.nmatch)) ||
-	                      !HIP_OK(ex->d_pairs.alloc(2u * nblocks + 2u))))
-		return -1;
-	r.mrec = ex->d_mrec;
-	r.msrc = ex->d_msrc;
-	r.mline = ex->d_mline;
-	r.pairs = ex->d_pairs;
-	if (!ex->begin(0, s)) return -1;
-	if (fsmhip::ext_launch_lengths(r, s) != 0) return -1;
-	if (!ex->end(0, s) || !ex->begin(1, s)) return -1;
-	if (nblocks != 0) {
-		hipLaunchKernelGGL(pairs_scan, dim3(1), dim3(1024), 0, s, r.pairs, nblocks);
-		if (!HIP_OK(hipGetLastError())) return -1;
-	}
-	if (!ex->end(1, s)) return -1;
-	/* the ONE wait: the records size off, line and match, the bytes the text and first[] */
-	if (nblocks != 0 && (!HIP_OK(hipMemcpyAsync(tot, r.pairs + 2u * nblocks, sizeof tot, hipMemcpyDeviceToHost, s)) || !HIP_OK(hipStreamSynchronize(s))))
-		return -1;
-	ex->nrec = (size_t)tot[0];
-	ex->nbytes = tot[1];
-	r.nrec = tot[0];
-	r.total = tot[1];
-	r.ngb = (r.total + fsmhip::EXT_BLOCK - 1u) / fsmhip::EXT_BLOCK;
-	if (!HIP_OK(ex->d_off.alloc(r.nrec + 1u))) return -1;
-	if (r.nrec != 0 && (!HIP_OK(ex->d_src.alloc(r.nrec)) || !HIP_OK(ex->d_line.alloc(r.nrec)) || !HIP_OK(ex->d_match.alloc(r.nrec)))) return -1;
-	if (r.total != 0 && (!HIP_OK(ex->d_bytes.alloc(r.ngb * fsmhip::EXT_BLOCK)) || !HIP_OK(ex->d_first.alloc(r.ngb + 1u)))) return -1;
-	r.out_off = ex->d_off;
-	r.src = ex->d_src;
-	r.line = ex->d_line;
-	r.match = ex->d_match;
-	r.out = ex->d_bytes;
-	r.first = ex->d_first;
-	const Grid g = grid_of(r.ngb, ex->device);
-	r.wgs = g.wgs;
-	r.per = g.per;
-	if (!ex->begin(2, s)) return -1;
-	if (r.nrec == 0) {                               /* no record: off[0] alone, and nothing is launched */
-		if (!HIP_OK(hipMemsetAsync(ex->d_off.p, 0, sizeof(uint64_t), s))) return -1;
-	} else if (fsmhip::ext_launch_offsets(r, s) != 0) {
-		return -1;
-	}
-	if (!ex->end(2, s) || !ex->begin(3, s)) return -1;
-	if (fsmhip::ext_launch_write(r, s) != 0) return -1;
-	return ex->end(3, s) ? 0 : -1;
-}
-
-static struct fsm_hip_extracted *extracted_new(const struct fsm_hip_matches *mt, const struct fsm_hip_rules *keep, int sep, const fsmhip::LineBatch &in,
-	hipStream_t s)
-{
-	fsmhip::ExtRun r;
-	r.base = in.base;
-	r.off = in.off;
-	r.pick = in.pick;
-	r.n = in.n;
-	r.m = in.m;
-	r.limit = in.limit;
-	r.moff = mt->d_off;
-	r.start = mt->d_start;
-	r.end = mt->d_end;
-	r.id = mt->d_id;
-	r.nmatch = mt->total;
-	if (keep != nullptr) {
-		r.keep = keep->d_bits;
-		r.nrules = keep->nrules;
-		r.keep_other = (keep->flags & FSM_HIP_RULES_KEEP_OTHER) != 0u;
-	}
-	r.sep = sep;
-	return run_new<struct fsm_hip_extracted>(mt->device, in.m, fsmhip::ext_grid_fits(mt->total), s, [&](struct fsm_hip_extracted *ex) {
-		return HIP_OK(hipStreamWaitEvent(s, mt->done(), 0)) ? extracted_passes(ex, r, s) : -1;   /* behind the matches' emit pass */
-	});
-}
-
-/* what all three forms refuse alike about the matches, the set and the separator */
-static bool extracted_args(const struct fsm_hip_matches *mt, const struct fsm_hip_rules *keep, int sep)
-{
-	if (!have_device()) { errno = ENODEV; return false; }
-	if (mt == nullptr || (keep != nullptr && keep->device != mt->device) || sep < -1 || sep > 255) { errno = EINVAL; return false; }
-	return true;
-}
-
-/* ... and the two batch forms about the batch; *in: the batch as given, which is the matches' own: it passes what theirs passed */
-static bool extracted_check(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b, const struct fsm_hip_rules *keep, int sep,
-	fsmhip::LineBatch *in)
-{
-	if (!extracted_args(mt, keep, sep)) return false;
-	if (!fsmhip::batch_shape(b, FSM_HIP_MATCHES_DROP_EMPTY, in)) return false;
-	if (in->m != (uint64_t)mt->m) { errno = EINVAL; return false; }
-	return true;
-}
-
-extern "C" struct fsm_hip_extracted *fsm_hip_matches_extract_device(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b,
-	const struct fsm_hip_rules *keep, int sep_byte, void *hip_stream)
-{
-	fsmhip::LineBatch in;
-	if (!extracted_check(mt, b, keep, sep_byte, &in) || !fsmhip::batch_device_ok(in)) return nullptr;
-	DevGuard dg(mt->device);
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
-	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	if (!fsmhip::batch_read_limit(&in, s)) return nullptr;   /* as the matches: line extents are clamped to the limit */
-	return extracted_new(mt, keep, sep_byte, in, s);
-}
-
-extern "C" struct fsm_hip_extracted *fsm_hip_matches_extract(const struct fsm_hip_matches *mt, const struct fsm_hip_match_batch *b,
-	const struct fsm_hip_rules *keep, int sep_byte)
-{
-	fsmhip::LineBatch host;
-	if (!extracted_check(mt, b, keep, sep_byte, &host) || !fsmhip::batch_host_arrays_ok(host)) return nullptr;
-	return run_host(mt->device, host, [&](const fsmhip::LineBatch &in, hipStream_t s) { return extracted_new(mt, keep, sep_byte, in, s); });
-}
-
-extern "C" struct fsm_hip_extracted *fsm_hip_text_extract(const struct fsm_hip_matches *mt, const struct fsm_hip_text *t,
-	const struct fsm_hip_text_hits *h, const struct fsm_hip_rules *keep, int sep_byte, void *hip_stream)
-{
-	if (!extracted_args(mt, keep, sep_byte)) return nullptr;
-	if (t == nullptr || mt->m != (h != nullptr ? h->m : t->n)) { errno = EINVAL; return nullptr; }
-	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	std::optional<DevGuard> dg;
-	fsmhip::LineBatch in;
-	if (!text_batch(t, h, {mt->device}, s, &dg, &in)) return nullptr;
-	return extracted_new(mt, keep, sep_byte, in, s);
-}
-
-extern "C" size_t fsm_hip_extracted_count(const struct fsm_hip_extracted *x) { return x == nullptr ? 0 : x->nrec; }
-extern "C" uint64_t fsm_hip_extracted_nbytes(const struct fsm_hip_extracted *x) { return x == nullptr ? 0 : x->nbytes; }
-extern "C" const uint64_t *fsm_hip_extracted_off_device(const struct fsm_hip_extracted *x) { return x == nullptr ? nullptr : x->d_off.p; }
-extern "C" const unsigned char *fsm_hip_extracted_bytes_device(const struct fsm_hip_extracted *x) { return x == nullptr ? nullptr : x->d_bytes.p; }
-extern "C" const uint64_t *fsm_hip_extracted_line_device(const struct fsm_hip_extracted *x) { return x == nullptr ? nullptr : x->d_line.p; }
-extern "C" const uint64_t *fsm_hip_extracted_match_device(const struct fsm_hip_extracted *x) { return x == nullptr ? nullptr : x->d_match.p; }
-
-extern "C" int fsm_hip_extracted_copy(const struct fsm_hip_extracted *x, uint64_t *off, void *bytes, uint64_t *line, uint64_t *match)
-{
-	if (x == nullptr) { errno = EINVAL; return -1; }
-	return copy_out(x->device, x->done(), {{off, x->d_off, (x->nrec + 1u) * sizeof(uint64_t)}, {bytes, x->d_bytes, (size_t)x->nbytes},
-	                                       {line, x->d_line, x->nrec * sizeof(uint64_t)}, {match, x->d_match, x->nrec * sizeof(uint64_t)}});
-}
-
-extern "C" double fsm_hip_extracted_ms(const struct fsm_hip_extracted *x) { return run_ms(x, 0, 3); }
-extern "C" double fsm_hip_extracted_pass_ms(const struct fsm_hip_extracted *x, int pass) { return run_ms(x, pass, pass); }
-
-/* ---- tally: counts of entries and of inputs per group and per rule (tally.hip, tally_spans) --------------------------------------
- * Nothing is owned and nothing waits in the device forms: the tables are the caller's, cleared on the stream unless
- * FSM_HIP_TALLY_ADD is given, then ONE launch.  The host forms stage group_off and the tables on a stream of their own and wait. */
-extern "C" size_t fsm_hip_tally_span_inputs(void) { return fsmhip::TALLY_SPAN; }
-extern "C" size_t fsm_hip_tally_window(void) { return fsmhip::TALLY_WINDOW; }
-extern "C" size_t fsm_hip_tally_lds_columns(void) { return fsmhip::TALLY_LDS_COLS; }
-extern "C" size_t fsm_hip_tally_max_line_columns(void) { return fsmhip::TALLY_LINE_COLS; }
-
-/* what every form refuses about the shape alike, behind ENODEV and the form's own EINVALs; *cells = G * C */
-static bool tally_shape(const void *group_off, size_t *ngroups, size_t nrules, unsigned flags, const void *count, const void *lines, size_t *cells)
-{
-	if ((count == nullptr && lines == nullptr) || (flags & ~FSM_HIP_TALLY_ADD) != 0u || (group_off != nullptr && *ngroups == 0)) { errno = EINVAL; return false; }
-	if (group_off == nullptr) *ngroups = 1;
-	if (nrules == SIZE_MAX || *ngroups > SIZE_MAX / sizeof(uint64_t) / (nrules + 1u)) { errno = EOVERFLOW; return false; }
-	if (lines != nullptr && nrules + 1u > fsmhip::TALLY_LINE_COLS) { errno = ENOTSUP; return false; }
-	*cells = *ngroups * (nrules + 1u);
-	return true;
-}
-
-/* the reduction on stream s, `device` current, behind tally_shape: the tables cleared unless they are added to, then the launch */
-static int tally_run(int device, const uint64_t *d_off, const uint32_t *d_id, size_t m, size_t total, const uint64_t *d_group_off, size_t ngroups,
-	size_t nrules, unsigned flags, uint64_t *d_count, uint64_t *d_lines, size_t cells, hipStream_t s)
-{
-	if ((flags & FSM_HIP_TALLY_ADD) == 0u)
-		for (uint64_t *tab : {d_count, d_lines})
-			if (tab != nullptr && !HIP_OK(hipMemsetAsync(tab, 0, cells * sizeof(uint64_t), s))) return -1;
-	fsmhip::TallyRun r;
-	r.off = d_off;
-	r.id = d_id;
-	r.m = m;
-	r.total = total;
-	r.group_off = d_group_off;
-	r.ngroups = ngroups;
-	r.nrules = nrules;
-	r.count = d_count;
-	r.lines = d_lines;
-	return fsmhip::tally_launch(r, device, s);
-}
-
-extern "C" int fsm_hip_tally_ids_device(const uint64_t *d_off, const uint32_t *d_id, size_t m, size_t total, const uint64_t *d_group_off,
-	size_t ngroups, size_t nrules, unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream)
-{
-	int dev = 0;
-	size_t cells = 0;
-	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return -1; }
-	if ((d_off == nullptr && m != 0) || (d_id == nullptr && m != 0 && total != 0)) { errno = EINVAL; return -1; }
-	if (!tally_shape(d_group_off, &ngroups, nrules, flags, d_count, d_lines, &cells)) return -1;
-	return tally_run(dev, d_off, d_id, m, total, d_group_off, ngroups, nrules, flags, d_count, d_lines, cells, static_cast<hipStream_t>(hip_stream));
-}
-
-/* the device form of an object's own arrays (a matches or a tokens object: both have device, m, total, d_off, d_id, done()) */
-template <typename T>
-static int tally_object_device(const T *o, const uint64_t *d_group_off, size_t ngroups, size_t nrules, unsigned flags, uint64_t *d_count,
-	uint64_t *d_lines, void *hip_stream)
-{
-	size_t cells = 0;
-	if (!have_device()) { errno = ENODEV; return -1; }
-	if (o == nullptr) { errno = EINVAL; return -1; }
-	if (!tally_shape(d_group_off, &ngroups, nrules, flags, d_count, d_lines, &cells)) return -1;
-	DevGuard dg(o->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	if (!HIP_OK(hipStreamWaitEvent(s, o->done(), 0))) return -1;      /* behind the object's emit pass */
-	return tally_run(o->device, o->d_off, o->d_id, o->m, o->total, d_group_off, ngroups, nrules, flags, d_count, d_lines, cells, s);
-}
-
-/* the host form: group_off checked and staged, the tables made on the device (uploaded when they are added to), the device form
- * on a stream of its own, the tables read back, ONE wait */
-template <typename T>
-static int tally_object_host(const T *o, const uint64_t *group_off, size_t ngroups, size_t nrules, unsigned flags, uint64_t *count, uint64_t *lines)
-{
-	size_t cells = 0;
-	if (!have_device()) { errno = ENODEV; return -1; }
-	if (o == nullptr) { errno = EINVAL; return -1; }
-	if (!tally_shape(group_off, &ngroups, nrules, flags, count, lines, &cells)) return -1;
-	if (group_off != nullptr) {
-		for (size_t g = 0; g < ngroups; g++)
-			if (group_off[g] > group_off[g + 1u]) { errno = EINVAL; return -1; }
-		if (group_off[ngroups] > o->m) { errno = EINVAL; return -1; }
-	}
-	DevGuard dg(o->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	DevStream own;
-	if (!HIP_OK(own.create(hipStreamNonBlocking))) return -1;
-	DevBuf<uint64_t> d_goff, d_tab[2];
-	uint64_t *host[2] = {count, lines};
-	int rc = 0;
-	if (group_off != nullptr && (!HIP_OK(d_goff.alloc(ngroups + 1u)) ||
-	                             !HIP_OK(hipMemcpyAsync(d_goff.p, group_off, (ngroups + 1u) * sizeof(uint64_t), hipMemcpyHostToDevice, own))))
-		rc = -1;
-	for (int i = 0; i < 2 && rc == 0; i++) {
-		if (host[i] == nullptr) continue;
-		if (!HIP_OK(d_tab[i].alloc(cells))) rc = -1;
-		else if ((flags & FSM_HIP_TALLY_ADD) != 0u && !HIP_OK(hipMemcpyAsync(d_tab[i].p, host[i], cells * sizeof(uint64_t), hipMemcpyHostToDevice, own))) rc = -1;
-	}
-	if (rc == 0 && !HIP_OK(hipStreamWaitEvent(own, o->done(), 0))) rc = -1;
-	if (rc == 0) rc = tally_run(o->device, o->d_off, o->d_id, o->m, o->total, d_goff.p, ngroups, nrules, flags, d_tab[0].p, d_tab[1].p, cells, own);
-	for (int i = 0; i < 2 && rc == 0; i++)
-		if (host[i] != nullptr && !HIP_OK(hipMemcpyAsync(host[i], d_tab[i].p, cells * sizeof(uint64_t), hipMemcpyDeviceToHost, own))) rc = -1;
-	const int e = errno;
-	const bool idle = HIP_OK(hipStreamSynchronize(own));                /* also when a step failed: the staged arrays go at return */
-	if (rc != 0) { errno = e; return -1; }
-	return idle ? 0 : -1;
-}
-
-/* the text form: the groups are the text's files -- file_lines, or the hits' file_first -- and a plain text is one group */
-template <typename T>
-static int tally_object_text(const T *o, const struct fsm_hip_text *t, const struct fsm_hip_text_hits *h, size_t nrules, unsigned flags,
-	uint64_t *d_count, uint64_t *d_lines, void *hip_stream)
-{
-	size_t cells = 0;
-	if (!have_device()) { errno = ENODEV; return -1; }
-	if (o == nullptr || t == nullptr || o->m != (h != nullptr ? h->m : t->n) || o->device != t->device || (h != nullptr && h->device != t->device)) {
-		errno = EINVAL;
-		return -1;
-	}
-	const uint64_t *d_goff = t->nfiles == 0 ? nullptr : h != nullptr ? h->d_file_first.p : t->d_file_lines.p;
-	size_t ngroups = t->nfiles;
-	if (t->nfiles != 0 && d_goff == nullptr) { errno = EINVAL; return -1; }   /* hits of another, plain text */
-	if (!tally_shape(d_goff, &ngroups, nrules, flags, d_count, d_lines, &cells)) return -1;
-	DevGuard dg(t->device);
-	if (!dg.ok()) { errno = ENODEV; return -1; }
-	hipStream_t s = static_cast<hipStream_t>(hip_stream);
-	if (!HIP_OK(hipStreamWaitEvent(s, h != nullptr ? h->ev[5] : t->ev[3], 0)) || !HIP_OK(hipStreamWaitEvent(s, o->done(), 0))) return -1;
-	return tally_run(o->device, o->d_off, o->d_id, o->m, o->total, d_goff, ngroups, nrules, flags, d_count, d_lines, cells, s);
-}
-
-extern "C" int fsm_hip_matches_tally_device(const struct fsm_hip_matches *mt, const uint64_t *d_group_off, size_t ngroups, size_t nrules,
-	unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream)
-{
-	return tally_object_device(mt, d_group_off, ngroups, nrules, flags, d_count, d_lines, hip_stream);
-}
-
-extern "C" int fsm_hip_tokens_tally_device(const struct fsm_hip_tokens *tk, const uint64_t *d_group_off, size_t ngroups, size_t nrules,
-	unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream)
-{
-	return tally_object_device(tk, d_group_off, ngroups, nrules, flags, d_count, d_lines, hip_stream);
-}
-
-extern "C" int fsm_hip_matches_tally(const struct fsm_hip_matches *mt, const uint64_t *group_off, size_t ngroups, size_t nrules, unsigned flags,
-	uint64_t *count, uint64_t *lines)
-{
-	return tally_object_host(mt, group_off, ngroups, nrules, flags, count, lines);
-}
-
-extern "C" int fsm_hip_tokens_tally(const struct fsm_hip_tokens *tk, const uint64_t *group_off, size_t ngroups, size_t nrules, unsigned flags,
-	uint64_t *count, uint64_t *lines)
-{
-	return tally_object_host(tk, group_off, ngroups, nrules, flags, count, lines);
-}
-
-extern "C" int fsm_hip_text_matches_tally(const struct fsm_hip_matches *mt, const struct fsm_hip_text *t, const struct fsm_hip_text_hits *hits,
-	size_t nrules, unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream)
-{
-	return tally_object_text(mt, t, hits, nrules, flags, d_count, d_lines, hip_stream);
-}
-
-extern "C" int fsm_hip_text_tokens_tally(const struct fsm_hip_tokens *tk, const struct fsm_hip_text *t, const struct fsm_hip_text_hits *hits,
-	size_t nrules, unsigned flags, uint64_t *d_count, uint64_t *d_lines, void *hip_stream)
-{
-	return tally_object_text(tk, t, hits, nrules, flags, d_count, d_lines, hip_stream);
-}
-
-/* ---- distinct: the distinct records of a packed text with their counts (distinct.hip) ---------------------------------------------
- * hash -> insert -> mark -> the scan of the block pairs by one workgroup -> ONE wait for D, the key bytes and the read limit -> the
- * allocation -> number -> write, which is the extraction's write pass over doff / src.  Five event pairs: mark + scan and number
- * are reported together, so the wait and the allocation lie in neither. */
-extern "C" size_t fsm_hip_distinct_long_bytes(void) { return fsmhip::DST_LONG_BYTES; }
-
-extern "C" size_t fsm_hip_distinct_table_slots(size_t R)
-{
-	if ((uint64_t)R > fsmhip::DST_MAX_RECORDS) { errno = EOVERFLOW; return 0; }
-	return (size_t)fsmhip::dst_table_slots(R);
-}
-
-struct __attribute__((visibility("hidden"))) fsm_hip_distinct : RunObject<5> {   /* hash, insert, mark + scan, number, write */
-	size_t D = 0;                            /* (m is R) */
-	uint64_t nbytes = 0;
-	DevBuf<uint64_t> d_len, d_hash;          /* R each: internal */
-	DevBuf<uint32_t> d_class;                /* R */
-	DevBuf<uint64_t> d_table, d_cnt;         /* one per slot: internal */
-	DevBuf<uint64_t> d_pairs;                /* per block of records, + DST_PAIRS_EXTRA: internal */
-	DevBuf<uint64_t> d_first, d_count;       /* D */
-	DevBuf<uint64_t> d_doff;                 /* D + 1; NULL under NO_TEXT */
-	DevBuf<uint64_t> d_src;                  /* D: internal */
-	DevBuf<uint64_t> d_bfirst;               /* per block of the output, + 1: internal */
-	DevBuf<unsigned char> d_dbytes;          /* nbytes, in whole blocks */
-	DevBuf<uint64_t> own_off;                /* the host form's staged input */
-	DevBuf<unsigned char> own_bytes;
-	DevBuf<uint32_t> own_tag;
-};
-
-extern "C" void fsm_hip_distinct_free(struct fsm_hip_distinct *dx) { run_free(dx); }
-
-/* the passes on stream s into *dx, its device current; r: the packed text, the bytes and the flag (the rest is set here) */
-static int distinct_passes(struct fsm_hip_distinct *dx, fsmhip::DstRun r, bool text, hipStream_t s)
-{
-	if (r.R == 0) {                                  /* no record: doff[0] alone, and nothing is launched */
-		if (text && (!HIP_OK(dx->d_doff.alloc(1)) || !HIP_OK(hipMemsetAsync(dx->d_doff.p, 0, sizeof(uint64_t), s)))) return -1;
-		for (DevEvent &ev : dx->ev)
-			if (!HIP_OK(hipEventRecord(ev, s))) return -1;
-		return 0;
-	}
-	const uint64_t nblocks = fsmhip::dst_blocks(r.R);
-	uint64_t tot[3] = {0, 0, 0};                     /* the firsts, the key bytes, the bytes that may be read */
-	r.slots = fsmhip::dst_table_slots(r.R);
-	if (!HIP_OK(dx->d_len.alloc(r.R)) || !HIP_OK(dx->d_hash.alloc(r.R)) || !HIP_OK(dx->d_class.alloc(r.R)) || !HIP_OK(dx->d_table.alloc(r.slots)) ||
-	    !HIP_OK(dx->d_cnt.alloc(r.slots)) || !HIP_OK(dx->d_pairs.alloc(2u * nblocks + fsmhip::DST_PAIRS_EXTRA)))
-		return -1;
-	r.len = dx->d_len;
-	r.hash = dx->d_hash;
-	r.cls = dx->d_class;
-	r.table = dx->d_table;
-	r.cnt = dx->d_cnt;
-	r.pairs = dx->d_pairs;
-	if (!dx->begin(0, s)) return -1;
-	if (!HIP_OK(hipMemsetAsync(r.pairs + 2u * nblocks, 0, fsmhip::DST_PAIRS_EXTRA * sizeof(uint64_t), s))) return -1;   /* the long records' count */
-	if (fsmhip::dst_launch_hash(r, s) != 0) return -1;
-	if (!dx->end(0, s) || !dx->begin(1, s)) return -1;
-	if (!HIP_OK(hipMemsetAsync(r.table, 0xff, r.slots * sizeof(uint64_t), s)) || !HIP_OK(hipMemsetAsync(r.cnt, 0, r.slots * sizeof(uint64_t), s))) return -1;
-	if (fsmhip::dst_launch_insert(r, s) != 0) return -1;
-	if (!dx->end(1, s) || !dx->begin(2, s)) return -1;
-	if (fsmhip::dst_launch_mark(r, s) != 0) return -1;
-	hipLaunchKernelGGL(pairs_scan, dim3(1), dim3(1024), 0, s, r.pairs, nblocks);
-	if (!HIP_OK(hipGetLastError())) return -1;
-	if (!dx->end(2, s)) return -1;
-	/* the ONE wait: D sizes first and count, the bytes the text of the keys */
-	if (!HIP_OK(hipMemcpyAsync(tot, r.pairs + 2u * nblocks, sizeof tot, hipMemcpyDeviceToHost, s)) || !HIP_OK(hipStreamSynchronize(s))) return -1;
-	dx->D = (size_t)tot[0];
-	dx->nbytes = text ? tot[1] : 0u;
-	r.D = tot[0];
-	r.total = dx->nbytes;
-	r.ngb = (r.total + fsmhip::EXT_BLOCK - 1u) / fsmhip::EXT_BLOCK;
-	if (r.D != 0 && (!HIP_OK(dx->d_first.alloc(r.D)) || !HIP_OK(dx->d_count.alloc(r.D)))) return -1;
-	if (text && (!HIP_OK(dx->d_doff.alloc(r.D + 1u)) || (r.D != 0 && !HIP_OK(dx->d_src.alloc(r.D))))) return -1;
-	if (r.total != 0 && (!HIP_OK(dx->d_dbytes.alloc(r.ngb * fsmhip::EXT_BLOCK)) || !HIP_OK(dx->d_bfirst.alloc(r.ngb + 1u)))) return -1;
-	r.first = dx->d_first;
-	r.count = dx->d_count;
-	r.doff = dx->d_doff;
-	r.src = dx->d_src;
-	r.bfirst = dx->d_bfirst;
-	if (!dx->begin(3, s)) return -1;
-	if (r.D == 0) {                                  /* (not with R >= 1; the arrays changed under the passes) */
-		if (text && !HIP_OK(hipMemsetAsync(dx->d_doff.p, 0, sizeof(uint64_t), s))) return -1;
-	} else if (fsmhip::dst_launch_number(r, s) != 0) {
-		return -1;
-	}
-	if (!dx->end(3, s) || !dx->begin(4, s)) return -1;
-	if (r.D != 0 && r.total != 0) {                  /* the extraction's write pass: record d is the key of first[d] */
-		fsmhip::ExtRun w;
-		w.base = r.bytes;
-		w.limit = tot[2];
-		w.sep = r.sep;
-		w.out_off = r.doff;
-		w.src = r.src;
-		w.first = r.bfirst;
-		w.out = dx->d_dbytes;
-		w.nrec = r.D;
-		w.total = r.total;
-		w.ngb = r.ngb;
-		const Grid g = grid_of(r.ngb, dx->device);
-		w.wgs = g.wgs;
-		w.per = g.per;
-		if (fsmhip::ext_launch_write(w, s) != 0) return -1;
-	}
-	return dx->end(4, s) ? 0 : -1;
-}
-
-/* what every form refuses alike, behind ENODEV and the form's own NULLs */
-static bool distinct_args(size_t R, int trim_byte, int sep_byte, unsigned flags)
-{
-	if (trim_byte < -1 || trim_byte > 255 || sep_byte < -1 || sep_byte > 255 || (flags & ~(FSM_HIP_DISTINCT_NO_TEXT | FSM_HIP_DISTINCT_WEAK_HASH)) != 0u) {
-		errno = EINVAL;
-		return false;
-	}
-	if ((uint64_t)R > fsmhip::DST_MAX_RECORDS) { errno = EOVERFLOW; return false; }
-	return true;
-}
-
-/* the object over device arrays on stream s, `device` current, behind `after` (or nothing) */
-static struct fsm_hip_distinct *distinct_new(int device, const uint64_t *d_off, const void *d_bytes, size_t R, uint64_t nbytes, int trim_byte,
-	const uint32_t *d_tag, int sep_byte, unsigned flags, hipEvent_t after, hipStream_t s)
-{
-	fsmhip::DstRun r;
-	r.off = d_off;
-	r.bytes = static_cast<const unsigned char *>(d_bytes);
-	r.tag = d_tag;
-	r.R = R;
-	r.nbytes = nbytes;
-	r.trim = trim_byte;
-	r.sep = sep_byte;
-	r.weak = (flags & FSM_HIP_DISTINCT_WEAK_HASH) != 0u;
-	return run_new<struct fsm_hip_distinct>(device, R, true, s, [&](struct fsm_hip_distinct *dx) {
-		if (after != nullptr && !HIP_OK(hipStreamWaitEvent(s, after, 0))) return -1;
-		return distinct_passes(dx, r, (flags & FSM_HIP_DISTINCT_NO_TEXT) == 0u, s);
-	});
-}
-
-extern "C" struct fsm_hip_distinct *fsm_hip_distinct_device(const uint64_t *d_off, const void *d_bytes, size_t R, uint64_t nbytes, int trim_byte,
-	const uint32_t *d_tag, int sep_byte, unsigned flags, void *hip_stream)
-{
-	int dev = 0;
-	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
-	if (d_off == nullptr || (d_bytes == nullptr && nbytes != 0)) { errno = EINVAL; return nullptr; }
-	if (!distinct_args(R, trim_byte, sep_byte, flags)) return nullptr;
-	return distinct_new(dev, d_off, d_bytes, R, nbytes, trim_byte, d_tag, sep_byte, flags, nullptr, static_cast<hipStream_t>(hip_stream));
-}
-
-extern "C" struct fsm_hip_distinct *fsm_hip_distinct(const uint64_t *off, const void *bytes, size_t R, int trim_byte, const uint32_t *tag, int sep_byte,
-	unsigned flags)
-{
-	int dev = 0;
-	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
-	if (off == nullptr) { errno = EINVAL; return nullptr; }
-	if (!distinct_args(R, trim_byte, sep_byte, flags)) return nullptr;
-	for (size_t r = 0; r < R; r++)
-		if (off[r] > off[r + 1u]) { errno = EINVAL; return nullptr; }
-	const uint64_t nbytes = R != 0 ? off[R] : 0u;
-	if (bytes == nullptr && nbytes != 0) { errno = EINVAL; return nullptr; }
-	DevStream own;
-	if (!HIP_OK(own.create(hipStreamNonBlocking))) return nullptr;
-	const hipStream_t s = own;
-	fsmhip::DstRun r;
-	r.R = R;
-	r.nbytes = nbytes;
-	r.trim = trim_byte;
-	r.sep = sep_byte;
-	r.weak = (flags & FSM_HIP_DISTINCT_WEAK_HASH) != 0u;
-	struct fsm_hip_distinct *dx = run_new<struct fsm_hip_distinct>(dev, R, true, s, [&](struct fsm_hip_distinct *o) {
-		if (!HIP_OK(o->own_off.alloc(R + 1u)) || !HIP_OK(hipMemcpyAsync(o->own_off.p, off, (R + 1u) * sizeof(uint64_t), hipMemcpyHostToDevice, s))) return -1;
-		if (nbytes != 0 && (!HIP_OK(o->own_bytes.alloc(nbytes)) || !HIP_OK(hipMemcpyAsync(o->own_bytes.p, bytes, nbytes, hipMemcpyHostToDevice, s)))) return -1;
-		if (tag != nullptr && R != 0 &&
-		    (!HIP_OK(o->own_tag.alloc(R)) || !HIP_OK(hipMemcpyAsync(o->own_tag.p, tag, R * sizeof(uint32_t), hipMemcpyHostToDevice, s))))
-			return -1;
-		r.off = o->own_off;
-		r.bytes = o->own_bytes;
-		r.tag = o->own_tag;
-		return distinct_passes(o, r, (flags & FSM_HIP_DISTINCT_NO_TEXT) == 0u, s);
-	});
-	if (dx == nullptr || HIP_OK(hipStreamSynchronize(s))) return dx;   /* (null: run_new left the stream idle) the stream goes at return */
-	const int e = errno;
-	run_free(dx);
-	errno = e;
-	return nullptr;
-}
-
-extern "C" struct fsm_hip_distinct *fsm_hip_extracted_distinct(const struct fsm_hip_extracted *x, int sep_byte, unsigned flags, void *hip_stream)
-{
-	if (!have_device()) { errno = ENODEV; return nullptr; }
-	if (x == nullptr) { errno = EINVAL; return nullptr; }
-	if (!distinct_args(x->nrec, x->sep, sep_byte, flags)) return nullptr;
-	DevGuard dg(x->device);
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
-	return distinct_new(x->device, x->d_off, x->d_bytes, x->nrec, x->nbytes, x->sep, nullptr, sep_byte, flags, x->done(), static_cast<hipStream_t>(hip_stream));
-}
-
-extern "C" struct fsm_hip_distinct *fsm_hip_text_hits_distinct(const struct fsm_hip_text_hits *h, int sep_byte, unsigned flags, void *hip_stream)
-{
-	if (!have_device()) { errno = ENODEV; return nullptr; }
-	if (h == nullptr || h->d_off.p == nullptr) { errno = EINVAL; return nullptr; }   /* (no offsets: FSM_HIP_HITS_NO_BYTES) */
-	if (!distinct_args(h->m, h->delim, sep_byte, flags)) return nullptr;
-	DevGuard dg(h->device);
-	if (!dg.ok()) { errno = ENODEV; return nullptr; }
-	return distinct_new(h->device, h->d_off, h->d_bytes, h->m, h->nbytes, h->delim, nullptr, sep_byte, flags, h->ev[5], static_cast<hipStream_t>(hip_stream));
-}
-
-extern "C" size_t fsm_hip_distinct_count(const struct fsm_hip_distinct *dx) { return dx == nullptr ? 0 : dx->D; }
-extern "C" size_t fsm_hip_distinct_records(const struct fsm_hip_distinct *dx) { return dx == nullptr ? 0 : dx->m; }
-extern "C" uint64_t fsm_hip_distinct_nbytes(const struct fsm_hip_distinct *dx) { return dx == nullptr ? 0 : dx->nbytes; }
-extern "C" const uint64_t *fsm_hip_distinct_first_device(const struct fsm_hip_distinct *dx) { return dx == nullptr ? nullptr : dx->d_first.p; }
-extern "C" const uint64_t *fsm_hip_distinct_count_device(const struct fsm_hip_distinct *dx) { return dx == nullptr ? nullptr : dx->d_count.p; }
-extern "C" const uint32_t *fsm_hip_distinct_class_device(const struct fsm_hip_distinct *dx) { return dx == nullptr ? nullptr : dx->d_class.p; }
-extern "C" const uint64_t *fsm_hip_distinct_off_device(const struct fsm_hip_distinct *dx) { return dx == nullptr ? nullptr : dx->d_doff.p; }
-extern "C" const unsigned char *fsm_hip_distinct_bytes_device(const struct fsm_hip_distinct *dx) { return dx == nullptr ? nullptr : dx->d_dbytes.p; }
-
-extern "C" int fsm_hip_distinct_copy(const struct fsm_hip_distinct *dx, uint64_t *first, uint64_t *count, uint32_t *cls, uint64_t *doff, void *dbytes)
-{
-	if (dx == nullptr || (doff != nullptr && dx->d_doff.p == nullptr)) { errno = EINVAL; return -1; }
-	return copy_out(dx->device, dx->done(), {{first, dx->d_first, dx->D * sizeof(uint64_t)}, {count, dx->d_count, dx->D * sizeof(uint64_t)},
-	                                         {cls, dx->d_class, dx->m * sizeof(uint32_t)}, {doff, dx->d_doff, (dx->D + 1u) * sizeof(uint64_t)},
-	                                         {dbytes, dx->d_dbytes, (size_t)dx->nbytes}});
-}
-
-extern "C" double fsm_hip_distinct_ms(const struct fsm_hip_distinct *dx) { return run_ms(dx, 0, 4); }
-
-extern "C" double fsm_hip_distinct_pass_ms(const struct fsm_hip_distinct *dx, int pass)
-{
-	if (pass < 0 || pass > 3) { errno = EINVAL; return -1.0; }
-	return pass < 2 ? run_ms(dx, pass, pass) : pass == 2 ? run_ms(dx, 2, 3) : run_ms(dx, 4, 4);
+	if (nblocks == 0) return 0;
+	hipLaunchKernelGGL(pairs_scan, dim3(1), dim3(1024), 0, s, pairs, nblocks);
+	return HIP_OK(hipGetLastError()) ? 0 : -1;
 }

@@ -1,31 +1,27 @@
 /*
- * tok.h -- what text.hip may know about a struct fsm_hip_tok_dfa (defined in tok.hip): its device, and how one pass of the
- * tokeniser's walk is launched.  The fronts (the tokens object, its scan) are in text.hip; the batch a pass runs over is
- * line_batch.h's.  Not part of the C ABI.
+ * tok.h -- what another unit reads of tok.hip: of a struct fsm_hip_tok_dfa (defined there) its device and its image as a walk
+ * reads it, for match.hip; and the tokens object, whose offsets and ids the tally counts.  Not part of the C ABI.
  */
 #ifndef FSMHIP_CSRC_TOK_H
 #define FSMHIP_CSRC_TOK_H
 
-#include <hip/hip_runtime_api.h>
-
 #include <cstdint>
 
-#include "line_batch.h"
+#include "front.h"
 
 struct fsm_hip_tok_dfa;
 
-namespace fsmhip {
-
-constexpr uint32_t TOK_THREADS = 256;        /* inputs per workgroup, one per lane */
-
-/* one pass over m inputs; every pointer is device memory */
-struct TokRun {
-	LineBatch in;                            /* flags: FSM_HIP_TOKENS_* */
-	uint64_t *count = nullptr, *err = nullptr;           /* the count pass writes them: m each */
-	const uint64_t *tok_off = nullptr;                   /* the emit pass reads it: m + 1 */
-	uint64_t *end_out = nullptr;                         /* ... and stores at tok_off[j] + t */
-	uint32_t *id_out = nullptr;
+/* count pass -> exclusive scan of the counts by one workgroup -> ONE wait for the total -> allocation -> emit pass.  The counts
+ * are scanned in place: d_off is count[m] first, tok_off[m + 1] afterwards (the total lands in its last entry). */
+struct __attribute__((visibility("hidden"))) fsm_hip_tokens : RunObject<3> {   /* the count pass, the scan, the emit pass */
+	size_t total = 0;
+	DevBuf<uint64_t> d_off;                  /* m + 1 */
+	DevBuf<uint64_t> d_err;                  /* m */
+	DevBuf<uint64_t> d_end;                  /* total */
+	DevBuf<uint32_t> d_id;                   /* total */
 };
+
+namespace fsmhip {
 
 /* the image as walk_tok reads it (image.h, TokImage), for match.hip; every pointer is device memory and lives as long as the image */
 struct TokView {
@@ -39,8 +35,6 @@ struct TokView {
 
 __attribute__((visibility("hidden"))) int tok_dfa_device(const fsm_hip_tok_dfa *td);
 __attribute__((visibility("hidden"))) TokView tok_dfa_view(const fsm_hip_tok_dfa *td);
-/* walk_tok<emit> on stream s, td's device current; 0, or -1 + errno */
-__attribute__((visibility("hidden"))) int tok_launch(const fsm_hip_tok_dfa *td, const TokRun &r, bool emit, hipStream_t s);
 
 }
 

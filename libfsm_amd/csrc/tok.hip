@@ -27,13 +27,30 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <optional>
 #include <vector>
 
 #include "../../include/fsm_hip.h"
 #include "dfa_access.h"
-#include "hip_host.h"
+#include "front.h"
 #include "image.h"
+#include "text_objects.h"
 #include "tok.h"
+
+namespace fsmhip {
+
+constexpr uint32_t TOK_THREADS = 256;        /* inputs per workgroup, one per lane */
+
+/* one pass over m inputs; every pointer is device memory */
+struct TokRun {
+	LineBatch in;                            /* flags: FSM_HIP_TOKENS_* */
+	uint64_t *count = nullptr, *err = nullptr;           /* the count pass writes them: m each */
+	const uint64_t *tok_off = nullptr;                   /* the emit pass reads it: m + 1 */
+	uint64_t *end_out = nullptr;                         /* ... and stores at tok_off[j] + t */
+	uint32_t *id_out = nullptr;
+};
+
+}
 
 using namespace fsmhip;
 
@@ -233,12 +250,6 @@ walk_tok(const TokArgs a)
 	}
 }
 
-bool tok_have_device()
-{
-	int ndev = 0;
-	return hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
-}
-
 }   // namespace
 
 /* the type is the library's own: its destructor is no exported symbol */
@@ -268,7 +279,8 @@ TokView tok_dfa_view(const fsm_hip_tok_dfa *td)
 	return v;
 }
 
-int tok_launch(const fsm_hip_tok_dfa *td, const TokRun &r, bool emit, hipStream_t s)
+/* walk_tok<emit> on stream s, td's device current; 0, or -1 + errno */
+static int tok_launch(const fsm_hip_tok_dfa *td, const TokRun &r, bool emit, hipStream_t s)
 {
 	if (r.in.m == 0) return 0;
 	if ((r.in.m + TOK_THREADS - 1u) / TOK_THREADS > 0x7fffffffu) { errno = ENOMEM; return -1; }
@@ -306,7 +318,7 @@ int tok_launch(const fsm_hip_tok_dfa *td, const TokRun &r, bool emit, hipStream_
 
 extern "C" struct fsm_hip_tok_dfa *fsm_hip_tok_dfa_create(const struct fsm_hip_dfa *dfa, int ids_mode)
 {
-	if (!tok_have_device()) { errno = ENODEV; return nullptr; }   /* no CPU path, as everywhere in this library */
+	if (!have_device()) { errno = ENODEV; return nullptr; }   /* no CPU path, as everywhere in this library */
 	if (dfa == nullptr) { errno = EINVAL; return nullptr; }
 	TokImage im;
 	const int r = build_tok_image(*dfa_plan(dfa), ids_mode, im);
@@ -345,3 +357,93 @@ extern "C" void fsm_hip_tok_dfa_free(struct fsm_hip_tok_dfa *td)
 }
 
 extern "C" int fsm_hip_tok_dfa_in_lds(const struct fsm_hip_tok_dfa *td) { return td != nullptr && td->in_lds != 0u ? 1 : 0; }
+
+/* ---- the tokens object (tok.h): count pass -> scan -> ONE wait for the total -> allocation -> emit pass (front.h) ---------------- */
+extern "C" void fsm_hip_tokens_free(struct fsm_hip_tokens *tk) { run_free(tk); }
+
+/* the passes on stream s into *tk, the image's device current; r: the inputs (its outputs are set here) */
+static int tokens_passes(struct fsm_hip_tokens *tk, const struct fsm_hip_tok_dfa *td, fsmhip::TokRun r, hipStream_t s)
+{
+	const uint64_t m = r.in.m;
+	uint64_t total = 0;
+	if (!HIP_OK(tk->d_off.alloc(m + 1u))) return -1;
+	if (m != 0 && !HIP_OK(tk->d_err.alloc(m))) return -1;
+	r.count = tk->d_off;
+	r.err = tk->d_err;
+	if (!tk->begin(0, s)) return -1;
+	if (m != 0 && fsmhip::tok_launch(td, r, false, s) != 0) return -1;
+	if (!tk->end(0, s) || !tk->begin(1, s)) return -1;
+	if (scan_total(tk->d_off, m, tk->ev[3], s, &total) != 0) return -1;   /* the total sizes the arrays */
+	tk->total = (size_t)total;
+	if (total != 0 && (!HIP_OK(tk->d_end.alloc(total)) || !HIP_OK(tk->d_id.alloc(total)))) return -1;
+	if (!tk->begin(2, s)) return -1;
+	if (total != 0) {
+		r.tok_off = tk->d_off;
+		r.end_out = tk->d_end;
+		r.id_out = tk->d_id;
+		if (fsmhip::tok_launch(td, r, true, s) != 0) return -1;
+	}
+	return tk->end(2, s) ? 0 : -1;
+}
+
+static struct fsm_hip_tokens *tokens_new(const struct fsm_hip_tok_dfa *td, const fsmhip::LineBatch &in, hipStream_t s)
+{
+	fsmhip::TokRun r;
+	r.in = in;
+	return run_new<struct fsm_hip_tokens>(fsmhip::tok_dfa_device(td), in.m, (in.m + fsmhip::TOK_THREADS - 1u) / fsmhip::TOK_THREADS <= 0x7fffffffu, s,
+	                                      [&](struct fsm_hip_tokens *tk) { return tokens_passes(tk, td, r, s); });
+}
+
+/* the arguments both forms refuse alike; *in: the batch as given */
+static bool tokens_check(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *b, fsmhip::LineBatch *in)
+{
+	if (!have_device()) { errno = ENODEV; return false; }
+	if (td == nullptr) { errno = EINVAL; return false; }
+	return fsmhip::batch_shape(b, FSM_HIP_TOKENS_NO_BACKTRACK | FSM_HIP_TOKENS_SKIP_BAD, in);
+}
+
+extern "C" struct fsm_hip_tokens *fsm_hip_tokens_run_device(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *b, void *hip_stream)
+{
+	fsmhip::LineBatch in;
+	if (!tokens_check(td, b, &in) || !fsmhip::batch_device_ok(in)) return nullptr;
+	DevGuard dg(fsmhip::tok_dfa_device(td));
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	return tokens_new(td, in, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" struct fsm_hip_tokens *fsm_hip_tokens_run(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_tok_batch *b)
+{
+	fsmhip::LineBatch host;
+	if (!tokens_check(td, b, &host) || !fsmhip::batch_host_arrays_ok(host)) return nullptr;
+	return run_host(fsmhip::tok_dfa_device(td), host, [&](const fsmhip::LineBatch &in, hipStream_t s) { return tokens_new(td, in, s); });
+}
+
+extern "C" struct fsm_hip_tokens *fsm_hip_text_tokens(const struct fsm_hip_tok_dfa *td, const struct fsm_hip_text *t, const struct fsm_hip_text_hits *h,
+	unsigned flags, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (td == nullptr || t == nullptr || (flags & ~(FSM_HIP_TOKENS_NO_BACKTRACK | FSM_HIP_TOKENS_SKIP_BAD)) != 0u) { errno = EINVAL; return nullptr; }
+	hipStream_t s = static_cast<hipStream_t>(hip_stream);
+	std::optional<DevGuard> dg;
+	fsmhip::LineBatch in;
+	if (!text_batch(t, h, {fsmhip::tok_dfa_device(td)}, s, &dg, &in)) return nullptr;
+	in.flags = flags;
+	return tokens_new(td, in, s);
+}
+
+extern "C" size_t fsm_hip_tokens_count(const struct fsm_hip_tokens *tk) { return tk == nullptr ? 0 : tk->m; }
+extern "C" size_t fsm_hip_tokens_total(const struct fsm_hip_tokens *tk) { return tk == nullptr ? 0 : tk->total; }
+extern "C" const uint64_t *fsm_hip_tokens_off_device(const struct fsm_hip_tokens *tk) { return tk == nullptr ? nullptr : tk->d_off.p; }
+extern "C" const uint64_t *fsm_hip_tokens_end_device(const struct fsm_hip_tokens *tk) { return tk == nullptr ? nullptr : tk->d_end.p; }
+extern "C" const uint32_t *fsm_hip_tokens_id_device(const struct fsm_hip_tokens *tk) { return tk == nullptr ? nullptr : tk->d_id.p; }
+extern "C" const uint64_t *fsm_hip_tokens_err_device(const struct fsm_hip_tokens *tk) { return tk == nullptr ? nullptr : tk->d_err.p; }
+
+extern "C" int fsm_hip_tokens_copy(const struct fsm_hip_tokens *tk, uint64_t *off, uint64_t *end, uint32_t *id, uint64_t *err)
+{
+	if (tk == nullptr) { errno = EINVAL; return -1; }
+	return copy_out(tk->device, tk->done(), {{off, tk->d_off, (tk->m + 1u) * sizeof(uint64_t)}, {end, tk->d_end, tk->total * sizeof(uint64_t)},
+	                                         {id, tk->d_id, tk->total * sizeof(uint32_t)}, {err, tk->d_err, tk->m * sizeof(uint64_t)}});
+}
+
+extern "C" double fsm_hip_tokens_ms(const struct fsm_hip_tokens *tk) { return run_ms(tk, 0, 2); }
+extern "C" double fsm_hip_tokens_pass_ms(const struct fsm_hip_tokens *tk, int pass) { return run_ms(tk, pass, pass); }

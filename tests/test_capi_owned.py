@@ -9,8 +9,8 @@ from libfsm_amd import capi
 from libfsm_amd.capi import _Freed, _Owned
 
 OWNERS = ["Plan", "HipDfa", "HipNode", "MultiPrepared", "LinesDfa", "HipText", "HipHits", "PosDfa", "HipSpans", "TokDfa", "HipTokens",
-          "HipMatches", "HipRepl", "HipReplaced", "HipRules", "HipExtracted"]
-FREED = OWNERS[-5:]             # close() is spelt free() as well, as before; no other class has a free()
+          "HipMatches", "HipRepl", "HipReplaced", "HipRules", "HipExtracted", "HipDistinct"]
+FREED = OWNERS[-6:]             # close() is spelt free() as well, as before; no other class has a free()
 
 
 class Stub:
@@ -35,7 +35,7 @@ def subclasses(cls):
         yield from subclasses(sub)
 
 
-def test_the_sixteen_classes_and_no_other_derive_from_the_owner():
+def test_the_seventeen_classes_and_no_other_derive_from_the_owner():
     assert sorted(c.__name__ for c in subclasses(_Owned) if c is not _Freed) == sorted(OWNERS)
     assert sorted(c.__name__ for c in subclasses(_Freed)) == sorted(FREED)
     assert [name for name in OWNERS if hasattr(getattr(capi, name), "free")] == FREED

@@ -1,5 +1,5 @@
 """GPU: the distinct records of a packed text (libfsm_amd/csrc/distinct.hip: dst_hash, dst_hash_long, dst_insert, dst_mark,
-dst_number, dst_class; the fronts, the scan of the block pairs and the write pass in text.hip).
+dst_number, dst_class and the fronts; the scan of the block pairs in text.hip, the write pass in extract.hip).
 
 first, count, class, doff and every byte of the keys are compared with tests/distinct_ref.py, the definition of include/fsm_hip.h
 ("distinct") restated as a Python dict over the trimmed keys in record order -- nothing that came from the device is ever used to

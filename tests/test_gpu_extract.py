@@ -1,4 +1,4 @@
-"""GPU: the extraction (libfsm_amd/csrc/extract.hip: ext_lengths, ext_offsets, ext_write; the fronts, the rule set and the scan
+"""GPU: the extraction (libfsm_amd/csrc/extract.hip: ext_lengths, ext_offsets, ext_write, the fronts and the rule set; the scan
 of the block pairs in text.hip).
 
 off, every byte, line and match are compared with tests/extract_ref.py, the definition of include/fsm_hip.h ("extract") restated

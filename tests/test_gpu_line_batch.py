@@ -1,5 +1,5 @@
-"""GPU: the three entry forms of the text fronts pinned to each other (libfsm_amd/csrc/line_batch.h and its users in text.hip and
-span.hip): the host form on NumPy arrays, the _device form on the same arrays uploaded (limit = the text's bytes, and limit = 0)
+"""GPU: the three entry forms of the text fronts pinned to each other (libfsm_amd/csrc/line_batch.h and its users in tok.hip, match.hip,
+replace.hip and span.hip): the host form on NumPy arrays, the _device form on the same arrays uploaded (limit = the text's bytes, and limit = 0)
 and the fsm_hip_text_* form on a text of the same bytes give equal arrays, and these are the Python references' (tokens_ref,
 matches_ref, replace_ref, span_ref).  One text of 5 lines, one of them empty, the last without a delimiter; then a pick with a
 repeat, and, for the text form, the hits of a lines DFA.  Last, what all four host forms refuse about a batch."""

@@ -1,4 +1,4 @@
-"""GPU: matches (libfsm_amd/csrc/match.hip: walk_mark, walk_match<false>, walk_match<true>; the fronts in text.hip).
+"""GPU: matches (libfsm_amd/csrc/match.hip: walk_mark, walk_match<false>, walk_match<true> and the fronts).
 
 Every answer -- count, match_off, start, end, id, total -- is compared with tests/matches_ref.py, the definition of
 include/fsm_hip.h ("matches") restated in Python over the automata's own formulas, never with the rounds on the device or with

@@ -1,4 +1,4 @@
-"""GPU: the replacement (libfsm_amd/csrc/replace.hip: repl_lengths, repl_offsets, repl_write<LDS / global table>; the fronts and
+"""GPU: the replacement (libfsm_amd/csrc/replace.hip: repl_lengths, repl_offsets, repl_write<LDS / global table> and the fronts;
 the scan of the block sums in text.hip).
 
 out_off and every output byte are compared with tests/replace_ref.py, the definition of include/fsm_hip.h ("replace") restated

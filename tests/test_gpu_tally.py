@@ -1,4 +1,4 @@
-"""GPU: the tally (libfsm_amd/csrc/tally.hip: tally_spans; the fronts in text.hip): matches and lines per rule and per group.
+"""GPU: the tally (libfsm_amd/csrc/tally.hip: tally_spans and the fronts): matches and lines per rule and per group.
 
 Every table is compared with tests/tally_ref.py -- np.bincount over col(id) per group, distinct (input, col) pairs for lines --
 never with anything that came from the device.  The first half feeds synthetic off / id / group_off arrays to

@@ -1,5 +1,5 @@
 """GPU: replacement templates -- the match itself inside its replacement (libfsm_amd/csrc/replace.hip: repl_lengths<true>,
-repl_write<LDS / global table, true>; fsm_hip_repl_create_template in text.hip).
+repl_write<LDS / global table, true>; fsm_hip_repl_create_template beside them).
 
 out_off and every output byte are compared with tests/template_ref.py, the definition of include/fsm_hip.h ("replace", the template
 table) restated in Python, over the matches of tests/matches_ref.py -- never over matches or offsets that came from the device.  The

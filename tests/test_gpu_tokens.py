@@ -1,4 +1,4 @@
-"""GPU: tokens (libfsm_amd/csrc/tok.hip: walk_tok<false>, walk_tok<true>; the fronts in text.hip).
+"""GPU: tokens (libfsm_amd/csrc/tok.hip: walk_tok<false>, walk_tok<true> and the fronts).
 
 Every answer -- count, tok_off, end, id, err, total -- is compared with tests/tokens_ref.py, the definition of include/fsm_hip.h
 ("tokens") restated in plain Python over the automaton's own formula, never with anything derived from the code under test.  The
