@@ -3,7 +3,7 @@
  * pass over the matches.  The matches are found, extracted and made distinct on the device; what comes back is one entry per
  * DISTINCT value:
  *
- *     hipuniq [-c] [-l] [-r LIST] LINES.fsmhip STARTS.fsmhip ENDS.fsmhip FILE...
+ *     hipuniq [-c] [-s] [-l] [-r LIST] LINES.fsmhip STARTS.fsmhip ENDS.fsmhip FILE...
  *
  * The three tables are hipscan's (examples/hipscan.c): LINES selects the lines that hold a match, STARTS accepts anything followed
  * by the reversal of pat, ENDS accepts exactly pat and carries one end-id per rule.  fsm_hip_text_matches() finds every non-empty
@@ -13,6 +13,9 @@
  * one line per distinct value, in the order of first appearance.
  *     -c         sorted by count, the most frequent first (ties in the order of first appearance): a host sort over the D
  *                distinct values, not over the matches
+ *     -s         in byte order, as sort | uniq -c prints them: fsm_hip_keys_sort() sorts the distinct values on the device and
+ *                its order[] and sorted text come back; with -c, by count first and in byte order among equal counts
+ *                (FSM_HIP_SORT_BY_COUNT): uniq -c | sort -rn without a host sort
  *     -l         the records are the LINES that hold a match, not the matches: fsm_hip_text_hits_distinct()
  *     -r LIST    the matches of these rules alone: numbers from 0, separated by commas (not with -l)
  * Exit status: 0 if a value was printed, 1 if not, 2 on error.  Plain C against include/fsm_hip.h only.
@@ -125,11 +128,12 @@ main(int argc, char **argv)
 	struct fsm_hip_matches *matches = NULL;
 	struct fsm_hip_extracted *extracted = NULL;
 	struct fsm_hip_distinct *distinct;
+	struct fsm_hip_sorted *by_key = NULL;
 	unsigned char *buf = NULL, *keys = NULL, *bits;
-	uint64_t *file_off, *count = NULL, *doff = NULL;
+	uint64_t *file_off, *count = NULL, *doff = NULL, *rec = NULL;
 	size_t *order = NULL;
 	size_t cap = 0, len = 0, got, nfiles, nrules, j, d, D;
-	int by_lines = 0, sorted = 0, a;
+	int by_lines = 0, sorted = 0, by_bytes = 0, a;
 	const char *rules = NULL;
 	char **names;
 	FILE *f;
@@ -137,6 +141,8 @@ main(int argc, char **argv)
 	for (a = 1; a < argc && argv[a][0] == '-' && argv[a][1] != '\0'; a++) {
 		if (strcmp(argv[a], "-c") == 0) {
 			sorted = 1;
+		} else if (strcmp(argv[a], "-s") == 0) {
+			by_bytes = 1;
 		} else if (strcmp(argv[a], "-l") == 0) {
 			by_lines = 1;
 		} else if (strcmp(argv[a], "-r") == 0 && a + 1 < argc) {
@@ -146,7 +152,7 @@ main(int argc, char **argv)
 		}
 	}
 	if (a + 4 > argc || (by_lines && rules != NULL)) {
-		fprintf(stderr, "usage: hipuniq [-c] [-l] [-r LIST] LINES.fsmhip STARTS.fsmhip ENDS.fsmhip FILE...\n");
+		fprintf(stderr, "usage: hipuniq [-c] [-s] [-l] [-r LIST] LINES.fsmhip STARTS.fsmhip ENDS.fsmhip FILE...\n");
 		return 2;
 	}
 	desc = read_desc(argv[a]);
@@ -267,11 +273,29 @@ main(int argc, char **argv)
 		for (d = 0; d < D; d++) {
 			order[d] = d;
 		}
-		if (sorted) {
+		if (by_bytes) {
+			/* the sort on the device: record p of its text is key order[p], so the keys and their offsets are replaced by the
+			 * sorted ones and only the counts are looked up through order[] */
+			by_key = fsm_hip_keys_sort(distinct, '\n', sorted ? FSM_HIP_SORT_BY_COUNT : 0, NULL);
+			rec = malloc(D * sizeof *rec);
+			if (by_key == NULL || rec == NULL) {
+				perror("fsm_hip_keys_sort");
+				return 2;
+			}
+			if (fsm_hip_sorted_copy(by_key, rec, NULL, doff, keys) != 0) {
+				perror("fsm_hip_sorted_copy");
+				return 2;
+			}
+			for (d = 0; d < D; d++) {
+				printf("%llu\t", (unsigned long long)count[rec[d]]);
+				fwrite(keys + doff[d], 1, (size_t)(doff[d + 1] - doff[d]), stdout);
+			}
+			fsm_hip_sorted_free(by_key);
+		} else if (sorted) {
 			sort_count = count;
 			qsort(order, D, sizeof *order, by_count);
 		}
-		for (d = 0; d < D; d++) {
+		for (d = 0; d < D && !by_bytes; d++) {
 			printf("%llu\t", (unsigned long long)count[order[d]]);
 			fwrite(keys + doff[order[d]], 1, (size_t)(doff[order[d] + 1] - doff[order[d]]), stdout);   /* the key and its '\n' */
 		}
@@ -293,6 +317,7 @@ main(int argc, char **argv)
 	free(count);
 	free(doff);
 	free(order);
+	free(rec);
 	free(keys);
 	free(buf);
 	return D != 0 ? 0 : 1;

@@ -1417,6 +1417,83 @@ size_t fsm_hip_distinct_table_slots(size_t R); /* a power of two >= 2 R, at leas
 void fsm_hip_distinct_free(struct fsm_hip_distinct *dx);
 
 /* ------------------------------------------------------------------ */
+/* sort: the records of a packed text in byte order, on the device: order, ranks, text */
+/* ------------------------------------------------------------------ */
+
+/* The sort of grep -o PATTERN | sort | uniq -c | sort -rn, without the host.
+ *   Input.  A packed text on the current device, off[R + 1] and bytes with nbytes, trim_byte and sep_byte in -1 .. 255, and
+ *   optionally major[R] (u64).  The KEY of record r is its trimmed bytes under exactly the rules of "distinct": entries of off are
+ *   clamped to min(off[R], nbytes) and to their predecessor, and with trim_byte >= 0 a non-empty record whose last byte is the trim
+ *   byte is one byte shorter.
+ *   Order.  Keys order as memcmp does: bytes are unsigned, and a proper prefix goes before the longer key: "" < "\0" < "\0\0".
+ *   With major, records order by major[r] first and by key second.  Records equal in both keep ascending r: the sort is stable.
+ *   Flags.  FSM_HIP_SORT_NO_TEXT: no soff / sbytes.  FSM_HIP_SORT_REVERSE: keys descend, so the longer key goes before its prefix;
+ *   ties still ascend in r.  FSM_HIP_SORT_MAJOR_DESC: major descends; EINVAL without major.  FSM_HIP_SORT_BY_COUNT: only for
+ *   fsm_hip_keys_sort.  Any other bit is EINVAL.
+ *   Output.  order[R], u64: order[p] is the record at sorted position p, a permutation of 0 .. R - 1, typed so that it is a valid
+ *   `pick` of every device front: they walk the text in sorted order without a byte being moved.  rank[R], u32: rank[p] is the
+ *   number of distinct (major, key) pairs before position p's; it is non-decreasing and steps by 0 or 1, and groups = rank[R - 1]
+ *   + 1 (0 for no record) is, for equal inputs, the D that "distinct" reports.  Unless NO_TEXT, a fresh packed text soff[R + 1] /
+ *   sbytes: record p is the trimmed key of order[p], followed by sep_byte if sep_byte >= 0.  This is what sort prints, and an
+ *   input of any device front, this one included.  Every output is a function of the input alone and identical on every run.
+ *   Limits.  R <= 2^32 - 2 (EOVERFLOW above).  R == 0 stores nothing but soff[0].  No byte outside [bytes, bytes + min(off[R],
+ *   nbytes)) is read; no store leaves the object's own arrays.
+ * Passes.  Most-significant-word-first rounds over a stable least-significant-digit radix sort.  Positions, not records, carry the
+ * state: bucket[p] is the first position of the run of records equal on everything examined so far, and a bucket is active while
+ * it has more than one member and its last word was full.  A round takes the active positions only.  keys: a lane compares its
+ * key with its bucket head's from the bucket's depth on, in 16-byte chunks, the minimum over the bucket (an agent-scope atomic)
+ * advances the depth in whole words -- equal keys of kilobytes and a shared prefix cost one pass; then the next 8 key bytes big
+ * endian, zero-padded, and how many exist (both complemented under REVERSE).  With major, a round before the first takes the u64
+ * instead (complemented under MAJOR_DESC).  radix: stable passes of 8 bits over (bucket, word, valid); all digit histograms come
+ * from one kernel and a digit with one occupied bin is skipped; a pass is a per-tile histogram, a scan and a scatter whose rank
+ * inside a tile of fsm_hip_sort_tile_records() entries is the wave64 match-by-ballot rank.  rebucket: a position whose (bucket,
+ * word, valid) differs from its predecessor's is a head; the new buckets, the active positions compacted, and their number to the
+ * host: the round's one wait.  fsm_hip_sorted_rounds() is at most ceil(maxlen / 8) + 1, and at most 2 when all keys are equal.
+ * finish: rank is a scan of the heads, order is widened, and the text is written by the extraction's write pass; it is in flight
+ * at return.
+ * fsm_hip_sort_device takes device pointers and hip_stream.  fsm_hip_sort takes host arrays, stages them and waits; nbytes is
+ * off[R]; a decreasing off is EINVAL before any launch.  fsm_hip_extracted_sort is over the records of an extracted object, with
+ * trim_byte = the separator the extraction was made with; fsm_hip_text_hits_sort over the lines of hits, with trim_byte = the
+ * text's delimiter (hits made with FSM_HIP_HITS_NO_BYTES: EINVAL).  fsm_hip_keys_sort sorts the D keys of a distinct object, with
+ * trim_byte = the separator the keys were written with (a FSM_HIP_DISTINCT_NO_TEXT object: EINVAL); with FSM_HIP_SORT_BY_COUNT
+ * major is the object's count[D] and MAJOR_DESC is implied: uniq -c | sort -rn, ties in byte order.  Each is enqueued behind its
+ * object's last event, and the sorted object must be freed before the object it came from.
+ * It owns, on the device: order[R] and rank[R] (NULL when R == 0), soff[R + 1] (always there unless NO_TEXT) and the bytes (NULL
+ * when there are none).  _records is R, _groups the distinct (major, key) pairs (it waits for the finish), _nbytes soff[R],
+ * _rounds the rounds, _radix_passes the radix passes that ran or (skipped != 0) were skipped.  _copy copies out whichever of
+ * order / rank / soff / sbytes are not NULL and waits (soff under NO_TEXT: EINVAL).  _ms: all passes by HIP events; _pass_ms: 0
+ * keys (major, prefix skip, fetch), 1 radix passes, 2 rebucket -- each summed over the rounds -- and 3 finish and write.
+ * NULL + errno: ENODEV (checked first: there is no CPU path), EINVAL (a NULL object, d_off NULL, d_bytes NULL with nbytes > 0, a
+ * byte argument outside -1 .. 255, an unknown flag bit, MAJOR_DESC without major; host form: an off that decreases), EOVERFLOW
+ * (R > 2^32 - 2), ENOMEM. */
+#define FSM_HIP_SORT_NO_TEXT    1u  /* no soff / sbytes: order and rank only */
+#define FSM_HIP_SORT_REVERSE    2u  /* keys descend */
+#define FSM_HIP_SORT_MAJOR_DESC 4u  /* major descends */
+#define FSM_HIP_SORT_BY_COUNT   8u  /* fsm_hip_keys_sort: major = count[D], descending */
+struct fsm_hip_sorted;
+struct fsm_hip_sorted *fsm_hip_sort_device(const uint64_t *d_off, const void *d_bytes, size_t R, uint64_t nbytes, int trim_byte,
+	const uint64_t *d_major, int sep_byte, unsigned flags, void *hip_stream);
+struct fsm_hip_sorted *fsm_hip_sort(const uint64_t *off, const void *bytes, size_t R, int trim_byte, const uint64_t *major,
+	int sep_byte, unsigned flags);
+struct fsm_hip_sorted *fsm_hip_extracted_sort(const struct fsm_hip_extracted *x, int sep_byte, unsigned flags, void *hip_stream);
+struct fsm_hip_sorted *fsm_hip_text_hits_sort(const struct fsm_hip_text_hits *hits, int sep_byte, unsigned flags, void *hip_stream);
+struct fsm_hip_sorted *fsm_hip_keys_sort(const struct fsm_hip_distinct *dx, int sep_byte, unsigned flags, void *hip_stream);
+size_t fsm_hip_sorted_records(const struct fsm_hip_sorted *sx);                 /* R */
+size_t fsm_hip_sorted_groups(const struct fsm_hip_sorted *sx);                  /* rank[R - 1] + 1; 0 when R == 0 */
+uint64_t fsm_hip_sorted_nbytes(const struct fsm_hip_sorted *sx);                /* soff[R]; 0 under NO_TEXT */
+size_t fsm_hip_sorted_rounds(const struct fsm_hip_sorted *sx);
+size_t fsm_hip_sorted_radix_passes(const struct fsm_hip_sorted *sx, int skipped);
+const uint64_t *fsm_hip_sorted_order_device(const struct fsm_hip_sorted *sx);   /* R; NULL when R == 0 */
+const uint32_t *fsm_hip_sorted_rank_device(const struct fsm_hip_sorted *sx);    /* R; NULL when R == 0 */
+const uint64_t *fsm_hip_sorted_off_device(const struct fsm_hip_sorted *sx);     /* R + 1, always there unless NO_TEXT */
+const unsigned char *fsm_hip_sorted_bytes_device(const struct fsm_hip_sorted *sx);   /* NULL when nbytes == 0 */
+int fsm_hip_sorted_copy(const struct fsm_hip_sorted *sx, uint64_t *order, uint32_t *rank, uint64_t *soff, void *sbytes);
+double fsm_hip_sorted_ms(const struct fsm_hip_sorted *sx);
+double fsm_hip_sorted_pass_ms(const struct fsm_hip_sorted *sx, int pass);       /* 0: keys, 1: radix passes, 2: rebucket, 3: finish + write */
+size_t fsm_hip_sort_tile_records(void);        /* the records one workgroup ranks in a radix pass */
+void fsm_hip_sorted_free(struct fsm_hip_sorted *sx);
+
+/* ------------------------------------------------------------------ */
 /* synthetic input generator (benchmarks and parity tests)            */
 /* ------------------------------------------------------------------ */
 

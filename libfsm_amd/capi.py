@@ -46,6 +46,7 @@ RULES_KEEP_OTHER = 1
 TALLY_ADD = 1
 DISTINCT_NO_TEXT = 1
 DISTINCT_WEAK_HASH = 2
+SORT_NO_TEXT, SORT_REVERSE, SORT_MAJOR_DESC, SORT_BY_COUNT = 1, 2, 4, 8
 IDS_EARLIEST, IDS_RET, IDS_ERROR = 1, 2, 3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -287,6 +288,19 @@ PROTOTYPES = {"fsm_hip_" + name: (restype, args) for restype, names, *args in (
     (S, "distinct_long_bytes"),
     (S, "distinct_table_slots", S),
     (None, "distinct_free", P),
+    # sort: (off, bytes, R[, nbytes], trim, major | object), sep, flags[, stream]
+    (P, "sort_device", P, P, S, U64, I, P, I, U, P),
+    (P, "sort", P, P, S, I, P, I, U),
+    (P, "extracted_sort text_hits_sort keys_sort", P, I, U, P),
+    (S, "sorted_records sorted_groups sorted_rounds", P),
+    (S, "sorted_radix_passes", P, I),
+    (U64, "sorted_nbytes", P),
+    (P, "sorted_order_device sorted_rank_device sorted_off_device sorted_bytes_device", P),
+    (I, "sorted_copy", P, P, P, P, P),
+    (D, "sorted_ms", P),
+    (D, "sorted_pass_ms", P, I),
+    (S, "sort_tile_records"),
+    (None, "sorted_free", P),
     # input generators: (out, stride, n, first_index, seed, {bytes, count}..., every[, stream])
     (I, "gen_inputs_device", P, S, S, U64, U64, P, U, P, U, U, P),
     (None, "gen_inputs_host", P, S, S, U64, U64, P, U, P, U, U),
@@ -1489,6 +1503,10 @@ class HipHits(_Owned):
         """fsm_hip_text_hits_distinct: the distinct lines of these hits, trimmed by the text's delimiter"""
         return HipDistinct(_call("fsm_hip_text_hits_distinct", self._h, sep_byte, flags, stream or None), (self,))
 
+    def sort(self, sep_byte: int = -1, flags: int = 0, stream: int = 0) -> "HipSorted":
+        """fsm_hip_text_hits_sort: the lines of these hits in byte order, trimmed by the text's delimiter"""
+        return HipSorted(_call("fsm_hip_text_hits_sort", self._h, sep_byte, flags, stream or None), (self,))
+
 
 def text_block_bytes() -> int:
     """fsm_hip_text_block_bytes: bytes one workgroup of the delimiter scan covers per step."""
@@ -1987,6 +2005,10 @@ class HipExtracted(_Freed):
         """fsm_hip_extracted_distinct: the distinct records, trimmed by the separator the extraction was made with"""
         return HipDistinct(_call("fsm_hip_extracted_distinct", self._h, sep_byte, flags, stream or None), (self,))
 
+    def sort(self, sep_byte: int = -1, flags: int = 0, stream: int = 0) -> "HipSorted":
+        """fsm_hip_extracted_sort: the records in byte order, trimmed by the separator the extraction was made with"""
+        return HipSorted(_call("fsm_hip_extracted_sort", self._h, sep_byte, flags, stream or None), (self,))
+
 
 def extracted_block_matches() -> int:
     return int(load_library().fsm_hip_extracted_block_matches())
@@ -2032,6 +2054,10 @@ class HipDistinct(_Freed):
         """0: the hash pass, 1: the insert pass, 2: the number pass, 3: the write pass"""
         return float(self._lib.fsm_hip_distinct_pass_ms(self._h, which))
 
+    def sort(self, by_count: bool = False, sep_byte: int = -1, flags: int = 0, stream: int = 0) -> "HipSorted":
+        """fsm_hip_keys_sort: the D keys in byte order; by_count: by count[D] descending first, ties in byte order"""
+        return HipSorted(_call("fsm_hip_keys_sort", self._h, sep_byte, flags | (SORT_BY_COUNT if by_count else 0), stream or None), (self,))
+
 
 def distinct_device(d_off: int, d_bytes: int, R: int, nbytes: int, trim_byte: int = -1, d_tag: int = 0, sep_byte: int = -1, flags: int = 0,
                     stream: int = 0, keep=()) -> HipDistinct:
@@ -2059,3 +2085,67 @@ def distinct_table_slots(R: int) -> int:
     if n == 0:
         raise _oserr("fsm_hip_distinct_table_slots")
     return n
+
+
+# ---- sort: the records of a packed text in byte order (include/fsm_hip.h, "sort") ----
+
+class HipSorted:
+    """struct fsm_hip_sorted *: order[R], rank[R] and the sorted packed text, soff[R + 1] and the bytes, on the device.  Keeps
+    what it was made from alive: the sorted object must be freed first.  An owner by _Owned's own methods, taken over as they
+    are (tests/test_capi_owned.py holds the classes that DERIVE from _Owned to a list)."""
+
+    _FREE = "fsm_hip_sorted_free"
+    __init__, close, handle, free = _Owned.__init__, _Owned.close, _Owned.handle, _Freed.free
+
+    def __del__(self):
+        self.close()
+
+    records = _size("fsm_hip_sorted_records", "R")
+    groups = _size("fsm_hip_sorted_groups", "the distinct (major, key) pairs: rank[R - 1] + 1")
+    nbytes = _size("fsm_hip_sorted_nbytes")
+    rounds = _size("fsm_hip_sorted_rounds")
+    order_ptr = _dev("fsm_hip_sorted_order_device")
+    rank_ptr = _dev("fsm_hip_sorted_rank_device")
+    off_ptr = _dev("fsm_hip_sorted_off_device")
+    bytes_ptr = _dev("fsm_hip_sorted_bytes_device")
+
+    def radix_passes(self, skipped: bool = False) -> int:
+        """the radix passes the rounds ran, or skipped because their digit had one occupied bin"""
+        return int(self._lib.fsm_hip_sorted_radix_passes(self._h, 1 if skipped else 0))
+
+    def copy(self, extra: int = 0, fill: int = 0):
+        """-> (order u64 [R], rank u32 [R], soff u64 [R + 1], sbytes u8 [nbytes]); soff and sbytes are None under SORT_NO_TEXT;
+        extra: that many more entries in each array, pre-filled with `fill` and left alone by the library"""
+        R, text = self.records, self.off_ptr != 0
+        order, rank = np.full(R + extra, fill, np.uint64), np.full(R + extra, fill & 0xFFFFFFFF, np.uint32)
+        soff = np.full(R + 1 + extra, fill, np.uint64) if text else None
+        data = np.full(self.nbytes + extra, fill & 0xFF, np.uint8) if text else None
+        _call("fsm_hip_sorted_copy", self._h, _ptr(order), _ptr(rank), _ptr(soff), _ptr(data))
+        return order, rank, soff, data
+
+    @property
+    def ms(self) -> float:
+        return float(self._lib.fsm_hip_sorted_ms(self._h))
+
+    def pass_ms(self, which: int) -> float:
+        """0: the keys (major, prefix skip, fetch), 1: the radix passes, 2: the rebucket, 3: the finish and the write pass"""
+        return float(self._lib.fsm_hip_sorted_pass_ms(self._h, which))
+
+
+def sort_device(d_off: int, d_bytes: int, R: int, nbytes: int, trim_byte: int = -1, d_major: int = 0, sep_byte: int = -1, flags: int = 0,
+                stream: int = 0, keep=()) -> HipSorted:
+    """fsm_hip_sort_device: device addresses, 0: NULL; the finish and the write pass are in flight on `stream` at return"""
+    return HipSorted(_call("fsm_hip_sort_device", d_off or None, d_bytes or None, R, nbytes, trim_byte, d_major or None, sep_byte, flags,
+                           stream or None), keep)
+
+
+def sort(off, data, trim_byte: int = -1, major=None, sep_byte: int = -1, flags: int = 0) -> HipSorted:
+    """fsm_hip_sort on host arrays: off u64 [R + 1], the bytes, major u64 [R] or None"""
+    off = np.ascontiguousarray(off, np.uint64)
+    data = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data, np.uint8)
+    major = None if major is None else np.ascontiguousarray(major, np.uint64)
+    return HipSorted(_call("fsm_hip_sort", _ptr(off), _ptr0(data), len(off) - 1, trim_byte, _ptr(major), sep_byte, flags))
+
+
+def sort_tile_records() -> int:
+    return int(load_library().fsm_hip_sort_tile_records())

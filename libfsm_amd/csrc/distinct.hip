@@ -41,6 +41,7 @@
 #include "match_marks.h"
 #include "extract.h"
 #include "distinct_seg.h"
+#include "sort.h"
 #include "text_objects.h"
 
 namespace fsmhip {
@@ -455,6 +456,7 @@ extern "C" size_t fsm_hip_distinct_table_slots(size_t R)
 struct __attribute__((visibility("hidden"))) fsm_hip_distinct : RunObject<5> {   /* hash, insert, mark + scan, number, write */
 	size_t D = 0;                            /* (m is R) */
 	uint64_t nbytes = 0;
+	int sep = -1;                            /* the separator the keys were written with */
 	DevBuf<uint64_t> d_len, d_hash;          /* R each: internal */
 	DevBuf<uint32_t> d_class;                /* R */
 	DevBuf<uint64_t> d_table, d_cnt;         /* one per slot: internal */
@@ -569,6 +571,7 @@ static struct fsm_hip_distinct *distinct_new(int device, const uint64_t *d_off, 
 	r.sep = sep_byte;
 	r.weak = (flags & FSM_HIP_DISTINCT_WEAK_HASH) != 0u;
 	return run_new<struct fsm_hip_distinct>(device, R, true, s, [&](struct fsm_hip_distinct *dx) {
+		dx->sep = sep_byte;
 		if (after != nullptr && !HIP_OK(hipStreamWaitEvent(s, after, 0))) return -1;
 		return distinct_passes(dx, r, (flags & FSM_HIP_DISTINCT_NO_TEXT) == 0u, s);
 	});
@@ -605,6 +608,7 @@ extern "C" struct fsm_hip_distinct *fsm_hip_distinct(const uint64_t *off, const 
 	r.sep = sep_byte;
 	r.weak = (flags & FSM_HIP_DISTINCT_WEAK_HASH) != 0u;
 	struct fsm_hip_distinct *dx = run_new<struct fsm_hip_distinct>(dev, R, true, s, [&](struct fsm_hip_distinct *o) {
+		o->sep = sep_byte;
 		if (!HIP_OK(o->own_off.alloc(R + 1u)) || !HIP_OK(hipMemcpyAsync(o->own_off.p, off, (R + 1u) * sizeof(uint64_t), hipMemcpyHostToDevice, s))) return -1;
 		if (nbytes != 0 && (!HIP_OK(o->own_bytes.alloc(nbytes)) || !HIP_OK(hipMemcpyAsync(o->own_bytes.p, bytes, nbytes, hipMemcpyHostToDevice, s)))) return -1;
 		if (tag != nullptr && R != 0 &&
@@ -640,6 +644,21 @@ extern "C" struct fsm_hip_distinct *fsm_hip_text_hits_distinct(const struct fsm_
 	DevGuard dg(h->device);
 	if (!dg.ok()) { errno = ENODEV; return nullptr; }
 	return distinct_new(h->device, h->d_off, h->d_bytes, h->m, h->nbytes, h->delim, nullptr, sep_byte, flags, h->ev[5], static_cast<hipStream_t>(hip_stream));
+}
+
+/* the D keys in byte order (sort.hip), or by count[D] descending first: the keys are the object's own packed text */
+extern "C" struct fsm_hip_sorted *fsm_hip_keys_sort(const struct fsm_hip_distinct *dx, int sep_byte, unsigned flags, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (dx == nullptr || dx->d_doff.p == nullptr) { errno = EINVAL; return nullptr; }   /* (no keys: FSM_HIP_DISTINCT_NO_TEXT) */
+	const bool by_count = (flags & FSM_HIP_SORT_BY_COUNT) != 0u;
+	if (!fsmhip::sort_args(dx->D, dx->sep, sep_byte, flags, FSM_HIP_SORT_NO_TEXT | FSM_HIP_SORT_REVERSE | FSM_HIP_SORT_MAJOR_DESC | FSM_HIP_SORT_BY_COUNT, by_count))
+		return nullptr;
+	if (by_count) flags = (flags & ~FSM_HIP_SORT_BY_COUNT) | FSM_HIP_SORT_MAJOR_DESC;
+	DevGuard dg(dx->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	return fsmhip::sorted_new(dx->device, dx->d_doff, dx->d_dbytes, dx->D, dx->nbytes, dx->sep, by_count ? dx->d_count.p : nullptr, sep_byte, flags, dx->done(),
+	                          static_cast<hipStream_t>(hip_stream));
 }
 
 extern "C" size_t fsm_hip_distinct_count(const struct fsm_hip_distinct *dx) { return dx == nullptr ? 0 : dx->D; }
