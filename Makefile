@@ -33,6 +33,7 @@ examples: lib
 	$(CC) -std=c99 -Wall -Iinclude examples/hipextract.c -o examples/hipextract -Llibfsm_amd -lfsm_hip -Wl,-rpath,$(CURDIR)/libfsm_amd -Wl,-rpath-link,/opt/rocm/lib
 	$(CC) -std=c99 -Wall -Iinclude examples/hipcount.c -o examples/hipcount -Llibfsm_amd -lfsm_hip -Wl,-rpath,$(CURDIR)/libfsm_amd -Wl,-rpath-link,/opt/rocm/lib
 	$(CC) -std=c99 -Wall -Iinclude examples/hipuniq.c -o examples/hipuniq -Llibfsm_amd -lfsm_hip -Wl,-rpath,$(CURDIR)/libfsm_amd -Wl,-rpath-link,/opt/rocm/lib
+	$(CC) -std=c99 -Wall -Iinclude examples/hipfgrep.c -o examples/hipfgrep -Llibfsm_amd -lfsm_hip -Wl,-rpath,$(CURDIR)/libfsm_amd -Wl,-rpath-link,/opt/rocm/lib
 	$(CC) -std=c99 -Wall -Iinclude examples/retest_hip.c -o examples/retest_hip -L$(LIBFSM) -lfsm_ref -Llibfsm_amd -lfsm_hip \
 		-Wl,-rpath,$(CURDIR)/$(LIBFSM) -Wl,-rpath,$(CURDIR)/libfsm_amd -Wl,-rpath-link,/opt/rocm/lib
 

@@ -1494,6 +1494,74 @@ size_t fsm_hip_sort_tile_records(void);        /* the records one workgroup rank
 void fsm_hip_sorted_free(struct fsm_hip_sorted *sx);
 
 /* ------------------------------------------------------------------ */
+/* find: the records of a packed text among the keys of a distinct object, on the device: class, bitmap, pick */
+/* ------------------------------------------------------------------ */
+
+/* grep -F -x -f LIST, comm, "the values of today's log that yesterday's did not have": the records of one text looked up among the
+ * records of another, without the host and without a second automaton.
+ *   Input.  A finished distinct object `keys`, the dictionary: D keys, made from a source text with a trim byte and optionally tags.
+ *   And a second packed text on its device, the probe: off[R + 1], bytes with nbytes, its own trim_byte in -1 .. 255, optionally
+ *   tag[R].  The KEY of a probe record is its trimmed bytes and its tag under exactly the rules of "distinct": entries of off are
+ *   clamped to min(off[R], nbytes) and to their predecessor, and at most one byte is trimmed.  A NULL tag array is tag 0 for every
+ *   record, on either side.  The two trim bytes need not be equal.
+ *   Output, all a function of the two inputs alone, identical on every run, independent of the hash, the table size and the
+ *   FSM_HIP_DISTINCT_WEAK_HASH the dictionary was built with.  class[R], u32: the d of the dictionary key equal to record r, or
+ *   FSM_HIP_FOUND_NONE (D <= 2^32 - 2: no key's number); an id array for fsm_hip_tally_ids_device, where with nrules = D the absent
+ *   records fall into the "other" column.  bitmap[ceil(R / 64)], u64: bit r & 63 of word r / 64 is set iff record r is present, the
+ *   bits at and above R in the last word are 0; over the lines of a text object it is exactly the bitmap fsm_hip_text_hits_device
+ *   takes.  pick[R], u64: the present records ascending in pick[0 .. P), the absent ones ascending in pick[P .. R); either half is a
+ *   valid `pick` of every device front.  FSM_HIP_FIND_NO_PICK: no such array and no pass for it.  present = P.
+ *   Limits.  R <= 2^32 - 2 (EOVERFLOW above).  No byte outside [bytes, bytes + min(off[R], nbytes)) of the probe is read, and none
+ *   outside the same limit of the dictionary's source.  R == 0 and D == 0 launch nothing that reads a table: no record gives no
+ *   array, no key gives every record absent.  The dictionary is const: it is bit for bit unchanged afterwards, and any number of
+ *   lookups may read it at once on different streams.  No store leaves the found object's own arrays.
+ * Passes.  hash: the distinct object's hash passes over the probe, with the dictionary's table size.  probe: a lane per record of at
+ * most fsm_hip_distinct_long_bytes() bytes walks its chain -- an empty slot: absent; a slot with its hash tag: the lengths, the
+ * tags, then the bytes of the two texts chunk by chunk, always: equal hashes decide nothing; equal: the slot's dense number -- and a
+ * wavefront per longer record walks the chain as one, its lanes taking strided chunks of both keys, a ballot ending the comparison
+ * at the first round of 64 chunks with a difference (under FSM_HIP_DISTINCT_WEAK_HASH no record is listed as long, as in the hash
+ * pass: a lane takes any length).  The table and the numbers are read by agent-scope atomic loads; nothing is written to them and
+ * there is no atomic read-modify-write.  mark: a wavefront's ballot is one bitmap word, one plain store; per block of records the
+ * pair (present, absent) and the scan of the block pairs by one workgroup; P stays on the device.  pick: the block's own scan
+ * redone.  Nothing waits: every array is sized by R, and everything may be in flight at return.
+ * fsm_hip_keys_find_device takes device pointers on the dictionary's device, which must be current, and hip_stream; it works
+ * behind the dictionary's last event.  fsm_hip_keys_find takes host arrays, stages them into the object, runs on a stream of its
+ * own and waits; nbytes is off[R]; a decreasing off is EINVAL before any launch.  fsm_hip_keys_find_extracted looks up the records
+ * of an extraction (trim: its separator), fsm_hip_keys_find_hits the lines of hits (trim: the text's delimiter; hits made with
+ * FSM_HIP_HITS_NO_BYTES: EINVAL), fsm_hip_keys_find_text the n lines of a text object, its offsets and bytes as they stand (trim:
+ * its delimiter): that bitmap goes straight into fsm_hip_text_hits_device on the same stream, with FSM_HIP_HITS_INVERT for -v.
+ * Each is enqueued behind its object's last event.  The found object must be freed before the dictionary and before what it probed.
+ * It owns, on the device: class[R] and the bitmap (NULL when R == 0) and pick[R] (NULL when R == 0 or under NO_PICK).  _records is
+ * R; _present is P and waits for the object's last event.  _copy copies out whichever of class / bitmap / pick are not NULL and
+ * waits (pick under NO_PICK: EINVAL).  _ms: all passes by HIP events; _pass_ms: 0 hash, 1 probe (both kernels), 2 mark + scan, 3
+ * pick.  The getters of NULL give 0 or NULL, _copy of NULL is EINVAL, _free of NULL does nothing.
+ * NULL + errno: ENODEV (checked first: there is no CPU path), EINVAL (a NULL object, d_off NULL, d_bytes NULL with nbytes > 0, a
+ * trim byte outside -1 .. 255, an unknown flag bit, objects on different devices; host form: an off that decreases), EOVERFLOW
+ * (R > 2^32 - 2), ENOMEM. */
+#define FSM_HIP_FIND_NO_PICK 1u             /* no pick[R] and no pass for it */
+#define FSM_HIP_FOUND_NONE   0xFFFFFFFFu    /* class of a record that equals no key */
+struct fsm_hip_found;
+struct fsm_hip_found *fsm_hip_keys_find_device(const struct fsm_hip_distinct *keys, const uint64_t *d_off, const void *d_bytes, size_t R,
+	uint64_t nbytes, int trim_byte, const uint32_t *d_tag, unsigned flags, void *hip_stream);
+struct fsm_hip_found *fsm_hip_keys_find(const struct fsm_hip_distinct *keys, const uint64_t *off, const void *bytes, size_t R, int trim_byte,
+	const uint32_t *tag, unsigned flags);
+struct fsm_hip_found *fsm_hip_keys_find_extracted(const struct fsm_hip_distinct *keys, const struct fsm_hip_extracted *x, unsigned flags,
+	void *hip_stream);
+struct fsm_hip_found *fsm_hip_keys_find_hits(const struct fsm_hip_distinct *keys, const struct fsm_hip_text_hits *hits, unsigned flags,
+	void *hip_stream);
+struct fsm_hip_found *fsm_hip_keys_find_text(const struct fsm_hip_distinct *keys, const struct fsm_hip_text *text, unsigned flags,
+	void *hip_stream);
+size_t fsm_hip_found_records(const struct fsm_hip_found *fx);                   /* R */
+size_t fsm_hip_found_present(const struct fsm_hip_found *fx);                   /* P; waits for the last event */
+const uint32_t *fsm_hip_found_class_device(const struct fsm_hip_found *fx);     /* R; NULL when R == 0 */
+const uint64_t *fsm_hip_found_bitmap_device(const struct fsm_hip_found *fx);    /* ceil(R / 64); NULL when R == 0 */
+const uint64_t *fsm_hip_found_pick_device(const struct fsm_hip_found *fx);      /* R; NULL when R == 0 or under NO_PICK */
+int fsm_hip_found_copy(const struct fsm_hip_found *fx, uint32_t *cls, uint64_t *bitmap, uint64_t *pick);
+double fsm_hip_found_ms(const struct fsm_hip_found *fx);
+double fsm_hip_found_pass_ms(const struct fsm_hip_found *fx, int pass);         /* 0: hash, 1: probe, 2: mark + scan, 3: pick */
+void fsm_hip_found_free(struct fsm_hip_found *fx);
+
+/* ------------------------------------------------------------------ */
 /* synthetic input generator (benchmarks and parity tests)            */
 /* ------------------------------------------------------------------ */
 

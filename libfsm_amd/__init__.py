@@ -19,4 +19,5 @@ from .capi import (  # noqa: F401
     TALLY_ADD, tally_ids_device, tally_span_inputs, tally_window, tally_lds_columns, tally_max_line_columns,
     DISTINCT_NO_TEXT, DISTINCT_WEAK_HASH, HipDistinct, distinct_device, distinct, distinct_long_bytes, distinct_table_slots,
     SORT_NO_TEXT, SORT_REVERSE, SORT_MAJOR_DESC, SORT_BY_COUNT, HipSorted, sort_device, sort, sort_tile_records,
+    FIND_NO_PICK, FOUND_NONE, HipFound,
 )

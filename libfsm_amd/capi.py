@@ -46,6 +46,8 @@ RULES_KEEP_OTHER = 1
 TALLY_ADD = 1
 DISTINCT_NO_TEXT = 1
 DISTINCT_WEAK_HASH = 2
+FIND_NO_PICK = 1
+FOUND_NONE = 0xFFFFFFFF
 SORT_NO_TEXT, SORT_REVERSE, SORT_MAJOR_DESC, SORT_BY_COUNT = 1, 2, 4, 8
 IDS_EARLIEST, IDS_RET, IDS_ERROR = 1, 2, 3
 
@@ -301,6 +303,16 @@ PROTOTYPES = {"fsm_hip_" + name: (restype, args) for restype, names, *args in (
     (D, "sorted_pass_ms", P, I),
     (S, "sort_tile_records"),
     (None, "sorted_free", P),
+    # find: keys, (off, bytes, R[, nbytes], trim, tag | object), flags[, stream]
+    (P, "keys_find_device", P, P, P, S, U64, I, P, U, P),
+    (P, "keys_find", P, P, P, S, I, P, U),
+    (P, "keys_find_extracted keys_find_hits keys_find_text", P, P, U, P),
+    (S, "found_records found_present", P),
+    (P, "found_class_device found_bitmap_device found_pick_device", P),
+    (I, "found_copy", P, P, P, P),
+    (D, "found_ms", P),
+    (D, "found_pass_ms", P, I),
+    (None, "found_free", P),
     # input generators: (out, stride, n, first_index, seed, {bytes, count}..., every[, stream])
     (I, "gen_inputs_device", P, S, S, U64, U64, P, U, P, U, U, P),
     (None, "gen_inputs_host", P, S, S, U64, U64, P, U, P, U, U),
@@ -2058,6 +2070,32 @@ class HipDistinct(_Freed):
         """fsm_hip_keys_sort: the D keys in byte order; by_count: by count[D] descending first, ties in byte order"""
         return HipSorted(_call("fsm_hip_keys_sort", self._h, sep_byte, flags | (SORT_BY_COUNT if by_count else 0), stream or None), (self,))
 
+    # the lookup (include/fsm_hip.h, "find"): each found object keeps this dictionary and what it probed alive
+    def find_device(self, d_off: int, d_bytes: int, R: int, nbytes: int, trim_byte: int = -1, d_tag: int = 0, flags: int = 0, stream: int = 0,
+                    keep=()) -> "HipFound":
+        """fsm_hip_keys_find_device: device addresses, 0: NULL; nothing waits, everything may be in flight on `stream` at return"""
+        return HipFound(_call("fsm_hip_keys_find_device", self._h, d_off or None, d_bytes or None, R, nbytes, trim_byte, d_tag or None, flags,
+                              stream or None), (self,) + tuple(keep))
+
+    def find(self, off, data, trim_byte: int = -1, tag=None, flags: int = 0) -> "HipFound":
+        """fsm_hip_keys_find on host arrays: off u64 [R + 1], the bytes, tag u32 [R] or None"""
+        off = np.ascontiguousarray(off, np.uint64)
+        data = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data, np.uint8)
+        tag = None if tag is None else np.ascontiguousarray(tag, np.uint32)
+        return HipFound(_call("fsm_hip_keys_find", self._h, _ptr(off), _ptr0(data), len(off) - 1, trim_byte, _ptr0(tag), flags), (self,))
+
+    def find_extracted(self, x: "HipExtracted", flags: int = 0, stream: int = 0) -> "HipFound":
+        """fsm_hip_keys_find_extracted: the records of an extraction, trimmed by its separator"""
+        return HipFound(_call("fsm_hip_keys_find_extracted", self._h, x.handle, flags, stream or None), (self, x))
+
+    def find_hits(self, hits: "HipHits", flags: int = 0, stream: int = 0) -> "HipFound":
+        """fsm_hip_keys_find_hits: the lines of hits, trimmed by the text's delimiter"""
+        return HipFound(_call("fsm_hip_keys_find_hits", self._h, hits.handle, flags, stream or None), (self, hits))
+
+    def find_text(self, text: "HipText", flags: int = 0, stream: int = 0) -> "HipFound":
+        """fsm_hip_keys_find_text: the lines of a text, trimmed by its delimiter; bitmap_ptr is what its hits_device takes"""
+        return HipFound(_call("fsm_hip_keys_find_text", self._h, text.handle, flags, stream or None), (self, text))
+
 
 def distinct_device(d_off: int, d_bytes: int, R: int, nbytes: int, trim_byte: int = -1, d_tag: int = 0, sep_byte: int = -1, flags: int = 0,
                     stream: int = 0, keep=()) -> HipDistinct:
@@ -2085,6 +2123,44 @@ def distinct_table_slots(R: int) -> int:
     if n == 0:
         raise _oserr("fsm_hip_distinct_table_slots")
     return n
+
+
+# ---- find: the records of a packed text among the keys of a distinct object (include/fsm_hip.h, "find") ----
+
+class HipFound:
+    """struct fsm_hip_found *: class[R], the bitmap of ceil(R / 64) words and pick[R] on the device.  Keeps the dictionary and what
+    it probed alive: the found object must be freed first.  An owner by _Owned's own methods, taken over as they are, as HipSorted
+    is (tests/test_capi_owned.py holds the classes that DERIVE from _Owned to a list)."""
+
+    _FREE = "fsm_hip_found_free"
+    __init__, close, handle, free = _Owned.__init__, _Owned.close, _Owned.handle, _Freed.free
+
+    def __del__(self):
+        self.close()
+
+    records = _size("fsm_hip_found_records", "R")
+    present = _size("fsm_hip_found_present", "P: the records that equal a key; waits for the object's last event")
+    class_ptr = _dev("fsm_hip_found_class_device")
+    bitmap_ptr = _dev("fsm_hip_found_bitmap_device")
+    pick_ptr = _dev("fsm_hip_found_pick_device")
+
+    def copy(self, extra: int = 0, fill: int = 0):
+        """-> (class u32 [R], bitmap u64 [ceil(R / 64)], pick u64 [R]); pick is None under FIND_NO_PICK; extra: that many more
+        entries in each array, pre-filled with `fill` and left alone by the library"""
+        R = self.records
+        cls = np.full(R + extra, fill & 0xFFFFFFFF, np.uint32)
+        bitmap = np.full((R + 63) // 64 + extra, fill, np.uint64)
+        pick = np.full(R + extra, fill, np.uint64) if self.pick_ptr != 0 or R == 0 else None
+        _call("fsm_hip_found_copy", self._h, _ptr(cls), _ptr(bitmap), _ptr(pick))
+        return cls, bitmap, pick
+
+    @property
+    def ms(self) -> float:
+        return float(self._lib.fsm_hip_found_ms(self._h))
+
+    def pass_ms(self, which: int) -> float:
+        """0: the hash pass, 1: the probe pass (both kernels), 2: mark and scan, 3: the pick pass"""
+        return float(self._lib.fsm_hip_found_pass_ms(self._h, which))
 
 
 # ---- sort: the records of a packed text in byte order (include/fsm_hip.h, "sort") ----

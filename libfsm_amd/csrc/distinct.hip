@@ -25,6 +25,16 @@
  *                    src[d], the index of the output blocks it covers -- and its rank into the counter's place
  *     dst_class      class[r] = the rank its slot now holds
  * The write pass is the extraction's (extract.hip, ext_write) over doff / src.
+ * The lookup (include/fsm_hip.h, "find"; find_seg.h) reads the table a finished object keeps: dst_hash and dst_hash_long over the
+ * PROBE text with the dictionary's slots, then
+ *     fnd_probe      a lane per probe record of at most DST_LONG_BYTES: its chain walked without a claim, the keys compared between
+ *                    the two texts, the class from the slot's dense number
+ *     fnd_probe_long a wavefront per listed record: the chain walked by all lanes alike, a candidate's chunks compared 64 at a time,
+ *                    a ballot ends the comparison at the first round with a difference
+ *     fnd_mark       a wavefront's ballot of class != NONE is one word of the bitmap; per block the pair (present, absent)
+ *     (scan)         the same scan of the block pairs; P stays on the device
+ *     fnd_pick       the block's scan redone: the present records first, the absent behind them, both ascending
+ * They write nothing of the dictionary and hold no read-modify-write: any number of lookups may read one table at once.
  * Coherence: a slot is read and written inside dst_insert by agent-scope atomics alone (a returning compare-and-swap, a min, a
  * relaxed atomic load) -- the XCDs do not see each other's L2, a plain load could keep an old word for ever.  The counters are
  * only added to.  Everything else a kernel reads was written by an EARLIER kernel or is the caller's read-only input.
@@ -41,6 +51,7 @@
 #include "match_marks.h"
 #include "extract.h"
 #include "distinct_seg.h"
+#include "find_seg.h"
 #include "sort.h"
 #include "text_objects.h"
 
@@ -75,6 +86,21 @@ struct DstRun {
 	uint64_t *src = nullptr;                 /* D: where each key's bytes begin in `bytes`; with doff */
 	uint64_t *bfirst = nullptr;              /* ngb + 1: the key that covers the first byte of each output block; with doff */
 	uint64_t D = 0, total = 0, ngb = 0;      /* known after the scan */
+};
+
+/* the lookup's arguments: the probe text as a run of the hash passes, the dictionary read-only, the outputs */
+struct FndRun {
+	DstRun p;                                /* off, bytes, tag, R, nbytes, trim of the probe; weak and slots the DICTIONARY's; len, hash,
+	                                            pairs its own; cls the list of its long records */
+	const uint64_t *k_off = nullptr;         /* the dictionary's source text: R_dict + 1 */
+	const unsigned char *k_bytes = nullptr;
+	const uint32_t *k_tag = nullptr;         /* R_dict, or null */
+	const uint64_t *k_len = nullptr;         /* R_dict: the trimmed lengths */
+	const uint64_t *table = nullptr, *cnt = nullptr;   /* slots each: the slot words, the dense numbers */
+	uint64_t k_R = 0, k_limit = 0, D = 0;    /* its records, the bytes of its source that may be read, its keys */
+	uint32_t *out = nullptr;                 /* R: class */
+	uint64_t *bitmap = nullptr;              /* ceil(R / 64) */
+	uint64_t *pick = nullptr;                /* R, or null (NO_PICK) */
 };
 
 }
@@ -401,6 +427,143 @@ dst_class(const DstRun a)
 	if (r < a.R) ((g_u32w)(uintptr_t)a.cls)[r] = (uint32_t)min64(((g_u64p)(uintptr_t)a.cnt)[slot_of(a, r)], a.D - 1u);
 }
 
+/* ---- the lookup: the records of a probe text among the keys of a finished table (find_seg.h) ---- */
+
+/* the keys of len bytes at ba of one text and at bb of another are equal, byte for byte */
+__device__ __forceinline__ bool key_equal2(uint64_t ax, uint64_t ba, uint64_t alimit, uint64_t bx, uint64_t bb, uint64_t blimit, uint64_t len)
+{
+	const uint64_t nch = dst_chunks(len);
+#pragma unroll 1
+	for (uint64_t i = 0; i < nch; i++) {
+		const uint32_t n = dst_chunk_bytes(len, i);
+		uint64_t alo, ahi, blo, bhi;
+		load_chunk(ax, ba + i * DST_CHUNK, n, alimit, &alo, &ahi);
+		load_chunk(bx, bb + i * DST_CHUNK, n, blimit, &blo, &bhi);
+		if (!dst_chunk_equal(alo, ahi, blo, bhi, n)) return false;
+	}
+	return true;
+}
+
+/* the table as another kernel, perhaps on another XCD, left it: agent-scope loads, as first_of reads it */
+__device__ __forceinline__ uint64_t slot_word_of(const FndRun &f, uint64_t i)
+{
+	return __hip_atomic_load((g_u64w)(uintptr_t)f.table + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint32_t dense_of(const FndRun &f, uint64_t i)
+{
+	return (uint32_t)min64(__hip_atomic_load((g_u64w)(uintptr_t)f.cnt + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), f.D - 1u);
+}
+__device__ __forceinline__ uint32_t key_tag_of(const FndRun &f, uint64_t q) { return f.k_tag != nullptr ? ((g_u32p)(uintptr_t)f.k_tag)[q] : 0u; }
+
+/* a probe record goes to fnd_probe_long exactly when dst_hash listed it */
+__device__ __forceinline__ bool probe_is_long(const FndRun &f, uint64_t len) { return !f.p.weak && len > DST_LONG_BYTES; }
+
+/* pass 2a (grid: dst_blocks(R); D >= 1): a lane per record */
+__global__ void __launch_bounds__(DST_THREADS)
+fnd_probe(const FndRun f)
+{
+	const uint64_t r = (uint64_t)blockIdx.x * DST_RECORDS + threadIdx.x;
+	if (r >= f.p.R) return;
+	const uint64_t limit = read_limit(f.p), bx = (uint64_t)(uintptr_t)f.p.bytes, kx = (uint64_t)(uintptr_t)f.k_bytes;
+	uint64_t beg, raw;
+	record_of(f.p, r, limit, &beg, &raw);
+	const uint64_t len = min64(((g_u64p)(uintptr_t)f.p.len)[r], raw);
+	if (probe_is_long(f, len)) return;
+	const uint32_t tag = tag_of(f.p, r);
+	((g_u32w)(uintptr_t)f.out)[r] = fnd_lookup(
+		((g_u64p)(uintptr_t)f.p.hash)[r], f.p.slots, f.k_R, [&](uint64_t i) { return slot_word_of(f, i); },
+		[&](uint64_t q) {
+			if (((g_u64p)(uintptr_t)f.k_len)[q] != len || key_tag_of(f, q) != tag) return false;
+			return key_equal2(bx, beg, limit, kx, ((g_u64p)(uintptr_t)f.k_off)[q], f.k_limit, len);
+		},
+		[&](uint64_t i) { return dense_of(f, i); });
+}
+
+/* pass 2b (D >= 1, not under the weak hash): a wavefront per listed record.  What the lanes branch on -- the list, the record, the
+ * slot words, the ballots -- is the same in all of them: the wavefront walks the chain as one. */
+__global__ void __launch_bounds__(DST_THREADS)
+fnd_probe_long(const FndRun f)
+{
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint64_t nlong = min64(((g_u64p)(uintptr_t)f.p.pairs)[2u * dst_blocks(f.p.R) + 3u], f.p.R);
+	const uint64_t limit = read_limit(f.p), bx = (uint64_t)(uintptr_t)f.p.bytes, kx = (uint64_t)(uintptr_t)f.k_bytes;
+#pragma unroll 1
+	for (uint64_t w = (uint64_t)blockIdx.x * DST_WAVES + (threadIdx.x >> 6); w < nlong; w += (uint64_t)gridDim.x * DST_WAVES) {
+		const uint64_t r = min64(((g_u32p)(uintptr_t)f.p.cls)[w], f.p.R - 1u);
+		uint64_t beg, raw;
+		record_of(f.p, r, limit, &beg, &raw);
+		const uint64_t len = min64(((g_u64p)(uintptr_t)f.p.len)[r], raw), nch = dst_chunks(len);
+		const uint32_t tag = tag_of(f.p, r);
+		const uint32_t cls = fnd_lookup(
+			((g_u64p)(uintptr_t)f.p.hash)[r], f.p.slots, f.k_R, [&](uint64_t i) { return slot_word_of(f, i); },
+			[&](uint64_t q) {
+				if (((g_u64p)(uintptr_t)f.k_len)[q] != len || key_tag_of(f, q) != tag) return false;
+				const uint64_t kbeg = ((g_u64p)(uintptr_t)f.k_off)[q];
+#pragma unroll 1
+				for (uint64_t base = 0; base < nch; base += 64u) {       /* ceil(nch / 64) rounds at the most */
+					const uint64_t i = base + lane;
+					bool differs = false;
+					if (i < nch) {
+						const uint32_t n = dst_chunk_bytes(len, i);
+						uint64_t alo, ahi, blo, bhi;
+						load_chunk(bx, beg + i * DST_CHUNK, n, limit, &alo, &ahi);
+						load_chunk(kx, kbeg + i * DST_CHUNK, n, f.k_limit, &blo, &bhi);
+						differs = !dst_chunk_equal(alo, ahi, blo, bhi, n);
+					}
+					if (__ballot(differs) != 0u) return false;
+				}
+				return true;
+			},
+			[&](uint64_t i) { return dense_of(f, i); });
+		if (lane == 0u) ((g_u32w)(uintptr_t)f.out)[r] = cls;
+	}
+}
+
+__device__ __forceinline__ bool is_present(const FndRun &f, uint64_t r) { return r < f.p.R && ((g_u32p)(uintptr_t)f.out)[r] != FND_NONE; }
+
+/* pass 3 (grid: dst_blocks(R)): the bitmap word of a wavefront is 4 * block + wave; the block's pair (present, absent) */
+__global__ void __launch_bounds__(DST_THREADS)
+fnd_mark(const FndRun f)
+{
+	__shared__ uint32_t wtot[DST_WAVES];
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	const uint64_t r = (uint64_t)blockIdx.x * DST_RECORDS + threadIdx.x;
+	const uint64_t m = __ballot(is_present(f, r));
+	if (lane == 0u) {
+		if (fnd_bitmap_word(r) < fnd_bitmap_words(f.p.R)) ((g_u64w)(uintptr_t)f.bitmap)[fnd_bitmap_word(r)] = m;
+		wtot[wave] = (uint32_t)__builtin_popcountll(m);
+	}
+	__syncthreads();
+	if (threadIdx.x == 0u) {
+		uint64_t present = 0;
+#pragma unroll
+		for (uint32_t w = 0; w < DST_WAVES; w++) present += wtot[w];
+		const uint64_t records = min64(f.p.R - r, DST_RECORDS);
+		*(g_u64x2w)(uintptr_t)(f.p.pairs + 2u * blockIdx.x) = u64x2d{present, records - present};
+	}
+}
+
+/* pass 4 (grid: dst_blocks(R)): before(r) = pairs[b] (scanned) + the present records of the block below r */
+__global__ void __launch_bounds__(DST_THREADS)
+fnd_pick(const FndRun f)
+{
+	__shared__ uint32_t wtot[DST_WAVES];
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	const uint64_t r = (uint64_t)blockIdx.x * DST_RECORDS + threadIdx.x;
+	const bool present = is_present(f, r);
+	const uint64_t m = __ballot(present);
+	if (lane == 0u) wtot[wave] = (uint32_t)__builtin_popcountll(m);
+	__syncthreads();
+	uint64_t before = ((g_u64p)(uintptr_t)f.p.pairs)[2u * blockIdx.x] + (uint64_t)__builtin_popcountll(m & (((uint64_t)1 << lane) - 1u));
+#pragma unroll
+	for (uint32_t w = 0; w < DST_WAVES; w++) before += w < wave ? wtot[w] : 0u;
+	const uint64_t P = ((g_u64p)(uintptr_t)f.p.pairs)[2u * dst_blocks(f.p.R)];
+	if (r >= f.p.R || before > r) return;
+	const uint64_t at = present ? fnd_pick_present(before) : fnd_pick_absent(r, before, P);
+	if (at < f.p.R) ((g_u64w)(uintptr_t)f.pick)[at] = r;
+}
+
 int launched() { return HIP_OK(hipGetLastError()) ? 0 : -1; }
 
 }   // namespace
@@ -439,6 +602,29 @@ static int dst_launch_number(const DstRun &r, hipStream_t s)
 	return launched();
 }
 
+/* the lookup's three launches, D >= 1 for the first */
+static int fnd_launch_probe(const FndRun &f, hipStream_t s)
+{
+	const uint64_t nb = dst_blocks(f.p.R);
+	hipLaunchKernelGGL(fnd_probe, dim3((unsigned)nb), dim3(DST_THREADS), 0, s, f);
+	if (launched() != 0) return -1;
+	if (f.p.weak) return 0;                          /* no record is listed */
+	hipLaunchKernelGGL(fnd_probe_long, dim3((unsigned)(nb < DST_LONG_BLOCKS ? nb : DST_LONG_BLOCKS)), dim3(DST_THREADS), 0, s, f);
+	return launched();
+}
+
+static int fnd_launch_mark(const FndRun &f, hipStream_t s)
+{
+	hipLaunchKernelGGL(fnd_mark, dim3((unsigned)dst_blocks(f.p.R)), dim3(DST_THREADS), 0, s, f);
+	return launched();
+}
+
+static int fnd_launch_pick(const FndRun &f, hipStream_t s)
+{
+	hipLaunchKernelGGL(fnd_pick, dim3((unsigned)dst_blocks(f.p.R)), dim3(DST_THREADS), 0, s, f);
+	return launched();
+}
+
 }   // namespace fsmhip
 
 /* ---- the fronts: the distinct records as an object of five event pairs (front.h) -------------------------------------------------
@@ -469,6 +655,8 @@ struct __attribute__((visibility("hidden"))) fsm_hip_distinct : RunObject<5> {  
 	DevBuf<uint64_t> own_off;                /* the host form's staged input */
 	DevBuf<unsigned char> own_bytes;
 	DevBuf<uint32_t> own_tag;
+	fsmhip::DstRun src;                      /* what a lookup needs: the source off, bytes, tag, R, nbytes, trim, weak and slots */
+	uint64_t limit = 0;                      /* ... and the bytes of the source that may be read */
 };
 
 extern "C" void fsm_hip_distinct_free(struct fsm_hip_distinct *dx) { run_free(dx); }
@@ -476,6 +664,7 @@ extern "C" void fsm_hip_distinct_free(struct fsm_hip_distinct *dx) { run_free(dx
 /* the passes on stream s into *dx, its device current; r: the packed text, the bytes and the flag (the rest is set here) */
 static int distinct_passes(struct fsm_hip_distinct *dx, fsmhip::DstRun r, bool text, hipStream_t s)
 {
+	dx->src = r;
 	if (r.R == 0) {                                  /* no record: doff[0] alone, and nothing is launched */
 		if (text && (!HIP_OK(dx->d_doff.alloc(1)) || !HIP_OK(hipMemsetAsync(dx->d_doff.p, 0, sizeof(uint64_t), s)))) return -1;
 		for (DevEvent &ev : dx->ev)
@@ -484,7 +673,7 @@ static int distinct_passes(struct fsm_hip_distinct *dx, fsmhip::DstRun r, bool t
 	}
 	const uint64_t nblocks = fsmhip::dst_blocks(r.R);
 	uint64_t tot[3] = {0, 0, 0};                     /* the firsts, the key bytes, the bytes that may be read */
-	r.slots = fsmhip::dst_table_slots(r.R);
+	r.slots = dx->src.slots = fsmhip::dst_table_slots(r.R);
 	if (!HIP_OK(dx->d_len.alloc(r.R)) || !HIP_OK(dx->d_hash.alloc(r.R)) || !HIP_OK(dx->d_class.alloc(r.R)) || !HIP_OK(dx->d_table.alloc(r.slots)) ||
 	    !HIP_OK(dx->d_cnt.alloc(r.slots)) || !HIP_OK(dx->d_pairs.alloc(2u * nblocks + fsmhip::DST_PAIRS_EXTRA)))
 		return -1;
@@ -507,6 +696,7 @@ static int distinct_passes(struct fsm_hip_distinct *dx, fsmhip::DstRun r, bool t
 	/* the ONE wait: D sizes first and count, the bytes the text of the keys */
 	if (!HIP_OK(hipMemcpyAsync(tot, r.pairs + 2u * nblocks, sizeof tot, hipMemcpyDeviceToHost, s)) || !HIP_OK(hipStreamSynchronize(s))) return -1;
 	dx->D = (size_t)tot[0];
+	dx->limit = tot[2];
 	dx->nbytes = text ? tot[1] : 0u;
 	r.D = tot[0];
 	r.total = dx->nbytes;
@@ -686,3 +876,208 @@ extern "C" double fsm_hip_distinct_pass_ms(const struct fsm_hip_distinct *dx, in
 	return pass < 2 ? run_ms(dx, pass, pass) : pass == 2 ? run_ms(dx, 2, 3) : run_ms(dx, 4, 4);
 }
 
+
+/* ---- the lookup's fronts: the found object of four event pairs -- hash, probe, mark + scan, pick.  Every array is sized by R, so no
+ * count has to reach the host: nothing waits, and everything may be in flight at return. ---------------------------------------- */
+struct __attribute__((visibility("hidden"))) fsm_hip_found : RunObject<4> {
+	bool has_pick = false;                   /* (m is R) */
+	DevBuf<uint64_t> d_len, d_hash;          /* R each: internal */
+	DevBuf<uint32_t> d_list;                 /* R: the long records, where there is no pick to lend its memory: internal */
+	DevBuf<uint64_t> d_pairs;                /* per block of records, + DST_PAIRS_EXTRA: internal; P behind the block pairs */
+	DevBuf<uint32_t> d_class;                /* R */
+	DevBuf<uint64_t> d_bitmap;               /* ceil(R / 64) */
+	DevBuf<uint64_t> d_pick;                 /* R; NULL under NO_PICK */
+	DevBuf<uint64_t> own_off;                /* the host form's staged input */
+	DevBuf<unsigned char> own_bytes;
+	DevBuf<uint32_t> own_tag;
+};
+
+extern "C" void fsm_hip_found_free(struct fsm_hip_found *fx) { run_free(fx); }
+
+/* the passes on stream s into *fx, its device current, behind the dictionary's last event; p: the probe text and its trim */
+static int found_passes(struct fsm_hip_found *fx, const struct fsm_hip_distinct *keys, fsmhip::DstRun p, hipStream_t s)
+{
+	if (!HIP_OK(hipStreamWaitEvent(s, keys->done(), 0))) return -1;
+	if (p.R == 0) {                                  /* no record: no array, and nothing is launched */
+		for (DevEvent &ev : fx->ev)
+			if (!HIP_OK(hipEventRecord(ev, s))) return -1;
+		return 0;
+	}
+	const uint64_t nblocks = fsmhip::dst_blocks(p.R);
+	const bool table = keys->D != 0;                 /* no key: no table is read, every record is absent */
+	if (!HIP_OK(fx->d_class.alloc(p.R)) || !HIP_OK(fx->d_bitmap.alloc(fsmhip::fnd_bitmap_words(p.R))) ||
+	    !HIP_OK(fx->d_pairs.alloc(2u * nblocks + fsmhip::DST_PAIRS_EXTRA)) || (fx->has_pick && !HIP_OK(fx->d_pick.alloc(p.R))))
+		return -1;
+	if (table && (!HIP_OK(fx->d_len.alloc(p.R)) || !HIP_OK(fx->d_hash.alloc(p.R)) || (!fx->has_pick && !HIP_OK(fx->d_list.alloc(p.R))))) return -1;
+	fsmhip::FndRun f;
+	p.sep = -1;
+	p.weak = keys->src.weak;                         /* the weak hash depends on the slots: both are the dictionary's */
+	p.slots = keys->src.slots;
+	p.len = fx->d_len;
+	p.hash = fx->d_hash;
+	p.cls = fx->has_pick ? reinterpret_cast<uint32_t *>(fx->d_pick.p) : fx->d_list.p;   /* pick is written last, behind fnd_probe_long */
+	p.pairs = fx->d_pairs;
+	f.p = p;
+	f.k_off = keys->src.off;
+	f.k_bytes = keys->src.bytes;
+	f.k_tag = keys->src.tag;
+	f.k_len = keys->d_len;
+	f.table = keys->d_table;
+	f.cnt = keys->d_cnt;
+	f.k_R = keys->m;
+	f.k_limit = keys->limit;
+	f.D = keys->D;
+	f.out = fx->d_class;
+	f.bitmap = fx->d_bitmap;
+	f.pick = fx->d_pick;
+	if (!fx->begin(0, s)) return -1;
+	if (!HIP_OK(hipMemsetAsync(p.pairs + 2u * nblocks, 0, fsmhip::DST_PAIRS_EXTRA * sizeof(uint64_t), s))) return -1;   /* the long records' count */
+	if (table && fsmhip::dst_launch_hash(p, s) != 0) return -1;
+	if (!fx->end(0, s) || !fx->begin(1, s)) return -1;
+	if (table) {
+		if (fsmhip::fnd_launch_probe(f, s) != 0) return -1;
+	} else if (!HIP_OK(hipMemsetAsync(f.out, 0xff, p.R * sizeof(uint32_t), s))) {
+		return -1;
+	}
+	if (!fx->end(1, s) || !fx->begin(2, s)) return -1;
+	if (fsmhip::fnd_launch_mark(f, s) != 0) return -1;
+	if (pairs_scan_launch(p.pairs, nblocks, s) != 0) return -1;
+	if (!fx->end(2, s) || !fx->begin(3, s)) return -1;
+	if (fx->has_pick && fsmhip::fnd_launch_pick(f, s) != 0) return -1;
+	return fx->end(3, s) ? 0 : -1;
+}
+
+/* what every form refuses alike, behind ENODEV and the form's own NULLs */
+static bool found_args(size_t R, int trim_byte, unsigned flags)
+{
+	if (trim_byte < -1 || trim_byte > 255 || (flags & ~FSM_HIP_FIND_NO_PICK) != 0u) { errno = EINVAL; return false; }
+	if ((uint64_t)R > fsmhip::DST_MAX_RECORDS) { errno = EOVERFLOW; return false; }
+	return true;
+}
+
+/* the object over device arrays on stream s, the dictionary's device current, behind `after` (or nothing) and the dictionary */
+static struct fsm_hip_found *found_new(const struct fsm_hip_distinct *keys, const uint64_t *d_off, const void *d_bytes, size_t R, uint64_t nbytes, int trim_byte,
+	const uint32_t *d_tag, unsigned flags, hipEvent_t after, hipStream_t s)
+{
+	fsmhip::DstRun p;
+	p.off = d_off;
+	p.bytes = static_cast<const unsigned char *>(d_bytes);
+	p.tag = d_tag;
+	p.R = R;
+	p.nbytes = nbytes;
+	p.trim = trim_byte;
+	return run_new<struct fsm_hip_found>(keys->device, R, true, s, [&](struct fsm_hip_found *fx) {
+		fx->has_pick = (flags & FSM_HIP_FIND_NO_PICK) == 0u;
+		if (after != nullptr && !HIP_OK(hipStreamWaitEvent(s, after, 0))) return -1;
+		return found_passes(fx, keys, p, s);
+	});
+}
+
+extern "C" struct fsm_hip_found *fsm_hip_keys_find_device(const struct fsm_hip_distinct *keys, const uint64_t *d_off, const void *d_bytes, size_t R,
+	uint64_t nbytes, int trim_byte, const uint32_t *d_tag, unsigned flags, void *hip_stream)
+{
+	int dev = 0;
+	if (!have_device() || hipGetDevice(&dev) != hipSuccess) { errno = ENODEV; return nullptr; }
+	if (keys == nullptr || d_off == nullptr || (d_bytes == nullptr && nbytes != 0) || keys->device != dev) { errno = EINVAL; return nullptr; }
+	if (!found_args(R, trim_byte, flags)) return nullptr;
+	return found_new(keys, d_off, d_bytes, R, nbytes, trim_byte, d_tag, flags, nullptr, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" struct fsm_hip_found *fsm_hip_keys_find(const struct fsm_hip_distinct *keys, const uint64_t *off, const void *bytes, size_t R, int trim_byte,
+	const uint32_t *tag, unsigned flags)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (keys == nullptr || off == nullptr) { errno = EINVAL; return nullptr; }
+	if (!found_args(R, trim_byte, flags)) return nullptr;
+	for (size_t r = 0; r < R; r++)
+		if (off[r] > off[r + 1u]) { errno = EINVAL; return nullptr; }
+	const uint64_t nbytes = R != 0 ? off[R] : 0u;
+	if (bytes == nullptr && nbytes != 0) { errno = EINVAL; return nullptr; }
+	DevGuard dg(keys->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	DevStream own;
+	if (!HIP_OK(own.create(hipStreamNonBlocking))) return nullptr;
+	const hipStream_t s = own;
+	fsmhip::DstRun p;
+	p.R = R;
+	p.nbytes = nbytes;
+	p.trim = trim_byte;
+	struct fsm_hip_found *fx = run_new<struct fsm_hip_found>(keys->device, R, true, s, [&](struct fsm_hip_found *o) {
+		o->has_pick = (flags & FSM_HIP_FIND_NO_PICK) == 0u;
+		if (!HIP_OK(o->own_off.alloc(R + 1u)) || !HIP_OK(hipMemcpyAsync(o->own_off.p, off, (R + 1u) * sizeof(uint64_t), hipMemcpyHostToDevice, s))) return -1;
+		if (nbytes != 0 && (!HIP_OK(o->own_bytes.alloc(nbytes)) || !HIP_OK(hipMemcpyAsync(o->own_bytes.p, bytes, nbytes, hipMemcpyHostToDevice, s)))) return -1;
+		if (tag != nullptr && R != 0 &&
+		    (!HIP_OK(o->own_tag.alloc(R)) || !HIP_OK(hipMemcpyAsync(o->own_tag.p, tag, R * sizeof(uint32_t), hipMemcpyHostToDevice, s))))
+			return -1;
+		p.off = o->own_off;
+		p.bytes = o->own_bytes;
+		p.tag = o->own_tag;
+		return found_passes(o, keys, p, s);
+	});
+	if (fx == nullptr || HIP_OK(hipStreamSynchronize(s))) return fx;   /* (null: run_new left the stream idle) the stream goes at return */
+	const int e = errno;
+	run_free(fx);
+	errno = e;
+	return nullptr;
+}
+
+extern "C" struct fsm_hip_found *fsm_hip_keys_find_extracted(const struct fsm_hip_distinct *keys, const struct fsm_hip_extracted *x, unsigned flags,
+	void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (keys == nullptr || x == nullptr || x->device != keys->device) { errno = EINVAL; return nullptr; }
+	if (!found_args(x->nrec, x->sep, flags)) return nullptr;
+	DevGuard dg(keys->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	return found_new(keys, x->d_off, x->d_bytes, x->nrec, x->nbytes, x->sep, nullptr, flags, x->done(), static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" struct fsm_hip_found *fsm_hip_keys_find_hits(const struct fsm_hip_distinct *keys, const struct fsm_hip_text_hits *h, unsigned flags, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (keys == nullptr || h == nullptr || h->d_off.p == nullptr || h->device != keys->device) { errno = EINVAL; return nullptr; }   /* (no offsets: NO_BYTES) */
+	if (!found_args(h->m, h->delim, flags)) return nullptr;
+	DevGuard dg(keys->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	return found_new(keys, h->d_off, h->d_bytes, h->m, h->nbytes, h->delim, nullptr, flags, h->ev[5], static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" struct fsm_hip_found *fsm_hip_keys_find_text(const struct fsm_hip_distinct *keys, const struct fsm_hip_text *t, unsigned flags, void *hip_stream)
+{
+	if (!have_device()) { errno = ENODEV; return nullptr; }
+	if (keys == nullptr || t == nullptr || t->device != keys->device) { errno = EINVAL; return nullptr; }
+	if (!found_args(t->n, t->delim, flags)) return nullptr;
+	DevGuard dg(keys->device);
+	if (!dg.ok()) { errno = ENODEV; return nullptr; }
+	return found_new(keys, t->d_off, t->d_text, t->n, t->nbytes, t->delim, nullptr, flags, t->ev[3], static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" size_t fsm_hip_found_records(const struct fsm_hip_found *fx) { return fx == nullptr ? 0 : fx->m; }
+
+/* P; it waits for the object's last event */
+extern "C" size_t fsm_hip_found_present(const struct fsm_hip_found *fx)
+{
+	uint64_t present = 0;
+	if (fx == nullptr || fx->m == 0) return 0;
+	if (copy_out(fx->device, fx->done(), {{&present, fx->d_pairs.p + 2u * fsmhip::dst_blocks(fx->m), sizeof present}}) != 0) return 0;
+	return (size_t)present;
+}
+
+extern "C" const uint32_t *fsm_hip_found_class_device(const struct fsm_hip_found *fx) { return fx == nullptr ? nullptr : fx->d_class.p; }
+extern "C" const uint64_t *fsm_hip_found_bitmap_device(const struct fsm_hip_found *fx) { return fx == nullptr ? nullptr : fx->d_bitmap.p; }
+extern "C" const uint64_t *fsm_hip_found_pick_device(const struct fsm_hip_found *fx) { return fx == nullptr ? nullptr : fx->d_pick.p; }
+
+extern "C" int fsm_hip_found_copy(const struct fsm_hip_found *fx, uint32_t *cls, uint64_t *bitmap, uint64_t *pick)
+{
+	if (fx == nullptr || (pick != nullptr && !fx->has_pick && fx->m != 0)) { errno = EINVAL; return -1; }   /* (no record: no array either way) */
+	return copy_out(fx->device, fx->done(), {{cls, fx->d_class, fx->m * sizeof(uint32_t)}, {bitmap, fx->d_bitmap, (size_t)fsmhip::fnd_bitmap_words(fx->m) * sizeof(uint64_t)},
+	                                         {pick, fx->d_pick, fx->m * sizeof(uint64_t)}});
+}
+
+extern "C" double fsm_hip_found_ms(const struct fsm_hip_found *fx) { return run_ms(fx, 0, 3); }
+
+extern "C" double fsm_hip_found_pass_ms(const struct fsm_hip_found *fx, int pass)
+{
+	if (pass < 0 || pass > 3) { errno = EINVAL; return -1.0; }
+	return run_ms(fx, pass, pass);
+}
